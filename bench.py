@@ -7,7 +7,11 @@ rank's BLOCKS counter blocks, already resident in HBM.  Workload = BASELINE.json
 (128 CTR blocks on one MI355X); with N ranks every rank owns its own 128 blocks (configs[3] at N=8:
 1,024 blocks), keys are broadcast once over RCCL and there is no data-path collective: "weak" scaling.
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline (`value`,
+`ms_per_step`, setup times); nothing else runs.  --dump-outputs DIR writes the last timed step's ciphertexts (torus_sample()).
+--full adds every other measurement and check: every block of the headline and of the extra steps decrypted and compared
+with AES (exit code 1 on a wrong block), the extra N=1 steps (CTR iteration with add_scalar, configs[4] decrypt shard,
+two contexts, one-block latency), per-stage times, power, per-rank times of a multi-rank run, and these objects:
   roofline      dominant kernel (blind rotation).  It leads with the roof that BINDS at this batch size (f64 vector
                 arithmetic: algorithmic flops per launch / measured launch time vs the f64 VALU peak); the HBM view
                 (algorithmic bytes per launch / launch time vs 8 TB/s) is nested under "hbm".  "traffic" (measured
@@ -125,6 +129,26 @@ def words_sha(t) -> str:
     return hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
 
 
+DUMP_BYTES = 32 << 20                         # --dump-outputs: at most this many bytes over all ranks
+
+
+def torus_sample(words: np.ndarray, max_values: int) -> np.ndarray:
+    """LWE ciphertexts (u64 torus words, [...][kN + 1], the body last) as float64 fractions of the torus, w / 2^64 in [0, 1).
+    When there are more than max_values words: every ciphertext's body and a fixed, seeded choice of its mask words (the same
+    columns for every ciphertext, leading shape kept); beyond max_values ciphertexts, a seeded choice of ciphertexts, one word each."""
+    width = words.shape[-1]
+    w = words.reshape(-1, width)
+    rng = np.random.default_rng(0)
+    if w.shape[0] > max_values:
+        w = w[np.sort(rng.choice(w.shape[0], max_values, replace=False))][:, width - 1:]
+    else:
+        keep = min(width, max_values // w.shape[0])
+        if keep < width:
+            w = w[:, np.append(np.sort(rng.choice(width - 1, keep - 1, replace=False)), width - 1)]
+        w = w.reshape(words.shape[:-1] + (keep,))
+    return w.astype(np.float64) * 2.0 ** -64
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -142,10 +166,18 @@ def main():
                          "so this is the only RCCL code a builder can run on hardware")
     ap.add_argument("--decrypt", action="store_true", help="time Server::aes_decrypt (BASELINE configs[4] path) instead of aes_encrypt")
     ap.add_argument("--no-ctr-iteration", action="store_true",
-                    help="skip the extra (untimed-step) measurement of the reference's whole CTR iteration that the default line reports at N=1")
+                    help="skip the extra (untimed-step) measurement of the reference's whole CTR iteration that --full reports at N=1")
     ap.add_argument("--ctr-add", action="store_true",
                     help="time the reference's whole CTR iteration (main.rs:59-61): Server::add_scalar(iv, i) on the GPU, then aes_encrypt")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else (module docstring); --no-verify, --no-cpu-baseline "
+                         "and --no-ctr-iteration leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the ciphertexts of the last step as float64 torus fractions to DIR/ciphertexts.npy "
+                         "(DIR/ciphertexts_rank<r>.npy with several ranks), at most %d MiB in all (torus_sample)" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # host-side Client work (key generation, encryption of the synthetic inputs) is OpenMP code: give every rank
     # its share of the cores instead of letting N ranks oversubscribe the node
@@ -270,15 +302,17 @@ def main():
     for _ in range(args.warmup):
         step(rk, state, n_blocks)
     eng.synchronize()
-    eng.profile_enable(True)
-    eng.profile_reset()
-    # socket power / shader clock of this rank's GPU while the timed steps run (librocm_smi64 in-process; None where it refuses)
-    sys.path.insert(0, str(ROOT / "tools"))
-    try:
-        from gpu_power import Sampler
-        sampler = Sampler(device=dev_index, period=0.05)
-    except Exception:
-        sampler = None
+    sampler = None
+    if args.full:
+        eng.profile_enable(True)
+        eng.profile_reset()
+        # socket power / shader clock of this rank's GPU while the timed steps run (librocm_smi64 in-process; None where it refuses)
+        sys.path.insert(0, str(ROOT / "tools"))
+        try:
+            from gpu_power import Sampler
+            sampler = Sampler(device=dev_index, period=0.05)
+        except Exception:
+            sampler = None
     barrier()
     if sampler is not None:
         sampler.__enter__()
@@ -297,8 +331,10 @@ def main():
                      "energy_j_per_step": None if ps["energy_j"] is None else ps["energy_j"] / args.steps,
                      "note": "rank 0's GPU over the timed steps (rocm_smi socket power, shader clock, energy counter): the blind rotation runs at "
                              "the socket's power cap, so a step takes (joules per step) / (watts)"}
-    prof = eng.profile_read()
-    eng.profile_enable(False)
+    prof = None
+    if args.full:
+        prof = eng.profile_read()
+        eng.profile_enable(False)
     own_elapsed = elapsed
     rank_elapsed = None
     if world > 1 or rccl1 is not None:
@@ -307,21 +343,28 @@ def main():
         if rccl1 is not None:
             rccl1["elapsed_all_reduce_max_ok"] = float(tt.item()) == elapsed
         elapsed = float(tt.item())
-    if world > 1:
+    if world > 1 and args.full:
         # every rank's own time, gathered to all (rank 0 prints them): a straggler is visible in the line itself
         mine = torch.tensor([own_elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         gathered = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(gathered, mine)
         rank_elapsed = [float(g.item()) for g in gathered]
 
+    if args.dump_outputs:
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        name = "ciphertexts.npy" if world == 1 else "ciphertexts_rank%d.npy" % rank
+        np.save(out_dir / name, torus_sample(state.cpu().numpy().view(np.uint64), DUMP_BYTES // 8 // world))
+
     # ---- CPU baseline (rank 0, outside the timed region; the other ranks wait at the final barrier) -----------------
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(p, keys, client)
 
     # ---- verify EVERY block (the reference asserts every block, client.rs:171): decrypt == AES applied (warmup+steps) times ----
     verified, wrong = None, {}
-    if not args.no_verify:
+    verify = args.full and not args.no_verify
+    if verify:
         want = list(counters)
         for _ in range(1 if args.ctr_add else args.warmup + args.steps):
             want = [aes128_decrypt_block(KEY, w) if args.decrypt else aes128_encrypt_block(KEY, w) for w in want]
@@ -338,7 +381,7 @@ def main():
 
     # ---- the reference's whole CTR iteration (main.rs:59-61: Server::add_scalar(iv, i), then aes_encrypt), one extra step ----
     ctr_iter = None
-    if rank == 0 and world == 1 and not args.ctr_add and not args.decrypt and not args.no_ctr_iteration:
+    if rank == 0 and world == 1 and args.full and not args.ctr_add and not args.decrypt and not args.no_ctr_iteration:
         iv_ct = torch.from_numpy(client.encrypt_u128(IV).view(np.int64)).to(dev)
         st2 = iv_ct.unsqueeze(0).repeat(n_blocks, 1, 1, 1).contiguous()
         torch.cuda.synchronize()
@@ -357,7 +400,7 @@ def main():
 
     # ---- BASELINE configs[4] shard: Server::aes_decrypt on 32 blocks (256 blocks / 8 GPUs), one extra verified step ------------
     dec32 = None
-    if rank == 0 and world == 1 and not args.ctr_add and not args.decrypt and not args.no_ctr_iteration and n_blocks >= 32 and not args.no_verify:
+    if rank == 0 and world == 1 and verify and not args.ctr_add and not args.decrypt and not args.no_ctr_iteration and n_blocks >= 32:
         st4 = state[:32].clone()
         eng.aes_decrypt(rk, st4, 32)                      # warm-up (workspace growth for the 4-LUT packing)
         eng.synchronize()                                 # the engine has its own stream: finish before torch overwrites st4
@@ -397,7 +440,7 @@ def main():
     # ---- the in-process split on ONE GPU: two contexts (keys uploaded once, cloned device to device), 64 blocks each from two host
     #      threads -- any hidden serialisation or workspace contention between contexts shows against the one-context headline ----
     two_ctx = None
-    if rank == 0 and world == 1 and not args.ctr_add and not args.decrypt and not args.no_ctr_iteration and n_blocks >= 2 and not args.no_verify:
+    if rank == 0 and world == 1 and verify and not args.ctr_add and not args.decrypt and not args.no_ctr_iteration and n_blocks >= 2:
         import threading
 
         half = n_blocks // 2
@@ -440,7 +483,7 @@ def main():
 
     # ---- BASELINE configs[1]: one AES block = 16 S-Box WoPBS in one call (latency, not throughput) ------------
     one_block_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         xb = state[0].clone()
         ob = torch.empty((16, 3, 8, p.big1), dtype=torch.int64, device=dev)
         torch.cuda.synchronize()
@@ -451,7 +494,7 @@ def main():
             eng.many_sbox(xb, 16, False, ob)
         eng.synchronize()
         one_block_ms = 1000.0 * (time.perf_counter() - t0) / 3
-        if not args.no_verify:
+        if verify:
             from tfhe_aes_amd.aes_clear import SBOX, mul2, mul3
             xin = [int(v) for v in client.decrypt_bytes(xb.cpu().numpy().view(np.uint64))]                 # the 16 input bytes
             got = client.decrypt_bytes(ob.cpu().numpy().view(np.uint64))                                   # [16][3]
@@ -463,6 +506,25 @@ def main():
         total_blocks = args.blocks * world
         value = total_blocks * args.steps / elapsed
         ms_per_step = 1000.0 * elapsed / args.steps
+        line = {
+            "metric": "AES-128 CTR blocks/sec (FHE)", "value": value, "unit": "blocks/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u64+f64", "data": "synthetic",
+            "config": {
+                "workload": ("reference CTR iteration (main.rs:59-61): %d blocks per GPU, Server::add_scalar (143 bit-CBS/block, 16-step carry chain) + "
+                             "Server::aes_encrypt (1280 bit-CBS/block)" % args.blocks) if args.ctr_add else
+                            ("configs[4] path: %d blocks per GPU, Server::aes_decrypt (2432 bit-CBS/block)" % args.blocks) if args.decrypt else
+                            ("configs[2]: %d CTR blocks per GPU, Server::aes_encrypt 10 rounds (1280 bit-CBS/block), "
+                             "counters pre-incremented client-side" % args.blocks),
+                "params": p.name, "blocks_per_gpu": args.blocks, "total_blocks": total_blocks,
+                "bit_cbs_per_step_per_gpu": args.blocks * (2432 if args.decrypt else 1280),
+            },
+            "ms_per_sbox": ms_per_step / (args.blocks * (304.0 if args.decrypt else 160.0)),
+            "setup_s": {"keygen": round(keygen_s, 2), ("key_upload_h2d" if world == 1 else "key_broadcast_" + ("rccl" if args.backend == "nccl" else args.backend)): round(bcast_s, 3),
+                        "key_bytes_moved": key_bytes_moved, "key_expand_and_convert_on_gpu": round(expand_s, 3),
+                        "aes_key_expansion": None if keyexp_s is None else round(keyexp_s, 3)},
+        }
+    if rank == 0 and args.full:
         # dominant kernel = blind rotation (K2)
         br = prof["blind_rotate"]
         launches = max(1, br["launches"])
@@ -528,20 +590,7 @@ def main():
                 pass
         # the kernel THIS context launches for such a batch (fheaes_k2_context_plan: after the occupancy fallbacks), not an assumption
         k2p = eng.k2_plan(int(bits_per_launch))
-        line = {
-            "metric": "AES-128 CTR blocks/sec (FHE)", "value": value, "unit": "blocks/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u64+f64", "data": "synthetic",
-            "config": {
-                "workload": ("reference CTR iteration (main.rs:59-61): %d blocks per GPU, Server::add_scalar (143 bit-CBS/block, 16-step carry chain) + "
-                             "Server::aes_encrypt (1280 bit-CBS/block)" % args.blocks) if args.ctr_add else
-                            ("configs[4] path: %d blocks per GPU, Server::aes_decrypt (2432 bit-CBS/block)" % args.blocks) if args.decrypt else
-                            ("configs[2]: %d CTR blocks per GPU, Server::aes_encrypt 10 rounds (1280 bit-CBS/block), "
-                             "counters pre-incremented client-side" % args.blocks),
-                "params": p.name, "blocks_per_gpu": args.blocks, "total_blocks": total_blocks,
-                "bit_cbs_per_step_per_gpu": args.blocks * (2432 if args.decrypt else 1280),
-            },
-            "ms_per_sbox": ms_per_step / (args.blocks * (304.0 if args.decrypt else 160.0)),
+        line.update({
             "verified_vs_aes": verified,
             # every block of the headline and of every extra step is decrypted and compared (the reference asserts every block,
             # client.rs:171); anything wrong is listed by step -> block indices and the process exits 1 after printing this line
@@ -580,10 +629,7 @@ def main():
                         "note": "one pass over the 342.5 MB Fourier BSK per launch + per-bit I/O (5,360 B in, 16,392 B out)"},
             },
             "roofline_k3": roofline_k3,
-            "setup_s": {"keygen": round(keygen_s, 2), ("key_upload_h2d" if world == 1 else "key_broadcast_" + ("rccl" if args.backend == "nccl" else args.backend)): round(bcast_s, 3),
-                        "key_bytes_moved": key_bytes_moved, "key_expand_and_convert_on_gpu": round(expand_s, 3),
-                        "aes_key_expansion": None if keyexp_s is None else round(keyexp_s, 3)},
-        }
+        })
         if world > 1:
             line["collective"] = {
                 "backend": args.backend + (" (RCCL)" if args.backend == "nccl" else ""), "world_size_seen": dist.get_world_size(),
@@ -593,6 +639,7 @@ def main():
                 "data_path_collectives": 0,
                 "note": "keys (seeded form) and round keys are broadcast once at start-up; the timed steps exchange nothing (CTR blocks are independent)",
             }
+    if rank == 0:
         if rccl1 is not None:
             rccl1["note"] = ("torch.distributed backend nccl (= RCCL) with world_size 1 on this GPU: communicator creation, the key broadcasts "
                              "and the MAX all-reduce ran through RCCL; no second GPU, so no xGMI transfer took place")
@@ -604,7 +651,7 @@ def main():
     if world > 1 or rccl1 is not None:
         dist.barrier()
         dist.destroy_process_group()
-    if not args.no_verify and (wrong or not verified):
+    if verify and (wrong or not verified):
         # a wrong plaintext is a failed run, whatever the throughput: the line above says where, the exit code says so to a driver
         print("bench.py: verification FAILED: %s" % (json.dumps(wrong) if wrong else "another rank's blocks"), file=sys.stderr, flush=True)
         sys.exit(1)

@@ -10,6 +10,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +38,7 @@ def _run_bench(nproc, extra, params="toy"):
 
 
 def test_bench_two_ranks_gloo():
-    line = _run_bench(2, ["--blocks", "2", "--steps", "1", "--warmup", "0"])
+    line = _run_bench(2, ["--blocks", "2", "--steps", "1", "--warmup", "0", "--full"])
     assert line["n_gpus"] == 2 and line["steps"] == 1 and line["scaling"] == "weak"
     assert line["verified_vs_aes"] is True
     assert line["config"]["total_blocks"] == 4
@@ -67,7 +68,7 @@ def test_bench_two_ranks_gloo_at_param_opt():
     ranks share the card; rank 0 generates the PARAM_OPT keys, the seeded form (194,494,496 B) crosses the process group, every rank
     regenerates the masks on the GPU (fheaes_upload_keys_seeded), takes its shard of the blocks, and rank 0 verifies against AES.  The
     first real 8-GPU run must not be the first time real-size keys cross this path."""
-    line = _run_bench(2, ["--blocks", "8", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], params="opt")
+    line = _run_bench(2, ["--blocks", "8", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"], params="opt")
     assert line["n_gpus"] == 2 and line["config"]["params"] == "PARAM_OPT"
     assert line["verified_vs_aes"] is True
     assert line["config"]["total_blocks"] == 16
@@ -89,7 +90,7 @@ def test_bench_one_rank_through_rccl():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
     res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--params", "toy", "--blocks", "2", "--steps", "1", "--warmup", "0",
-                          "--rccl-one-rank", "--no-cpu-baseline", "--no-ctr-iteration"], cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=900)
+                          "--rccl-one-rank", "--full", "--no-cpu-baseline", "--no-ctr-iteration"], cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=900)
     # The only acceptable skip: RCCL could not CREATE a communicator on this box (bench.py prints RCCL_COMMUNICATOR_READY to stderr
     # once init_process_group and the probe all-reduce have succeeded).  The skip reason carries the whole stderr tail.  Any error
     # after the marker -- the seeded-key broadcasts, the elapsed-time all-reduce, destroy_process_group -- fails the test.
@@ -111,7 +112,7 @@ def test_bench_single_rank_line_has_the_extra_verified_steps():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--params", "toy", "--blocks", "32", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--params", "toy", "--blocks", "32", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
@@ -130,12 +131,12 @@ def test_bench_single_rank_line_has_the_extra_verified_steps():
 
 
 def test_bench_driver_shape_at_param_opt_verifies_every_block():
-    """the driver's command at reduced cost (PARAM_OPT, 32 blocks, 6 + 2 steps, no CPU baseline): every block of the headline and of
+    """the driver's command with --full at reduced cost (PARAM_OPT, 32 blocks, 6 + 2 steps, no CPU baseline): every block of the headline and of
     every extra step is decrypted and compared, the line says so (`all_verified`, `wrong_blocks`), and a wrong block is a non-zero exit"""
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--params", "opt", "--blocks", "32", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"],
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--params", "opt", "--blocks", "32", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline"],
                          cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
@@ -153,8 +154,8 @@ def test_bench_exit_code_follows_verification(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
     env["FHEAES_BENCH_SABOTAGE_VERIFY"] = "1"
-    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--params", "toy", "--blocks", "4", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
-                          "--no-ctr-iteration"], cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=600)
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--params", "toy", "--blocks", "4", "--steps", "1", "--warmup", "0", "--full",
+                          "--no-cpu-baseline", "--no-ctr-iteration"], cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 1, res.stdout[-2000:] + res.stderr[-4000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
     assert line["all_verified"] is False and line["verified_vs_aes"] is False and line["wrong_blocks"] == {"headline_rank0": [0]}
@@ -165,3 +166,29 @@ def test_bench_refuses_world_size_mismatch():
     res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--params", "toy", "--blocks", "1"], cwd=str(ROOT),
                          capture_output=True, text=True, timeout=300)
     assert res.returncode != 0 and "WORLD_SIZE" in (res.stderr + res.stdout)
+
+
+def test_plain_run_times_only_the_headline_and_dumps_what_full_computes(tmp_path):
+    """a plain run prints the headline of exactly --steps timed steps and nothing that --full adds; --dump-outputs writes the last step's
+    ciphertexts as float64 torus fractions, and a --full run of the same arguments (every block verified against AES) writes the same"""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
+        env.pop(k, None)
+    lines = {}
+    for mode in ("plain", "full"):
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--params", "toy", "--blocks", "2", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(tmp_path / mode)] + (["--full", "--no-cpu-baseline"] if mode == "full" else [])
+        res = subprocess.run(cmd, cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        js = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1
+        lines[mode] = json.loads(js[0])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["unit"] == "blocks/s" and plain["higher_is_better"] is True
+    assert abs(plain["value"] - 2 * 1000.0 / plain["ms_per_step"]) < 1e-6 * plain["value"]
+    for k in ("verified_vs_aes", "roofline", "roofline_k3", "stage_ms_per_step", "cpu_baseline", "ctr_iteration_with_add_scalar"):
+        assert k not in plain
+    assert full["all_verified"] is True and full["ctr_iteration_with_add_scalar"]["verified_vs_aes"] is True
+    a, b = np.load(tmp_path / "plain" / "ciphertexts.npy"), np.load(tmp_path / "full" / "ciphertexts.npy")
+    assert a.dtype == np.float64 and a.shape == (2, 16, 8, 513)          # PARAM_TOY: 2 blocks x 128 bit ciphertexts x (kN + 1) words
+    assert np.all((a >= 0) & (a <= 1)) and np.array_equal(a, b)

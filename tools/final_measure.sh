@@ -45,9 +45,9 @@ cd $R
 python3 tools/summarize_pmc_k3.py $O/pmc_k3 profiles/${ROUND}_pmc_pfpks 16384 > $O/pmc_k3_summary.txt
 cp profiles/${ROUND}_pmc_pfpks.json $O/
 cd /tmp
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err
 tail -1 $O/bench.json | cut -c1-300
-# the driver's exact command (every block of every step verified; exit code 1 on a wrong one)
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err && echo "driver-style bench: all verified" || echo "driver-style bench FAILED (see bench_driver_style.err)"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline > $O/prof.log 2>&1
+# the driver's command with --full (every block of every step verified; exit code 1 on a wrong one)
+python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_style.json 2> $O/bench_driver_style.err && echo "driver-style bench: all verified" || echo "driver-style bench FAILED (see bench_driver_style.err)"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline > $O/prof.log 2>&1
 echo done
