@@ -214,6 +214,20 @@ int fheaes_k2_context_plan(fheaes_ctx *ctx, uint64_t m, int *form, uint64_t *uni
  * (" parking=claimed" / " parking=private").  Ownership of a slot is recorded in memory and never inferred from the compute unit a
  * workgroup runs on: a queue preempted mid-kernel resumes its workgroups on other compute units (round 5's defect). */
 int fheaes_k2_set_parking(fheaes_ctx *ctx, int claimed);
+/* Test hook of the claimed parking slots (tests/test_gpu_park_slots.py).  The pool is FHEAES_K2_PARK_SLOTS owner words, 128 per XCC
+ * (0 = free, else 1 + the index of the owning workgroup).  `initial_owner` (host, FHEAES_K2_PARK_SLOTS words) non-NULL: every
+ * claimed-mode paired launch starts from a copy of these words instead of zeros -- a nonzero word is a slot someone else owns for the
+ * whole launch; NULL restores the default.  `record` = 1: every such launch writes {slot used, XCC id when it released the slot} per workgroup (slot >=
+ * FHEAES_K2_PARK_SLOTS: the workgroup's private fallback slot FHEAES_K2_PARK_SLOTS + its index).  No effect on the other kernel forms or
+ * with private parking.  Synchronises the context's stream. */
+#define FHEAES_K2_PARK_SLOTS 1024
+int fheaes_k2_park_debug(fheaes_ctx *ctx, const uint32_t *initial_owner, int record);
+/* Synchronises, then reads the two counters the paired kernel keeps for the life of the context (workgroups that fell back to a private
+ * slot; releases that found an owner word other than their own), the owner words as the last claimed launch left them (`owner_out`:
+ * FHEAES_K2_PARK_SLOTS words or NULL) and the records of the last launch recorded since fheaes_k2_park_debug (`record_out`: [record_cap][2]
+ * words or NULL; `record_n` receives the number of records, that launch's grid, or 0).  A `record_cap` below it is FHEAES_ERR_INVALID. */
+int fheaes_k2_park_read(fheaes_ctx *ctx, uint64_t *fallbacks, uint64_t *violations, uint32_t *owner_out, uint32_t *record_out,
+                        uint64_t record_cap, uint64_t *record_n);
 const char *fheaes_version(void);
 
 #ifdef __cplusplus

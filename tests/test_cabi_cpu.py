@@ -49,6 +49,16 @@ def test_invalid_parameters_are_errors_not_ub():
     assert lib.fheaes_synchronize(None) == -1
 
 
+def test_park_slot_hooks_reject_a_null_context():
+    lib = _native.load_library()
+    u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+    owner, fb, vi, n = (u32 * 1024)(), u64(), u64(), u64()
+    assert lib.fheaes_k2_park_debug(None, owner, 1) == -1
+    assert lib.fheaes_k2_park_debug(None, None, 0) == -1
+    assert lib.fheaes_k2_park_read(None, ctypes.byref(fb), ctypes.byref(vi), owner, None, 0, ctypes.byref(n)) == -1
+    assert lib.fheaes_k2_park_read(None, None, None, None, None, 0, None) == -1
+
+
 def test_no_gpu_means_failure_not_fallback():
     import torch
 

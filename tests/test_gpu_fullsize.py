@@ -227,7 +227,8 @@ def test_k2_sustained_launches_stay_deterministic(opt):
     OTHER compute units.  Round 5 indexed the parking slab by the compute unit a workgroup STARTED on: after such a preemption two live
     workgroups shared a slot and 200-260 rows of one launch came out wrong -- never in a short test, always in the driver's 80-second
     bench.  Here: 16,384-bit launches back to back for 75 s, every launch compared with the first on the GPU, plus interleaved 4,096-bit
-    launches (the configs[4] shard's size)."""
+    launches (the configs[4] shard's size).  The slot counters (fheaes_k2_park_read) are read around the soak: a preemption that broke
+    slot ownership shows as a fallback or a violation even where the words happen to match, and no slot may be left owned."""
     import time
 
     import torch
@@ -241,6 +242,7 @@ def test_k2_sustained_launches_stay_deterministic(opt):
     E.cbs_pbs_batch(small, ref, m)
     E.synchronize()
     assert E.k2_plan(m)["kernel"].startswith("blind_rotate_pair_kernel")
+    park0 = E.k2_park_read()
     t0, launches, bad = time.time(), 0, []
     while time.time() - t0 < 75.0:
         E.cbs_pbs_batch(small, out, m)
@@ -253,8 +255,12 @@ def test_k2_sustained_launches_stay_deterministic(opt):
             E.synchronize()
             if not torch.equal(out[4096:8192], ref[4096:8192]):
                 bad.append((launches, round(time.time() - t0, 1), -int((out[4096:8192] != ref[4096:8192]).any(dim=1).sum().item())))
+    park1 = E.k2_park_read()
     assert launches > 200
     assert not bad, "launches that differ from the first (launch, seconds, rows): %s" % bad
+    assert park1["fallbacks"] == park0["fallbacks"], "%d workgroups fell back to a private slot" % (park1["fallbacks"] - park0["fallbacks"])
+    assert park1["violations"] == park0["violations"], "%d releases of a slot not owned" % (park1["violations"] - park0["violations"])
+    assert not park1["owner"].any(), "owner words left taken: %s" % np.flatnonzero(park1["owner"])[:16]
 
 
 def test_chained_encrypt_steps_then_decrypt_shard_every_block(opt, opt_server):

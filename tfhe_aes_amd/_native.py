@@ -16,6 +16,7 @@ from . import _build
 from .params import CParams, WopbsParameters
 
 HOST, DEVICE = 0, 1
+K2_PARK_SLOTS = 1024            # FHEAES_K2_PARK_SLOTS: owner words of the paired kernel's shared parking slots, 128 per XCC
 STAGES = ("keyswitch", "blind_rotate", "pfpks", "ggsw_fft", "vertical_packing", "linear")
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -63,6 +64,8 @@ SIGNATURES = {
     "fheaes_k2_context_plan": (_c.c_int, [_ctx, _c.c_uint64, _c.POINTER(_c.c_int), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32),
                                         _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32), _c.c_char_p, _c.c_size_t]),
     "fheaes_k2_set_parking": (_c.c_int, [_ctx, _c.c_int]),
+    "fheaes_k2_park_debug": (_c.c_int, [_ctx, _c.POINTER(_c.c_uint32), _c.c_int]),
+    "fheaes_k2_park_read": (_c.c_int, [_ctx, _u64p, _u64p, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32), _c.c_uint64, _u64p]),
     "fheaes_version": (_c.c_char_p, []),
 }
 
@@ -275,6 +278,30 @@ class Engine:
     def k2_set_parking(self, claimed: bool):
         """paired blind-rotation kernel: parking slots claimed from a shared pool (default) or one private slot per workgroup"""
         self._check(self._lib.fheaes_k2_set_parking(self._h, 1 if claimed else 0))
+
+    def k2_park_debug(self, initial=None, record: bool = False):
+        """test hook (fheaes_k2_park_debug): claimed-mode paired launches start from the owner words `initial` (K2_PARK_SLOTS words;
+        nonzero = taken for the whole launch) instead of zeros, None restores the default; `record`: each such launch records
+        {slot, XCC} per workgroup (k2_park_read)"""
+        ptr = None
+        if initial is not None:
+            pat = np.ascontiguousarray(np.asarray(initial, dtype=np.uint32))
+            if pat.shape != (K2_PARK_SLOTS,):
+                raise ValueError("initial owner words: expected %d, got shape %s" % (K2_PARK_SLOTS, pat.shape))
+            ptr = pat.ctypes.data_as(_c.POINTER(_c.c_uint32))
+        self._check(self._lib.fheaes_k2_park_debug(self._h, ptr, 1 if record else 0))
+
+    def k2_park_read(self) -> dict:
+        """{"fallbacks", "violations": the context's cumulative counters, "owner": uint32[K2_PARK_SLOTS] as the last claimed launch left
+        them, "record": uint32[grid][2] = (slot, XCC) per workgroup of the last recorded launch (empty: none)}"""
+        fb, vi, n = _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
+        u32p = _c.POINTER(_c.c_uint32)
+        self._check(self._lib.fheaes_k2_park_read(self._h, None, None, None, None, 0, _c.byref(n)))
+        owner = np.zeros(K2_PARK_SLOTS, dtype=np.uint32)
+        rec = np.zeros((n.value, 2), dtype=np.uint32)
+        self._check(self._lib.fheaes_k2_park_read(self._h, _c.byref(fb), _c.byref(vi), owner.ctypes.data_as(u32p), rec.ctypes.data_as(u32p),
+                                                  n.value, _c.byref(n)))
+        return {"fallbacks": fb.value, "violations": vi.value, "owner": owner, "record": rec[:n.value]}
 
     def read_bsk_fourier(self, i: int) -> np.ndarray:
         p = self.params

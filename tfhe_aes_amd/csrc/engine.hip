@@ -214,6 +214,10 @@ struct fheaes_ctx {
     int k2_home = -1;                    // blind rotation: 1 = the LDS-home form runs two workgroups per CU here (queried once), 0 = parked form
     int k2_pair_ok = -1;                 // 1 = the paired kernel (159,504 B of LDS per workgroup) can be resident on a CU here (queried once)
     int k2_park_claim = 1;               // paired kernel's parking slots: 1 = claimed from a shared pool (kern_blindrot_pair.h), 0 = one private slot per workgroup
+    // test hook (fheaes_k2_park_debug): claimed-mode paired launches start from the owner words in ws_park_pattern instead of zeros, and
+    // record {slot, XCC} per workgroup into ws_park_record; k2_park_record_n = grid of the last recorded launch since the hook was set
+    bool k2_park_pattern = false, k2_park_record = false;
+    uint64_t k2_park_record_n = 0;
     // keys
     int8_t *ksk_frag = nullptr, *pfpksk_frag = nullptr;      // balanced key bytes in MFMA B-fragment order
     uint32_t ks_ksteps = 0, ks_coltiles = 0, pf_ksteps = 0, pf_coltiles = 0;
@@ -226,6 +230,7 @@ struct fheaes_ctx {
     int lutset_n[LUTSET_COUNT] = {};
     // workspace
     DevBuf ws_small, ws_pbs, ws_ggsw, ws_ggswf, ws_vp, ws_tmp_a, ws_tmp_b, ws_luts, ws_misc, ws_digits, ws_park, ws_park_owner, ws_tree;
+    DevBuf ws_park_pattern, ws_park_record;
     DevBuf stage[4];                     // host-memspace calls stage their arguments here (grow-only, reused)
     // pinned host staging for the counter bytes of add_scalar; `pin_ev` marks the last copy out of it
     uint8_t *pin = nullptr;
@@ -521,6 +526,22 @@ bool k2_home_allowed(fheaes_ctx *c)
     return c->k2_home == 1;
 }
 
+// the paired kernel's owner words (BRP_PARK_SLOTS x uint32) and the BRP_PARK_TAIL_WORDS uint64 behind them (fallbacks, ownership
+// violations, record pointer).  Zeroed once, when allocated: the reset before every launch touches only the owner words, so the counters
+// accumulate for the life of the context (fheaes_k2_park_read); the record pointer is set by the launches under the test hook and
+// cleared by fheaes_k2_park_debug
+static_assert(FHEAES_K2_PARK_SLOTS == BRP_PARK_SLOTS, "include/fheaes.h and kern_blindrot_pair.h disagree on the number of parking slots");
+constexpr size_t PARK_OWNER_BYTES = BRP_PARK_SLOTS * sizeof(uint32_t) + BRP_PARK_TAIL_WORDS * sizeof(uint64_t);
+constexpr size_t PARK_RECORD_PTR_OFFSET = BRP_PARK_SLOTS * sizeof(uint32_t) + 2 * sizeof(uint64_t);
+
+int ensure_park_owner(fheaes_ctx *c)
+{
+    if (c->ws_park_owner.p) return FHEAES_OK;
+    TRY(ensure(c, c->ws_park_owner, PARK_OWNER_BYTES));
+    HIP_TRY(c, hipMemsetAsync(c->ws_park_owner.p, 0, PARK_OWNER_BYTES, c->stream));
+    return FHEAES_OK;
+}
+
 // bytes of the paired kernel's parking slab for a launch of `grid` workgroups: claimed slots = the shared pool + one private overflow slot
 // per workgroup behind it (never touched unless a pool is exhausted), private slots = one per workgroup
 size_t k2_pair_park_bytes(const fheaes_ctx *c, uint64_t grid)
@@ -576,10 +597,22 @@ int launch_cbs_pbs(fheaes_ctx *c, const uint64_t *lwe_small, uint64_t m, uint32_
         a.park = (uint64_t *)c->ws_park.p; a.park_bytes = park_bytes;
         if (c->k2_park_claim) {
             // owner words of the shared slots: all free when a launch starts (every workgroup gives its slot back before it ends; the
-            // memset makes that hold even after a launch that was aborted)
-            TRY(ensure(c, c->ws_park_owner, BRP_PARK_SLOTS * sizeof(uint32_t)));
-            HIP_TRY(c, hipMemsetAsync(c->ws_park_owner.p, 0, BRP_PARK_SLOTS * sizeof(uint32_t), c->stream));
+            // memset makes that hold even after a launch that was aborted) -- or, under the test hook, the pattern it set
+            TRY(ensure_park_owner(c));
+            if (c->k2_park_pattern)
+                HIP_TRY(c, hipMemcpyAsync(c->ws_park_owner.p, c->ws_park_pattern.p, BRP_PARK_SLOTS * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+            else
+                HIP_TRY(c, hipMemsetAsync(c->ws_park_owner.p, 0, BRP_PARK_SLOTS * sizeof(uint32_t), c->stream));
             a.park_owner = (uint32_t *)c->ws_park_owner.p;
+            if (c->k2_park_record) {
+                TRY(ensure(c, c->ws_park_record, (size_t)gridp * 2 * sizeof(uint32_t)));
+                HIP_TRY(c, hipMemsetAsync(c->ws_park_record.p, 0xFF, (size_t)gridp * 2 * sizeof(uint32_t), c->stream));   // unwritten = ~0
+                const uint64_t rp = (uint64_t)(uintptr_t)c->ws_park_record.p;
+                uint32_t *const rp_word = (uint32_t *)((char *)c->ws_park_owner.p + PARK_RECORD_PTR_OFFSET);
+                HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)rp_word, (int)(uint32_t)rp, 1, c->stream));
+                HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)(rp_word + 1), (int)(uint32_t)(rp >> 32), 1, c->stream));
+                c->k2_park_record_n = gridp;
+            }
         }
 #ifdef EP_STAMPS
         static const char *namesP[EP_NPH] = {"stage+rotate+decomp_first", "decomp_next", "fwd head", "pre-level barrier", "fwd tail (transpose+dft16)",
@@ -830,6 +863,46 @@ int fheaes_k2_set_parking(fheaes_ctx *ctx, int claimed)
     ctx->k2_park_claim = claimed;
     return FHEAES_OK;
 }
+int fheaes_k2_park_debug(fheaes_ctx *ctx, const uint32_t *initial_owner, int record)
+{
+    if (!ctx) return FHEAES_ERR_INVALID;
+    CtxLock lock__(ctx);
+    if (record != 0 && record != 1) return ctx->fail(FHEAES_ERR_INVALID, "k2_park_debug: record must be 0 or 1 (got %d)", record);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (initial_owner) {
+        TRY(ensure(ctx, ctx->ws_park_pattern, BRP_PARK_SLOTS * sizeof(uint32_t)));
+        HIP_TRY(ctx, hipMemcpy(ctx->ws_park_pattern.p, initial_owner, BRP_PARK_SLOTS * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (ctx->ws_park_owner.p)        // no record pointer until a recorded launch sets one
+        HIP_TRY(ctx, hipMemset((char *)ctx->ws_park_owner.p + PARK_RECORD_PTR_OFFSET, 0, sizeof(uint64_t)));
+    ctx->k2_park_pattern = initial_owner != nullptr;
+    ctx->k2_park_record = record == 1;
+    ctx->k2_park_record_n = 0;
+    return FHEAES_OK;
+}
+int fheaes_k2_park_read(fheaes_ctx *ctx, uint64_t *fallbacks, uint64_t *violations, uint32_t *owner_out, uint32_t *record_out,
+                        uint64_t record_cap, uint64_t *record_n)
+{
+    if (!ctx) return FHEAES_ERR_INVALID;
+    CtxLock lock__(ctx);
+    if (record_out && record_cap < ctx->k2_park_record_n)
+        return ctx->fail(FHEAES_ERR_INVALID, "k2_park_read: %llu records do not fit record_cap = %llu", (unsigned long long)ctx->k2_park_record_n,
+                         (unsigned long long)record_cap);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t words[PARK_OWNER_BYTES / sizeof(uint32_t)] = {};       // never allocated (no claimed paired launch yet): all zero
+    if (ctx->ws_park_owner.p) HIP_TRY(ctx, hipMemcpy(words, ctx->ws_park_owner.p, PARK_OWNER_BYTES, hipMemcpyDeviceToHost));
+    uint64_t counters[2];
+    std::memcpy(counters, words + BRP_PARK_SLOTS, sizeof counters);
+    if (fallbacks) *fallbacks = counters[0];
+    if (violations) *violations = counters[1];
+    if (owner_out) std::memcpy(owner_out, words, BRP_PARK_SLOTS * sizeof(uint32_t));
+    if (record_out && ctx->k2_park_record_n)
+        HIP_TRY(ctx, hipMemcpy(record_out, ctx->ws_park_record.p, ctx->k2_park_record_n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (record_n) *record_n = ctx->k2_park_record_n;
+    return FHEAES_OK;
+}
 const char *fheaes_version(void) { return FHEAES_VERSION_STR; }
 
 const char *fheaes_last_error(const fheaes_ctx *ctx)
@@ -916,7 +989,7 @@ void fheaes_destroy(fheaes_ctx *c)
     for (auto ev : c->free_events) (void)hipEventDestroy(ev);
     void *ptrs[] = {c->ksk_frag, c->pfpksk_frag, c->bskf, c->tw_d, c->ws_digits.p,
                     c->ws_small.p, c->ws_pbs.p, c->ws_ggsw.p, c->ws_ggswf.p, c->ws_vp.p, c->ws_tmp_a.p, c->ws_tmp_b.p, c->ws_luts.p, c->ws_misc.p,
-                    c->ws_park.p, c->ws_park_owner.p, c->ws_tree.p};
+                    c->ws_park.p, c->ws_park_owner.p, c->ws_tree.p, c->ws_park_pattern.p, c->ws_park_record.p};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &b : c->stage) if (b.p) (void)hipFree(b.p);
     if (c->pin) (void)hipHostFree(c->pin);
@@ -971,7 +1044,7 @@ int fheaes_reserve(fheaes_ctx *c, uint64_t max_bits)
         if (pl.form == 1) TRY(ensure(c, c->ws_park, (size_t)(pl.units_main + pl.units_tail) * BR16_PARK_WORDS_PER_WG * 8));
         if (pl.form == 2) {
             TRY(ensure(c, c->ws_park, k2_pair_park_bytes(c, pl.units_main + pl.units_tail)));
-            TRY(ensure(c, c->ws_park_owner, BRP_PARK_SLOTS * sizeof(uint32_t)));
+            TRY(ensure_park_owner(c));
         }
     }
     return FHEAES_OK;

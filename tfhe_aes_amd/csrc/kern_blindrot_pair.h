@@ -50,6 +50,11 @@
 //     the Infinity Cache instead of 180 MB per 16,384-bit launch streaming through them (round 5: 203.9 -> 199.2 ms per launch).
 //     A workgroup that finds its XCC's 128 slots taken (never observed; it would take four times the resident workgroups)
 //     falls back to the private slot BRP_PARK_SLOTS + blockIdx.x behind them;
+//     Behind the owner words (BRP_PARK_TAIL_WORDS): two uint64 counters, zeroed once per context and never reset, of the workgroups
+//     that fell back and of the releases that found an owner word other than their own, then a record pointer (test hook, 0 = off):
+//     thread 0 records {slot used, XCC id at the release} per workgroup (fheaes_k2_park_debug / _read, tests/test_gpu_park_slots.py).
+//     All of it runs after the loop: the code in front of the loop is as before, because K2's time moves by 2-3 % with the placement
+//     of the loop's code alone (three s_nop in thread 0's claim branch: +2 %);
 //     A compute unit's L1 cannot serve a stale line of a re-used slot: a lane reads back only what it has itself stored since it
 //     owns the slot (stores update or invalidate the line), and a workgroup streams ~600 KB of key rows per iteration through the
 //     32 KB L1, so nothing an earlier owner left there survives even one iteration (27 us), let alone a hand-over;
@@ -59,10 +64,11 @@
 // the workgroups resume on whatever CU the dispatcher gives them (HIP's own __smid(): "the results vary over time"), a resumed
 // workgroup keeps the slot of the CU it STARTED on, and the next workgroup dispatched to that CU derives the same slot -- two live
 // accumulators in one slot.  On the MI355X boxes of this pool such a preemption happens every ~30 s of sustained load; it corrupted
-// the parked halves of 200-260 rows of one launch each time (profiles/r06_park_collision.txt).  Ownership is
+// the parked halves of 200-260 rows of one launch each time (profiles/r06_park_collision_stage_stress.txt).  Ownership is
 // now a fact recorded in memory, not an inference from where a wave happens to run.
 #define BRP_PARK_SLOTS 1024
 #define BRP_SLOTS_PER_XCC 128
+#define BRP_PARK_TAIL_WORDS 3  /* uint64 words behind the owner words: [0] fallbacks to a private slot, [1] ownership violations, [2] record pointer */
 #ifndef BRP_MAC_PRIO
 #define BRP_MAC_PRIO 1       /* wave priority during the multiply-accumulate (0 / 1 / 3: 214.2 / 211.8 / 212.0 ms per 16,384-bit launch) */
 #endif
@@ -79,7 +85,7 @@
 #endif
 #define BRP_HALF_TILES (EP_GROUPS - 1)                                                   /* 15 tiles per half: group 15 shares group 14's */
 #define BRP_LDS_DOUBLES(R) (2 * FHE_TW_ENTRIES + 2 * BRP_HALF_TILES * GROUP_TILE_DOUBLES + ((R) == 3 ? 6 * FHE_N : 0))   /* R = 3: 159,488 B */
-#define BRP_LDS_EXTRA_DOUBLES 2                                                          /* + the claimed parking slot, broadcast to the eight wavefronts */
+#define BRP_LDS_EXTRA_DOUBLES 2                                                          /* + the claimed parking slot, broadcast to the eight wavefronts, and its owner value */
 #define BRP_PARK_WORDS_PER_HALF (BRP_RESIDENT_HI ? 8 * EP_THREADS * 2 : 16 * EP_THREADS * 2)   /* per half and iteration: 32 KB (lo[] only) or 64 KB */
 
 __device__ __forceinline__ int brp_opaque_tid()
@@ -175,7 +181,7 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
                 break;
             }
         }
-        *slot_word = got;
+        *reinterpret_cast<uint2 *>(slot_word) = make_uint2(got, unit_index + 1u);     // + the owner value, for the release
     }
 #define BRP_PARK_SLOT(a) ((unsigned)(a) * (EP_THREADS * 16))
     __syncthreads();   // tables and the claimed slot visible
@@ -647,7 +653,25 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
     if (A.park_owner) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (tid == 0 && park_slot < BRP_PARK_SLOTS) __hip_atomic_store(A.park_owner + park_slot, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) {
+            unsigned long long *const tail = reinterpret_cast<unsigned long long *>(A.park_owner + BRP_PARK_SLOTS);
+            const unsigned me = slot_word[1];
+            if (park_slot < BRP_PARK_SLOTS) {
+                // an owner word that is not this workgroup's own is counted: a slot released by someone else, or claimed twice
+                if (__hip_atomic_exchange(A.park_owner + park_slot, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != me)
+                    __hip_atomic_fetch_add(tail + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else {
+                __hip_atomic_fetch_add(tail, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            // from memory, not from the kernel arguments (those are loaded at the kernel's entry and would stay live across the loop)
+            uint32_t *const record = reinterpret_cast<uint32_t *>(__hip_atomic_load(tail + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            if (record) {
+                unsigned hw_xcc;
+                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(hw_xcc));
+                record[2 * (me - 1u)] = park_slot;
+                record[2 * (me - 1u) + 1] = hw_xcc & 7u;
+            }
+        }
     }
 
     // ---- sample extract coefficient 0 ---------------------------------------------------------------
