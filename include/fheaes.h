@@ -111,7 +111,8 @@ int fheaes_clone_info(fheaes_ctx *ctx, int *path, uint64_t *bytes, double *secon
 /* The reference builds tfhe-rs with `noise-asserts` (Cargo.toml:7) under MaxNoiseLevel::new(5) (client.rs:92): a sum of more than
  * five nominal-noise ciphertexts between two bootstraps panics (many_wopbs.rs:101-108 resets every WoPBS output to NOMINAL).
  * What the engine has is a STATIC SCHEDULE ASSERTION, not runtime noise tracking: each linear layer of the engine's own AES schedule
- * declares how many WoPBS outputs it sums per output word (MixColumns + AddRoundKey = 4 + 1, the key-expansion sums = 2); a layer
+ * declares how many WoPBS outputs it sums per output word (MixColumns + AddRoundKey = 4 + 1, the key-expansion sums = 2, the equivalent
+ * inverse cipher's InvShiftRows + InvMixColumns + AddRoundKey = 4 + 1, its round-key conversion's InvMixColumns = 4, refreshed after); a layer
  * whose gather table would sum more than the limit is refused with FHEAES_ERR_INVALID, and the largest count any call on this context
  * has declared can be read back.  Ciphertext words carry no noise metadata: a state that a caller has already summed before passing
  * it in counts as nominal here.  Callers that add ciphertext words themselves (the stage-level entry points hand out raw uint64
@@ -168,6 +169,20 @@ int fheaes_aes_key_expansion(fheaes_ctx *ctx, const uint64_t *key, uint64_t *rou
 int fheaes_aes_encrypt(fheaes_ctx *ctx, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace);
 /* Server::aes_decrypt (server.rs:67), batched. */
 int fheaes_aes_decrypt(fheaes_ctx *ctx, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace);
+/* The equivalent inverse cipher (FIPS-197 section 5.3.5, Fig. 15), added in 0.4 as two entry points next to the reference's schedule
+ * (fheaes_aes_decrypt stays word for word Server::aes_decrypt, server.rs:67-105).  That schedule runs two WoPBS per round -- INV_SBOX,
+ * then the 4-LUT {9x, 11x, 13x, 14x} InvMixColumns -- which, as server.rs:86-89 says, almost doubles the time of encryption: 19 x 128
+ * bit circuit bootstraps per block against 1,280.  InvMixColumns is linear, so IMC(InvS(x)) + IMC(k) needs ONE WoPBS per byte, with the
+ * composed tables {9, 11, 13, 14} * InvS[x], once the round keys have gone through InvMixColumns: 10 WoPBS per block, as for encryption.
+ * The words differ from fheaes_aes_decrypt's (another algorithm); the plaintext is the same.
+ *
+ * Decryption round keys from the expanded ones, once per AES key (2 x 1,152 bit circuit bootstraps):
+ * dw[0] = w[0], dw[10] = w[10], dw[r] = InvMixColumns(w[r]) for r = 1..9, each byte refreshed to nominal noise by an identity WoPBS
+ * (as the key expansion's refresh, server.rs:150; without it a round would sum 4 WoPBS outputs + a key of level 4 = 8 > 5).
+ * round_keys, dec_round_keys: [11][16][8][kN+1].  Identical (or overlapping) buffers are FHEAES_ERR_INVALID. */
+int fheaes_aes_decryption_round_keys(fheaes_ctx *ctx, const uint64_t *round_keys, uint64_t *dec_round_keys, int memspace);
+/* The equivalent inverse cipher, batched, in place: state [n_blocks][16][8][kN+1], dec_round_keys from fheaes_aes_decryption_round_keys. */
+int fheaes_aes_decrypt_equivalent(fheaes_ctx *ctx, const uint64_t *dec_round_keys, uint64_t *state, uint64_t n_blocks, int memspace);
 /* Server::add_scalar (server.rs:172), batched: state[b] += counters[b] (u128 as {hi, lo}, host array
  * of 2*n_blocks words regardless of memspace).  The first-byte carry uses counter & 0xFF (the
  * reference's server.rs:182 is wrong for counters >= 256). */

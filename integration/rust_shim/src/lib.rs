@@ -73,6 +73,9 @@ extern "C" {
     pub fn fheaes_aes_key_expansion(ctx: *mut fheaes_ctx, key: *const u64, round_keys: *mut u64, memspace: c_int) -> c_int;
     pub fn fheaes_aes_encrypt(ctx: *mut fheaes_ctx, round_keys: *const u64, state: *mut u64, n_blocks: u64, memspace: c_int) -> c_int;
     pub fn fheaes_aes_decrypt(ctx: *mut fheaes_ctx, round_keys: *const u64, state: *mut u64, n_blocks: u64, memspace: c_int) -> c_int;
+    // the equivalent inverse cipher (FIPS-197 5.3.5): round-key conversion once per key, then one WoPBS per round
+    pub fn fheaes_aes_decryption_round_keys(ctx: *mut fheaes_ctx, round_keys: *const u64, dec_round_keys: *mut u64, memspace: c_int) -> c_int;
+    pub fn fheaes_aes_decrypt_equivalent(ctx: *mut fheaes_ctx, dec_round_keys: *const u64, state: *mut u64, n_blocks: u64, memspace: c_int) -> c_int;
     pub fn fheaes_add_scalar(ctx: *mut fheaes_ctx, state: *mut u64, n_blocks: u64, counters_hi_lo: *const u64, memspace: c_int) -> c_int;
 }
 

@@ -53,6 +53,8 @@ SIGNATURES = {
     "fheaes_aes_key_expansion": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_int]),
     "fheaes_aes_encrypt": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_int]),
     "fheaes_aes_decrypt": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_int]),
+    "fheaes_aes_decryption_round_keys": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_decrypt_equivalent": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_int]),
     "fheaes_add_scalar": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _u64p, _c.c_int]),
     "fheaes_profile_enable": (_c.c_int, [_ctx, _c.c_int]),
     "fheaes_profile_reset": (_c.c_int, [_ctx]),
@@ -244,6 +246,15 @@ class Engine:
 
     def aes_decrypt(self, round_keys, state, n_blocks: int):
         self._check(self._lib.fheaes_aes_decrypt(self._h, _ptr(round_keys)[0], _ptr(state)[0], n_blocks, self._space(round_keys, state)))
+
+    def aes_decryption_round_keys(self, round_keys, dec_round_keys):
+        """the equivalent inverse cipher's round keys (FIPS-197 section 5.3.5): dw[r] = InvMixColumns(w[r]) for r = 1..9, refreshed"""
+        self._check(self._lib.fheaes_aes_decryption_round_keys(self._h, _ptr(round_keys)[0], _ptr(dec_round_keys)[0],
+                                                               self._space(round_keys, dec_round_keys)))
+
+    def aes_decrypt_equivalent(self, dec_round_keys, state, n_blocks: int):
+        self._check(self._lib.fheaes_aes_decrypt_equivalent(self._h, _ptr(dec_round_keys)[0], _ptr(state)[0], n_blocks,
+                                                            self._space(dec_round_keys, state)))
 
     def add_scalar(self, state, n_blocks: int, counters):
         cnt = np.zeros((n_blocks, 2), dtype=np.uint64)

@@ -110,3 +110,20 @@ def aes128_decrypt_block(key: int, block: int) -> int:
     s = [INV_SBOX[b] for b in _inv_shift_rows(s)]
     s = [a ^ b for a, b in zip(s, rk[0])]
     return sum(b << (8 * (15 - i)) for i, b in enumerate(s))
+
+
+def inv_mix_columns_round_keys(expanded):
+    """the equivalent inverse cipher's round keys (FIPS-197 section 5.3.5): dw[0] = w[0], dw[10] = w[10], dw[r] = InvMixColumns(w[r])"""
+    return [list(expanded[0])] + [_mix(list(expanded[r]), (14, 11, 13, 9)) for r in range(1, 10)] + [list(expanded[10])]
+
+
+def aes128_decrypt_block_equivalent(dw, block: int) -> int:
+    """FIPS-197 Fig. 15 with the round keys of inv_mix_columns_round_keys: InvSubBytes, InvShiftRows, InvMixColumns, AddRoundKey"""
+    s = [(block >> (8 * (15 - i))) & 0xFF for i in range(16)]
+    s = [a ^ b for a, b in zip(s, dw[10])]
+    for rnd in range(9, 0, -1):
+        s = _mix(_inv_shift_rows([INV_SBOX[b] for b in s]), (14, 11, 13, 9))
+        s = [a ^ b for a, b in zip(s, dw[rnd])]
+    s = _inv_shift_rows([INV_SBOX[b] for b in s])
+    s = [a ^ b for a, b in zip(s, dw[0])]
+    return sum(b << (8 * (15 - i)) for i, b in enumerate(s))

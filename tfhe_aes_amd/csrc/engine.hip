@@ -26,7 +26,7 @@
 #include "ks_launch.h"                 // kern_keyswitch.h: the kernels themselves, or (two-unit product build) their argument block + launch functions
 #include "kern_linear.h"
 
-#define FHEAES_VERSION_STR "fheaes-mi355x 0.3 (gfx950)" FHEAES_BUILD_KIND      /* " dev" when built with developer knobs (knobs.h) */
+#define FHEAES_VERSION_STR "fheaes-mi355x 0.4 (gfx950)" FHEAES_BUILD_KIND      /* " dev" when built with developer knobs (knobs.h) */
 #define MAX_CHUNK_BITS 32768ull
 #define MAX_WOPBS_BITS 16u            /* widest radix input of many_wopbs_without_padding (LUT of 2^16 entries per output bit) */
 
@@ -114,7 +114,8 @@ const AesTables &aes_tables()
     return t;
 }
 
-enum { LUTSET_ENC_ROUND = 0, LUTSET_SBOX, LUTSET_INV_SBOX, LUTSET_DEC_MUL, LUTSET_IDENTITY, LUTSET_COUNT };
+// 0..4 mirror oracle.LUTSET_*; LUTSET_DEC_EQ_ROUND (the equivalent inverse cipher's round, FIPS-197 section 5.3.5) is appended after them
+enum { LUTSET_ENC_ROUND = 0, LUTSET_SBOX, LUTSET_INV_SBOX, LUTSET_DEC_MUL, LUTSET_IDENTITY, LUTSET_DEC_EQ_ROUND, LUTSET_COUNT };
 
 // words of one (LUT, output bit) row: gen_lut.rs:19-23, lut_size = max(2^nb_block, polynomial_size)
 inline uint64_t lut_row_words(uint32_t nb) { return nb > 9 ? (1ull << nb) : (uint64_t)FHE_N; }
@@ -142,6 +143,9 @@ int build_lutset_host(int which, std::vector<uint64_t> &out)
         case LUTSET_DEC_MUL:
             f[0][x] = AesTables::mul((uint8_t)x, 9); f[1][x] = AesTables::mul((uint8_t)x, 11);
             f[2][x] = AesTables::mul((uint8_t)x, 13); f[3][x] = AesTables::mul((uint8_t)x, 14); n = 4; break;
+        case LUTSET_DEC_EQ_ROUND:                                   // {9, 11, 13, 14} * InvS[x]: same order as LUTSET_DEC_MUL, so MC_DEC indexes it
+            f[0][x] = AesTables::mul(T.inv[x], 9); f[1][x] = AesTables::mul(T.inv[x], 11);
+            f[2][x] = AesTables::mul(T.inv[x], 13); f[3][x] = AesTables::mul(T.inv[x], 14); n = 4; break;
         default: f[0][x] = (uint64_t)x; break;
         }
     }
@@ -176,6 +180,16 @@ GatherTable table_dec_mix()
     GatherTable t{}; t.terms = 4;
     for (int col = 0; col < 4; ++col) for (int row = 0; row < 4; ++row) for (int r2 = 0; r2 < 4; ++r2) {
         t.src[4 * col + row][r2] = (int8_t)(4 * col + r2);
+        t.lut[4 * col + row][r2] = (int8_t)MC_DEC[row][r2];
+    }
+    return t;
+}
+// InvShiftRows folded into InvMixColumns (the equivalent inverse cipher's round): out[c][r] = sum_j MC_DEC[r][j] * in[(c - j) & 3][j]
+GatherTable table_dec_eq_round()
+{
+    GatherTable t{}; t.terms = 4;
+    for (int col = 0; col < 4; ++col) for (int row = 0; row < 4; ++row) for (int r2 = 0; r2 < 4; ++r2) {
+        t.src[4 * col + row][r2] = (int8_t)(4 * ((col - r2) & 3) + r2);
         t.lut[4 * col + row][r2] = (int8_t)MC_DEC[row][r2];
     }
     return t;
@@ -1427,31 +1441,94 @@ static int aes_decrypt_dev(fheaes_ctx *c, const uint64_t *rk, uint64_t *state, u
     return FHEAES_OK;
 }
 
-static int aes_crypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace, bool dec)
+// The equivalent inverse cipher (FIPS-197 section 5.3.5, Fig. 15): InvMixColumns is linear, so IMC(InvS(x)) + IMC(w[r]) is one WoPBS
+// per byte with the composed tables {9, 11, 13, 14} * InvS[x] (LUTSET_DEC_EQ_ROUND), summed through the InvShiftRows-folded gather with
+// dw[r] = IMC(w[r]) as the round key: 10 WoPBS per block like aes_encrypt_dev, against the 19 of aes_decrypt_dev (the reference's own
+// schedule, server.rs:67-105, which says at :86-89 that it almost doubles the time of encryption).  dw: fheaes_aes_decryption_round_keys.
+static int aes_decrypt_eq_dev(fheaes_ctx *c, const uint64_t *dw, uint64_t *state, uint64_t n_blocks)
+{
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
+    TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
+    uint64_t *vp = (uint64_t *)c->ws_vp.p;
+    const GatherTable t_round = table_dec_eq_round(), t_inv = table_shift_rows(true);
+    TRY(launch_add_bcast(c, state, dw + 10ull * sw, sw, n_blocks));
+    for (int round = 9; round >= 1; --round) {
+        TRY(many_sbox_dev(c, state, nbytes, LUTSET_DEC_EQ_ROUND, vp));
+        TRY(launch_gather(c, vp, 4, dw + (uint64_t)round * sw, state, n_blocks, t_round));     // 4 WoPBS outputs + dw[round] = 5
+    }
+    TRY(many_sbox_dev(c, state, nbytes, LUTSET_INV_SBOX, vp));
+    TRY(launch_gather(c, vp, 1, dw, state, n_blocks, t_inv));
+    return FHEAES_OK;
+}
+
+typedef int (*AesDevFn)(fheaes_ctx *, const uint64_t *, uint64_t *, uint64_t);
+
+static int aes_crypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace, AesDevFn dev)
 {
     TRY(check_keys(c));
     if (!round_keys || !state) return c->fail(FHEAES_ERR_INVALID, "null pointer");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (memspace == FHEAES_DEVICE) return dec ? aes_decrypt_dev(c, round_keys, state, n_blocks) : aes_encrypt_dev(c, round_keys, state, n_blocks);
+    if (memspace == FHEAES_DEVICE) return dev(c, round_keys, state, n_blocks);
     Staged s(c);
     void *drk, *dst;
     const uint64_t sw = 16ull * 8 * c->big1;
     TRY(s.in(round_keys, 11 * sw * 8, &drk));
     TRY(s.in(state, n_blocks * sw * 8, &dst));
-    TRY(dec ? aes_decrypt_dev(c, (const uint64_t *)drk, (uint64_t *)dst, n_blocks) : aes_encrypt_dev(c, (const uint64_t *)drk, (uint64_t *)dst, n_blocks));
+    TRY(dev(c, (const uint64_t *)drk, (uint64_t *)dst, n_blocks));
     return s.out(state, dst, n_blocks * sw * 8);
 }
 
 int fheaes_aes_encrypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace)
 {
     CtxLock lock__(c);
-    return aes_crypt(c, round_keys, state, n_blocks, memspace, false);
+    return aes_crypt(c, round_keys, state, n_blocks, memspace, aes_encrypt_dev);
 }
 
 int fheaes_aes_decrypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace)
 {
     CtxLock lock__(c);
-    return aes_crypt(c, round_keys, state, n_blocks, memspace, true);
+    return aes_crypt(c, round_keys, state, n_blocks, memspace, aes_decrypt_dev);
+}
+
+int fheaes_aes_decrypt_equivalent(fheaes_ctx *c, const uint64_t *dec_round_keys, uint64_t *state, uint64_t n_blocks, int memspace)
+{
+    CtxLock lock__(c);
+    return aes_crypt(c, dec_round_keys, state, n_blocks, memspace, aes_decrypt_eq_dev);
+}
+
+// dw[0] = w[0], dw[10] = w[10], dw[r] = InvMixColumns(w[r]) for r = 1..9: the 144 bytes of w[1..9] in one batch -- the 4-LUT
+// {9x, 11x, 13x, 14x} WoPBS, the InvMixColumns gather (4 terms, no key) and an identity WoPBS that brings every byte back to nominal
+// noise, as the key expansion's refresh does (server.rs:150): a round of the equivalent inverse cipher then sums 4 WoPBS outputs + 1 key
+static int dec_round_keys_dev(fheaes_ctx *c, const uint64_t *w, uint64_t *dw)
+{
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 9 * 16;
+    TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
+    TRY(ensure(c, c->ws_tmp_a, nbytes * bw * 8));
+    uint64_t *vp = (uint64_t *)c->ws_vp.p, *mix = (uint64_t *)c->ws_tmp_a.p;
+    HIP_TRY(c, hipMemcpyAsync(dw, w, sw * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dw + 10ull * sw, w + 10ull * sw, sw * 8, hipMemcpyDeviceToDevice, c->stream));
+    TRY(many_sbox_dev(c, w + sw, nbytes, LUTSET_DEC_MUL, vp));
+    TRY(launch_gather(c, vp, 4, nullptr, mix, 9, table_dec_mix()));
+    TRY(many_sbox_dev(c, mix, nbytes, LUTSET_IDENTITY, dw + sw));
+    return FHEAES_OK;
+}
+
+int fheaes_aes_decryption_round_keys(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *dec_round_keys, int memspace)
+{
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!round_keys || !dec_round_keys) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    const uint64_t sw = 16ull * 8 * c->big1;
+    const uintptr_t a = (uintptr_t)round_keys, b = (uintptr_t)dec_round_keys, bytes = 11 * sw * 8;
+    if (a < b + bytes && b < a + bytes) return c->fail(FHEAES_ERR_INVALID, "round_keys and dec_round_keys overlap (the conversion is not in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (memspace == FHEAES_DEVICE) return dec_round_keys_dev(c, round_keys, dec_round_keys);
+    Staged s(c);
+    void *drk, *ddw;
+    TRY(s.in(round_keys, bytes, &drk));
+    TRY(s.alloc(&ddw, bytes));
+    TRY(dec_round_keys_dev(c, (const uint64_t *)drk, (uint64_t *)ddw));
+    return s.out(dec_round_keys, ddw, bytes);
 }
 
 static int key_expansion_dev(fheaes_ctx *c, const uint64_t *key, uint64_t *w)

@@ -2,6 +2,7 @@
 
 Same names, argument meaning and error behaviour as
   /root/reference/src/server/server.rs        Server::{new, aes_encrypt, aes_decrypt, aes_key_expansion, add_scalar}
+  (plus aes_decryption_round_keys / aes_decrypt_equivalent: the FIPS-197 section 5.3.5 equivalent inverse cipher)
   /root/reference/src/server/sbox/sbox.rs     sbox, many_sbox, mul2 .. mul14
   /root/reference/src/server/sbox/many_wopbs.rs  many_wopbs_without_padding
   /root/reference/src/server/sbox/gen_lut.rs  gen_lut
@@ -122,6 +123,20 @@ class Server:
         self.engine.aes_decrypt(encrypted_round_keys, state, n_blocks)
         return state
 
+    def aes_decryption_round_keys(self, round_keys):
+        """round keys [11][16][8][kN+1] -> the equivalent inverse cipher's (FIPS-197 section 5.3.5): w[0], InvMixColumns(w[1..9]) refreshed
+        to nominal noise, w[10].  Once per AES key (2 x 1,152 bit circuit bootstraps); feeds aes_decrypt_equivalent."""
+        dw = _empty_like(round_keys, (11, 16, 8, self.params.big1))
+        self.engine.aes_decryption_round_keys(round_keys, dw)
+        return dw
+
+    def aes_decrypt_equivalent(self, dec_round_keys, state):
+        """the equivalent inverse cipher, in place: one WoPBS per round (10 per block, as aes_encrypt) instead of aes_decrypt's two
+        (server.rs:67-105, :86-89).  Same plaintext as aes_decrypt, other ciphertext words.  state [16][8][kN+1] or [B][16][8][kN+1]."""
+        n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
+        self.engine.aes_decrypt_equivalent(dec_round_keys, state, n_blocks)
+        return state
+
     def add_scalar(self, state, i):
         """server.rs:172, in place.  ``i`` is one integer, or one per block of a batched state."""
         n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
@@ -193,6 +208,15 @@ class ServerGroup:
 
     def aes_decrypt(self, round_keys, state):
         return self._fan_out(lambda s, shard, lo: s.aes_decrypt(round_keys, shard), state)
+
+    def aes_decryption_round_keys(self, round_keys):
+        """converted on context 0; finished before returning, since device round keys are then read from the other contexts' streams"""
+        dw = self.servers[0].aes_decryption_round_keys(round_keys)
+        self.servers[0].synchronize()
+        return dw
+
+    def aes_decrypt_equivalent(self, dec_round_keys, state):
+        return self._fan_out(lambda s, shard, lo: s.aes_decrypt_equivalent(dec_round_keys, shard), state)
 
     def add_scalar(self, state, counters):
         counters = list(counters)
