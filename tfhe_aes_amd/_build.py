@@ -72,11 +72,10 @@ def unit_flags(unit: str):
     raise ValueError(unit)
 
 
-def engine_flags(unit: str = "engine"):
-    """flags of a SINGLE-UNIT developer build (`hipcc <these> -o lib.so csrc/engine.hip`, as tools/ablate_*.py do it): engine.hip alone
-    is then a complete library, every kernel in it compiled under the scheduler setting of the product unit named (`unit="keyswitch"`
-    for experiments on K1 / K3)"""
-    return _common_flags() + ["-shared"] + (NO_POST_RA_SCHED if unit == "engine" else [])
+def engine_flags():
+    """flags of a SINGLE-UNIT developer build (`hipcc <these> -o lib.so csrc/engine.hip`, as tools/ablate_k2.py does it): engine.hip alone
+    is then a complete library, every kernel in it compiled under the scheduler setting of the "engine" unit"""
+    return _common_flags() + ["-shared"] + NO_POST_RA_SCHED
 
 
 def build_engine(force: bool = False, extra=()) -> Path:

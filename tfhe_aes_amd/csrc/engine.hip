@@ -385,39 +385,22 @@ struct StampReport {
 #endif
 
 // ---- how a blind-rotation batch is cut into workgroups (fheaes_k2_launch_plan) -------------------------------------------------
-#ifndef LATENCY_BATCH_BITS
 #define LATENCY_BATCH_BITS 256ull      /* at most one 512-thread workgroup per CU */
-#endif
-#ifndef PBS_BALANCE
-#define PBS_BALANCE 1
-#endif
-#ifndef PBS_SMALL_R2
-#define PBS_SMALL_R2 1
-#endif
-#ifndef K2_PAIR
-#define K2_PAIR 1                      /* batches above K2_PAIR_MIN_BITS take the paired form (kern_blindrot_pair.h): one 512-thread workgroup per CU */
-#endif
-#ifndef K2_PAIR_MIN_BITS
-#define K2_PAIR_MIN_BITS 768ull
-#endif
-#ifndef K2_PAIR_TAIL4
-#define K2_PAIR_TAIL4 1                /* 1: the paired form fills its last generation with four-ciphertext units on every CU; 0: six-ciphertext units only
-                                          (the last generation then covers fewer CUs) -- measured at 4,096 bits, see DESIGN.md */
-#endif
+#define K2_PAIR_MIN_BITS 768ull        /* batches above this take the paired form (kern_blindrot_pair.h): one 512-thread workgroup per CU */
 struct K2Plan { int form; uint64_t units_main; uint32_t r_main; uint64_t units_tail; uint32_t r_tail; };
 K2Plan k2_plan(uint64_t m, uint32_t cu_count, uint32_t k1, bool allow_pair = true)
 {
     K2Plan pl{};
     if (m <= LATENCY_BATCH_BITS) { pl.form = 0; pl.units_main = m; pl.r_main = 1; return pl; }
-    if (K2_PAIR && allow_pair && k1 == 5 && m > K2_PAIR_MIN_BITS) {
+    if (allow_pair && k1 == 5 && m > K2_PAIR_MIN_BITS) {
         // paired form: units of 6 and of 4 ciphertexts, one workgroup per CU, a whole number of generations that covers the batch
         // (16,384 bits = 2,560 x 6 + 256 x 4 = 11 generations; 4,096 = 512 x 6 + 256 x 4 = 3; 1,152 = 64 x 6 + 192 x 4 = 1); the
-        // smaller units last
+        // smaller units last: the last generation is filled with four-ciphertext units on every CU instead of covering fewer CUs
+        // with six-ciphertext ones (measured at 4,096 bits)
         pl.form = 2; pl.r_main = 6; pl.r_tail = 4;
         const uint64_t gens = (m + 6ull * cu_count - 1) / (6ull * cu_count);
         uint64_t nu = gens * cu_count;
         uint64_t four = 6 * nu >= m ? (6 * nu - m) / 2 : 0;      // units that can give up two of their six slots
-        if (!K2_PAIR_TAIL4) { pl.units_main = (m + 5) / 6; pl.units_tail = 0; return pl; }
         if (four > nu) four = nu;
         if (four == nu && 4 * nu > m) { nu = (m + 3) / 4; four = nu; }          // less than one generation of 4-ciphertext units
         pl.units_tail = four; pl.units_main = nu - four;
@@ -426,10 +409,10 @@ K2Plan k2_plan(uint64_t m, uint32_t cu_count, uint32_t k1, bool allow_pair = tru
     pl.form = 1;
     pl.r_main = k1 == 5 ? 3 : 8;
     pl.units_main = (m + pl.r_main - 1) / pl.r_main;
-    if (PBS_BALANCE && k1 == 5) {
+    if (k1 == 5) {
         const uint64_t slots = 2ull * cu_count;
         pl.r_tail = 2;
-        if (PBS_SMALL_R2 && (m + 1) / 2 <= cu_count) {
+        if ((m + 1) / 2 <= cu_count) {
             // at most one two-ciphertext unit per CU: shorter units than three-ciphertext ones, still one per CU
             pl.units_main = 0;
             pl.units_tail = (m + 1) / 2;
@@ -460,16 +443,9 @@ int launch_keyswitch(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *ou
     a.afrag = af; a.bfrag = c->ksk_frag; a.ksteps = c->ks_ksteps; a.coltiles = c->ks_coltiles;
     a.in = in; a.in_stride = c->big1; a.body_index = (int32_t)c->big; a.body_col = c->n; a.ncols = c->n + 1;
     a.out = out; a.out_stride = c->n + 1; a.out_z_stride = 0; a.m = m;
-#ifndef KS1_LDS
-#define KS1_LDS 1                      /* 1 (round 6: 1.87 -> 1.48 ms per 16,384-bit launch, same words): K1 through the LDS-tiled kernel too; 0: one wave = one tile, operands from L2 */
-#endif
-#if KS1_LDS
+    // K1 through the LDS-tiled kernel too (round 6: 1.87 -> 1.48 ms per 16,384-bit launch, same words)
     dim3 grid((c->ks_coltiles + KSL_COL_TILES - 1) / KSL_COL_TILES, (unsigned)((m + 16 * KSL_CT_TILES - 1) / (16 * KSL_CT_TILES)), 1);
     ks_launch_mfma_lds(1, grid, c->stream, a);
-#else
-    dim3 grid((c->ks_coltiles + 3) / 4, (unsigned)((m + KS_CT_TILE - 1) / KS_CT_TILE), 1);
-    ks_launch_mfma(1, grid, c->stream, a);
-#endif
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
@@ -489,16 +465,8 @@ int launch_pfpks(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out, u
     a.afrag = af; a.bfrag = c->pfpksk_frag; a.ksteps = c->pf_ksteps; a.coltiles = c->pf_coltiles;
     a.in = in; a.in_stride = c->big1; a.body_index = -1; a.body_col = 0; a.ncols = gsz;
     a.out = out; a.out_stride = out_stride; a.out_z_stride = gsz; a.m = m;
-#ifndef KS_LDS
-#define KS_LDS 1
-#endif
-#if KS_LDS
     dim3 grid((c->pf_coltiles + KSL_COL_TILES - 1) / KSL_COL_TILES, (unsigned)((m + 16 * KSL_CT_TILES - 1) / (16 * KSL_CT_TILES)), c->k1);
     ks_launch_mfma_lds(2, grid, c->stream, a);
-#else
-    dim3 grid((c->pf_coltiles + 3) / 4, (unsigned)((m + KS_CT_TILE - 1) / KS_CT_TILE), c->k1);
-    ks_launch_mfma(2, grid, c->stream, a);
-#endif
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
@@ -534,7 +502,7 @@ bool k2_home_allowed(fheaes_ctx *c)
     if (c->k2_home < 0) {
         int per_cu = 0;
         const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, blind_rotate16_kernel<5, 5, 8, 3, 2, true>, EP_THREADS, 0);
-        c->k2_home = (BR16_W3_LDS_HOME && oe == hipSuccess && per_cu >= 2) ? 1 : 0;
+        c->k2_home = (oe == hipSuccess && per_cu >= 2) ? 1 : 0;
         (void)hipGetLastError();         // a failed query means "fall back", not a failed launch
     }
     return c->k2_home == 1;

@@ -22,15 +22,8 @@
 #include "fft_consts.h"
 
 #define FHE_N 512
-#ifndef FFT_XPOSE_PRIO
 #define FFT_XPOSE_PRIO 2   /* wave priority while a transpose's LDS writes/reads are being issued (measured -0.7 %) */
-#endif
-#ifndef FFT_CHUNK
 #define FFT_CHUNK 4            /* butterflies issued together (see dft16) */
-#endif
-#ifndef FFT_CHUNK_BARRIERS
-#define FFT_CHUNK_BARRIERS 1
-#endif
 #define FHE_H 256
 #define GROUP_TILE_BYTES 4352          /* 16 rows x 17 complex x 16 B */
 #define GROUP_TILE_DOUBLES (GROUP_TILE_BYTES / 8)
@@ -95,7 +88,7 @@ __device__ __forceinline__ void dft16(double (&xr)[16], double (&xi)[16], Hook h
                     ti[j] = __builtin_fma(c, xi[Q], xi[P]);
                 }
             }
-            if (FFT_CHUNK_BARRIERS) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < CHUNK; ++j) {
                 const int i = c0 + j, blk = (i / half) * n, k = i % half;
@@ -107,7 +100,7 @@ __device__ __forceinline__ void dft16(double (&xr)[16], double (&xi)[16], Hook h
                     ti[j] = __builtin_fma(s, xr[Q], ti[j]);
                 }
             }
-            if (FFT_CHUNK_BARRIERS) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < CHUNK; ++j) {
                 const int i = c0 + j, blk = (i / half) * n, k = i % half;
@@ -125,7 +118,7 @@ __device__ __forceinline__ void dft16(double (&xr)[16], double (&xi)[16], Hook h
                     xr[P] = tr[j]; xi[P] = ti[j];
                 }
             }
-            if (FFT_CHUNK_BARRIERS) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
             chunk_hook(st, c0);
         }
         hook(st);
@@ -154,9 +147,7 @@ __device__ __forceinline__ void wg_barrier_lds_only()
 // row and receives tile[b][col] for every col.
 __device__ __forceinline__ void group_transpose(double (&xr)[16], double (&xi)[16], double *tile, int b)
 {
-#if FFT_XPOSE_PRIO
     __builtin_amdgcn_s_setprio(FFT_XPOSE_PRIO);
-#endif
 #pragma unroll
     for (int k1 = 0; k1 < 16; ++k1) {
         double2 v; v.x = xr[k1]; v.y = xi[k1];
@@ -169,9 +160,7 @@ __device__ __forceinline__ void group_transpose(double (&xr)[16], double (&xi)[1
         xr[c] = v.x; xi[c] = v.y;
     }
     wave_lds_sync();
-#if FFT_XPOSE_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // Table reads in batches of eight, issued a whole pass ahead of their use: with one or two waves per SIMD nothing hides an LDS
@@ -275,13 +264,6 @@ __device__ __forceinline__ uint64_t torus_acc_scaled(uint64_t acc, double w)
 }
 __device__ __forceinline__ uint64_t torus_acc(uint64_t acc, double v)
 {
-#ifdef FHE_TORUS_CONV_OLD
-    double w = v * 0x1p-72;
-    w -= __builtin_rint(w);
-    double r = __builtin_rint(w * 0x1p64);
-    if (r >= 0x1p63) r -= 0x1p64;
-    return acc + (uint64_t)(long long)r;
-#else
     double w = v * 0x1p-72;
     w -= __builtin_rint(w);                                  // exact, |w| <= 1/2
     const double C_HI = 0x1.8p20, C_LO = 0x1.8p-12;
@@ -294,7 +276,6 @@ __device__ __forceinline__ uint64_t torus_acc(uint64_t acc, double v)
     r[0] = bl[0];
     r[1] = bh[0] + bl[1] + 0xC0C80000u;                      // - 0x3F380000: the exponent word of C_LO
     return acc + __builtin_bit_cast(uint64_t, r);
-#endif
 }
 __device__ __forceinline__ uint64_t torus_from_double(double v) { return torus_acc(0, v); }
 

@@ -24,63 +24,18 @@
 #include "fft_dev.h"
 #include "kern_extprod.h"
 
-#ifndef BR16_MAC_PRIO
-#define BR16_MAC_PRIO 0
-#endif
-#ifndef BR16_EARLY
 #define BR16_EARLY 15      /* GGSW entries (of 25 per level; scaled to K1*K1) requested between the instructions of the transform's
                               second half.  Measured at 16,384 bits: 0 -> 267 ms, 12 -> 267, 13 -> 255, 14 -> 253, 15 -> 251.5, 16 -> 263,
                               20 -> 268, 25 -> 297 (spills past 18); some of them ahead of the tiles-free barrier, or the late ones
                               between the digit stores: no gain. */
-#endif
-#ifndef BR16_XPOSE_IN_TWIDDLE
-#define BR16_XPOSE_IN_TWIDDLE 1    /* with BR16_STORE_IN_PASS2: 239 -> 231 ms per 16,384-bit launch; either one alone: no change */
-#endif
-#ifndef BR16_STAGE_AT_END
-#define BR16_STAGE_AT_END 1
-#endif
-#ifndef BR16_HEAD
-#define BR16_HEAD 0        /* GGSW entries (of 25 per level) requested between the stages of pass 1 */
-#endif
-#ifndef BR16_LATE_IN_PASS2
-#define BR16_LATE_IN_PASS2 1
-#endif
-#ifndef BR16_READ_IN_PASS2
-#define BR16_READ_IN_PASS2 1
-#endif
-#ifndef BR16_STORE_IN_PASS2
-#define BR16_STORE_IN_PASS2 1
-#endif
-#ifndef BR16_PARK_AUX_ST
 #define BR16_PARK_AUX_ST 0 /* cache policy bits of the parking stores (1 = sc0, 2 = nt, 16 = sc1; measured: see DESIGN.md) */
-#endif
-#ifndef BR16_PARK_AUX_LD
 #define BR16_PARK_AUX_LD 2 /* ... and of the parking loads.  nt: the reload is the line's last use, it should not displace GGSW rows in L2.
                               Measured per 16,384-bit launch (rocprofv3 FETCH_SIZE x 2, same box): loads default 775 GB / 239 ms, nt 527 GB /
                               235 ms; stores sc1 or sc0+sc1 on top: no further change; nt STORES: 242-247 ms (slower), whatever the loads do */
-#endif
 #define BR16_PARK_WORDS_PER_WG (16 * EP_THREADS * 2)       /* 16 chunks of 16 bytes per thread (lo[a], hi[a]): 64 KB per workgroup */
-#ifndef BR16_PARK_OWNERS_ONLY
-#define BR16_PARK_OWNERS_ONLY 1   /* lane groups that own no polynomial (group 15 of a three-ciphertext unit, groups 10-15 of a two-ciphertext
-                                     one) park nothing: their buffer offset is out of range, so the store is dropped and the load returns 0
-                                     (round 3 stored and reloaded their 4 KB per group 669 times for nothing: 45 GB per launch) */
-#endif
-#ifndef BR16_W3_LDS_HOME
-#define BR16_W3_LDS_HOME 1        /* three-ciphertext units: the accumulators of wavefront 3 (groups 12-14) LIVE in LDS instead of the parking
-                                     slab -- see blind_rotate16_unit.  Needs 81,920 B of LDS per workgroup (two of them = all 160 KB of a CU);
-                                     the launcher falls back to the parked form if the runtime does not place two such workgroups on a CU */
-#endif
-#ifndef BR16_RESIDENT_HI
-#define BR16_RESIDENT_HI 0        /* 1: the upper halves hi[] of the (negated) accumulator stay in registers for the whole rotation; only lo[]
-                                     is parked (two coefficients per 16-byte chunk: 8 stores + 8 loads per lane and iteration instead of 16 + 16).
-                                     Costs 32 VGPRs, i.e. 8 of the 15 GGSW entries that BR16_EARLY keeps in flight across the transform */
-#endif
-#ifndef BR16_MAC_TAIL
-#define BR16_MAC_TAIL (BR16_RESIDENT_HI ? 5 : 0)   /* GGSW entries (of 25 per level) requested only after the multiply-accumulate has used row 0 */
-#endif
-#ifndef BR16_W1_LATE
-#define BR16_W1_LATE BR16_RESIDENT_HI
-#endif
+/* three-ciphertext units: the accumulators of wavefront 3 (groups 12-14) LIVE in LDS instead of the parking slab -- see
+   blind_rotate16_unit.  Needs 81,920 B of LDS per workgroup (two of them = all 160 KB of a CU); the launcher falls back to the parked
+   form if the runtime does not place two such workgroups on a CU */
 #define BR16_HOME_LDS_DOUBLES (2 * FHE_TW_ENTRIES + (EP_GROUPS - 1) * GROUP_TILE_DOUBLES + 3 * FHE_N)   /* table + 15 tiles + 3 accumulators = 81,920 B */
 
 __device__ __forceinline__ int br16_opaque_tid()
@@ -90,9 +45,6 @@ __device__ __forceinline__ int br16_opaque_tid()
     return t;
 }
 
-#ifndef BR16_PAD_DOUBLES
-#define BR16_PAD_DOUBLES 0     /* developer ablation: extra LDS so that only one workgroup fits a CU */
-#endif
 // One unit of work = R ciphertexts starting at `inst0`, one workgroup (the body of the kernel below).
 //
 // HOME (three-ciphertext units, R * K1 = 15): group 15 owns nothing and has always computed a duplicate of group 14 (same ciphertext,
@@ -134,10 +86,12 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
         }
         return reinterpret_cast<uint64_t *>(lds + gq * GROUP_TILE_DOUBLES);
     };
-    // byte offset of a lane in a parking chunk; lanes that park nothing get an out-of-range offset (raw buffer: dropped / zero)
+    // byte offset of a lane in a parking chunk; lanes that park nothing (group 15 of a three-ciphertext unit, groups 10-15 of a
+    // two-ciphertext one) get an out-of-range offset: the store is dropped and the load returns 0 (round 3 stored and reloaded
+    // their 4 KB per group 669 times for nothing: 45 GB per launch)
     auto park_lane = [&](const int tq) -> unsigned {
         if (HOME) return (tq >> 4) < HOME_G0 ? (unsigned)tq * 16u : 0x80000000u;              // wavefront 3 parks nothing
-        if (BR16_PARK_OWNERS_ONLY && R * K1 < EP_GROUPS) return (tq >> 4) < R * K1 ? (unsigned)tq * 16u : 0x80000000u;
+        if (R * K1 < EP_GROUPS) return (tq >> 4) < R * K1 ? (unsigned)tq * 16u : 0x80000000u;
         return (unsigned)tq * 16u;
     };
 
@@ -188,37 +142,21 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
         uint64_t *stage = stage_of(tq);
         stage[16 * a + (tq & 15)] = lo[a];
         stage[256 + 16 * a + (tq & 15)] = hi[a];
-#ifndef BR16_ABL_NOPARK
-#if BR16_RESIDENT_HI
-        if (a & 1) {                                             // compile-time: a is an unrolled loop index
-            ep_u32x4 v;
-            v[0] = (uint32_t)lo[a - 1]; v[1] = (uint32_t)(lo[a - 1] >> 32); v[2] = (uint32_t)lo[a]; v[3] = (uint32_t)(lo[a] >> 32);
-            __builtin_amdgcn_raw_buffer_store_b128(v, park_rsrc, park_lane(tq), park_wg + BR16_PARK_SLOT(a >> 1), BR16_PARK_AUX_ST);
-        }
-#else
         {                                                        // (wavefront 3 of a HOME unit: out of range, it has just written its home)
             ep_u32x4 v;
             v[0] = (uint32_t)lo[a]; v[1] = (uint32_t)(lo[a] >> 32); v[2] = (uint32_t)hi[a]; v[3] = (uint32_t)(hi[a] >> 32);
             __builtin_amdgcn_raw_buffer_store_b128(v, park_rsrc, park_lane(tq), park_wg + BR16_PARK_SLOT(a), BR16_PARK_AUX_ST);
         }
-#endif
-#endif
     };
-#if BR16_STAGE_AT_END
     {
         const int tq = br16_opaque_tid();
 #pragma unroll
         for (int a = 0; a < 16; ++a) stage_park(a, tq);
     }
-#endif
     for (uint32_t it = 0; it < A.iters; ++it) {
         const int t = mod_switch_1024(a_next);
         a_next = lwe[it + 1];                                    // one iteration ahead (the last one reads the body: unused)
-#ifdef BR16_ABL_SAMEKEY
-        const unsigned g_bytes = (it & 1) * GGSW_BYTES;          // developer ablation (wrong results): two L2-resident GGSWs = a 100 % L2 hit rate
-#else
         const unsigned g_bytes = it * GGSW_BYTES;                // wave-uniform byte offset of this iteration's GGSW
-#endif
 
         // ---- accumulator -> tile and parking slab; d = acc * X^t - acc; first (least significant) digit -----------
         uint32_t st_lo[16], st_hi[16];
@@ -229,10 +167,6 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
             const int tq = br16_opaque_tid();
             const int bq_ = tq & 15;
             uint64_t *stage = stage_of(tq);
-#if !BR16_STAGE_AT_END
-#pragma unroll
-            for (int a = 0; a < 16; ++a) stage_park(a, tq);
-#endif
             wave_lds_sync();
             fft_tw_load8(w0, tw, bq_, FHE_TW_STRIDE);             // first half of the lane's table column (T[0..7][b]): lands during the rotation
             __builtin_amdgcn_sched_barrier(0);
@@ -269,11 +203,7 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
         // One decomposition level.  On entry w0 / w1 hold (or are about to receive) the lane's table column, and xr/xi the digits.
         // `last`: the most significant level (the last one of the iteration): its multiply-accumulate also requests the parked
         // accumulator, a few chunks per row, instead of a burst of 16 loads behind it
-#if BR16_RESIDENT_HI
-        uint64_t pkl[16];                                         // the parked half (lo[]) on its way back
-#else
         ulonglong2 pk[16];
-#endif
         auto level_body = [&](const int l, const bool tiles_busy, auto last) {
             const int tq = br16_opaque_tid();
             const int bq_ = tq & 15;
@@ -285,79 +215,40 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
 #pragma unroll
                 for (int q = 0; q < K1 * K1; ++q) {
                     if (q < from || q >= to) continue;
-#ifdef BR16_ABL_HALFKEY
-                    if (q % K1 >= 3) continue;                    // developer ablation (wrong results): 60 % of the key bytes, same arithmetic
-#endif
-#ifdef BR16_ABL_NOLOAD
-                    bm[q / K1][q % K1] = make_double2((double)(tq + q), (double)(tq - q));
-#else
                     bm[q / K1][q % K1] = ep_key_load(bsk_rsrc, (unsigned)tq * 16u, gl_bytes + (unsigned)q * (FHE_H * 16));
-#endif
                 }
                 __builtin_amdgcn_sched_barrier(0);
             };
             // ---- forward transform (fft_dev.h): pass 1 (frequency offset 1/4, constants only), twiddle by the table column read a
             //      whole decomposition step ago, transpose, pass 2 ---------------------------------------------------------------
-#if !BR16_W1_LATE
             fft_tw_load8(w1, tw, 8 * FHE_TW_STRIDE + bq_, FHE_TW_STRIDE);   // second half of the column (T[8..15][b]): lands during pass 1
-#endif
             __builtin_amdgcn_sched_barrier(0);
-            // pass 1 is pure vector work (192 fused operations, no table): the first BR16_HEAD GGSW entries are requested between its
-            // stages, as many as the register file has room for while the table column and the working set are both live
-            constexpr int NH = BR16_HEAD * K1 * K1 / 25;
-#ifndef BR16_ABL_NOFFT
-            dft16<false, true>(xr, xi, [&](const int stage) { if (NH) { __builtin_amdgcn_sched_barrier(0); key_rows(NH * stage / 4, NH * (stage + 1) / 4); } });
-#else
-            key_rows(0, NH);
-#endif
+            dft16<false, true>(xr, xi);
             __builtin_amdgcn_sched_barrier(0);
-#if !BR16_XPOSE_IN_TWIDDLE
-            fft_tw_mul<false, 8>(xr, xi, w0);
-            fft_tw_mul<false, 8>(xr + 8, xi + 8, w1);
-#endif
             EP_STAMP(2);
             // The first BR16_EARLY entries are requested a few at a time BETWEEN the instructions of the transpose and of the
             // second DFT16, into the registers the twiddle buffers have just left: a burst of 25 loads blocks the in-order
             // wave for as long as the L1 takes to accept them (~150 cycles each with one workgroup per CU); spaced out,
             // the same acceptance time passes under the wave's own LDS and vector work.
-            constexpr int NE = BR16_EARLY * K1 * K1 / 25 > NH ? BR16_EARLY * K1 * K1 / 25 : NH, NHOOK = 7;
-            constexpr int NT = BR16_MAC_TAIL * K1 * K1 / 25;    // the last NT entries (of the last rows) are requested from inside the multiply-accumulate
-            auto early = [&](const int h) { key_rows(NH + (NE - NH) * h / NHOOK, NH + (NE - NH) * (h + 1) / NHOOK); };
+            constexpr int NE = BR16_EARLY * K1 * K1 / 25, NHOOK = 7;
+            auto early = [&](const int h) { key_rows(NE * h / NHOOK, NE * (h + 1) / NHOOK); };
             if (tiles_busy) wg_barrier_lds_only();                // every thread is done reading the previous level's digits
             EP_STAMP(3);
-#if defined(BR16_ABL_NOFFT)
-            group_transpose(xr, xi, tile, bq_);
-            key_rows(0, NE);
-#elif defined(BR16_ABL_NOXPOSE)
-            dft16<false, false>(xr, xi);
-            key_rows(0, NE);
-#else
             {
-#if FFT_XPOSE_PRIO
                 __builtin_amdgcn_s_setprio(FFT_XPOSE_PRIO);
-#endif
 #pragma unroll
                 for (int k1 = 0; k1 < 16; ++k1) {
-#if BR16_W1_LATE
-                    // the second half of the table column is requested only now (it lands during the first eight multiplies): while pass 1
-                    // runs the registers hold one half of the column, not both
-                    if (k1 == 0) { fft_tw_load8(w1, tw, 8 * FHE_TW_STRIDE + bq_, FHE_TW_STRIDE); __builtin_amdgcn_sched_barrier(0); }
-#endif
-#if BR16_XPOSE_IN_TWIDDLE
                     // each value leaves for the transpose tile as soon as its twiddle multiply is done: 16 stores spread over 64
-                    // vector instructions instead of a burst
+                    // vector instructions instead of a burst (together with the digit stores from inside pass 2, below: 239 -> 231 ms
+                    // per 16,384-bit launch; either one alone: no change)
                     if (k1 < 8) cmul(xr[k1], xi[k1], w0[k1].x, w0[k1].y); else cmul(xr[k1], xi[k1], w1[k1 - 8].x, w1[k1 - 8].y);
-#endif
                     double2 v; v.x = xr[k1]; v.y = xi[k1];
                     *reinterpret_cast<double2 *>(tile + 2 * (k1 * 17 + bq_)) = v;
-#if BR16_XPOSE_IN_TWIDDLE
                     if ((k1 & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-#endif
                     if (NE && k1 == 7) { __builtin_amdgcn_sched_barrier(0); early(0); }
                 }
                 if (NE) { __builtin_amdgcn_sched_barrier(0); early(1); }
                 wave_lds_sync();
-#if BR16_READ_IN_PASS2 && BR16_STORE_IN_PASS2
                 // transposed reads in the order the first butterfly stage consumes them (registers fft_reg(0), fft_reg(1), ...), and
                 // NO wait behind them: the butterflies start as the pairs arrive.  The group's reads must all have been issued and
                 // returned before its first digit store reuses the tile: that wait sits in front of that store (stage 3), by when it is free.
@@ -368,27 +259,13 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
                     xr[c] = v.x; xi[c] = v.y;
                 }
                 if (NE) { __builtin_amdgcn_sched_barrier(0); early(2); }
-#else
-#pragma unroll
-                for (int c = 0; c < 16; ++c) {
-                    double2 v = *reinterpret_cast<const double2 *>(tile + 2 * (bq_ * 17 + c));
-                    xr[c] = v.x; xi[c] = v.y;
-                }
-                if (NE) { __builtin_amdgcn_sched_barrier(0); early(2); }
-                wave_lds_sync();
-#endif
-#if FFT_XPOSE_PRIO
                 __builtin_amdgcn_s_setprio(0);
-#endif
-#if BR16_STORE_IN_PASS2
                 // the transformed digits leave for the tile as the last butterfly stage produces them (outputs k and k + 8 of butterfly
                 // k), instead of as a burst of 16 stores behind the transform: the LDS queue is what the waves of a CU wait for most
                 dft16<false, false>(xr, xi, [&](const int stage) { if (NE) { __builtin_amdgcn_sched_barrier(0); early(3 + stage); } },
                                     [&](const int stage, const int c0) {
                                         if (stage != 3) return;
-#if BR16_READ_IN_PASS2
                                         if (c0 == 0) wave_lds_sync();      // every lane of the group has its transposed values (see the reads)
-#endif
 #pragma unroll
                                         for (int j = 0; j < FFT_CHUNK; ++j) {
 #pragma unroll
@@ -399,41 +276,20 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
                                             }
                                         }
                                         __builtin_amdgcn_sched_barrier(0);
-#if BR16_LATE_IN_PASS2
                                         // ... and the registers of the values just stored take the next share of the remaining GGSW entries
                                         {
-                                            constexpr int NL = K1 * K1 - NE - NT, PARTS = 8 / FFT_CHUNK;
+                                            constexpr int NL = K1 * K1 - NE, PARTS = 8 / FFT_CHUNK;
                                             const int part = c0 / FFT_CHUNK;
                                             key_rows(NE + NL * part / PARTS, NE + NL * (part + 1) / PARTS);
                                         }
-#endif
                                     });
-#else
-                dft16<false, false>(xr, xi, [&](const int stage) { if (NE) { __builtin_amdgcn_sched_barrier(0); early(3 + stage); } });
-#endif
             }
-#endif
             EP_STAMP(4);
-            // store the transformed digits, then request the remaining GGSW entries of this level into the registers the
-            // working set has just left
-#if !BR16_STORE_IN_PASS2 || defined(BR16_ABL_NOFFT) || defined(BR16_ABL_NOXPOSE)
-#pragma unroll
-            for (int k2 = 0; k2 < 16; ++k2) {
-                double2 v; v.x = xr[k2]; v.y = xi[k2];
-                *reinterpret_cast<double2 *>(tile + 2 * (bq_ + 16 * k2)) = v;
-            }
-#endif
             __builtin_amdgcn_sched_barrier(0);
-#if !(BR16_LATE_IN_PASS2 && BR16_STORE_IN_PASS2) || defined(BR16_ABL_NOFFT) || defined(BR16_ABL_NOXPOSE)
-            key_rows(NE, K1 * K1 - NT);
-#endif
             EP_STAMP(5);
             wg_barrier_lds_only();                                // digits of all groups visible; key loads stay in flight
             EP_STAMP(6);
             // ---- multiply-accumulate role: thread tq owns Fourier point tq; digits are read one row ahead ---------------
-#if BR16_MAC_PRIO
-            __builtin_amdgcn_s_setprio(BR16_MAC_PRIO);
-#endif
             double2 dn[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) dn[r] = *reinterpret_cast<const double2 *>(lds + (r * K1) * GROUP_TILE_DOUBLES + 2 * tq);
@@ -447,18 +303,11 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
                     for (int r = 0; r < R; ++r) dn[r] = *reinterpret_cast<const double2 *>(lds + (r * K1 + p + 1) * GROUP_TILE_DOUBLES + 2 * tq);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-#ifdef BR16_ABL_NOMAC
-                if (p == 0)
-#endif
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
 #pragma unroll
                     for (int c = 0; c < K1; ++c) {
-#ifdef BR16_ABL_HALFKEY
-                        const double2 kq = bm[p][c >= 3 ? c - 3 : c];
-#else
                         const double2 kq = bm[p][c];
-#endif
                         fr[r][c] = __builtin_fma(d[r].x, kq.x, fr[r][c]);
                         fr[r][c] = __builtin_fma(-d[r].y, kq.y, fr[r][c]);
                         fi[r][c] = __builtin_fma(d[r].x, kq.y, fi[r][c]);
@@ -466,24 +315,8 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if (NT && p == 0) key_rows(K1 * K1 - NT, K1 * K1);      // into the registers row 0 has just left
                 if constexpr (decltype(last)::value) {
                     // parked accumulator back: lands during the products exchange and the inverse transform
-#if BR16_RESIDENT_HI
-#pragma unroll
-                    for (int j = 8 * p / K1; j < 8 * (p + 1) / K1; ++j) {
-#ifdef BR16_ABL_NOPARK
-                        pkl[2 * j] = 0; pkl[2 * j + 1] = 0;
-#else
-                        const ep_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(park_rsrc, park_lane(tq), park_wg + BR16_PARK_SLOT(j), BR16_PARK_AUX_LD);
-                        pkl[2 * j] = ((unsigned long long)v[1] << 32) | v[0];
-                        pkl[2 * j + 1] = ((unsigned long long)v[3] << 32) | v[2];
-#endif
-                    }
-#elif defined(BR16_ABL_NOPARK)
-#pragma unroll
-                    for (int a = 16 * p / K1; a < 16 * (p + 1) / K1; ++a) { pk[a].x = 0; pk[a].y = 0; }
-#else
                     {
 #pragma unroll
                         for (int a = 16 * p / K1; a < 16 * (p + 1) / K1; ++a) {
@@ -492,13 +325,9 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
                             pk[a].y = ((unsigned long long)v[3] << 32) | v[2];
                         }
                     }
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-#if BR16_MAC_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
             EP_STAMP(7);
         };
 
@@ -544,7 +373,6 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
         // inverse transform (fft_dev.h's nega_inv, the table row read a pass ahead)
         dft16<true, false>(xr, xi);
         __builtin_amdgcn_sched_barrier(0);
-#if BR16_XPOSE_IN_TWIDDLE
         // as in the forward transform: every value leaves for the transpose tile as soon as its twiddle multiply is done
 #pragma unroll
         for (int c = 0; c < 16; ++c) {
@@ -560,45 +388,26 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
             double2 v = *reinterpret_cast<const double2 *>(tile + 2 * (bq_ * 17 + c));
             xr[c] = v.x; xi[c] = v.y;
         }
-#else
-        fft_tw_mul<true, 8>(xr, xi, w0, 1);
-        fft_tw_mul<true, 8>(xr + 8, xi + 8, w1);
-        __builtin_amdgcn_sched_barrier(0);
-        group_transpose(xr, xi, tile, bq_);
-#endif
         if (home_wave) {
             // wavefront 3 of a HOME unit: the old accumulator comes from its LDS home (the lane's own coefficients: written by this
             // lane, no synchronisation needed), landing during the transform's last pass
             const uint64_t *home = stage_of(tq);
 #pragma unroll
-#if BR16_RESIDENT_HI
-            for (int a = 0; a < 16; ++a) pkl[a] = home[16 * a + bq_];
-#else
             for (int a = 0; a < 16; ++a) { pk[a].x = home[16 * a + bq_]; pk[a].y = home[256 + 16 * a + bq_]; }
-#endif
         }
         dft16<true, false>(xr, xi);
 #pragma unroll
         for (int a = 1; a < 16; ++a) cmulc(xr[a], xi[a], FHE_PSI16_RE[a], FHE_PSI16_IM[a]);
         EP_STAMP(9);
-#if BR16_STAGE_AT_END
         wave_lds_sync();     // the inverse transform's transposed reads of this tile are complete in every lane of the group
-#endif
 #pragma unroll
         for (int a = 0; a < 16; ++a) {
-#if BR16_RESIDENT_HI
-            lo[a] = torus_acc(pkl[a], -xr[a]);                // negated accumulator: -(acc + r) = -acc + (-r)
-            hi[a] = torus_acc(hi[a], -xi[a]);
-#else
             lo[a] = torus_acc(pk[a].x, -xr[a]);               // negated accumulator: -(acc + r) = -acc + (-r)
             hi[a] = torus_acc(pk[a].y, -xi[a]);
-#endif
-#if BR16_STAGE_AT_END
             // ... and leaves for the tile and the parking slab at once: 16 LDS + 16 memory stores spread over the conversion's
             // vector work instead of a burst at the top of the next iteration (the last iteration's copies are never read)
             stage_park(a, tq);
             if ((a & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         EP_STAMP(10);
     }
@@ -641,8 +450,8 @@ __device__ __forceinline__ void blind_rotate16_unit(const ExtProdArgs &A, double
 template <int K1, int LEVELS, int BASE_LOG, int R, int R2 = 0, bool HOME = false>
 __global__ __launch_bounds__(EP_THREADS, 2) void blind_rotate16_kernel(const ExtProdArgs A)
 {
-    constexpr int LDS_DOUBLES = HOME ? BR16_HOME_LDS_DOUBLES : EP_LDS_DOUBLES + BR16_PAD_DOUBLES;
-    static_assert(LDS_DOUBLES >= EP_LDS_DOUBLES && (BR16_PAD_DOUBLES > 0 || LDS_DOUBLES * 8 <= 81920), "two workgroups must fit the 160 KB of a CU");
+    constexpr int LDS_DOUBLES = HOME ? BR16_HOME_LDS_DOUBLES : EP_LDS_DOUBLES;
+    static_assert(LDS_DOUBLES >= EP_LDS_DOUBLES && LDS_DOUBLES * 8 <= 81920, "two workgroups must fit the 160 KB of a CU");
     __shared__ __attribute__((aligned(16))) double lds_all[LDS_DOUBLES];
     if constexpr (R2 > 0) {
         if (blockIdx.x >= A.units_main) {       // scalar branch

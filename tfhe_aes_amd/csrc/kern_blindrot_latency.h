@@ -14,9 +14,8 @@
 //   groups 0..K1-1          inverse transform of output polynomial c, accumulate into LDS.
 // Round 2: the chain of an iteration was dominated by exposed round trips, not by arithmetic -- 25 dependent GGSW
 // row fetches with two rows in flight (~600 cycles each), and one LDS table read in flight per twiddle multiply.  Now
-//   * (rounds 2-5) the K1 rows of the first level of the multiply-accumulate were requested at the TOP of the iteration and one level
-//     stayed in flight afterwards; round 6 (BL_ROWS_AHEAD = 3, below): nothing is held across the transform, three levels of rows
-//     are requested at once behind it -- one exposed L2 round trip per iteration instead of one per level;
+//   * nothing is held across the transform, three levels of rows are requested at once behind it (BL_ROWS_AHEAD, below) -- one
+//     exposed L2 round trip per iteration instead of one per level;
 //   * the multiply-accumulate is split by output column over all 512 threads (3 + 2 columns), halving its length and
 //     the registers a row occupies; key rows come through raw buffer loads with scalar row offsets;
 //   * the transform's table entries are read as one batch, a whole pass ahead of their use (fft_dev.h);
@@ -29,18 +28,12 @@
 #include "kern_extprod.h"
 
 #define BL_THREADS 512
-#ifndef BL_L2_PREFETCH
-#define BL_L2_PREFETCH 1
-#endif
-#ifndef BL_ROWS_AHEAD
-#define BL_ROWS_AHEAD 3      /* levels of GGSW rows in flight during the multiply-accumulate.  1 (rounds 2-5): the first level requested at the top of the
-                                iteration (its registers live through the rotation and the transform), level k+1 requested while level k is used -- the
-                                stamps of round 6 (profiles/r06_latency_stamps_before.txt) show the phase waiting a whole (hot-spotted: every workgroup walks
-                                the same rows at the same time) L2 round trip per level: 9.7 k of an iteration's 25.6 k cycles for 300 fused
-                                multiply-adds per thread.  3: nothing is held across the transform; when its registers are free the rows of levels
-                                0, 1 and 2 are requested at once (three register sets), level k+3 refills the set level k has just left, row by row:
-                                one exposed round trip per iteration instead of five */
-#endif
+#define BL_ROWS_AHEAD 3      /* levels of GGSW rows in flight during the multiply-accumulate: nothing is held across the transform; when its registers
+                                are free the rows of levels 0, 1 and 2 are requested at once (three register sets), level k+3 refills the set level k
+                                has just left, row by row: one exposed L2 round trip per iteration.  With one level in flight (rounds 2-5) the stamps
+                                of round 6 (profiles/r06_latency_stamps_before.txt) show the phase waiting a whole (hot-spotted: every workgroup walks
+                                the same rows at the same time) round trip per level: 9.7 k of an iteration's 25.6 k cycles for 300 fused
+                                multiply-adds per thread */
 
 template <int K1, int LEVELS, int BASE_LOG>
 __global__ __launch_bounds__(BL_THREADS, 2) void blind_rotate_latency_kernel(const ExtProdArgs A)
@@ -91,29 +84,12 @@ __global__ __launch_bounds__(BL_THREADS, 2) void blind_rotate_latency_kernel(con
 #endif
 
     unsigned pf_sink = 0;
-    // One level of GGSW rows in flight per thread: (Fourier point tid mod 256) x (this half's share of the columns).  The rows of
-    // the first level of iteration it+1 do not depend on data: they are requested at the end of iteration it (and here for it = 0).
-#if BL_ROWS_AHEAD != 3
-    double2 bq[1][K1][CA];
-#endif
+    // GGSW rows per thread: (Fourier point tid mod 256) x (this half's share of the columns)
     const unsigned col_bytes = half_b ? (unsigned)CA * (FHE_H * 16) : 0u;      // wave-uniform
-#if BL_ROWS_AHEAD != 3
-    auto load_row = [&](unsigned gb, unsigned mp_, int k, int p, double2 (&dst)[CA]) {
-#pragma unroll
-        for (int c = 0; c < CA; ++c)
-            if (c < CB || !half_b) dst[c] = ep_key_load(bsk_rsrc, mp_ * 16u, gb + row_bytes(k, p) + col_bytes + (unsigned)c * (FHE_H * 16));
-    };
-#pragma unroll
-    for (int p = 0; p < K1; ++p) load_row(0u, (unsigned)(tid & 255), 0, p, bq[0][p]);
-#endif
     for (uint32_t it = 0; it < A.iters; ++it) {
         const int t = mod_switch_1024(a_next);
         a_next = lwe[it + 1];                          // one iteration ahead (the last one reads the body: unused)
-#ifdef BL_ABL_SAMEKEY
-        const unsigned g_bytes = 0, g_next = 0;        // developer ablation (wrong results): every iteration reads GGSW 0, L2-resident
-#else
         const unsigned g_bytes = it * GGSW_BYTES, g_next = g_bytes + GGSW_BYTES;
-#endif
         int tq = tid;
         asm volatile("" : "+v"(tq));                   // addresses below are recomputed from this, not kept across iterations
         const int bq_ = tq & 15, mp = tq & 255;
@@ -147,7 +123,6 @@ __global__ __launch_bounds__(BL_THREADS, 2) void blind_rotate_latency_kernel(con
         EP_STAMP(1);
         wg_barrier_lds_only();                         // digits of every level in place
         EP_STAMP(11);
-#if BL_L2_PREFETCH
         // ---- 1c. in a small batch every workgroup is at the same iteration, so the first touch of a GGSW would be a DRAM round trip
         //      on the multiply-accumulate's critical path.  The workgroups that share an XCD (dealt to the 8 XCDs round-robin) walk
         //      the NEXT iteration's GGSW between them, one dword per 128-byte line, an iteration ahead of its use.  Nobody waits
@@ -163,7 +138,6 @@ __global__ __launch_bounds__(BL_THREADS, 2) void blind_rotate_latency_kernel(con
                 if ((unsigned)i * nshare < 8u)
                     pf[i] = __builtin_amdgcn_raw_buffer_load_b32(bsk_rsrc, (mine + nshare * ((unsigned)tq + 512u * i)) * 128u, g_next, 0);
         }
-#endif
         // ---- 1b. every (level, polynomial) group transforms its digit polynomial ------------------------------------------
         if (transform) {
             double xr[16], xi[16];
@@ -181,7 +155,6 @@ __global__ __launch_bounds__(BL_THREADS, 2) void blind_rotate_latency_kernel(con
                 *reinterpret_cast<double2 *>(tile + 2 * (bq_ + 16 * k2)) = v;
             }
         }
-#if BL_ROWS_AHEAD == 3
         // ---- 2. multiply-accumulate: all 512 threads, one Fourier point and a share of the columns each.  The two halves of the
         //      workgroup own 3 and 2 columns (k + 1 = 5): each half runs its OWN copy of the phase with the column count a compile-time
         //      constant and its own row registers (with one shared copy and a per-column `if (half_b)` the compiler sinks the conditional
@@ -234,44 +207,8 @@ __global__ __launch_bounds__(BL_THREADS, 2) void blind_rotate_latency_kernel(con
             for (int k = 0; k < LEVELS; ++k) mac_level(k, rows[k % 3]);
         };
         if (half_b) mac_phase(std::integral_constant<int, CB>{}); else mac_phase(std::integral_constant<int, CA>{});
-#else
-        EP_STAMP(3);
-        wg_barrier_lds_only();                         // digits visible; the key loads stay in flight
-        EP_STAMP(4);
-        // ---- 2. multiply-accumulate: all 512 threads, one Fourier point and a share of the columns each ---------------
-        double fr[CA], fi[CA];
-#pragma unroll
-        for (int c = 0; c < CA; ++c) { fr[c] = 0.0; fi[c] = 0.0; }
-#pragma unroll 1
-        for (int k = 0; k < LEVELS; ++k) {
-            const double *dl = lds + (size_t)k * K1 * GROUP_TILE_DOUBLES + 2 * mp;      // digits of chain level k
-            double2 dn = *reinterpret_cast<const double2 *>(dl);
-#pragma unroll
-            for (int p = 0; p < K1; ++p) {
-                double2 bv[CA];
-#pragma unroll
-                for (int c = 0; c < CA; ++c) bv[c] = bq[0][p][c];
-                if (k + 1 < LEVELS) load_row(g_bytes, (unsigned)mp, k + 1, p, bq[0][p]);      // the same row of the next level, one level ahead
-                const double2 d = dn;
-                if (p + 1 < K1) dn = *reinterpret_cast<const double2 *>(dl + (p + 1) * GROUP_TILE_DOUBLES);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int c = 0; c < CA; ++c) {
-                    if (c < CB || !half_b) {
-                        fr[c] = __builtin_fma(d.x, bv[c].x, fr[c]);
-                        fr[c] = __builtin_fma(-d.y, bv[c].y, fr[c]);
-                        fi[c] = __builtin_fma(d.x, bv[c].y, fi[c]);
-                        fi[c] = __builtin_fma(d.y, bv[c].x, fi[c]);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#endif
-#if BL_L2_PREFETCH
 #pragma unroll
         for (int i = 0; i < 8; ++i) pf_sink ^= pf[i];
-#endif
         EP_STAMP(5);
         wg_barrier_lds_only();                         // all digits consumed: tiles 0..K1-1 may take the products
         EP_STAMP(6);
@@ -282,13 +219,6 @@ __global__ __launch_bounds__(BL_THREADS, 2) void blind_rotate_latency_kernel(con
                 *reinterpret_cast<double2 *>(lds + ((half_b ? CA : 0) + c) * GROUP_TILE_DOUBLES + 2 * mp) = v;
             }
         }
-#if BL_ROWS_AHEAD != 3
-        // the first level's rows of the NEXT iteration: every row register is free again
-        if (it + 1 < A.iters) {
-#pragma unroll
-            for (int p = 0; p < K1; ++p) load_row(g_next, (unsigned)mp, 0, p, bq[0][p]);
-        }
-#endif
         EP_STAMP(7);
         wg_barrier_lds_only();
         EP_STAMP(8);

@@ -13,7 +13,7 @@
 //     A thread therefore needs 15 of the 25 GGSW entries of a level, every entry it fetches serves 2R (or R) ciphertexts, and the
 //     CU pulls 60 % of the bytes through its vector-memory path that two independent workgroups pull (the column-4 rows twice, the
 //     second time out of L1).  It reads twice the digits from LDS instead (3.6 pJ/B against 12 pJ/B for an L2 hit, 39-100 beyond).
-//   * 15 entries in flight instead of 25 frees 40 VGPRs: the upper halves hi[] of the accumulator stay in registers (BRP_RESIDENT_HI),
+//   * 15 entries in flight instead of 25 frees 40 VGPRs: the upper halves hi[] of the accumulator stay in registers,
 //     only lo[] is parked -- and the wavefronts 3 and 7 park nothing at all: as in kern_blindrot16.h's HOME form, group 15 of a half
 //     mirrors group 14 (same tile, same values), and the LDS that leaves free (2 tiles + what one workgroup per CU does not use) is
 //     the permanent home of the six accumulators of those two wavefronts.
@@ -26,21 +26,10 @@
 #include "kern_blindrot16.h"
 
 #define BRP_THREADS 512
-#ifndef BRP_EARLY
 #define BRP_EARLY 9          /* GGSW entries (of 15 per thread and level) requested between the instructions of the transform's second half
                                 (6 / 8 / 9 / 10 / 12: 218.6 / 215.4 / 215.1 / 214.1 / 216.8 ms per 16,384-bit launch; 12 spills 4 registers) */
-#endif
-#ifndef BRP_TAIL
 #define BRP_TAIL 4           /* ... requested only after the multiply-accumulate has used row 0, into the registers that row has left
                                 (0 / 2 / 3 / 4 / 5 / 6 on one box: 214.4 / 210.1 / 211.3 / 209.8 / 210.5 / 213.2 ms; on a slower one 220.4 / 218.8 for 0 / 4) */
-#endif
-#ifndef BRP_RESIDENT_HI
-#define BRP_RESIDENT_HI 1
-#endif
-#ifndef BRP_W1_LATE
-#define BRP_W1_LATE 2           /* 1: second half of the table column requested at the start of the twiddle pass; 2: in two requests of four entries, each
-                                into registers the first half has just left (no spill with hi[] resident: 249 VGPRs) */
-#endif
 // Parking slots (round 6).  The parked half of the accumulator lives in a slab of 64 KB slots.  A workgroup's slot is either
 //   * CLAIMED (ExtProdArgs::park_owner != null, the default): the first BRP_PARK_SLOTS = 8 x 128 slots are shared by all generations of
 //     all launches -- 128 per XCC (HW_REG_XCC_ID: only that XCC's L2 ever caches a slot's lines, so a slot never needs a cross-XCC
@@ -69,24 +58,12 @@
 #define BRP_PARK_SLOTS 1024
 #define BRP_SLOTS_PER_XCC 128
 #define BRP_PARK_TAIL_WORDS 3  /* uint64 words behind the owner words: [0] fallbacks to a private slot, [1] ownership violations, [2] record pointer */
-#ifndef BRP_MAC_PRIO
 #define BRP_MAC_PRIO 1       /* wave priority during the multiply-accumulate (0 / 1 / 3: 214.2 / 211.8 / 212.0 ms per 16,384-bit launch) */
-#endif
-#ifndef BRP_CHUNK
 #define BRP_CHUNK 1          /* butterflies issued together in this kernel's transforms (fft_dev.h dft16; 1 / 2 / 4 / 8: 211.5 / 214.4 / 214.2 / 223.4 ms) */
-#endif
-#ifndef BRP_SKIP_IDLE_WAVES
-#define BRP_SKIP_IDLE_WAVES 1 /* four-ciphertext units (R = 2): the last wavefront of either half (lane groups 12-15) owns no polynomial -- it is needed for
-                                the multiply-accumulate (every thread owns a Fourier point) and for the products exchange, but its rotation, transforms
-                                and conversion work on nothing.  1: those two wavefronts run their OWN iteration body (the same barriers, their key
-                                rows, the multiply-accumulate, the exchange; a wave-uniform branch at the top of the iteration) -- one generation of
-                                eleven in a 16,384-bit launch, one of three in a 4,096-bit one.  The six-ciphertext body is not touched (its one idle
-                                group shares a wavefront with three busy ones) */
-#endif
 #define BRP_HALF_TILES (EP_GROUPS - 1)                                                   /* 15 tiles per half: group 15 shares group 14's */
 #define BRP_LDS_DOUBLES(R) (2 * FHE_TW_ENTRIES + 2 * BRP_HALF_TILES * GROUP_TILE_DOUBLES + ((R) == 3 ? 6 * FHE_N : 0))   /* R = 3: 159,488 B */
 #define BRP_LDS_EXTRA_DOUBLES 2                                                          /* + the claimed parking slot, broadcast to the eight wavefronts, and its owner value */
-#define BRP_PARK_WORDS_PER_HALF (BRP_RESIDENT_HI ? 8 * EP_THREADS * 2 : 16 * EP_THREADS * 2)   /* per half and iteration: 32 KB (lo[] only) or 64 KB */
+#define BRP_PARK_WORDS_PER_HALF (8 * EP_THREADS * 2)                                     /* per half and iteration: 32 KB (lo[] only) */
 
 __device__ __forceinline__ int brp_opaque_tid()
 {
@@ -117,8 +94,12 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
     const int r_own = owner ? g / K1 : R - 1;
     const int p_own = owner ? g % K1 : K1 - 1;
     const bool home_wave = HOME && __builtin_amdgcn_readfirstlane(tq0) >= 16 * HOME_G0;
-    // wave-uniform: this wavefront's four lane groups own no polynomial (R = 2: groups 12..15 of either half)
-    const bool idle_wave = BRP_SKIP_IDLE_WAVES && R * K1 <= 12 && __builtin_amdgcn_readfirstlane(tq0) >= 16 * 12;
+    // wave-uniform: this wavefront's four lane groups own no polynomial (R = 2: groups 12..15 of either half).  It is needed for the
+    // multiply-accumulate (every thread owns a Fourier point) and for the products exchange, but its rotation, transforms and
+    // conversion would work on nothing: it runs its OWN iteration body (the same barriers, its key rows, the multiply-accumulate, the
+    // exchange; a wave-uniform branch at the top of the iteration) -- one generation of eleven in a 16,384-bit launch, one of three
+    // in a 4,096-bit one.  The six-ciphertext body is not touched (its one idle group shares a wavefront with three busy ones)
+    const bool idle_wave = R * K1 <= 12 && __builtin_amdgcn_readfirstlane(tq0) >= 16 * 12;
     double *ldsh = lds + hh * (BRP_HALF_TILES * GROUP_TILE_DOUBLES);                      // this half's tiles (scalar)
     double *ldso = lds + (1 - hh) * (BRP_HALF_TILES * GROUP_TILE_DOUBLES);                // the other half's
     auto tile_of = [&](const int tq) -> double * {
@@ -204,19 +185,11 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
         uint64_t *stage = stage_of(tq);
         stage[16 * a + (tq & 15)] = lo[a];
         stage[256 + 16 * a + (tq & 15)] = hi[a];
-#if BRP_RESIDENT_HI
         if (a & 1) {
             ep_u32x4 v;
             v[0] = (uint32_t)lo[a - 1]; v[1] = (uint32_t)(lo[a - 1] >> 32); v[2] = (uint32_t)lo[a]; v[3] = (uint32_t)(lo[a] >> 32);
             __builtin_amdgcn_raw_buffer_store_b128(v, park_rsrc, park_lane(tq), park_wg + BRP_PARK_SLOT(a >> 1), BR16_PARK_AUX_ST);
         }
-#else
-        {
-            ep_u32x4 v;
-            v[0] = (uint32_t)lo[a]; v[1] = (uint32_t)(lo[a] >> 32); v[2] = (uint32_t)hi[a]; v[3] = (uint32_t)(hi[a] >> 32);
-            __builtin_amdgcn_raw_buffer_store_b128(v, park_rsrc, park_lane(tq), park_wg + BRP_PARK_SLOT(a), BR16_PARK_AUX_ST);
-        }
-#endif
     };
     if (!idle_wave) {
         const int tq = brp_opaque_tid() & 255;
@@ -233,7 +206,7 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
         const unsigned g_bytes = it * GGSW_BYTES;
 
         if (idle_wave) {
-            // ---- a wavefront without polynomials (BRP_SKIP_IDLE_WAVES): the barriers of the others, its key rows, its share of the
+            // ---- a wavefront without polynomials (idle_wave): the barriers of the others, its key rows, its share of the
             //      multiply-accumulate and of the products exchange -- nothing else.  Same sums in the same order as level_body below ----
             const int tq = brp_opaque_tid() & 255;
             double g2r[RT][2], g2i[RT][2], g4r[R], g4i[R];
@@ -346,11 +319,7 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
 #pragma unroll
         for (int r = 0; r < R; ++r) { f4r[r] = 0.0; f4i[r] = 0.0; }
 
-#if BRP_RESIDENT_HI
         uint64_t pkl[16];
-#else
-        ulonglong2 pk[16];
-#endif
         auto level_body = [&](const int l, const bool tiles_busy, auto last) {
             const int tq = brp_opaque_tid() & 255;
             const int bq_ = tq & 15;
@@ -374,9 +343,6 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
                 }
                 __builtin_amdgcn_sched_barrier(0);
             };
-#if !BRP_W1_LATE
-            fft_tw_load8(w1, tw, 8 * FHE_TW_STRIDE + bq_, FHE_TW_STRIDE);
-#endif
             __builtin_amdgcn_sched_barrier(0);
             dft16<false, true, BRP_CHUNK>(xr, xi);
             __builtin_amdgcn_sched_barrier(0);
@@ -388,22 +354,17 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
 #endif
             EP_STAMP(3);
             {
-#if FFT_XPOSE_PRIO
                 __builtin_amdgcn_s_setprio(FFT_XPOSE_PRIO);
-#endif
 #pragma unroll
                 for (int k1 = 0; k1 < 16; ++k1) {
-#if BRP_W1_LATE == 1
-                    if (k1 == 0) { fft_tw_load8(w1, tw, 8 * FHE_TW_STRIDE + bq_, FHE_TW_STRIDE); __builtin_amdgcn_sched_barrier(0); }
-#elif BRP_W1_LATE == 2
                     // the second half of the table column in two requests of four entries, each into registers the first half has just left
+                    // (no spill with hi[] resident: 249 VGPRs)
                     if (k1 == 3 || k1 == 7) {
                         const int e0 = k1 == 3 ? 0 : 4;
 #pragma unroll
                         for (int e = e0; e < e0 + 4; ++e) w1[e] = tw[(8 + e) * FHE_TW_STRIDE + bq_];
                         __builtin_amdgcn_sched_barrier(0);
                     }
-#endif
 #ifdef BRP_ABL_FEWCMUL
                     if (k1 % 3 != 0 || k1 == 0)      // timing proxy: 5 of the 16 twiddle multiplies (20 of a transform's 404 f64 instructions) left out
 #endif
@@ -430,9 +391,7 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
                 }
 #endif
                 if (NE) { __builtin_amdgcn_sched_barrier(0); early(2); }
-#if FFT_XPOSE_PRIO
                 __builtin_amdgcn_s_setprio(0);
-#endif
                 dft16<false, false, BRP_CHUNK>(xr, xi, [&](const int stage) { if (NE) { __builtin_amdgcn_sched_barrier(0); early(3 + stage); } },
                                     [&](const int stage, const int c0) {
                                         if (stage != 3) return;
@@ -467,9 +426,7 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
             EP_STAMP(6);
             // ---- multiply-accumulate: thread (hh, tq) owns Fourier point tq; digits of row p for the RT ciphertexts, one row ahead ----
             // local ciphertext r': r' < R in this half's tiles, r' >= R in the other half's (tile (r' mod R) * K1 + p of that half)
-#if BRP_MAC_PRIO
             __builtin_amdgcn_s_setprio(BRP_MAC_PRIO);
-#endif
             const double *own = ldsh + 2 * tq, *oth = ldso + 2 * tq;
             double2 dn[RT];
 #pragma unroll
@@ -510,7 +467,6 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
                 if (NT && p == 0) key_rows(NQ - NT, NQ);
                 if constexpr (decltype(last)::value) {
                     // parked accumulator back: lands during the products exchange and the inverse transform
-#if BRP_RESIDENT_HI
 #pragma unroll
                     for (int j = 8 * p / K1; j < 8 * (p + 1) / K1; ++j) {
 #ifdef BR16_ABL_NOPARK
@@ -521,20 +477,10 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
                         pkl[2 * j + 1] = ((unsigned long long)v[3] << 32) | v[2];
 #endif
                     }
-#else
-#pragma unroll
-                    for (int a = 16 * p / K1; a < 16 * (p + 1) / K1; ++a) {
-                        const ep_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(park_rsrc, park_lane(tq), park_wg + BRP_PARK_SLOT(a), BR16_PARK_AUX_LD);
-                        pk[a].x = ((unsigned long long)v[1] << 32) | v[0];
-                        pk[a].y = ((unsigned long long)v[3] << 32) | v[2];
-                    }
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-#if BRP_MAC_PRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
             EP_STAMP(7);
         };
 
@@ -616,11 +562,7 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
             // a home wavefront: the old accumulator (the lane's own coefficients) comes from its LDS home
             const uint64_t *home = stage_of(tq);
 #pragma unroll
-#if BRP_RESIDENT_HI
             for (int a = 0; a < 16; ++a) pkl[a] = home[16 * a + bq_];
-#else
-            for (int a = 0; a < 16; ++a) { pk[a].x = home[16 * a + bq_]; pk[a].y = home[256 + 16 * a + bq_]; }
-#endif
         }
         dft16<true, false, BRP_CHUNK>(xr, xi);
         // conj psi^(16a) with the back-conversion's 2^-72 folded into the constants (exact: a power of two commutes with the roundings)
@@ -631,13 +573,8 @@ __device__ __forceinline__ void blind_rotate_pair_unit(const ExtProdArgs &A, dou
         wave_lds_sync();
 #pragma unroll
         for (int a = 0; a < 16; ++a) {
-#if BRP_RESIDENT_HI
             lo[a] = torus_acc_scaled(pkl[a], -xr[a]);
             hi[a] = torus_acc_scaled(hi[a], -xi[a]);
-#else
-            lo[a] = torus_acc_scaled(pk[a].x, -xr[a]);
-            hi[a] = torus_acc_scaled(pk[a].y, -xi[a]);
-#endif
             stage_park(a, tq);
             if ((a & 1) == 1) __builtin_amdgcn_sched_barrier(0);
         }

@@ -15,23 +15,11 @@
 #include "fft_dev.h"
 
 #define EP_THREADS 256
-#ifndef EP_EARLY_LOAD
-#define EP_EARLY_LOAD 2   /* GGSW rows started before the pre-multiply barrier (measured -3.5 %); 0 = none */
-#endif
-#ifndef EP_MAC_PRIO
+#define EP_EARLY_LOAD 2   /* GGSW rows started before the pre-multiply barrier (measured -3.5 %) */
 #define EP_MAC_PRIO 1   /* wave priority while the load-latency-bound multiply-accumulate runs (measured -1.7 %) */
-#endif
-#ifndef EP_ROT_CHUNK
 #define EP_ROT_CHUNK 4
-#endif
-#ifdef ABL_MAC_NOLOAD   /* developer ablation: no key traffic */
-#define EP_LOADB(expr, p, c) make_double2((double)(tid + (c) + (p)), (double)(tid - (c)))
-#else
-#define EP_LOADB(expr, p, c) (expr)
-#endif
-#ifndef EP_PREFETCH
 #define EP_PREFETCH 2
-#endif
+#define EP_MIN_WAVES 2
 #define EP_GROUPS 16
 #define EP_LDS_DOUBLES (EP_GROUPS * GROUP_TILE_DOUBLES + 2 * FHE_TW_ENTRIES)
 
@@ -74,9 +62,7 @@ struct ExtProdArgs {
 // One 16-byte key element through a raw buffer load: the address is (buffer base, scalar) + (row offset, scalar) +
 // (16 * point, the only vector part), so a key fetch costs no vector address arithmetic at all.
 typedef unsigned ep_u32x4 __attribute__((ext_vector_type(4)));
-#ifndef EP_KEY_AUX
 #define EP_KEY_AUX 0       /* cache policy bits of the key loads (1 = sc0, 2 = nt, 16 = sc1) */
-#endif
 __device__ __forceinline__ double2 ep_key_load(__amdgpu_buffer_rsrc_t rsrc, unsigned lane_bytes, unsigned row_bytes)
 {
     ep_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_bytes, row_bytes, EP_KEY_AUX);
@@ -90,16 +76,10 @@ __device__ __forceinline__ double2 ep_key_load(__amdgpu_buffer_rsrc_t rsrc, unsi
 #define EP_NPH 12
 #define EP_STAMP(ph) do { unsigned long long t__ = __builtin_readcyclecounter(); ph_cyc[ph] += t__ - t_last; t_last = t__; } while (0)
 #else
-#ifndef EP_FENCE_MASK
-#define EP_FENCE_MASK 0        /* developer knob: bit ph set = the wave drains its LDS/scalar-memory counter at phase boundary ph (what a stamp does) */
-#endif
-#define EP_STAMP(ph) do { if ((EP_FENCE_MASK >> (ph)) & 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); } while (0)
+#define EP_STAMP(ph) do { } while (0)
 #endif
 
 template <int K1, int LEVELS, int BASE_LOG, int R, bool VP>
-#ifndef EP_MIN_WAVES
-#define EP_MIN_WAVES 2
-#endif
 __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kernel(const ExtProdArgs A)
 {
     static_assert(R * K1 <= EP_GROUPS, "too many polynomials for 16 lane groups");
@@ -220,29 +200,19 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
         // (A lambda called once for the first level and once inside the loop, so that xr/xi are provably dead
         // during the multiply-accumulate of every level: no loop-carried copy survives the level.)
         auto level_body = [&](const int l, const bool tiles_busy) {
-#ifndef EP_LATE_BARRIER
             if (tiles_busy) __syncthreads();
-#endif
             EP_STAMP(3);
             // first half of the transform needs no tile; the barrier that frees the tiles (other threads
             // may still be reading the previous level's digits) sits as late as possible
-#ifndef ABL_NO_FFT
             {
                 double2 w0[8], w1[8];
                 fft_fwd_table(w0, w1, tw, b);
                 nega_fwd_head(xr, xi, w0, w1);
             }
-#endif
-#ifdef EP_LATE_BARRIER
-            if (tiles_busy) __syncthreads();
-#endif
             EP_STAMP(2);
-#ifndef ABL_NO_FFT
             nega_fwd_tail(xr, xi, tile, b);
-#endif
             EP_STAMP(4);
             const double2 *Gl = G + (size_t)l * K1 * K1 * FHE_H + tid;
-#if EP_EARLY_LOAD
             // Store a few transformed digits, start a GGSW row into the registers that just died, repeat: the
             // first EARLY rows are in flight across the remaining stores and the barrier (which therefore
             // must not drain vmcnt).
@@ -271,34 +241,18 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
             EP_STAMP(5);
             wg_barrier_lds_only();
             EP_STAMP(6);
-#else
-#pragma unroll
-            for (int k2 = 0; k2 < 16; ++k2) {
-                double2 v; v.x = xr[k2]; v.y = xi[k2];
-                *reinterpret_cast<double2 *>(tile + 2 * (b + 16 * k2)) = v;
-            }
-            __syncthreads();
-#endif
             // ---- multiply-accumulate role: thread tid owns Fourier point tid ------------------
-#ifndef ABL_NO_MAC
             // The K1 x K1 GGSW entries of this level stream from L2; without software pipelining every
             // row costs one exposed round trip (measured: 71 of 341 ms).  xr/xi are dead here, so PF rows
             // are kept in flight in their registers.
-#if EP_MAC_PRIO
             __builtin_amdgcn_s_setprio(EP_MAC_PRIO);
-#endif
             constexpr int PF = (K1 < EP_PREFETCH) ? K1 : EP_PREFETCH;
-#if !EP_EARLY_LOAD
-            double2 bq[PF][K1];
-            constexpr int P_FIRST = 0;
-#else
             constexpr int P_FIRST = EARLY;
-#endif
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int p = P_FIRST; p < PF; ++p)
 #pragma unroll
-                for (int c = 0; c < K1; ++c) bq[p][c] = EP_LOADB(Gl[(size_t)(p * K1 + c) * FHE_H], p, c);
+                for (int c = 0; c < K1; ++c) bq[p][c] = Gl[(size_t)(p * K1 + c) * FHE_H];
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int p = 0; p < K1; ++p) {
@@ -307,16 +261,12 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
                 for (int c = 0; c < K1; ++c) bv[c] = bq[p % PF][c];
                 if (p + PF < K1) {
 #pragma unroll
-                    for (int c = 0; c < K1; ++c) bq[p % PF][c] = EP_LOADB(Gl[(size_t)((p + PF) * K1 + c) * FHE_H], p, c);
+                    for (int c = 0; c < K1; ++c) bq[p % PF][c] = Gl[(size_t)((p + PF) * K1 + c) * FHE_H];
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-#ifdef ABL_MAC_NOLDS
-                    double2 d; d.x = (double)(tid + r); d.y = (double)(p - tid);
-#else
                     double2 d = *reinterpret_cast<const double2 *>(lds + (r * K1 + p) * GROUP_TILE_DOUBLES + 2 * tid);
-#endif
 #pragma unroll
                     for (int c = 0; c < K1; ++c) {
                         fr[r][c] = __builtin_fma(d.x, bv[c].x, fr[r][c]);
@@ -327,10 +277,7 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-#if EP_MAC_PRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
-#endif
             EP_STAMP(7);
         };
         level_body(LEVELS - 1, false);
@@ -362,9 +309,7 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
         }
         wave_lds_sync();
         EP_STAMP(8);
-#ifndef ABL_NO_FFT
         nega_inv(xr, xi, tw, tile, b);
-#endif
         EP_STAMP(9);
 #pragma unroll
         for (int a = 0; a < 16; ++a) {

@@ -13,19 +13,16 @@
 // each accumulated exactly in int32 by v_mfma_i32_16x16x64_i8 (|sum| <= Q*128*128 < 2^31) and recombined
 // with shifts in uint64.  Bit-exact against the oracle by construction (integer arithmetic, any order).
 //
-// Operands are stored in HBM directly in MFMA fragment order, so every lane fetches its 16 operand bytes
-// with one coalesced 16-byte load (1 KB per wave per fragment) and nothing is staged through LDS:
+// Operands are stored in HBM directly in MFMA fragment order (1 KB per fragment: 16 operand bytes per lane):
 //   A (digits): [ct tile of 16][kstep][plane][lane 64][16 B]   lane l: ciphertext 16T + l%16, rows 64*kstep + 16*(l/16) + e
 //   B (key)   : [z][kstep][column tile of 16][byte plane j][lane 64][16 B]   lane l: column 16C + l%16, same rows
-// One wave owns a 64-ciphertext x 16-column output tile (4 x 8 int32x4 accumulators); the 4 waves of a
-// workgroup take 4 adjacent column tiles of the same 64 ciphertexts, so their A loads coincide in L1.
+// One wave owns a 64-ciphertext x 16-column output tile (4 x 8 int32x4 accumulators).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fft_dev.h"
 
-#define KS_THREADS 256
-#define KS_CT_TILE 64          /* ciphertexts per workgroup */
+#define KS_CT_TILE 64          /* ciphertexts per wave: the digit planes are sized in whole tiles of this many */
 #define KS_KSTEP 64            /* K rows per MFMA */
 
 typedef int ks_int4 __attribute__((ext_vector_type(4)));
@@ -47,15 +44,12 @@ struct KeyswitchArgs {
 };
 
 // ---- LDS-tiled form: 512 threads = 8 waves own a 128-ciphertext x 64-column output tile -------------------
-// The one-wave-one-tile kernel above is bound by the L2 -> CU operand stream (40 KB per 240 MFMAs: measured
-// 36 % of the int8 MFMA rate).  Here the 8 digit fragments and the 32 key fragments of a K step are brought in
+// A one-wave-one-tile kernel that fetches its operands straight from L2 (rounds 1-5) is bound by the L2 -> CU operand stream
+// (40 KB per 240 MFMAs: measured 36 % of the int8 MFMA rate).  Here the 8 digit fragments and the 32 key fragments of a K step are brought in
 // ONCE per workgroup by LDS-DMA (global_load_lds_dwordx4: 1 KB per wave instruction, no VGPR staging; the
 // fragments are already stored in MFMA lane order, so the LDS image is the HBM image) and read by every wave
 // that needs them: 48 KB per 480 MFMAs.  Double buffered: the loads of step ks+1 fly during the MFMAs of ks.
-#ifndef KSL_CT_TILES
-#define KSL_CT_TILES 8          /* 8: 128 ciphertexts per 512-thread workgroup, one workgroup per CU (96 KB of LDS); 4: 64 ciphertexts per 256-thread
-                                   workgroup, two independent workgroups per CU (80 KB each: no common barrier, the key fragments come in twice) */
-#endif
+#define KSL_CT_TILES 8          /* 128 ciphertexts per 512-thread workgroup, one workgroup per CU (96 KB of LDS) */
 #define KSL_THREADS (64 * KSL_CT_TILES)
 #define KSL_COL_TILES 4         /* 64 columns */
 
@@ -141,65 +135,6 @@ __global__ __launch_bounds__(256) void digits_kernel(const uint64_t *in, uint64_
         *reinterpret_cast<ks_int4 *>(o + 1024) = w;
     }
 }
-
-template <int PLANES>
-__global__ __launch_bounds__(KS_THREADS, 2) void keyswitch_mfma_kernel(const KeyswitchArgs A)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t C = blockIdx.x * 4 + wave;                 // this wave's column tile
-    if (C >= A.coltiles) return;                              // whole wave exits together (no barriers in this kernel)
-    const uint64_t T0 = (uint64_t)blockIdx.y * (KS_CT_TILE / 16);
-    const uint32_t z = blockIdx.z;
-
-    ks_int4 acc[4][8];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int s = 0; s < 8; ++s) acc[t][s] = (ks_int4){0, 0, 0, 0};
-
-    const int8_t *ap = A.afrag + (T0 * A.ksteps * PLANES) * 1024 + (uint64_t)lane * 16;
-    const int8_t *bp = A.bfrag + (((uint64_t)z * A.ksteps * A.coltiles + C) * 8) * 1024 + (uint64_t)lane * 16;
-    const uint64_t a_tile_stride = (uint64_t)A.ksteps * PLANES * 1024;      // between ciphertext tiles
-    const uint64_t b_step_stride = (uint64_t)A.coltiles * 8 * 1024;         // between k steps
-
-    for (uint32_t ks = 0; ks < A.ksteps; ++ks) {
-        ks_int4 a[4][PLANES], b[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) b[s] = *reinterpret_cast<const ks_int4 *>(bp + (uint64_t)ks * b_step_stride + (uint64_t)s * 1024);
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int pl = 0; pl < PLANES; ++pl)
-                a[t][pl] = *reinterpret_cast<const ks_int4 *>(ap + (uint64_t)t * a_tile_stride + ((uint64_t)ks * PLANES + pl) * 1024);
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t][s] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[t][0], b[s], acc[t][s], 0, 0, 0);
-            if (PLANES == 2 && s >= 1) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) acc[t][s] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[t][1], b[s - 1], acc[t][s], 0, 0, 0);
-            }
-        }
-    }
-
-    // D layout of v_mfma_*_16x16: lane l holds column l%16, rows 4*(l/16) + r, r = 0..3
-    const uint32_t col = C * 16 + (lane & 15);
-    if (col >= A.ncols) return;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const uint64_t ct = (T0 + t) * 16 + (uint64_t)(lane >> 4) * 4 + r;
-            if (ct >= A.m) continue;
-            uint64_t v = 0;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) v += (uint64_t)(int64_t)acc[t][s][r] << (8 * s);
-            v = (uint64_t)0 - v;
-            if (A.body_index >= 0 && col == A.body_col) v += A.in[ct * A.in_stride + (uint32_t)A.body_index];
-            A.out[ct * A.out_stride + (uint64_t)z * A.out_z_stride + col] = v;
-        }
-}
-
 
 template <int PLANES>
 __global__ __launch_bounds__(KSL_THREADS, 2) void keyswitch_mfma_lds_kernel(const KeyswitchArgs A)

@@ -8,7 +8,7 @@
 //   engine.hip        -DFHEAES_SPLIT_KS, post-RA scheduler off: everything but the key-switching kernels; it sees their
 //                     constants and argument block only (FHEAES_KS_DECLS_ONLY) and calls the functions below;
 //   keyswitch_tu.hip  the key-switching kernels and the definitions of these functions, default scheduler.
-// Without -DFHEAES_SPLIT_KS (developer tools that compile engine.hip alone: tools/ablate_*.py, the ISA listings) the functions are
+// Without -DFHEAES_SPLIT_KS (developer tools that compile engine.hip alone: tools/ablate_k2.py, tools/latency_stamps.py, the ISA listings) the functions are
 // defined right here and engine.hip is a complete library by itself.
 #pragma once
 #ifdef FHEAES_SPLIT_KS
@@ -32,7 +32,6 @@
 #ifdef FHEAES_KS_LAUNCH_DECL
 void ks_launch_digits_k1(dim3 grid, hipStream_t s, const uint64_t *in, uint64_t in_stride, uint32_t n_in, uint64_t m, uint32_t ksteps, int8_t *frag);
 void ks_launch_digits_k3(dim3 grid, hipStream_t s, const uint64_t *in, uint64_t in_stride, uint32_t n_in, uint64_t m, uint32_t ksteps, int8_t *frag);
-void ks_launch_mfma(int planes, dim3 grid, hipStream_t s, const KeyswitchArgs &a);
 void ks_launch_mfma_lds(int planes, dim3 grid, hipStream_t s, const KeyswitchArgs &a);
 void ks_launch_keybytes(dim3 grid, hipStream_t s, const uint64_t *key, uint64_t key_z_stride, uint32_t rows, uint32_t ncols, uint32_t ksteps,
                         uint32_t coltiles, int8_t *frag);
@@ -48,11 +47,6 @@ FHEAES_KS_LAUNCH_LINKAGE void ks_launch_digits_k1(dim3 grid, hipStream_t s, cons
 FHEAES_KS_LAUNCH_LINKAGE void ks_launch_digits_k3(dim3 grid, hipStream_t s, const uint64_t *in, uint64_t in_stride, uint32_t n_in, uint64_t m, uint32_t ksteps, int8_t *frag)
 {
     hipLaunchKernelGGL((digits_kernel<12, 3, 2>), grid, dim3(256), 0, s, in, in_stride, n_in, m, ksteps, frag);
-}
-FHEAES_KS_LAUNCH_LINKAGE void ks_launch_mfma(int planes, dim3 grid, hipStream_t s, const KeyswitchArgs &a)
-{
-    if (planes == 1) hipLaunchKernelGGL((keyswitch_mfma_kernel<1>), grid, dim3(KS_THREADS), 0, s, a);
-    else hipLaunchKernelGGL((keyswitch_mfma_kernel<2>), grid, dim3(KS_THREADS), 0, s, a);
 }
 FHEAES_KS_LAUNCH_LINKAGE void ks_launch_mfma_lds(int planes, dim3 grid, hipStream_t s, const KeyswitchArgs &a)
 {
