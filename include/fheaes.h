@@ -183,6 +183,28 @@ int fheaes_aes_decrypt(fheaes_ctx *ctx, const uint64_t *round_keys, uint64_t *st
 int fheaes_aes_decryption_round_keys(fheaes_ctx *ctx, const uint64_t *round_keys, uint64_t *dec_round_keys, int memspace);
 /* The equivalent inverse cipher, batched, in place: state [n_blocks][16][8][kN+1], dec_round_keys from fheaes_aes_decryption_round_keys. */
 int fheaes_aes_decrypt_equivalent(fheaes_ctx *ctx, const uint64_t *dec_round_keys, uint64_t *state, uint64_t n_blocks, int memspace);
+/* AES-192 and AES-256 (FIPS-197 with Nk = 6 / 8 key words and Nr = 12 / 14 rounds): the five AES entry points above with the key size as
+ * an argument.  The reference has no counterpart: it is AES-128 only (server.rs:107 expands 4 key words into 44, main.rs runs that one
+ * cipher); K1-K5 are blind to the key size, so these are the same schedules with Nr in place of 10.  `key_bits` is 128, 192 or 256,
+ * anything else is FHEAES_ERR_INVALID; with key_bits = 128 every function gives word for word what its counterpart above gives (one
+ * implementation: the entry points above pass 128).  round_keys and dec_round_keys are [Nr+1][16][8][kN+1], Nr = 10 / 12 / 14: round
+ * key r is words 4r..4r+3 of the expanded key.
+ *
+ * Key expansion (FIPS-197 section 5.2): key [key_bits/8][8][kN+1], bytes in FIPS-197 order (byte 0 first).  The reference's rule
+ * (server.rs:107-155: every new word refreshed by an identity WoPBS) for general Nk: RotWord + SubWord + Rcon when i % Nk == 0, SubWord
+ * alone when Nk > 6 and i % Nk == 4; 40 / 46 / 52 new words of which 10 / 8 / 13 pass through SubWord.  Every sum has two nominal terms. */
+int fheaes_aes_key_expansion_bits(fheaes_ctx *ctx, const uint64_t *key, uint32_t key_bits, uint64_t *round_keys, int memspace);
+/* The cipher of FIPS-197 Fig. 5 with Server::aes_encrypt's schedule (server.rs:39): Nr - 1 rounds of the 3-LUT {S, 2S, 3S} WoPBS and
+ * the MixColumns gather, then the S-Box round: Nr x 128 = 1,280 / 1,536 / 1,792 bit circuit bootstraps per block. */
+int fheaes_aes_encrypt_bits(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks, int memspace);
+/* The inverse cipher of FIPS-197 Fig. 12 with Server::aes_decrypt's schedule (server.rs:67): two WoPBS in each of Nr - 1 rounds and one
+ * in the last, (2 Nr - 1) x 128 = 2,432 / 2,944 / 3,456 bit circuit bootstraps per block. */
+int fheaes_aes_decrypt_bits(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks, int memspace);
+/* The equivalent inverse cipher of FIPS-197 Fig. 15: dw[0] = w[0], dw[Nr] = w[Nr], dw[r] = InvMixColumns(w[r]) for r = 1..Nr-1, the
+ * 16 (Nr - 1) middle bytes refreshed in one batch; then Nr WoPBS per block, as for encryption.  Overlapping buffers are FHEAES_ERR_INVALID. */
+int fheaes_aes_decryption_round_keys_bits(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t *dec_round_keys, int memspace);
+int fheaes_aes_decrypt_equivalent_bits(fheaes_ctx *ctx, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks,
+                                       int memspace);
 /* Server::add_scalar (server.rs:172), batched: state[b] += counters[b] (u128 as {hi, lo}, host array
  * of 2*n_blocks words regardless of memspace).  The first-byte carry uses counter & 0xFF (the
  * reference's server.rs:182 is wrong for counters >= 256). */

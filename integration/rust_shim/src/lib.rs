@@ -76,6 +76,12 @@ extern "C" {
     // the equivalent inverse cipher (FIPS-197 5.3.5): round-key conversion once per key, then one WoPBS per round
     pub fn fheaes_aes_decryption_round_keys(ctx: *mut fheaes_ctx, round_keys: *const u64, dec_round_keys: *mut u64, memspace: c_int) -> c_int;
     pub fn fheaes_aes_decrypt_equivalent(ctx: *mut fheaes_ctx, dec_round_keys: *const u64, state: *mut u64, n_blocks: u64, memspace: c_int) -> c_int;
+    // AES-192 / AES-256 (FIPS-197 Nk = 6 / 8, Nr = 12 / 14): the five above with key_bits = 128 | 192 | 256; the reference is AES-128 only
+    pub fn fheaes_aes_key_expansion_bits(ctx: *mut fheaes_ctx, key: *const u64, key_bits: u32, round_keys: *mut u64, memspace: c_int) -> c_int;
+    pub fn fheaes_aes_encrypt_bits(ctx: *mut fheaes_ctx, round_keys: *const u64, key_bits: u32, state: *mut u64, n_blocks: u64, memspace: c_int) -> c_int;
+    pub fn fheaes_aes_decrypt_bits(ctx: *mut fheaes_ctx, round_keys: *const u64, key_bits: u32, state: *mut u64, n_blocks: u64, memspace: c_int) -> c_int;
+    pub fn fheaes_aes_decryption_round_keys_bits(ctx: *mut fheaes_ctx, round_keys: *const u64, key_bits: u32, dec_round_keys: *mut u64, memspace: c_int) -> c_int;
+    pub fn fheaes_aes_decrypt_equivalent_bits(ctx: *mut fheaes_ctx, dec_round_keys: *const u64, key_bits: u32, state: *mut u64, n_blocks: u64, memspace: c_int) -> c_int;
     pub fn fheaes_add_scalar(ctx: *mut fheaes_ctx, state: *mut u64, n_blocks: u64, counters_hi_lo: *const u64, memspace: c_int) -> c_int;
 }
 

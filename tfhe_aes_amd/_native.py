@@ -55,6 +55,11 @@ SIGNATURES = {
     "fheaes_aes_decrypt": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_int]),
     "fheaes_aes_decryption_round_keys": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_int]),
     "fheaes_aes_decrypt_equivalent": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_int]),
+    "fheaes_aes_key_expansion_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_encrypt_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint64, _c.c_int]),
+    "fheaes_aes_decrypt_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint64, _c.c_int]),
+    "fheaes_aes_decryption_round_keys_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_decrypt_equivalent_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint64, _c.c_int]),
     "fheaes_add_scalar": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _u64p, _c.c_int]),
     "fheaes_profile_enable": (_c.c_int, [_ctx, _c.c_int]),
     "fheaes_profile_reset": (_c.c_int, [_ctx]),
@@ -255,6 +260,27 @@ class Engine:
     def aes_decrypt_equivalent(self, dec_round_keys, state, n_blocks: int):
         self._check(self._lib.fheaes_aes_decrypt_equivalent(self._h, _ptr(dec_round_keys)[0], _ptr(state)[0], n_blocks,
                                                             self._space(dec_round_keys, state)))
+
+    # AES-192 / AES-256 (and AES-128 again): the same five with the key size as an argument, key_bits in {128, 192, 256};
+    # key [key_bits/8][8][kN+1], round keys [Nr+1][16][8][kN+1] with Nr = 10 / 12 / 14
+    def aes_key_expansion_bits(self, key, key_bits: int, round_keys):
+        self._check(self._lib.fheaes_aes_key_expansion_bits(self._h, _ptr(key)[0], key_bits, _ptr(round_keys)[0], self._space(key, round_keys)))
+
+    def aes_encrypt_bits(self, round_keys, key_bits: int, state, n_blocks: int):
+        self._check(self._lib.fheaes_aes_encrypt_bits(self._h, _ptr(round_keys)[0], key_bits, _ptr(state)[0], n_blocks,
+                                                      self._space(round_keys, state)))
+
+    def aes_decrypt_bits(self, round_keys, key_bits: int, state, n_blocks: int):
+        self._check(self._lib.fheaes_aes_decrypt_bits(self._h, _ptr(round_keys)[0], key_bits, _ptr(state)[0], n_blocks,
+                                                      self._space(round_keys, state)))
+
+    def aes_decryption_round_keys_bits(self, round_keys, key_bits: int, dec_round_keys):
+        self._check(self._lib.fheaes_aes_decryption_round_keys_bits(self._h, _ptr(round_keys)[0], key_bits, _ptr(dec_round_keys)[0],
+                                                                    self._space(round_keys, dec_round_keys)))
+
+    def aes_decrypt_equivalent_bits(self, dec_round_keys, key_bits: int, state, n_blocks: int):
+        self._check(self._lib.fheaes_aes_decrypt_equivalent_bits(self._h, _ptr(dec_round_keys)[0], key_bits, _ptr(state)[0], n_blocks,
+                                                                 self._space(dec_round_keys, state)))
 
     def add_scalar(self, state, n_blocks: int, counters):
         cnt = np.zeros((n_blocks, 2), dtype=np.uint64)

@@ -1,10 +1,11 @@
-"""Clear-text AES-128 and the S-Box LUT functions of the path.
+"""Clear-text AES (FIPS-197: 128-, 192- and 256-bit keys) and the S-Box LUT functions of the path.
 
 Stands in for (a) the RustCrypto ``aes`` crate the reference verifies against
 (/root/reference/src/client/client.rs:166-171) and (b) the reference's tables and GF(2^8)
 helpers (src/tables/table.rs, src/server/sbox/sbox.rs:20-42).  Tables are derived from the
 field definition (inverse in GF(2^8) mod x^8+x^4+x^3+x+1, then the FIPS-197 affine map), not
-copied; tests pin them against FIPS-197 values.
+copied; tests pin them against FIPS-197 values.  The reference is AES-128 only; the other two key sizes are pinned by the
+vectors of FIPS-197 appendices A and C and of SP 800-38A (tests/test_aes_key_sizes_cpu.py).
 """
 from __future__ import annotations
 
@@ -54,17 +55,25 @@ def mul13(x): return gf_mul(x, 13)
 def mul14(x): return gf_mul(x, 14)
 
 
-def expand_key(key: int):
-    kb = [(key >> (8 * (15 - i))) & 0xFF for i in range(16)]
-    w = [kb[4 * i:4 * i + 4] for i in range(4)]
-    for i in range(4, 44):
+def expand_key(key):
+    """FIPS-197 section 5.2.  `key`: 16 / 24 / 32 `bytes` (AES-128 / 192 / 256), or an int, which is a 128-bit key with byte 0 the
+    most significant.  Returns the Nr + 1 = 11 / 13 / 15 round keys of 16 bytes."""
+    kb = list(key) if isinstance(key, (bytes, bytearray)) else [(key >> (8 * (15 - i))) & 0xFF for i in range(16)]
+    if len(kb) not in (16, 24, 32):
+        raise ValueError("an AES key has 16, 24 or 32 bytes, got %d" % len(kb))
+    nk = len(kb) // 4
+    nr = nk + 6
+    w = [kb[4 * i:4 * i + 4] for i in range(nk)]
+    for i in range(nk, 4 * (nr + 1)):
         t = list(w[i - 1])
-        if i % 4 == 0:
+        if i % nk == 0:
             t = t[1:] + t[:1]
             t = [SBOX[b] for b in t]
-            t[0] ^= RCON[i // 4 - 1]
-        w.append([a ^ b for a, b in zip(w[i - 4], t)])
-    return [sum(w[4 * r:4 * r + 4], []) for r in range(11)]
+            t[0] ^= RCON[i // nk - 1]
+        elif nk > 6 and i % nk == 4:
+            t = [SBOX[b] for b in t]
+        w.append([a ^ b for a, b in zip(w[i - nk], t)])
+    return [sum(w[4 * r:4 * r + 4], []) for r in range(nr + 1)]
 
 
 def _shift_rows(s):
@@ -87,43 +96,63 @@ def _mix(s, m):
     return out
 
 
-def aes128_encrypt_block(key: int, block: int) -> int:
-    rk = expand_key(key)
-    s = [(block >> (8 * (15 - i))) & 0xFF for i in range(16)]
-    s = [a ^ b for a, b in zip(s, rk[0])]
-    for rnd in range(1, 10):
-        s = _mix(_shift_rows([SBOX[b] for b in s]), (2, 3, 1, 1))
-        s = [a ^ b for a, b in zip(s, rk[rnd])]
-    s = _shift_rows([SBOX[b] for b in s])
-    s = [a ^ b for a, b in zip(s, rk[10])]
+def _state(block: int):
+    return [(block >> (8 * (15 - i))) & 0xFF for i in range(16)]
+
+
+def _u128(s) -> int:
     return sum(b << (8 * (15 - i)) for i, b in enumerate(s))
 
 
-def aes128_decrypt_block(key: int, block: int) -> int:
+def aes_encrypt_block(key, block: int) -> int:
+    """FIPS-197 Fig. 5 for a key of 16 / 24 / 32 bytes (or a 128-bit int, as expand_key); the block is a u128, byte 0 = MSB"""
     rk = expand_key(key)
-    s = [(block >> (8 * (15 - i))) & 0xFF for i in range(16)]
-    s = [a ^ b for a, b in zip(s, rk[10])]
-    for rnd in range(9, 0, -1):
+    nr = len(rk) - 1
+    s = [a ^ b for a, b in zip(_state(block), rk[0])]
+    for rnd in range(1, nr):
+        s = _mix(_shift_rows([SBOX[b] for b in s]), (2, 3, 1, 1))
+        s = [a ^ b for a, b in zip(s, rk[rnd])]
+    s = _shift_rows([SBOX[b] for b in s])
+    return _u128(a ^ b for a, b in zip(s, rk[nr]))
+
+
+def aes_decrypt_block(key, block: int) -> int:
+    """FIPS-197 Fig. 12, the inverse cipher, in the order Server::aes_decrypt takes it (AddRoundKey before InvMixColumns)"""
+    rk = expand_key(key)
+    nr = len(rk) - 1
+    s = [a ^ b for a, b in zip(_state(block), rk[nr])]
+    for rnd in range(nr - 1, 0, -1):
         s = [INV_SBOX[b] for b in _inv_shift_rows(s)]
         s = [a ^ b for a, b in zip(s, rk[rnd])]
         s = _mix(s, (14, 11, 13, 9))
     s = [INV_SBOX[b] for b in _inv_shift_rows(s)]
-    s = [a ^ b for a, b in zip(s, rk[0])]
-    return sum(b << (8 * (15 - i)) for i, b in enumerate(s))
+    return _u128(a ^ b for a, b in zip(s, rk[0]))
+
+
+def aes128_encrypt_block(key: int, block: int) -> int:
+    return aes_encrypt_block(key, block)
+
+
+def aes128_decrypt_block(key: int, block: int) -> int:
+    return aes_decrypt_block(key, block)
 
 
 def inv_mix_columns_round_keys(expanded):
-    """the equivalent inverse cipher's round keys (FIPS-197 section 5.3.5): dw[0] = w[0], dw[10] = w[10], dw[r] = InvMixColumns(w[r])"""
-    return [list(expanded[0])] + [_mix(list(expanded[r]), (14, 11, 13, 9)) for r in range(1, 10)] + [list(expanded[10])]
+    """the equivalent inverse cipher's round keys (FIPS-197 section 5.3.5): dw[0] = w[0], dw[Nr] = w[Nr], dw[r] = InvMixColumns(w[r])"""
+    nr = len(expanded) - 1
+    return [list(expanded[0])] + [_mix(list(expanded[r]), (14, 11, 13, 9)) for r in range(1, nr)] + [list(expanded[nr])]
 
 
-def aes128_decrypt_block_equivalent(dw, block: int) -> int:
-    """FIPS-197 Fig. 15 with the round keys of inv_mix_columns_round_keys: InvSubBytes, InvShiftRows, InvMixColumns, AddRoundKey"""
-    s = [(block >> (8 * (15 - i))) & 0xFF for i in range(16)]
-    s = [a ^ b for a, b in zip(s, dw[10])]
-    for rnd in range(9, 0, -1):
+def aes_decrypt_block_equivalent(dw, block: int) -> int:
+    """FIPS-197 Fig. 15 with the Nr + 1 round keys of inv_mix_columns_round_keys: InvSubBytes, InvShiftRows, InvMixColumns, AddRoundKey"""
+    nr = len(dw) - 1
+    s = [a ^ b for a, b in zip(_state(block), dw[nr])]
+    for rnd in range(nr - 1, 0, -1):
         s = _mix(_inv_shift_rows([INV_SBOX[b] for b in s]), (14, 11, 13, 9))
         s = [a ^ b for a, b in zip(s, dw[rnd])]
     s = _inv_shift_rows([INV_SBOX[b] for b in s])
-    s = [a ^ b for a, b in zip(s, dw[0])]
-    return sum(b << (8 * (15 - i)) for i, b in enumerate(s))
+    return _u128(a ^ b for a, b in zip(s, dw[0]))
+
+
+def aes128_decrypt_block_equivalent(dw, block: int) -> int:
+    return aes_decrypt_block_equivalent(dw, block)

@@ -225,9 +225,16 @@ class ServerKeys:
 # parameter set and the kind recorded and checked on load.
 CIPHERTEXT_KINDS = {
     "state": (16, 8),           # [blocks][16 bytes][8 bits][kN+1]      Server::aes_encrypt / aes_decrypt / add_scalar
-    "round_keys": (11, 16, 8),  # [11][16][8][kN+1]                     Server::aes_key_expansion output
+    "round_keys": (11, 16, 8),  # [11][16][8][kN+1]                     Server::aes_key_expansion output ([13] / [15]: AES-192 / AES-256)
     "bytes": (8,),              # [n][8][kN+1]                          sbox / many_sbox inputs
 }
+
+
+def _has_kind_shape(shape, kind: str, params: WopbsParameters) -> bool:
+    tail = CIPHERTEXT_KINDS[kind] + (params.big1,)
+    if kind == "round_keys" and len(shape) >= 4 and shape[-4] in (13, 15):       # Nr + 1 round keys of AES-192 / AES-256
+        return shape[-3:] == tail[1:]
+    return shape[-len(tail):] == tail
 
 
 def save_ciphertexts(path, params: WopbsParameters, kind: str, words: np.ndarray) -> None:
@@ -235,7 +242,7 @@ def save_ciphertexts(path, params: WopbsParameters, kind: str, words: np.ndarray
         raise ValueError("kind must be one of %s" % ", ".join(CIPHERTEXT_KINDS))
     tail = CIPHERTEXT_KINDS[kind] + (params.big1,)
     a = np.ascontiguousarray(words, dtype=np.uint64)
-    if a.shape[-len(tail):] != tail:
+    if not _has_kind_shape(a.shape, kind, params):
         raise ValueError("a %r array must end in shape %r, got %r" % (kind, tail, a.shape))
     np.savez(path, shape=_param_shape(params), kind=np.frombuffer(kind.encode().ljust(16, b"\0"), dtype=np.uint8), words=a)
 
@@ -248,8 +255,7 @@ def load_ciphertexts(path, params: WopbsParameters, kind: str) -> np.ndarray:
         if got != kind:
             raise ValueError("ciphertext file holds %r, expected %r" % (got, kind))
         a = z["words"].astype(np.uint64)
-    tail = CIPHERTEXT_KINDS[kind] + (params.big1,)
-    if a.shape[-len(tail):] != tail:
+    if not _has_kind_shape(a.shape, kind, params):
         raise ValueError("ciphertext file has the wrong array shape")
     return a
 
@@ -331,6 +337,12 @@ class Client:
     def encrypt_u128(self, x: int) -> np.ndarray:
         """one AES state / key: [16][8][kN+1]"""
         return self.encrypt_bytes(u128_to_bytes(x))
+
+    def encrypt_aes_key(self, key: bytes) -> np.ndarray:
+        """an AES key of 16 / 24 / 32 bytes, in FIPS-197 order (byte 0 first): [len][8][kN+1], what Server.aes_key_expansion takes"""
+        if len(key) not in (16, 24, 32):
+            raise ValueError("an AES key has 16, 24 or 32 bytes, got %d" % len(key))
+        return self.encrypt_bytes(list(key))
 
     def client_encrypt(self):
         """client.rs:123: (server keys, encrypted iv, encrypted key)."""

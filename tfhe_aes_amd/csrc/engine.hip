@@ -1374,30 +1374,40 @@ int fheaes_sbox(fheaes_ctx *c, uint64_t *bytes, uint64_t n_bytes, int inv, int m
 }
 
 // ---- Server API -------------------------------------------------------------------------------
-static int aes_encrypt_dev(fheaes_ctx *c, const uint64_t *rk, uint64_t *state, uint64_t n_blocks)
+// FIPS-197 Fig. 4: Nr = 10 / 12 / 14 rounds for Nk = 4 / 6 / 8 key words; 0: not an AES key size.  The reference is AES-128 only
+// (server.rs:107, main.rs); every schedule below is its schedule with Nr in place of 10.
+static int aes_rounds(uint32_t key_bits) { return key_bits == 128 ? 10 : key_bits == 192 ? 12 : key_bits == 256 ? 14 : 0; }
+
+static int check_key_bits(fheaes_ctx *c, uint32_t key_bits)
+{
+    if (!aes_rounds(key_bits)) return c->fail(FHEAES_ERR_INVALID, "key_bits must be 128, 192 or 256, got %u", key_bits);
+    return FHEAES_OK;
+}
+
+static int aes_encrypt_dev(fheaes_ctx *c, const uint64_t *rk, uint64_t *state, uint64_t n_blocks, int nr)
 {
     const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
     TRY(ensure(c, c->ws_vp, nbytes * 3 * bw * 8));
     uint64_t *vp = (uint64_t *)c->ws_vp.p;
     const GatherTable t_round = table_enc_round(), t_shift = table_shift_rows(false);
     TRY(launch_add_bcast(c, state, rk, sw, n_blocks));                                   // server.rs:42
-    for (int round = 1; round < 10; ++round) {                                           // server.rs:44-57
+    for (int round = 1; round < nr; ++round) {                                           // server.rs:44-57
         TRY(many_sbox_dev(c, state, nbytes, LUTSET_ENC_ROUND, vp));
         TRY(launch_gather(c, vp, 3, rk + (uint64_t)round * sw, state, n_blocks, t_round));
     }
     TRY(many_sbox_dev(c, state, nbytes, LUTSET_SBOX, vp));                               // server.rs:59-63
-    TRY(launch_gather(c, vp, 1, rk + 10ull * sw, state, n_blocks, t_shift));
+    TRY(launch_gather(c, vp, 1, rk + (uint64_t)nr * sw, state, n_blocks, t_shift));
     return FHEAES_OK;
 }
 
-static int aes_decrypt_dev(fheaes_ctx *c, const uint64_t *rk, uint64_t *state, uint64_t n_blocks)
+static int aes_decrypt_dev(fheaes_ctx *c, const uint64_t *rk, uint64_t *state, uint64_t n_blocks, int nr)
 {
     const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
     TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
     uint64_t *vp = (uint64_t *)c->ws_vp.p;
     const GatherTable t_inv = table_shift_rows(true), t_mix = table_dec_mix();
-    TRY(launch_add_bcast(c, state, rk + 10ull * sw, sw, n_blocks));                      // server.rs:70
-    for (int round = 10; round >= 2; --round) {                                          // server.rs:72-96
+    TRY(launch_add_bcast(c, state, rk + (uint64_t)nr * sw, sw, n_blocks));               // server.rs:70
+    for (int round = nr; round >= 2; --round) {                                          // server.rs:72-96
         // inv_shift_rows commutes with the bytewise S-Box: INV_SBOX first, then the permutation + round key
         TRY(many_sbox_dev(c, state, nbytes, LUTSET_INV_SBOX, vp));
         TRY(launch_gather(c, vp, 1, rk + (uint64_t)(round - 1) * sw, state, n_blocks, t_inv));
@@ -1411,16 +1421,16 @@ static int aes_decrypt_dev(fheaes_ctx *c, const uint64_t *rk, uint64_t *state, u
 
 // The equivalent inverse cipher (FIPS-197 section 5.3.5, Fig. 15): InvMixColumns is linear, so IMC(InvS(x)) + IMC(w[r]) is one WoPBS
 // per byte with the composed tables {9, 11, 13, 14} * InvS[x] (LUTSET_DEC_EQ_ROUND), summed through the InvShiftRows-folded gather with
-// dw[r] = IMC(w[r]) as the round key: 10 WoPBS per block like aes_encrypt_dev, against the 19 of aes_decrypt_dev (the reference's own
+// dw[r] = IMC(w[r]) as the round key: Nr WoPBS per block like aes_encrypt_dev, against the 2 Nr - 1 of aes_decrypt_dev (the reference's own
 // schedule, server.rs:67-105, which says at :86-89 that it almost doubles the time of encryption).  dw: fheaes_aes_decryption_round_keys.
-static int aes_decrypt_eq_dev(fheaes_ctx *c, const uint64_t *dw, uint64_t *state, uint64_t n_blocks)
+static int aes_decrypt_eq_dev(fheaes_ctx *c, const uint64_t *dw, uint64_t *state, uint64_t n_blocks, int nr)
 {
     const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
     TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
     uint64_t *vp = (uint64_t *)c->ws_vp.p;
     const GatherTable t_round = table_dec_eq_round(), t_inv = table_shift_rows(true);
-    TRY(launch_add_bcast(c, state, dw + 10ull * sw, sw, n_blocks));
-    for (int round = 9; round >= 1; --round) {
+    TRY(launch_add_bcast(c, state, dw + (uint64_t)nr * sw, sw, n_blocks));
+    for (int round = nr - 1; round >= 1; --round) {
         TRY(many_sbox_dev(c, state, nbytes, LUTSET_DEC_EQ_ROUND, vp));
         TRY(launch_gather(c, vp, 4, dw + (uint64_t)round * sw, state, n_blocks, t_round));     // 4 WoPBS outputs + dw[round] = 5
     }
@@ -1429,115 +1439,153 @@ static int aes_decrypt_eq_dev(fheaes_ctx *c, const uint64_t *dw, uint64_t *state
     return FHEAES_OK;
 }
 
-typedef int (*AesDevFn)(fheaes_ctx *, const uint64_t *, uint64_t *, uint64_t);
+typedef int (*AesDevFn)(fheaes_ctx *, const uint64_t *, uint64_t *, uint64_t, int);
 
-static int aes_crypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace, AesDevFn dev)
+static int aes_crypt(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks, int memspace, AesDevFn dev)
 {
     TRY(check_keys(c));
     if (!round_keys || !state) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    const int nr = aes_rounds(key_bits);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (memspace == FHEAES_DEVICE) return dev(c, round_keys, state, n_blocks);
+    if (memspace == FHEAES_DEVICE) return dev(c, round_keys, state, n_blocks, nr);
     Staged s(c);
     void *drk, *dst;
     const uint64_t sw = 16ull * 8 * c->big1;
-    TRY(s.in(round_keys, 11 * sw * 8, &drk));
+    TRY(s.in(round_keys, (uint64_t)(nr + 1) * sw * 8, &drk));
     TRY(s.in(state, n_blocks * sw * 8, &dst));
-    TRY(dev(c, (const uint64_t *)drk, (uint64_t *)dst, n_blocks));
+    TRY(dev(c, (const uint64_t *)drk, (uint64_t *)dst, n_blocks, nr));
     return s.out(state, dst, n_blocks * sw * 8);
+}
+
+int fheaes_aes_encrypt_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks, int memspace)
+{
+    CtxLock lock__(c);
+    return aes_crypt(c, round_keys, key_bits, state, n_blocks, memspace, aes_encrypt_dev);
 }
 
 int fheaes_aes_encrypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace)
 {
+    return fheaes_aes_encrypt_bits(c, round_keys, 128, state, n_blocks, memspace);
+}
+
+int fheaes_aes_decrypt_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks, int memspace)
+{
     CtxLock lock__(c);
-    return aes_crypt(c, round_keys, state, n_blocks, memspace, aes_encrypt_dev);
+    return aes_crypt(c, round_keys, key_bits, state, n_blocks, memspace, aes_decrypt_dev);
 }
 
 int fheaes_aes_decrypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace)
 {
+    return fheaes_aes_decrypt_bits(c, round_keys, 128, state, n_blocks, memspace);
+}
+
+int fheaes_aes_decrypt_equivalent_bits(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks,
+                                       int memspace)
+{
     CtxLock lock__(c);
-    return aes_crypt(c, round_keys, state, n_blocks, memspace, aes_decrypt_dev);
+    return aes_crypt(c, dec_round_keys, key_bits, state, n_blocks, memspace, aes_decrypt_eq_dev);
 }
 
 int fheaes_aes_decrypt_equivalent(fheaes_ctx *c, const uint64_t *dec_round_keys, uint64_t *state, uint64_t n_blocks, int memspace)
 {
-    CtxLock lock__(c);
-    return aes_crypt(c, dec_round_keys, state, n_blocks, memspace, aes_decrypt_eq_dev);
+    return fheaes_aes_decrypt_equivalent_bits(c, dec_round_keys, 128, state, n_blocks, memspace);
 }
 
-// dw[0] = w[0], dw[10] = w[10], dw[r] = InvMixColumns(w[r]) for r = 1..9: the 144 bytes of w[1..9] in one batch -- the 4-LUT
+// dw[0] = w[0], dw[Nr] = w[Nr], dw[r] = InvMixColumns(w[r]) for r = 1..Nr-1: the 16 (Nr - 1) bytes of w[1..Nr-1] in one batch -- the 4-LUT
 // {9x, 11x, 13x, 14x} WoPBS, the InvMixColumns gather (4 terms, no key) and an identity WoPBS that brings every byte back to nominal
 // noise, as the key expansion's refresh does (server.rs:150): a round of the equivalent inverse cipher then sums 4 WoPBS outputs + 1 key
-static int dec_round_keys_dev(fheaes_ctx *c, const uint64_t *w, uint64_t *dw)
+static int dec_round_keys_dev(fheaes_ctx *c, const uint64_t *w, uint64_t *dw, int nr)
 {
-    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 9 * 16;
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = (uint64_t)(nr - 1) * 16;
     TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
     TRY(ensure(c, c->ws_tmp_a, nbytes * bw * 8));
     uint64_t *vp = (uint64_t *)c->ws_vp.p, *mix = (uint64_t *)c->ws_tmp_a.p;
     HIP_TRY(c, hipMemcpyAsync(dw, w, sw * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dw + 10ull * sw, w + 10ull * sw, sw * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dw + (uint64_t)nr * sw, w + (uint64_t)nr * sw, sw * 8, hipMemcpyDeviceToDevice, c->stream));
     TRY(many_sbox_dev(c, w + sw, nbytes, LUTSET_DEC_MUL, vp));
-    TRY(launch_gather(c, vp, 4, nullptr, mix, 9, table_dec_mix()));
+    TRY(launch_gather(c, vp, 4, nullptr, mix, (uint64_t)(nr - 1), table_dec_mix()));
     TRY(many_sbox_dev(c, mix, nbytes, LUTSET_IDENTITY, dw + sw));
     return FHEAES_OK;
 }
 
-int fheaes_aes_decryption_round_keys(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *dec_round_keys, int memspace)
+int fheaes_aes_decryption_round_keys_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t *dec_round_keys, int memspace)
 {
     CtxLock lock__(c);
     TRY(check_keys(c));
     if (!round_keys || !dec_round_keys) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    const int nr = aes_rounds(key_bits);
     const uint64_t sw = 16ull * 8 * c->big1;
-    const uintptr_t a = (uintptr_t)round_keys, b = (uintptr_t)dec_round_keys, bytes = 11 * sw * 8;
+    const uintptr_t a = (uintptr_t)round_keys, b = (uintptr_t)dec_round_keys, bytes = (uint64_t)(nr + 1) * sw * 8;
     if (a < b + bytes && b < a + bytes) return c->fail(FHEAES_ERR_INVALID, "round_keys and dec_round_keys overlap (the conversion is not in place)");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (memspace == FHEAES_DEVICE) return dec_round_keys_dev(c, round_keys, dec_round_keys);
+    if (memspace == FHEAES_DEVICE) return dec_round_keys_dev(c, round_keys, dec_round_keys, nr);
     Staged s(c);
     void *drk, *ddw;
     TRY(s.in(round_keys, bytes, &drk));
     TRY(s.alloc(&ddw, bytes));
-    TRY(dec_round_keys_dev(c, (const uint64_t *)drk, (uint64_t *)ddw));
+    TRY(dec_round_keys_dev(c, (const uint64_t *)drk, (uint64_t *)ddw, nr));
     return s.out(dec_round_keys, ddw, bytes);
 }
 
-static int key_expansion_dev(fheaes_ctx *c, const uint64_t *key, uint64_t *w)
+int fheaes_aes_decryption_round_keys(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *dec_round_keys, int memspace)
+{
+    return fheaes_aes_decryption_round_keys_bits(c, round_keys, 128, dec_round_keys, memspace);
+}
+
+// FIPS-197 section 5.2 for Nk = 4 / 6 / 8 key words under the reference's rule (server.rs:107-155 is the Nk = 4 case): every new word is
+// refreshed by an identity WoPBS; RotWord + SubWord + Rcon when i % Nk == 0, SubWord alone when Nk > 6 and i % Nk == 4; 4 (Nr + 1) words
+static int key_expansion_dev(fheaes_ctx *c, const uint64_t *key, uint64_t *w, int nr)
 {
     static const uint8_t RCON[10] = {0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1B, 0x36};
     const uint64_t bw = 8ull * c->big1, ww = 4 * bw;
     TRY(ensure(c, c->ws_tmp_a, ww * 8));
     TRY(ensure(c, c->ws_tmp_b, ww * 8));
     uint64_t *ta = (uint64_t *)c->ws_tmp_a.p, *tb = (uint64_t *)c->ws_tmp_b.p;
-    HIP_TRY(c, hipMemcpyAsync(w, key, 4 * ww * 8, hipMemcpyDeviceToDevice, c->stream));             // server.rs:122-128
-    for (int i = 4; i < 44; ++i) {                                                                  // server.rs:131-155
-        const uint64_t *prev = w + (uint64_t)(i - 1) * ww;
-        if (i % 4 == 0) {
+    const int nk = nr - 6;                                                                          // FIPS-197 Fig. 4: Nr = Nk + 6
+    HIP_TRY(c, hipMemcpyAsync(w, key, (uint64_t)nk * ww * 8, hipMemcpyDeviceToDevice, c->stream));  // server.rs:122-128
+    for (int i = nk; i < 4 * (nr + 1); ++i) {                                                       // server.rs:131-155
+        const uint64_t *prev = w + (uint64_t)(i - 1) * ww, *back = w + (uint64_t)(i - nk) * ww;
+        if (i % nk == 0) {
             for (int j = 0; j < 4; ++j)                                                             // fhe_rot_word
                 HIP_TRY(c, hipMemcpyAsync(ta + (uint64_t)j * bw, prev + (uint64_t)((j + 1) & 3) * bw, bw * 8, hipMemcpyDeviceToDevice, c->stream));
             TRY(many_sbox_dev(c, ta, 4, LUTSET_SBOX, tb));                                          // fhe_sub_word
-            hipLaunchKernelGGL(add_const_byte_kernel, dim3(1), dim3(64), 0, c->stream, tb, c->big1, (uint32_t)RCON[i / 4 - 1]);
+            hipLaunchKernelGGL(add_const_byte_kernel, dim3(1), dim3(64), 0, c->stream, tb, c->big1, (uint32_t)RCON[i / nk - 1]);
             HIP_TRY(c, hipGetLastError());
-            TRY(launch_add2(c, ta, tb, w + (uint64_t)(i - 4) * ww, ww));
+            TRY(launch_add2(c, ta, tb, back, ww));
+        } else if (nk > 6 && i % nk == 4) {                                                         // FIPS-197 5.2: SubWord alone (Nk = 8)
+            TRY(many_sbox_dev(c, prev, 4, LUTSET_SBOX, tb));
+            TRY(launch_add2(c, ta, tb, back, ww));
         } else {
-            TRY(launch_add2(c, ta, prev, w + (uint64_t)(i - 4) * ww, ww));
+            TRY(launch_add2(c, ta, prev, back, ww));
         }
         TRY(many_sbox_dev(c, ta, 4, LUTSET_IDENTITY, w + (uint64_t)i * ww));                        // refresh, server.rs:150
     }
     return FHEAES_OK;
 }
 
-int fheaes_aes_key_expansion(fheaes_ctx *c, const uint64_t *key, uint64_t *round_keys, int memspace)
+int fheaes_aes_key_expansion_bits(fheaes_ctx *c, const uint64_t *key, uint32_t key_bits, uint64_t *round_keys, int memspace)
 {
     CtxLock lock__(c);
     TRY(check_keys(c));
     if (!key || !round_keys) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    const int nr = aes_rounds(key_bits);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (memspace == FHEAES_DEVICE) return key_expansion_dev(c, key, round_keys);
+    if (memspace == FHEAES_DEVICE) return key_expansion_dev(c, key, round_keys, nr);
     Staged s(c);
     void *dk, *dw;
-    const uint64_t sw = 16ull * 8 * c->big1;
-    TRY(s.in(key, sw * 8, &dk));
-    TRY(s.alloc(&dw, 11 * sw * 8));
-    TRY(key_expansion_dev(c, (const uint64_t *)dk, (uint64_t *)dw));
-    return s.out(round_keys, dw, 11 * sw * 8);
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw;
+    TRY(s.in(key, key_bits / 8 * bw * 8, &dk));
+    TRY(s.alloc(&dw, (uint64_t)(nr + 1) * sw * 8));
+    TRY(key_expansion_dev(c, (const uint64_t *)dk, (uint64_t *)dw, nr));
+    return s.out(round_keys, dw, (uint64_t)(nr + 1) * sw * 8);
+}
+
+int fheaes_aes_key_expansion(fheaes_ctx *c, const uint64_t *key, uint64_t *round_keys, int memspace)
+{
+    return fheaes_aes_key_expansion_bits(c, key, 128, round_keys, memspace);
 }
 
 static int add_scalar_dev(fheaes_ctx *c, uint64_t *state, uint64_t n_blocks, const uint64_t *counters)

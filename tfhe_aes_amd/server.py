@@ -2,12 +2,14 @@
 
 Same names, argument meaning and error behaviour as
   /root/reference/src/server/server.rs        Server::{new, aes_encrypt, aes_decrypt, aes_key_expansion, add_scalar}
-  (plus aes_decryption_round_keys / aes_decrypt_equivalent: the FIPS-197 section 5.3.5 equivalent inverse cipher)
+  (plus aes_decryption_round_keys / aes_decrypt_equivalent: the FIPS-197 section 5.3.5 equivalent inverse cipher; plus AES-192
+  and AES-256, which the reference does not have: the same methods read the key size from the leading axis of the key / round keys)
   /root/reference/src/server/sbox/sbox.rs     sbox, many_sbox, mul2 .. mul14
   /root/reference/src/server/sbox/many_wopbs.rs  many_wopbs_without_padding
   /root/reference/src/server/sbox/gen_lut.rs  gen_lut
 but batched (a leading block axis) and over flat uint64 arrays:
-  byte = [8][kN+1], state = [16][8][kN+1], round keys = [11][16][8][kN+1].
+  byte = [8][kN+1], state = [16][8][kN+1], AES key = [16 | 24 | 32][8][kN+1], round keys = [Nr+1][16][8][kN+1] with
+  Nr = 10 | 12 | 14 rounds (FIPS-197 Fig. 4).
 Arrays may be numpy (host; staged through HBM by the engine) or torch CUDA tensors (resident,
 asynchronous on the engine's stream).  All compute happens in libfheaes.so (HIP); this module
 only allocates outputs and forwards.  README.md:57-59 of the reference spells the methods
@@ -50,6 +52,18 @@ def _to_space(arr: np.ndarray, ref):
     # the copy ran on torch's current stream; the engine reads `dev` on ITS stream: finish the copy first
     torch.cuda.current_stream(ref.device).synchronize()
     return dev
+
+
+KEY_BYTES_TO_BITS = {16: 128, 24: 192, 32: 256}       # leading axis of an encrypted AES key
+ROUND_KEYS_TO_BITS = {11: 128, 13: 192, 15: 256}      # leading axis of its round keys, Nr + 1
+
+
+def _key_bits(arr, table, what, ndim=4) -> int:
+    """the AES key size an encrypted key / round-key array stands for; any other leading size is refused before the library is called"""
+    lead = int(arr.shape[0])
+    if arr.ndim != ndim or lead not in table:
+        raise ValueError("%s must be [%s]%s[8][kN+1], got shape %s" % (what, " | ".join(map(str, table)), "[16]" * (ndim - 3), tuple(arr.shape)))
+    return table[lead]
 
 
 class Server:
@@ -106,35 +120,57 @@ class Server:
 
     # ---- Server API -------------------------------------------------------------
     def aes_key_expansion(self, key):
-        """server.rs:107: key [16][8][kN+1] -> round keys [11][16][8][kN+1]."""
-        rk = _empty_like(key, (11, 16, 8, self.params.big1))
-        self.engine.aes_key_expansion(key, rk)
+        """server.rs:107: key [16][8][kN+1] -> round keys [11][16][8][kN+1]; a key of 24 / 32 bytes (AES-192 / AES-256, FIPS-197
+        section 5.2) -> [13 | 15][16][8][kN+1]."""
+        bits = _key_bits(key, KEY_BYTES_TO_BITS, "key", ndim=3)
+        rk = _empty_like(key, (bits // 32 + 7, 16, 8, self.params.big1))
+        if bits == 128:
+            self.engine.aes_key_expansion(key, rk)
+        else:
+            self.engine.aes_key_expansion_bits(key, bits, rk)
         return rk
 
     def aes_encrypt(self, encrypted_round_keys, state):
-        """server.rs:39, in place.  state [16][8][kN+1] or a batch [B][16][8][kN+1]."""
+        """server.rs:39, in place.  state [16][8][kN+1] or a batch [B][16][8][kN+1]; 11 / 13 / 15 round keys: AES-128 / 192 / 256."""
+        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
-        self.engine.aes_encrypt(encrypted_round_keys, state, n_blocks)
+        if bits == 128:
+            self.engine.aes_encrypt(encrypted_round_keys, state, n_blocks)
+        else:
+            self.engine.aes_encrypt_bits(encrypted_round_keys, bits, state, n_blocks)
         return state
 
     def aes_decrypt(self, encrypted_round_keys, state):
-        """server.rs:67, in place."""
+        """server.rs:67, in place; 11 / 13 / 15 round keys: AES-128 / 192 / 256."""
+        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
-        self.engine.aes_decrypt(encrypted_round_keys, state, n_blocks)
+        if bits == 128:
+            self.engine.aes_decrypt(encrypted_round_keys, state, n_blocks)
+        else:
+            self.engine.aes_decrypt_bits(encrypted_round_keys, bits, state, n_blocks)
         return state
 
     def aes_decryption_round_keys(self, round_keys):
-        """round keys [11][16][8][kN+1] -> the equivalent inverse cipher's (FIPS-197 section 5.3.5): w[0], InvMixColumns(w[1..9]) refreshed
-        to nominal noise, w[10].  Once per AES key (2 x 1,152 bit circuit bootstraps); feeds aes_decrypt_equivalent."""
-        dw = _empty_like(round_keys, (11, 16, 8, self.params.big1))
-        self.engine.aes_decryption_round_keys(round_keys, dw)
+        """round keys [Nr+1][16][8][kN+1] -> the equivalent inverse cipher's (FIPS-197 section 5.3.5): w[0], InvMixColumns(w[1..Nr-1])
+        refreshed to nominal noise, w[Nr].  Once per AES key (2 x 128 (Nr - 1) bit circuit bootstraps: 2 x 1,152 at AES-128); feeds
+        aes_decrypt_equivalent."""
+        bits = _key_bits(round_keys, ROUND_KEYS_TO_BITS, "round keys")
+        dw = _empty_like(round_keys, tuple(round_keys.shape))
+        if bits == 128:
+            self.engine.aes_decryption_round_keys(round_keys, dw)
+        else:
+            self.engine.aes_decryption_round_keys_bits(round_keys, bits, dw)
         return dw
 
     def aes_decrypt_equivalent(self, dec_round_keys, state):
-        """the equivalent inverse cipher, in place: one WoPBS per round (10 per block, as aes_encrypt) instead of aes_decrypt's two
+        """the equivalent inverse cipher, in place: one WoPBS per round (Nr per block, as aes_encrypt) instead of aes_decrypt's two
         (server.rs:67-105, :86-89).  Same plaintext as aes_decrypt, other ciphertext words.  state [16][8][kN+1] or [B][16][8][kN+1]."""
+        bits = _key_bits(dec_round_keys, ROUND_KEYS_TO_BITS, "decryption round keys")
         n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
-        self.engine.aes_decrypt_equivalent(dec_round_keys, state, n_blocks)
+        if bits == 128:
+            self.engine.aes_decrypt_equivalent(dec_round_keys, state, n_blocks)
+        else:
+            self.engine.aes_decrypt_equivalent_bits(dec_round_keys, bits, state, n_blocks)
         return state
 
     def add_scalar(self, state, i):
