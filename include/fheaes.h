@@ -209,6 +209,26 @@ int fheaes_aes_decrypt_equivalent_bits(fheaes_ctx *ctx, const uint64_t *dec_roun
  * of 2*n_blocks words regardless of memspace).  The first-byte carry uses counter & 0xFF (the
  * reference's server.rs:182 is wrong for counters >= 256). */
 int fheaes_add_scalar(fheaes_ctx *ctx, uint64_t *state, uint64_t n_blocks, const uint64_t *counters_hi_lo, int memspace);
+/* Public blocks and CTR with a PUBLIC nonce (transciphering: the client sends data under AES-CTR and the AES key under FHE).  The reference
+ * has no counterpart: its CTR (main.rs:59-61) encrypts the IV and adds the block index homomorphically (add_scalar: a 16-step carry chain,
+ * 143 bit circuit bootstraps per block) before aes_encrypt.  With a public counter the carry chain is clear arithmetic, and most of the
+ * first two rounds is common to all blocks of a batch: a WoPBS is a deterministic function of its input words, so every DISTINCT S-Box
+ * input of the batch is evaluated once (the rule is exact; 128 consecutive AES-128 counters: 17,051 byte-WoPBS
+ * instead of 20,480).  Clear 128-bit values are HOST arrays of (hi, lo) pairs whatever `memspace` says, as fheaes_add_scalar's counters:
+ * value = hi << 64 | lo, byte 0 of the AES block the most significant.  round_keys [Nr+1][16][8][kN+1] and state_out
+ * [n_blocks][16][8][kN+1] live in `memspace`; key_bits as above; n_blocks = 0 is FHEAES_OK; FHEAES_DEVICE calls only enqueue.
+ *
+ * aes_encrypt of public blocks: word for word what fheaes_aes_encrypt_bits writes for a state of trivial ciphertexts of these blocks
+ * (mask 0, body = bit << 63). */
+int fheaes_aes_encrypt_public_bits(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *blocks_hi_lo,
+                                   uint64_t n_blocks, uint64_t *state_out, int memspace);
+/* SP 800-38A CTR: block i = E_K((iv + first_block + i) mod 2^128) ^ data[i], the clear data folded into the last linear layer (its bits
+ * added to the bodies); data_hi_lo == NULL: the keystream itself.  iv_hi_lo: one (hi, lo) pair; data_hi_lo: n_blocks pairs. */
+int fheaes_aes_ctr_bits(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *iv_hi_lo, uint64_t first_block,
+                        const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace);
+/* How many byte-WoPBS the two calls above run in each round for these blocks: unique_bytes_per_round[r - 1], r = 1..Nr (host logic only,
+ * no context, no GPU; fheaes_aes_encrypt_bits runs 16 n_blocks in every round). */
+int fheaes_aes_public_plan(const uint64_t *blocks_hi_lo, uint64_t n_blocks, uint32_t key_bits, uint64_t *unique_bytes_per_round);
 
 /* ---- measurement --------------------------------------------------------------- */
 #define FHEAES_STAGE_KEYSWITCH 0

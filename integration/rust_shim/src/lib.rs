@@ -14,6 +14,7 @@
 //!   GpuServer::aes_encrypt                 Server::aes_encrypt             src/server/server.rs:39   (batched over CTR blocks)
 //!   GpuServer::aes_decrypt                 Server::aes_decrypt             src/server/server.rs:67   (batched)
 //!   GpuServer::add_scalar                  Server::add_scalar              src/server/server.rs:172  (batched; carry defect of :182 fixed)
+//!   GpuServer::aes_ctr                     (no counterpart: CTR with a PUBLIC nonce, the loop of main.rs:55-64 without add_scalar)
 //!   GpuServer::clone_on                    (Server is shared by reference between rayon threads, main.rs:55-64; a GPU context
 //!                                           is cloned instead: one PCIe key upload, device-to-device copies, fheaes_clone_keys)
 //!   GpuServerGroup::{new, aes_encrypt, aes_decrypt, add_scalar}
@@ -83,6 +84,12 @@ extern "C" {
     pub fn fheaes_aes_decryption_round_keys_bits(ctx: *mut fheaes_ctx, round_keys: *const u64, key_bits: u32, dec_round_keys: *mut u64, memspace: c_int) -> c_int;
     pub fn fheaes_aes_decrypt_equivalent_bits(ctx: *mut fheaes_ctx, dec_round_keys: *const u64, key_bits: u32, state: *mut u64, n_blocks: u64, memspace: c_int) -> c_int;
     pub fn fheaes_add_scalar(ctx: *mut fheaes_ctx, state: *mut u64, n_blocks: u64, counters_hi_lo: *const u64, memspace: c_int) -> c_int;
+    // public blocks / CTR with a public nonce: clear u128 values as host (hi, lo) pairs; every distinct S-Box input evaluated once
+    pub fn fheaes_aes_encrypt_public_bits(ctx: *mut fheaes_ctx, round_keys: *const u64, key_bits: u32, blocks_hi_lo: *const u64, n_blocks: u64,
+                                          state_out: *mut u64, memspace: c_int) -> c_int;
+    pub fn fheaes_aes_ctr_bits(ctx: *mut fheaes_ctx, round_keys: *const u64, key_bits: u32, iv_hi_lo: *const u64, first_block: u64,
+                               data_hi_lo: *const u64, n_blocks: u64, state_out: *mut u64, memspace: c_int) -> c_int;
+    pub fn fheaes_aes_public_plan(blocks_hi_lo: *const u64, n_blocks: u64, key_bits: u32, unique_bytes_per_round: *mut u64) -> c_int;
 }
 
 // ------------------------------------------------------------------------------------------------ helpers
@@ -411,6 +418,39 @@ impl GpuServer {
         for (s, words) in states.iter_mut().zip(st.chunks_exact(state_words)) {
             rewrap_state(words, s);
         }
+    }
+
+    /// SP 800-38A CTR with a PUBLIC nonce, the whole loop of main.rs:55-64 in one call and without an encrypted IV:
+    /// block i = E_K((iv + first_block + i) mod 2^128) ^ data[i] (`data = None`: the keystream).  No counterpart in the reference,
+    /// which adds the block index to an encrypted IV (add_scalar) first.  11 / 13 / 15 round keys: AES-128 / 192 / 256.  The engine
+    /// evaluates every distinct S-Box input of the batch once (consecutive counters share most of rounds 1 and 2).
+    pub fn aes_ctr(&self, round_keys: &[Vec<Radix>], iv: u128, first_block: u64, n_blocks: usize, data: Option<&[u128]>) -> Vec<Vec<Radix>> {
+        let key_bits: u32 = match round_keys.len() {
+            11 => 128,
+            13 => 192,
+            15 => 256,
+            n => panic!("{} round keys: not an AES key size", n),
+        };
+        let mut rk = Vec::new();
+        for r in round_keys {
+            flatten_state(r, &mut rk);
+        }
+        let state_words = rk.len() / round_keys.len();
+        let iv_hi_lo = [(iv >> 64) as u64, iv as u64];
+        let data_hi_lo: Option<Vec<u64>> = data.map(|d| {
+            assert_eq!(d.len(), n_blocks);
+            d.iter().flat_map(|c| [(c >> 64) as u64, *c as u64]).collect()
+        });
+        let mut out = vec![0u64; n_blocks * state_words];
+        let rc = unsafe {
+            fheaes_aes_ctr_bits(self.ctx, rk.as_ptr(), key_bits, iv_hi_lo.as_ptr(), first_block,
+                                data_hi_lo.as_ref().map_or(std::ptr::null(), |d| d.as_ptr()), n_blocks as u64, out.as_mut_ptr(), FHEAES_HOST)
+        };
+        assert!(rc == 0, "{}", self.last_error());
+        let byte_words = state_words / 16;
+        out.chunks_exact(state_words)
+            .map(|block| block.chunks_exact(byte_words).zip(round_keys[0].iter()).map(|(w, like)| rewrap(w, like)).collect())
+            .collect()
     }
 }
 

@@ -61,6 +61,9 @@ SIGNATURES = {
     "fheaes_aes_decryption_round_keys_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_int]),
     "fheaes_aes_decrypt_equivalent_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint64, _c.c_int]),
     "fheaes_add_scalar": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _u64p, _c.c_int]),
+    "fheaes_aes_encrypt_public_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_ctr_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _c.c_uint64, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_public_plan": (_c.c_int, [_u64p, _c.c_uint64, _c.c_uint32, _u64p]),
     "fheaes_profile_enable": (_c.c_int, [_ctx, _c.c_int]),
     "fheaes_profile_reset": (_c.c_int, [_ctx]),
     "fheaes_profile_read": (_c.c_int, [_ctx, _c.c_int, _dp, _u64p, _u64p]),
@@ -289,6 +292,21 @@ class Engine:
             cnt[i, 1] = int(v) & (2 ** 64 - 1)
         self._check(self._lib.fheaes_add_scalar(self._h, _ptr(state)[0], n_blocks, cnt.ctypes.data_as(_u64p), self._space(state)))
 
+    # public blocks / CTR with a public nonce: clear 128-bit values travel as host (hi, lo) pairs, as add_scalar's counters
+    def aes_encrypt_public_bits(self, round_keys, key_bits: int, blocks, state_out):
+        cnt = u128_pairs(blocks)
+        self._check(self._lib.fheaes_aes_encrypt_public_bits(self._h, _ptr(round_keys)[0], key_bits, cnt.ctypes.data_as(_u64p), len(cnt),
+                                                             _ptr(state_out)[0], self._space(round_keys, state_out)))
+
+    def aes_ctr_bits(self, round_keys, key_bits: int, iv: int, first_block: int, data, n_blocks: int, state_out):
+        ivp = u128_pairs([iv])
+        dat = u128_pairs(data) if data is not None else None
+        if dat is not None and len(dat) != n_blocks:
+            raise ValueError("one data block per counter block expected")
+        self._check(self._lib.fheaes_aes_ctr_bits(self._h, _ptr(round_keys)[0], key_bits, ivp.ctypes.data_as(_u64p), first_block,
+                                                  dat.ctypes.data_as(_u64p) if dat is not None else None, n_blocks, _ptr(state_out)[0],
+                                                  self._space(round_keys, state_out)))
+
     # -- measurement ------------------------------------------------------------
     def profile_enable(self, on: bool = True):
         self._check(self._lib.fheaes_profile_enable(self._h, int(on)))
@@ -345,6 +363,31 @@ class Engine:
         out = np.empty((p.pbs_level, p.k + 1, p.k + 1, 256, 2), dtype=np.float64)
         self._check(self._lib.fheaes_read_bsk_fourier(self._h, i, out.ctypes.data_as(_dp)))
         return out
+
+
+def u128_pairs(values) -> np.ndarray:
+    """128-bit values (ints, or 16 `bytes` each with byte 0 the most significant) -> the (hi, lo) uint64 pairs of the C ABI, [n][2]"""
+    out = np.zeros((len(values), 2), dtype=np.uint64)
+    for i, v in enumerate(values):
+        if isinstance(v, (bytes, bytearray)):
+            if len(v) != 16:
+                raise ValueError("an AES block has 16 bytes, got %d" % len(v))
+            v = int.from_bytes(v, "big")
+        v = int(v)
+        if not 0 <= v < 1 << 128:
+            raise ValueError("a block is a 128-bit value")
+        out[i, 0], out[i, 1] = v >> 64, v & (2 ** 64 - 1)
+    return out
+
+
+def aes_public_plan(blocks, key_bits: int = 128) -> list[int]:
+    """byte-WoPBS per round (rounds 1..Nr) that aes_encrypt_public / aes_ctr run for these blocks (fheaes_aes_public_plan: host only, no GPU)"""
+    cnt = u128_pairs(blocks)
+    out = np.zeros(14, dtype=np.uint64)
+    rc = load_library().fheaes_aes_public_plan(cnt.ctypes.data_as(_u64p), len(cnt), key_bits, out.ctypes.data_as(_u64p))
+    if rc != 0:
+        raise FheAesError(rc, "fheaes_aes_public_plan: key_bits must be 128, 192 or 256")
+    return [int(x) for x in out[:{128: 10, 192: 12, 256: 14}[key_bits]]]
 
 
 def get_twiddles() -> np.ndarray:

@@ -116,6 +116,11 @@ def aes_encrypt_block(key, block: int) -> int:
     return _u128(a ^ b for a, b in zip(s, rk[nr]))
 
 
+def ctr_keystream(key, iv: int, first_block: int, n_blocks: int) -> list[int]:
+    """SP 800-38A CTR: keystream block i = E_K((iv + first_block + i) mod 2^128), i < n_blocks, as u128 (byte 0 = MSB)"""
+    return [aes_encrypt_block(key, (iv + first_block + i) % (1 << 128)) for i in range(n_blocks)]
+
+
 def aes_decrypt_block(key, block: int) -> int:
     """FIPS-197 Fig. 12, the inverse cipher, in the order Server::aes_decrypt takes it (AddRoundKey before InvMixColumns)"""
     rk = expand_key(key)

@@ -334,6 +334,15 @@ class Client:
         bits = ((v[:, None] >> np.arange(8, dtype=np.uint64)[None, :]) & 1).astype(np.uint8)
         return self.encrypt_bits(bits)
 
+    def trivial_bytes(self, values) -> np.ndarray:
+        """noise-free "encryptions" of PUBLIC bytes that anyone can write down: mask 0, body = bit << 63; [..., 8, kN+1] for values
+        of shape [...].  A legal input wherever an encrypted byte is (a state of 16 n such bytes is what Server.aes_encrypt_public
+        computes on, word for word)."""
+        v = np.asarray(values, dtype=np.uint64)
+        out = np.zeros(v.shape + (8, self.params.big1), dtype=np.uint64)
+        out[..., self.params.big] = ((v[..., None] >> np.arange(8, dtype=np.uint64)) & np.uint64(1)) << np.uint64(63)
+        return out
+
     def encrypt_u128(self, x: int) -> np.ndarray:
         """one AES state / key: [16][8][kN+1]"""
         return self.encrypt_bytes(u128_to_bytes(x))

@@ -14,6 +14,7 @@
 #include <mutex>
 #include <string>
 #include <type_traits>
+#include <unordered_map>
 #include <vector>
 
 #include "knobs.h"
@@ -1645,6 +1646,200 @@ int fheaes_add_scalar(fheaes_ctx *c, uint64_t *state, uint64_t n_blocks, const u
     TRY(s.in(state, n_blocks * sw * 8, &dst));
     TRY(add_scalar_dev(c, (uint64_t *)dst, n_blocks, counters_hi_lo));
     return s.out(state, dst, n_blocks * sw * 8);
+}
+
+// ---- public blocks and CTR with a public nonce ------------------------------------------------
+// aes_encrypt on PUBLIC blocks (trivial ciphertexts) with every distinct S-Box input of the batch evaluated once.  A WoPBS is a
+// deterministic function of its input words, so two state bytes with word-equal inputs need one evaluation.  The rule that finds them
+// is exact and runs on the host before anything is enqueued: every S-Box input gets an id, round by round,
+//   round 1:   id(b, p) = (p, byte p of block b)                      -- the input is rk[0][p] + trivial(byte)
+//   round r+1: id(b, p) = (p, id_r(b, s_0), .., id_r(b, s_3))         -- s_j: the four sources of table_enc_round() for position p
+// and equal tuples are one id: sums of word-equal ciphertexts plus the same round-key byte are word-equal.  The ids of a round are its
+// POOL; round r runs one WoPBS over pool r and an indexed gather (kern_linear.h) into pool r+1, the last gather writes [block][16].
+struct PublicPlan {
+    struct Layer { size_t head, term; uint32_t n, terms; };     // offsets into `words`; n outputs of `terms` terms each
+    std::vector<Layer> layers;      // [0]: pool of round 1 (no terms), [r]: pool of round r+1 (4 terms), [Nr]: the state, 16 n_blocks bytes (1 term)
+    std::vector<uint32_t> words;    // every layer's PUBLIC_HEAD words, then its PUBLIC_TERM words: one upload per call
+    uint64_t max_vp_bytes_per_bw = 0;                            // max over the rounds of pool size x LUTs of that round's set
+};
+
+static inline uint32_t u128_byte(const uint64_t *hi_lo, int p) { return (uint32_t)((p < 8 ? hi_lo[0] >> (8 * (7 - p)) : hi_lo[1] >> (8 * (15 - p))) & 0xFF); }
+
+struct PublicKey5 {
+    uint32_t v[5];
+    bool operator==(const PublicKey5 &o) const { return !memcmp(v, o.v, sizeof v); }
+};
+struct PublicKey5Hash {
+    size_t operator()(const PublicKey5 &k) const
+    {
+        uint64_t h = 0xCBF29CE484222325ull;
+        for (uint32_t x : k.v) { h ^= x; h *= 0x100000001B3ull; }
+        return (size_t)(h ^ (h >> 29));
+    }
+};
+
+// blocks / data: n_blocks (hi, lo) pairs, data may be null
+static void public_plan(const uint64_t *blocks, const uint64_t *data, uint64_t n_blocks, int nr, PublicPlan &pl)
+{
+    const GatherTable t_round = table_enc_round(), t_shift = table_shift_rows(false);
+    const uint64_t nbytes = 16 * n_blocks;
+    std::vector<uint32_t> id(nbytes), next(nbytes);
+    pl.layers.clear(); pl.words.clear();
+    pl.layers.reserve((size_t)nr + 1);
+    {   // round 1
+        std::vector<int64_t> seen(16 * 256, -1);
+        std::vector<uint32_t> head;
+        for (uint64_t b = 0; b < n_blocks; ++b) for (int p = 0; p < 16; ++p) {
+            const uint32_t v = u128_byte(blocks + 2 * b, p);
+            int64_t &s = seen[(size_t)p * 256 + v];
+            if (s < 0) { s = (int64_t)head.size(); head.push_back(PUBLIC_HEAD(p, v)); }
+            id[16 * b + p] = (uint32_t)s;
+        }
+        pl.layers.push_back({0, head.size(), (uint32_t)head.size(), 0});
+        pl.words = std::move(head);
+    }
+    for (int r = 1; r < nr; ++r) {   // pool of round r + 1 from the ids of round r
+        std::unordered_map<PublicKey5, uint32_t, PublicKey5Hash> seen;
+        seen.reserve(nbytes);
+        std::vector<uint32_t> head, term;
+        for (uint64_t b = 0; b < n_blocks; ++b) for (int p = 0; p < 16; ++p) {
+            PublicKey5 k{{(uint32_t)p, 0, 0, 0, 0}};
+            for (int j = 0; j < 4; ++j) k.v[1 + j] = id[16 * b + t_round.src[p][j]];
+            auto ins = seen.emplace(k, (uint32_t)head.size());
+            if (ins.second) {
+                head.push_back(PUBLIC_HEAD(p, 0));
+                for (int j = 0; j < 4; ++j) term.push_back(PUBLIC_TERM(k.v[1 + j], t_round.lut[p][j]));
+            }
+            next[16 * b + p] = ins.first->second;
+        }
+        id.swap(next);
+        const size_t h0 = pl.words.size();
+        pl.layers.push_back({h0, h0 + head.size(), (uint32_t)head.size(), 4});
+        pl.words.insert(pl.words.end(), head.begin(), head.end());
+        pl.words.insert(pl.words.end(), term.begin(), term.end());
+    }
+    {   // ShiftRows + the last round key (+ CTR's clear data) into [block][16]
+        const size_t h0 = pl.words.size();
+        pl.layers.push_back({h0, h0 + nbytes, (uint32_t)nbytes, 1});
+        pl.words.resize(h0 + 2 * nbytes);
+        for (uint64_t b = 0; b < n_blocks; ++b) for (int p = 0; p < 16; ++p) {
+            pl.words[h0 + 16 * b + p] = PUBLIC_HEAD(p, data ? u128_byte(data + 2 * b, p) : 0);
+            pl.words[h0 + nbytes + 16 * b + p] = PUBLIC_TERM(id[16 * b + t_shift.src[p][0]], 0);
+        }
+    }
+    pl.max_vp_bytes_per_bw = 0;
+    for (int r = 1; r <= nr; ++r) pl.max_vp_bytes_per_bw = std::max<uint64_t>(pl.max_vp_bytes_per_bw, (uint64_t)pl.layers[r - 1].n * (r < nr ? 3 : 1));
+}
+
+#define PUBLIC_MAX_BLOCKS (1ull << 26)      /* 16 n pool entries x 4 must fit a PUBLIC_TERM word */
+
+static int launch_public_round1(fheaes_ctx *c, const uint32_t *head, const uint64_t *rk0, uint64_t *out, uint64_t n_pool)
+{
+    TRY(noise_guard(c, 1, "the initial AddRoundKey on public bytes"));          // a trivial ciphertext carries no noise
+    StageScope sc(c, FHEAES_STAGE_LINEAR, (n_pool + 15) / 16);
+    dim3 grid((8 * c->big1 + 1023) / 1024, (unsigned)std::min<uint64_t>(n_pool, 65535));
+    hipLaunchKernelGGL(public_round1_kernel, grid, dim3(256), 0, c->stream, head, rk0, out, n_pool, c->big1);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+static int launch_gather_indexed(fheaes_ctx *c, const uint64_t *pool, uint32_t n_luts, const uint32_t *head, const uint32_t *term, uint32_t terms,
+                                 const uint64_t *rk, uint64_t *out, uint64_t n_out)
+{
+    TRY(noise_guard(c, terms + 1u, "the indexed linear layer (MixColumns / ShiftRows + AddRoundKey over a pool)"));
+    StageScope sc(c, FHEAES_STAGE_LINEAR, (n_out + 15) / 16);
+    dim3 grid((8 * c->big1 + 1023) / 1024, (unsigned)std::min<uint64_t>(n_out, 65535));
+    hipLaunchKernelGGL(gather_add_indexed_kernel, grid, dim3(256), 0, c->stream, pool, n_luts, head, term, terms, rk, out, n_out, c->big1);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+// `out` [n_blocks][16][8][kN+1] doubles as the pool buffer: no pool has more than 16 n_blocks entries
+static int aes_public_dev(fheaes_ctx *c, const uint64_t *rk, const PublicPlan &pl, int nr, uint64_t *out)
+{
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw;
+    // the index tables go through the context's pinned buffer (as add_scalar's counter bytes): the call only enqueues
+    const size_t tab_bytes = pl.words.size() * sizeof(uint32_t);
+    if (c->pin_ev) HIP_TRY(c, hipEventSynchronize(c->pin_ev));
+    else HIP_TRY(c, hipEventCreateWithFlags(&c->pin_ev, hipEventDisableTiming));
+    if (c->pin_bytes < tab_bytes) {
+        if (c->pin) { HIP_TRY(c, hipHostFree(c->pin)); c->pin = nullptr; c->pin_bytes = 0; }
+        HIP_TRY(c, hipHostMalloc((void **)&c->pin, tab_bytes, hipHostMallocDefault));
+        c->pin_bytes = tab_bytes;
+    }
+    memcpy(c->pin, pl.words.data(), tab_bytes);
+    TRY(ensure(c, c->ws_misc, tab_bytes));
+    const uint32_t *tab = (const uint32_t *)c->ws_misc.p;
+    HIP_TRY(c, hipMemcpyAsync(c->ws_misc.p, c->pin, tab_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(c->pin_ev, c->stream));
+    TRY(ensure(c, c->ws_vp, pl.max_vp_bytes_per_bw * bw * 8));               // the largest pool, not 16 n
+    uint64_t *vp = (uint64_t *)c->ws_vp.p;
+    TRY(launch_public_round1(c, tab + pl.layers[0].head, rk, out, pl.layers[0].n));
+    for (int round = 1; round <= nr; ++round) {
+        const PublicPlan::Layer &in = pl.layers[round - 1], &to = pl.layers[round];
+        TRY(many_sbox_dev(c, out, in.n, round < nr ? LUTSET_ENC_ROUND : LUTSET_SBOX, vp));
+        TRY(launch_gather_indexed(c, vp, round < nr ? 3 : 1, tab + to.head, tab + to.term, to.terms, rk + (uint64_t)round * sw, out, to.n));
+    }
+    return FHEAES_OK;
+}
+
+static int aes_public(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *blocks, const uint64_t *data, uint64_t n_blocks,
+                      uint64_t *state_out, int memspace)
+{
+    const int nr = aes_rounds(key_bits);
+    if (n_blocks > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %llu", (unsigned long long)PUBLIC_MAX_BLOCKS);
+    HIP_TRY(c, hipSetDevice(c->device));
+    PublicPlan pl;
+    public_plan(blocks, data, n_blocks, nr, pl);
+    if (memspace == FHEAES_DEVICE) return aes_public_dev(c, round_keys, pl, nr, state_out);
+    Staged s(c);
+    void *drk, *dst;
+    const uint64_t sw = 16ull * 8 * c->big1;
+    TRY(s.in(round_keys, (uint64_t)(nr + 1) * sw * 8, &drk));
+    TRY(s.alloc(&dst, n_blocks * sw * 8));
+    TRY(aes_public_dev(c, (const uint64_t *)drk, pl, nr, (uint64_t *)dst));
+    return s.out(state_out, dst, n_blocks * sw * 8);
+}
+
+int fheaes_aes_encrypt_public_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *blocks_hi_lo, uint64_t n_blocks,
+                                   uint64_t *state_out, int memspace)
+{
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!round_keys || !blocks_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    if (n_blocks == 0) return FHEAES_OK;
+    return aes_public(c, round_keys, key_bits, blocks_hi_lo, nullptr, n_blocks, state_out, memspace);
+}
+
+int fheaes_aes_ctr_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *iv_hi_lo, uint64_t first_block,
+                        const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
+{
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!round_keys || !iv_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    if (n_blocks == 0) return FHEAES_OK;
+    if (n_blocks > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %llu", (unsigned long long)PUBLIC_MAX_BLOCKS);
+    // counter block i = (iv + first_block + i) mod 2^128 (SP 800-38A appendix B.1 with m = 128)
+    std::vector<uint64_t> ctr(2 * n_blocks);
+    const uint64_t lo0 = iv_hi_lo[1] + first_block, hi0 = iv_hi_lo[0] + (lo0 < first_block ? 1 : 0);
+    for (uint64_t i = 0; i < n_blocks; ++i) {
+        const uint64_t lo = lo0 + i;
+        ctr[2 * i] = hi0 + (lo < lo0 ? 1 : 0);
+        ctr[2 * i + 1] = lo;
+    }
+    return aes_public(c, round_keys, key_bits, ctr.data(), data_hi_lo, n_blocks, state_out, memspace);
+}
+
+int fheaes_aes_public_plan(const uint64_t *blocks_hi_lo, uint64_t n_blocks, uint32_t key_bits, uint64_t *unique_bytes_per_round)
+{
+    const int nr = aes_rounds(key_bits);
+    if (!blocks_hi_lo || !unique_bytes_per_round || !nr || n_blocks > PUBLIC_MAX_BLOCKS) return FHEAES_ERR_INVALID;
+    PublicPlan pl;
+    if (n_blocks) public_plan(blocks_hi_lo, nullptr, n_blocks, nr, pl);
+    for (int r = 1; r <= nr; ++r) unique_bytes_per_round[r - 1] = n_blocks ? pl.layers[r - 1].n : 0;
+    return FHEAES_OK;
 }
 
 // ---- measurement ------------------------------------------------------------------------------

@@ -54,6 +54,67 @@ __global__ void add_const_byte_kernel(uint64_t *byte_ct, uint32_t lwe_words, uin
     if (j < 8) byte_ct[(uint64_t)j * lwe_words + lwe_words - 1] += (uint64_t)((value >> j) & 1u) << 63;
 }
 
+// ---- public blocks / CTR with a public nonce (fheaes_aes_encrypt_public_bits, fheaes_aes_ctr_bits) ------------------------------
+// Every distinct S-Box input of a batch of PUBLIC blocks is evaluated once: a round works on a POOL of distinct bytes instead of
+// [n_blocks][16].  One uint32 head word per pool entry says where it sits in the state and which clear byte goes with it:
+#define PUBLIC_HEAD(pos, clear) ((uint32_t)(pos) | ((uint32_t)(clear) << 8))     // bits 0..3: state position p, bits 8..15: clear byte
+// and one uint32 per term says what to sum: WoPBS output `lut` of pool entry `src` of the round before
+#define PUBLIC_TERM(src, lut) (((uint32_t)(src) << 2) | (uint32_t)(lut))
+
+// Pool of round 1: out[u] = rk0[p_u] + trivial(v_u), i.e. the round key's words with ((v_u >> bit) & 1) << 63 added to each body:
+// word for word the initial AddRoundKey on a trivial ciphertext (mask 0, body = bit << 63) of v_u.
+// head: [n_pool]; rk0: [16][byte_words]; out: [n_pool][byte_words]; byte_words = 8 * lwe_words
+__global__ __launch_bounds__(256) void public_round1_kernel(const uint32_t *head, const uint64_t *rk0, uint64_t *out, uint64_t n_pool,
+                                                            uint32_t lwe_words)
+{
+    const uint32_t byte_words = 8 * lwe_words;
+    for (uint64_t u = blockIdx.y; u < n_pool; u += gridDim.y) {
+        const uint32_t h = head[u], pos = h & 15u, clear = (h >> 8) & 0xFFu;
+        const uint64_t *kb = rk0 + (uint64_t)pos * byte_words;
+        uint64_t *ob = out + u * byte_words;
+        for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
+            const uint32_t bit = w / lwe_words;
+            uint64_t v = kb[w];
+            if (w - bit * lwe_words == lwe_words - 1) v += (uint64_t)((clear >> bit) & 1u) << 63;
+            ob[w] = v;
+        }
+    }
+}
+
+// The linear layer between two pools, and from the last pool into the state: gather_add_kernel with the sources of every output
+// byte read from a table in device memory instead of being the same for every block.
+//   out[u] = sum_{j < terms} pool[src_uj][lut_uj] + rk[p_u] + trivial(clear_u)
+// pool: [n_src][n_luts][byte_words] (WoPBS outputs of the round before); head: [n_out] PUBLIC_HEAD; term: [n_out][terms] PUBLIC_TERM;
+// rk: [16][byte_words]; out: [n_out][byte_words].  clear_u is 0 except in CTR's last layer (the data byte).  Wrapping uint64 sums: any
+// order of the terms gives gather_add_kernel's words.
+__global__ __launch_bounds__(256) void gather_add_indexed_kernel(const uint64_t *pool, uint32_t n_luts, const uint32_t *head, const uint32_t *term,
+                                                                 uint32_t terms, const uint64_t *rk, uint64_t *out, uint64_t n_out, uint32_t lwe_words)
+{
+    const uint32_t byte_words = 8 * lwe_words;
+    for (uint64_t u = blockIdx.y; u < n_out; u += gridDim.y) {
+        const uint32_t h = head[u], pos = h & 15u, clear = (h >> 8) & 0xFFu;
+        const uint64_t *kb = rk + (uint64_t)pos * byte_words;
+        const uint64_t *s[4];                                    // terms <= 4; fully unrolled so that the pointers stay in registers
+#pragma unroll
+        for (uint32_t t = 0; t < 4; ++t) {
+            const uint32_t e = t < terms ? term[u * terms + t] : 0u;
+            s[t] = pool + ((uint64_t)(e >> 2) * n_luts + (e & 3u)) * byte_words;
+        }
+        uint64_t *ob = out + u * byte_words;
+        for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
+            uint64_t v = kb[w];
+#pragma unroll
+            for (uint32_t t = 0; t < 4; ++t)
+                if (t < terms) v += s[t][w];
+            if (clear) {
+                const uint32_t bit = w / lwe_words;
+                if (w - bit * lwe_words == lwe_words - 1) v += (uint64_t)((clear >> bit) & 1u) << 63;
+            }
+            ob[w] = v;
+        }
+    }
+}
+
 // Builds the radix inputs of add_scalar (server.rs:216-222): in[blk][0..8) = state[blk][byte] and, for
 // bits == 9, in[blk][8] = carry[blk]
 __global__ __launch_bounds__(256) void pack9_kernel(const uint64_t *state, const uint64_t *carry, uint64_t *in9,

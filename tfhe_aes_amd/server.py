@@ -3,7 +3,8 @@
 Same names, argument meaning and error behaviour as
   /root/reference/src/server/server.rs        Server::{new, aes_encrypt, aes_decrypt, aes_key_expansion, add_scalar}
   (plus aes_decryption_round_keys / aes_decrypt_equivalent: the FIPS-197 section 5.3.5 equivalent inverse cipher; plus AES-192
-  and AES-256, which the reference does not have: the same methods read the key size from the leading axis of the key / round keys)
+  and AES-256, which the reference does not have: the same methods read the key size from the leading axis of the key / round keys;
+  plus aes_encrypt_public / aes_ctr: public blocks and SP 800-38A CTR with a PUBLIC nonce, every distinct S-Box input evaluated once)
   /root/reference/src/server/sbox/sbox.rs     sbox, many_sbox, mul2 .. mul14
   /root/reference/src/server/sbox/many_wopbs.rs  many_wopbs_without_padding
   /root/reference/src/server/sbox/gen_lut.rs  gen_lut
@@ -64,6 +65,20 @@ def _key_bits(arr, table, what, ndim=4) -> int:
     if arr.ndim != ndim or lead not in table:
         raise ValueError("%s must be [%s]%s[8][kN+1], got shape %s" % (what, " | ".join(map(str, table)), "[16]" * (ndim - 3), tuple(arr.shape)))
     return table[lead]
+
+
+def _data_blocks(data, n_blocks: int):
+    """CTR's clear data as a list of n_blocks blocks (ints or 16 bytes each); one `bytes` of 16 n_blocks is cut into blocks"""
+    if data is None:
+        return None
+    if isinstance(data, (bytes, bytearray)):
+        if len(data) != 16 * n_blocks:
+            raise ValueError("data must hold 16 bytes per block (a partial last block: pad it, then slice the result)")
+        return [bytes(data[16 * i:16 * i + 16]) for i in range(n_blocks)]
+    data = list(data)
+    if len(data) != n_blocks:
+        raise ValueError("one data block per counter block expected")
+    return data
 
 
 class Server:
@@ -182,6 +197,41 @@ class Server:
         self.engine.add_scalar(state, n_blocks, counters)
         return state
 
+    def aes_encrypt_public(self, encrypted_round_keys, blocks, out=None):
+        """aes_encrypt of PUBLIC blocks (ints, or 16 `bytes` each) under encrypted round keys: a new [n][16][8][kN+1] (or `out`), in the memory
+        space of the round keys, word for word aes_encrypt(round keys, Client.trivial_bytes(blocks)); every distinct S-Box input of
+        the batch is evaluated once (include/fheaes.h: fheaes_aes_encrypt_public_bits)."""
+        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
+        blocks = list(blocks)
+        out = self._public_out(encrypted_round_keys, len(blocks), out)
+        self.engine.aes_encrypt_public_bits(encrypted_round_keys, bits, blocks, out)
+        return out
+
+    def aes_ctr(self, encrypted_round_keys, iv, first_block: int, n_blocks: int, data=None, out=None):
+        """SP 800-38A CTR with a PUBLIC nonce: block i = E_K((iv + first_block + i) mod 2^128) ^ data[i] as a new [n_blocks][16][8][kN+1]
+        (data None: the keystream).  `iv`: an int or 16 bytes; `data`: n_blocks ints / 16-byte blocks, or one `bytes` of 16 n_blocks."""
+        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
+        n_blocks, first_block = int(n_blocks), int(first_block)
+        if n_blocks < 0 or first_block < 0:
+            raise ValueError("n_blocks and first_block must be >= 0")
+        iv = int.from_bytes(iv, "big") if isinstance(iv, (bytes, bytearray)) else int(iv)
+        if not 0 <= iv < 1 << 128:
+            raise ValueError("iv is a 128-bit value")
+        if first_block >> 64:                    # the C ABI takes a 64-bit block index; the counter is mod 2^128 anyway
+            iv, first_block = (iv + (first_block >> 64 << 64)) % (1 << 128), first_block & (2 ** 64 - 1)
+        data = _data_blocks(data, n_blocks)
+        out = self._public_out(encrypted_round_keys, n_blocks, out)
+        self.engine.aes_ctr_bits(encrypted_round_keys, bits, iv, first_block, data, n_blocks, out)
+        return out
+
+    def _public_out(self, round_keys, n_blocks: int, out):
+        shape = (n_blocks, 16, 8, self.params.big1)
+        if out is None:
+            return _empty_like(round_keys, shape)
+        if tuple(out.shape) != shape:
+            raise ValueError("out must be %s, got %s" % (shape, tuple(out.shape)))
+        return out
+
     # README.md:57-59 spellings
     aes_encryption = aes_encrypt
     aes_decryption = aes_decrypt
@@ -257,6 +307,23 @@ class ServerGroup:
     def add_scalar(self, state, counters):
         counters = list(counters)
         return self._fan_out(lambda s, shard, lo: s.add_scalar(shard, counters[lo:lo + int(shard.shape[0])]), state)
+
+    def _fan_out_new(self, round_keys, n, fn):
+        """the public-input calls produce a NEW [n][16][8][kN+1]: allocate it next to the round keys, let every context fill its shard"""
+        out = _empty_like(round_keys, (n, 16, 8, self.params.big1))
+        return self._fan_out(lambda s, shard, lo: fn(s, shard, lo, int(shard.shape[0])), out)
+
+    def aes_encrypt_public(self, round_keys, blocks):
+        """Server.aes_encrypt_public, the blocks sharded contiguously; each context plans the sharing inside its own shard"""
+        blocks = list(blocks)
+        return self._fan_out_new(round_keys, len(blocks), lambda s, shard, lo, k: s.aes_encrypt_public(round_keys, blocks[lo:lo + k], out=shard))
+
+    def aes_ctr(self, round_keys, iv, first_block: int, n_blocks: int, data=None):
+        """Server.aes_ctr: context i takes the counter blocks of its shard (first_block + lo ..) and the matching data"""
+        n_blocks = int(n_blocks)
+        data = _data_blocks(data, n_blocks)
+        return self._fan_out_new(round_keys, n_blocks, lambda s, shard, lo, k: s.aes_ctr(round_keys, iv, int(first_block) + lo, k,
+                                                                                        None if data is None else data[lo:lo + k], out=shard))
 
     def aes_key_expansion(self, key):
         return self.servers[0].aes_key_expansion(key)
