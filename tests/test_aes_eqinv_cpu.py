@@ -2,7 +2,7 @@
 ordinary inverse cipher, the library exports the two entry points and refuses a NULL context, and the word-exact model the GPU tests
 compare against (tests/test_gpu_aes_eqinv.py) decrypts to the plaintext at PARAM_TOY.
 
-The model is written here from FIPS-197 rather than from engine.hip: the oracle's WoPBS with LUTs built by server.gen_lut from the
+The model is written here from FIPS-197 rather than from csrc/aes_schedule.h: the oracle's WoPBS with LUTs built by server.gen_lut from the
 aes_clear tables, and numpy uint64 wrapping sums for the linear layers (InvShiftRows, InvMixColumns, AddRoundKey)."""
 import ctypes
 

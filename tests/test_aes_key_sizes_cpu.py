@@ -2,7 +2,7 @@
 vectors of FIPS-197 appendices A and C and of SP 800-38A, the five `_bits` entry points of the library, and the word-exact model the GPU
 tests compare against (tests/test_gpu_aes_key_sizes.py).
 
-The CPU oracle has AES-128 schedules only, so the model is written here from FIPS-197 rather than from engine.hip: the oracle's WoPBS
+The CPU oracle has AES-128 schedules only, so the model is written here from FIPS-197 rather than from csrc/aes_schedule.h: the oracle's WoPBS
 with LUTs built by server.gen_lut from the aes_clear tables, and numpy uint64 wrapping sums for the linear layers (RotWord, Rcon,
 ShiftRows, MixColumns, AddRoundKey and their inverses).  At 128 bits it has to reproduce the oracle's own key expansion, encryption and
 decryption word for word; that pins its conventions before it is trusted for the other two key sizes."""

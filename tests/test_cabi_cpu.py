@@ -78,7 +78,7 @@ def test_param_struct_layout_matches_header():
 
 
 def test_k2_launch_plan_covers_the_batch_in_whole_generations():
-    """host logic of engine.hip::launch_cbs_pbs (no GPU): how a blind-rotation batch is cut into workgroups.  Latency form (0) up to 256
+    """host logic of engine_launch.h::k2_plan (no GPU): how a blind-rotation batch is cut into workgroups.  Latency form (0) up to 256
     bits; up to 768 bits one unit of kern_blindrot16.h per CU (form 1: two-ciphertext units up to 2 x CUs bits, then three); beyond
     that the paired form (2, kern_blindrot_pair.h): one 512-thread workgroup per CU, units of six and of four ciphertexts that cover
     the batch in a whole number of generations, the smaller ones last"""

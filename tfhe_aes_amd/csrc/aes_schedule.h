@@ -1,0 +1,299 @@
+// aes_schedule.h -- the AES schedules of the reference's Server (src/server/server.rs:39-178) on device buffers: encryption, both
+// decryptions, the decryption round keys, the key expansion, add_scalar, and public blocks / CTR with a public nonce.
+#pragma once
+
+static int many_sbox_dev(fheaes_ctx *c, const uint64_t *bytes, uint64_t n_bytes, int set, uint64_t *out)
+{
+    return wopbs_dev(c, bytes, n_bytes, 8, c->lutset_d[set], (uint32_t)c->lutset_n[set], 0, out);
+}
+
+// ---- Server API -------------------------------------------------------------------------------
+// FIPS-197 Fig. 4: Nr = 10 / 12 / 14 rounds for Nk = 4 / 6 / 8 key words; 0: not an AES key size.  The reference is AES-128 only
+// (server.rs:107, main.rs); every schedule below is its schedule with Nr in place of 10.
+static int aes_rounds(uint32_t key_bits) { return key_bits == 128 ? 10 : key_bits == 192 ? 12 : key_bits == 256 ? 14 : 0; }
+
+static int check_key_bits(fheaes_ctx *c, uint32_t key_bits)
+{
+    if (!aes_rounds(key_bits)) return c->fail(FHEAES_ERR_INVALID, "key_bits must be 128, 192 or 256, got %u", key_bits);
+    return FHEAES_OK;
+}
+
+static int aes_encrypt_dev(fheaes_ctx *c, const uint64_t *rk, uint64_t *state, uint64_t n_blocks, int nr)
+{
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
+    TRY(ensure(c, c->ws_vp, nbytes * 3 * bw * 8));
+    uint64_t *vp = (uint64_t *)c->ws_vp.p;
+    const GatherTable t_round = table_enc_round(), t_shift = table_shift_rows(false);
+    TRY(launch_add_bcast(c, state, rk, sw, n_blocks));                                   // server.rs:42
+    for (int round = 1; round < nr; ++round) {                                           // server.rs:44-57
+        TRY(many_sbox_dev(c, state, nbytes, LUTSET_ENC_ROUND, vp));
+        TRY(launch_gather(c, vp, 3, rk + (uint64_t)round * sw, state, n_blocks, t_round));
+    }
+    TRY(many_sbox_dev(c, state, nbytes, LUTSET_SBOX, vp));                               // server.rs:59-63
+    TRY(launch_gather(c, vp, 1, rk + (uint64_t)nr * sw, state, n_blocks, t_shift));
+    return FHEAES_OK;
+}
+
+static int aes_decrypt_dev(fheaes_ctx *c, const uint64_t *rk, uint64_t *state, uint64_t n_blocks, int nr)
+{
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
+    TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
+    uint64_t *vp = (uint64_t *)c->ws_vp.p;
+    const GatherTable t_inv = table_shift_rows(true), t_mix = table_dec_mix();
+    TRY(launch_add_bcast(c, state, rk + (uint64_t)nr * sw, sw, n_blocks));               // server.rs:70
+    for (int round = nr; round >= 2; --round) {                                          // server.rs:72-96
+        // inv_shift_rows commutes with the bytewise S-Box: INV_SBOX first, then the permutation + round key
+        TRY(many_sbox_dev(c, state, nbytes, LUTSET_INV_SBOX, vp));
+        TRY(launch_gather(c, vp, 1, rk + (uint64_t)(round - 1) * sw, state, n_blocks, t_inv));
+        TRY(many_sbox_dev(c, state, nbytes, LUTSET_DEC_MUL, vp));
+        TRY(launch_gather(c, vp, 4, nullptr, state, n_blocks, t_mix));
+    }
+    TRY(many_sbox_dev(c, state, nbytes, LUTSET_INV_SBOX, vp));                           // server.rs:98-104
+    TRY(launch_gather(c, vp, 1, rk, state, n_blocks, t_inv));
+    return FHEAES_OK;
+}
+
+// The equivalent inverse cipher (FIPS-197 section 5.3.5, Fig. 15): InvMixColumns is linear, so IMC(InvS(x)) + IMC(w[r]) is one WoPBS
+// per byte with the composed tables {9, 11, 13, 14} * InvS[x] (LUTSET_DEC_EQ_ROUND), summed through the InvShiftRows-folded gather with
+// dw[r] = IMC(w[r]) as the round key: Nr WoPBS per block like aes_encrypt_dev, against the 2 Nr - 1 of aes_decrypt_dev (the reference's own
+// schedule, server.rs:67-105, which says at :86-89 that it almost doubles the time of encryption).  dw: fheaes_aes_decryption_round_keys.
+static int aes_decrypt_eq_dev(fheaes_ctx *c, const uint64_t *dw, uint64_t *state, uint64_t n_blocks, int nr)
+{
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
+    TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
+    uint64_t *vp = (uint64_t *)c->ws_vp.p;
+    const GatherTable t_round = table_dec_eq_round(), t_inv = table_shift_rows(true);
+    TRY(launch_add_bcast(c, state, dw + (uint64_t)nr * sw, sw, n_blocks));
+    for (int round = nr - 1; round >= 1; --round) {
+        TRY(many_sbox_dev(c, state, nbytes, LUTSET_DEC_EQ_ROUND, vp));
+        TRY(launch_gather(c, vp, 4, dw + (uint64_t)round * sw, state, n_blocks, t_round));     // 4 WoPBS outputs + dw[round] = 5
+    }
+    TRY(many_sbox_dev(c, state, nbytes, LUTSET_INV_SBOX, vp));
+    TRY(launch_gather(c, vp, 1, dw, state, n_blocks, t_inv));
+    return FHEAES_OK;
+}
+
+typedef int (*AesDevFn)(fheaes_ctx *, const uint64_t *, uint64_t *, uint64_t, int);
+
+// dw[0] = w[0], dw[Nr] = w[Nr], dw[r] = InvMixColumns(w[r]) for r = 1..Nr-1: the 16 (Nr - 1) bytes of w[1..Nr-1] in one batch -- the 4-LUT
+// {9x, 11x, 13x, 14x} WoPBS, the InvMixColumns gather (4 terms, no key) and an identity WoPBS that brings every byte back to nominal
+// noise, as the key expansion's refresh does (server.rs:150): a round of the equivalent inverse cipher then sums 4 WoPBS outputs + 1 key
+static int dec_round_keys_dev(fheaes_ctx *c, const uint64_t *w, uint64_t *dw, int nr)
+{
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = (uint64_t)(nr - 1) * 16;
+    TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
+    TRY(ensure(c, c->ws_tmp_a, nbytes * bw * 8));
+    uint64_t *vp = (uint64_t *)c->ws_vp.p, *mix = (uint64_t *)c->ws_tmp_a.p;
+    HIP_TRY(c, hipMemcpyAsync(dw, w, sw * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dw + (uint64_t)nr * sw, w + (uint64_t)nr * sw, sw * 8, hipMemcpyDeviceToDevice, c->stream));
+    TRY(many_sbox_dev(c, w + sw, nbytes, LUTSET_DEC_MUL, vp));
+    TRY(launch_gather(c, vp, 4, nullptr, mix, (uint64_t)(nr - 1), table_dec_mix()));
+    TRY(many_sbox_dev(c, mix, nbytes, LUTSET_IDENTITY, dw + sw));
+    return FHEAES_OK;
+}
+
+// FIPS-197 section 5.2 for Nk = 4 / 6 / 8 key words under the reference's rule (server.rs:107-155 is the Nk = 4 case): every new word is
+// refreshed by an identity WoPBS; RotWord + SubWord + Rcon when i % Nk == 0, SubWord alone when Nk > 6 and i % Nk == 4; 4 (Nr + 1) words
+static int key_expansion_dev(fheaes_ctx *c, const uint64_t *key, uint64_t *w, int nr)
+{
+    static const uint8_t RCON[10] = {0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1B, 0x36};
+    const uint64_t bw = 8ull * c->big1, ww = 4 * bw;
+    TRY(ensure(c, c->ws_tmp_a, ww * 8));
+    TRY(ensure(c, c->ws_tmp_b, ww * 8));
+    uint64_t *ta = (uint64_t *)c->ws_tmp_a.p, *tb = (uint64_t *)c->ws_tmp_b.p;
+    const int nk = nr - 6;                                                                          // FIPS-197 Fig. 4: Nr = Nk + 6
+    HIP_TRY(c, hipMemcpyAsync(w, key, (uint64_t)nk * ww * 8, hipMemcpyDeviceToDevice, c->stream));  // server.rs:122-128
+    for (int i = nk; i < 4 * (nr + 1); ++i) {                                                       // server.rs:131-155
+        const uint64_t *prev = w + (uint64_t)(i - 1) * ww, *back = w + (uint64_t)(i - nk) * ww;
+        if (i % nk == 0) {
+            for (int j = 0; j < 4; ++j)                                                             // fhe_rot_word
+                HIP_TRY(c, hipMemcpyAsync(ta + (uint64_t)j * bw, prev + (uint64_t)((j + 1) & 3) * bw, bw * 8, hipMemcpyDeviceToDevice, c->stream));
+            TRY(many_sbox_dev(c, ta, 4, LUTSET_SBOX, tb));                                          // fhe_sub_word
+            hipLaunchKernelGGL(add_const_byte_kernel, dim3(1), dim3(64), 0, c->stream, tb, c->big1, (uint32_t)RCON[i / nk - 1]);
+            HIP_TRY(c, hipGetLastError());
+            TRY(launch_add2(c, ta, tb, back, ww));
+        } else if (nk > 6 && i % nk == 4) {                                                         // FIPS-197 5.2: SubWord alone (Nk = 8)
+            TRY(many_sbox_dev(c, prev, 4, LUTSET_SBOX, tb));
+            TRY(launch_add2(c, ta, tb, back, ww));
+        } else {
+            TRY(launch_add2(c, ta, prev, back, ww));
+        }
+        TRY(many_sbox_dev(c, ta, 4, LUTSET_IDENTITY, w + (uint64_t)i * ww));                        // refresh, server.rs:150
+    }
+    return FHEAES_OK;
+}
+
+// Host bytes that a device call needs go through the context's pinned buffer, so that the call only ENQUEUES (fheaes.h: FHEAES_DEVICE
+// calls are not synchronised): `fill` writes `bytes` bytes into it and they are copied to the front of ws_misc (grown to ws_bytes).
+// The only wait is for the copy out of that buffer that an earlier call enqueued (pin_ev).
+template <class Fill> static int upload_pinned(fheaes_ctx *c, size_t bytes, size_t ws_bytes, Fill fill)
+{
+    if (c->pin_ev) HIP_TRY(c, hipEventSynchronize(c->pin_ev));
+    else HIP_TRY(c, hipEventCreateWithFlags(&c->pin_ev, hipEventDisableTiming));
+    if (c->pin_bytes < bytes) {
+        if (c->pin) { HIP_TRY(c, hipHostFree(c->pin)); c->pin = nullptr; c->pin_bytes = 0; }
+        HIP_TRY(c, hipHostMalloc((void **)&c->pin, bytes, hipHostMallocDefault));
+        c->pin_bytes = bytes;
+    }
+    fill(c->pin);
+    TRY(ensure(c, c->ws_misc, ws_bytes));
+    HIP_TRY(c, hipMemcpyAsync(c->ws_misc.p, c->pin, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(c->pin_ev, c->stream));
+    return FHEAES_OK;
+}
+
+static int add_scalar_dev(fheaes_ctx *c, uint64_t *state, uint64_t n_blocks, const uint64_t *counters)
+{
+    const uint32_t lw = c->big1;
+    // counter bytes, MSB first (server.rs:174-178): addend[byte][blk], in front of the carries in ws_misc
+    TRY(upload_pinned(c, 16 * n_blocks, 16 * n_blocks + n_blocks * lw * 8 + 64, [&](uint8_t *add) {
+        for (uint64_t b = 0; b < n_blocks; ++b) {
+            uint64_t hi = counters[2 * b], lo = counters[2 * b + 1];
+            for (int j = 0; j < 8; ++j) { add[(15 - j) * n_blocks + b] = (uint8_t)(lo >> (8 * j)); add[(7 - j) * n_blocks + b] = (uint8_t)(hi >> (8 * j)); }
+        }
+    }));
+    uint8_t *add_d = (uint8_t *)c->ws_misc.p;
+    uint64_t *carry = (uint64_t *)((uint8_t *)c->ws_misc.p + ((16 * n_blocks + 63) / 64) * 64);
+    TRY(ensure(c, c->ws_tmp_a, n_blocks * 9ull * lw * 8));
+    TRY(ensure(c, c->ws_tmp_b, n_blocks * 2ull * 9 * lw * 8));
+    TRY(ensure(c, c->ws_luts, n_blocks * 2ull * 9 * FHE_N * 8));
+    uint64_t *in9 = (uint64_t *)c->ws_tmp_a.p, *res = (uint64_t *)c->ws_tmp_b.p, *luts = (uint64_t *)c->ws_luts.p;
+    for (int byte = 15; byte >= 0; --byte) {
+        const uint32_t bits = byte == 15 ? 8 : 9;
+        dim3 g1((bits * lw + 255) / 256, (unsigned)n_blocks);
+        hipLaunchKernelGGL(pack9_kernel, g1, dim3(256), 0, c->stream, (const uint64_t *)state, (const uint64_t *)carry, in9, (uint32_t)byte, lw, n_blocks, bits);
+        hipLaunchKernelGGL(counter_lut_kernel, dim3((2 * bits * FHE_N + 255) / 256, (unsigned)n_blocks), dim3(256), 0, c->stream, luts,
+                           (const uint8_t *)(add_d + (size_t)byte * n_blocks), bits, n_blocks);
+        HIP_TRY(c, hipGetLastError());
+        TRY(wopbs_dev(c, in9, n_blocks, bits, luts, 2, 1, res));
+        hipLaunchKernelGGL(unpack_sum_carry_kernel, dim3((9 * lw + 255) / 256, (unsigned)n_blocks), dim3(256), 0, c->stream, (const uint64_t *)res, bits, state, carry,
+                           (uint32_t)byte, lw, n_blocks);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return FHEAES_OK;
+}
+
+// ---- public blocks and CTR with a public nonce ------------------------------------------------
+// aes_encrypt on PUBLIC blocks (trivial ciphertexts) with every distinct S-Box input of the batch evaluated once.  A WoPBS is a
+// deterministic function of its input words, so two state bytes with word-equal inputs need one evaluation.  The rule that finds them
+// is exact and runs on the host before anything is enqueued: every S-Box input gets an id, round by round,
+//   round 1:   id(b, p) = (p, byte p of block b)                      -- the input is rk[0][p] + trivial(byte)
+//   round r+1: id(b, p) = (p, id_r(b, s_0), .., id_r(b, s_3))         -- s_j: the four sources of table_enc_round() for position p
+// and equal tuples are one id: sums of word-equal ciphertexts plus the same round-key byte are word-equal.  The ids of a round are its
+// POOL; round r runs one WoPBS over pool r and an indexed gather (kern_linear.h) into pool r+1, the last gather writes [block][16].
+struct PublicPlan {
+    struct Layer { size_t head, term; uint32_t n, terms; };     // offsets into `words`; n outputs of `terms` terms each
+    std::vector<Layer> layers;      // [0]: pool of round 1 (no terms), [r]: pool of round r+1 (4 terms), [Nr]: the state, 16 n_blocks bytes (1 term)
+    std::vector<uint32_t> words;    // every layer's PUBLIC_HEAD words, then its PUBLIC_TERM words: one upload per call
+    uint64_t max_vp_bytes_per_bw = 0;                            // max over the rounds of pool size x LUTs of that round's set
+};
+
+static inline uint32_t u128_byte(const uint64_t *hi_lo, int p) { return (uint32_t)((p < 8 ? hi_lo[0] >> (8 * (7 - p)) : hi_lo[1] >> (8 * (15 - p))) & 0xFF); }
+
+struct PublicKey5 {
+    uint32_t v[5];
+    bool operator==(const PublicKey5 &o) const { return !memcmp(v, o.v, sizeof v); }
+};
+struct PublicKey5Hash {
+    size_t operator()(const PublicKey5 &k) const
+    {
+        uint64_t h = 0xCBF29CE484222325ull;
+        for (uint32_t x : k.v) { h ^= x; h *= 0x100000001B3ull; }
+        return (size_t)(h ^ (h >> 29));
+    }
+};
+
+// blocks / data: n_blocks (hi, lo) pairs, data may be null
+static void public_plan(const uint64_t *blocks, const uint64_t *data, uint64_t n_blocks, int nr, PublicPlan &pl)
+{
+    const GatherTable t_round = table_enc_round(), t_shift = table_shift_rows(false);
+    const uint64_t nbytes = 16 * n_blocks;
+    std::vector<uint32_t> id(nbytes), next(nbytes);
+    pl.layers.clear(); pl.words.clear();
+    pl.layers.reserve((size_t)nr + 1);
+    {   // round 1
+        std::vector<int64_t> seen(16 * 256, -1);
+        std::vector<uint32_t> head;
+        for (uint64_t b = 0; b < n_blocks; ++b) for (int p = 0; p < 16; ++p) {
+            const uint32_t v = u128_byte(blocks + 2 * b, p);
+            int64_t &s = seen[(size_t)p * 256 + v];
+            if (s < 0) { s = (int64_t)head.size(); head.push_back(PUBLIC_HEAD(p, v)); }
+            id[16 * b + p] = (uint32_t)s;
+        }
+        pl.layers.push_back({0, head.size(), (uint32_t)head.size(), 0});
+        pl.words = std::move(head);
+    }
+    for (int r = 1; r < nr; ++r) {   // pool of round r + 1 from the ids of round r
+        std::unordered_map<PublicKey5, uint32_t, PublicKey5Hash> seen;
+        seen.reserve(nbytes);
+        std::vector<uint32_t> head, term;
+        for (uint64_t b = 0; b < n_blocks; ++b) for (int p = 0; p < 16; ++p) {
+            PublicKey5 k{{(uint32_t)p, 0, 0, 0, 0}};
+            for (int j = 0; j < 4; ++j) k.v[1 + j] = id[16 * b + t_round.src[p][j]];
+            auto ins = seen.emplace(k, (uint32_t)head.size());
+            if (ins.second) {
+                head.push_back(PUBLIC_HEAD(p, 0));
+                for (int j = 0; j < 4; ++j) term.push_back(PUBLIC_TERM(k.v[1 + j], t_round.lut[p][j]));
+            }
+            next[16 * b + p] = ins.first->second;
+        }
+        id.swap(next);
+        const size_t h0 = pl.words.size();
+        pl.layers.push_back({h0, h0 + head.size(), (uint32_t)head.size(), 4});
+        pl.words.insert(pl.words.end(), head.begin(), head.end());
+        pl.words.insert(pl.words.end(), term.begin(), term.end());
+    }
+    {   // ShiftRows + the last round key (+ CTR's clear data) into [block][16]
+        const size_t h0 = pl.words.size();
+        pl.layers.push_back({h0, h0 + nbytes, (uint32_t)nbytes, 1});
+        pl.words.resize(h0 + 2 * nbytes);
+        for (uint64_t b = 0; b < n_blocks; ++b) for (int p = 0; p < 16; ++p) {
+            pl.words[h0 + 16 * b + p] = PUBLIC_HEAD(p, data ? u128_byte(data + 2 * b, p) : 0);
+            pl.words[h0 + nbytes + 16 * b + p] = PUBLIC_TERM(id[16 * b + t_shift.src[p][0]], 0);
+        }
+    }
+    pl.max_vp_bytes_per_bw = 0;
+    for (int r = 1; r <= nr; ++r) pl.max_vp_bytes_per_bw = std::max<uint64_t>(pl.max_vp_bytes_per_bw, (uint64_t)pl.layers[r - 1].n * (r < nr ? 3 : 1));
+}
+
+#define PUBLIC_MAX_BLOCKS (1ull << 26)      /* 16 n pool entries x 4 must fit a PUBLIC_TERM word */
+
+static int launch_public_round1(fheaes_ctx *c, const uint32_t *head, const uint64_t *rk0, uint64_t *out, uint64_t n_pool)
+{
+    TRY(noise_guard(c, 1, "the initial AddRoundKey on public bytes"));          // a trivial ciphertext carries no noise
+    StageScope sc(c, FHEAES_STAGE_LINEAR, (n_pool + 15) / 16);
+    dim3 grid((8 * c->big1 + 1023) / 1024, (unsigned)std::min<uint64_t>(n_pool, 65535));
+    hipLaunchKernelGGL(public_round1_kernel, grid, dim3(256), 0, c->stream, head, rk0, out, n_pool, c->big1);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+static int launch_gather_indexed(fheaes_ctx *c, const uint64_t *pool, uint32_t n_luts, const uint32_t *head, const uint32_t *term, uint32_t terms,
+                                 const uint64_t *rk, uint64_t *out, uint64_t n_out)
+{
+    TRY(noise_guard(c, terms + 1u, "the indexed linear layer (MixColumns / ShiftRows + AddRoundKey over a pool)"));
+    StageScope sc(c, FHEAES_STAGE_LINEAR, (n_out + 15) / 16);
+    dim3 grid((8 * c->big1 + 1023) / 1024, (unsigned)std::min<uint64_t>(n_out, 65535));
+    hipLaunchKernelGGL(gather_add_indexed_kernel, grid, dim3(256), 0, c->stream, pool, n_luts, head, term, terms, rk, out, n_out, c->big1);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+// `out` [n_blocks][16][8][kN+1] doubles as the pool buffer: no pool has more than 16 n_blocks entries
+static int aes_public_dev(fheaes_ctx *c, const uint64_t *rk, const PublicPlan &pl, int nr, uint64_t *out)
+{
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw;
+    // the index tables go through the context's pinned buffer (as add_scalar's counter bytes): the call only enqueues
+    const size_t tab_bytes = pl.words.size() * sizeof(uint32_t);
+    TRY(upload_pinned(c, tab_bytes, tab_bytes, [&](uint8_t *pin) { memcpy(pin, pl.words.data(), tab_bytes); }));
+    const uint32_t *tab = (const uint32_t *)c->ws_misc.p;
+    TRY(ensure(c, c->ws_vp, pl.max_vp_bytes_per_bw * bw * 8));               // the largest pool, not 16 n
+    uint64_t *vp = (uint64_t *)c->ws_vp.p;
+    TRY(launch_public_round1(c, tab + pl.layers[0].head, rk, out, pl.layers[0].n));
+    for (int round = 1; round <= nr; ++round) {
+        const PublicPlan::Layer &in = pl.layers[round - 1], &to = pl.layers[round];
+        TRY(many_sbox_dev(c, out, in.n, round < nr ? LUTSET_ENC_ROUND : LUTSET_SBOX, vp));
+        TRY(launch_gather_indexed(c, vp, round < nr ? 3 : 1, tab + to.head, tab + to.term, to.terms, rk + (uint64_t)round * sw, out, to.n));
+    }
+    return FHEAES_OK;
+}

@@ -1,0 +1,395 @@
+// engine_launch.h -- how a batch becomes kernel launches: the blind rotation's launch plan, one launcher per kernel of kern_*.h,
+// the noise guard of the linear layers, and many_wopbs_without_padding on device buffers (many_wopbs.rs:31-116).
+#pragma once
+
+#define MAX_CHUNK_BITS 32768ull
+#define MAX_WOPBS_BITS 16u            /* widest radix input of many_wopbs_without_padding (LUT of 2^16 entries per output bit) */
+
+namespace {
+
+// ---- how a blind-rotation batch is cut into workgroups (fheaes_k2_launch_plan) -------------------------------------------------
+#define LATENCY_BATCH_BITS 256ull      /* at most one 512-thread workgroup per CU */
+#define K2_PAIR_MIN_BITS 768ull        /* batches above this take the paired form (kern_blindrot_pair.h): one 512-thread workgroup per CU */
+struct K2Plan { int form; uint64_t units_main; uint32_t r_main; uint64_t units_tail; uint32_t r_tail; };
+K2Plan k2_plan(uint64_t m, uint32_t cu_count, uint32_t k1, bool allow_pair = true)
+{
+    K2Plan pl{};
+    if (m <= LATENCY_BATCH_BITS) { pl.form = 0; pl.units_main = m; pl.r_main = 1; return pl; }
+    if (allow_pair && k1 == 5 && m > K2_PAIR_MIN_BITS) {
+        // paired form: units of 6 and of 4 ciphertexts, one workgroup per CU, a whole number of generations that covers the batch
+        // (16,384 bits = 2,560 x 6 + 256 x 4 = 11 generations; 4,096 = 512 x 6 + 256 x 4 = 3; 1,152 = 64 x 6 + 192 x 4 = 1); the
+        // smaller units last: the last generation is filled with four-ciphertext units on every CU instead of covering fewer CUs
+        // with six-ciphertext ones (measured at 4,096 bits)
+        pl.form = 2; pl.r_main = 6; pl.r_tail = 4;
+        const uint64_t gens = (m + 6ull * cu_count - 1) / (6ull * cu_count);
+        uint64_t nu = gens * cu_count;
+        uint64_t four = 6 * nu >= m ? (6 * nu - m) / 2 : 0;      // units that can give up two of their six slots
+        if (four > nu) four = nu;
+        if (four == nu && 4 * nu > m) { nu = (m + 3) / 4; four = nu; }          // less than one generation of 4-ciphertext units
+        pl.units_tail = four; pl.units_main = nu - four;
+        return pl;
+    }
+    pl.form = 1;
+    pl.r_main = k1 == 5 ? 3 : 8;
+    pl.units_main = (m + pl.r_main - 1) / pl.r_main;
+    if (k1 == 5) {
+        const uint64_t slots = 2ull * cu_count;
+        pl.r_tail = 2;
+        if ((m + 1) / 2 <= cu_count) {
+            // at most one two-ciphertext unit per CU: shorter units than three-ciphertext ones, still one per CU
+            pl.units_main = 0;
+            pl.units_tail = (m + 1) / 2;
+        } else if (pl.units_main > slots) {
+            // more units than slots (two workgroups per CU): a whole number of generations of 3- and 2-ciphertext units that
+            // cover the batch exactly, the 2-ciphertext ones last (see blind_rotate16_kernel)
+            const uint64_t nu = slots * ((m + 3 * slots - 1) / (3 * slots));
+            if (2 * nu <= m) {
+                pl.units_tail = 3 * nu - m;
+                pl.units_main = nu - pl.units_tail;
+            }
+        }
+    }
+    return pl;
+}
+
+// ---- kernel launchers ------------------------------------------------------------------------
+int launch_keyswitch(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out)
+{
+    if (m == 0) return FHEAES_OK;
+    StageScope sc(c, FHEAES_STAGE_KEYSWITCH, m);
+    const uint64_t ct_tiles16 = ((m + KS_CT_TILE - 1) / KS_CT_TILE) * (KS_CT_TILE / 16);
+    TRY(ensure(c, c->ws_digits, ct_tiles16 * c->ks_ksteps * 1024));
+    int8_t *af = (int8_t *)c->ws_digits.p;
+    const uint64_t threads = ct_tiles16 * c->ks_ksteps * 64;
+    ks_launch_digits_k1(dim3((unsigned)((threads + 255) / 256)), c->stream, in, (uint64_t)c->big1, c->big, m, c->ks_ksteps, af);
+    KeyswitchArgs a{};
+    a.afrag = af; a.bfrag = c->ksk_frag; a.ksteps = c->ks_ksteps; a.coltiles = c->ks_coltiles;
+    a.in = in; a.in_stride = c->big1; a.body_index = (int32_t)c->big; a.body_col = c->n; a.ncols = c->n + 1;
+    a.out = out; a.out_stride = c->n + 1; a.out_z_stride = 0; a.m = m;
+    // K1 through the LDS-tiled kernel too (round 6: 1.87 -> 1.48 ms per 16,384-bit launch, same words)
+    dim3 grid((c->ks_coltiles + KSL_COL_TILES - 1) / KSL_COL_TILES, (unsigned)((m + 16 * KSL_CT_TILES - 1) / (16 * KSL_CT_TILES)), 1);
+    ks_launch_mfma_lds(1, grid, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+// out: rows of one GGSW level: [m][out_stride] with key r at offset r*(k+1)N
+int launch_pfpks(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out, uint64_t out_stride)
+{
+    if (m == 0) return FHEAES_OK;
+    StageScope sc(c, FHEAES_STAGE_PFPKS, m);
+    const uint32_t gsz = c->k1 * FHE_N;
+    const uint64_t ct_tiles16 = ((m + KS_CT_TILE - 1) / KS_CT_TILE) * (KS_CT_TILE / 16);
+    TRY(ensure(c, c->ws_digits, ct_tiles16 * c->pf_ksteps * 2 * 1024));
+    int8_t *af = (int8_t *)c->ws_digits.p;
+    const uint64_t threads = ct_tiles16 * c->pf_ksteps * 64;
+    ks_launch_digits_k3(dim3((unsigned)((threads + 255) / 256)), c->stream, in, (uint64_t)c->big1, c->big1, m, c->pf_ksteps, af);
+    KeyswitchArgs a{};
+    a.afrag = af; a.bfrag = c->pfpksk_frag; a.ksteps = c->pf_ksteps; a.coltiles = c->pf_coltiles;
+    a.in = in; a.in_stride = c->big1; a.body_index = -1; a.body_col = 0; a.ncols = gsz;
+    a.out = out; a.out_stride = out_stride; a.out_z_stride = gsz; a.m = m;
+    dim3 grid((c->pf_coltiles + KSL_COL_TILES - 1) / KSL_COL_TILES, (unsigned)((m + 16 * KSL_CT_TILES - 1) / (16 * KSL_CT_TILES)), c->k1);
+    ks_launch_mfma_lds(2, grid, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+int launch_forward_fourier(fheaes_ctx *c, const uint64_t *in, uint64_t polys, double2 *out, int stage)
+{
+    if (polys == 0) return FHEAES_OK;
+    StageScope sc(c, stage, polys);
+    uint64_t wgs = (polys + EP_GROUPS - 1) / EP_GROUPS;
+    if (wgs > 8192) wgs = 8192;
+    hipLaunchKernelGGL(forward_fourier_kernel, dim3((unsigned)wgs), dim3(EP_THREADS), 0, c->stream, in, out, polys, c->tw_d);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+// the paired kernel takes nearly all of a CU's LDS: where the runtime cannot place even one such workgroup (a driver that reserves LDS)
+// every batch falls back to the 16-form instead of failing the launch
+bool k2_pair_allowed(fheaes_ctx *c)
+{
+    if (c->k2_pair_ok < 0) {
+        int per_cu = 0;
+        const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, blind_rotate_pair_kernel<5, 5, 8, 3, 2>, BRP_THREADS, 0);
+        c->k2_pair_ok = (oe == hipSuccess && per_cu >= 1) ? 1 : 0;
+        (void)hipGetLastError();
+    }
+    return c->k2_pair_ok == 1;
+}
+
+// the 16-form's LDS-home variant takes exactly half of a CU's 160 KB per workgroup: use it only where the runtime really places two
+bool k2_home_allowed(fheaes_ctx *c)
+{
+    if (c->k1 != 5) return false;
+    if (c->k2_home < 0) {
+        int per_cu = 0;
+        const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, blind_rotate16_kernel<5, 5, 8, 3, 2, true>, EP_THREADS, 0);
+        c->k2_home = (oe == hipSuccess && per_cu >= 2) ? 1 : 0;
+        (void)hipGetLastError();         // a failed query means "fall back", not a failed launch
+    }
+    return c->k2_home == 1;
+}
+
+// the paired kernel's owner words (BRP_PARK_SLOTS x uint32) and the BRP_PARK_TAIL_WORDS uint64 behind them (fallbacks, ownership
+// violations, record pointer).  Zeroed once, when allocated: the reset before every launch touches only the owner words, so the counters
+// accumulate for the life of the context (fheaes_k2_park_read); the record pointer is set by the launches under the test hook and
+// cleared by fheaes_k2_park_debug
+static_assert(FHEAES_K2_PARK_SLOTS == BRP_PARK_SLOTS, "include/fheaes.h and kern_blindrot_pair.h disagree on the number of parking slots");
+constexpr size_t PARK_OWNER_BYTES = BRP_PARK_SLOTS * sizeof(uint32_t) + BRP_PARK_TAIL_WORDS * sizeof(uint64_t);
+constexpr size_t PARK_RECORD_PTR_OFFSET = BRP_PARK_SLOTS * sizeof(uint32_t) + 2 * sizeof(uint64_t);
+
+int ensure_park_owner(fheaes_ctx *c)
+{
+    if (c->ws_park_owner.p) return FHEAES_OK;
+    TRY(ensure(c, c->ws_park_owner, PARK_OWNER_BYTES));
+    HIP_TRY(c, hipMemsetAsync(c->ws_park_owner.p, 0, PARK_OWNER_BYTES, c->stream));
+    return FHEAES_OK;
+}
+
+// bytes of the paired kernel's parking slab for a launch of `grid` workgroups: claimed slots = the shared pool + one private overflow slot
+// per workgroup behind it (never touched unless a pool is exhausted), private slots = one per workgroup
+size_t k2_pair_park_bytes(const fheaes_ctx *c, uint64_t grid)
+{
+    return (size_t)((c->k2_park_claim ? BRP_PARK_SLOTS : 0) + grid) * 2 * BRP_PARK_WORDS_PER_HALF * 8;
+}
+
+// Everything a blind-rotation launch of m bits on this context comes to: the plan after the occupancy fallbacks, the kernel and its name,
+// the grid, the parking slab.  launch_cbs_pbs launches from it, fheaes_reserve sizes from it, fheaes_k2_context_plan reports it.
+struct K2Launch {
+    K2Plan pl;
+    void (*kernel)(ExtProdArgs);
+    const char *name;
+    unsigned grid, threads;
+    size_t park_bytes;          // 0: the form parks nothing
+    bool park_owner;            // the launch claims its parking slots through the owner words (ensure_park_owner)
+};
+K2Launch k2_launch(fheaes_ctx *c, uint64_t m)
+{
+    K2Launch L{};
+    L.pl = k2_plan(m, c->cu_count, c->k1, k2_pair_allowed(c));
+    L.grid = (unsigned)(L.pl.units_main + L.pl.units_tail);
+    if (L.pl.form == 0) {
+        // latency regime: one ciphertext per 512-thread workgroup, all levels transformed at once (kern_blindrot_latency.h)
+        L.threads = BL_THREADS;
+        if (c->k1 == 5) { L.kernel = blind_rotate_latency_kernel<5, 5, 8>; L.name = "blind_rotate_latency_kernel<5,5,8>"; }
+        else { L.kernel = blind_rotate_latency_kernel<2, 5, 8>; L.name = "blind_rotate_latency_kernel<2,5,8>"; }
+        // (257..768 bits: the throughput form below with at most one workgroup per CU, 14.6 ms per launch; the round-1
+        //  one-ciphertext-per-workgroup form of kern_extprod.h took 21.6 ms there and the latency form in two waves 16-18 ms)
+    } else if (L.pl.form == 2) {
+        // paired throughput form (kern_blindrot_pair.h): one 512-thread workgroup per CU, 6 (or 4) ciphertexts share every key fetch
+        L.threads = BRP_THREADS;
+        L.kernel = blind_rotate_pair_kernel<5, 5, 8, 3, 2>;
+        L.name = c->k2_park_claim ? "blind_rotate_pair_kernel<5,5,8,3,2> parking=claimed" : "blind_rotate_pair_kernel<5,5,8,3,2> parking=private";
+        L.park_bytes = k2_pair_park_bytes(c, L.grid);
+        L.park_owner = c->k2_park_claim != 0;
+    } else {
+        // throughput form (kern_blindrot16.h): accumulator parked in HBM between uses, key rows prefetched across the transform
+        L.threads = EP_THREADS;
+        if (c->k1 == 5 && k2_home_allowed(c)) { L.kernel = blind_rotate16_kernel<5, 5, 8, 3, 2, true>; L.name = "blind_rotate16_kernel<5,5,8,3,2,true>"; }
+        else if (c->k1 == 5) { L.kernel = blind_rotate16_kernel<5, 5, 8, 3, 2, false>; L.name = "blind_rotate16_kernel<5,5,8,3,2,false>"; }
+        else { L.kernel = blind_rotate16_kernel<2, 5, 8, 8>; L.name = "blind_rotate16_kernel<2,5,8,8,0,false>"; }
+        L.park_bytes = (size_t)L.grid * BR16_PARK_WORDS_PER_WG * 8;
+    }
+    return L;
+}
+
+int launch_cbs_pbs(fheaes_ctx *c, const uint64_t *lwe_small, uint64_t m, uint32_t level, uint64_t *out)
+{
+    if (m == 0) return FHEAES_OK;
+    // the blind-rotation kernels address the Fourier BSK as ONE raw buffer with 32-bit byte offsets
+    if ((uint64_t)c->n * c->p.pbs_level * c->k1 * c->k1 * FHE_H * 16 > 0x7FFFFFFFull)
+        return c->fail(FHEAES_ERR_INVALID, "bootstrapping key larger than 2 GiB is not supported by the blind-rotation kernels");
+    StageScope sc(c, FHEAES_STAGE_BLIND_ROTATE, m);
+    ExtProdArgs a{};
+    a.ggsw = c->bskf; a.tw = c->tw_d;
+    a.out = out; a.count = m; a.iters = c->n; a.lwe_in = lwe_small;
+    const uint64_t half_delta = 1ull << (64 - c->p.cbs_base_log * level - 1);
+    a.tv_const = (uint64_t)0 - half_delta; a.body_shift = 1ull << 62; a.post_add = half_delta;
+    const K2Launch L = k2_launch(c, m);
+    if (L.pl.form != 0) a.units_main = (uint32_t)L.pl.units_main;
+    if (L.park_bytes) {
+        if (L.park_bytes > 0x7FFFFFFFull) return c->fail(FHEAES_ERR_INVALID, "internal: parking slab of %zu bytes exceeds one raw buffer", L.park_bytes);
+        TRY(ensure(c, c->ws_park, L.park_bytes));
+        a.park = (uint64_t *)c->ws_park.p; a.park_bytes = L.park_bytes;
+    }
+    if (L.park_owner) {
+        // owner words of the shared slots: all free when a launch starts (every workgroup gives its slot back before it ends; the
+        // memset makes that hold even after a launch that was aborted) -- or, under the test hook, the pattern it set
+        TRY(ensure_park_owner(c));
+        if (c->k2_park_pattern)
+            HIP_TRY(c, hipMemcpyAsync(c->ws_park_owner.p, c->ws_park_pattern.p, BRP_PARK_SLOTS * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        else
+            HIP_TRY(c, hipMemsetAsync(c->ws_park_owner.p, 0, BRP_PARK_SLOTS * sizeof(uint32_t), c->stream));
+        a.park_owner = (uint32_t *)c->ws_park_owner.p;
+        if (c->k2_park_record) {
+            TRY(ensure(c, c->ws_park_record, (size_t)L.grid * 2 * sizeof(uint32_t)));
+            HIP_TRY(c, hipMemsetAsync(c->ws_park_record.p, 0xFF, (size_t)L.grid * 2 * sizeof(uint32_t), c->stream));   // unwritten = ~0
+            const uint64_t rp = (uint64_t)(uintptr_t)c->ws_park_record.p;
+            uint32_t *const rp_word = (uint32_t *)((char *)c->ws_park_owner.p + PARK_RECORD_PTR_OFFSET);
+            HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)rp_word, (int)(uint32_t)rp, 1, c->stream));
+            HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)(rp_word + 1), (int)(uint32_t)(rp >> 32), 1, c->stream));
+            c->k2_park_record_n = L.grid;
+        }
+    }
+#ifdef EP_STAMPS
+    static const char *namesL[EP_NPH] = {"barrier (result) + accumulate", "rotate+decompose (1 coeff x K1)", "read digits + forward fft", "digit stores", "barrier (digits)", "MAC", "barrier (MAC done)",
+                                         "products store + next rows", "barrier (products)", "inverse fft -> doubles", "barrier (acc)", "barrier (decomposition)"};
+    static const char *namesT[EP_NPH] = {"stage+rotate+decomp_first", "decomp_next", "fwd head", "pre-level barrier", "fwd tail (transpose+dft16)",       // both throughput forms
+                                         "digit stores+late loads", "exchange barrier", "MAC", "products exchange", "inverse fft", "convert+add", "loop head"};
+    StampReport rep(c, (size_t)L.grid * (L.threads / 64), L.pl.form == 0 ? namesL : namesT, L.pl.form == 0 ? 8 : 0);
+    a.stamps = rep.d;
+#endif
+    hipLaunchKernelGGL(L.kernel, dim3(L.grid), dim3(L.threads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+int launch_vertical_packing(fheaes_ctx *c, const double2 *ggswf, uint64_t n_inputs, uint32_t bits, const uint64_t *luts,
+                            uint32_t n_luts, int per_input, uint64_t *out)
+{
+    if (n_inputs == 0) return FHEAES_OK;
+    StageScope sc(c, FHEAES_STAGE_VERTICAL_PACKING, n_inputs * n_luts * bits);
+    const uint32_t inst_per_input = n_luts * bits;
+    const uint64_t W = lut_row_words(bits);
+    // ---- inputs wider than 9 bits: CMUX tree over bits 9..bits-1 (kern_extprod.h, cmux_level_kernel), root -> ws_tree ----
+    const uint64_t *glwe_root = nullptr;
+    if (bits > 9) {
+        const uint32_t tree_bits = bits - 9;
+        const uint64_t instances = n_inputs * inst_per_input, gsz = (uint64_t)c->k1 * FHE_N;
+        // level t writes (2^(tree_bits-1-t)) nodes per instance; ping-pong between the two halves of ws_tree
+        const uint64_t half_words = instances * (1ull << (tree_bits - 1)) * gsz;
+        TRY(ensure(c, c->ws_tree, 2 * half_words * 8));
+        uint64_t *buf[2] = {(uint64_t *)c->ws_tree.p, (uint64_t *)c->ws_tree.p + half_words};
+        for (uint32_t t = 0; t < tree_bits; ++t) {
+            CmuxArgs a{};
+            a.ggsw = ggswf; a.tw = c->tw_d;
+            a.luts = t == 0 ? luts : nullptr; a.in = t == 0 ? nullptr : buf[(t - 1) & 1]; a.out = buf[t & 1];
+            a.bits = bits; a.bit = 9 + t; a.nodes_out = 1u << (tree_bits - 1 - t);
+            a.inst_per_input = inst_per_input; a.lut_per_input = per_input ? 1 : 0; a.lut_words = W;
+            const uint64_t jobs = (uint64_t)inst_per_input * a.nodes_out;
+            if (c->k1 == 5) {
+                constexpr int R = 3;
+                a.wg_per_input = (uint32_t)((jobs + R - 1) / R);
+                hipLaunchKernelGGL((cmux_level_kernel<5, 15, R>), dim3((unsigned)(n_inputs * a.wg_per_input)), dim3(EP_THREADS), 0, c->stream, a);
+            } else {
+                constexpr int R = 8;
+                a.wg_per_input = (uint32_t)((jobs + R - 1) / R);
+                hipLaunchKernelGGL((cmux_level_kernel<2, 15, R>), dim3((unsigned)(n_inputs * a.wg_per_input)), dim3(EP_THREADS), 0, c->stream, a);
+            }
+            HIP_TRY(c, hipGetLastError());
+        }
+        glwe_root = buf[(tree_bits - 1) & 1];
+    }
+    ExtProdArgs a{};
+    a.ggsw = ggswf; a.tw = c->tw_d;
+    a.out = out; a.count = n_inputs * n_luts * bits; a.iters = bits < 9 ? bits : 9; a.ggsw_per_input = bits;
+    a.luts = luts; a.lut_words = W; a.glwe_in = glwe_root;
+    a.n_luts = n_luts; a.lut_per_input = per_input ? 1 : 0; a.inst_per_input = inst_per_input;
+    if (c->k1 == 5) {
+        constexpr int R = 3;
+        a.wg_per_input = (a.inst_per_input + R - 1) / R;
+        hipLaunchKernelGGL((extprod_rotate_kernel<5, 1, 15, R, true>), dim3((unsigned)(n_inputs * a.wg_per_input)), dim3(EP_THREADS), 0, c->stream, a);
+    } else {
+        constexpr int R = 8;
+        a.wg_per_input = (a.inst_per_input + R - 1) / R;
+        hipLaunchKernelGGL((extprod_rotate_kernel<2, 1, 15, R, true>), dim3((unsigned)(n_inputs * a.wg_per_input)), dim3(EP_THREADS), 0, c->stream, a);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+// static schedule assertion (NOT runtime noise tracking: words carry no metadata): every linear layer of the engine's own AES schedule
+// declares here how many WoPBS outputs it sums per word; a table that would sum more than tfhe-rs' noise-asserts allow is refused
+int noise_guard(fheaes_ctx *c, uint32_t level, const char *what)
+{
+    if (level > c->noise_level_seen) c->noise_level_seen = level;
+    if (level > FHEAES_MAX_NOISE_LEVEL)
+        return c->fail(FHEAES_ERR_INVALID, "%s would sum %u nominal-noise ciphertexts; the parameter set allows %u (MaxNoiseLevel, client.rs:92)", what, level,
+                       (unsigned)FHEAES_MAX_NOISE_LEVEL);
+    return FHEAES_OK;
+}
+
+int launch_gather(fheaes_ctx *c, const uint64_t *src, uint32_t n_luts, const uint64_t *rk, uint64_t *out, uint64_t n_blocks, const GatherTable &t)
+{
+    if (n_blocks == 0) return FHEAES_OK;
+    TRY(noise_guard(c, (uint32_t)t.terms + (rk ? 1u : 0u), "the linear layer (MixColumns / ShiftRows + AddRoundKey)"));
+    StageScope sc(c, FHEAES_STAGE_LINEAR, n_blocks);
+    const uint32_t bw = 8 * c->big1;
+    dim3 grid((bw + 1023) / 1024, 16, (unsigned)n_blocks);
+    hipLaunchKernelGGL(gather_add_kernel, grid, dim3(256), 0, c->stream, src, n_luts, rk, out, n_blocks, bw, t);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+int launch_add_bcast(fheaes_ctx *c, uint64_t *dst, const uint64_t *src, uint64_t words_per_block, uint64_t n_blocks)
+{
+    if (n_blocks == 0) return FHEAES_OK;
+    TRY(noise_guard(c, 2, "the initial AddRoundKey"));
+    StageScope sc(c, FHEAES_STAGE_LINEAR, n_blocks);
+    uint64_t total = words_per_block * n_blocks;
+    unsigned grid = (unsigned)std::min<uint64_t>((total + 255) / 256, 16384);
+    hipLaunchKernelGGL(add_bcast_kernel, dim3(grid), dim3(256), 0, c->stream, dst, src, words_per_block, n_blocks);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+int launch_add2(fheaes_ctx *c, uint64_t *dst, const uint64_t *a, const uint64_t *b, uint64_t words)
+{
+    TRY(noise_guard(c, 2, "a key-expansion word sum"));
+    StageScope sc(c, FHEAES_STAGE_LINEAR, 1);
+    unsigned grid = (unsigned)std::min<uint64_t>((words + 255) / 256, 16384);
+    hipLaunchKernelGGL(add2_kernel, dim3(grid), dim3(256), 0, c->stream, dst, a, b, words);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+int check_keys(fheaes_ctx *c)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    if (!c->have_keys) return c->fail(FHEAES_ERR_NOKEYS, "evaluation keys have not been uploaded");
+    return FHEAES_OK;
+}
+
+// ---- many_wopbs_without_padding on device buffers ----------------------------------------------
+// the workspace of one chunk of `bits` input bits: K1's output, K2's output, the GGSWs in both domains (cbs_level == 1)
+int ensure_wopbs_ws(fheaes_ctx *c, uint64_t bits)
+{
+    const uint64_t ggsw_words = (uint64_t)c->k1 * c->k1 * FHE_N;
+    TRY(ensure(c, c->ws_small, bits * (c->n + 1) * 8));
+    TRY(ensure(c, c->ws_pbs, bits * c->big1 * 8));
+    TRY(ensure(c, c->ws_ggsw, bits * ggsw_words * 8));
+    TRY(ensure(c, c->ws_ggswf, bits * ggsw_words * 8));
+    return FHEAES_OK;
+}
+
+int wopbs_dev(fheaes_ctx *c, const uint64_t *lwe_in, uint64_t n_inputs, uint32_t bits, const uint64_t *luts, uint32_t n_luts,
+              int per_input, uint64_t *lwe_out)
+{
+    if (bits < 1 || bits > MAX_WOPBS_BITS) return c->fail(FHEAES_ERR_INVALID, "bits_per_input must be in 1..%u (got %u)", MAX_WOPBS_BITS, bits);
+    if (n_luts < 1) return c->fail(FHEAES_ERR_INVALID, "n_luts must be >= 1");
+    if (n_inputs == 0) return FHEAES_OK;
+    uint64_t chunk_inputs = std::max<uint64_t>(1, MAX_CHUNK_BITS / bits);
+    if (bits > 9) {
+        // the CMUX tree keeps 2^(bits-9) GLWEs per (input, LUT, output bit) in flight: bound that workspace to ~2 GiB per chunk
+        const uint64_t per_input = (uint64_t)n_luts * bits * (1ull << (bits - 9)) * c->k1 * FHE_N * 8;
+        chunk_inputs = std::max<uint64_t>(1, std::min<uint64_t>(chunk_inputs, (2ull << 30) / per_input));
+    }
+    const uint64_t W = lut_row_words(bits);
+    const uint64_t ggsw_words = (uint64_t)c->k1 * c->k1 * FHE_N;    // cbs_level == 1
+    TRY(ensure_wopbs_ws(c, std::min<uint64_t>(n_inputs, chunk_inputs) * bits));
+    for (uint64_t i0 = 0; i0 < n_inputs; i0 += chunk_inputs) {
+        const uint64_t ni = std::min<uint64_t>(chunk_inputs, n_inputs - i0);
+        const uint64_t m = ni * bits;
+        const uint64_t *in = lwe_in + i0 * bits * c->big1;
+        TRY(launch_keyswitch(c, in, m, (uint64_t *)c->ws_small.p));
+        TRY(launch_cbs_pbs(c, (const uint64_t *)c->ws_small.p, m, 1, (uint64_t *)c->ws_pbs.p));
+        TRY(launch_pfpks(c, (const uint64_t *)c->ws_pbs.p, m, (uint64_t *)c->ws_ggsw.p, ggsw_words));
+        TRY(launch_forward_fourier(c, (const uint64_t *)c->ws_ggsw.p, m * c->k1 * c->k1, (double2 *)c->ws_ggswf.p, FHEAES_STAGE_GGSW_FFT));
+        const uint64_t *l = per_input ? luts + i0 * n_luts * bits * W : luts;
+        TRY(launch_vertical_packing(c, (const double2 *)c->ws_ggswf.p, ni, bits, l, n_luts, per_input, lwe_out + i0 * n_luts * bits * c->big1));
+    }
+    return FHEAES_OK;
+}
+
+}  // namespace

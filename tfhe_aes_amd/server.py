@@ -139,30 +139,21 @@ class Server:
         section 5.2) -> [13 | 15][16][8][kN+1]."""
         bits = _key_bits(key, KEY_BYTES_TO_BITS, "key", ndim=3)
         rk = _empty_like(key, (bits // 32 + 7, 16, 8, self.params.big1))
-        if bits == 128:
-            self.engine.aes_key_expansion(key, rk)
-        else:
-            self.engine.aes_key_expansion_bits(key, bits, rk)
+        self.engine.aes_key_expansion_bits(key, bits, rk)
         return rk
 
     def aes_encrypt(self, encrypted_round_keys, state):
         """server.rs:39, in place.  state [16][8][kN+1] or a batch [B][16][8][kN+1]; 11 / 13 / 15 round keys: AES-128 / 192 / 256."""
         bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
-        if bits == 128:
-            self.engine.aes_encrypt(encrypted_round_keys, state, n_blocks)
-        else:
-            self.engine.aes_encrypt_bits(encrypted_round_keys, bits, state, n_blocks)
+        self.engine.aes_encrypt_bits(encrypted_round_keys, bits, state, n_blocks)
         return state
 
     def aes_decrypt(self, encrypted_round_keys, state):
         """server.rs:67, in place; 11 / 13 / 15 round keys: AES-128 / 192 / 256."""
         bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
-        if bits == 128:
-            self.engine.aes_decrypt(encrypted_round_keys, state, n_blocks)
-        else:
-            self.engine.aes_decrypt_bits(encrypted_round_keys, bits, state, n_blocks)
+        self.engine.aes_decrypt_bits(encrypted_round_keys, bits, state, n_blocks)
         return state
 
     def aes_decryption_round_keys(self, round_keys):
@@ -171,10 +162,7 @@ class Server:
         aes_decrypt_equivalent."""
         bits = _key_bits(round_keys, ROUND_KEYS_TO_BITS, "round keys")
         dw = _empty_like(round_keys, tuple(round_keys.shape))
-        if bits == 128:
-            self.engine.aes_decryption_round_keys(round_keys, dw)
-        else:
-            self.engine.aes_decryption_round_keys_bits(round_keys, bits, dw)
+        self.engine.aes_decryption_round_keys_bits(round_keys, bits, dw)
         return dw
 
     def aes_decrypt_equivalent(self, dec_round_keys, state):
@@ -182,10 +170,7 @@ class Server:
         (server.rs:67-105, :86-89).  Same plaintext as aes_decrypt, other ciphertext words.  state [16][8][kN+1] or [B][16][8][kN+1]."""
         bits = _key_bits(dec_round_keys, ROUND_KEYS_TO_BITS, "decryption round keys")
         n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
-        if bits == 128:
-            self.engine.aes_decrypt_equivalent(dec_round_keys, state, n_blocks)
-        else:
-            self.engine.aes_decrypt_equivalent_bits(dec_round_keys, bits, state, n_blocks)
+        self.engine.aes_decrypt_equivalent_bits(dec_round_keys, bits, state, n_blocks)
         return state
 
     def add_scalar(self, state, i):
