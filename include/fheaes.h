@@ -230,6 +230,35 @@ int fheaes_aes_ctr_bits(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t ke
  * no context, no GPU; fheaes_aes_encrypt_bits runs 16 n_blocks in every round). */
 int fheaes_aes_public_plan(const uint64_t *blocks_hi_lo, uint64_t n_blocks, uint32_t key_bits, uint64_t *unique_bytes_per_round);
 
+/* ---- packed ciphertexts --------------------------------------------------------- */
+/* Every entry point above hands its result out one LWE ciphertext per bit: kN + 1 words (16,392 bytes at PARAM_OPT) for one bit.  A
+ * packing key switch puts N = 512 bits into the N coefficients of ONE GLWE ciphertext, (k+1)N words (20,480 bytes) for 512 bits:
+ * 409.8 times smaller, for storing or sending what the engine computed.  The reference has nothing here: it hands whole radix
+ * ciphertexts across in memory (client.rs:147-175) and never packs or serialises them; in tfhe-rs the counterpart is the compressed
+ * ciphertext list, which needs a packing key of its own.  This needs NO new key: block r = k of the PFPKSK every context holds is
+ * GLWE_S(sigma_i * 2^(64 - b(l+1))) with f(x) = x, an LWE -> GLWE key-switching key that puts the message into the constant coefficient.
+ *
+ * With ks[t] = [(k+1)][N] the private functional packing key switch of LWE t under key block k (what fheaes_pfpks_batch writes at
+ * out[t][k]; the body goes through the gadget like the mask), in wrapping uint64 arithmetic:
+ *   packed[g] = sum over i < N with gN + i < m of X^i * ks[gN + i],
+ * negacyclic in each of the k+1 polynomials (coefficient c of X^i * P is P[c - i] for c >= i and -P[c - i + N] for c < i).  Bit t of the
+ * flattened input lives in GLWE t / N, coefficient t % N (four AES blocks fill one GLWE); the coefficients of a partly filled last GLWE
+ * beyond m are encryptions of zero.  Unpacking is sample extraction of coefficient i = t % N -- for polynomial j < k mask word
+ * jN + c = A_j[i - c] (c <= i) or -A_j[i - c + N] (c > i), body = B[i] -- an LWE ciphertext of bit t under the big key (the GLWE key
+ * flattened), a valid input of every entry point.
+ *
+ * Noise: packing adds an error of variance
+ *   sigma^2 = N (kN+1) L (B^2 / 12) sigma_pfks^2 + (kN/2 + 1) 2^(2R) / 12,   B = 2^pfks_base_log, L = pfks_level, R = 64 - L pfks_base_log,
+ * sigma_pfks = pfks_noise_std * 2^64: std 2^33.5 at PARAM_OPT against a decoding margin of 2^62; unpacking adds none.  Words carry no
+ * noise metadata: an unpacked word counts as NOMINAL for the noise guard above, like any state a caller passes in. */
+/* words of the packed form of m bits: ceil(m / N) * (k+1) * N; 0 for a NULL context */
+size_t fheaes_packed_words(const fheaes_ctx *ctx, uint64_t m);
+/* lwe_in [m][kN+1] -> glwe_out [ceil(m/N)][(k+1)N].  Needs uploaded keys (FHEAES_ERR_NOKEYS); m = 0 is FHEAES_OK; overlapping buffers
+ * are FHEAES_ERR_INVALID; FHEAES_DEVICE calls only enqueue.  Works in chunks inside the workspace K3 owns (fheaes_reserve bounds it). */
+int fheaes_pack_bits(fheaes_ctx *ctx, const uint64_t *lwe_in, uint64_t m, uint64_t *glwe_out, int memspace);
+/* glwe_in [ceil(m/N)][(k+1)N] -> lwe_out [m][kN+1]: a permutation with signs, no keys needed.  Same argument rules. */
+int fheaes_unpack_bits(fheaes_ctx *ctx, const uint64_t *glwe_in, uint64_t m, uint64_t *lwe_out, int memspace);
+
 /* ---- measurement --------------------------------------------------------------- */
 #define FHEAES_STAGE_KEYSWITCH 0
 #define FHEAES_STAGE_BLIND_ROTATE 1
@@ -238,7 +267,8 @@ int fheaes_aes_public_plan(const uint64_t *blocks_hi_lo, uint64_t n_blocks, uint
 #define FHEAES_STAGE_VERTICAL_PACKING 4
 #define FHEAES_STAGE_LINEAR 5
 #define FHEAES_STAGE_COUNT 6
-/* When enabled every kernel launch is bracketed by HIP events on the launch stream. */
+/* When enabled every kernel launch is bracketed by HIP events on the launch stream.  fheaes_pack_bits accounts its matrix product under
+ * FHEAES_STAGE_PFPKS and its fold under FHEAES_STAGE_LINEAR, fheaes_unpack_bits its extraction under FHEAES_STAGE_LINEAR (units: bits). */
 int fheaes_profile_enable(fheaes_ctx *ctx, int on);
 int fheaes_profile_reset(fheaes_ctx *ctx);
 /* synchronises, then returns accumulated kernel time, launches and units (bits or polys) of a stage */

@@ -15,6 +15,8 @@
 //!   GpuServer::aes_decrypt                 Server::aes_decrypt             src/server/server.rs:67   (batched)
 //!   GpuServer::add_scalar                  Server::add_scalar              src/server/server.rs:172  (batched; carry defect of :182 fixed)
 //!   GpuServer::aes_ctr                     (no counterpart: CTR with a PUBLIC nonce, the loop of main.rs:55-64 without add_scalar)
+//!   GpuServer::{pack, unpack}              (no counterpart: N = 512 one-bit ciphertexts in one GLWE, 409.8 times smaller, and back;
+//!                                           tfhe-rs' compressed ciphertext list is the nearest thing and needs a key of its own)
 //!   GpuServer::clone_on                    (Server is shared by reference between rayon threads, main.rs:55-64; a GPU context
 //!                                           is cloned instead: one PCIe key upload, device-to-device copies, fheaes_clone_keys)
 //!   GpuServerGroup::{new, aes_encrypt, aes_decrypt, add_scalar}
@@ -90,6 +92,10 @@ extern "C" {
     pub fn fheaes_aes_ctr_bits(ctx: *mut fheaes_ctx, round_keys: *const u64, key_bits: u32, iv_hi_lo: *const u64, first_block: u64,
                                data_hi_lo: *const u64, n_blocks: u64, state_out: *mut u64, memspace: c_int) -> c_int;
     pub fn fheaes_aes_public_plan(blocks_hi_lo: *const u64, n_blocks: u64, key_bits: u32, unique_bytes_per_round: *mut u64) -> c_int;
+    // packed ciphertexts: N = 512 bits per GLWE through key block k of the PFPKSK the context holds (no new key), and back
+    pub fn fheaes_packed_words(ctx: *const fheaes_ctx, m: u64) -> usize;
+    pub fn fheaes_pack_bits(ctx: *mut fheaes_ctx, lwe_in: *const u64, m: u64, glwe_out: *mut u64, memspace: c_int) -> c_int;
+    pub fn fheaes_unpack_bits(ctx: *mut fheaes_ctx, glwe_in: *const u64, m: u64, lwe_out: *mut u64, memspace: c_int) -> c_int;
 }
 
 // ------------------------------------------------------------------------------------------------ helpers
@@ -451,6 +457,33 @@ impl GpuServer {
         out.chunks_exact(state_words)
             .map(|block| block.chunks_exact(byte_words).zip(round_keys[0].iter()).map(|(w, like)| rewrap(w, like)).collect())
             .collect()
+    }
+
+    /// Any vector of AES bytes (states, blocks of states) as packed GLWE words: bit t of the flattened bytes in GLWE t / N,
+    /// coefficient t % N; `ceil(m / N) * (k+1) * N` words for m = 8 * bytes.len() bits instead of m * (kN+1).  What a
+    /// transciphering server stores or sends instead of the radix ciphertexts: a packing key switch under block k of the PFPKSK
+    /// the engine already holds, so nothing is added to key generation.  The client decrypts coefficient t of the GLWE phase.
+    pub fn pack(&self, bytes: &[Radix]) -> Vec<u64> {
+        let mut flat = Vec::new();
+        flatten_state(bytes, &mut flat);
+        let m = (8 * bytes.len()) as u64;
+        let mut out = vec![0u64; unsafe { fheaes_packed_words(self.ctx, m) }];
+        let rc = unsafe { fheaes_pack_bits(self.ctx, flat.as_ptr(), m, out.as_mut_ptr(), FHEAES_HOST) };
+        assert!(rc == 0, "{}", self.last_error());
+        out
+    }
+
+    /// The inverse shape: sample extraction of every coefficient, back into the radix bytes of `like` (one per packed byte; they
+    /// give the metadata, as in many_wopbs.rs:87-115).  The bytes come back at nominal noise plus the packing error
+    /// (include/fheaes.h) and are valid inputs of every method above.
+    pub fn unpack(&self, packed: &[u64], like: &[Radix]) -> Vec<Radix> {
+        let m = (8 * like.len()) as u64;
+        assert_eq!(packed.len(), unsafe { fheaes_packed_words(self.ctx, m) });
+        let lwe_words = like[0].blocks()[0].ct.lwe_size().0;
+        let mut out = vec![0u64; m as usize * lwe_words];
+        let rc = unsafe { fheaes_unpack_bits(self.ctx, packed.as_ptr(), m, out.as_mut_ptr(), FHEAES_HOST) };
+        assert!(rc == 0, "{}", self.last_error());
+        out.chunks_exact(8 * lwe_words).zip(like.iter()).map(|(w, l)| rewrap(w, l)).collect()
     }
 }
 

@@ -64,6 +64,9 @@ SIGNATURES = {
     "fheaes_aes_encrypt_public_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_ctr_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _c.c_uint64, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_public_plan": (_c.c_int, [_u64p, _c.c_uint64, _c.c_uint32, _u64p]),
+    "fheaes_packed_words": (_c.c_size_t, [_ctx, _c.c_uint64]),
+    "fheaes_pack_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_unpack_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_profile_enable": (_c.c_int, [_ctx, _c.c_int]),
     "fheaes_profile_reset": (_c.c_int, [_ctx]),
     "fheaes_profile_read": (_c.c_int, [_ctx, _c.c_int, _dp, _u64p, _u64p]),
@@ -306,6 +309,16 @@ class Engine:
         self._check(self._lib.fheaes_aes_ctr_bits(self._h, _ptr(round_keys)[0], key_bits, ivp.ctypes.data_as(_u64p), first_block,
                                                   dat.ctypes.data_as(_u64p) if dat is not None else None, n_blocks, _ptr(state_out)[0],
                                                   self._space(round_keys, state_out)))
+
+    # -- packed ciphertexts: N bits per GLWE (include/fheaes.h) -------------------
+    def packed_words(self, m: int) -> int:
+        return self._lib.fheaes_packed_words(self._h, m)
+
+    def pack_bits(self, lwe_in, m: int, glwe_out):
+        self._check(self._lib.fheaes_pack_bits(self._h, _ptr(lwe_in)[0], m, _ptr(glwe_out)[0], self._space(lwe_in, glwe_out)))
+
+    def unpack_bits(self, glwe_in, m: int, lwe_out):
+        self._check(self._lib.fheaes_unpack_bits(self._h, _ptr(glwe_in)[0], m, _ptr(lwe_out)[0], self._space(glwe_in, lwe_out)))
 
     # -- measurement ------------------------------------------------------------
     def profile_enable(self, on: bool = True):

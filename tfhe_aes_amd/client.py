@@ -227,11 +227,19 @@ CIPHERTEXT_KINDS = {
     "state": (16, 8),           # [blocks][16 bytes][8 bits][kN+1]      Server::aes_encrypt / aes_decrypt / add_scalar
     "round_keys": (11, 16, 8),  # [11][16][8][kN+1]                     Server::aes_key_expansion output ([13] / [15]: AES-192 / AES-256)
     "bytes": (8,),              # [n][8][kN+1]                          sbox / many_sbox inputs
+    "packed": (),               # [G][(k+1)N]                           Server.pack output: N bits per GLWE ciphertext
 }
 
 
+def _kind_tail(kind: str, params: WopbsParameters) -> tuple:
+    """the trailing axes of an array of this kind: LWE ciphertexts of kN+1 words, or (packed) GLWE ciphertexts of (k+1)N"""
+    return CIPHERTEXT_KINDS[kind] + (((params.k + 1) * params.N,) if kind == "packed" else (params.big1,))
+
+
 def _has_kind_shape(shape, kind: str, params: WopbsParameters) -> bool:
-    tail = CIPHERTEXT_KINDS[kind] + (params.big1,)
+    tail = _kind_tail(kind, params)
+    if kind == "packed":
+        return len(shape) == 2 and shape[-1:] == tail
     if kind == "round_keys" and len(shape) >= 4 and shape[-4] in (13, 15):       # Nr + 1 round keys of AES-192 / AES-256
         return shape[-3:] == tail[1:]
     return shape[-len(tail):] == tail
@@ -240,7 +248,7 @@ def _has_kind_shape(shape, kind: str, params: WopbsParameters) -> bool:
 def save_ciphertexts(path, params: WopbsParameters, kind: str, words: np.ndarray) -> None:
     if kind not in CIPHERTEXT_KINDS:
         raise ValueError("kind must be one of %s" % ", ".join(CIPHERTEXT_KINDS))
-    tail = CIPHERTEXT_KINDS[kind] + (params.big1,)
+    tail = _kind_tail(kind, params)
     a = np.ascontiguousarray(words, dtype=np.uint64)
     if not _has_kind_shape(a.shape, kind, params):
         raise ValueError("a %r array must end in shape %r, got %r" % (kind, tail, a.shape))
@@ -391,6 +399,23 @@ class Client:
         count = int(np.prod(shape)) if shape else 1
         _load().fheaes_client_glwe_phase(ctypes.byref(self._c), _u8(self.glwe_sk), _u64(glwe), count, _u64(out))
         return out
+
+    def decrypt_packed(self, packed: np.ndarray, m: int, return_phase: bool = False):
+        """[G][(k+1)N] from Server.pack -> the m bits it holds (bit t: GLWE t // N, coefficient t % N), decoded like decrypt_bits
+        (message at the MSB, rounded); with `return_phase` also the m phases B - sum A_j S_j of those coefficients."""
+        p = self.params
+        packed = np.ascontiguousarray(packed, dtype=np.uint64)
+        m = int(m)
+        if packed.shape != ((m + p.N - 1) // p.N, (p.k + 1) * p.N):
+            raise ValueError("%d bits are packed as [%d][%d] words, got shape %s" % (m, (m + p.N - 1) // p.N, (p.k + 1) * p.N, packed.shape))
+        phase = self.glwe_phase(packed).reshape(-1)[:m]
+        bits = ((phase + np.uint64(1 << 62)) >> np.uint64(63)).astype(np.uint8)
+        return (bits, phase) if return_phase else bits
+
+    def decrypt_packed_bytes(self, packed: np.ndarray, n_bytes: int) -> np.ndarray:
+        """the packed form of [n_bytes][8][kN+1] (states, blocks of states: any array of bytes) -> uint8[n_bytes]"""
+        bits = self.decrypt_packed(packed, 8 * int(n_bytes)).reshape(-1, 8).astype(np.uint64)
+        return (bits << np.arange(8, dtype=np.uint64)).sum(axis=-1).astype(np.uint8)
 
     # -- verification (client.rs:147-216) --------------------------------------
     def client_decrypt_and_verify(self, states) -> None:

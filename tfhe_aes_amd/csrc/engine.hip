@@ -745,6 +745,51 @@ int fheaes_aes_public_plan(const uint64_t *blocks_hi_lo, uint64_t n_blocks, uint
     return FHEAES_OK;
 }
 
+// ---- packing ----------------------------------------------------------------------------------
+size_t fheaes_packed_words(const fheaes_ctx *c, uint64_t m)
+{
+    if (!c) return 0;
+    return (size_t)((m + FHE_N - 1) / FHE_N) * c->k1 * FHE_N;
+}
+
+static bool overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+int fheaes_pack_bits(fheaes_ctx *c, const uint64_t *lwe_in, uint64_t m, uint64_t *glwe_out, int memspace)
+{
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (m == 0) return FHEAES_OK;
+    if (!lwe_in || !glwe_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    const uint64_t in_bytes = m * c->big1 * 8, out_bytes = (uint64_t)fheaes_packed_words(c, m) * 8;
+    if (overlap(lwe_in, in_bytes, glwe_out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "lwe_in and glwe_out overlap (packing is not in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    TRY(s.in(lwe_in, in_bytes, &lwe_in));
+    TRY(s.out(glwe_out, out_bytes, &glwe_out));
+    TRY(pack_dev(c, lwe_in, m, glwe_out));
+    return s.finish();
+}
+
+int fheaes_unpack_bits(fheaes_ctx *c, const uint64_t *glwe_in, uint64_t m, uint64_t *lwe_out, int memspace)
+{
+    CtxLock lock__(c);
+    if (!c) return FHEAES_ERR_INVALID;
+    if (m == 0) return FHEAES_OK;
+    if (!glwe_in || !lwe_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    const uint64_t in_bytes = (uint64_t)fheaes_packed_words(c, m) * 8, out_bytes = m * c->big1 * 8;
+    if (overlap(glwe_in, in_bytes, lwe_out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "glwe_in and lwe_out overlap (unpacking is not in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    TRY(s.in(glwe_in, in_bytes, &glwe_in));
+    TRY(s.out(lwe_out, out_bytes, &lwe_out));
+    TRY(unpack_dev(c, glwe_in, m, lwe_out));
+    return s.finish();
+}
+
 // ---- measurement ------------------------------------------------------------------------------
 int fheaes_profile_enable(fheaes_ctx *c, int on)
 {

@@ -73,8 +73,9 @@ int launch_keyswitch(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *ou
     return FHEAES_OK;
 }
 
-// out: rows of one GGSW level: [m][out_stride] with key r at offset r*(k+1)N
-int launch_pfpks(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out, uint64_t out_stride)
+// out: rows of one GGSW level: [m][out_stride] with key r at offset r*(k+1)N.  `block` >= 0: key block r = `block` alone, its
+// (k+1)N words at offset 0 of every row (block k is the LWE -> GLWE key of fheaes_pack_bits): a fifth of the matrix product
+int launch_pfpks(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out, uint64_t out_stride, int block = -1)
 {
     if (m == 0) return FHEAES_OK;
     StageScope sc(c, FHEAES_STAGE_PFPKS, m);
@@ -86,9 +87,10 @@ int launch_pfpks(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out, u
     ks_launch_digits_k3(dim3((unsigned)((threads + 255) / 256)), c->stream, in, (uint64_t)c->big1, c->big1, m, c->pf_ksteps, af);
     KeyswitchArgs a{};
     a.afrag = af; a.bfrag = c->pfpksk_frag; a.ksteps = c->pf_ksteps; a.coltiles = c->pf_coltiles;
+    if (block >= 0) a.bfrag += (size_t)block * c->pf_ksteps * c->pf_coltiles * 8 * 1024;
     a.in = in; a.in_stride = c->big1; a.body_index = -1; a.body_col = 0; a.ncols = gsz;
-    a.out = out; a.out_stride = out_stride; a.out_z_stride = gsz; a.m = m;
-    dim3 grid((c->pf_coltiles + KSL_COL_TILES - 1) / KSL_COL_TILES, (unsigned)((m + 16 * KSL_CT_TILES - 1) / (16 * KSL_CT_TILES)), c->k1);
+    a.out = out; a.out_stride = out_stride; a.out_z_stride = block >= 0 ? 0 : gsz; a.m = m;
+    dim3 grid((c->pf_coltiles + KSL_COL_TILES - 1) / KSL_COL_TILES, (unsigned)((m + 16 * KSL_CT_TILES - 1) / (16 * KSL_CT_TILES)), block >= 0 ? 1 : c->k1);
     ks_launch_mfma_lds(2, grid, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
@@ -341,6 +343,49 @@ int launch_add2(fheaes_ctx *c, uint64_t *dst, const uint64_t *a, const uint64_t 
     unsigned grid = (unsigned)std::min<uint64_t>((words + 255) / 256, 16384);
     hipLaunchKernelGGL(add2_kernel, dim3(grid), dim3(256), 0, c->stream, dst, a, b, words);
     HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+// ---- packing (fheaes_pack_bits, fheaes_unpack_bits) ---------------------------------------------------------------------------
+static_assert(PACK_N == FHE_N && PACK_N % PACK_FOLD_ROWS == 0, "kern_linear.h's packing kernels are written for N = 512");
+
+// in [m][kN+1] -> out [ceil(m/N)][(k+1)N], device pointers.  Chunks start on multiples of N bits, so a GLWE belongs to one chunk.
+// Key block k's switch of a chunk goes into ws_ggsw, the workspace K3 owns: (k+1)N words per bit where a GGSW level takes (k+1)^2 N,
+// so a workspace that fheaes_reserve (or an earlier WoPBS) has sized for b bits holds a chunk of up to 5b here and is not grown;
+// only a context that has less than one GLWE's worth of it allocates (for this call's bits, at most MAX_CHUNK_BITS).
+int pack_dev(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out)
+{
+    if (m == 0) return FHEAES_OK;
+    const uint64_t gsz = (uint64_t)c->k1 * FHE_N;
+    uint64_t chunk = c->ws_ggsw.bytes / (gsz * 8) / FHE_N * FHE_N;
+    if (chunk == 0) {
+        chunk = std::min<uint64_t>((m + FHE_N - 1) / FHE_N * FHE_N, MAX_CHUNK_BITS);
+        TRY(ensure(c, c->ws_ggsw, chunk * gsz * 8));
+    }
+    chunk = std::min<uint64_t>(chunk, MAX_CHUNK_BITS);
+    uint64_t *ks = (uint64_t *)c->ws_ggsw.p;
+    for (uint64_t t0 = 0; t0 < m; t0 += chunk) {
+        const uint64_t mc = std::min<uint64_t>(chunk, m - t0), glwes = (mc + FHE_N - 1) / FHE_N;
+        TRY(launch_pfpks(c, in + t0 * c->big1, mc, ks, gsz, (int)c->k));
+        uint64_t *o = out + t0 / FHE_N * gsz;
+        StageScope sc(c, FHEAES_STAGE_LINEAR, mc);
+        HIP_TRY(c, hipMemsetAsync(o, 0, glwes * gsz * 8, c->stream));
+        hipLaunchKernelGGL(pack_fold_kernel, dim3(FHE_N / PACK_FOLD_ROWS, c->k1, (unsigned)glwes), dim3(256), 0, c->stream, ks, mc, c->k1, o);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return FHEAES_OK;
+}
+
+// in [ceil(m/N)][(k+1)N] -> out [m][kN+1], device pointers: a permutation with signs, no workspace, no keys
+int unpack_dev(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out)
+{
+    for (uint64_t t0 = 0; t0 < m; t0 += MAX_CHUNK_BITS) {
+        const uint64_t mc = std::min<uint64_t>(MAX_CHUNK_BITS, m - t0);
+        StageScope sc(c, FHEAES_STAGE_LINEAR, mc);
+        hipLaunchKernelGGL(sample_extract_kernel, dim3((unsigned)((mc + UNPACK_BITS_PER_WG - 1) / UNPACK_BITS_PER_WG)), dim3(256), 0, c->stream,
+                           in + t0 / FHE_N * (uint64_t)c->k1 * FHE_N, mc, c->k, out + t0 * c->big1);
+        HIP_TRY(c, hipGetLastError());
+    }
     return FHEAES_OK;
 }
 

@@ -217,3 +217,78 @@ __global__ __launch_bounds__(256) void expand_masks_kernel(uint64_t *out, const 
         }
     }
 }
+
+// ---- packing: N bits in the N coefficients of one GLWE (fheaes_pack_bits, fheaes_unpack_bits) -----------------------------------
+// ks[t] = [(k+1)][N]: LWE t through key block r = k of the PFPKSK (f(x) = x: the message sits in the constant coefficient).
+//   packed[g] = sum_{i < cnt_g} X^i * ks[gN + i]   negacyclic in each polynomial: coefficient c takes +P[c - i] (c >= i), -P[c - i + N] (c < i)
+// Every input word is read once and nothing is reused: the kernel is a stream over ks.  One workgroup takes PACK_FOLD_ROWS values of i
+// for one (GLWE, polynomial): for fixed i the 512 rotated reads of a row are two contiguous runs, each thread keeps coefficients c and
+// c + 256, and the partial sums of the N / PACK_FOLD_ROWS workgroups of a polynomial meet in `packed` (zeroed by the launcher) with one
+// 64-bit atomic add per coefficient.  Wrapping integer sums: any order gives the same words.
+#define PACK_N 512
+#define PACK_FOLD_ROWS 32
+#define PACK_FOLD_UNROLL 8
+
+// ks: [m][k1][N] (bits of this launch, the first one at coefficient 0 of packed[0]); packed: [ceil(m / N)][k1][N], zero on entry
+__global__ __launch_bounds__(256) void pack_fold_kernel(const uint64_t *ks, uint64_t m, uint32_t k1, uint64_t *packed)
+{
+    const uint32_t split = blockIdx.x, j = blockIdx.y;
+    const uint64_t g = blockIdx.z;
+    const uint64_t left = m - g * PACK_N;                               // bits of this GLWE onward: the grid has no GLWE beyond m
+    const uint32_t cnt = left < PACK_N ? (uint32_t)left : PACK_N;
+    const uint32_t i0 = split * PACK_FOLD_ROWS;
+    if (i0 >= cnt) return;                                              // a partly filled last GLWE: nothing to add from here on
+    const uint32_t i1 = i0 + PACK_FOLD_ROWS < cnt ? i0 + PACK_FOLD_ROWS : cnt;
+    const uint32_t c = threadIdx.x;                                     // coefficients c and c + 256
+    const uint64_t row_words = (uint64_t)k1 * PACK_N;
+    const uint64_t *src = ks + (g * PACK_N) * row_words + (uint64_t)j * PACK_N;
+    uint64_t lo = 0, hi = 0;
+    uint32_t i = i0;
+    for (; i + PACK_FOLD_UNROLL <= i1; i += PACK_FOLD_UNROLL) {
+        uint64_t a[PACK_FOLD_UNROLL], b[PACK_FOLD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < PACK_FOLD_UNROLL; ++u) {
+            const uint64_t *row = src + (uint64_t)(i + u) * row_words;
+            a[u] = row[(c - (i + u)) & (PACK_N - 1)];
+            b[u] = row[(c + 256 - (i + u)) & (PACK_N - 1)];
+        }
+#pragma unroll
+        for (int u = 0; u < PACK_FOLD_UNROLL; ++u) {
+            lo += c >= i + u ? a[u] : (uint64_t)0 - a[u];
+            hi += c + 256 >= i + u ? b[u] : (uint64_t)0 - b[u];
+        }
+    }
+    for (; i < i1; ++i) {
+        const uint64_t *row = src + (uint64_t)i * row_words;
+        const uint64_t a = row[(c - i) & (PACK_N - 1)], b = row[(c + 256 - i) & (PACK_N - 1)];
+        lo += c >= i ? a : (uint64_t)0 - a;
+        hi += c + 256 >= i ? b : (uint64_t)0 - b;
+    }
+    unsigned long long *dst = (unsigned long long *)(packed + g * row_words + (uint64_t)j * PACK_N);
+    atomicAdd(dst + c, (unsigned long long)lo);
+    atomicAdd(dst + c + 256, (unsigned long long)hi);
+}
+
+// Sample extraction of coefficient i = t % N of GLWE t / N: the blind rotation's extraction of coefficient 0, for any coefficient.
+//   mask word jN + c = A_j[i - c] (c <= i), -A_j[i - c + N] (c > i); body = B[i]
+// One workgroup per bit writes the kN + 1 words of its LWE in order; the reads run backwards through a polynomial that the N bits of a
+// GLWE share (20 KB, cache resident), so HBM sees the writes: 16,392 B per bit.
+// packed: [ceil(m / N)][k + 1][N]; lwe: [m][kN + 1]
+#define UNPACK_BITS_PER_WG 4
+__global__ __launch_bounds__(256) void sample_extract_kernel(const uint64_t *packed, uint64_t m, uint32_t k, uint64_t *lwe)
+{
+    const uint32_t big = k * PACK_N;
+    for (uint32_t u = 0; u < UNPACK_BITS_PER_WG; ++u) {
+        const uint64_t t = (uint64_t)blockIdx.x * UNPACK_BITS_PER_WG + u;
+        if (t >= m) return;
+        const uint32_t i = (uint32_t)(t & (PACK_N - 1));
+        const uint64_t *glwe = packed + (t / PACK_N) * (uint64_t)(k + 1) * PACK_N;
+        uint64_t *o = lwe + t * (uint64_t)(big + 1);
+        for (uint32_t w = threadIdx.x; w < big; w += blockDim.x) {
+            const uint32_t c = w & (PACK_N - 1);
+            const uint64_t v = glwe[(w - c) + ((i - c) & (PACK_N - 1))];
+            o[w] = c <= i ? v : (uint64_t)0 - v;
+        }
+        if (threadIdx.x == 0) o[big] = glwe[(uint64_t)big + i];
+    }
+}

@@ -217,6 +217,42 @@ class Server:
             raise ValueError("out must be %s, got %s" % (shape, tuple(out.shape)))
         return out
 
+    # ---- packed ciphertexts ------------------------------------------------------
+    def pack(self, ct, out=None):
+        """any [..., kN+1] array of one-bit LWE ciphertexts -> [G][(k+1)N], G = ceil(m / N) GLWE ciphertexts holding N = 512 bits each, in
+        the memory space of `ct`: bit t of the flattened input sits in GLWE t // N, coefficient t % N (include/fheaes.h:
+        fheaes_pack_bits).  409.8 times smaller at PARAM_OPT; no key beyond the ones the Server holds; Client.decrypt_packed reads it."""
+        p = self.params
+        if int(ct.shape[-1]) != p.big1:
+            raise ValueError("pack takes [..., kN+1] = [..., %d] words, got shape %s" % (p.big1, tuple(ct.shape)))
+        m = 1
+        for d in ct.shape[:-1]:
+            m *= int(d)
+        shape = ((m + p.N - 1) // p.N, (p.k + 1) * p.N)
+        if out is None:
+            out = _empty_like(ct, shape)
+        elif tuple(out.shape) != shape:
+            raise ValueError("out must be %s, got %s" % (shape, tuple(out.shape)))
+        if m:
+            self.engine.pack_bits(ct, m, out)
+        return out
+
+    def unpack(self, packed, shape, out=None):
+        """the inverse shape: [G][(k+1)N] -> [*shape, kN+1] (sample extraction of coefficient t % N of GLWE t // N for bit t), LWE
+        ciphertexts under the big key that every entry point takes; `shape` may be an int (the number of bits)."""
+        p = self.params
+        shape = (int(shape),) if isinstance(shape, int) else tuple(int(d) for d in shape)
+        m = 1
+        for d in shape:
+            m *= d
+        if tuple(packed.shape) != ((m + p.N - 1) // p.N, (p.k + 1) * p.N):
+            raise ValueError("%d bits are packed as [%d][%d] words, got shape %s" % (m, (m + p.N - 1) // p.N, (p.k + 1) * p.N, tuple(packed.shape)))
+        if out is None:
+            out = _empty_like(packed, shape + (p.big1,))
+        if m:
+            self.engine.unpack_bits(packed, m, out)
+        return out
+
     # README.md:57-59 spellings
     aes_encryption = aes_encrypt
     aes_decryption = aes_decrypt
@@ -242,28 +278,21 @@ class ServerGroup:
         for d in devices[1:]:
             self.servers.append(Server(None, device=d, clone_from=self.servers[0]))
 
-    def _fan_out(self, fn, state):
+    def _run_shards(self, jobs):
+        """one host thread per context; jobs[i] is None (an empty shard) or a callable for context i"""
         import threading
 
-        from .dist import shard_blocks
-
-        if state.ndim != 4:
-            # Server.aes_encrypt also takes ONE state [16][8][kN+1]; here the first axis is what gets sharded, so a single state would
-            # be cut into 16 "blocks" of one byte each: refuse it instead of computing nonsense
-            raise ValueError("ServerGroup works on a batch [n_blocks][16][8][kN+1]; wrap a single state as state[None]")
-        n, g = int(state.shape[0]), len(self.servers)
-        errs = [None] * g
+        errs = [None] * len(jobs)
 
         def work(i):
-            lo, hi = shard_blocks(n, g, i)
             try:
-                if hi > lo:
-                    fn(self.servers[i], state[lo:hi], lo)
+                if jobs[i] is not None:
+                    jobs[i](self.servers[i])
                     self.servers[i].synchronize()
             except Exception as e:       # surfaced below, on the caller's thread
                 errs[i] = e
 
-        ts = [threading.Thread(target=work, args=(i,)) for i in range(g)]
+        ts = [threading.Thread(target=work, args=(i,)) for i in range(len(jobs))]
         for t in ts:
             t.start()
         for t in ts:
@@ -271,6 +300,17 @@ class ServerGroup:
         for e in errs:
             if e is not None:
                 raise e
+
+    def _fan_out(self, fn, state):
+        from .dist import shard_blocks
+
+        if state.ndim != 4:
+            # Server.aes_encrypt also takes ONE state [16][8][kN+1]; here the first axis is what gets sharded, so a single state would
+            # be cut into 16 "blocks" of one byte each: refuse it instead of computing nonsense
+            raise ValueError("ServerGroup works on a batch [n_blocks][16][8][kN+1]; wrap a single state as state[None]")
+        n, g = int(state.shape[0]), len(self.servers)
+        shards = [shard_blocks(n, g, i) for i in range(g)]
+        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: fn(s, state[lo:hi], lo)) for lo, hi in shards])
         return state
 
     def aes_encrypt(self, round_keys, state):
@@ -312,6 +352,44 @@ class ServerGroup:
 
     def aes_key_expansion(self, key):
         return self.servers[0].aes_key_expansion(key)
+
+    def _glwe_shards(self, n_glwes: int):
+        from .dist import shard_blocks
+
+        return [shard_blocks(n_glwes, len(self.servers), i) for i in range(len(self.servers))]
+
+    def pack(self, ct):
+        """Server.pack, sharded on whole GLWEs (N bits = 4 AES blocks): context i packs GLWEs i * G / n .. of the flattened input, so the
+        words are those of one context whatever the number of contexts"""
+        p = self.params
+        if int(ct.shape[-1]) != p.big1:
+            raise ValueError("pack takes [..., kN+1] = [..., %d] words, got shape %s" % (p.big1, tuple(ct.shape)))
+        flat = ct.reshape(-1, p.big1)
+        m = int(flat.shape[0])
+        out = _empty_like(ct, ((m + p.N - 1) // p.N, (p.k + 1) * p.N))
+        jobs = []
+        for lo, hi in self._glwe_shards(int(out.shape[0])):
+            b0, b1 = lo * p.N, min(hi * p.N, m)
+            jobs.append(None if hi <= lo else (lambda s, lo=lo, hi=hi, b0=b0, b1=b1: s.pack(flat[b0:b1], out=out[lo:hi])))
+        self._run_shards(jobs)
+        return out
+
+    def unpack(self, packed, shape):
+        """Server.unpack with the same split: context i extracts the bits of its GLWEs"""
+        p = self.params
+        shape = (int(shape),) if isinstance(shape, int) else tuple(int(d) for d in shape)
+        m = 1
+        for d in shape:
+            m *= d
+        if tuple(packed.shape) != ((m + p.N - 1) // p.N, (p.k + 1) * p.N):
+            raise ValueError("%d bits are packed as [%d][%d] words, got shape %s" % (m, (m + p.N - 1) // p.N, (p.k + 1) * p.N, tuple(packed.shape)))
+        out = _empty_like(packed, (m, p.big1))
+        jobs = []
+        for lo, hi in self._glwe_shards(int(packed.shape[0])):
+            b0, b1 = lo * p.N, min(hi * p.N, m)
+            jobs.append(None if hi <= lo else (lambda s, lo=lo, hi=hi, b0=b0, b1=b1: s.unpack(packed[lo:hi], b1 - b0, out=out[b0:b1])))
+        self._run_shards(jobs)
+        return out.reshape(shape + (p.big1,))
 
     def clone_info(self):
         """per cloned context: how its keys got there ({"path": "same_device" | "peer" | "staged", "bytes", "seconds"})"""
