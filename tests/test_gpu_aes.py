@@ -16,6 +16,11 @@ def toy_server(toy):
     return Server(toy.keys, device=0, engine=toy.engine())
 
 
+@pytest.fixture(scope="module")
+def opt_server(opt):
+    return Server(opt.keys, device=0, engine=opt.engine())
+
+
 @pytest.mark.parametrize("n_luts_set", [orc.LUTSET_SBOX, orc.LUTSET_ENC_ROUND, orc.LUTSET_DEC_MUL])
 def test_many_wopbs_8bit(toy, toy_server, n_luts_set):
     vals = [0x00, 0x53, 0xFF, 0xA7, 0x10]
@@ -66,6 +71,26 @@ def test_many_wopbs_wider_than_log_n_uses_the_cmux_tree(toy, toy_server, nb, n_l
             assert int(sum(int(dec[i, li, j]) << j for j in range(nb))) == f(v), (v, li)
 
 
+def test_many_wopbs_11bit_at_k4_hands_the_cmux_root_to_vertical_packing(opt, opt_server):
+    """The same at the reference's parameter set (k = 4: cmux_level_kernel<5,15,3> and vertical_packing_kernel<5,15,3>), 2 inputs of
+    11 bits, 1 LUT: 11 instances per input are no multiple of the 3 a workgroup carries, so the clamped slots run; two tree levels,
+    the first from the LUT polynomials, the second from the ping-pong buffer; the root reaches the blind rotation as a GLWE.
+    Bit-exact against the oracle + decrypts to f(x)."""
+    c, nb = opt.client, 11
+    f = lambda v: (v * 37 + 5) % (1 << nb)
+    lut = gen_lut(2, 1, 512, nb, f)
+    assert lut.shape == (nb, 1 << nb)
+    vals = [0x3A5, 0x5C2]                                   # bits 10, 9 = 0, 1 and 1, 0: both sides of both tree levels
+    bits = np.array([[(v >> j) & 1 for j in range(nb)] for v in vals], dtype=np.uint8)
+    x = c.encrypt_bits(bits)
+    got = opt_server.many_wopbs_without_padding(x, [lut])
+    want = opt.oracle.wopbs_batch(x, np.stack([lut]))
+    assert np.array_equal(got, want)
+    dec = c.decrypt_bits(got)
+    for i, v in enumerate(vals):
+        assert int(sum(int(dec[i, 0, j]) << j for j in range(nb))) == f(v), v
+
+
 def test_sbox_and_many_sbox(toy, toy_server):
     c = toy.client
     vals = [0x3C, 0x00, 0x80]
@@ -99,11 +124,6 @@ def test_aes_pipeline_bit_exact_and_golden(golden):
     assert sha(srv.aes_decrypt(rk, enc.copy())) == g["aes_decrypt"]
     assert sha(srv.add_scalar(st.copy(), 0x1FF)) == g["add_scalar_0x1ff"]
     c.test_verify(enc, srv.aes_decryption(rk, enc.copy()))  # Client::test_verify (client.rs:178-216)
-
-
-@pytest.fixture(scope="module")
-def opt_server(opt):
-    return Server(opt.keys, device=0, engine=opt.engine())
 
 
 @pytest.mark.parametrize("which", ["toy", "opt"])

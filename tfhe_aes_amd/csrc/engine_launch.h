@@ -176,8 +176,8 @@ K2Launch k2_launch(fheaes_ctx *c, uint64_t m)
         L.threads = BL_THREADS;
         if (c->k1 == 5) { L.kernel = blind_rotate_latency_kernel<5, 5, 8>; L.name = "blind_rotate_latency_kernel<5,5,8>"; }
         else { L.kernel = blind_rotate_latency_kernel<2, 5, 8>; L.name = "blind_rotate_latency_kernel<2,5,8>"; }
-        // (257..768 bits: the throughput form below with at most one workgroup per CU, 14.6 ms per launch; the round-1
-        //  one-ciphertext-per-workgroup form of kern_extprod.h took 21.6 ms there and the latency form in two waves 16-18 ms)
+        // (257..768 bits: the throughput form below with at most one workgroup per CU, 14.6 ms per launch; the latency form in
+        //  two waves took 16-18 ms there)
     } else if (L.pl.form == 2) {
         // paired throughput form (kern_blindrot_pair.h): one 512-thread workgroup per CU, 6 (or 4) ciphertexts share every key fetch
         L.threads = BRP_THREADS;
@@ -252,6 +252,11 @@ int launch_vertical_packing(fheaes_ctx *c, const double2 *ggswf, uint64_t n_inpu
 {
     if (n_inputs == 0) return FHEAES_OK;
     StageScope sc(c, FHEAES_STAGE_VERTICAL_PACKING, n_inputs * n_luts * bits);
+    // the kernel pair of this parameter set and R, its instances (or CMUX jobs) per workgroup
+    const bool k4 = c->k1 == 5;
+    const uint32_t R = k4 ? 3 : 8;
+    void (*const cmux_kernel)(CmuxArgs) = k4 ? cmux_level_kernel<5, 15, 3> : cmux_level_kernel<2, 15, 8>;
+    void (*const vp_kernel)(VpArgs) = k4 ? vertical_packing_kernel<5, 15, 3> : vertical_packing_kernel<2, 15, 8>;
     const uint32_t inst_per_input = n_luts * bits;
     const uint64_t W = lut_row_words(bits);
     // ---- inputs wider than 9 bits: CMUX tree over bits 9..bits-1 (kern_extprod.h, cmux_level_kernel), root -> ws_tree ----
@@ -270,33 +275,19 @@ int launch_vertical_packing(fheaes_ctx *c, const double2 *ggswf, uint64_t n_inpu
             a.bits = bits; a.bit = 9 + t; a.nodes_out = 1u << (tree_bits - 1 - t);
             a.inst_per_input = inst_per_input; a.lut_per_input = per_input ? 1 : 0; a.lut_words = W;
             const uint64_t jobs = (uint64_t)inst_per_input * a.nodes_out;
-            if (c->k1 == 5) {
-                constexpr int R = 3;
-                a.wg_per_input = (uint32_t)((jobs + R - 1) / R);
-                hipLaunchKernelGGL((cmux_level_kernel<5, 15, R>), dim3((unsigned)(n_inputs * a.wg_per_input)), dim3(EP_THREADS), 0, c->stream, a);
-            } else {
-                constexpr int R = 8;
-                a.wg_per_input = (uint32_t)((jobs + R - 1) / R);
-                hipLaunchKernelGGL((cmux_level_kernel<2, 15, R>), dim3((unsigned)(n_inputs * a.wg_per_input)), dim3(EP_THREADS), 0, c->stream, a);
-            }
+            a.wg_per_input = (uint32_t)((jobs + R - 1) / R);
+            hipLaunchKernelGGL(cmux_kernel, dim3((unsigned)(n_inputs * a.wg_per_input)), dim3(EP_THREADS), 0, c->stream, a);
             HIP_TRY(c, hipGetLastError());
         }
         glwe_root = buf[(tree_bits - 1) & 1];
     }
-    ExtProdArgs a{};
+    VpArgs a{};
     a.ggsw = ggswf; a.tw = c->tw_d;
-    a.out = out; a.count = n_inputs * n_luts * bits; a.iters = bits < 9 ? bits : 9; a.ggsw_per_input = bits;
+    a.out = out; a.iters = bits < 9 ? bits : 9; a.ggsw_per_input = bits;
     a.luts = luts; a.lut_words = W; a.glwe_in = glwe_root;
-    a.n_luts = n_luts; a.lut_per_input = per_input ? 1 : 0; a.inst_per_input = inst_per_input;
-    if (c->k1 == 5) {
-        constexpr int R = 3;
-        a.wg_per_input = (a.inst_per_input + R - 1) / R;
-        hipLaunchKernelGGL((extprod_rotate_kernel<5, 1, 15, R, true>), dim3((unsigned)(n_inputs * a.wg_per_input)), dim3(EP_THREADS), 0, c->stream, a);
-    } else {
-        constexpr int R = 8;
-        a.wg_per_input = (a.inst_per_input + R - 1) / R;
-        hipLaunchKernelGGL((extprod_rotate_kernel<2, 1, 15, R, true>), dim3((unsigned)(n_inputs * a.wg_per_input)), dim3(EP_THREADS), 0, c->stream, a);
-    }
+    a.lut_per_input = per_input ? 1 : 0; a.inst_per_input = inst_per_input;
+    a.wg_per_input = (inst_per_input + R - 1) / R;
+    hipLaunchKernelGGL(vp_kernel, dim3((unsigned)(n_inputs * a.wg_per_input)), dim3(EP_THREADS), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }

@@ -1,8 +1,8 @@
 // kern_blindrot16.h -- K2, blind rotation of the circuit-bootstrap PBS + sample extract,
-// throughput form for large batches (the same arithmetic and lane mapping as extprod_rotate_kernel in
-// kern_extprod.h, which stays the form of K5; bit-identical results).
+// throughput form for large batches: R ciphertexts per 256-thread workgroup in the lane mapping stated at the top of
+// kern_extprod.h, five decomposition levels per iteration through one ring of LDS tiles.
 //
-// What differs from kern_extprod.h, and why (measured with per-phase s_memtime stamps and rocprofv3 counters, profiles/r02_*, r03_*):
+// What it does beyond that mapping, and why (measured with per-phase s_memtime stamps and rocprofv3 counters, profiles/r02_*, r03_*):
 //  * the accumulator (64 VGPRs per lane) is dead weight between the rotation at the top of an iteration and the
 //    accumulate at its end; it is PARKED: stored once per iteration with coalesced 16-byte buffer stores into a per-workgroup
 //    slab, reloaded (non-temporal: its last use) into registers that are free by then, a whole products exchange + inverse

@@ -1,16 +1,17 @@
-// kern_extprod.h -- the external-product kernels:
-//   K2  blind rotation of the circuit-bootstrap PBS + sample extract   
-//   K5  vertical packing = CMUX blind rotation over the LUT + sample extract (8 a15)
-//   K4  torus polynomials -> Fourier domain (BSK upload, ggsw.fill_with_forward_fourier, 8 a14)
+// kern_extprod.h -- what the external-product kernels share, and the ones that are not the blind rotation:
+//   shared  ExtProdArgs, ep_key_load, ep_load_table, EP_STAMP, EP_THREADS / EP_GROUPS: used by K2, the blind rotation of the
+//           circuit-bootstrap PBS, whose three forms are kern_blindrot_latency.h, kern_blindrot16.h and kern_blindrot_pair.h
+//   K5      vertical packing = CMUX blind rotation over the LUT + sample extract: vertical_packing_kernel,
+//           and cmux_level_kernel, the CMUX tree in front of it for inputs wider than 9 bits
+//   K4      torus polynomials -> Fourier domain (BSK upload, ggsw.fill_with_forward_fourier, 8 a14): forward_fourier_kernel
 //
-// One 256-thread workgroup = 16 lane-groups of 16.  Group g < R*K1 owns polynomial p = g % K1 of
-// ciphertext r = g / K1 of the workgroup's R ciphertexts: its 512 accumulator coefficients live
-// in that group's registers for the whole rotation (coefficients 16a+b and 256+16a+b in lane b).
-// Per iteration and per decomposition level the groups transform their digit polynomials
-// (fft_dev.h) into the LDS tile ring, then ALL 256 threads switch roles: thread t owns Fourier
-// point t and multiplies the R x K1 transformed digits with the K1 x K1 GGSW entries streamed from
-// HBM/L2, so each 16-byte key element fetched is used by R ciphertexts.  After the last level the
-// products go back through LDS to the owning groups for the inverse transform.
+// The lane mapping of K5 and of the CMUX tree (the blind-rotation headers start from the same one).  One 256-thread workgroup =
+// 16 lane-groups of 16.  Group g < R*K1 owns polynomial p = g % K1 of instance r = g / K1 of the workgroup's R instances: its 512
+// accumulator coefficients live in that group's registers for the whole rotation (coefficients 16a+b and 256+16a+b in lane b).
+// Per iteration the groups transform their digit polynomials (fft_dev.h) into their LDS tiles, then ALL 256 threads switch roles:
+// thread t owns Fourier point t and multiplies the R x K1 transformed digits with the K1 x K1 GGSW entries streamed from HBM/L2,
+// so each 16-byte key element fetched is used by R instances.  The products go back through LDS to the owning groups for the
+// inverse transform.
 #pragma once
 #include "fft_dev.h"
 
@@ -29,27 +30,17 @@ __device__ __forceinline__ void ep_load_table(double2 *tw_lds, const double2 *tw
     for (int i = threadIdx.x; i < FHE_TW_ENTRIES; i += blockDim.x) tw_lds[i] = tw_g[i];
 }
 
+// the blind rotation's arguments, all three forms (kern_blindrot_latency.h, kern_blindrot16.h, kern_blindrot_pair.h)
 struct ExtProdArgs {
-    // common
-    const double2 *ggsw;        // PBS: BSK Fourier [n][L][K1][K1][256]; VP: [n_inputs][bits][L][K1][K1][256]
+    const double2 *ggsw;        // BSK Fourier [n][L][K1][K1][256]
     const double2 *tw;          // [FHE_TW_ENTRIES] tw[17 k1 + b] = psi^(b (4 k1 + 1)), the transform's one table (fft_dev.h)
-    uint64_t *out;              // PBS: [m][big+1]; VP: [n_inputs][n_luts][bits][big+1]
-    uint64_t count;             // PBS: ciphertexts m; VP: n_inputs * n_luts * bits instances
-    uint32_t iters;             // PBS: n; VP: bits
-    // PBS mode
+    uint64_t *out;              // [m][big+1]
+    uint64_t count;             // ciphertexts m
+    uint32_t iters;             // n
     const uint64_t *lwe_in;     // [m][n+1]
     uint64_t tv_const;          // every coefficient of the test vector
     uint64_t body_shift;        // added to the input body before the modulus switch (2^62)
     uint64_t post_add;          // added to the output body
-    // VP mode
-    const uint64_t *luts;       // [n_sets][n_luts][bits][512]
-    uint32_t n_luts;
-    uint32_t lut_per_input;
-    uint32_t inst_per_input;    // n_luts * bits
-    uint32_t wg_per_input;      // ceil(inst_per_input / R)
-    uint32_t ggsw_per_input;    // VP: GGSWs per input in `ggsw` (= input bits; `iters` of them, the low bits, drive the rotation)
-    uint64_t lut_words;         // VP: words per (LUT, output bit) in `luts` (512, or 2^bits when a CMUX tree ran first)
-    const uint64_t *glwe_in;    // VP: non-null: the accumulator starts from this GLWE [instance][K1][512] (root of the CMUX tree)
     uint64_t *park;             // kern_blindrot16.h: accumulator parking space, 64 KB per workgroup
     uint64_t park_bytes;        //   its size (< 2^31: one raw buffer)
     uint32_t *park_owner;       // kern_blindrot_pair.h: owner words of the shared parking slots (0 = free), or null: one private slot per workgroup
@@ -79,8 +70,26 @@ __device__ __forceinline__ double2 ep_key_load(__amdgpu_buffer_rsrc_t rsrc, unsi
 #define EP_STAMP(ph) do { } while (0)
 #endif
 
-template <int K1, int LEVELS, int BASE_LOG, int R, bool VP>
-__global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kernel(const ExtProdArgs A)
+// K5's arguments
+struct VpArgs {
+    const double2 *ggsw;        // Fourier GGSWs [n_inputs][ggsw_per_input][K1][K1][256]
+    const double2 *tw;          // [FHE_TW_ENTRIES] the transform's one table (fft_dev.h)
+    uint64_t *out;              // [n_inputs][n_luts][bits][big+1]
+    uint32_t iters;             // GGSWs per input that drive the rotation: the low min(bits, 9)
+    const uint64_t *luts;       // [n_sets][n_luts][bits][lut_words]
+    uint32_t lut_per_input;     // 1: every input has a LUT set of its own; 0: all share set 0
+    uint32_t inst_per_input;    // n_luts * bits
+    uint32_t wg_per_input;      // ceil(inst_per_input / R)
+    uint32_t ggsw_per_input;    // GGSWs per input in `ggsw` (= input bits)
+    uint64_t lut_words;         // words per (LUT, output bit) in `luts` (512, or 2^bits when a CMUX tree ran first)
+    const uint64_t *glwe_in;    // non-null: the accumulator starts from this GLWE [instance][K1][512] (root of the CMUX tree)
+};
+
+// K5: one workgroup blind-rotates R LUT polynomials of one radix input over that input's GGSWs (one decomposition level), bit `it`
+// rotating by X^(-2^it), and sample-extracts coefficient 0 of each.  The accumulator starts from the LUT polynomial as a trivial
+// GLWE, or from `glwe_in` (the root of the CMUX tree below) for inputs wider than 9 bits.
+template <int K1, int BASE_LOG, int R>
+__global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void vertical_packing_kernel(const VpArgs A)
 {
     static_assert(R * K1 <= EP_GROUPS, "too many polynomials for 16 lane groups");
     __shared__ __attribute__((aligned(16))) double lds[EP_LDS_DOUBLES];
@@ -95,76 +104,37 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
 
     ep_load_table(tw, A.tw);
 
-    // ---- which ciphertext / instance does this group work on -------------------------------
-    uint64_t inst;            // PBS: ciphertext index; VP: global instance index
-    uint64_t input = 0;       // VP: which radix input (selects the GGSW list)
-    bool valid;
-    if (!VP) {
-        inst = (uint64_t)blockIdx.x * R + r_own;
-        valid = inst < A.count;
-        if (!valid) inst = A.count - 1;
-    } else {
-        input = blockIdx.x / A.wg_per_input;
-        uint32_t local = (blockIdx.x % A.wg_per_input) * R + r_own;
-        valid = local < A.inst_per_input;
-        if (!valid) local = A.inst_per_input - 1;
-        inst = input * A.inst_per_input + local;
-    }
+    // ---- which instance does this group work on: idle groups and the slots past the last instance repeat the last one ----------
+    const uint64_t input = blockIdx.x / A.wg_per_input;           // which radix input (selects the GGSW list)
+    uint32_t local = (blockIdx.x % A.wg_per_input) * R + r_own;
+    const bool valid = local < A.inst_per_input;
+    if (!valid) local = A.inst_per_input - 1;
+    const uint64_t inst = input * A.inst_per_input + local;       // global instance index
 
     // ---- accumulator init --------------------------------------------------------------------
     uint64_t lo[16], hi[16];
-    const uint64_t *lwe = nullptr;
-    if (!VP) {
-        lwe = A.lwe_in + inst * (uint64_t)(A.iters + 1);
-        const int bt = mod_switch_1024(lwe[A.iters] + A.body_shift);
-        const int t = (1024 - bt) & 1023;
+    if (A.glwe_in) {
+        const uint64_t *src = A.glwe_in + (inst * K1 + p_own) * FHE_N;
+#pragma unroll
+        for (int a = 0; a < 16; ++a) { lo[a] = src[16 * a + b]; hi[a] = src[256 + 16 * a + b]; }
+    } else {
+        const uint64_t set = A.lut_per_input ? input : 0;
+        const uint64_t *lut = A.luts + (set * A.inst_per_input + inst % A.inst_per_input) * A.lut_words;
 #pragma unroll
         for (int a = 0; a < 16; ++a) {
-            int j0 = 16 * a + b, j1 = j0 + 256;
-            int e0 = ((j0 - t) & 511) + t, e1 = ((j1 - t) & 511) + t;
-            uint64_t v0 = ((e0 >> 9) & 1) ? (uint64_t)0 - A.tv_const : A.tv_const;
-            uint64_t v1 = ((e1 >> 9) & 1) ? (uint64_t)0 - A.tv_const : A.tv_const;
-            lo[a] = (p_own == K1 - 1) ? v0 : 0;
-            hi[a] = (p_own == K1 - 1) ? v1 : 0;
-        }
-    } else {
-        if (A.glwe_in) {
-            const uint64_t *src = A.glwe_in + (inst * K1 + p_own) * FHE_N;
-#pragma unroll
-            for (int a = 0; a < 16; ++a) { lo[a] = src[16 * a + b]; hi[a] = src[256 + 16 * a + b]; }
-        } else {
-            uint64_t local = inst % A.inst_per_input;
-            uint64_t set = A.lut_per_input ? input : 0;
-            const uint64_t *lut = A.luts + (set * A.inst_per_input + local) * A.lut_words;
-#pragma unroll
-            for (int a = 0; a < 16; ++a) {
-                lo[a] = (p_own == K1 - 1) ? lut[16 * a + b] : 0;
-                hi[a] = (p_own == K1 - 1) ? lut[256 + 16 * a + b] : 0;
-            }
+            lo[a] = (p_own == K1 - 1) ? lut[16 * a + b] : 0;
+            hi[a] = (p_own == K1 - 1) ? lut[256 + 16 * a + b] : 0;
         }
     }
     __syncthreads();   // tables visible
-#ifdef EP_STAMPS
-    unsigned long long ph_cyc[EP_NPH];
-    for (int i = 0; i < EP_NPH; ++i) ph_cyc[i] = 0;
-    unsigned long long t_last = __builtin_readcyclecounter();
-#endif
 
-    const size_t ggsw_stride = (size_t)LEVELS * K1 * K1 * FHE_H;   // double2 elements per GGSW
+    const size_t ggsw_stride = (size_t)K1 * K1 * FHE_H;   // double2 elements per GGSW
 
     for (uint32_t it = 0; it < A.iters; ++it) {
-        int t;
-        const double2 *G;
-        if (!VP) {
-            t = mod_switch_1024(lwe[it]);
-            G = A.ggsw + (size_t)it * ggsw_stride;
-        } else {
-            t = (1024 - (1 << it)) & 1023;
-            G = A.ggsw + ((size_t)input * A.ggsw_per_input + it) * ggsw_stride;
-        }
+        const int t = (1024 - (1 << it)) & 1023;
+        const double2 *G = A.ggsw + ((size_t)input * A.ggsw_per_input + it) * ggsw_stride;
 
-        // ---- d = acc * X^t - acc, first decomposition level -----------------------------------
-        EP_STAMP(11);
+        // ---- d = acc * X^t - acc, decomposed ---------------------------------------------------
         uint64_t *stage = reinterpret_cast<uint64_t *>(tile);
 #pragma unroll
         for (int a = 0; a < 16; ++a) {
@@ -172,7 +142,6 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
             stage[256 + 16 * a + b] = hi[a];
         }
         wave_lds_sync();
-        uint32_t st_lo[16], st_hi[16];
         double xr[16], xi[16];
 #pragma unroll
         for (int a = 0; a < 16; ++a) {
@@ -182,13 +151,13 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
             if (((s0 + t) >> 9) & 1) v0 = (uint64_t)0 - v0;
             if (((s1 + t) >> 9) & 1) v1 = (uint64_t)0 - v1;
             v0 -= lo[a]; v1 -= hi[a];
-            xr[a] = (double)decompose_first<BASE_LOG, LEVELS>(v0, st_lo[a]);
-            xi[a] = (double)decompose_first<BASE_LOG, LEVELS>(v1, st_hi[a]);
-            // bound the number of rotated coefficients in flight (each is 2 VGPRs on top of acc, state and digits)
+            uint32_t st;
+            xr[a] = (double)decompose_first<BASE_LOG, 1>(v0, st);
+            xi[a] = (double)decompose_first<BASE_LOG, 1>(v1, st);
+            // bound the number of rotated coefficients in flight (each is 2 VGPRs on top of acc and digits)
             if ((a & (EP_ROT_CHUNK - 1)) == EP_ROT_CHUNK - 1) __builtin_amdgcn_sched_barrier(0);
         }
         wave_lds_sync();
-        EP_STAMP(0);
 
         double fr[R][K1], fi[R][K1];
 #pragma unroll
@@ -196,30 +165,23 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
 #pragma unroll
             for (int c = 0; c < K1; ++c) { fr[r][c] = 0.0; fi[r][c] = 0.0; }
 
-        // One decomposition level: transform the digit polynomials, exchange through LDS, multiply-accumulate.
-        // (A lambda called once for the first level and once inside the loop, so that xr/xi are provably dead
-        // during the multiply-accumulate of every level: no loop-carried copy survives the level.)
-        auto level_body = [&](const int l, const bool tiles_busy) {
-            if (tiles_busy) __syncthreads();
-            EP_STAMP(3);
-            // first half of the transform needs no tile; the barrier that frees the tiles (other threads
-            // may still be reading the previous level's digits) sits as late as possible
+        // Transform the digit polynomials, exchange through LDS, multiply-accumulate.  (A lambda although it is called once: written
+        // as a plain block the compiler emits other code for the whole kernel, and this code is the measured one.)
+        auto level_body = [&]() {
             {
                 double2 w0[8], w1[8];
                 fft_fwd_table(w0, w1, tw, b);
                 nega_fwd_head(xr, xi, w0, w1);
             }
-            EP_STAMP(2);
             nega_fwd_tail(xr, xi, tile, b);
-            EP_STAMP(4);
-            const double2 *Gl = G + (size_t)l * K1 * K1 * FHE_H + tid;
+            const double2 *Gl = G + tid;
             // Store a few transformed digits, start a GGSW row into the registers that just died, repeat: the
             // first EARLY rows are in flight across the remaining stores and the barrier (which therefore
             // must not drain vmcnt).
-            constexpr int PF0 = (K1 < EP_PREFETCH) ? K1 : EP_PREFETCH;
-            constexpr int EARLY = (EP_EARLY_LOAD < PF0) ? EP_EARLY_LOAD : PF0;
+            constexpr int PF = (K1 < EP_PREFETCH) ? K1 : EP_PREFETCH;
+            constexpr int EARLY = (EP_EARLY_LOAD < PF) ? EP_EARLY_LOAD : PF;
             constexpr int CHUNK = (K1 * 2 * 2 + 3) / 4;          // digits whose registers hold one row of K1 double2
-            double2 bq[PF0][K1];
+            double2 bq[PF][K1];
 #pragma unroll
             for (int e = 0; e < EARLY; ++e) {
 #pragma unroll
@@ -238,19 +200,14 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
                 *reinterpret_cast<double2 *>(tile + 2 * (b + 16 * k2)) = v;
             }
             __builtin_amdgcn_sched_barrier(0);
-            EP_STAMP(5);
             wg_barrier_lds_only();
-            EP_STAMP(6);
             // ---- multiply-accumulate role: thread tid owns Fourier point tid ------------------
-            // The K1 x K1 GGSW entries of this level stream from L2; without software pipelining every
-            // row costs one exposed round trip (measured: 71 of 341 ms).  xr/xi are dead here, so PF rows
-            // are kept in flight in their registers.
+            // The K1 x K1 GGSW entries stream from L2; without software pipelining every row costs one
+            // exposed round trip.  xr/xi are dead here, so PF rows are kept in flight in their registers.
             __builtin_amdgcn_s_setprio(EP_MAC_PRIO);
-            constexpr int PF = (K1 < EP_PREFETCH) ? K1 : EP_PREFETCH;
-            constexpr int P_FIRST = EARLY;
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int p = P_FIRST; p < PF; ++p)
+            for (int p = EARLY; p < PF; ++p)
 #pragma unroll
                 for (int c = 0; c < K1; ++c) bq[p][c] = Gl[(size_t)(p * K1 + c) * FHE_H];
             __builtin_amdgcn_sched_barrier(0);
@@ -278,22 +235,11 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
                 __builtin_amdgcn_sched_barrier(0);
             }
             __builtin_amdgcn_s_setprio(0);
-            EP_STAMP(7);
         };
-        level_body(LEVELS - 1, false);
-#pragma unroll 1
-        for (int l = LEVELS - 2; l >= 0; --l) {
-#pragma unroll
-            for (int a = 0; a < 16; ++a) {
-                xr[a] = (double)decompose_next<BASE_LOG>(st_lo[a]);
-                xi[a] = (double)decompose_next<BASE_LOG>(st_hi[a]);
-            }
-            EP_STAMP(1);
-            level_body(l, true);
-        }
+        level_body();
 
         // ---- products back to the owning groups, inverse transform, accumulate ----------------
-        __syncthreads();             // every thread is done reading the last level's digits from the tiles
+        __syncthreads();             // every thread is done reading the digits from the tiles
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -308,20 +254,13 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
             xr[k2] = v.x; xi[k2] = v.y;
         }
         wave_lds_sync();
-        EP_STAMP(8);
         nega_inv(xr, xi, tw, tile, b);
-        EP_STAMP(9);
 #pragma unroll
         for (int a = 0; a < 16; ++a) {
             lo[a] += torus_from_double(xr[a]);
             hi[a] += torus_from_double(xi[a]);
         }
-        EP_STAMP(10);
     }
-#ifdef EP_STAMPS
-    if (A.stamps && (tid & 63) == 0)
-        for (int i = 0; i < EP_NPH; ++i) A.stamps[((size_t)blockIdx.x * 4 + (tid >> 6)) * EP_NPH + i] = ph_cyc[i];
-#endif
 
     // ---- sample extract coefficient 0 ---------------------------------------------
     if (owner && valid) {
@@ -336,7 +275,7 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
                 om[FHE_N - j1] = (uint64_t)0 - hi[a];
             }
         } else if (b == 0) {
-            o[big] = lo[0] + (VP ? 0 : A.post_add);
+            o[big] = lo[0];
         }
     }
 }
@@ -350,7 +289,7 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void extprod_rotate_kerne
 // one decomposition level.  Not on the AES path (8- and 9-bit inputs only); it completes many_wopbs_without_padding.
 struct CmuxArgs {
     const double2 *ggsw;        // Fourier GGSWs [n_inputs][bits][K1][K1][256]
-    const double2 *tw;          // the transform's table (see ExtProdArgs)
+    const double2 *tw;          // [FHE_TW_ENTRIES] the transform's one table (fft_dev.h)
     const uint64_t *luts;       // leaf level: [n_sets][inst_per_input][lut_words]; else null
     const uint64_t *in;         // inner levels: GLWE [instances][2 * nodes_out][K1][512]
     uint64_t *out;              // GLWE [instances][nodes_out][K1][512]
