@@ -230,6 +230,46 @@ int fheaes_aes_ctr_bits(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t ke
  * no context, no GPU; fheaes_aes_encrypt_bits runs 16 n_blocks in every round). */
 int fheaes_aes_public_plan(const uint64_t *blocks_hi_lo, uint64_t n_blocks, uint32_t key_bits, uint64_t *unique_bytes_per_round);
 
+/* ---- many AES keys ---------------------------------------------------------------- */
+/* One FHE key pair, many AES keys (producers, sessions, rotated keys), each reaching the server encrypted under that FHE key: short
+ * messages under many keys.  The reference has no counterpart (one key, main.rs).  K1-K5 know nothing about AES keys and a WoPBS is a
+ * deterministic function of its input words, so the calls below are the schedules above with the keys as one more batch axis: every
+ * one gives, WORD FOR WORD, what the single-key calls give key by key, in launches that are as full as the whole batch makes them (a
+ * key expansion step is one 32 n_keys-bit WoPBS instead of n_keys of 32 bits, 6.4 ms each whatever they carry).
+ *
+ * `n_keys` sets of round keys are [n_keys][Nr+1][16][8][kN+1]: slice i is a valid argument of every single-key entry point.  One key
+ * size per call.  n_keys = 0 or n_keys > FHEAES_MAX_KEYS is FHEAES_ERR_INVALID (the bound: a key index has 16 bits in the head word of a
+ * pool entry of the public calls).  `key_of_block` is a HOST array of n_blocks uint32 whatever `memspace` says, as fheaes_add_scalar's
+ * counters; an entry >= n_keys is FHEAES_ERR_INVALID; a key that no block names is legal.  n_blocks = 0 is FHEAES_OK; FHEAES_DEVICE calls
+ * only enqueue; the noise guard sees the counts of the single-key schedules. */
+#define FHEAES_MAX_KEYS 65536
+/* keys [n_keys][key_bits/8][8][kN+1] -> round_keys [n_keys][Nr+1][16][8][kN+1]: the rule of fheaes_aes_key_expansion_bits with every step
+ * ONE WoPBS over the 4 n_keys bytes of word i of all keys (40 / 46 / 52 identity refreshes, 10 / 8 / 13 SubWords); slice i is word for
+ * word fheaes_aes_key_expansion_bits of key i. */
+int fheaes_aes_key_expansion_batch(fheaes_ctx *ctx, const uint64_t *keys, uint32_t key_bits, uint64_t n_keys, uint64_t *round_keys, int memspace);
+/* The 16 (Nr - 1) n_keys middle bytes of all keys through one {9x, 11x, 13x, 14x} WoPBS, one InvMixColumns gather and one identity WoPBS;
+ * slice i is word for word fheaes_aes_decryption_round_keys_bits of slice i.  Overlapping buffers are FHEAES_ERR_INVALID. */
+int fheaes_aes_decryption_round_keys_batch(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys,
+                                           uint64_t *dec_round_keys, int memspace);
+/* fheaes_aes_encrypt_bits / _decrypt_bits / _decrypt_equivalent_bits with a key per block: state block b is processed in place under
+ * round_keys[key_of_block[b]] (dec_round_keys for the equivalent inverse cipher), word for word what the single-key call writes for that
+ * block under that key; every round is one WoPBS over all 16 n_blocks bytes. */
+int fheaes_aes_encrypt_keyed(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
+                             uint64_t *state, uint64_t n_blocks, int memspace);
+int fheaes_aes_decrypt_keyed(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
+                             uint64_t *state, uint64_t n_blocks, int memspace);
+int fheaes_aes_decrypt_equivalent_keyed(fheaes_ctx *ctx, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t n_keys,
+                                        const uint32_t *key_of_block, uint64_t *state, uint64_t n_blocks, int memspace);
+/* fheaes_aes_encrypt_public_bits with a key per block; data_hi_lo (n_blocks pairs, may be NULL) is folded into the last layer as in
+ * fheaes_aes_ctr_bits, so several CTR streams under several keys are one call (the caller builds the counter blocks).  The sharing rule
+ * gains the key: the id of a round-1 input is (key, position, byte), so equal blocks under different keys are different inputs and are
+ * never shared, and equal inputs under the same key still are. */
+int fheaes_aes_public_keyed(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
+                            const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace);
+/* fheaes_aes_public_plan for the call above (host logic only, no context, no GPU); with every key 0 it gives fheaes_aes_public_plan's counts. */
+int fheaes_aes_public_plan_keyed(const uint64_t *blocks_hi_lo, const uint32_t *key_of_block, uint64_t n_blocks, uint64_t n_keys,
+                                 uint32_t key_bits, uint64_t *unique_bytes_per_round);
+
 /* ---- packed ciphertexts --------------------------------------------------------- */
 /* Every entry point above hands its result out one LWE ciphertext per bit: kN + 1 words (16,392 bytes at PARAM_OPT) for one bit.  A
  * packing key switch puts N = 512 bits into the N coefficients of ONE GLWE ciphertext, (k+1)N words (20,480 bytes) for 512 bits:

@@ -92,6 +92,20 @@ extern "C" {
     pub fn fheaes_aes_ctr_bits(ctx: *mut fheaes_ctx, round_keys: *const u64, key_bits: u32, iv_hi_lo: *const u64, first_block: u64,
                                data_hi_lo: *const u64, n_blocks: u64, state_out: *mut u64, memspace: c_int) -> c_int;
     pub fn fheaes_aes_public_plan(blocks_hi_lo: *const u64, n_blocks: u64, key_bits: u32, unique_bytes_per_round: *mut u64) -> c_int;
+    // many AES keys under one FHE key: round keys [n_keys][Nr+1][16][8][kN+1], key_of_block a host array; word for word the single-key calls
+    pub fn fheaes_aes_key_expansion_batch(ctx: *mut fheaes_ctx, keys: *const u64, key_bits: u32, n_keys: u64, round_keys: *mut u64, memspace: c_int) -> c_int;
+    pub fn fheaes_aes_decryption_round_keys_batch(ctx: *mut fheaes_ctx, round_keys: *const u64, key_bits: u32, n_keys: u64, dec_round_keys: *mut u64,
+                                                  memspace: c_int) -> c_int;
+    pub fn fheaes_aes_encrypt_keyed(ctx: *mut fheaes_ctx, round_keys: *const u64, key_bits: u32, n_keys: u64, key_of_block: *const u32, state: *mut u64,
+                                    n_blocks: u64, memspace: c_int) -> c_int;
+    pub fn fheaes_aes_decrypt_keyed(ctx: *mut fheaes_ctx, round_keys: *const u64, key_bits: u32, n_keys: u64, key_of_block: *const u32, state: *mut u64,
+                                    n_blocks: u64, memspace: c_int) -> c_int;
+    pub fn fheaes_aes_decrypt_equivalent_keyed(ctx: *mut fheaes_ctx, dec_round_keys: *const u64, key_bits: u32, n_keys: u64, key_of_block: *const u32,
+                                               state: *mut u64, n_blocks: u64, memspace: c_int) -> c_int;
+    pub fn fheaes_aes_public_keyed(ctx: *mut fheaes_ctx, round_keys: *const u64, key_bits: u32, n_keys: u64, key_of_block: *const u32,
+                                   blocks_hi_lo: *const u64, data_hi_lo: *const u64, n_blocks: u64, state_out: *mut u64, memspace: c_int) -> c_int;
+    pub fn fheaes_aes_public_plan_keyed(blocks_hi_lo: *const u64, key_of_block: *const u32, n_blocks: u64, n_keys: u64, key_bits: u32,
+                                        unique_bytes_per_round: *mut u64) -> c_int;
     // packed ciphertexts: N = 512 bits per GLWE through key block k of the PFPKSK the context holds (no new key), and back
     pub fn fheaes_packed_words(ctx: *const fheaes_ctx, m: u64) -> usize;
     pub fn fheaes_pack_bits(ctx: *mut fheaes_ctx, lwe_in: *const u64, m: u64, glwe_out: *mut u64, memspace: c_int) -> c_int;

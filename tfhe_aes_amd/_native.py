@@ -21,6 +21,7 @@ STAGES = ("keyswitch", "blind_rotate", "pfpks", "ggsw_fft", "vertical_packing", 
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _dp = ctypes.POINTER(ctypes.c_double)
+_u32p = ctypes.POINTER(ctypes.c_uint32)
 _ctx = ctypes.c_void_p
 _c = ctypes
 
@@ -64,6 +65,13 @@ SIGNATURES = {
     "fheaes_aes_encrypt_public_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_ctr_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _c.c_uint64, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_public_plan": (_c.c_int, [_u64p, _c.c_uint64, _c.c_uint32, _u64p]),
+    "fheaes_aes_key_expansion_batch": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_decryption_round_keys_batch": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_encrypt_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _c.c_void_p, _c.c_uint64, _c.c_int]),
+    "fheaes_aes_decrypt_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _c.c_void_p, _c.c_uint64, _c.c_int]),
+    "fheaes_aes_decrypt_equivalent_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _c.c_void_p, _c.c_uint64, _c.c_int]),
+    "fheaes_aes_public_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _u64p, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_public_plan_keyed": (_c.c_int, [_u64p, _u32p, _c.c_uint64, _c.c_uint64, _c.c_uint32, _u64p]),
     "fheaes_packed_words": (_c.c_size_t, [_ctx, _c.c_uint64]),
     "fheaes_pack_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_unpack_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
@@ -310,6 +318,37 @@ class Engine:
                                                   dat.ctypes.data_as(_u64p) if dat is not None else None, n_blocks, _ptr(state_out)[0],
                                                   self._space(round_keys, state_out)))
 
+    # many AES keys: round keys [n_keys][Nr+1][16][8][kN+1]; key_of_block (one key index per block) travels as a host uint32 array
+    def aes_key_expansion_batch(self, keys, key_bits: int, n_keys: int, round_keys):
+        self._check(self._lib.fheaes_aes_key_expansion_batch(self._h, _ptr(keys)[0], key_bits, n_keys, _ptr(round_keys)[0], self._space(keys, round_keys)))
+
+    def aes_decryption_round_keys_batch(self, round_keys, key_bits: int, n_keys: int, dec_round_keys):
+        self._check(self._lib.fheaes_aes_decryption_round_keys_batch(self._h, _ptr(round_keys)[0], key_bits, n_keys, _ptr(dec_round_keys)[0],
+                                                                     self._space(round_keys, dec_round_keys)))
+
+    def _keyed(self, fn, round_keys, key_bits: int, n_keys: int, key_of_block, state, n_blocks: int):
+        kob = key_indices(key_of_block, n_blocks)
+        self._check(fn(self._h, _ptr(round_keys)[0], key_bits, n_keys, kob.ctypes.data_as(_u32p), _ptr(state)[0], n_blocks, self._space(round_keys, state)))
+
+    def aes_encrypt_keyed(self, round_keys, key_bits: int, n_keys: int, key_of_block, state, n_blocks: int):
+        self._keyed(self._lib.fheaes_aes_encrypt_keyed, round_keys, key_bits, n_keys, key_of_block, state, n_blocks)
+
+    def aes_decrypt_keyed(self, round_keys, key_bits: int, n_keys: int, key_of_block, state, n_blocks: int):
+        self._keyed(self._lib.fheaes_aes_decrypt_keyed, round_keys, key_bits, n_keys, key_of_block, state, n_blocks)
+
+    def aes_decrypt_equivalent_keyed(self, dec_round_keys, key_bits: int, n_keys: int, key_of_block, state, n_blocks: int):
+        self._keyed(self._lib.fheaes_aes_decrypt_equivalent_keyed, dec_round_keys, key_bits, n_keys, key_of_block, state, n_blocks)
+
+    def aes_public_keyed(self, round_keys, key_bits: int, n_keys: int, key_of_block, blocks, data, state_out):
+        cnt = u128_pairs(blocks)
+        kob = key_indices(key_of_block, len(cnt))
+        dat = u128_pairs(data) if data is not None else None
+        if dat is not None and len(dat) != len(cnt):
+            raise ValueError("one data block per block expected")
+        self._check(self._lib.fheaes_aes_public_keyed(self._h, _ptr(round_keys)[0], key_bits, n_keys, kob.ctypes.data_as(_u32p), cnt.ctypes.data_as(_u64p),
+                                                      dat.ctypes.data_as(_u64p) if dat is not None else None, len(cnt), _ptr(state_out)[0],
+                                                      self._space(round_keys, state_out)))
+
     # -- packed ciphertexts: N bits per GLWE (include/fheaes.h) -------------------
     def packed_words(self, m: int) -> int:
         return self._lib.fheaes_packed_words(self._h, m)
@@ -391,6 +430,30 @@ def u128_pairs(values) -> np.ndarray:
             raise ValueError("a block is a 128-bit value")
         out[i, 0], out[i, 1] = v >> 64, v & (2 ** 64 - 1)
     return out
+
+
+def key_indices(key_of_block, n_blocks: int) -> np.ndarray:
+    """one AES key index per block -> the host uint32 array of the C ABI (at least one word, so that its pointer is never NULL)"""
+    idx = [int(k) for k in key_of_block]
+    if len(idx) != n_blocks:
+        raise ValueError("one key index per block expected: %d for %d blocks" % (len(idx), n_blocks))
+    if any(not 0 <= k < 1 << 32 for k in idx):
+        raise ValueError("a key index is a uint32")
+    out = np.zeros(max(n_blocks, 1), dtype=np.uint32)
+    out[:n_blocks] = idx
+    return out
+
+
+def aes_public_plan_keyed(blocks, key_of_block, n_keys: int, key_bits: int = 128) -> list[int]:
+    """aes_public_plan for aes_encrypt_public_keyed / aes_ctr_streams: the id of a round-1 input is (key, position, byte), so equal blocks
+    under different keys share nothing (fheaes_aes_public_plan_keyed: host only, no GPU)"""
+    cnt = u128_pairs(blocks)
+    kob = key_indices(key_of_block, len(cnt))
+    out = np.zeros(14, dtype=np.uint64)
+    rc = load_library().fheaes_aes_public_plan_keyed(cnt.ctypes.data_as(_u64p), kob.ctypes.data_as(_u32p), len(cnt), n_keys, key_bits, out.ctypes.data_as(_u64p))
+    if rc != 0:
+        raise FheAesError(rc, "fheaes_aes_public_plan_keyed: key_bits must be 128, 192 or 256, n_keys in 1..65536 and every key index below n_keys")
+    return [int(x) for x in out[:{128: 10, 192: 12, 256: 14}[key_bits]]]
 
 
 def aes_public_plan(blocks, key_bits: int = 128) -> list[int]:

@@ -121,6 +121,17 @@ def ctr_keystream(key, iv: int, first_block: int, n_blocks: int) -> list[int]:
     return [aes_encrypt_block(key, (iv + first_block + i) % (1 << 128)) for i in range(n_blocks)]
 
 
+def ctr_streams(keys, streams) -> list[int]:
+    """several SP 800-38A CTR streams under several keys, as Server.aes_ctr_streams takes them: `streams` is a list of
+    (key_index, iv, first_block, n_blocks, data_or_None), data a list of n_blocks u128; returns the streams' blocks concatenated in order,
+    keystream ^ data (data None: the keystream)"""
+    out = []
+    for key_index, iv, first_block, n_blocks, data in streams:
+        ks = ctr_keystream(keys[key_index], iv, first_block, n_blocks)
+        out += ks if data is None else [k ^ d for k, d in zip(ks, data)]
+    return out
+
+
 def aes_decrypt_block(key, block: int) -> int:
     """FIPS-197 Fig. 12, the inverse cipher, in the order Server::aes_decrypt takes it (AddRoundKey before InvMixColumns)"""
     rk = expand_key(key)

@@ -18,7 +18,7 @@ static int check_key_bits(fheaes_ctx *c, uint32_t key_bits)
     return FHEAES_OK;
 }
 
-static int aes_encrypt_dev(fheaes_ctx *c, const uint64_t *rk, uint64_t *state, uint64_t n_blocks, int nr)
+static int aes_encrypt_dev(fheaes_ctx *c, const KeySets &rk, uint64_t *state, uint64_t n_blocks, int nr)
 {
     const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
     TRY(ensure(c, c->ws_vp, nbytes * 3 * bw * 8));
@@ -27,26 +27,27 @@ static int aes_encrypt_dev(fheaes_ctx *c, const uint64_t *rk, uint64_t *state, u
     TRY(launch_add_bcast(c, state, rk, sw, n_blocks));                                   // server.rs:42
     for (int round = 1; round < nr; ++round) {                                           // server.rs:44-57
         TRY(many_sbox_dev(c, state, nbytes, LUTSET_ENC_ROUND, vp));
-        TRY(launch_gather(c, vp, 3, rk + (uint64_t)round * sw, state, n_blocks, t_round));
+        TRY(launch_gather(c, vp, 3, rk.round(round, sw), state, n_blocks, t_round));
     }
     TRY(many_sbox_dev(c, state, nbytes, LUTSET_SBOX, vp));                               // server.rs:59-63
-    TRY(launch_gather(c, vp, 1, rk + (uint64_t)nr * sw, state, n_blocks, t_shift));
+    TRY(launch_gather(c, vp, 1, rk.round(nr, sw), state, n_blocks, t_shift));
     return FHEAES_OK;
 }
 
-static int aes_decrypt_dev(fheaes_ctx *c, const uint64_t *rk, uint64_t *state, uint64_t n_blocks, int nr)
+static int aes_decrypt_dev(fheaes_ctx *c, const KeySets &rk, uint64_t *state, uint64_t n_blocks, int nr)
 {
     const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
     TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
     uint64_t *vp = (uint64_t *)c->ws_vp.p;
     const GatherTable t_inv = table_shift_rows(true), t_mix = table_dec_mix();
-    TRY(launch_add_bcast(c, state, rk + (uint64_t)nr * sw, sw, n_blocks));               // server.rs:70
+    const KeySets no_key{nullptr, nullptr, 0};
+    TRY(launch_add_bcast(c, state, rk.round(nr, sw), sw, n_blocks));                     // server.rs:70
     for (int round = nr; round >= 2; --round) {                                          // server.rs:72-96
         // inv_shift_rows commutes with the bytewise S-Box: INV_SBOX first, then the permutation + round key
         TRY(many_sbox_dev(c, state, nbytes, LUTSET_INV_SBOX, vp));
-        TRY(launch_gather(c, vp, 1, rk + (uint64_t)(round - 1) * sw, state, n_blocks, t_inv));
+        TRY(launch_gather(c, vp, 1, rk.round(round - 1, sw), state, n_blocks, t_inv));
         TRY(many_sbox_dev(c, state, nbytes, LUTSET_DEC_MUL, vp));
-        TRY(launch_gather(c, vp, 4, nullptr, state, n_blocks, t_mix));
+        TRY(launch_gather(c, vp, 4, no_key, state, n_blocks, t_mix));
     }
     TRY(many_sbox_dev(c, state, nbytes, LUTSET_INV_SBOX, vp));                           // server.rs:98-104
     TRY(launch_gather(c, vp, 1, rk, state, n_blocks, t_inv));
@@ -57,68 +58,80 @@ static int aes_decrypt_dev(fheaes_ctx *c, const uint64_t *rk, uint64_t *state, u
 // per byte with the composed tables {9, 11, 13, 14} * InvS[x] (LUTSET_DEC_EQ_ROUND), summed through the InvShiftRows-folded gather with
 // dw[r] = IMC(w[r]) as the round key: Nr WoPBS per block like aes_encrypt_dev, against the 2 Nr - 1 of aes_decrypt_dev (the reference's own
 // schedule, server.rs:67-105, which says at :86-89 that it almost doubles the time of encryption).  dw: fheaes_aes_decryption_round_keys.
-static int aes_decrypt_eq_dev(fheaes_ctx *c, const uint64_t *dw, uint64_t *state, uint64_t n_blocks, int nr)
+static int aes_decrypt_eq_dev(fheaes_ctx *c, const KeySets &dw, uint64_t *state, uint64_t n_blocks, int nr)
 {
     const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
     TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
     uint64_t *vp = (uint64_t *)c->ws_vp.p;
     const GatherTable t_round = table_dec_eq_round(), t_inv = table_shift_rows(true);
-    TRY(launch_add_bcast(c, state, dw + (uint64_t)nr * sw, sw, n_blocks));
+    TRY(launch_add_bcast(c, state, dw.round(nr, sw), sw, n_blocks));
     for (int round = nr - 1; round >= 1; --round) {
         TRY(many_sbox_dev(c, state, nbytes, LUTSET_DEC_EQ_ROUND, vp));
-        TRY(launch_gather(c, vp, 4, dw + (uint64_t)round * sw, state, n_blocks, t_round));     // 4 WoPBS outputs + dw[round] = 5
+        TRY(launch_gather(c, vp, 4, dw.round(round, sw), state, n_blocks, t_round));     // 4 WoPBS outputs + dw[round] = 5
     }
     TRY(many_sbox_dev(c, state, nbytes, LUTSET_INV_SBOX, vp));
     TRY(launch_gather(c, vp, 1, dw, state, n_blocks, t_inv));
     return FHEAES_OK;
 }
 
-typedef int (*AesDevFn)(fheaes_ctx *, const uint64_t *, uint64_t *, uint64_t, int);
+typedef int (*AesDevFn)(fheaes_ctx *, const KeySets &, uint64_t *, uint64_t, int);
 
-// dw[0] = w[0], dw[Nr] = w[Nr], dw[r] = InvMixColumns(w[r]) for r = 1..Nr-1: the 16 (Nr - 1) bytes of w[1..Nr-1] in one batch -- the 4-LUT
-// {9x, 11x, 13x, 14x} WoPBS, the InvMixColumns gather (4 terms, no key) and an identity WoPBS that brings every byte back to nominal
-// noise, as the key expansion's refresh does (server.rs:150): a round of the equivalent inverse cipher then sums 4 WoPBS outputs + 1 key
-static int dec_round_keys_dev(fheaes_ctx *c, const uint64_t *w, uint64_t *dw, int nr)
+// dw[0] = w[0], dw[Nr] = w[Nr], dw[r] = InvMixColumns(w[r]) for r = 1..Nr-1, for n_keys sets of round keys [n_keys][Nr+1][16]: the
+// 16 (Nr - 1) n_keys middle bytes in one batch -- the 4-LUT {9x, 11x, 13x, 14x} WoPBS, the InvMixColumns gather (4 terms, no key) and an
+// identity WoPBS that brings every byte back to nominal noise, as the key expansion's refresh does (server.rs:150): a round of the
+// equivalent inverse cipher then sums 4 WoPBS outputs + 1 key.  A WoPBS reads and writes contiguous bytes: with several keys the middle
+// bytes are gathered from their stride first and the refreshed ones placed back; one key's already are where they belong.
+static int dec_round_keys_dev(fheaes_ctx *c, const uint64_t *w, uint64_t *dw, int nr, uint64_t n_keys)
 {
-    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = (uint64_t)(nr - 1) * 16;
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, ks = (uint64_t)(nr + 1) * sw, mid = (uint64_t)(nr - 1) * 16, nbytes = mid * n_keys;
+    const bool strided = n_keys > 1;
     TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
     TRY(ensure(c, c->ws_tmp_a, nbytes * bw * 8));
-    uint64_t *vp = (uint64_t *)c->ws_vp.p, *mix = (uint64_t *)c->ws_tmp_a.p;
-    HIP_TRY(c, hipMemcpyAsync(dw, w, sw * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dw + (uint64_t)nr * sw, w + (uint64_t)nr * sw, sw * 8, hipMemcpyDeviceToDevice, c->stream));
-    TRY(many_sbox_dev(c, w + sw, nbytes, LUTSET_DEC_MUL, vp));
-    TRY(launch_gather(c, vp, 4, nullptr, mix, (uint64_t)(nr - 1), table_dec_mix()));
-    TRY(many_sbox_dev(c, mix, nbytes, LUTSET_IDENTITY, dw + sw));
+    if (strided) TRY(ensure(c, c->ws_tmp_b, nbytes * bw * 8));
+    uint64_t *vp = (uint64_t *)c->ws_vp.p, *mix = (uint64_t *)c->ws_tmp_a.p, *flat = (uint64_t *)c->ws_tmp_b.p;
+    TRY(launch_key_rows(c, dw, ks, w, ks, 0, nullptr, 0, 0, 16, n_keys, 1));
+    TRY(launch_key_rows(c, dw + (uint64_t)nr * sw, ks, w + (uint64_t)nr * sw, ks, 0, nullptr, 0, 0, 16, n_keys, 1));
+    if (strided) TRY(launch_key_rows(c, flat, mid * bw, w + sw, ks, 0, nullptr, 0, 0, (uint32_t)mid, n_keys, 1));
+    TRY(many_sbox_dev(c, strided ? flat : w + sw, nbytes, LUTSET_DEC_MUL, vp));
+    TRY(launch_gather(c, vp, 4, KeySets{nullptr, nullptr, 0}, mix, nbytes / 16, table_dec_mix()));
+    TRY(many_sbox_dev(c, mix, nbytes, LUTSET_IDENTITY, strided ? flat : dw + sw));
+    if (strided) TRY(launch_key_rows(c, dw + sw, ks, flat, mid * bw, 0, nullptr, 0, 0, (uint32_t)mid, n_keys, 1));
     return FHEAES_OK;
 }
 
 // FIPS-197 section 5.2 for Nk = 4 / 6 / 8 key words under the reference's rule (server.rs:107-155 is the Nk = 4 case): every new word is
-// refreshed by an identity WoPBS; RotWord + SubWord + Rcon when i % Nk == 0, SubWord alone when Nk > 6 and i % Nk == 4; 4 (Nr + 1) words
-static int key_expansion_dev(fheaes_ctx *c, const uint64_t *key, uint64_t *w, int nr)
+// refreshed by an identity WoPBS; RotWord + SubWord + Rcon when i % Nk == 0, SubWord alone when Nk > 6 and i % Nk == 4; 4 (Nr + 1) words.
+// n_keys keys at once, key [n_keys][4 Nk][8][kN+1] -> w [n_keys][Nr+1][16][8][kN+1]: word i of key j lives at j * (Nr+1) * 16 bytes, and every
+// step works on word i of ALL keys -- one launch per word operation and one WoPBS over 4 n_keys bytes, whatever n_keys is.  The WoPBS
+// work on contiguous words [n_keys][4]: ta (sums, RotWord), tb (SubWord results), tc (refreshed words, placed at their stride after;
+// one key's word is written where it belongs).
+static int key_expansion_dev(fheaes_ctx *c, const uint64_t *key, uint64_t *w, int nr, uint64_t n_keys)
 {
     static const uint8_t RCON[10] = {0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1B, 0x36};
-    const uint64_t bw = 8ull * c->big1, ww = 4 * bw;
-    TRY(ensure(c, c->ws_tmp_a, ww * 8));
-    TRY(ensure(c, c->ws_tmp_b, ww * 8));
-    uint64_t *ta = (uint64_t *)c->ws_tmp_a.p, *tb = (uint64_t *)c->ws_tmp_b.p;
+    const uint64_t bw = 8ull * c->big1, ww = 4 * bw, ks = (uint64_t)(nr + 1) * 16 * bw;
     const int nk = nr - 6;                                                                          // FIPS-197 Fig. 4: Nr = Nk + 6
-    HIP_TRY(c, hipMemcpyAsync(w, key, (uint64_t)nk * ww * 8, hipMemcpyDeviceToDevice, c->stream));  // server.rs:122-128
+    const bool strided = n_keys > 1;
+    TRY(ensure(c, c->ws_tmp_a, n_keys * ww * 8));
+    TRY(ensure(c, c->ws_tmp_b, n_keys * ww * 8));
+    if (strided) TRY(ensure(c, c->ws_tmp_c, n_keys * ww * 8));
+    uint64_t *ta = (uint64_t *)c->ws_tmp_a.p, *tb = (uint64_t *)c->ws_tmp_b.p, *tc = (uint64_t *)c->ws_tmp_c.p;
+    TRY(launch_key_rows(c, w, ks, key, (uint64_t)nk * ww, 0, nullptr, 0, 0, 4u * nk, n_keys, 1));      // server.rs:122-128
     for (int i = nk; i < 4 * (nr + 1); ++i) {                                                       // server.rs:131-155
         const uint64_t *prev = w + (uint64_t)(i - 1) * ww, *back = w + (uint64_t)(i - nk) * ww;
         if (i % nk == 0) {
-            for (int j = 0; j < 4; ++j)                                                             // fhe_rot_word
-                HIP_TRY(c, hipMemcpyAsync(ta + (uint64_t)j * bw, prev + (uint64_t)((j + 1) & 3) * bw, bw * 8, hipMemcpyDeviceToDevice, c->stream));
-            TRY(many_sbox_dev(c, ta, 4, LUTSET_SBOX, tb));                                          // fhe_sub_word
-            hipLaunchKernelGGL(add_const_byte_kernel, dim3(1), dim3(64), 0, c->stream, tb, c->big1, (uint32_t)RCON[i / nk - 1]);
-            HIP_TRY(c, hipGetLastError());
-            TRY(launch_add2(c, ta, tb, back, ww));
+            TRY(launch_key_rows(c, ta, ww, prev, ks, 1, nullptr, 0, 0, 4, n_keys, 1));              // fhe_rot_word
+            TRY(many_sbox_dev(c, ta, 4 * n_keys, LUTSET_SBOX, tb));                                 // fhe_sub_word
+            TRY(launch_key_rows(c, ta, ww, tb, ww, 0, back, ks, RCON[i / nk - 1], 4, n_keys, 2));   // + Rcon (trivial) + w[i - Nk]
         } else if (nk > 6 && i % nk == 4) {                                                         // FIPS-197 5.2: SubWord alone (Nk = 8)
-            TRY(many_sbox_dev(c, prev, 4, LUTSET_SBOX, tb));
-            TRY(launch_add2(c, ta, tb, back, ww));
+            if (strided) TRY(launch_key_rows(c, ta, ww, prev, ks, 0, nullptr, 0, 0, 4, n_keys, 1));
+            TRY(many_sbox_dev(c, strided ? ta : prev, 4 * n_keys, LUTSET_SBOX, tb));
+            TRY(launch_key_rows(c, ta, ww, tb, ww, 0, back, ks, 0, 4, n_keys, 2));
         } else {
-            TRY(launch_add2(c, ta, prev, back, ww));
+            TRY(launch_key_rows(c, ta, ww, prev, ks, 0, back, ks, 0, 4, n_keys, 2));
         }
-        TRY(many_sbox_dev(c, ta, 4, LUTSET_IDENTITY, w + (uint64_t)i * ww));                        // refresh, server.rs:150
+        uint64_t *fresh = w + (uint64_t)i * ww;
+        TRY(many_sbox_dev(c, ta, 4 * n_keys, LUTSET_IDENTITY, strided ? tc : fresh));               // refresh, server.rs:150
+        if (strided) TRY(launch_key_rows(c, fresh, ks, tc, ww, 0, nullptr, 0, 0, 4, n_keys, 1));
     }
     return FHEAES_OK;
 }
@@ -177,9 +190,10 @@ static int add_scalar_dev(fheaes_ctx *c, uint64_t *state, uint64_t n_blocks, con
 // aes_encrypt on PUBLIC blocks (trivial ciphertexts) with every distinct S-Box input of the batch evaluated once.  A WoPBS is a
 // deterministic function of its input words, so two state bytes with word-equal inputs need one evaluation.  The rule that finds them
 // is exact and runs on the host before anything is enqueued: every S-Box input gets an id, round by round,
-//   round 1:   id(b, p) = (p, byte p of block b)                      -- the input is rk[0][p] + trivial(byte)
+//   round 1:   id(b, p) = (key of b, p, byte p of block b)            -- the input is rk[key][0][p] + trivial(byte)
 //   round r+1: id(b, p) = (p, id_r(b, s_0), .., id_r(b, s_3))         -- s_j: the four sources of table_enc_round() for position p
-// and equal tuples are one id: sums of word-equal ciphertexts plus the same round-key byte are word-equal.  The ids of a round are its
+// and equal tuples are one id: sums of word-equal ciphertexts plus the same round-key byte are word-equal (the sources of an id all belong
+// to one block, so an id has one AES key: equal blocks under different keys are never shared).  The ids of a round are its
 // POOL; round r runs one WoPBS over pool r and an indexed gather (kern_linear.h) into pool r+1, the last gather writes [block][16].
 struct PublicPlan {
     struct Layer { size_t head, term; uint32_t n, terms; };     // offsets into `words`; n outputs of `terms` terms each
@@ -203,22 +217,23 @@ struct PublicKey5Hash {
     }
 };
 
-// blocks / data: n_blocks (hi, lo) pairs, data may be null
-static void public_plan(const uint64_t *blocks, const uint64_t *data, uint64_t n_blocks, int nr, PublicPlan &pl)
+// blocks / data: n_blocks (hi, lo) pairs, data may be null; key_of_block: n_blocks key indices below PUBLIC_MAX_KEYS, or null (all 0)
+static void public_plan(const uint64_t *blocks, const uint64_t *data, const uint32_t *key_of_block, uint64_t n_blocks, int nr, PublicPlan &pl)
 {
+    auto key_of = [&](uint64_t b) { return key_of_block ? key_of_block[b] : 0u; };
     const GatherTable t_round = table_enc_round(), t_shift = table_shift_rows(false);
     const uint64_t nbytes = 16 * n_blocks;
     std::vector<uint32_t> id(nbytes), next(nbytes);
     pl.layers.clear(); pl.words.clear();
     pl.layers.reserve((size_t)nr + 1);
     {   // round 1
-        std::vector<int64_t> seen(16 * 256, -1);
+        std::unordered_map<uint32_t, uint32_t> seen;              // the head word IS (key, p, byte)
         std::vector<uint32_t> head;
         for (uint64_t b = 0; b < n_blocks; ++b) for (int p = 0; p < 16; ++p) {
-            const uint32_t v = u128_byte(blocks + 2 * b, p);
-            int64_t &s = seen[(size_t)p * 256 + v];
-            if (s < 0) { s = (int64_t)head.size(); head.push_back(PUBLIC_HEAD(p, v)); }
-            id[16 * b + p] = (uint32_t)s;
+            const uint32_t h = PUBLIC_HEAD(p, u128_byte(blocks + 2 * b, p), key_of(b));
+            auto ins = seen.emplace(h, (uint32_t)head.size());
+            if (ins.second) head.push_back(h);
+            id[16 * b + p] = ins.first->second;
         }
         pl.layers.push_back({0, head.size(), (uint32_t)head.size(), 0});
         pl.words = std::move(head);
@@ -232,7 +247,7 @@ static void public_plan(const uint64_t *blocks, const uint64_t *data, uint64_t n
             for (int j = 0; j < 4; ++j) k.v[1 + j] = id[16 * b + t_round.src[p][j]];
             auto ins = seen.emplace(k, (uint32_t)head.size());
             if (ins.second) {
-                head.push_back(PUBLIC_HEAD(p, 0));
+                head.push_back(PUBLIC_HEAD(p, 0, key_of(b)));
                 for (int j = 0; j < 4; ++j) term.push_back(PUBLIC_TERM(k.v[1 + j], t_round.lut[p][j]));
             }
             next[16 * b + p] = ins.first->second;
@@ -248,7 +263,7 @@ static void public_plan(const uint64_t *blocks, const uint64_t *data, uint64_t n
         pl.layers.push_back({h0, h0 + nbytes, (uint32_t)nbytes, 1});
         pl.words.resize(h0 + 2 * nbytes);
         for (uint64_t b = 0; b < n_blocks; ++b) for (int p = 0; p < 16; ++p) {
-            pl.words[h0 + 16 * b + p] = PUBLIC_HEAD(p, data ? u128_byte(data + 2 * b, p) : 0);
+            pl.words[h0 + 16 * b + p] = PUBLIC_HEAD(p, data ? u128_byte(data + 2 * b, p) : 0, key_of(b));
             pl.words[h0 + nbytes + 16 * b + p] = PUBLIC_TERM(id[16 * b + t_shift.src[p][0]], 0);
         }
     }
@@ -256,44 +271,46 @@ static void public_plan(const uint64_t *blocks, const uint64_t *data, uint64_t n
     for (int r = 1; r <= nr; ++r) pl.max_vp_bytes_per_bw = std::max<uint64_t>(pl.max_vp_bytes_per_bw, (uint64_t)pl.layers[r - 1].n * (r < nr ? 3 : 1));
 }
 
+static_assert(FHEAES_MAX_KEYS == PUBLIC_MAX_KEYS, "fheaes.h's bound on n_keys is the key field of PUBLIC_HEAD");
 #define PUBLIC_MAX_BLOCKS (1ull << 26)      /* 16 n pool entries x 4 must fit a PUBLIC_TERM word */
 
-static int launch_public_round1(fheaes_ctx *c, const uint32_t *head, const uint64_t *rk0, uint64_t *out, uint64_t n_pool)
+static int launch_public_round1(fheaes_ctx *c, const uint32_t *head, const uint64_t *rk0, uint64_t key_stride, uint64_t *out, uint64_t n_pool)
 {
     TRY(noise_guard(c, 1, "the initial AddRoundKey on public bytes"));          // a trivial ciphertext carries no noise
     StageScope sc(c, FHEAES_STAGE_LINEAR, (n_pool + 15) / 16);
     dim3 grid((8 * c->big1 + 1023) / 1024, (unsigned)std::min<uint64_t>(n_pool, 65535));
-    hipLaunchKernelGGL(public_round1_kernel, grid, dim3(256), 0, c->stream, head, rk0, out, n_pool, c->big1);
+    hipLaunchKernelGGL(public_round1_kernel, grid, dim3(256), 0, c->stream, head, rk0, key_stride, out, n_pool, c->big1);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
 
 static int launch_gather_indexed(fheaes_ctx *c, const uint64_t *pool, uint32_t n_luts, const uint32_t *head, const uint32_t *term, uint32_t terms,
-                                 const uint64_t *rk, uint64_t *out, uint64_t n_out)
+                                 const uint64_t *rk, uint64_t key_stride, uint64_t *out, uint64_t n_out)
 {
     TRY(noise_guard(c, terms + 1u, "the indexed linear layer (MixColumns / ShiftRows + AddRoundKey over a pool)"));
     StageScope sc(c, FHEAES_STAGE_LINEAR, (n_out + 15) / 16);
     dim3 grid((8 * c->big1 + 1023) / 1024, (unsigned)std::min<uint64_t>(n_out, 65535));
-    hipLaunchKernelGGL(gather_add_indexed_kernel, grid, dim3(256), 0, c->stream, pool, n_luts, head, term, terms, rk, out, n_out, c->big1);
+    hipLaunchKernelGGL(gather_add_indexed_kernel, grid, dim3(256), 0, c->stream, pool, n_luts, head, term, terms, rk, key_stride, out, n_out, c->big1);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
 
-// `out` [n_blocks][16][8][kN+1] doubles as the pool buffer: no pool has more than 16 n_blocks entries
+// `out` [n_blocks][16][8][kN+1] doubles as the pool buffer: no pool has more than 16 n_blocks entries.  rk: [n_keys][Nr+1][16][8][kN+1],
+// the key of every pool entry is in its head word
 static int aes_public_dev(fheaes_ctx *c, const uint64_t *rk, const PublicPlan &pl, int nr, uint64_t *out)
 {
-    const uint64_t bw = 8ull * c->big1, sw = 16 * bw;
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, ks = (uint64_t)(nr + 1) * sw;
     // the index tables go through the context's pinned buffer (as add_scalar's counter bytes): the call only enqueues
     const size_t tab_bytes = pl.words.size() * sizeof(uint32_t);
     TRY(upload_pinned(c, tab_bytes, tab_bytes, [&](uint8_t *pin) { memcpy(pin, pl.words.data(), tab_bytes); }));
     const uint32_t *tab = (const uint32_t *)c->ws_misc.p;
     TRY(ensure(c, c->ws_vp, pl.max_vp_bytes_per_bw * bw * 8));               // the largest pool, not 16 n
     uint64_t *vp = (uint64_t *)c->ws_vp.p;
-    TRY(launch_public_round1(c, tab + pl.layers[0].head, rk, out, pl.layers[0].n));
+    TRY(launch_public_round1(c, tab + pl.layers[0].head, rk, ks, out, pl.layers[0].n));
     for (int round = 1; round <= nr; ++round) {
         const PublicPlan::Layer &in = pl.layers[round - 1], &to = pl.layers[round];
         TRY(many_sbox_dev(c, out, in.n, round < nr ? LUTSET_ENC_ROUND : LUTSET_SBOX, vp));
-        TRY(launch_gather_indexed(c, vp, round < nr ? 3 : 1, tab + to.head, tab + to.term, to.terms, rk + (uint64_t)round * sw, out, to.n));
+        TRY(launch_gather_indexed(c, vp, round < nr ? 3 : 1, tab + to.head, tab + to.term, to.terms, rk + (uint64_t)round * sw, ks, out, to.n));
     }
     return FHEAES_OK;
 }

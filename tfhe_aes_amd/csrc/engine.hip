@@ -581,25 +581,59 @@ int fheaes_sbox(fheaes_ctx *c, uint64_t *bytes, uint64_t n_bytes, int inv, int m
     return s.finish();
 }
 
-static int aes_crypt(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks, int memspace, AesDevFn dev)
+static bool overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+static int check_n_keys(fheaes_ctx *c, uint64_t n_keys)
+{
+    if (n_keys == 0 || n_keys > FHEAES_MAX_KEYS) return c->fail(FHEAES_ERR_INVALID, "n_keys must be in 1..%u (got %llu)", (unsigned)FHEAES_MAX_KEYS, (unsigned long long)n_keys);
+    return FHEAES_OK;
+}
+
+// key_of_block (HOST, n_blocks entries) names one of n_keys sets of round keys per block
+static int check_key_of_block(fheaes_ctx *c, const uint32_t *key_of_block, uint64_t n_blocks, uint64_t n_keys)
+{
+    for (uint64_t b = 0; b < n_blocks; ++b)
+        if (key_of_block[b] >= n_keys)
+            return c->fail(FHEAES_ERR_INVALID, "key_of_block[%llu] = %u, but there are %llu keys", (unsigned long long)b, key_of_block[b], (unsigned long long)n_keys);
+    return FHEAES_OK;
+}
+
+// The three block ciphers.  key_of_block null: the single-key entry points (one set of round keys, no table); else block b runs under
+// round_keys[key_of_block[b]] of [n_keys][Nr+1][16][8][kN+1], the table going to the device through the pinned buffer (one key: no table either).
+static int aes_crypt(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, uint64_t *state,
+                     uint64_t n_blocks, int memspace, AesDevFn dev)
 {
     TRY(check_keys(c));
     if (!round_keys || !state) return c->fail(FHEAES_ERR_INVALID, "null pointer");
     TRY(check_key_bits(c, key_bits));
     const int nr = aes_rounds(key_bits);
+    const uint64_t sw = 16ull * 8 * c->big1, ks = (uint64_t)(nr + 1) * sw;
+    if (key_of_block) {
+        TRY(check_n_keys(c, n_keys));
+        TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
+        if (n_blocks == 0) return FHEAES_OK;
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     Staged s(c, memspace);
-    const uint64_t sw = 16ull * 8 * c->big1;
-    TRY(s.in(round_keys, (uint64_t)(nr + 1) * sw * 8, &round_keys));
+    TRY(s.in(round_keys, n_keys * ks * 8, &round_keys));
     TRY(s.inout(state, n_blocks * sw * 8, &state));
-    TRY(dev(c, round_keys, state, n_blocks, nr));
+    const uint32_t *table = nullptr;
+    if (key_of_block && n_keys > 1) {
+        TRY(upload_pinned(c, n_blocks * sizeof(uint32_t), n_blocks * sizeof(uint32_t), [&](uint8_t *pin) { memcpy(pin, key_of_block, n_blocks * sizeof(uint32_t)); }));
+        table = (const uint32_t *)c->ws_misc.p;
+    }
+    TRY(dev(c, KeySets{round_keys, table, ks}, state, n_blocks, nr));
     return s.finish();
 }
 
 int fheaes_aes_encrypt_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks, int memspace)
 {
     CtxLock lock__(c);
-    return aes_crypt(c, round_keys, key_bits, state, n_blocks, memspace, aes_encrypt_dev);
+    return aes_crypt(c, round_keys, key_bits, 1, nullptr, state, n_blocks, memspace, aes_encrypt_dev);
 }
 
 int fheaes_aes_encrypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace)
@@ -610,7 +644,7 @@ int fheaes_aes_encrypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *stat
 int fheaes_aes_decrypt_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks, int memspace)
 {
     CtxLock lock__(c);
-    return aes_crypt(c, round_keys, key_bits, state, n_blocks, memspace, aes_decrypt_dev);
+    return aes_crypt(c, round_keys, key_bits, 1, nullptr, state, n_blocks, memspace, aes_decrypt_dev);
 }
 
 int fheaes_aes_decrypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace)
@@ -622,7 +656,7 @@ int fheaes_aes_decrypt_equivalent_bits(fheaes_ctx *c, const uint64_t *dec_round_
                                        int memspace)
 {
     CtxLock lock__(c);
-    return aes_crypt(c, dec_round_keys, key_bits, state, n_blocks, memspace, aes_decrypt_eq_dev);
+    return aes_crypt(c, dec_round_keys, key_bits, 1, nullptr, state, n_blocks, memspace, aes_decrypt_eq_dev);
 }
 
 int fheaes_aes_decrypt_equivalent(fheaes_ctx *c, const uint64_t *dec_round_keys, uint64_t *state, uint64_t n_blocks, int memspace)
@@ -630,48 +664,100 @@ int fheaes_aes_decrypt_equivalent(fheaes_ctx *c, const uint64_t *dec_round_keys,
     return fheaes_aes_decrypt_equivalent_bits(c, dec_round_keys, 128, state, n_blocks, memspace);
 }
 
-int fheaes_aes_decryption_round_keys_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t *dec_round_keys, int memspace)
+static int aes_crypt_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, uint64_t *state,
+                           uint64_t n_blocks, int memspace, AesDevFn dev)
 {
     CtxLock lock__(c);
     TRY(check_keys(c));
+    if (!key_of_block) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    return aes_crypt(c, round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, dev);
+}
+
+int fheaes_aes_encrypt_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, uint64_t *state,
+                             uint64_t n_blocks, int memspace)
+{
+    return aes_crypt_keyed(c, round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_encrypt_dev);
+}
+
+int fheaes_aes_decrypt_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, uint64_t *state,
+                             uint64_t n_blocks, int memspace)
+{
+    return aes_crypt_keyed(c, round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_decrypt_dev);
+}
+
+int fheaes_aes_decrypt_equivalent_keyed(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
+                                        uint64_t *state, uint64_t n_blocks, int memspace)
+{
+    return aes_crypt_keyed(c, dec_round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_decrypt_eq_dev);
+}
+
+// the two per-key calls: n_keys sets in, n_keys sets out
+static int dec_round_keys(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t *dec_round_keys, int memspace)
+{
+    TRY(check_keys(c));
     if (!round_keys || !dec_round_keys) return c->fail(FHEAES_ERR_INVALID, "null pointer");
     TRY(check_key_bits(c, key_bits));
+    TRY(check_n_keys(c, n_keys));
     const int nr = aes_rounds(key_bits);
-    const uint64_t sw = 16ull * 8 * c->big1;
-    const uintptr_t a = (uintptr_t)round_keys, b = (uintptr_t)dec_round_keys, bytes = (uint64_t)(nr + 1) * sw * 8;
-    if (a < b + bytes && b < a + bytes) return c->fail(FHEAES_ERR_INVALID, "round_keys and dec_round_keys overlap (the conversion is not in place)");
+    const uint64_t sw = 16ull * 8 * c->big1, bytes = n_keys * (uint64_t)(nr + 1) * sw * 8;
+    if (overlap(round_keys, bytes, dec_round_keys, bytes)) return c->fail(FHEAES_ERR_INVALID, "round_keys and dec_round_keys overlap (the conversion is not in place)");
     HIP_TRY(c, hipSetDevice(c->device));
     Staged s(c, memspace);
     TRY(s.in(round_keys, bytes, &round_keys));
     TRY(s.out(dec_round_keys, bytes, &dec_round_keys));
-    TRY(dec_round_keys_dev(c, round_keys, dec_round_keys, nr));
+    TRY(dec_round_keys_dev(c, round_keys, dec_round_keys, nr, n_keys));
     return s.finish();
 }
 
-int fheaes_aes_decryption_round_keys(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *dec_round_keys, int memspace)
+int fheaes_aes_decryption_round_keys_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t *dec_round_keys_out, int memspace)
 {
-    return fheaes_aes_decryption_round_keys_bits(c, round_keys, 128, dec_round_keys, memspace);
+    CtxLock lock__(c);
+    return dec_round_keys(c, round_keys, key_bits, 1, dec_round_keys_out, memspace);
+}
+
+int fheaes_aes_decryption_round_keys(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *dec_round_keys_out, int memspace)
+{
+    return fheaes_aes_decryption_round_keys_bits(c, round_keys, 128, dec_round_keys_out, memspace);
+}
+
+int fheaes_aes_decryption_round_keys_batch(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t *dec_round_keys_out,
+                                           int memspace)
+{
+    CtxLock lock__(c);
+    return dec_round_keys(c, round_keys, key_bits, n_keys, dec_round_keys_out, memspace);
+}
+
+static int key_expansion(fheaes_ctx *c, const uint64_t *key, uint32_t key_bits, uint64_t n_keys, uint64_t *round_keys, int memspace)
+{
+    TRY(check_keys(c));
+    if (!key || !round_keys) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    TRY(check_n_keys(c, n_keys));
+    const int nr = aes_rounds(key_bits);
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw;
+    TRY(s.in(key, n_keys * (key_bits / 8) * bw * 8, &key));
+    TRY(s.out(round_keys, n_keys * (uint64_t)(nr + 1) * sw * 8, &round_keys));
+    TRY(key_expansion_dev(c, key, round_keys, nr, n_keys));
+    return s.finish();
 }
 
 int fheaes_aes_key_expansion_bits(fheaes_ctx *c, const uint64_t *key, uint32_t key_bits, uint64_t *round_keys, int memspace)
 {
     CtxLock lock__(c);
-    TRY(check_keys(c));
-    if (!key || !round_keys) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    TRY(check_key_bits(c, key_bits));
-    const int nr = aes_rounds(key_bits);
-    HIP_TRY(c, hipSetDevice(c->device));
-    Staged s(c, memspace);
-    const uint64_t bw = 8ull * c->big1, sw = 16 * bw;
-    TRY(s.in(key, key_bits / 8 * bw * 8, &key));
-    TRY(s.out(round_keys, (uint64_t)(nr + 1) * sw * 8, &round_keys));
-    TRY(key_expansion_dev(c, key, round_keys, nr));
-    return s.finish();
+    return key_expansion(c, key, key_bits, 1, round_keys, memspace);
 }
 
 int fheaes_aes_key_expansion(fheaes_ctx *c, const uint64_t *key, uint64_t *round_keys, int memspace)
 {
     return fheaes_aes_key_expansion_bits(c, key, 128, round_keys, memspace);
+}
+
+int fheaes_aes_key_expansion_batch(fheaes_ctx *c, const uint64_t *keys, uint32_t key_bits, uint64_t n_keys, uint64_t *round_keys, int memspace)
+{
+    CtxLock lock__(c);
+    return key_expansion(c, keys, key_bits, n_keys, round_keys, memspace);
 }
 
 int fheaes_add_scalar(fheaes_ctx *c, uint64_t *state, uint64_t n_blocks, const uint64_t *counters_hi_lo, int memspace)
@@ -688,17 +774,18 @@ int fheaes_add_scalar(fheaes_ctx *c, uint64_t *state, uint64_t n_blocks, const u
     return s.finish();
 }
 
-static int aes_public(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *blocks, const uint64_t *data, uint64_t n_blocks,
-                      uint64_t *state_out, int memspace)
+// key_of_block null: every block under the one set `round_keys`
+static int aes_public(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, const uint64_t *blocks,
+                      const uint64_t *data, uint64_t n_blocks, uint64_t *state_out, int memspace)
 {
     const int nr = aes_rounds(key_bits);
     if (n_blocks > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %llu", (unsigned long long)PUBLIC_MAX_BLOCKS);
     HIP_TRY(c, hipSetDevice(c->device));
     PublicPlan pl;
-    public_plan(blocks, data, n_blocks, nr, pl);
+    public_plan(blocks, data, key_of_block, n_blocks, nr, pl);
     Staged s(c, memspace);
     const uint64_t sw = 16ull * 8 * c->big1;
-    TRY(s.in(round_keys, (uint64_t)(nr + 1) * sw * 8, &round_keys));
+    TRY(s.in(round_keys, n_keys * (uint64_t)(nr + 1) * sw * 8, &round_keys));
     TRY(s.out(state_out, n_blocks * sw * 8, &state_out));
     TRY(aes_public_dev(c, round_keys, pl, nr, state_out));
     return s.finish();
@@ -712,7 +799,7 @@ int fheaes_aes_encrypt_public_bits(fheaes_ctx *c, const uint64_t *round_keys, ui
     if (!round_keys || !blocks_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
     TRY(check_key_bits(c, key_bits));
     if (n_blocks == 0) return FHEAES_OK;
-    return aes_public(c, round_keys, key_bits, blocks_hi_lo, nullptr, n_blocks, state_out, memspace);
+    return aes_public(c, round_keys, key_bits, 1, nullptr, blocks_hi_lo, nullptr, n_blocks, state_out, memspace);
 }
 
 int fheaes_aes_ctr_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *iv_hi_lo, uint64_t first_block,
@@ -732,7 +819,25 @@ int fheaes_aes_ctr_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_
         ctr[2 * i] = hi0 + (lo < lo0 ? 1 : 0);
         ctr[2 * i + 1] = lo;
     }
-    return aes_public(c, round_keys, key_bits, ctr.data(), data_hi_lo, n_blocks, state_out, memspace);
+    return aes_public(c, round_keys, key_bits, 1, nullptr, ctr.data(), data_hi_lo, n_blocks, state_out, memspace);
+}
+
+int fheaes_aes_public_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
+                            const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
+{
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!round_keys || !key_of_block || !blocks_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    TRY(check_n_keys(c, n_keys));
+    TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
+    if (n_blocks == 0) return FHEAES_OK;
+    return aes_public(c, round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace);
+}
+
+static void plan_counts(const PublicPlan &pl, uint64_t n_blocks, int nr, uint64_t *unique_bytes_per_round)
+{
+    for (int r = 1; r <= nr; ++r) unique_bytes_per_round[r - 1] = n_blocks ? pl.layers[r - 1].n : 0;
 }
 
 int fheaes_aes_public_plan(const uint64_t *blocks_hi_lo, uint64_t n_blocks, uint32_t key_bits, uint64_t *unique_bytes_per_round)
@@ -740,8 +845,21 @@ int fheaes_aes_public_plan(const uint64_t *blocks_hi_lo, uint64_t n_blocks, uint
     const int nr = aes_rounds(key_bits);
     if (!blocks_hi_lo || !unique_bytes_per_round || !nr || n_blocks > PUBLIC_MAX_BLOCKS) return FHEAES_ERR_INVALID;
     PublicPlan pl;
-    if (n_blocks) public_plan(blocks_hi_lo, nullptr, n_blocks, nr, pl);
-    for (int r = 1; r <= nr; ++r) unique_bytes_per_round[r - 1] = n_blocks ? pl.layers[r - 1].n : 0;
+    if (n_blocks) public_plan(blocks_hi_lo, nullptr, nullptr, n_blocks, nr, pl);
+    plan_counts(pl, n_blocks, nr, unique_bytes_per_round);
+    return FHEAES_OK;
+}
+
+int fheaes_aes_public_plan_keyed(const uint64_t *blocks_hi_lo, const uint32_t *key_of_block, uint64_t n_blocks, uint64_t n_keys, uint32_t key_bits,
+                                 uint64_t *unique_bytes_per_round)
+{
+    const int nr = aes_rounds(key_bits);
+    if (!blocks_hi_lo || !key_of_block || !unique_bytes_per_round || !nr || n_blocks > PUBLIC_MAX_BLOCKS || n_keys == 0 || n_keys > FHEAES_MAX_KEYS)
+        return FHEAES_ERR_INVALID;
+    for (uint64_t b = 0; b < n_blocks; ++b) if (key_of_block[b] >= n_keys) return FHEAES_ERR_INVALID;
+    PublicPlan pl;
+    if (n_blocks) public_plan(blocks_hi_lo, nullptr, key_of_block, n_blocks, nr, pl);
+    plan_counts(pl, n_blocks, nr, unique_bytes_per_round);
     return FHEAES_OK;
 }
 
@@ -750,12 +868,6 @@ size_t fheaes_packed_words(const fheaes_ctx *c, uint64_t m)
 {
     if (!c) return 0;
     return (size_t)((m + FHE_N - 1) / FHE_N) * c->k1 * FHE_N;
-}
-
-static bool overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + b_bytes && y < x + a_bytes;
 }
 
 int fheaes_pack_bits(fheaes_ctx *c, const uint64_t *lwe_in, uint64_t m, uint64_t *glwe_out, int memspace)

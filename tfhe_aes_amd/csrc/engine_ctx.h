@@ -66,7 +66,7 @@ struct fheaes_ctx {
     uint64_t *lutset_d[LUTSET_COUNT] = {};
     int lutset_n[LUTSET_COUNT] = {};
     // workspace
-    DevBuf ws_small, ws_pbs, ws_ggsw, ws_ggswf, ws_vp, ws_tmp_a, ws_tmp_b, ws_luts, ws_misc, ws_digits, ws_park, ws_park_owner, ws_tree;
+    DevBuf ws_small, ws_pbs, ws_ggsw, ws_ggswf, ws_vp, ws_tmp_a, ws_tmp_b, ws_tmp_c, ws_luts, ws_misc, ws_digits, ws_park, ws_park_owner, ws_tree;
     DevBuf ws_park_pattern, ws_park_record;
     DevBuf stage[4];                     // host-memspace calls stage their arguments here (grow-only, reused)
     // pinned host staging for the counter bytes of add_scalar; `pin_ev` marks the last copy out of it

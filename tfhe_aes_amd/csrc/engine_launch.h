@@ -303,36 +303,47 @@ int noise_guard(fheaes_ctx *c, uint32_t level, const char *what)
     return FHEAES_OK;
 }
 
-int launch_gather(fheaes_ctx *c, const uint64_t *src, uint32_t n_luts, const uint64_t *rk, uint64_t *out, uint64_t n_blocks, const GatherTable &t)
+// The AES keys of a call: `rk` holds n sets of round keys `stride` words apart (slice i of [n_keys][Nr+1][16][8][kN+1]) and block b works
+// under set of_block[b] (a device table).  of_block null: one set for every block -- the single-key entry points, which upload no table.
+struct KeySets {
+    const uint64_t *rk;
+    const uint32_t *of_block;
+    uint64_t stride;
+    KeySets round(uint64_t r, uint64_t sw) const { return {rk + r * sw, of_block, stride}; }
+};
+
+int launch_gather(fheaes_ctx *c, const uint64_t *src, uint32_t n_luts, const KeySets &k, uint64_t *out, uint64_t n_blocks, const GatherTable &t)
 {
     if (n_blocks == 0) return FHEAES_OK;
-    TRY(noise_guard(c, (uint32_t)t.terms + (rk ? 1u : 0u), "the linear layer (MixColumns / ShiftRows + AddRoundKey)"));
+    TRY(noise_guard(c, (uint32_t)t.terms + (k.rk ? 1u : 0u), "the linear layer (MixColumns / ShiftRows + AddRoundKey)"));
     StageScope sc(c, FHEAES_STAGE_LINEAR, n_blocks);
     const uint32_t bw = 8 * c->big1;
     dim3 grid((bw + 1023) / 1024, 16, (unsigned)n_blocks);
-    hipLaunchKernelGGL(gather_add_kernel, grid, dim3(256), 0, c->stream, src, n_luts, rk, out, n_blocks, bw, t);
+    hipLaunchKernelGGL(gather_add_kernel, grid, dim3(256), 0, c->stream, src, n_luts, k.rk, k.of_block, k.stride, out, n_blocks, bw, t);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
 
-int launch_add_bcast(fheaes_ctx *c, uint64_t *dst, const uint64_t *src, uint64_t words_per_block, uint64_t n_blocks)
+int launch_add_bcast(fheaes_ctx *c, uint64_t *dst, const KeySets &k, uint64_t words_per_block, uint64_t n_blocks)
 {
     if (n_blocks == 0) return FHEAES_OK;
     TRY(noise_guard(c, 2, "the initial AddRoundKey"));
     StageScope sc(c, FHEAES_STAGE_LINEAR, n_blocks);
-    uint64_t total = words_per_block * n_blocks;
-    unsigned grid = (unsigned)std::min<uint64_t>((total + 255) / 256, 16384);
-    hipLaunchKernelGGL(add_bcast_kernel, dim3(grid), dim3(256), 0, c->stream, dst, src, words_per_block, n_blocks);
+    const unsigned gx = (unsigned)std::min<uint64_t>((words_per_block + 255) / 256, 64);
+    dim3 grid(gx, (unsigned)std::min<uint64_t>(n_blocks, std::max<uint64_t>(1, 16384 / gx)));
+    hipLaunchKernelGGL(add_bcast_kernel, grid, dim3(256), 0, c->stream, dst, k.rk, k.of_block, k.stride, words_per_block, n_blocks);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
 
-int launch_add2(fheaes_ctx *c, uint64_t *dst, const uint64_t *a, const uint64_t *b, uint64_t words)
+// key_rows_kernel over n_bytes bytes of each of n_keys keys; `level`: the nominal-noise ciphertexts one output word sums (1: a copy)
+int launch_key_rows(fheaes_ctx *c, uint64_t *dst, uint64_t dst_stride, const uint64_t *a, uint64_t a_stride, uint32_t rot, const uint64_t *b,
+                    uint64_t b_stride, uint32_t rcon, uint32_t n_bytes, uint64_t n_keys, uint32_t level)
 {
-    TRY(noise_guard(c, 2, "a key-expansion word sum"));
-    StageScope sc(c, FHEAES_STAGE_LINEAR, 1);
-    unsigned grid = (unsigned)std::min<uint64_t>((words + 255) / 256, 16384);
-    hipLaunchKernelGGL(add2_kernel, dim3(grid), dim3(256), 0, c->stream, dst, a, b, words);
+    if (level > 1) TRY(noise_guard(c, level, "a key-expansion word sum"));
+    StageScope sc(c, FHEAES_STAGE_LINEAR, n_keys);
+    dim3 grid((8 * c->big1 + 1023) / 1024, n_bytes, (unsigned)std::min<uint64_t>(n_keys, 65535));
+    hipLaunchKernelGGL(key_rows_kernel, grid, dim3(256), 0, c->stream, dst, dst_stride, a, a_stride, rot, b, b_stride, rcon, c->big1, n_keys);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }

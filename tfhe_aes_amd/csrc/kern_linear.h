@@ -16,61 +16,81 @@ struct GatherTable {
     int8_t lut[16][4];      // which LUT output of that byte
 };
 
-// src: [n_blocks][16][n_luts][byte_words]; rk: [16][byte_words] or null; out: [n_blocks][16][byte_words]
-__global__ __launch_bounds__(256) void gather_add_kernel(const uint64_t *src, uint32_t n_luts, const uint64_t *rk, uint64_t *out,
-                                                         uint64_t n_blocks, uint32_t byte_words, const GatherTable tab)
+// src: [n_blocks][16][n_luts][byte_words]; rk: [n_keys][key_stride words] with [16][byte_words] at its front, or null;
+// key_of_block: [n_blocks] or null (every block under rk's first key); out: [n_blocks][16][byte_words]
+__global__ __launch_bounds__(256) void gather_add_kernel(const uint64_t *src, uint32_t n_luts, const uint64_t *rk, const uint32_t *key_of_block,
+                                                         uint64_t key_stride, uint64_t *out, uint64_t n_blocks, uint32_t byte_words, const GatherTable tab)
 {
     const uint64_t blk = blockIdx.z;
     const uint32_t byte = blockIdx.y;
     const uint64_t *sb = src + blk * 16 * (uint64_t)n_luts * byte_words;
+    const uint64_t *kb = rk ? rk + (key_of_block ? key_of_block[blk] * key_stride : 0) + (uint64_t)byte * byte_words : nullptr;
     uint64_t *ob = out + (blk * 16 + byte) * (uint64_t)byte_words;
     for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
-        uint64_t v = rk ? rk[(uint64_t)byte * byte_words + w] : 0;
+        uint64_t v = kb ? kb[w] : 0;
         for (int t = 0; t < tab.terms; ++t)
             v += sb[((uint64_t)tab.src[byte][t] * n_luts + tab.lut[byte][t]) * byte_words + w];
         ob[w] = v;
     }
 }
 
-// dst[blk][i] += src[i]  (add_round_key with one key set for all blocks)
-__global__ __launch_bounds__(256) void add_bcast_kernel(uint64_t *dst, const uint64_t *src, uint64_t words_per_block, uint64_t n_blocks)
+// dst[blk][i] += rk[key_of_block[blk]][i]  (add_round_key; key_of_block null: one key set for all blocks).  dst: [n_blocks][words_per_block];
+// rk: [n_keys][key_stride words], the round key at the front of each
+__global__ __launch_bounds__(256) void add_bcast_kernel(uint64_t *dst, const uint64_t *rk, const uint32_t *key_of_block, uint64_t key_stride,
+                                                        uint64_t words_per_block, uint64_t n_blocks)
 {
-    uint64_t total = words_per_block * n_blocks;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x)
-        dst[i] += src[i % words_per_block];
+    for (uint64_t blk = blockIdx.y; blk < n_blocks; blk += gridDim.y) {
+        const uint64_t *kb = rk + (key_of_block ? key_of_block[blk] * key_stride : 0);
+        uint64_t *db = dst + blk * words_per_block;
+        for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words_per_block; i += (uint64_t)gridDim.x * blockDim.x)
+            db[i] += kb[i];
+    }
 }
 
-// dst[i] = a[i] + b[i]
-__global__ __launch_bounds__(256) void add2_kernel(uint64_t *dst, const uint64_t *a, const uint64_t *b, uint64_t words)
+// Rows of bytes moved between strided sets, one set per AES key: the word operations of the key expansion over all keys at once (RotWord,
+// w[i-1] or the SubWord result + w[i-Nk] + Rcon, placing refreshed words at their stride) and the strided copies of the round-key
+// conversion.  For key j and byte q < n_bytes:
+//   dst[j][q] = a[j][(q & ~3) | ((q + rot) & 3)] + (b ? b[j][q] : 0) + (q == 0 ? trivial(rcon) : 0)
+// a, b, dst: rows of byte_words = 8 * lwe_words words, key j's at j * {a,b,dst}_stride words.  trivial(v): bit j of v << 63 on body j.
+__global__ __launch_bounds__(256) void key_rows_kernel(uint64_t *dst, uint64_t dst_stride, const uint64_t *a, uint64_t a_stride, uint32_t rot,
+                                                       const uint64_t *b, uint64_t b_stride, uint32_t rcon, uint32_t lwe_words, uint64_t n_keys)
 {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (uint64_t)gridDim.x * blockDim.x)
-        dst[i] = a[i] + b[i];
-}
-
-// trivial (noise-free) byte constant added to an encrypted byte: body of bit j += ((value >> j) & 1) << 63
-__global__ void add_const_byte_kernel(uint64_t *byte_ct, uint32_t lwe_words, uint32_t value)
-{
-    int j = threadIdx.x;
-    if (j < 8) byte_ct[(uint64_t)j * lwe_words + lwe_words - 1] += (uint64_t)((value >> j) & 1u) << 63;
+    const uint32_t byte_words = 8 * lwe_words, q = blockIdx.y;
+    const uint32_t clear = q == 0 ? rcon : 0u;
+    for (uint64_t j = blockIdx.z; j < n_keys; j += gridDim.z) {
+        const uint64_t *ab = a + j * a_stride + (uint64_t)((q & ~3u) | ((q + rot) & 3u)) * byte_words;
+        const uint64_t *bb = b ? b + j * b_stride + (uint64_t)q * byte_words : nullptr;
+        uint64_t *ob = dst + j * dst_stride + (uint64_t)q * byte_words;
+        for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
+            uint64_t v = ab[w];
+            if (bb) v += bb[w];
+            if (clear) {
+                const uint32_t bit = w / lwe_words;
+                if (w - bit * lwe_words == lwe_words - 1) v += (uint64_t)((clear >> bit) & 1u) << 63;
+            }
+            ob[w] = v;
+        }
+    }
 }
 
 // ---- public blocks / CTR with a public nonce (fheaes_aes_encrypt_public_bits, fheaes_aes_ctr_bits) ------------------------------
 // Every distinct S-Box input of a batch of PUBLIC blocks is evaluated once: a round works on a POOL of distinct bytes instead of
 // [n_blocks][16].  One uint32 head word per pool entry says where it sits in the state and which clear byte goes with it:
-#define PUBLIC_HEAD(pos, clear) ((uint32_t)(pos) | ((uint32_t)(clear) << 8))     // bits 0..3: state position p, bits 8..15: clear byte
+#define PUBLIC_HEAD(pos, clear, key) ((uint32_t)(pos) | ((uint32_t)(clear) << 8) | ((uint32_t)(key) << 16))     // bits 0..3: state position p, 8..15: clear byte, 16..31: AES key
+#define PUBLIC_MAX_KEYS 65536u      /* the key index of a pool entry has 16 bits */
 // and one uint32 per term says what to sum: WoPBS output `lut` of pool entry `src` of the round before
 #define PUBLIC_TERM(src, lut) (((uint32_t)(src) << 2) | (uint32_t)(lut))
 
-// Pool of round 1: out[u] = rk0[p_u] + trivial(v_u), i.e. the round key's words with ((v_u >> bit) & 1) << 63 added to each body:
+// Pool of round 1: out[u] = rk0[key_u][p_u] + trivial(v_u), i.e. the round key's words with ((v_u >> bit) & 1) << 63 added to each body:
 // word for word the initial AddRoundKey on a trivial ciphertext (mask 0, body = bit << 63) of v_u.
-// head: [n_pool]; rk0: [16][byte_words]; out: [n_pool][byte_words]; byte_words = 8 * lwe_words
-__global__ __launch_bounds__(256) void public_round1_kernel(const uint32_t *head, const uint64_t *rk0, uint64_t *out, uint64_t n_pool,
+// head: [n_pool]; rk0: [n_keys][key_stride words], [16][byte_words] at the front of each; out: [n_pool][byte_words]; byte_words = 8 * lwe_words
+__global__ __launch_bounds__(256) void public_round1_kernel(const uint32_t *head, const uint64_t *rk0, uint64_t key_stride, uint64_t *out, uint64_t n_pool,
                                                             uint32_t lwe_words)
 {
     const uint32_t byte_words = 8 * lwe_words;
     for (uint64_t u = blockIdx.y; u < n_pool; u += gridDim.y) {
         const uint32_t h = head[u], pos = h & 15u, clear = (h >> 8) & 0xFFu;
-        const uint64_t *kb = rk0 + (uint64_t)pos * byte_words;
+        const uint64_t *kb = rk0 + (h >> 16) * key_stride + (uint64_t)pos * byte_words;
         uint64_t *ob = out + u * byte_words;
         for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
             const uint32_t bit = w / lwe_words;
@@ -83,17 +103,17 @@ __global__ __launch_bounds__(256) void public_round1_kernel(const uint32_t *head
 
 // The linear layer between two pools, and from the last pool into the state: gather_add_kernel with the sources of every output
 // byte read from a table in device memory instead of being the same for every block.
-//   out[u] = sum_{j < terms} pool[src_uj][lut_uj] + rk[p_u] + trivial(clear_u)
+//   out[u] = sum_{j < terms} pool[src_uj][lut_uj] + rk[key_u][p_u] + trivial(clear_u)
 // pool: [n_src][n_luts][byte_words] (WoPBS outputs of the round before); head: [n_out] PUBLIC_HEAD; term: [n_out][terms] PUBLIC_TERM;
-// rk: [16][byte_words]; out: [n_out][byte_words].  clear_u is 0 except in CTR's last layer (the data byte).  Wrapping uint64 sums: any
+// rk: [n_keys][key_stride words], [16][byte_words] at the front of each; out: [n_out][byte_words].  clear_u is 0 except in CTR's last layer (the data byte).  Wrapping uint64 sums: any
 // order of the terms gives gather_add_kernel's words.
 __global__ __launch_bounds__(256) void gather_add_indexed_kernel(const uint64_t *pool, uint32_t n_luts, const uint32_t *head, const uint32_t *term,
-                                                                 uint32_t terms, const uint64_t *rk, uint64_t *out, uint64_t n_out, uint32_t lwe_words)
+                                                                 uint32_t terms, const uint64_t *rk, uint64_t key_stride, uint64_t *out, uint64_t n_out, uint32_t lwe_words)
 {
     const uint32_t byte_words = 8 * lwe_words;
     for (uint64_t u = blockIdx.y; u < n_out; u += gridDim.y) {
         const uint32_t h = head[u], pos = h & 15u, clear = (h >> 8) & 0xFFu;
-        const uint64_t *kb = rk + (uint64_t)pos * byte_words;
+        const uint64_t *kb = rk + (h >> 16) * key_stride + (uint64_t)pos * byte_words;
         const uint64_t *s[4];                                    // terms <= 4; fully unrolled so that the pointers stay in registers
 #pragma unroll
         for (uint32_t t = 0; t < 4; ++t) {

@@ -4,7 +4,9 @@ Same names, argument meaning and error behaviour as
   /root/reference/src/server/server.rs        Server::{new, aes_encrypt, aes_decrypt, aes_key_expansion, add_scalar}
   (plus aes_decryption_round_keys / aes_decrypt_equivalent: the FIPS-197 section 5.3.5 equivalent inverse cipher; plus AES-192
   and AES-256, which the reference does not have: the same methods read the key size from the leading axis of the key / round keys;
-  plus aes_encrypt_public / aes_ctr: public blocks and SP 800-38A CTR with a PUBLIC nonce, every distinct S-Box input evaluated once)
+  plus aes_encrypt_public / aes_ctr: public blocks and SP 800-38A CTR with a PUBLIC nonce, every distinct S-Box input evaluated once;
+  plus the *_many / *_keyed / aes_ctr_streams methods: many AES keys under one FHE key, round keys [n_keys][Nr+1][16][8][kN+1] and a key
+  index per block, word for word the single-key methods key by key)
   /root/reference/src/server/sbox/sbox.rs     sbox, many_sbox, mul2 .. mul14
   /root/reference/src/server/sbox/many_wopbs.rs  many_wopbs_without_padding
   /root/reference/src/server/sbox/gen_lut.rs  gen_lut
@@ -79,6 +81,32 @@ def _data_blocks(data, n_blocks: int):
     if len(data) != n_blocks:
         raise ValueError("one data block per counter block expected")
     return data
+
+
+def _many_key_bits(arr, what):
+    """(key size, n_keys) of [n_keys][Nr+1][16][8][kN+1]"""
+    if arr.ndim != 5 or int(arr.shape[0]) < 1:
+        raise ValueError("%s of many keys must be [n_keys][11 | 13 | 15][16][8][kN+1] with n_keys >= 1, got shape %s" % (what, tuple(arr.shape)))
+    return _key_bits(arr[0], ROUND_KEYS_TO_BITS, what), int(arr.shape[0])
+
+
+def ctr_stream_blocks(streams):
+    """CTR streams (key_index, iv, first_block, n_blocks, data_or_None) -> (key per block, counter blocks, data blocks or None), the
+    counters (iv + first_block + i) mod 2^128 as aes_ctr builds them; a stream without data contributes zero blocks of data"""
+    key_of_block, blocks, data, any_data = [], [], [], False
+    for key_index, iv, first_block, n_blocks, d in streams:
+        n_blocks, first_block = int(n_blocks), int(first_block)
+        if n_blocks < 0 or first_block < 0:
+            raise ValueError("n_blocks and first_block must be >= 0")
+        iv = int.from_bytes(iv, "big") if isinstance(iv, (bytes, bytearray)) else int(iv)
+        if not 0 <= iv < 1 << 128:
+            raise ValueError("iv is a 128-bit value")
+        d = _data_blocks(d, n_blocks)
+        any_data = any_data or d is not None
+        key_of_block += [int(key_index)] * n_blocks
+        blocks += [(iv + first_block + i) % (1 << 128) for i in range(n_blocks)]
+        data += [0] * n_blocks if d is None else d
+    return key_of_block, blocks, data if any_data else None
 
 
 class Server:
@@ -209,13 +237,72 @@ class Server:
         self.engine.aes_ctr_bits(encrypted_round_keys, bits, iv, first_block, data, n_blocks, out)
         return out
 
-    def _public_out(self, round_keys, n_blocks: int, out):
-        shape = (n_blocks, 16, 8, self.params.big1)
+    # ---- many AES keys under one FHE key ----------------------------------------------
+    def aes_key_expansion_many(self, keys, out=None):
+        """keys [n_keys][16 | 24 | 32][8][kN+1] (one key size) -> round keys [n_keys][Nr+1][16][8][kN+1] (or `out`); slice i is
+        aes_key_expansion(keys[i]) word for word, every step one WoPBS over all keys (include/fheaes.h: fheaes_aes_key_expansion_batch)."""
+        if keys.ndim != 4 or int(keys.shape[0]) < 1:
+            raise ValueError("keys must be [n_keys][16 | 24 | 32][8][kN+1] with n_keys >= 1, got shape %s" % (tuple(keys.shape),))
+        bits = _key_bits(keys[0], KEY_BYTES_TO_BITS, "key", ndim=3)
+        n_keys = int(keys.shape[0])
+        rk = self._many_out(keys, (n_keys, bits // 32 + 7, 16, 8, self.params.big1), out)
+        self.engine.aes_key_expansion_batch(keys, bits, n_keys, rk)
+        return rk
+
+    @staticmethod
+    def _many_out(ref, shape, out):
         if out is None:
-            return _empty_like(round_keys, shape)
+            return _empty_like(ref, shape)
         if tuple(out.shape) != shape:
             raise ValueError("out must be %s, got %s" % (shape, tuple(out.shape)))
         return out
+
+    def aes_decryption_round_keys_many(self, round_keys, out=None):
+        """[n_keys][Nr+1][16][8][kN+1] -> the equivalent inverse cipher's round keys of every key (or `out`), the middle bytes of all keys in
+        one batch; slice i is aes_decryption_round_keys(round_keys[i]) word for word."""
+        bits, n_keys = _many_key_bits(round_keys, "round keys")
+        dw = self._many_out(round_keys, tuple(round_keys.shape), out)
+        self.engine.aes_decryption_round_keys_batch(round_keys, bits, n_keys, dw)
+        return dw
+
+    def _keyed(self, call, round_keys, key_of_block, state):
+        bits, n_keys = _many_key_bits(round_keys, "round keys")
+        if state.ndim != 4:
+            raise ValueError("a keyed call works on a batch [n_blocks][16][8][kN+1]; wrap a single state as state[None]")
+        call(round_keys, bits, n_keys, list(key_of_block), state, int(state.shape[0]))
+        return state
+
+    def aes_encrypt_keyed(self, round_keys, key_of_block, state):
+        """aes_encrypt with a key per block, in place: block b of state [n_blocks][16][8][kN+1] under round_keys[key_of_block[b]], the words
+        aes_encrypt(round_keys[key_of_block[b]], ...) writes for it; every round is one WoPBS over all blocks."""
+        return self._keyed(self.engine.aes_encrypt_keyed, round_keys, key_of_block, state)
+
+    def aes_decrypt_keyed(self, round_keys, key_of_block, state):
+        """aes_decrypt with a key per block, in place."""
+        return self._keyed(self.engine.aes_decrypt_keyed, round_keys, key_of_block, state)
+
+    def aes_decrypt_equivalent_keyed(self, dec_round_keys, key_of_block, state):
+        """aes_decrypt_equivalent with a key per block, in place; dec_round_keys from aes_decryption_round_keys_many."""
+        return self._keyed(self.engine.aes_decrypt_equivalent_keyed, dec_round_keys, key_of_block, state)
+
+    def aes_encrypt_public_keyed(self, round_keys, key_of_block, blocks, data=None, out=None):
+        """aes_encrypt_public with a key per block (and, as aes_ctr, clear `data` blocks folded into the last layer): a new
+        [n][16][8][kN+1] (or `out`).  Equal S-Box inputs under the same key are evaluated once, equal blocks under different keys are not shared."""
+        bits, n_keys = _many_key_bits(round_keys, "round keys")
+        blocks = list(blocks)
+        out = self._public_out(round_keys, len(blocks), out)
+        self.engine.aes_public_keyed(round_keys, bits, n_keys, list(key_of_block), blocks, _data_blocks(data, len(blocks)), out)
+        return out
+
+    def aes_ctr_streams(self, round_keys, streams, out=None):
+        """several SP 800-38A CTR streams with PUBLIC nonces under several keys in one call: `streams` is a list of
+        (key_index, iv, first_block, n_blocks, data_or_None), each as the arguments of aes_ctr; returns the streams' blocks concatenated in
+        order, [sum n_blocks][16][8][kN+1], each stream's word for word aes_ctr(round_keys[key_index], iv, first_block, n_blocks, data)."""
+        key_of_block, blocks, data = ctr_stream_blocks(streams)
+        return self.aes_encrypt_public_keyed(round_keys, key_of_block, blocks, data=data, out=out)
+
+    def _public_out(self, round_keys, n_blocks: int, out):
+        return self._many_out(round_keys, (n_blocks, 16, 8, self.params.big1), out)
 
     # ---- packed ciphertexts ------------------------------------------------------
     def pack(self, ct, out=None):
@@ -352,6 +439,53 @@ class ServerGroup:
 
     def aes_key_expansion(self, key):
         return self.servers[0].aes_key_expansion(key)
+
+    # many AES keys: the keyed calls shard on blocks, every context reading the whole set of round keys; the per-key calls shard on keys
+    def _fan_out_keys(self, arr, out, fn):
+        """context i takes keys i * G / n .. of `arr` [n_keys][...] into the same slices of `out`; finished before returning, since device
+        round keys are then read from every context's stream"""
+        from .dist import shard_blocks
+
+        g = len(self.servers)
+        shards = [shard_blocks(int(arr.shape[0]), g, i) for i in range(g)]
+        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: fn(s, arr[lo:hi], out[lo:hi])) for lo, hi in shards])
+        return out
+
+    def aes_key_expansion_many(self, keys):
+        if keys.ndim != 4 or int(keys.shape[1]) not in KEY_BYTES_TO_BITS:
+            raise ValueError("keys must be [n_keys][16 | 24 | 32][8][kN+1], got shape %s" % (tuple(keys.shape),))
+        out = _empty_like(keys, (int(keys.shape[0]), int(keys.shape[1]) // 4 + 7, 16, 8, self.params.big1))
+        return self._fan_out_keys(keys, out, lambda s, part, o: s.aes_key_expansion_many(part, out=o))
+
+    def aes_decryption_round_keys_many(self, round_keys):
+        _many_key_bits(round_keys, "round keys")
+        out = _empty_like(round_keys, tuple(round_keys.shape))
+        return self._fan_out_keys(round_keys, out, lambda s, part, o: s.aes_decryption_round_keys_many(part, out=o))
+
+    def aes_encrypt_keyed(self, round_keys, key_of_block, state):
+        kob = list(key_of_block)
+        return self._fan_out(lambda s, shard, lo: s.aes_encrypt_keyed(round_keys, kob[lo:lo + int(shard.shape[0])], shard), state)
+
+    def aes_decrypt_keyed(self, round_keys, key_of_block, state):
+        kob = list(key_of_block)
+        return self._fan_out(lambda s, shard, lo: s.aes_decrypt_keyed(round_keys, kob[lo:lo + int(shard.shape[0])], shard), state)
+
+    def aes_decrypt_equivalent_keyed(self, dec_round_keys, key_of_block, state):
+        kob = list(key_of_block)
+        return self._fan_out(lambda s, shard, lo: s.aes_decrypt_equivalent_keyed(dec_round_keys, kob[lo:lo + int(shard.shape[0])], shard), state)
+
+    def aes_encrypt_public_keyed(self, round_keys, key_of_block, blocks, data=None):
+        """Server.aes_encrypt_public_keyed, the blocks sharded contiguously; each context plans the sharing inside its own shard"""
+        kob, blocks = list(key_of_block), list(blocks)
+        data = _data_blocks(data, len(blocks))
+        if len(kob) != len(blocks):
+            raise ValueError("one key index per block expected")
+        return self._fan_out_new(round_keys, len(blocks), lambda s, shard, lo, k: s.aes_encrypt_public_keyed(
+            round_keys, kob[lo:lo + k], blocks[lo:lo + k], data=None if data is None else data[lo:lo + k], out=shard))
+
+    def aes_ctr_streams(self, round_keys, streams):
+        key_of_block, blocks, data = ctr_stream_blocks(streams)
+        return self.aes_encrypt_public_keyed(round_keys, key_of_block, blocks, data=data)
 
     def _glwe_shards(self, n_glwes: int):
         from .dist import shard_blocks
