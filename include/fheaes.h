@@ -328,6 +328,12 @@ int fheaes_read_bsk_fourier(fheaes_ctx *ctx, uint32_t i, double *out);
  * slots (form 1: two per CU, form 2: one per CU) the counts make the launch a whole number of generations that covers the batch exactly. */
 int fheaes_k2_launch_plan(uint64_t m, uint32_t cu_count, uint32_t k, int *form, uint64_t *units_main, uint32_t *r_main,
                           uint64_t *units_tail, uint32_t *r_tail);
+/* fheaes_k2_launch_plan for a device whose runtime cannot place the paired kernel (`allow_pair` = 0: every batch above 256 bits takes
+ * form 1; up to two workgroups per CU, and beyond 2 x cu_count units of three a whole number of generations of three- and
+ * two-ciphertext units that covers the batch exactly, the two-ciphertext units last, once the batch holds two ciphertexts per unit;
+ * k = 1 is the same either way).  `allow_pair` = 1 is fheaes_k2_launch_plan; any other value is FHEAES_ERR_INVALID.  Host logic only. */
+int fheaes_k2_launch_plan_forms(uint64_t m, uint32_t cu_count, uint32_t k, int allow_pair, int *form, uint64_t *units_main, uint32_t *r_main,
+                                uint64_t *units_tail, uint32_t *r_tail);
 /* The same for a CONTEXT: the form and the kernel this context really launches for a batch of `m` bits on its device, after the
  * occupancy fallbacks (the paired kernel needs 159,504 B of LDS per workgroup: where the runtime cannot place one on a CU every batch
  * takes form 1; the 16-form's LDS-home variant needs two workgroups of 81,920 B per CU, else its parked variant runs).  `kernel`
@@ -341,6 +347,13 @@ int fheaes_k2_context_plan(fheaes_ctx *ctx, uint64_t m, int *form, uint64_t *uni
  * (" parking=claimed" / " parking=private").  Ownership of a slot is recorded in memory and never inferred from the compute unit a
  * workgroup runs on: a queue preempted mid-kernel resumes its workgroups on other compute units (round 5's defect). */
 int fheaes_k2_set_parking(fheaes_ctx *ctx, int claimed);
+/* Test hook of the occupancy fallbacks (tests/test_gpu_k2_shapes.py): `allow_pair` = 0 takes the paired kernel away from this context,
+ * `allow_home` = 0 the 16-form's LDS-home variant, exactly as a refused occupancy query does; 1 means "whatever the query allows" -- the
+ * effective setting is "queried AND allowed", so the hook can only take a form away and never grants one the device refused.  Default:
+ * both 1.  Each argument is 0 or 1 (else FHEAES_ERR_INVALID).  fheaes_k2_context_plan, fheaes_reserve and every launch follow the
+ * setting; with the pair denied the paired kernel's parking pool and owner words are not touched.  Per context: other contexts and
+ * the plans of k = 1 (which has neither form) are unaffected.  Synchronises the context's stream. */
+int fheaes_k2_set_forms(fheaes_ctx *ctx, int allow_pair, int allow_home);
 /* Test hook of the claimed parking slots (tests/test_gpu_park_slots.py).  The pool is FHEAES_K2_PARK_SLOTS owner words, 128 per XCC
  * (0 = free, else 1 + the index of the owning workgroup).  `initial_owner` (host, FHEAES_K2_PARK_SLOTS words) non-NULL: every
  * claimed-mode paired launch starts from a copy of these words instead of zeros -- a nonzero word is a slot someone else owns for the

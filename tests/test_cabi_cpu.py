@@ -114,6 +114,55 @@ def test_k2_launch_plan_covers_the_batch_in_whole_generations():
         assert lib.fheaes_k2_launch_plan(bad[0], bad[1], 4, C.byref(f), C.byref(a), C.byref(b), C.byref(c), C.byref(d)) != 0
 
 
+def test_k2_launch_plan_without_the_paired_kernel():
+    """k2_plan(..., allow_pair = false), the plan of a device whose runtime cannot place the paired kernel (engine_launch.h::
+    k2_pair_allowed) and of fheaes_k2_set_forms(ctx, 0, ...): every batch above 256 bits takes the 16-form.  Up to 2 x CUs units of
+    three ciphertexts (two workgroups per CU); from 4 x CUs bits a whole number of generations of three- and two-ciphertext units that
+    covers the batch exactly, the two-ciphertext units last"""
+    import ctypes as C
+
+    lib = _native.load_library()
+    def plan(m, allow_pair=0, cus=256, k=4):
+        form, um, ut = C.c_int(), C.c_uint64(), C.c_uint64()
+        rm, rt = C.c_uint32(), C.c_uint32()
+        assert lib.fheaes_k2_launch_plan_forms(m, cus, k, allow_pair, C.byref(form), C.byref(um), C.byref(rm), C.byref(ut), C.byref(rt)) == 0
+        return form.value, um.value, rm.value, ut.value, rt.value
+
+    assert plan(769) == (1, 257, 3, 0, 2)              # two home workgroups on one CU
+    assert plan(1536) == (1, 512, 3, 0, 2)             # every slot taken
+    assert plan(1537) == (1, 513, 3, 0, 2)             # one unit beyond the slots: too few bits for a generation of two-ciphertext units
+    assert plan(2048) == (1, 0, 3, 1024, 2)            # two generations of two-ciphertext units only
+    assert plan(2100) == (1, 52, 3, 972, 2)            # mixed generations
+    for m in list(range(769, 9000, 7)) + [16384, 32768]:
+        form, um, rm, ut, rt = plan(m)
+        assert (form, rm, rt) == (1, 3, 2), m
+        assert m <= 3 * um + 2 * ut <= m + 2, m
+        if um and ut:
+            assert 3 * um + 2 * ut == m and (um + ut) % 512 == 0, m        # whole generations of two workgroups per CU, exact cover
+    # below the paired form's threshold, at k = 1 and with the pair allowed the two entry points agree
+    def plan0(m, cus=256, k=4):
+        form, um, ut = C.c_int(), C.c_uint64(), C.c_uint64()
+        rm, rt = C.c_uint32(), C.c_uint32()
+        assert lib.fheaes_k2_launch_plan(m, cus, k, C.byref(form), C.byref(um), C.byref(rm), C.byref(ut), C.byref(rt)) == 0
+        return form.value, um.value, rm.value, ut.value, rt.value
+    for m in (1, 256, 257, 512, 513, 768):
+        assert plan(m) == plan0(m) == plan(m, allow_pair=1)
+    for m in (769, 1536, 2100, 16384):
+        assert plan(m, allow_pair=1) == plan0(m) and plan(m, k=1) == plan0(m, k=1)
+    f = C.c_int(); a = C.c_uint64(); b = C.c_uint32(); c = C.c_uint64(); d = C.c_uint32()
+    for bad in ((0, 256, 0), (16, 0, 0), (800, 256, 2), (800, 256, -1)):
+        assert lib.fheaes_k2_launch_plan_forms(bad[0], bad[1], 4, bad[2], C.byref(f), C.byref(a), C.byref(b), C.byref(c), C.byref(d)) == -1
+    assert lib.fheaes_k2_launch_plan_forms(800, 256, 4, 0, None, C.byref(a), C.byref(b), C.byref(c), C.byref(d)) == -1
+
+
+def test_k2_forms_hook_rejects_a_null_context():
+    """fheaes_k2_set_forms without a context is FHEAES_ERR_INVALID whatever the arguments (the bad-argument codes on a live context:
+    tests/test_gpu_k2_shapes.py)"""
+    lib = _native.load_library()
+    for pair, home in ((1, 1), (0, 0), (0, 1), (2, 1), (1, -1)):
+        assert lib.fheaes_k2_set_forms(None, pair, home) == -1
+
+
 def test_fft_constants_header_matches_the_twiddle_table():
     """csrc/fft_consts.h (generated by tools/gen_fft_consts.py) holds the lane-independent twiddles of the kernels' transform as
     literals: psi^(16 m), m < 32.  They must BE the table both sides derive from the same specification -- the engine's host

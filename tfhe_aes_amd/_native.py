@@ -82,9 +82,12 @@ SIGNATURES = {
     "fheaes_read_bsk_fourier": (_c.c_int, [_ctx, _c.c_uint32, _dp]),
     "fheaes_k2_launch_plan": (_c.c_int, [_c.c_uint64, _c.c_uint32, _c.c_uint32, _c.POINTER(_c.c_int), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32),
                                        _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32)]),
+    "fheaes_k2_launch_plan_forms": (_c.c_int, [_c.c_uint64, _c.c_uint32, _c.c_uint32, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_uint64),
+                                             _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32)]),
     "fheaes_k2_context_plan": (_c.c_int, [_ctx, _c.c_uint64, _c.POINTER(_c.c_int), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32),
                                         _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32), _c.c_char_p, _c.c_size_t]),
     "fheaes_k2_set_parking": (_c.c_int, [_ctx, _c.c_int]),
+    "fheaes_k2_set_forms": (_c.c_int, [_ctx, _c.c_int, _c.c_int]),
     "fheaes_k2_park_debug": (_c.c_int, [_ctx, _c.POINTER(_c.c_uint32), _c.c_int]),
     "fheaes_k2_park_read": (_c.c_int, [_ctx, _u64p, _u64p, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32), _c.c_uint64, _u64p]),
     "fheaes_version": (_c.c_char_p, []),
@@ -385,6 +388,11 @@ class Engine:
     def k2_set_parking(self, claimed: bool):
         """paired blind-rotation kernel: parking slots claimed from a shared pool (default) or one private slot per workgroup"""
         self._check(self._lib.fheaes_k2_set_parking(self._h, 1 if claimed else 0))
+
+    def k2_set_forms(self, allow_pair: bool = True, allow_home: bool = True):
+        """test hook (fheaes_k2_set_forms): take the paired kernel and / or the 16-form's LDS-home variant away from this context, as a
+        refused occupancy query does; True restores "whatever the query allows", never more.  k2_plan reports what launches"""
+        self._check(self._lib.fheaes_k2_set_forms(self._h, 1 if allow_pair else 0, 1 if allow_home else 0))
 
     def k2_park_debug(self, initial=None, record: bool = False):
         """test hook (fheaes_k2_park_debug): claimed-mode paired launches start from the owner words `initial` (K2_PARK_SLOTS words;

@@ -67,6 +67,14 @@ int fheaes_k2_launch_plan(uint64_t m, uint32_t cu_count, uint32_t k, int *form, 
     *form = pl.form; *units_main = pl.units_main; *r_main = pl.r_main; *units_tail = pl.units_tail; *r_tail = pl.r_tail;
     return FHEAES_OK;
 }
+int fheaes_k2_launch_plan_forms(uint64_t m, uint32_t cu_count, uint32_t k, int allow_pair, int *form, uint64_t *units_main, uint32_t *r_main,
+                                uint64_t *units_tail, uint32_t *r_tail)
+{
+    if (!form || !units_main || !r_main || !units_tail || !r_tail || cu_count == 0 || m == 0 || (allow_pair != 0 && allow_pair != 1)) return FHEAES_ERR_INVALID;
+    const K2Plan pl = k2_plan(m, cu_count, k + 1, allow_pair == 1);
+    *form = pl.form; *units_main = pl.units_main; *r_main = pl.r_main; *units_tail = pl.units_tail; *r_tail = pl.r_tail;
+    return FHEAES_OK;
+}
 int fheaes_k2_context_plan(fheaes_ctx *ctx, uint64_t m, int *form, uint64_t *units_main, uint32_t *r_main, uint64_t *units_tail,
                            uint32_t *r_tail, char *kernel, size_t kernel_cap)
 {
@@ -86,6 +94,17 @@ int fheaes_k2_set_parking(fheaes_ctx *ctx, int claimed)
     if (claimed != 0 && claimed != 1) return ctx->fail(FHEAES_ERR_INVALID, "k2_set_parking: 1 = claimed slots, 0 = one private slot per workgroup (got %d)", claimed);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->k2_park_claim = claimed;
+    return FHEAES_OK;
+}
+int fheaes_k2_set_forms(fheaes_ctx *ctx, int allow_pair, int allow_home)
+{
+    if (!ctx) return FHEAES_ERR_INVALID;
+    CtxLock lock__(ctx);
+    if ((allow_pair != 0 && allow_pair != 1) || (allow_home != 0 && allow_home != 1))
+        return ctx->fail(FHEAES_ERR_INVALID, "k2_set_forms: each of allow_pair, allow_home is 0 or 1 (got %d, %d)", allow_pair, allow_home);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->k2_deny_pair = allow_pair == 0;
+    ctx->k2_deny_home = allow_home == 0;
     return FHEAES_OK;
 }
 int fheaes_k2_park_debug(fheaes_ctx *ctx, const uint32_t *initial_owner, int record)

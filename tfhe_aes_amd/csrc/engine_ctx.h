@@ -50,6 +50,7 @@ struct fheaes_ctx {
     uint32_t noise_level_seen = 0;
     int k2_home = -1;                    // blind rotation: 1 = the LDS-home form runs two workgroups per CU here (queried once), 0 = parked form
     int k2_pair_ok = -1;                 // 1 = the paired kernel (159,504 B of LDS per workgroup) can be resident on a CU here (queried once)
+    bool k2_deny_pair = false, k2_deny_home = false;     // test hook (fheaes_k2_set_forms): a form the queries allow is not used; never grants one
     int k2_park_claim = 1;               // paired kernel's parking slots: 1 = claimed from a shared pool (kern_blindrot_pair.h), 0 = one private slot per workgroup
     // test hook (fheaes_k2_park_debug): claimed-mode paired launches start from the owner words in ws_park_pattern instead of zeros, and
     // record {slot, XCC} per workgroup into ws_park_record; k2_park_record_n = grid of the last recorded launch since the hook was set

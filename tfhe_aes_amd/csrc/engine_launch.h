@@ -108,9 +108,10 @@ int launch_forward_fourier(fheaes_ctx *c, const uint64_t *in, uint64_t polys, do
 }
 
 // the paired kernel takes nearly all of a CU's LDS: where the runtime cannot place even one such workgroup (a driver that reserves LDS)
-// every batch falls back to the 16-form instead of failing the launch
+// every batch falls back to the 16-form instead of failing the launch.  fheaes_k2_set_forms can only take the form away: "queried and allowed"
 bool k2_pair_allowed(fheaes_ctx *c)
 {
+    if (c->k2_deny_pair) return false;
     if (c->k2_pair_ok < 0) {
         int per_cu = 0;
         const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, blind_rotate_pair_kernel<5, 5, 8, 3, 2>, BRP_THREADS, 0);
@@ -123,7 +124,7 @@ bool k2_pair_allowed(fheaes_ctx *c)
 // the 16-form's LDS-home variant takes exactly half of a CU's 160 KB per workgroup: use it only where the runtime really places two
 bool k2_home_allowed(fheaes_ctx *c)
 {
-    if (c->k1 != 5) return false;
+    if (c->k1 != 5 || c->k2_deny_home) return false;
     if (c->k2_home < 0) {
         int per_cu = 0;
         const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, blind_rotate16_kernel<5, 5, 8, 3, 2, true>, EP_THREADS, 0);
