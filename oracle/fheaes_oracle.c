@@ -647,6 +647,22 @@ static void vertical_packing(const orc_params *p, const double *ggswf, int nbits
     free(tree); free(ct1);
 }
 
+/* exported for the edge-word tests: vertical packing of ONE (LUT, output bit) on caller-made Fourier GGSWs, given in the engine's
+ * interleaved layout [nbits][cbs_level][k1][k1][256][2] (fheaes_vertical_packing_batch) and converted here to the planar one */
+void orc_vertical_packing(const orc_params *p, const double *ggsw_interleaved, int nbits, const uint64_t *lut, uint64_t *lwe_out)
+{
+    init_twiddles();
+    size_t polys = (size_t)nbits * p->cbs_level * K1(p) * K1(p);
+    double *gf = (double *)malloc(polys * NPOLY * sizeof(double));
+    for (size_t q = 0; q < polys; ++q)
+        for (int t = 0; t < HALF; ++t) {
+            gf[q * NPOLY + t] = ggsw_interleaved[q * NPOLY + 2 * t];
+            gf[q * NPOLY + HALF + t] = ggsw_interleaved[q * NPOLY + 2 * t + 1];
+        }
+    vertical_packing(p, gf, nbits, lut, lwe_out);
+    free(gf);
+}
+
 /* ------------------------------------------------------------------------- */
 /* many_wopbs_without_padding (many_wopbs.rs:31-116), batched                  */
 /* ------------------------------------------------------------------------- */

@@ -57,6 +57,7 @@ def lib():
             "orc_mod_switch": (ctypes.c_int, [ctypes.c_uint64]),
             "orc_polys_to_fourier": (None, [u64p, ctypes.c_int64, dp]),
             "orc_external_product_add": (None, [pp, ctypes.c_int, ctypes.c_int, u64p, u64p, u64p]),
+            "orc_vertical_packing": (None, [pp, dp, ctypes.c_int, u64p, u64p]),
             "orc_keys_create": (vp, [pp, u64p, u64p, u64p]),
             "orc_keys_destroy": (None, [vp]),
             "orc_keyswitch": (None, [vp, u64p, u64p]),
@@ -151,6 +152,22 @@ def external_product_add(p, level: int, base_log: int, ggsw_std: np.ndarray, d: 
     lib().orc_external_product_add(ctypes.byref(cp), level, base_log, _u64(np.ascontiguousarray(ggsw_std)),
                                    _u64(np.ascontiguousarray(d)), _u64(acc))
     return acc
+
+
+def vertical_packing(p, ggsw_f: np.ndarray, bits: int, lut: np.ndarray) -> np.ndarray:
+    """vertical packing of caller-made Fourier GGSWs (no keys): ggsw_f [bits][cbs_level][k+1][k+1][256][2] as the engine takes them,
+    lut [..., W] with W = max(2^bits, 512) words per (LUT, output bit) -> [..., kN+1]"""
+    cp = orc_params(p)
+    k1, W = p.k + 1, max(512, 1 << bits)
+    g = np.ascontiguousarray(ggsw_f, dtype=np.float64)
+    assert g.size == bits * p.cbs_level * k1 * k1 * 512
+    lut = np.ascontiguousarray(lut, dtype=np.uint64)
+    assert lut.shape[-1] == W
+    rows = lut.reshape(-1, W)
+    out = np.empty((rows.shape[0], p.big1), dtype=np.uint64)
+    for i in range(rows.shape[0]):
+        lib().orc_vertical_packing(ctypes.byref(cp), _p(g, ctypes.c_double), bits, _u64(rows[i]), _u64(out[i]))
+    return out.reshape(lut.shape[:-1] + (p.big1,))
 
 
 def tables():

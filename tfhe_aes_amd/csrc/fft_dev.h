@@ -242,7 +242,8 @@ __device__ __forceinline__ void nega_inv(double (&xr)[16], double (&xi)[16], con
 // of magic-number additions: a double in [2^20, 2^21) has ulp 2^-32, one in [2^-12, 2^-11) ulp 2^-64, so the low mantissa
 // bits of  w' + 1.5 * 2^20  and of  (w' - H 2^-32) + 1.5 * 2^-12  are H and l as two's complement integers.
 // 7 f64 instructions + 2 integer ones against 13 + 3 for the compiler's expansion of the definition; identical for every
-// double (checked against the definition on the CPU, 6e7 values around the tie / wrap / tiny cases).
+// double.  tests/test_gpu_edge_words.py runs the GPU instructions on the exact ties, w = +-1/2, w * 2^32 half-integer and the carry
+// from the low word (the constant-spectrum CMUX family of tests/edge_words.py) against an exact rational evaluation of the definition.
 // torus_acc(acc, v) = acc + torus_from_double(v).
 typedef uint32_t fhe_u32x2 __attribute__((ext_vector_type(2)));
 // torus_acc_scaled(acc, w): the same with w = v * 2^-72 already formed by the caller.  The scaling by a power of two commutes with every
