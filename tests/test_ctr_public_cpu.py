@@ -1,6 +1,6 @@
 """Public blocks and CTR with a public nonce, without a GPU: the sharing rule (fheaes_aes_public_plan) against the table of DESIGN.md
-section 7 and against a restatement of the rule written here, aes_clear.ctr_keystream against SP 800-38A F.5, and the shared schedule
-itself -- one WoPBS per distinct S-Box input, written with the CPU oracle's WoPBS and numpy wrapping sums -- against the oracle's own
+section 7 and against a restatement of the rule (aes_model.rule), aes_clear.ctr_keystream against SP 800-38A F.5, and the shared schedule
+itself (aes_model.shared_encrypt) -- one WoPBS per distinct S-Box input, written with the CPU oracle's WoPBS and numpy wrapping sums -- against the oracle's own
 aes_encrypt on trivial ciphertexts of the same blocks, word for word.  That last test pins the two facts the GPU path rests on: the
 rule is exact (equal ids have word-equal inputs), and a trivial ciphertext is a legal input."""
 import ctypes
@@ -8,54 +8,10 @@ import ctypes
 import numpy as np
 import pytest
 
-from test_aes_eqinv_cpu import own_client
-from test_aes_key_sizes_cpu import A2_KEY, A3_KEY, NR, AesModel
+from aes_model import TABLE, AesModel, rule, shared_encrypt
+from aes_vectors import BASE, F1_KEY, F1_PT, F5, F5_CTR, MASK128, NR, counters, own_client
 from tfhe_aes_amd import _native, aes_clear
 from tfhe_aes_amd.client import u128_to_bytes
-
-MASK128 = (1 << 128) - 1
-BASE = 0x00112233445566778899AABBCCDDEE00             # sixteen distinct bytes, the low one 00
-F5_CTR = 0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF
-F1_KEY = bytes.fromhex("2b7e151628aed2a6abf7158809cf4f3c")
-F1_PT = [0x6BC1BEE22E409F96E93D7E117393172A, 0xAE2D8A571E03AC9C9EB76FAC45AF8E51, 0x30C81C46A35CE411E5FBC1191A0A52EF,
-         0xF69F2445DF4F9B17AD2B417BE66C3710]
-# SP 800-38A F.5.1 / F.5.3 / F.5.5: key, first and last ciphertext block
-F5 = {128: (F1_KEY, 0x874D6191B620E3261BEF6864990DB6CE, 0x1E031DDA2FBE03D1792170A0F3009CEE),
-      192: (A2_KEY, 0x1ABC932417521CA24F2B0459FE7E6E0B, 0x4F78A7F6D29809585A97DAEC58C6B050),
-      256: (A3_KEY, 0x601EC313775789A5B7A7F504BBF3D228, 0xDFC9C58DB67AADA613C2DD08457941A6)}
-
-
-def counters(start, n):
-    return [(start + i) & MASK128 for i in range(n)]
-
-
-# blocks, key size -> (round 1, round 2, every later round, sum): byte-WoPBS, the table of the design document
-TABLE = [
-    (counters(BASE, 128), 128, (143, 524, 2048, 17051)),
-    (counters(BASE | 0xFA, 128), 128, (144, 528, 2048, 17056)),
-    (counters(BASE | 0xFFC0, 128), 128, (145, 532, 2048, 17061)),
-    (counters(BASE | 0xFF, 130), 128, (146, 536, 2080, 17322)),
-    (counters(BASE, 128), 256, (143, 524, 2048, 25243)),
-    (counters(BASE, 32), 128, (47, 140, 512, 4283)),
-    (counters(F5_CTR, 4), 128, (20, 32, 64, 564)),
-    ([BASE, BASE + 1, BASE, BASE + 1], 128, (17, 20, 32, 293)),
-]
-
-# the four sources of table_enc_round() for position p = 4 col + row (ShiftRows folded into MixColumns): row j of column col + j
-SOURCES = [[4 * ((col + j) % 4) + j for j in range(4)] for col in range(4) for _ in range(4)]
-
-
-def rule(blocks, nr):
-    """the sharing rule restated: ids per (block, position), round by round; returns (distinct ids per round, the ids of every round)"""
-    ids = [[(p, v) for p, v in enumerate(u128_to_bytes(b))] for b in blocks]
-    counts, all_ids = [], []
-    for _ in range(nr):
-        number = {}
-        ids = [[number.setdefault(i, len(number)) for i in blk] for blk in ids]       # equal tuples are one id
-        counts.append(len(number))
-        all_ids.append(ids)
-        ids = [[(p,) + tuple(blk[s] for s in SOURCES[p]) for p in range(16)] for blk in ids]
-    return counts, all_ids
 
 
 # ---- 1. the plan ---------------------------------------------------------------------------------------------------------------------
@@ -152,42 +108,6 @@ def test_trivial_bytes_are_mask_zero_body_bit(toy):
     assert np.array_equal(t[..., -1] >> np.uint64(63), [[[0] * 8, [1, 0, 1, 0, 0, 1, 0, 1]], [[1] * 8, [1, 0, 0, 0, 0, 0, 0, 0]]])
     assert not (t[..., -1] & np.uint64((1 << 63) - 1)).any()
     assert np.array_equal(c.decrypt_bytes(t), [[0x00, 0xA5], [0xFF, 0x01]])
-
-
-def shared_encrypt(model, rk, trivial, blocks):
-    """aes_encrypt of public blocks with one WoPBS per distinct S-Box input: the pools and index tables come from rule(), the WoPBS from
-    the oracle, the linear layers are numpy wrapping sums.  rk [Nr+1][16][8][kN+1]; trivial [n][16][8][kN+1]; returns the same shape."""
-    nr = rk.shape[0] - 1
-    counts, ids = rule(blocks, nr)
-    n = len(blocks)
-    # pool of round 1: one entry per distinct (position, byte value)
-    pool = np.zeros((counts[0],) + rk.shape[2:], dtype=np.uint64)
-    for b in range(n):
-        for p in range(16):
-            pool[ids[0][b][p]] = rk[0, p] + trivial[b, p]
-    evaluated = 0
-    for r in range(1, nr + 1):
-        luts = model.enc_round if r < nr else model.sbox
-        y = model.O.wopbs_batch(pool, luts)                                  # [pool][L][8][kN+1]
-        evaluated += len(pool)
-        if r == nr:
-            break
-        pool = np.zeros((counts[r],) + rk.shape[2:], dtype=np.uint64)
-        done = set()
-        for b in range(n):
-            for p in range(16):
-                u = ids[r][b][p]
-                if u not in done:                                            # MixColumns row p % 4: {2, 3, 1, 1} rotated, LUTs {S, 2S, 3S}
-                    done.add(u)
-                    for j, s in enumerate(SOURCES[p]):
-                        pool[u] += y[ids[r - 1][b][s], (1, 2, 0, 0)[(j - p % 4) % 4]]
-                    pool[u] += rk[r, p]
-    out = np.empty_like(trivial)
-    for b in range(n):
-        for col in range(4):
-            for row in range(4):
-                out[b, 4 * col + row] = y[ids[nr - 1][b][4 * ((col + row) % 4) + row], 0] + rk[nr, 4 * col + row]
-    return out, evaluated
 
 
 def test_shared_schedule_is_the_oracles_aes_encrypt_on_trivial_bytes(toy):

@@ -4,21 +4,12 @@ import numpy as np
 import pytest
 
 from conftest import Kit, sha
+from gpu_support import dev, host, opt_server, toy_server  # noqa: F401
 from oracle import oracle as orc
 from tfhe_aes_amd import PARAM_TOY, aes_clear
 from tfhe_aes_amd.server import Server, gen_lut
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def toy_server(toy):
-    return Server(toy.keys, device=0, engine=toy.engine())
-
-
-@pytest.fixture(scope="module")
-def opt_server(opt):
-    return Server(opt.keys, device=0, engine=opt.engine())
 
 
 @pytest.mark.parametrize("n_luts_set", [orc.LUTSET_SBOX, orc.LUTSET_ENC_ROUND, orc.LUTSET_DEC_MUL])
@@ -160,18 +151,14 @@ def test_batched_blocks_equal_per_block_oracle(toy, toy_server):
 
 
 def test_device_resident_tensors_match_host_path(toy, toy_server):
-    import torch
-
     c, p = toy.client, toy.params
     st = c.encrypt_u128(0x00112233445566778899AABBCCDDEEFF)
     rk = toy.oracle.aes_key_expansion(c.encrypt_u128(c.key))
-    host = toy_server.aes_encrypt(rk, st.copy())
-    d_rk = torch.from_numpy(rk.view(np.int64)).cuda()
-    d_st = torch.from_numpy(st.view(np.int64)).cuda()
-    torch.cuda.synchronize()
+    want = toy_server.aes_encrypt(rk, st.copy())
+    d_rk, d_st = dev(rk), dev(st)
     toy_server.aes_encrypt(d_rk, d_st)
     toy_server.synchronize()
-    assert np.array_equal(d_st.cpu().numpy().view(np.uint64), host)
+    assert np.array_equal(host(d_st), want)
     with pytest.raises(ValueError):
         toy_server.aes_encrypt(rk, d_st)                   # mixed memory spaces are refused
 
@@ -185,7 +172,7 @@ def test_device_tensors_with_host_luts(toy, toy_server):
     x = c.encrypt_bytes([0x11, 0xC4, 0x7E])
     luts = list(orc.build_lutset(orc.LUTSET_DEC_MUL))
     want = toy.oracle.wopbs_batch(x, np.stack(luts))
-    d_x = torch.from_numpy(x.view(np.int64)).cuda()
+    d_x = dev(x)
     outs = []
     for _ in range(3):                                       # several calls in flight, temporaries churn in between
         outs.append(toy_server.many_wopbs_without_padding(d_x, luts))
@@ -193,31 +180,26 @@ def test_device_tensors_with_host_luts(toy, toy_server):
         del junk
     toy_server.synchronize()
     for o in outs:
-        assert np.array_equal(o.cpu().numpy().view(np.uint64), want)
+        assert np.array_equal(host(o), want)
 
 
 def test_add_scalar_then_encrypt_enqueued_without_sync(toy, toy_server):
     """FHEAES_DEVICE calls only enqueue (fheaes.h): add_scalar + aes_encrypt on device tensors with ONE final
     synchronize equal the host-path results"""
-    import torch
-
     c = toy.client
     iv = 0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF
     rk = toy.oracle.aes_key_expansion(c.encrypt_u128(c.key))
     st = np.stack([c.encrypt_u128(iv)] * 2)
-    host = toy_server.aes_encrypt(rk, toy_server.add_scalar(st.copy(), [5, 0x1FF]))
-    d_rk = torch.from_numpy(rk.view(np.int64)).cuda()
-    d_a = torch.from_numpy(st.view(np.int64)).cuda()
-    d_b = torch.from_numpy(st.view(np.int64)).cuda()
-    torch.cuda.synchronize()
+    want = toy_server.aes_encrypt(rk, toy_server.add_scalar(st.copy(), [5, 0x1FF]))
+    d_rk, d_a, d_b = dev(rk), dev(st), dev(st)
     toy_server.add_scalar(d_a, [5, 0x1FF])
     toy_server.add_scalar(d_b, [0x1FF, 5])                   # second call reuses the pinned counter staging
     toy_server.aes_encrypt(d_rk, d_a)
     toy_server.aes_encrypt(d_rk, d_b)
     toy_server.synchronize()
-    a, b = d_a.cpu().numpy().view(np.uint64), d_b.cpu().numpy().view(np.uint64)
-    assert np.array_equal(a, host)
-    assert np.array_equal(b[0], host[1]) and np.array_equal(b[1], host[0])
+    a, b = host(d_a), host(d_b)
+    assert np.array_equal(a, want)
+    assert np.array_equal(b[0], want[1]) and np.array_equal(b[1], want[0])
 
 
 def test_concurrent_callers_are_serialised(toy, toy_server):

@@ -1,12 +1,14 @@
 """The equivalent inverse cipher on the MI355X (fheaes_aes_decryption_round_keys + fheaes_aes_decrypt_equivalent, FIPS-197 section
-5.3.5): word for word against the model of tests/test_aes_eqinv_cpu.py (the CPU oracle's WoPBS with composed LUTs, numpy wrapping sums),
+5.3.5): word for word against aes_model.AesModel (the CPU oracle's WoPBS with composed LUTs, numpy wrapping sums),
 decrypting to the plaintext at the toy set and at PARAM_OPT, within the noise guard, with the host / device / multi-context paths agreeing."""
 
 import numpy as np
 import pytest
 
+from aes_model import AesModel, noise
+from aes_vectors import FIPS_C1_CT, FIPS_C1_KEY, FIPS_C1_PT
 from conftest import sha
-from test_aes_eqinv_cpu import FIPS_C1_CT, FIPS_C1_KEY, FIPS_C1_PT, EqInvModel, own_client
+from gpu_support import dev, host, oc, opt_server, tc, toy_server  # noqa: F401
 from tfhe_aes_amd import _native, aes_clear
 from tfhe_aes_amd.server import Server, ServerGroup
 
@@ -15,43 +17,11 @@ pytestmark = pytest.mark.gpu
 IV = 0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF
 
 
-def _to_dev(a):
-    import torch
-
-    d = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-    torch.cuda.synchronize()
-    return d
-
-
-def _host(d):
-    return d.cpu().numpy().view(np.uint64)
-
-
-def _noise(c, words):
-    bits, ph = c.decrypt_bits(words, return_phase=True)
-    return (ph - (bits.astype(np.uint64) << np.uint64(63))).astype(np.int64)
-
-
-@pytest.fixture(scope="module")
-def toy_server(toy):
-    return Server(toy.keys, device=0, engine=toy.engine())
-
-
-@pytest.fixture(scope="module")
-def tc(toy):
-    return own_client(toy)
-
-
-@pytest.fixture(scope="module")
-def oc(opt):
-    return own_client(opt)
-
-
 @pytest.fixture(scope="module")
 def toy_case(toy, tc):
     """(round keys of the kit's AES key from the oracle, the model, the model's decryption round keys)"""
     w = toy.oracle.aes_key_expansion(tc.encrypt_u128(tc.key))
-    model = EqInvModel(toy.oracle)
+    model = AesModel(toy.oracle)
     return w, model, model.dec_round_keys(w)
 
 
@@ -69,7 +39,7 @@ def test_toy_three_blocks_word_exact(toy, toy_server, toy_case, tc):
     pts = [IV, 0, (1 << 128) - 1]
     st = np.stack([c.encrypt_u128(aes_clear.aes128_encrypt_block(key, v)) for v in pts])
     got = toy_server.aes_decrypt_equivalent(dw, st.copy())
-    assert np.array_equal(got, model.decrypt(dw, st))
+    assert np.array_equal(got, model.decrypt_equivalent(dw, st))
     assert [c.decrypt_u128(got[i]) for i in range(3)] == pts
 
 
@@ -78,14 +48,14 @@ def test_toy_host_and_device_memspace_agree(toy, toy_server, toy_case, tc):
     w, _, _ = toy_case
     st = np.stack([c.encrypt_u128(aes_clear.aes128_encrypt_block(c.key, IV + i)) for i in range(2)])
     dw = toy_server.aes_decryption_round_keys(w)
-    host = toy_server.aes_decrypt_equivalent(dw, st.copy())
-    d_w = _to_dev(w)                                                 # kept alive: the device calls are only enqueued
+    want = toy_server.aes_decrypt_equivalent(dw, st.copy())
+    d_w = dev(w)                                                     # kept alive: the device calls are only enqueued
     d_dw = toy_server.aes_decryption_round_keys(d_w)
-    d_st = _to_dev(st)
+    d_st = dev(st)
     toy_server.aes_decrypt_equivalent(d_dw, d_st)
     toy_server.synchronize()
-    assert np.array_equal(_host(d_dw), dw)
-    assert np.array_equal(_host(d_st), host)
+    assert np.array_equal(host(d_dw), dw)
+    assert np.array_equal(host(d_st), want)
     with pytest.raises(ValueError):
         toy_server.aes_decrypt_equivalent(dw, d_st)                  # mixed memory spaces are refused
 
@@ -138,7 +108,7 @@ def test_errors_before_keys_null_pointers_and_in_place_conversion(toy, toy_case,
     assert lib.fheaes_aes_decryption_round_keys(h, wp, wp, _native.HOST) == -1               # identical buffers: not in place
     assert b"overlap" in lib.fheaes_last_error(h)
     assert lib.fheaes_aes_decryption_round_keys(h, wp, wp + 8 * 16 * 8 * p.big1, _native.HOST) == -1     # overlapping ones
-    d_w = _to_dev(w)
+    d_w = dev(w)
     assert lib.fheaes_aes_decryption_round_keys(h, d_w.data_ptr(), d_w.data_ptr(), _native.DEVICE) == -1
     with pytest.raises(_native.FheAesError) as e:
         eng.aes_decryption_round_keys(w, w)
@@ -163,22 +133,17 @@ def test_toy_server_group_matches_one_context(toy, toy_server, toy_case, tc):
             s.engine.close()
 
 
-@pytest.fixture(scope="module")
-def opt_server(opt):
-    return Server(opt.keys, device=0, engine=opt.engine())
-
-
 def test_param_opt_one_block_word_exact(opt, opt_server, oc):
     """key conversion + one block at the reference's parameter set against the model (~450 byte WoPBS on the oracle)"""
     c = oc
     key, pt = c.key, 0x3243F6A8885A308D313198A2E0370734
     w = opt_server.aes_key_expansion(c.encrypt_u128(key))
-    model = EqInvModel(opt.oracle)
+    model = AesModel(opt.oracle)
     dw = opt_server.aes_decryption_round_keys(w)
     assert np.array_equal(dw, model.dec_round_keys(w))
     st = c.encrypt_u128(aes_clear.aes128_encrypt_block(key, pt))
     got = opt_server.aes_decrypt_equivalent(dw, st.copy())
-    assert np.array_equal(got, model.decrypt(dw, st))
+    assert np.array_equal(got, model.decrypt_equivalent(dw, st))
     assert c.decrypt_u128(got) == pt
 
 
@@ -189,34 +154,34 @@ def test_param_opt_32_block_shard_on_device(opt, opt_server, oc):
     c = oc
     key = c.key
     n = 32
-    d_rk = _to_dev(opt_server.aes_key_expansion(c.encrypt_u128(key)))
+    d_rk = dev(opt_server.aes_key_expansion(c.encrypt_u128(key)))
     d_dw = opt_server.aes_decryption_round_keys(d_rk)
     pts = [(IV + 0x9E3779B97F4A7C15 * i) & ((1 << 128) - 1) for i in range(n)]
     states = np.stack([c.encrypt_u128(aes_clear.aes128_encrypt_block(key, v)) for v in pts])
-    d_ref, d_eq = _to_dev(states), _to_dev(states)
+    d_ref, d_eq = dev(states), dev(states)
     opt_server.aes_decrypt(d_rk, d_ref)
     opt_server.aes_decrypt_equivalent(d_dw, d_eq)
     opt_server.synchronize()
-    ref, eq = _host(d_ref), _host(d_eq)
+    ref, eq = host(d_ref), host(d_eq)
     got_ref, got_eq = c.decrypt_bytes(ref), c.decrypt_bytes(eq)
     want = np.array([[(v >> (8 * (15 - b))) & 0xFF for b in range(16)] for v in pts], dtype=np.uint8)
     wrong = [i for i in range(n) if not np.array_equal(got_eq[i], want[i])]
     assert not wrong, "blocks wrong after aes_decrypt_equivalent: %s" % wrong
     assert np.array_equal(got_eq, got_ref)
     # output noise: one fresh WoPBS output + one round key, as test_128_ctr_blocks_param_opt bounds it
-    err = _noise(c, eq)
+    err = noise(c, eq)
     assert np.abs(err).max() < 1 << 59, "max |noise| = 2^%.1f" % np.log2(float(np.abs(err).max()))
     assert np.abs(err).std() < 1 << 56
     # dw[1..9] went through an identity WoPBS: the noise of one fresh WoPBS output, like the refreshed words of the key
     # expansion (server.rs:150); summed and not refreshed they would carry four (twice the standard deviation)
-    dw, rk = _host(d_dw), _host(d_rk)
+    dw, rk = host(d_dw), host(d_rk)
     assert np.array_equal(dw[0], rk[0]) and np.array_equal(dw[10], rk[10])
-    e_dw, e_rk = _noise(c, dw[1:10]), _noise(c, rk[1:11])
+    e_dw, e_rk = noise(c, dw[1:10]), noise(c, rk[1:11])
     assert np.abs(e_dw).max() < 1 << 59
     ratio = float(np.abs(e_dw).std()) / float(np.abs(e_rk).std())
     assert 0.7 < ratio < 1.4, "noise std of dw[1..9] / fresh round keys = %.2f" % ratio
     # determinism: a second launch from the same input
-    d_eq2 = _to_dev(states)
+    d_eq2 = dev(states)
     opt_server.aes_decrypt_equivalent(d_dw, d_eq2)
     opt_server.synchronize()
-    assert sha(_host(d_eq2)) == sha(eq)
+    assert sha(host(d_eq2)) == sha(eq)

@@ -1,60 +1,22 @@
 """AES-192 and AES-256 on the MI355X (the five fheaes_aes_*_bits entry points, FIPS-197 with Nk = 6 / 8 and Nr = 12 / 14): word for word
-against the model of tests/test_aes_key_sizes_cpu.py (the CPU oracle's WoPBS, numpy wrapping sums; pinned to the oracle's own AES-128
-there), the FIPS-197 appendix C vectors end to end, the 128-bit case against the entry points that have no key-size argument, errors,
+against aes_model.AesModel (the CPU oracle's WoPBS, numpy wrapping sums; pinned to the oracle's own AES-128 in
+test_aes_key_sizes_cpu.py), the FIPS-197 appendix C vectors end to end, the 128-bit case against the entry points that have no key-size argument, errors,
 the noise guard, several contexts, and 32 resident blocks per key size at PARAM_OPT."""
 
 import numpy as np
 import pytest
 
+from aes_model import AesModel, noise
+from aes_vectors import A2_KEY, A3_KEY, FIPS_C, FIPS_C_PT, MASK128, NR, block_bytes, key_words
 from conftest import sha
-from test_aes_eqinv_cpu import own_client
-from test_aes_key_sizes_cpu import FIPS_C, FIPS_C_PT, NR, AesModel, key_words
+from gpu_support import dev, host, oc, opt_server, tc, toy_server  # noqa: F401
 from tfhe_aes_amd import _native, aes_clear
 from tfhe_aes_amd.server import Server, ServerGroup
 
 pytestmark = pytest.mark.gpu
 
 IV = 0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF
-MASK128 = (1 << 128) - 1
-# keys of the PARAM_OPT tests: the NIST SP 800-38A ones (F.1.3, F.1.5)
-OPT_KEYS = {192: bytes.fromhex("8e73b0f7da0e6452c810f32b809079e562f8ead2522c6b7b"),
-            256: bytes.fromhex("603deb1015ca71be2b73aef0857d77811f352c073b6108d72d9810a30914dff4")}
-
-
-def _to_dev(a):
-    import torch
-
-    d = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-    torch.cuda.synchronize()
-    return d
-
-
-def _host(d):
-    return d.cpu().numpy().view(np.uint64)
-
-
-def _noise(c, words):
-    bits, ph = c.decrypt_bits(words, return_phase=True)
-    return (ph - (bits.astype(np.uint64) << np.uint64(63))).astype(np.int64)
-
-
-def _block_bytes(values):
-    return np.array([[(v >> (8 * (15 - b))) & 0xFF for b in range(16)] for v in values], dtype=np.uint8)
-
-
-@pytest.fixture(scope="module")
-def toy_server(toy):
-    return Server(toy.keys, device=0, engine=toy.engine())
-
-
-@pytest.fixture(scope="module")
-def tc(toy):
-    return own_client(toy)
-
-
-@pytest.fixture(scope="module")
-def oc(opt):
-    return own_client(opt)
+OPT_KEYS = {192: A2_KEY, 256: A3_KEY}                   # keys of the PARAM_OPT tests: the NIST SP 800-38A ones (F.1.3, F.1.5)
 
 
 @pytest.fixture(scope="module")
@@ -126,23 +88,23 @@ def test_toy_host_arrays_and_resident_tensors_agree(toy, toy_server, toy_cases, 
     dec = toy_server.aes_decrypt(rk, enc.copy())
     dw = toy_server.aes_decryption_round_keys(rk)
     eq = toy_server.aes_decrypt_equivalent(dw, enc.copy())
-    d_ek = _to_dev(ek)                                               # kept alive: the device calls are only enqueued
+    d_ek = dev(ek)                                                   # kept alive: the device calls are only enqueued
     d_rk = toy_server.aes_key_expansion(d_ek)
-    d_enc = _to_dev(st)
+    d_enc = dev(st)
     toy_server.aes_encrypt(d_rk, d_enc)
     toy_server.synchronize()
-    d_dec = _to_dev(_host(d_enc))
+    d_dec = dev(host(d_enc))
     toy_server.aes_decrypt(d_rk, d_dec)
     d_dw = toy_server.aes_decryption_round_keys(d_rk)
-    d_eq = _to_dev(_host(d_enc))
+    d_eq = dev(host(d_enc))
     toy_server.aes_decrypt_equivalent(d_dw, d_eq)
     toy_server.synchronize()
     assert tuple(d_rk.shape) == rk.shape and tuple(d_dw.shape) == dw.shape
-    assert np.array_equal(_host(d_rk), rk)
-    assert np.array_equal(_host(d_enc), enc)
-    assert np.array_equal(_host(d_dec), dec)
-    assert np.array_equal(_host(d_dw), dw)
-    assert np.array_equal(_host(d_eq), eq)
+    assert np.array_equal(host(d_rk), rk)
+    assert np.array_equal(host(d_enc), enc)
+    assert np.array_equal(host(d_dec), dec)
+    assert np.array_equal(host(d_dw), dw)
+    assert np.array_equal(host(d_eq), eq)
     with pytest.raises(ValueError):
         toy_server.aes_encrypt(rk, d_eq)                             # mixed memory spaces are refused
 
@@ -176,11 +138,11 @@ def test_bits_entry_points_at_128_give_the_words_of_the_old_ones(toy, tc):
     assert np.array_equal(eq_new, eq_old)
     assert [tc.decrypt_u128(eq_old[i]) for i in range(2)] == [IV, IV + 1]
     # ... and on resident tensors
-    d_rk, d_a, d_b = _to_dev(rk_old), _to_dev(st), _to_dev(st)
+    d_rk, d_a, d_b = dev(rk_old), dev(st), dev(st)
     eng.aes_encrypt(d_rk, d_a, 2)
     eng.aes_encrypt_bits(d_rk, 128, d_b, 2)
     eng.synchronize()
-    assert np.array_equal(_host(d_a), enc_old) and np.array_equal(_host(d_b), enc_old)
+    assert np.array_equal(host(d_a), enc_old) and np.array_equal(host(d_b), enc_old)
 
 
 # ---- errors ----------------------------------------------------------------------------------------------------------------------------
@@ -231,7 +193,7 @@ def test_errors_key_bits_missing_keys_overlap_and_shapes(toy, toy_server, toy_ca
     assert lib.fheaes_aes_decryption_round_keys_bits(h, a, 256, a + 12 * rkw * 8, _native.HOST) == -1
     assert b"overlap" in lib.fheaes_last_error(h)
     assert lib.fheaes_aes_decryption_round_keys_bits(h, a + 12 * rkw * 8, 256, a, _native.HOST) == -1
-    d_w = _to_dev(w)
+    d_w = dev(w)
     assert lib.fheaes_aes_decryption_round_keys_bits(h, d_w.data_ptr(), 256, d_w.data_ptr(), _native.DEVICE) == -1
     assert np.array_equal(both[:15 * rkw], w.reshape(-1))            # nothing was written
     # shapes that are no AES key size never reach the library
@@ -291,11 +253,6 @@ def test_toy_server_group_matches_one_context_at_256_bits(toy, toy_server, toy_c
 
 
 # ---- PARAM_OPT ---------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def opt_server(opt):
-    return Server(opt.keys, device=0, engine=opt.engine())
-
-
 def test_param_opt_aes256_key_expansion_and_one_block_word_exact(opt, opt_server, oc):
     """at the reference's parameter set against the model: 65 four-byte and 14 sixteen-byte WoPBS calls on the oracle (484 byte WoPBS)"""
     key, pt = OPT_KEYS[256], 0x3243F6A8885A308D313198A2E0370734
@@ -316,41 +273,41 @@ def test_param_opt_32_blocks_on_device(opt, opt_server, oc, bits):
     Every block decrypts to the FIPS-197 ciphertext, then to its plaintext; the outputs carry the noise of one fresh WoPBS output plus
     one round key (the last round does not depend on Nr: the bounds of test_gpu_aes_eqinv.py); a second launch gives the same words."""
     c, key, n = oc, OPT_KEYS[bits], 32
-    d_ek = _to_dev(c.encrypt_aes_key(key))
+    d_ek = dev(c.encrypt_aes_key(key))
     d_rk = opt_server.aes_key_expansion(d_ek)
     d_dw = opt_server.aes_decryption_round_keys(d_rk)
     pts = [(IV + 0x9E3779B97F4A7C15 * i) & MASK128 for i in range(n)]
     cts = [aes_clear.aes_encrypt_block(key, v) for v in pts]
     states = np.stack([c.encrypt_u128(v) for v in pts])
-    d_enc = _to_dev(states)
+    d_enc = dev(states)
     opt_server.aes_encrypt(d_rk, d_enc)
     opt_server.synchronize()
     assert tuple(d_rk.shape) == (NR[bits] + 1, 16, 8, opt.params.big1)
-    assert np.array_equal(c.decrypt_bytes(_host(d_rk)), key_words(aes_clear.expand_key(key)))
-    enc = _host(d_enc)
+    assert np.array_equal(c.decrypt_bytes(host(d_rk)), key_words(aes_clear.expand_key(key)))
+    enc = host(d_enc)
     got = c.decrypt_bytes(enc)
-    want = _block_bytes(cts)
+    want = block_bytes(cts)
     wrong = [i for i in range(n) if not np.array_equal(got[i], want[i])]
     assert not wrong, "blocks wrong after aes_encrypt: %s" % wrong
-    d_eq, d_ref = _to_dev(enc), _to_dev(enc[:4])
+    d_eq, d_ref = dev(enc), dev(enc[:4])
     opt_server.aes_decrypt_equivalent(d_dw, d_eq)
     opt_server.aes_decrypt(d_rk, d_ref)
     opt_server.synchronize()
-    eq, ref = _host(d_eq), _host(d_ref)
+    eq, ref = host(d_eq), host(d_ref)
     got = c.decrypt_bytes(eq)
-    want = _block_bytes(pts)
+    want = block_bytes(pts)
     wrong = [i for i in range(n) if not np.array_equal(got[i], want[i])]
     assert not wrong, "blocks wrong after aes_decrypt_equivalent: %s" % wrong
     assert np.array_equal(c.decrypt_bytes(ref), want[:4])
     for name, words in (("aes_encrypt", enc), ("aes_decrypt_equivalent", eq), ("aes_decrypt", ref)):
-        err = np.abs(_noise(c, words))
+        err = np.abs(noise(c, words))
         print("AES-%d %s: max |noise| = 2^%.2f, std = 2^%.2f" % (bits, name, np.log2(float(err.max())), np.log2(float(err.std()))))
         assert err.max() < 1 << 59, "%s: max |noise| = 2^%.1f" % (name, np.log2(float(err.max())))
         assert err.std() < 1 << 56, "%s: std = 2^%.1f" % (name, np.log2(float(err.std())))
     # determinism: a second launch from the same inputs
-    d_enc2, d_eq2 = _to_dev(states), _to_dev(enc)
+    d_enc2, d_eq2 = dev(states), dev(enc)
     opt_server.aes_encrypt(d_rk, d_enc2)
     opt_server.aes_decrypt_equivalent(d_dw, d_eq2)
     opt_server.synchronize()
-    assert sha(_host(d_enc2)) == sha(enc)
-    assert sha(_host(d_eq2)) == sha(eq)
+    assert sha(host(d_enc2)) == sha(enc)
+    assert sha(host(d_eq2)) == sha(eq)

@@ -7,9 +7,9 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-from test_aes_eqinv_cpu import own_client
-from test_aes_key_sizes_cpu import NR
-from test_ctr_public_cpu import BASE, F1_PT, F5, F5_CTR, MASK128, counters
+from aes_model import noise
+from aes_vectors import BASE, F1_PT, F5, F5_CTR, MASK128, NR, block_bytes, counters
+from gpu_support import dev, host, oc, opt_rk128, opt_server, tc, toy_server  # noqa: F401
 from tfhe_aes_amd import _native, aes_clear
 from tfhe_aes_amd.client import u128_to_bytes
 from tfhe_aes_amd.server import Server, ServerGroup
@@ -26,49 +26,13 @@ CASES = {
 }
 
 
-def _to_dev(a):
-    import torch
-
-    d = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-    torch.cuda.synchronize()
-    return d
-
-
-def _host(d):
-    return d.cpu().numpy().view(np.uint64)
-
-
-def _noise(c, words):
-    bits, ph = c.decrypt_bits(words, return_phase=True)
-    return (ph - (bits.astype(np.uint64) << np.uint64(63))).astype(np.int64)
-
-
 def _trivial(c, blocks):
     return c.trivial_bytes([u128_to_bytes(b) for b in blocks])
-
-
-def _block_bytes(values):
-    return np.array([u128_to_bytes(v) for v in values], dtype=np.uint8)
 
 
 def _xor_clear(c, words, data):
     """what folding clear data into ciphertext words means: bit << 63 added to the bodies"""
     return words + _trivial(c, data)
-
-
-@pytest.fixture(scope="module")
-def toy_server(toy):
-    return Server(toy.keys, device=0, engine=toy.engine())
-
-
-@pytest.fixture(scope="module")
-def tc(toy):
-    return own_client(toy)
-
-
-@pytest.fixture(scope="module")
-def oc(opt):
-    return own_client(opt)
 
 
 @pytest.fixture(scope="module")
@@ -87,7 +51,7 @@ def test_toy_public_blocks_are_aes_encrypt_on_trivial_bytes(toy, toy_server, toy
     want = toy_server.aes_encrypt(rk, _trivial(tc, blocks))
     assert np.array_equal(got, want), "%d words differ" % int((got != want).sum())
     key = F5[bits][0]
-    assert np.array_equal(tc.decrypt_bytes(got), _block_bytes([aes_clear.aes_encrypt_block(key, b) for b in blocks]))
+    assert np.array_equal(tc.decrypt_bytes(got), block_bytes([aes_clear.aes_encrypt_block(key, b) for b in blocks]))
     as_bytes = toy_server.aes_encrypt_public(rk, [b.to_bytes(16, "big") for b in blocks])
     assert np.array_equal(as_bytes, got)
 
@@ -95,15 +59,15 @@ def test_toy_public_blocks_are_aes_encrypt_on_trivial_bytes(toy, toy_server, toy
 @pytest.mark.parametrize("bits", [128, 192, 256])
 def test_toy_host_arrays_and_resident_tensors_agree(toy, toy_server, toy_rk, tc, bits):
     rk, blocks = toy_rk[bits], CASES["wrap5"]
-    host = toy_server.aes_encrypt_public(rk, blocks)
-    host_ctr = toy_server.aes_ctr(rk, blocks[0], 0, 5, data=F1_PT + [0])
-    d_rk = _to_dev(rk)
+    want = toy_server.aes_encrypt_public(rk, blocks)
+    want_ctr = toy_server.aes_ctr(rk, blocks[0], 0, 5, data=F1_PT + [0])
+    d_rk = dev(rk)
     d_out = toy_server.aes_encrypt_public(d_rk, blocks)
     d_ctr = toy_server.aes_ctr(d_rk, blocks[0], 0, 5, data=F1_PT + [0])
     toy_server.synchronize()
-    assert d_out.is_cuda and tuple(d_out.shape) == host.shape
-    assert np.array_equal(_host(d_out), host)
-    assert np.array_equal(_host(d_ctr), host_ctr)
+    assert d_out.is_cuda and tuple(d_out.shape) == want.shape
+    assert np.array_equal(host(d_out), want)
+    assert np.array_equal(host(d_ctr), want_ctr)
 
 
 @pytest.mark.parametrize("bits", [128, 192, 256])
@@ -113,11 +77,11 @@ def test_toy_ctr_is_public_encryption_of_the_counter_blocks_plus_clear_data(toy,
     blocks = counters(iv, 5)
     stream = toy_server.aes_ctr(rk, iv, 0, 5)
     assert np.array_equal(stream, toy_server.aes_encrypt_public(rk, blocks))
-    assert np.array_equal(tc.decrypt_bytes(stream), _block_bytes(aes_clear.ctr_keystream(key, iv, 0, 5)))
+    assert np.array_equal(tc.decrypt_bytes(stream), block_bytes(aes_clear.ctr_keystream(key, iv, 0, 5)))
     data = F1_PT + [MASK128]
     ct = toy_server.aes_ctr(rk, iv, 0, 5, data=data)
     assert np.array_equal(ct, _xor_clear(tc, stream, data))
-    assert np.array_equal(tc.decrypt_bytes(ct), _block_bytes([k ^ d for k, d in zip(aes_clear.ctr_keystream(key, iv, 0, 5), data)]))
+    assert np.array_equal(tc.decrypt_bytes(ct), block_bytes([k ^ d for k, d in zip(aes_clear.ctr_keystream(key, iv, 0, 5), data)]))
     # first_block continues the stream; iv as bytes, data as one bytes object
     tail = toy_server.aes_ctr(rk, iv.to_bytes(16, "big"), 3, 2, data=b"".join(d.to_bytes(16, "big") for d in data[3:]))
     assert np.array_equal(tail, ct[3:])
@@ -215,20 +179,6 @@ def test_errors(toy, toy_server, toy_rk, tc):
 
 
 # ---- PARAM_OPT ---------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def opt_server(opt):
-    return Server(opt.keys, device=0, engine=opt.engine())
-
-
-@pytest.fixture(scope="module")
-def opt_rk128(opt_server, oc):
-    """resident round keys of the F.1.1 key, expanded on the GPU"""
-    d_ek = _to_dev(oc.encrypt_aes_key(F5[128][0]))
-    d_rk = opt_server.aes_key_expansion(d_ek)
-    opt_server.synchronize()
-    return d_rk
-
-
 @pytest.mark.parametrize("bits", [128, 192, 256])
 def test_param_opt_sp800_38a_f5_end_to_end(opt, opt_server, oc, bits):
     """F.5.1 / F.5.3 / F.5.5: the key expanded on the GPU, aes_ctr with the NIST plaintext as data, the client decrypts the NIST ciphertext"""
@@ -239,7 +189,7 @@ def test_param_opt_sp800_38a_f5_end_to_end(opt, opt_server, oc, bits):
     got = oc.decrypt_bytes(ct)
     want = [k ^ p for k, p in zip(aes_clear.ctr_keystream(key, F5_CTR, 0, 4), F1_PT)]
     assert want[0] == first and want[3] == last
-    assert np.array_equal(got, _block_bytes(want))
+    assert np.array_equal(got, block_bytes(want))
 
 
 def test_param_opt_128_aligned_blocks_are_aes_encrypt_on_the_trivial_state(opt, opt_server, opt_rk128, oc):
@@ -250,16 +200,16 @@ def test_param_opt_128_aligned_blocks_are_aes_encrypt_on_the_trivial_state(opt, 
     blocks = counters(BASE, n)
     assert sum(_native.aes_public_plan(blocks)) == 17051
     d_out = opt_server.aes_ctr(opt_rk128, BASE, 0, n)
-    d_ref = _to_dev(_trivial(oc, blocks))
+    d_ref = dev(_trivial(oc, blocks))
     opt_server.aes_encrypt(opt_rk128, d_ref)
     opt_server.synchronize()
-    out, ref = _host(d_out), _host(d_ref)
+    out, ref = host(d_out), host(d_ref)
     assert np.array_equal(out, ref), "%d words differ" % int((out != ref).sum())
     got = oc.decrypt_bytes(out)
-    want = _block_bytes(aes_clear.ctr_keystream(key, BASE, 0, n))
+    want = block_bytes(aes_clear.ctr_keystream(key, BASE, 0, n))
     wrong = [i for i in range(n) if not np.array_equal(got[i], want[i])]
     assert not wrong, "blocks wrong: %s" % wrong
-    err = np.abs(_noise(oc, out))
+    err = np.abs(noise(oc, out))
     print("aes_ctr, 128 blocks: max |noise| = 2^%.2f, std = 2^%.2f" % (np.log2(float(err.max())), np.log2(float(err.std()))))
     assert err.max() < 1 << 59, "max |noise| = 2^%.1f" % np.log2(float(err.max()))
     assert err.std() < 1 << 56, "std = 2^%.1f" % np.log2(float(err.std()))
@@ -274,9 +224,9 @@ def test_param_opt_server_group_of_two_contexts_equals_one(opt, opt_server, opt_
     group = ServerGroup(opt.keys, devices=(0, 0))
     try:
         d_two = group.aes_ctr(opt_rk128, BASE | 0xF0, 0, n, data=data)
-        assert np.array_equal(_host(d_two), _host(d_one))
+        assert np.array_equal(host(d_two), host(d_one))
     finally:
         for s in group.servers:
             s.engine.close()
     want = [k ^ d for k, d in zip(aes_clear.ctr_keystream(F5[128][0], BASE | 0xF0, 0, n), data)]
-    assert np.array_equal(oc.decrypt_bytes(_host(d_one)), _block_bytes(want))
+    assert np.array_equal(oc.decrypt_bytes(host(d_one)), block_bytes(want))

@@ -17,19 +17,11 @@ import pytest
 
 import edge_words as ew
 from edge_words import PARAM_EDGE
+from gpu_support import FORMS, HOME, LATENCY, PAIR, PARKED, dev, filled, guarded, guards_intact, host, plan_tuple, settled
 from oracle import oracle as orc
 from tfhe_aes_amd import PARAM_TOY, _native
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = -0x5A5A5A5A5A5A5A5B      # an int64 bit pattern no kernel is asked to write (test_gpu_k2_shapes.py)
-GUARD = 2
-
-LATENCY = "blind_rotate_latency_kernel<5,5,8>"
-HOME = "blind_rotate16_kernel<5,5,8,3,2,true>"
-PARKED = "blind_rotate16_kernel<5,5,8,3,2,false>"
-PAIR = "blind_rotate_pair_kernel<5,5,8,3,2>"
-FORMS = {"default": (True, True), "pair denied": (False, True), "home denied": (True, False), "both denied": (False, False)}
 
 # (body, forms, m, plan at 256 CUs, kernel, ciphertexts per unit): one unit size per launch, so that row j sits in slot j mod unit
 K2_BODIES = [
@@ -43,40 +35,6 @@ K2_BODIES = [
 ]
 
 
-def _plan_tuple(pl):
-    return (pl["form"], pl["units_main"], pl["r_main"], pl["units_tail"], pl["r_tail"])
-
-
-def _settled(t):
-    """t, once everything queued on torch's stream is done: a context runs on a non-blocking stream of its own, which does not wait for
-    the fill, copy or gather that made one of its arguments"""
-    import torch
-
-    torch.cuda.synchronize()
-    return t
-
-
-def _dev(a):
-    import torch
-
-    return _settled(torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda())
-
-
-def _guarded(rows, words):
-    import torch
-
-    buf = _settled(torch.full((rows + 2 * GUARD, words), SENTINEL, dtype=torch.int64, device="cuda"))
-    return buf, buf[GUARD:GUARD + rows]
-
-
-def _guards_intact(buf):
-    return bool((buf[:GUARD] == SENTINEL).all().item()) and bool((buf[-GUARD:] == SENTINEL).all().item())
-
-
-def _host(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
 def _bits(a):
     return np.ascontiguousarray(a).view(np.uint64)
 
@@ -85,11 +43,9 @@ def _bits(a):
 @pytest.fixture(scope="module")
 def edge_engine():
     """a PARAM_EDGE context and zero KSK / PFPKSK on the device (K2 needs keys uploaded, not these two: 630 MB that never cross PCIe)"""
-    import torch
-
     p = PARAM_EDGE
     E = _native.Engine(p, device=0)
-    zeros = _settled((torch.zeros(p.ksk_words, dtype=torch.int64, device="cuda"), torch.zeros(p.pfpksk_words, dtype=torch.int64, device="cuda")))
+    zeros = filled((p.ksk_words,), 0), filled((p.pfpksk_words,), 0)
     yield E, zeros
     E.close()
 
@@ -118,10 +74,10 @@ class K2Edge:
         self.x, _ = ew.k2_rows(p.n)
         self.rows = self.x.shape[0]
         assert self.rows % 12 == 0                                   # a cyclic shift keeps every row's slot residue for units of 2, 3, 4, 6
-        E.upload_keys(zeros[0], _dev(bsk), zeros[1])
+        E.upload_keys(zeros[0], dev(bsk), zeros[1])
         oracle = orc.Oracle(p, np.zeros(1, dtype=np.uint64), bsk, np.zeros(1, dtype=np.uint64))
         self.want = oracle.cbs_pbs(self.x)
-        self.x_d, self.want_d = _dev(self.x), _dev(self.want)
+        self.x_d, self.want_d = dev(self.x), dev(self.want)
 
 
 @pytest.fixture(scope="module", params=["trivial", "random", "extreme"])
@@ -151,16 +107,16 @@ def test_k2_edge_rows_through_every_kernel_body(body, forms, m, plan, kernel, un
     try:
         E.k2_set_forms(*FORMS[forms])
         pl = E.k2_plan(m)
-        assert _plan_tuple(pl) == plan and pl["kernel"].startswith(kernel), pl               # the launch this case exists for
+        assert plan_tuple(pl) == plan and pl["kernel"].startswith(kernel), pl                # the launch this case exists for
         for o in range(unit):
             for i in range(-(-n_rows // m)):
                 idx = (np.arange(m) + i * m - o) % n_rows
-                idx_d = torch.from_numpy(idx).cuda()
-                buf, out = _guarded(m, p.big1)
-                rows_d = _settled(k2edge.x_d[idx_d].contiguous())
+                idx_d = dev(idx)
+                buf, out = guarded(m, p.big1)
+                rows_d = settled(k2edge.x_d[idx_d].contiguous())
                 E.cbs_pbs_batch(rows_d, out, m)
                 E.synchronize()
-                assert _guards_intact(buf), "a store outside the %d output rows" % m
+                assert guards_intact(buf), "a store outside the %d output rows" % m
                 if not torch.equal(out, k2edge.want_d[idx_d]):
                     bad = torch.nonzero((out != k2edge.want_d[idx_d]).any(dim=1)).flatten().cpu().numpy()
                     raise AssertionError("%s key, %s, offset %d, launch %d: %d of %d rows differ from the oracle, edge rows %s ..."
@@ -181,14 +137,14 @@ def test_k2_edge_rows_on_the_toy_kernels(toy_engine):
     bsk = rng.integers(0, 1 << 64, p.bsk_words, dtype=np.uint64)
     E.upload_keys(ksk, bsk, pf)
     pl = E.k2_plan(m)
-    assert pl["kernel"].startswith("blind_rotate16_kernel<2,5,8,8") and _plan_tuple(pl) == (1, m // 8, 8, 0, 0), pl
-    buf, out = _guarded(m, p.big1)
-    x_d = _dev(x)                                               # named: alive until the context's stream is done with it
+    assert pl["kernel"].startswith("blind_rotate16_kernel<2,5,8,8") and plan_tuple(pl) == (1, m // 8, 8, 0, 0), pl
+    buf, out = guarded(m, p.big1)
+    x_d = dev(x)                                                # named: alive until the context's stream is done with it
     E.cbs_pbs_batch(x_d, out, m)
     E.synchronize()
     want = orc.Oracle(p, ksk, bsk, pf).cbs_pbs(x)
-    got = _host(out)
-    assert _guards_intact(buf)
+    got = host(out)
+    assert guards_intact(buf)
     assert np.array_equal(got, want), np.flatnonzero((got != want).any(axis=1))[:16]
 
 
@@ -210,14 +166,14 @@ def test_key_switches_toy_edge_inputs_and_keys(pattern, toy_engine):
     o = orc.Oracle(p, ksk, bsk, pf)
     x1, _ = ew.ks_inputs(p, "K1", m)
     x3, _ = ew.ks_inputs(p, "K3", m)
-    x1_d, x3_d = _dev(x1), _dev(x3)
-    buf1, out1 = _guarded(m, p.n + 1)
-    buf3, out3 = _guarded(m, (p.k + 1) ** 2 * p.N)
+    x1_d, x3_d = dev(x1), dev(x3)
+    buf1, out1 = guarded(m, p.n + 1)
+    buf3, out3 = guarded(m, (p.k + 1) ** 2 * p.N)
     E.keyswitch_batch(x1_d, out1, m)
     E.pfpks_batch(x3_d, out3, m)
     E.synchronize()
-    got1, got3 = _host(out1), _host(out3).reshape(m, p.k + 1, (p.k + 1) * p.N)
-    assert _guards_intact(buf1) and _guards_intact(buf3)
+    got1, got3 = host(out1), host(out3).reshape(m, p.k + 1, (p.k + 1) * p.N)
+    assert guards_intact(buf1) and guards_intact(buf3)
     want1, want3 = o.keyswitch(x1), o.pfpks(x3)
     assert np.array_equal(got1, want1), np.flatnonzero((got1 != want1).any(axis=1))[:16]
     assert np.array_equal(got3, want3), np.flatnonzero((got3 != want3).any(axis=(1, 2)))[:16]
@@ -237,14 +193,14 @@ def test_key_switches_k4_edge_inputs_mixture_keys():
     E = _native.Engine(p, device=0)
     try:
         E.upload_keys(ksk, bsk, pf)
-        x1_d, x3_d = _dev(x1), _dev(x3)
-        buf1, out1 = _guarded(m, p.n + 1)
-        buf3, out3 = _guarded(m, (p.k + 1) ** 2 * p.N)
+        x1_d, x3_d = dev(x1), dev(x3)
+        buf1, out1 = guarded(m, p.n + 1)
+        buf3, out3 = guarded(m, (p.k + 1) ** 2 * p.N)
         E.keyswitch_batch(x1_d, out1, m)
         E.pfpks_batch(x3_d, out3, m)
         E.synchronize()
-        got1, got3 = _host(out1), _host(out3).reshape(m, p.k + 1, (p.k + 1) * p.N)
-        assert _guards_intact(buf1) and _guards_intact(buf3)
+        got1, got3 = host(out1), host(out3).reshape(m, p.k + 1, (p.k + 1) * p.N)
+        assert guards_intact(buf1) and guards_intact(buf3)
     finally:
         E.close()
     o = orc.Oracle(p, ksk, bsk, pf)
@@ -258,13 +214,13 @@ def test_key_switches_k4_edge_inputs_mixture_keys():
 def test_k4_edge_polynomials(k, edge_engine, toy_engine):
     E = edge_engine[0] if k == 4 else toy_engine
     x, _ = ew.k4_polys()
-    buf, out = _guarded(x.shape[0], 512)
-    x_d = _dev(x)
+    buf, out = guarded(x.shape[0], 512)
+    x_d = dev(x)
     E.forward_fourier_batch(x_d, out, x.shape[0])
     E.synchronize()
     want = orc.polys_to_fourier(x)
-    assert _guards_intact(buf)
-    got = _host(out)
+    assert guards_intact(buf)
+    got = host(out)
     assert np.array_equal(got, _bits(want).reshape(x.shape[0], 512)), np.flatnonzero((got != _bits(want).reshape(x.shape[0], 512)).any(axis=1))
 
 
@@ -277,12 +233,12 @@ def _vp_oracle(p, ggsw_f, luts, per_input):
 def _vp_engine(E, p, ggsw_f, luts, n_luts, per_input):
     n_inputs, bits = ggsw_f.shape[0], ggsw_f.shape[1]
     rows = n_inputs * n_luts * bits
-    buf, out = _guarded(rows, p.big1)
-    ggsw_d, luts_d = _dev(_bits(ggsw_f)), _dev(luts)
+    buf, out = guarded(rows, p.big1)
+    ggsw_d, luts_d = dev(_bits(ggsw_f)), dev(luts)
     E.vertical_packing_batch(ggsw_d, n_inputs, bits, luts_d, n_luts, per_input, out)
     E.synchronize()
-    assert _guards_intact(buf)
-    return _host(out).reshape(n_inputs, n_luts, bits, p.big1)
+    assert guards_intact(buf)
+    return host(out).reshape(n_inputs, n_luts, bits, p.big1)
 
 
 @pytest.mark.parametrize("k", [4, 1])

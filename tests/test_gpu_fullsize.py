@@ -3,7 +3,9 @@ hours): every block decrypts to AES-CTR, decrypt(encrypt(x)) == x, and launches 
 import numpy as np
 import pytest
 
+from aes_model import noise
 from conftest import sha
+from gpu_support import dev, host, opt_server, settled  # noqa: F401
 from tfhe_aes_amd import aes_clear
 from tfhe_aes_amd.server import Server
 
@@ -12,41 +14,30 @@ pytestmark = pytest.mark.gpu
 IV = 0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF
 
 
-@pytest.fixture(scope="module")
-def opt_server(opt):
-    return Server(opt.keys, device=0, engine=opt.engine())
-
-
 def test_128_ctr_blocks_param_opt(opt, opt_server):
     """BASELINE configs[2]: 128 CTR blocks, full 10 rounds, on one MI355X"""
-    import torch
-
     c, p = opt.client, opt.params
     key = c.key
     rk = opt_server.aes_key_expansion(c.encrypt_u128(key))
     assert np.array_equal(c.decrypt_bytes(rk), np.array(aes_clear.expand_key(key), dtype=np.uint8))
     n = 128
     states = np.stack([c.encrypt_u128(IV + i) for i in range(n)])
-    d_rk = torch.from_numpy(rk.view(np.int64)).cuda()
-    d_st = torch.from_numpy(states.view(np.int64)).cuda()
-    torch.cuda.synchronize()
+    d_rk, d_st = dev(rk), dev(states)
     opt_server.aes_encrypt(d_rk, d_st)
     opt_server.synchronize()
-    out = d_st.cpu().numpy().view(np.uint64)
+    out = host(d_st)
     for i in range(n):
         assert c.decrypt_u128(out[i]) == aes_clear.aes128_encrypt_block(key, IV + i), "block %d" % i
     # noise budget over all 16,384 output bits: outputs carry one fresh WoPBS result + one round key (2 addends);
     # the decision threshold is 2^62 (README.md:175-180 of the reference: p_fail 2^-64 at 5 addends)
-    bits, ph = c.decrypt_bits(out, return_phase=True)
-    err = (ph - (bits.astype(np.uint64) << np.uint64(63))).astype(np.int64)
+    err = noise(c, out)
     assert np.abs(err).max() < 1 << 59, "max |noise| = 2^%.1f" % np.log2(float(np.abs(err).max()))
     assert np.abs(err).std() < 1 << 56
     # determinism at full size: a second launch on the same inputs gives the same words
-    d_st2 = torch.from_numpy(states.view(np.int64)).cuda()
-    torch.cuda.synchronize()
+    d_st2 = dev(states)
     opt_server.aes_encrypt(d_rk, d_st2)
     opt_server.synchronize()
-    assert sha(d_st2.cpu().numpy()) == sha(out)
+    assert sha(host(d_st2)) == sha(out)
     # round trip on a few blocks (decrypt costs 1.9x, BASELINE configs[4] path)
     back = opt_server.aes_decrypt(rk, out[:4].copy())
     for i in range(4):
@@ -56,30 +47,24 @@ def test_128_ctr_blocks_param_opt(opt, opt_server):
 def test_32_block_decrypt_param_opt(opt, opt_server):
     """BASELINE configs[4] shard size: 32 blocks per GPU through aes_decrypt (inverse S-Box + 4-LUT inverse MixColumns,
     4,096 bits per launch): decrypt(encrypt(x)) == x for every block, and the ciphertexts fed in are AES ciphertexts"""
-    import torch
-
     c = opt.client
     key = c.key
     rk = opt_server.aes_key_expansion(c.encrypt_u128(key))
     n = 32
     pts = [(IV + 0x9E3779B97F4A7C15 * i) & ((1 << 128) - 1) for i in range(n)]
     states = np.stack([c.encrypt_u128(v) for v in pts])
-    d_rk = torch.from_numpy(rk.view(np.int64)).cuda()
-    d_st = torch.from_numpy(states.view(np.int64)).cuda()
-    torch.cuda.synchronize()
+    d_rk, d_st = dev(rk), dev(states)
     opt_server.aes_encrypt(d_rk, d_st)
     opt_server.synchronize()
-    mid = d_st.cpu().numpy().view(np.uint64)
+    mid = host(d_st)
     for i in range(n):
         assert c.decrypt_u128(mid[i]) == aes_clear.aes128_encrypt_block(key, pts[i]), "block %d" % i
     opt_server.aes_decrypt(d_rk, d_st)
     opt_server.synchronize()
-    out = d_st.cpu().numpy().view(np.uint64)
+    out = host(d_st)
     for i in range(n):
         assert c.decrypt_u128(out[i]) == pts[i], "block %d" % i
-    bits, ph = c.decrypt_bits(out, return_phase=True)
-    err = (ph - (bits.astype(np.uint64) << np.uint64(63))).astype(np.int64)
-    assert np.abs(err).max() < 1 << 59
+    assert np.abs(noise(c, out)).max() < 1 << 59
 
 
 def test_ctr_counter_add_param_opt(opt, opt_server):
@@ -93,8 +78,6 @@ def test_ctr_counter_add_param_opt(opt, opt_server):
 def test_1024_ctr_blocks_on_one_gpu(opt, opt_server):
     """BASELINE configs[3] total size (1,024 CTR blocks) on ONE GPU: 131,072 bits per round, processed in four
     workspace chunks; every block must decrypt to AES-CTR (the 8-GPU run shards the same stream 128 per GPU)."""
-    import torch
-
     c, p = opt.client, opt.params
     key = c.key
     rk = opt_server.aes_key_expansion(c.encrypt_u128(key))
@@ -106,13 +89,11 @@ def test_1024_ctr_blocks_on_one_gpu(opt, opt_server):
             bv = (v >> (8 * (15 - byte))) & 0xFF
             bits[i, byte] = [(bv >> j) & 1 for j in range(8)]
     states = c.encrypt_bits(bits)                                   # one call: [1024][16][8][kN+1]
-    d_rk = torch.from_numpy(rk.view(np.int64)).cuda()
-    d_st = torch.from_numpy(states.view(np.int64)).cuda()
+    d_rk, d_st = dev(rk), dev(states)
     del states
-    torch.cuda.synchronize()
     opt_server.aes_encrypt(d_rk, d_st)
     opt_server.synchronize()
-    out = d_st.cpu().numpy().view(np.uint64)
+    out = host(d_st)
     got = c.decrypt_bytes(out)                                      # [1024][16]
     for i in range(n):
         want = aes_clear.aes128_encrypt_block(key, (IV + i) & ((1 << 128) - 1))
@@ -150,7 +131,7 @@ def test_k2_launch_forms_agree_at_full_size(opt):
     assert got[3]["kernel"].startswith("blind_rotate16_kernel<5,5,8,3,2,true") and got[4]["kernel"].startswith("blind_rotate_latency_kernel<5")
     rng = np.random.default_rng(16384)
     m = 16384
-    small = torch.from_numpy(rng.integers(0, 1 << 64, (m, p.n + 1), dtype=np.uint64).view(np.int64)).cuda()
+    small = dev(rng.integers(0, 1 << 64, (m, p.n + 1), dtype=np.uint64))
     full = torch.empty((m, p.big1), dtype=torch.int64, device="cuda")
     E.cbs_pbs_batch(small, full, m)
     E.synchronize()
@@ -159,7 +140,7 @@ def test_k2_launch_forms_agree_at_full_size(opt):
         E.cbs_pbs_batch(small[lo:lo + 1024], part[lo:lo + 1024], 1024)
     E.synchronize()
     assert torch.equal(full, part)
-    part.zero_()
+    settled(part.zero_())
     for lo in range(0, m, 768):                                     # the whole batch again through the 16-form kernel
         n = min(768, m - lo)
         E.cbs_pbs_batch(small[lo:lo + n], part[lo:lo + n], n)
@@ -171,7 +152,8 @@ def test_k2_launch_forms_agree_at_full_size(opt):
     E.cbs_pbs_batch(small[:256], lat, 256)
     E.synchronize()
     assert torch.equal(full[4096:8192], mid) and torch.equal(full[:256], lat)
-    assert sha(full.cpu().numpy()) != sha(np.zeros_like(full.cpu().numpy()))
+    words = host(full)
+    assert sha(words) != sha(np.zeros_like(words))
 
 
 def test_six_generation_launch_against_the_oracle_word_for_word(opt):
@@ -201,7 +183,7 @@ def test_k2_parking_modes_agree(opt):
     p, E = opt.params, opt.engine()
     rng = np.random.default_rng(0x9A6B)
     m = 16384
-    small = torch.from_numpy(rng.integers(0, 1 << 64, (m, p.n + 1), dtype=np.uint64).view(np.int64)).cuda()
+    small = dev(rng.integers(0, 1 << 64, (m, p.n + 1), dtype=np.uint64))
     outs = {}
     try:
         for claimed in (True, False):
@@ -236,7 +218,7 @@ def test_k2_sustained_launches_stay_deterministic(opt):
     p, E = opt.params, opt.engine()
     rng = np.random.default_rng(0x50AC)
     m = 16384
-    small = torch.from_numpy(rng.integers(0, 1 << 64, (m, p.n + 1), dtype=np.uint64).view(np.int64)).cuda()
+    small = dev(rng.integers(0, 1 << 64, (m, p.n + 1), dtype=np.uint64))
     ref = torch.empty((m, p.big1), dtype=torch.int64, device="cuda")
     out = torch.empty_like(ref)
     E.cbs_pbs_batch(small, ref, m)
@@ -267,33 +249,28 @@ def test_chained_encrypt_steps_then_decrypt_shard_every_block(opt, opt_server):
     """The driver's bench shape under pytest: 128 blocks through six chained aes_encrypt steps (16,384-bit launches), every block checked
     after the last; then the configs[4] shard -- aes_decrypt of blocks 0..31 (4,096-bit launches) -- twice from the same input: every
     block checked, and the two runs give the same words (server.rs:39-105; the reference asserts every block, client.rs:171)."""
-    import torch
-
     c = opt.client
     key = c.key
     rk = opt_server.aes_key_expansion(c.encrypt_u128(key))
     n, steps = 128, 6
     pts = [(IV + i) & ((1 << 128) - 1) for i in range(n)]
-    d_rk = torch.from_numpy(rk.view(np.int64)).cuda()
-    d_st = torch.from_numpy(np.stack([c.encrypt_u128(v) for v in pts]).view(np.int64)).cuda()
-    torch.cuda.synchronize()
+    d_rk, d_st = dev(rk), dev(np.stack([c.encrypt_u128(v) for v in pts]))
     want = list(pts)
     for _ in range(steps):
         opt_server.aes_encrypt(d_rk, d_st)
         want = [aes_clear.aes128_encrypt_block(key, w) for w in want]
     opt_server.synchronize()
-    got = c.decrypt_bytes(d_st.cpu().numpy().view(np.uint64))
+    got = c.decrypt_bytes(host(d_st))
     wrong = [i for i in range(n) if [int(v) for v in got[i]] != [(want[i] >> (8 * (15 - b))) & 0xFF for b in range(16)]]
     assert not wrong, "blocks wrong after %d chained encrypt steps: %s" % (steps, wrong)
     shas = []
     for _ in range(2):
-        d4 = d_st[:32].clone()
-        torch.cuda.synchronize()
+        d4 = settled(d_st[:32].clone())
         opt_server.aes_decrypt(d_rk, d4)
         opt_server.synchronize()
-        host = d4.cpu().numpy().view(np.uint64)
-        shas.append(sha(host))
-        got = c.decrypt_bytes(host)
+        words = host(d4)
+        shas.append(sha(words))
+        got = c.decrypt_bytes(words)
         back = [aes_clear.aes128_decrypt_block(key, w) for w in want[:32]]
         wrong = [i for i in range(32) if [int(v) for v in got[i]] != [(back[i] >> (8 * (15 - b))) & 0xFF for b in range(16)]]
         assert not wrong, "blocks wrong after aes_decrypt: %s" % wrong

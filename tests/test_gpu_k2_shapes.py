@@ -23,6 +23,7 @@ Wall time on an MI355X (pytest --durations=0): NOT MEASURED YET, see DESIGN.md s
 import numpy as np
 import pytest
 
+from gpu_support import FORMS, HOME, LATENCY, PAIR, PARKED, dev, guarded, guards_intact, host, plan_tuple, unit_rows
 from oracle import oracle as orc
 from tfhe_aes_amd import _native
 
@@ -30,14 +31,6 @@ pytestmark = pytest.mark.gpu
 
 ROWS = 2112                          # the largest shape is 2,101 bits; 2,112 = 32 x 66
 ORACLE_ROW_CAP = 400                 # distinct rows the oracle may be asked for in this file (about 10 ms each on 16 cores)
-SENTINEL = -0x5A5A5A5A5A5A5A5B      # an int64 bit pattern no kernel is asked to write
-GUARD = 2
-
-LATENCY = "blind_rotate_latency_kernel<5,5,8>"
-HOME = "blind_rotate16_kernel<5,5,8,3,2,true>"
-PARKED = "blind_rotate16_kernel<5,5,8,3,2,false>"
-PAIR = "blind_rotate_pair_kernel<5,5,8,3,2>"
-FORMS = {"default": (True, True), "pair denied": (False, True), "home denied": (True, False), "both denied": (False, False)}
 
 # (forms, m, (form, units_main, r_main, units_tail, r_tail) at 256 CUs, kernel-name prefix): engine_launch.h::k2_plan / k2_launch
 CASES = [
@@ -66,43 +59,13 @@ CASES = [
 ]
 
 
-def _plan_tuple(pl):
-    return (pl["form"], pl["units_main"], pl["r_main"], pl["units_tail"], pl["r_tail"])
-
-
-def _unit_rows(plan, m):
+def _corner_rows(plan, m):
     """rows of the first unit, the last main unit, the first tail unit and the last unit of a launch, ragged slots left out"""
-    _, um, rm, ut, rt = plan
-    units = [(0, rm if um else rt)]
-    if um:
-        units.append(((um - 1) * rm, rm))
-    if ut:
-        units += [(um * rm, rt), (um * rm + (ut - 1) * rt, rt)]
-    rows = sorted({i for s, r in units for i in range(s, min(s + r, m))})
+    _, um, _, ut, _ = plan
+    units = {0, um + ut - 1} | ({um - 1} if um else set()) | ({um} if ut else set())
+    rows = sorted({i for u in units for i in unit_rows(plan, u, m)})
     assert 0 < len(rows) <= 20 and rows[-1] == m - 1
     return rows
-
-
-def _dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-
-
-def _guarded(rows, words):
-    """(a sentinel-filled device tensor of rows + 2 GUARD rows, its middle `rows` rows)"""
-    import torch
-
-    buf = torch.full((rows + 2 * GUARD, words), SENTINEL, dtype=torch.int64, device="cuda")
-    return buf, buf[GUARD:GUARD + rows]
-
-
-def _guards_intact(buf):
-    return bool((buf[:GUARD] == SENTINEL).all().item()) and bool((buf[-GUARD:] == SENTINEL).all().item())
-
-
-def _host(t):
-    return t.cpu().numpy().view(np.uint64)
 
 
 class K2Ref:
@@ -114,7 +77,7 @@ class K2Ref:
         p, E = opt.params, opt.engine()
         self.opt = opt
         self.small = np.random.default_rng(0x2112).integers(0, 1 << 64, (ROWS, p.n + 1), dtype=np.uint64)
-        self.small_d = _dev(self.small)
+        self.small_d = dev(self.small)
         pl = E.k2_plan(256)
         assert pl["form"] == 0 and pl["kernel"].startswith(LATENCY)
         self.cut = torch.empty((ROWS, p.big1), dtype=torch.int64, device="cuda")
@@ -142,7 +105,7 @@ def test_cut_reference_against_the_oracle(k2ref):
     """the reference every shape below is compared with in full is itself the oracle's on 32 rows spread evenly over the input"""
     rows = list(range(0, ROWS, ROWS // 32))
     assert len(rows) == 32
-    assert np.array_equal(_host(k2ref.cut[rows]), k2ref.oracle(rows))
+    assert np.array_equal(host(k2ref.cut[rows]), k2ref.oracle(rows))
 
 
 @pytest.mark.parametrize("forms,m,plan,kernel", CASES, ids=["%s-%d" % (c[0].replace(" ", "_"), c[1]) for c in CASES])
@@ -153,18 +116,18 @@ def test_k2_launch_shape(forms, m, plan, kernel, opt, k2ref):
     try:
         E.k2_set_forms(*FORMS[forms])
         pl = E.k2_plan(m)
-        assert _plan_tuple(pl) == plan and pl["kernel"].startswith(kernel), pl          # the launch this case exists for
-        buf, out = _guarded(m, p.big1)
+        assert plan_tuple(pl) == plan and pl["kernel"].startswith(kernel), pl           # the launch this case exists for
+        buf, out = guarded(m, p.big1)
         E.cbs_pbs_batch(k2ref.small_d[:m], out, m)
         E.synchronize()
     finally:
         E.k2_set_forms(True, True)
-    assert _guards_intact(buf), "a store outside the %d output rows" % m
+    assert guards_intact(buf), "a store outside the %d output rows" % m
     if not torch.equal(out, k2ref.cut[:m]):
         bad = torch.nonzero((out != k2ref.cut[:m]).any(dim=1)).flatten().cpu().numpy()
         raise AssertionError("%d of %d rows differ from the cut reference: %s ..." % (len(bad), m, bad[:24]))
-    rows = _unit_rows(plan, m)
-    assert np.array_equal(_host(out[rows]), k2ref.oracle(rows))
+    rows = _corner_rows(plan, m)
+    assert np.array_equal(host(out[rows]), k2ref.oracle(rows))
 
 
 def test_pair_denied_launch_leaves_the_parking_pool_alone(opt, k2ref):
@@ -180,8 +143,8 @@ def test_pair_denied_launch_leaves_the_parking_pool_alone(opt, k2ref):
         before = E.k2_park_read()
         E.k2_set_forms(False, True)
         pl = E.k2_plan(m)
-        assert _plan_tuple(pl) == (1, 257, 3, 0, 2) and pl["kernel"].startswith(HOME)
-        buf, out = _guarded(m, p.big1)
+        assert plan_tuple(pl) == (1, 257, 3, 0, 2) and pl["kernel"].startswith(HOME)
+        buf, out = guarded(m, p.big1)
         E.cbs_pbs_batch(k2ref.small_d[:m], out, m)
         E.synchronize()
         after = E.k2_park_read()
@@ -190,7 +153,7 @@ def test_pair_denied_launch_leaves_the_parking_pool_alone(opt, k2ref):
         E.k2_park_debug(None, record=False)
     assert len(after["record"]) == 0 and (after["fallbacks"], after["violations"]) == (before["fallbacks"], before["violations"])
     assert np.array_equal(after["owner"], before["owner"])
-    assert _guards_intact(buf) and torch.equal(out, k2ref.cut[:m])
+    assert guards_intact(buf) and torch.equal(out, k2ref.cut[:m])
 
 
 def test_forms_hook_is_per_context_and_deny_only(opt, toy):
@@ -205,10 +168,10 @@ def test_forms_hook_is_per_context_and_deny_only(opt, toy):
         names_other = [other.k2_plan(m)["kernel"] for m in sizes]
         assert names_other == [d["kernel"] for d in default]
         toy_plan = T.k2_plan(530)
-        assert toy_plan["kernel"].startswith("blind_rotate16_kernel<2,5,8,8") and _plan_tuple(toy_plan)[:4] == (1, 67, 8, 0)
+        assert toy_plan["kernel"].startswith("blind_rotate16_kernel<2,5,8,8") and plan_tuple(toy_plan)[:4] == (1, 67, 8, 0)
         E.k2_set_forms(False, False)
         assert [E.k2_plan(m)["kernel"] for m in sizes] == [LATENCY, PARKED, PARKED, PARKED]
-        assert _plan_tuple(E.k2_plan(2100)) == (1, 52, 3, 972, 2)
+        assert plan_tuple(E.k2_plan(2100)) == (1, 52, 3, 972, 2)
         assert [other.k2_plan(m)["kernel"] for m in sizes] == names_other
         assert T.k2_plan(530) == toy_plan
         for bad in ((2, 1), (1, 2), (-1, 0), (0, 7)):
@@ -236,10 +199,10 @@ def test_k1_keyswitch_stays_inside_its_output(opt):
     x = np.random.default_rng(0x1200).integers(0, 1 << 64, (m, p.big1), dtype=np.uint64)
     want = np.zeros((m, p.n + 1), dtype=np.uint64)
     E.keyswitch_batch(x, want, m)
-    buf, out = _guarded(m, p.n + 1)
-    E.keyswitch_batch(_dev(x), out, m)
+    buf, out = guarded(m, p.n + 1)
+    E.keyswitch_batch(dev(x), out, m)
     E.synchronize()
-    assert _guards_intact(buf) and np.array_equal(_host(out), want) and want.any()
+    assert guards_intact(buf) and np.array_equal(host(out), want) and want.any()
 
 
 def test_k3_pfpks_stays_inside_its_output(opt):
@@ -248,10 +211,10 @@ def test_k3_pfpks_stays_inside_its_output(opt):
     x = np.random.default_rng(0x3033).integers(0, 1 << 64, (m, p.big1), dtype=np.uint64)
     want = np.zeros((m, words), dtype=np.uint64)
     E.pfpks_batch(x, want, m)
-    buf, out = _guarded(m, words)
-    E.pfpks_batch(_dev(x), out, m)
+    buf, out = guarded(m, words)
+    E.pfpks_batch(dev(x), out, m)
     E.synchronize()
-    assert _guards_intact(buf) and np.array_equal(_host(out), want) and want.any()
+    assert guards_intact(buf) and np.array_equal(host(out), want) and want.any()
 
 
 @pytest.mark.parametrize("polys", [17, 300])
@@ -260,10 +223,10 @@ def test_k4_forward_fourier_stays_inside_its_output(polys, opt):
     x = np.random.default_rng(0x4000 + polys).integers(0, 1 << 64, (polys, 512), dtype=np.uint64)
     want = np.zeros((polys, 256, 2), dtype=np.float64)
     E.forward_fourier_batch(x, want, polys)
-    buf, out = _guarded(polys, 512)
-    E.forward_fourier_batch(_dev(x), out, polys)
+    buf, out = guarded(polys, 512)
+    E.forward_fourier_batch(dev(x), out, polys)
     E.synchronize()
-    assert _guards_intact(buf) and np.array_equal(_host(out), want.view(np.uint64).reshape(polys, 512)) and want.any()
+    assert guards_intact(buf) and np.array_equal(host(out), want.view(np.uint64).reshape(polys, 512)) and want.any()
 
 
 def _ggsw_fourier(opt, x):
@@ -296,10 +259,10 @@ def test_k5_vertical_packing_stays_inside_its_output(opt):
         rows = 2 * n_luts * bits
         want = np.zeros((rows, p.big1), dtype=np.uint64)
         E.vertical_packing_batch(ggsw_f, 2, bits, luts, n_luts, per_input, want)
-        buf, out = _guarded(rows, p.big1)
-        E.vertical_packing_batch(_dev(ggsw_f), 2, bits, _dev(luts), n_luts, per_input, out)
+        buf, out = guarded(rows, p.big1)
+        E.vertical_packing_batch(dev(ggsw_f), 2, bits, dev(luts), n_luts, per_input, out)
         E.synchronize()
-        assert _guards_intact(buf) and np.array_equal(_host(out), want) and want.any(), bits
+        assert guards_intact(buf) and np.array_equal(host(out), want) and want.any(), bits
 
 
 def test_cmux_tree_11bit_stays_inside_its_output(opt):
@@ -312,7 +275,7 @@ def test_cmux_tree_11bit_stays_inside_its_output(opt):
     x = c.encrypt_bits(np.array([[(v >> j) & 1 for j in range(nb)] for v in (0x3A5, 0x5C2)], dtype=np.uint8))
     want = np.zeros((2 * nb, p.big1), dtype=np.uint64)
     E.wopbs_batch(x, 2, nb, luts, 1, False, want)
-    buf, out = _guarded(2 * nb, p.big1)
-    E.wopbs_batch(_dev(x), 2, nb, _dev(luts), 1, False, out)
+    buf, out = guarded(2 * nb, p.big1)
+    E.wopbs_batch(dev(x), 2, nb, dev(luts), 1, False, out)
     E.synchronize()
-    assert _guards_intact(buf) and np.array_equal(_host(out), want) and want.any()
+    assert guards_intact(buf) and np.array_equal(host(out), want) and want.any()

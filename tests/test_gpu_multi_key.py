@@ -4,11 +4,9 @@ on the uint64 words; the clear AES of tfhe_aes_amd.aes_clear says that those wor
 import numpy as np
 import pytest
 
-from test_aes_eqinv_cpu import own_client
-from test_aes_key_sizes_cpu import NR, key_words
-from test_ctr_public_cpu import BASE, F1_PT, MASK128
+from aes_vectors import BASE, F1_PT, MASK128, NR, block_bytes, key_words, own_client
+from gpu_support import dev, host, tc, toy_server  # noqa: F401
 from tfhe_aes_amd import _native, aes_clear
-from tfhe_aes_amd.client import u128_to_bytes
 from tfhe_aes_amd.server import Server, ServerGroup
 
 pytestmark = pytest.mark.gpu
@@ -21,32 +19,6 @@ def aes_keys(bits, n=3):
     """n distinct clear AES keys of `bits` bits"""
     rng = np.random.default_rng(0xA5 + bits)
     return [rng.bytes(bits // 8) for _ in range(n)]
-
-
-def _to_dev(a):
-    import torch
-
-    d = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-    torch.cuda.synchronize()
-    return d
-
-
-def _host(d):
-    return d.cpu().numpy().view(np.uint64)
-
-
-def _block_bytes(values):
-    return np.array([u128_to_bytes(v) for v in values], dtype=np.uint8)
-
-
-@pytest.fixture(scope="module")
-def toy_server(toy):
-    return Server(toy.keys, device=0, engine=toy.engine())
-
-
-@pytest.fixture(scope="module")
-def tc(toy):
-    return own_client(toy)
 
 
 @pytest.fixture(scope="module")
@@ -133,7 +105,7 @@ def test_toy_public_keyed_is_aes_encrypt_public_per_key_and_does_the_planned_wor
             idx = [b for b, k in enumerate(kob) if k == j]
             want[idx] = srv.aes_encrypt_public(rk[j], [blocks[b] for b in idx])
         assert np.array_equal(got, want), "%d words differ" % int((got != want).sum())
-        assert np.array_equal(tc.decrypt_bytes(got), _block_bytes([aes_clear.aes_encrypt_block(keys[k], v) for k, v in zip(kob, blocks)]))
+        assert np.array_equal(tc.decrypt_bytes(got), block_bytes([aes_clear.aes_encrypt_block(keys[k], v) for k, v in zip(kob, blocks)]))
     finally:
         srv.engine.close()
 
@@ -153,7 +125,7 @@ def test_toy_ctr_streams_are_aes_ctr_per_stream(toy, toy_server, toy_keys, tc, b
         want = toy_server.aes_ctr(rk[k], iv, first, n, data=data)
         assert np.array_equal(got[at:at + n], want), "stream at block %d: %d words differ" % (at, int((got[at:at + n] != want).sum()))
         at += n
-    assert np.array_equal(tc.decrypt_bytes(got), _block_bytes(aes_clear.ctr_streams(keys, STREAMS)))
+    assert np.array_equal(tc.decrypt_bytes(got), block_bytes(aes_clear.ctr_streams(keys, STREAMS)))
 
 
 # ---- memory spaces ----------------------------------------------------------------------------------------------------------------------
@@ -162,16 +134,16 @@ def test_toy_host_arrays_and_resident_tensors_agree(toy, toy_server, toy_keys, t
     st = np.stack([tc.encrypt_u128(v) for v in PTS])
     enc = toy_server.aes_encrypt_keyed(rk, KOB, st.copy())
     ctr = toy_server.aes_ctr_streams(rk, STREAMS)
-    d_ek = _to_dev(ek)                                                        # kept alive: the device calls are only enqueued
+    d_ek = dev(ek)                                                            # kept alive: the device calls are only enqueued
     d_rk = toy_server.aes_key_expansion_many(d_ek)
-    d_enc = _to_dev(st)
+    d_enc = dev(st)
     toy_server.aes_encrypt_keyed(d_rk, KOB, d_enc)
     d_ctr = toy_server.aes_ctr_streams(d_rk, STREAMS)
     toy_server.synchronize()
     assert d_rk.is_cuda and tuple(d_rk.shape) == rk.shape
-    assert np.array_equal(_host(d_rk), rk)
-    assert np.array_equal(_host(d_enc), enc)
-    assert np.array_equal(_host(d_ctr), ctr)
+    assert np.array_equal(host(d_rk), rk)
+    assert np.array_equal(host(d_enc), enc)
+    assert np.array_equal(host(d_ctr), ctr)
     with pytest.raises(ValueError):
         toy_server.aes_encrypt_keyed(rk, KOB, d_enc)                          # mixed memory spaces are refused
 

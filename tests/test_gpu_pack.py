@@ -1,5 +1,5 @@
 """fheaes_pack_bits / fheaes_unpack_bits on the MI355X.  Every word comparison is exact (array_equal): the reference is built from what
-existed before -- the oracle's packing key switch under key block k, a numpy fold, a numpy sample extraction (tests/test_pack_cpu.py) --
+existed before -- the oracle's packing key switch under key block k, a numpy fold, a numpy sample extraction (aes_model.py) --
 and u64 wrapping sums give the same words in any order.  Then the round trip through the engine's own entry points at PARAM_OPT: a
 128-block aes_ctr packed and decrypted, unpacked bytes through the S-Box, a block through aes_ctr, pack, unpack and the equivalent
 inverse cipher; several contexts; host arrays against resident tensors; a reservation that forces chunks; the errors."""
@@ -8,12 +8,12 @@ import math
 import numpy as np
 import pytest
 
-from test_aes_eqinv_cpu import own_client
-from test_ctr_public_cpu import BASE, F1_PT, F5, MASK128
-from test_pack_cpu import added_error, pack_sigma, ref_pack, ref_unpack
+from aes_model import added_error, pack_sigma, ref_fold, ref_ks, ref_unpack
+from aes_vectors import BASE, F1_PT, F5, MASK128
+from gpu_support import dev, host, oc, opt_rk128, opt_server, tc, toy_server  # noqa: F401
 from tfhe_aes_amd import _native, aes_clear
 from tfhe_aes_amd.client import u128_to_bytes
-from tfhe_aes_amd.server import Server, ServerGroup
+from tfhe_aes_amd.server import ServerGroup
 
 pytestmark = pytest.mark.gpu
 
@@ -21,43 +21,9 @@ TOY_M = (1, 7, 512, 513, 1541)
 OPT_M = (513, 1100)
 
 
-def _to_dev(a):
-    import torch
-
-    d = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-    torch.cuda.synchronize()
-    return d
-
-
-def _host(d):
-    return d.cpu().numpy().view(np.uint64)
-
-
-@pytest.fixture(scope="module")
-def toy_server(toy):
-    return Server(toy.keys, device=0, engine=toy.engine())
-
-
-@pytest.fixture(scope="module")
-def opt_server(opt):
-    return Server(opt.keys, device=0, engine=opt.engine())
-
-
-@pytest.fixture(scope="module")
-def tc(toy):
-    return own_client(toy)
-
-
-@pytest.fixture(scope="module")
-def oc(opt):
-    return own_client(opt)
-
-
 def _cases(kit, client, sizes, seed):
     """m -> (bits, their encryptions, the reference packing), all cut from ONE reference run over max(sizes) bits where that is the same
     thing: GLWE g of a packing depends on bits gN .. gN + N - 1 alone, so only a partly filled last GLWE needs a fold of its own"""
-    from test_pack_cpu import ref_fold, ref_ks
-
     top = max(sizes)
     bits = np.random.default_rng(seed).integers(0, 2, top).astype(np.uint8)
     lwe = client.encrypt_bits(bits)
@@ -119,12 +85,12 @@ def test_shapes_follow_the_input(toy, toy_server, tc, toy_cases):
 def test_host_arrays_and_resident_tensors_agree(toy, opt, toy_server, opt_server, toy_cases, opt_cases, which):
     server, cases, m = (toy_server, toy_cases, 1541) if which == "toy" else (opt_server, opt_cases, 513)
     _, lwe, want = cases[m]
-    d_packed = server.pack(_to_dev(lwe))
+    d_packed = server.pack(dev(lwe))
     d_back = server.unpack(d_packed, m)
     server.synchronize()
     assert d_packed.is_cuda and d_back.is_cuda
-    assert np.array_equal(_host(d_packed), want)
-    assert np.array_equal(_host(d_back), server.unpack(want, m))
+    assert np.array_equal(host(d_packed), want)
+    assert np.array_equal(host(d_back), server.unpack(want, m))
 
 
 def test_a_small_reservation_forces_chunks_and_the_words_stay(toy, toy_cases):
@@ -153,21 +119,14 @@ def test_server_group_of_two_contexts_gives_the_words_of_one(toy, toy_server, to
         got = group.pack(lwe)
         assert np.array_equal(got, want)
         assert np.array_equal(group.unpack(got, 1541), toy_server.unpack(want, 1541))
-        d_got = group.pack(_to_dev(lwe[:512]))                       # one GLWE: the second context has nothing to do
-        assert np.array_equal(_host(d_got), want[:1])
+        d_got = group.pack(dev(lwe[:512]))                           # one GLWE: the second context has nothing to do
+        assert np.array_equal(host(d_got), want[:1])
     finally:
         for s in group.servers:
             s.engine.close()
 
 
 # ---- PARAM_OPT, end to end ---------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def opt_rk128(opt_server, oc):
-    d_rk = opt_server.aes_key_expansion(_to_dev(oc.encrypt_aes_key(F5[128][0])))
-    opt_server.synchronize()
-    return d_rk
-
-
 def test_param_opt_a_128_block_ctr_output_packs_into_32_glwes(opt, opt_server, opt_rk128, oc):
     """16,384 bits, the output of aes_ctr on 128 blocks with data: 268.6 MB become 655,360 bytes that decrypt to the AES-CTR plaintext,
     with an added error within 8 sigma of the parameter set's prediction, and the words are those of packing the 32 slices separately"""
@@ -177,7 +136,7 @@ def test_param_opt_a_128_block_ctr_output_packs_into_32_glwes(opt, opt_server, o
     d_packed = opt_server.pack(d_ct)
     d_slices = [opt_server.pack(d_ct.reshape(-1, p.big1)[512 * g:512 * g + 512]) for g in range(32)]
     opt_server.synchronize()
-    packed, ct = _host(d_packed), _host(d_ct)
+    packed, ct = host(d_packed), host(d_ct)
     assert ct.nbytes == 268566528 and packed.nbytes == 655360 and packed.shape == (32, 2560)
     want = b"".join((k ^ d).to_bytes(16, "big") for k, d in zip(aes_clear.ctr_keystream(key, BASE, 0, n), data))
     assert oc.decrypt_packed_bytes(packed, 16 * n).tobytes() == want
@@ -186,7 +145,7 @@ def test_param_opt_a_128_block_ctr_output_packs_into_32_glwes(opt, opt_server, o
     print("pack, 16,384 bits at PARAM_OPT: added error std 2^%.2f, max 2^%.2f = %.2f sigma (sigma 2^%.2f)" % (
         math.log2(err.std()), math.log2(np.abs(err).max()), np.abs(err).max() / sigma, math.log2(sigma)))
     assert np.abs(err).max() <= 8 * sigma
-    assert np.array_equal(np.concatenate([_host(s) for s in d_slices]), packed)
+    assert np.array_equal(np.concatenate([host(s) for s in d_slices]), packed)
 
 
 def test_param_opt_unpacked_bytes_are_valid_sbox_inputs(opt, opt_server, oc):
@@ -206,9 +165,9 @@ def test_param_opt_ctr_pack_unpack_then_the_equivalent_inverse_cipher(opt, opt_s
     opt_server.aes_decrypt_equivalent(d_dw, d_state)
     opt_server.synchronize()
     block = aes_clear.ctr_keystream(key, BASE | 0x42, 0, 1)[0] ^ F1_PT[2]
-    assert np.array_equal(oc.decrypt_bytes(_host(d_ct))[0], np.array(u128_to_bytes(block), dtype=np.uint8))
+    assert np.array_equal(oc.decrypt_bytes(host(d_ct))[0], np.array(u128_to_bytes(block), dtype=np.uint8))
     want = aes_clear.aes_decrypt_block(key, block)
-    assert np.array_equal(oc.decrypt_bytes(_host(d_state))[0], np.array(u128_to_bytes(want), dtype=np.uint8))
+    assert np.array_equal(oc.decrypt_bytes(host(d_state))[0], np.array(u128_to_bytes(want), dtype=np.uint8))
 
 
 # ---- errors --------------------------------------------------------------------------------------------------------------------------------

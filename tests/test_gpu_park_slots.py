@@ -12,6 +12,7 @@ from contextlib import contextmanager
 import numpy as np
 import pytest
 
+from gpu_support import dev, filled, host, unit_rows
 from tfhe_aes_amd import _native
 
 pytestmark = pytest.mark.gpu
@@ -21,19 +22,10 @@ TAKEN = 0xFFFFFFFF                 # an owner word no workgroup of a launch can 
 SIZES = (16384, 4096, 1001)        # 11 generations of 2,816 workgroups; 768 workgroups; 251 four-ciphertext ones, the last with one row
 
 
-def _unit_rows(plan, u, m):
-    um = plan["units_main"]
-    lo = u * plan["r_main"] if u < um else um * plan["r_main"] + (u - um) * plan["r_tail"]
-    hi = lo + (plan["r_main"] if u < um else plan["r_tail"])
-    return list(range(lo, min(hi, m)))
-
-
 @pytest.fixture(scope="module")
 def park(opt):
     """per size: seeded small-LWE inputs on the GPU, the private-parking output (checked against the oracle on the rows of the first, a
     middle and the last workgroup) and the grid"""
-    import torch
-
     p, E = opt.params, opt.engine()
     data = {}
     try:
@@ -44,13 +36,13 @@ def park(opt):
             grid = plan["units_main"] + plan["units_tail"]
             rng = np.random.default_rng(0x9A60000 + m)
             small_np = rng.integers(0, 1 << 64, (m, p.n + 1), dtype=np.uint64)
-            small = torch.from_numpy(small_np.view(np.int64)).cuda()
-            want = torch.full((m, p.big1), -1, dtype=torch.int64, device="cuda")
+            small = dev(small_np)
+            want = filled((m, p.big1), -1)
             E.cbs_pbs_batch(small, want, m)
             E.synchronize()
-            first, mid, last = _unit_rows(plan, 0, m), _unit_rows(plan, grid // 2, m), _unit_rows(plan, grid - 1, m)
+            first, mid, last = unit_rows(plan, 0, m), unit_rows(plan, grid // 2, m), unit_rows(plan, grid - 1, m)
             rows = [first[0], first[-1], mid[0], mid[-1]] + last
-            assert np.array_equal(want[rows].cpu().numpy().view(np.uint64), opt.oracle.cbs_pbs(small_np[rows])), m
+            assert np.array_equal(host(want[rows]), opt.oracle.cbs_pbs(small_np[rows])), m
             data[m] = (small, want, grid)
     finally:
         E.k2_set_parking(True)
@@ -69,12 +61,10 @@ def _hook(E, initial=None, record=True):
 
 def _launch(opt, park, m):
     """one claimed-or-private launch of the size's inputs; (output, counters before, counters and records after)"""
-    import torch
-
     E = opt.engine()
     small, want, _ = park[m]
     before = E.k2_park_read()
-    out = torch.full_like(want, -1)
+    out = filled(want.shape, -1)
     E.cbs_pbs_batch(small, out, m)
     after = E.k2_park_read()
     return out, before, after
@@ -192,8 +182,6 @@ def test_random_half_taken_is_never_claimed(opt, park):
 def test_park_hook_leaves_other_modes_and_contexts_alone(opt, toy, park):
     import ctypes as C
 
-    import torch
-
     E = opt.engine()
     m = 1001
     _, want, grid = park[m]
@@ -222,12 +210,12 @@ def test_park_hook_leaves_other_modes_and_contexts_alone(opt, toy, park):
     T, tp = toy.engine(), toy.params
     assert T.k2_plan(2048)["form"] != 2
     rng = np.random.default_rng(0x70F1)
-    small = torch.from_numpy(rng.integers(0, 1 << 64, (2048, tp.n + 1), dtype=np.uint64).view(np.int64)).cuda()
-    ref = torch.full((2048, tp.big1), -1, dtype=torch.int64, device="cuda")
+    small = dev(rng.integers(0, 1 << 64, (2048, tp.n + 1), dtype=np.uint64))
+    ref = filled((2048, tp.big1), -1)
     T.cbs_pbs_batch(small, ref, 2048)
     with _hook(T, pattern, True):
         before = T.k2_park_read()
-        got = torch.full_like(ref, -1)
+        got = filled(ref.shape, -1)
         T.cbs_pbs_batch(small, got, 2048)
         after = T.k2_park_read()
     assert _deltas(before, after) == (0, 0) and after["record"].shape == (0, 2) and np.array_equal(after["owner"], before["owner"])

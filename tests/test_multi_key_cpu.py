@@ -1,13 +1,13 @@
 """Many AES keys under one FHE key, without a GPU: the seven new entry points are declared, exported and bound; the keyed sharing rule
-(fheaes_aes_public_plan_keyed) against a restatement written here -- tests/test_ctr_public_cpu.py's rule() with the key in the round-1 id --
+(fheaes_aes_public_plan_keyed) against a restatement written here -- aes_model.rule() with the key in the round-1 id --
 and against the counts of DESIGN.md section 7; the argument errors that need no context; aes_clear.ctr_streams against SP 800-38A F.5."""
 import ctypes
 
 import numpy as np
 import pytest
 
-from test_aes_key_sizes_cpu import NR
-from test_ctr_public_cpu import BASE, F1_PT, F5, F5_CTR, MASK128, SOURCES, TABLE, counters, rule
+from aes_model import SOURCES, TABLE, rule
+from aes_vectors import BASE, F1_PT, F5, F5_CTR, MASK128, NR, counters
 from tfhe_aes_amd import _native, aes_clear
 from tfhe_aes_amd.client import u128_to_bytes
 from tfhe_aes_amd.server import ctr_stream_blocks

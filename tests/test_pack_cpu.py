@@ -1,102 +1,28 @@
 """Packing N = 512 ciphertext bits into one GLWE ciphertext with the keys at hand (include/fheaes.h: fheaes_pack_bits,
-fheaes_unpack_bits), on the CPU: the reference of the words, built from what already exists -- the oracle's private functional packing
-key switch under key block k, a numpy fold and a numpy sample extraction -- decodes, adds the predicted noise and extracts to valid LWE
+fheaes_unpack_bits), on the CPU: the reference of the words (aes_model.py: ref_pack, ref_unpack), built from what already exists -- the
+oracle's private functional packing key switch under key block k, a numpy fold and a numpy sample extraction -- decodes, adds the predicted noise and extracts to valid LWE
 ciphertexts; the "packed" interchange kind; the three symbols and their NULL-context behaviour.  tests/test_gpu_pack.py holds the
 engine to these words.
 
-The noise bound is computed from the parameter set, not from what the code gives:
+The noise bound (aes_model.pack_sigma) is computed from the parameter set, not from what the code gives:
     sigma^2 = N (kN+1) L (B^2 / 12) sigma_pfks^2  +  (kN/2 + 1) 2^(2R) / 12
 B = 2^pfks_base_log, L = pfks_level, R = 64 - L pfks_base_log, sigma_pfks = pfks_noise_std 2^64: N rotated key switches, each a sum of
 (kN+1) L digits (uniform in a range of width B) times fresh key noise, plus the rounding of the gadget to its 2^R grid against a binary
 key of kN bits (half of them set) and the body.  The added error must stay within 8 sigma: over at most 2^15 samples a Gaussian
 exceeds that with probability below 2^-30."""
-import ctypes
 import math
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-from test_aes_eqinv_cpu import own_client
+from aes_model import added_error, pack_sigma, ref_ks, ref_pack, ref_unpack
+from gpu_support import tc  # noqa: F401
 from tfhe_aes_amd import _native
 from tfhe_aes_amd.client import load_ciphertexts, save_ciphertexts
 
 
-# ---- the reference ----------------------------------------------------------------------------------------------------------------------
-def ref_ks(kit, lwe):
-    """[m][kN+1] -> [m][(k+1)N]: Oracle.pfpks(lwe)[:, k], asked of the oracle for key block k alone (a fifth of the work), bits in parallel"""
-    from oracle import oracle as orc
-
-    p, o = kit.params, kit.oracle
-    x = np.ascontiguousarray(lwe, dtype=np.uint64).reshape(-1, p.big1)
-    out = np.empty((x.shape[0], (p.k + 1) * p.N), dtype=np.uint64)
-    fn, u64p = orc.lib().orc_pfpks, ctypes.POINTER(ctypes.c_uint64)
-
-    def one(i):
-        fn(o._h, p.k, x[i].ctypes.data_as(u64p), out[i].ctypes.data_as(u64p))
-
-    with ThreadPoolExecutor(16) as pool:
-        list(pool.map(one, range(x.shape[0])))
-    return out
-
-
-def ref_fold(ks, p):
-    """packed[g] = sum_i X^i ks[gN + i], negacyclic in each of the k+1 polynomials; [m][(k+1)N] -> [ceil(m/N)][(k+1)N]"""
-    N, k1 = p.N, p.k + 1
-    m = ks.shape[0]
-    out = np.zeros(((m + N - 1) // N, k1, N), dtype=np.uint64)
-    polys = ks.reshape(m, k1, N)
-    with np.errstate(over="ignore"):
-        for t in range(m):
-            g, i = divmod(t, N)
-            rot = np.roll(polys[t], i, axis=-1)            # coefficient c takes P[c - i] ...
-            rot[:, :i] = np.uint64(0) - rot[:, :i]         # ... negated where it wrapped (c < i)
-            out[g] += rot
-    return out.reshape(-1, k1 * N)
-
-
-def ref_pack(kit, lwe):
-    return ref_fold(ref_ks(kit, lwe), kit.params)
-
-
-def ref_unpack(packed, m, p):
-    """sample extraction of coefficient t % N of GLWE t // N: [G][(k+1)N] -> [m][kN+1]"""
-    N, k = p.N, p.k
-    out = np.empty((m, p.big1), dtype=np.uint64)
-    glwe = np.ascontiguousarray(packed, dtype=np.uint64).reshape(-1, k + 1, N)
-    c = np.arange(N)
-    with np.errstate(over="ignore"):
-        for t in range(m):
-            g, i = divmod(t, N)
-            a = glwe[g, :k][:, (i - c) % N]                # A_j[i - c] for c <= i, A_j[i - c + N] for c > i
-            a[:, i + 1:] = np.uint64(0) - a[:, i + 1:]
-            out[t, :k * N] = a.reshape(-1)
-            out[t, k * N] = glwe[g, k, i]
-    return out
-
-
-def pack_sigma(p) -> float:
-    B, L = 2.0 ** p.pfks_base_log, p.pfks_level
-    R = 64 - L * p.pfks_base_log
-    s = p.pfks_noise_std * 2.0 ** 64
-    return math.sqrt(p.N * p.big1 * L * (B * B / 12.0) * s * s + (p.big / 2 + 1) * 2.0 ** (2 * R) / 12.0)
-
-
-def added_error(c, packed, lwe):
-    """phase of coefficient t minus the phase of input t, as signed integers"""
-    m = int(np.prod(lwe.shape[:-1]))
-    _, ph_in = c.decrypt_bits(lwe, return_phase=True)
-    _, ph = c.decrypt_packed(packed, m, return_phase=True)
-    return (ph - ph_in.reshape(-1)).astype(np.int64)
-
-
 # ---- PARAM_TOY ----------------------------------------------------------------------------------------------------------------------------
 M = 600
-
-
-@pytest.fixture(scope="module")
-def tc(toy):
-    return own_client(toy)
 
 
 @pytest.fixture(scope="module")
