@@ -299,6 +299,57 @@ int fheaes_pack_bits(fheaes_ctx *ctx, const uint64_t *lwe_in, uint64_t m, uint64
 /* glwe_in [ceil(m/N)][(k+1)N] -> lwe_out [m][kN+1]: a permutation with signs, no keys needed.  Same argument rules. */
 int fheaes_unpack_bits(fheaes_ctx *ctx, const uint64_t *glwe_in, uint64_t m, uint64_t *lwe_out, int memspace);
 
+/* ---- wire formats --------------------------------------------------------------- */
+/* Everything above is sized for compute: a client sends kN + 1 words (16,392 bytes at PARAM_OPT) per bit, 2,098,176 bytes for one AES-128
+ * key, and a packed result is 64-bit words.  Two compact forms for the wire, one per direction; nothing above changes.
+ *
+ * SEEDED LWE CIPHERTEXTS (client -> server).  kN of the kN + 1 words of a fresh LWE ciphertext are a uniformly random mask, public by
+ * construction.  A list of m seeded ciphertexts is (mask_key: a PUBLIC 256-bit key, uint32[8]; first_index: uint64; bodies: uint64[m]).
+ * Ciphertext t expands to [ mask(first_index + t) | bodies[t] ]: mask word j < kN of ciphertext q is 64-bit word j % 8 of the RFC 8439
+ * block j / 8 under (mask_key, nonce = (6, q low 32, q high 32)) -- the stream of fheaes_upload_keys_seeded with the tag MASK_TAG_LWE = 6
+ * (csrc/client.c).  8 bytes per bit instead of 16,392; one AES-128 key is 128 x 8 + 40 = 1,064 bytes instead of 2 MB; 65,536 AES keys
+ * are 67.1 MB instead of 137.5 GB.  An expanded ciphertext is an ordinary LWE under the big key, a legal input of every entry point.
+ *   THE RULE THE CLIENT KEEPS: a (mask_key, index) pair is used for ONE ciphertext only, under ONE secret key.  Two ciphertexts with the
+ *   same mask differ by their messages and noises alone (b - b' = (m - m') 2^63 + e - e'), which gives the message difference away.  The
+ *   Python Client draws a fresh mask_key for every seeded encryption call; first_index exists so that one list can be cut into shards
+ *   (shard s passes first_index + its offset) and so that a sender may run several lists under one mask_key on disjoint index ranges.
+ * The reference has no counterpart (client.rs:123-138 hands full ciphertexts across in memory); in tfhe-rs it is SeededLweCiphertextList.
+ *
+ * lwe_out[t] = [ mask words of ciphertext first_index + t | bodies[t] ],  t < m;  lwe_out [m][kN+1].
+ * mask_key: HOST array of 8 uint32 whatever memspace says (as fheaes_upload_keys_seeded); bodies, lwe_out in memspace.  No keys needed: a
+ * context at any parameter set.  m = 0 is FHEAES_OK; overlapping buffers FHEAES_ERR_INVALID; FHEAES_DEVICE calls only enqueue.
+ * Accounted under FHEAES_STAGE_LINEAR (units: bits). */
+int fheaes_expand_lwe_seeded(fheaes_ctx *ctx, const uint32_t *mask_key, uint64_t first_index, const uint64_t *bodies, uint64_t m,
+                             uint64_t *lwe_out, int memspace);
+
+/* MODULUS-SWITCHED PACKED CIPHERTEXTS (server -> client, or to storage).  Width w, 8 <= w <= 32.  A word x of a packed GLWE becomes the
+ * w-bit value
+ *   v = ((x + 2^(63-w)) >> (64-w)) mod 2^w          (the sum wraps in uint64: words within 2^(63-w) of 2^64 round to 0)
+ * and is read back as x' = v << (64-w).  Within GLWE g the word of polynomial j, coefficient c is field e = jN + c, at bits
+ * [e w, (e+1) w) of that GLWE's little-endian bit string (bit b of the string = bit b % 64 of word b / 64).  With N = 512 a polynomial is
+ * exactly 8 w words; a GLWE is (k+1) 8 w words and starts on a word boundary; the container stays uint64_t.  w = 64 means "not switched":
+ * the _mod entry points then give the words of the plain ones.  Any other width is FHEAES_ERR_INVALID.  128 AES blocks at w = 16:
+ * 163,840 bytes instead of 655,360 packed (268.6 MB unpacked).
+ *
+ * Noise: each word moves by at most 2^(63-w), uniformly; the phase of a coefficient moves by a sum over the body and the h set key bits:
+ *   variance (1 + h) 2^(2(64-w)) / 12,   hard bound (1 + h) 2^(63-w).
+ * At PARAM_OPT (h about 1,024) and w = 16: std 2^51.2, bound 2^57.0 (below 2^58), against a WoPBS output noise below std 2^56 / max 2^59 and a decoding
+ * margin of 2^62 -- w = 16 cannot flip a bit that was decodable with that room (the default of the Python layer).  Smaller widths are the
+ * caller's arithmetic, as summed ciphertexts are for the noise guard; words carry no noise metadata.
+ *
+ * Argument rules of fheaes_pack_bits / fheaes_unpack_bits: m = 0 or n_glwe = 0 is FHEAES_OK, overlapping buffers FHEAES_ERR_INVALID,
+ * FHEAES_ERR_NOKEYS only where packing needs keys, FHEAES_DEVICE calls only enqueue; all under FHEAES_STAGE_LINEAR. */
+size_t fheaes_packed_words_mod(const fheaes_ctx *ctx, uint64_t m, uint32_t width);     /* ceil(m/N)(k+1)N width/64; 0 for NULL or a bad width */
+/* 64-bit packed GLWEs [n_glwe][(k+1)N] -> [n_glwe][(k+1) 8 width]: no keys */
+int fheaes_packed_mod_switch(fheaes_ctx *ctx, const uint64_t *glwe_in, uint64_t n_glwe, uint32_t width, uint64_t *out, int memspace);
+/* fheaes_pack_bits followed by the switch: word for word fheaes_packed_mod_switch(fheaes_pack_bits(..)); each chunk's 64-bit GLWEs are
+ * staged in workspace the context owns (at most 64 GLWEs).  Like fheaes_pack_bits' own workspace it is grown, with a stream
+ * synchronisation, by the first call that needs more of it than any call before (a larger m, up to one chunk); from then on a
+ * FHEAES_DEVICE call only enqueues. */
+int fheaes_pack_bits_mod(fheaes_ctx *ctx, const uint64_t *lwe_in, uint64_t m, uint32_t width, uint64_t *out, int memspace);
+/* sample extraction straight from the w-bit fields: word for word fheaes_unpack_bits of the read-back GLWEs (x' = v << (64-w)) */
+int fheaes_unpack_bits_mod(fheaes_ctx *ctx, const uint64_t *in, uint64_t m, uint32_t width, uint64_t *lwe_out, int memspace);
+
 /* ---- measurement --------------------------------------------------------------- */
 #define FHEAES_STAGE_KEYSWITCH 0
 #define FHEAES_STAGE_BLIND_ROTATE 1

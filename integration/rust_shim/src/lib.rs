@@ -110,6 +110,13 @@ extern "C" {
     pub fn fheaes_packed_words(ctx: *const fheaes_ctx, m: u64) -> usize;
     pub fn fheaes_pack_bits(ctx: *mut fheaes_ctx, lwe_in: *const u64, m: u64, glwe_out: *mut u64, memspace: c_int) -> c_int;
     pub fn fheaes_unpack_bits(ctx: *mut fheaes_ctx, glwe_in: *const u64, m: u64, lwe_out: *mut u64, memspace: c_int) -> c_int;
+    // wire formats: seeded input ciphertexts (public mask key, first index, bodies) and packed words switched to `width` bits
+    pub fn fheaes_expand_lwe_seeded(ctx: *mut fheaes_ctx, mask_key: *const u32, first_index: u64, bodies: *const u64, m: u64, lwe_out: *mut u64,
+                                    memspace: c_int) -> c_int;
+    pub fn fheaes_packed_words_mod(ctx: *const fheaes_ctx, m: u64, width: u32) -> usize;
+    pub fn fheaes_packed_mod_switch(ctx: *mut fheaes_ctx, glwe_in: *const u64, n_glwe: u64, width: u32, out: *mut u64, memspace: c_int) -> c_int;
+    pub fn fheaes_pack_bits_mod(ctx: *mut fheaes_ctx, lwe_in: *const u64, m: u64, width: u32, out: *mut u64, memspace: c_int) -> c_int;
+    pub fn fheaes_unpack_bits_mod(ctx: *mut fheaes_ctx, packed_in: *const u64, m: u64, width: u32, lwe_out: *mut u64, memspace: c_int) -> c_int;
 }
 
 // ------------------------------------------------------------------------------------------------ helpers

@@ -75,6 +75,11 @@ SIGNATURES = {
     "fheaes_packed_words": (_c.c_size_t, [_ctx, _c.c_uint64]),
     "fheaes_pack_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_unpack_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_expand_lwe_seeded": (_c.c_int, [_ctx, _u32p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_packed_words_mod": (_c.c_size_t, [_ctx, _c.c_uint64, _c.c_uint32]),
+    "fheaes_packed_mod_switch": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_void_p, _c.c_int]),
+    "fheaes_pack_bits_mod": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_void_p, _c.c_int]),
+    "fheaes_unpack_bits_mod": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_void_p, _c.c_int]),
     "fheaes_profile_enable": (_c.c_int, [_ctx, _c.c_int]),
     "fheaes_profile_reset": (_c.c_int, [_ctx]),
     "fheaes_profile_read": (_c.c_int, [_ctx, _c.c_int, _dp, _u64p, _u64p]),
@@ -361,6 +366,25 @@ class Engine:
 
     def unpack_bits(self, glwe_in, m: int, lwe_out):
         self._check(self._lib.fheaes_unpack_bits(self._h, _ptr(glwe_in)[0], m, _ptr(lwe_out)[0], self._space(glwe_in, lwe_out)))
+
+    # -- wire formats: seeded input ciphertexts, modulus-switched packed outputs (include/fheaes.h) --
+    def expand_lwe_seeded(self, mask_key, first_index: int, bodies, m: int, lwe_out):
+        """lwe_out[t] = [mask words of ciphertext first_index + t | bodies[t]]; mask_key: the public 256-bit key, 8 uint32 on the host"""
+        mk = np.ascontiguousarray(np.asarray(mask_key, dtype=np.uint32).reshape(8))
+        self._check(self._lib.fheaes_expand_lwe_seeded(self._h, mk.ctypes.data_as(_u32p), int(first_index), _ptr(bodies)[0], m, _ptr(lwe_out)[0],
+                                                       self._space(bodies, lwe_out)))
+
+    def packed_words_mod(self, m: int, width: int) -> int:
+        return self._lib.fheaes_packed_words_mod(self._h, m, width)
+
+    def packed_mod_switch(self, glwe_in, n_glwe: int, width: int, out):
+        self._check(self._lib.fheaes_packed_mod_switch(self._h, _ptr(glwe_in)[0], n_glwe, width, _ptr(out)[0], self._space(glwe_in, out)))
+
+    def pack_bits_mod(self, lwe_in, m: int, width: int, out):
+        self._check(self._lib.fheaes_pack_bits_mod(self._h, _ptr(lwe_in)[0], m, width, _ptr(out)[0], self._space(lwe_in, out)))
+
+    def unpack_bits_mod(self, packed_in, m: int, width: int, lwe_out):
+        self._check(self._lib.fheaes_unpack_bits_mod(self._h, _ptr(packed_in)[0], m, width, _ptr(lwe_out)[0], self._space(packed_in, lwe_out)))
 
     # -- measurement ------------------------------------------------------------
     def profile_enable(self, on: bool = True):

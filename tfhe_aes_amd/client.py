@@ -40,11 +40,12 @@ def _load():
         lib.fheaes_client_chacha20_block.argtypes = [u32p, ctypes.c_uint32, u32p, u32p]
         lib.fheaes_client_chacha20_block.restype = None
         lib.fheaes_client_encrypt_bits.argtypes = [pp, u32p, u8p, ctypes.c_double, u8p, ctypes.c_uint64, u64p]
+        lib.fheaes_client_encrypt_bits_seeded.argtypes = [pp, u32p, u32p, ctypes.c_uint64, u8p, ctypes.c_double, u8p, ctypes.c_uint64, u64p]
         lib.fheaes_client_decrypt_bits.argtypes = [pp, u8p, u64p, ctypes.c_uint64, u8p, u64p]
         lib.fheaes_client_phase_small.argtypes = [pp, u8p, u64p, ctypes.c_uint64, u64p]
         lib.fheaes_client_glwe_phase.argtypes = [pp, u8p, u64p, ctypes.c_uint64, u64p]
         for f in (lib.fheaes_client_gen_secret_keys, lib.fheaes_client_gen_ksk, lib.fheaes_client_gen_bsk,
-                  lib.fheaes_client_gen_pfpksk, lib.fheaes_client_encrypt_bits, lib.fheaes_client_decrypt_bits,
+                  lib.fheaes_client_gen_pfpksk, lib.fheaes_client_encrypt_bits, lib.fheaes_client_encrypt_bits_seeded, lib.fheaes_client_decrypt_bits,
                   lib.fheaes_client_phase_small, lib.fheaes_client_glwe_phase):
             f.restype = None
         _lib = lib
@@ -75,6 +76,7 @@ def test_key(seed: int, purpose: int, counter: int = 0) -> np.ndarray:
 
 
 MASK_TAG_KSK, MASK_TAG_BSK, MASK_TAG_PFPKSK = 3, 4, 5          # csrc/client.c, csrc/kern_linear.h
+MASK_TAG_LWE = 6                                               # seeded input ciphertexts (SeededCiphertexts, fheaes_expand_lwe_seeded)
 
 
 def chacha20_blocks(key8: np.ndarray, counters: np.ndarray, nonce0: int, nonce1: np.ndarray, nonce2: np.ndarray) -> np.ndarray:
@@ -104,14 +106,16 @@ def chacha20_blocks(key8: np.ndarray, counters: np.ndarray, nonce0: int, nonce1:
         return np.stack([x[i] + init[i] for i in range(16)], axis=-1)
 
 
-def mask_words(mask_key: np.ndarray, tag: int, n_cts: int, words_per_ct: int) -> np.ndarray:
+def mask_words(mask_key: np.ndarray, tag: int, n_cts: int, words_per_ct: int, first_ct: int = 0) -> np.ndarray:
     """The public mask stream of csrc/client.c in numpy: [n_cts][words_per_ct] uint64 -- 64-bit word j % 8 of ChaCha20 block
-    j / 8 under (mask key, nonce = (tag, ct)).  Host-side twin of the engine's expansion kernel."""
+    j / 8 under (mask key, nonce = (tag, ct)), for the ciphertexts ct = first_ct .. first_ct + n_cts - 1 (a 64-bit index, wrapping).
+    Host-side twin of the engine's expansion kernels."""
     blocks = (words_per_ct + 7) // 8
     out = np.empty((n_cts, blocks * 8), dtype=np.uint64)
     step = max(1, (1 << 21) // blocks)                                     # bound the temporaries
     for c0 in range(0, n_cts, step):
-        ct = np.arange(c0, min(n_cts, c0 + step), dtype=np.uint64)
+        with np.errstate(over="ignore"):
+            ct = np.arange(c0, min(n_cts, c0 + step), dtype=np.uint64) + np.uint64(int(first_ct) & (2 ** 64 - 1))
         w = chacha20_blocks(mask_key, np.arange(blocks, dtype=np.uint32)[None, :], tag, (ct & np.uint64(0xFFFFFFFF)).astype(np.uint32)[:, None],
                             (ct >> np.uint64(32)).astype(np.uint32)[:, None])      # [cts][blocks][16]
         out[c0:c0 + len(ct)] = np.ascontiguousarray(w).view(np.uint64).reshape(len(ct), blocks * 8)
@@ -165,6 +169,84 @@ class SeededServerKeys:
         if (out.ksk_body.size, out.bsk_body.size, out.pfpksk_body.size) != want or out.mask_seed.size != 8:
             raise ValueError("key file has the wrong array sizes")
         return out
+
+
+@dataclass
+class SeededCiphertexts:
+    """One-bit LWE ciphertexts as (public mask key, first index, bodies): ciphertext t of the flattened list is
+    [mask(first_index + t) | bodies[t]], its kN mask words the public ChaCha20 stream under (mask_key, MASK_TAG_LWE, first_index + t)
+    (include/fheaes.h, "wire formats"), regenerated on the GPU by ``Server.expand`` and on the host by ``expand()``: 8 bytes per bit
+    travel instead of 8 (kN + 1).  ``bodies`` keeps the logical shape, e.g. [16][8] for an AES-128 key.
+
+    The rule the sender keeps: a (mask_key, index) pair serves ONE ciphertext, under ONE secret key -- two bodies over one mask give
+    the difference of their messages away.  ``Client.encrypt_*_seeded`` draws a fresh mask key for every call."""
+    params: WopbsParameters
+    mask_key: np.ndarray           # the PUBLIC 256-bit mask key, uint32[8]
+    first_index: int               # index of the first ciphertext in the mask stream (uint64)
+    bodies: np.ndarray             # uint64[...]
+
+    @property
+    def nbytes(self) -> int:
+        return 32 + 8 + 8 * int(self.bodies.size)
+
+    def expand(self) -> np.ndarray:
+        """the full ciphertexts, bodies.shape + (kN+1,): the numpy twin of fheaes_expand_lwe_seeded"""
+        p = self.params
+        b = np.ascontiguousarray(self.bodies, dtype=np.uint64)
+        out = np.empty((b.size, p.big1), dtype=np.uint64)
+        out[:, :p.big] = mask_words(self.mask_key, MASK_TAG_LWE, b.size, p.big, first_ct=self.first_index)
+        out[:, p.big] = b.reshape(-1)
+        return out.reshape(b.shape + (p.big1,))
+
+    def save(self, path) -> None:
+        np.savez(path, shape=_param_shape(self.params), mask_key=np.asarray(self.mask_key, dtype=np.uint32),
+                 first_index=np.array([int(self.first_index)], dtype=np.uint64), bodies=np.asarray(self.bodies, dtype=np.uint64))
+
+    @staticmethod
+    def load(path, params: WopbsParameters) -> "SeededCiphertexts":
+        with np.load(path, allow_pickle=False) as z:
+            if list(map(int, z["shape"])) != list(map(int, _param_shape(params))):
+                raise ValueError("ciphertext file was produced for a different parameter set")
+            mask_key, first, bodies = z["mask_key"], z["first_index"], z["bodies"]
+        if mask_key.shape != (8,) or mask_key.dtype != np.uint32 or first.shape != (1,) or first.dtype != np.uint64 or bodies.dtype != np.uint64:
+            raise ValueError("ciphertext file has the wrong array shapes (mask_key uint32[8], first_index uint64[1], bodies uint64[...])")
+        return SeededCiphertexts(params, mask_key.copy(), int(first[0]), bodies.copy())
+
+
+# ---- modulus-switched packed ciphertexts (include/fheaes.h, "wire formats") -------------------------------------------------------------
+PACKED_WIDTHS = tuple(range(8, 33)) + (64,)
+
+
+def _check_width(width: int) -> int:
+    width = int(width)
+    if width not in PACKED_WIDTHS:
+        raise ValueError("width must be in 8..32, or 64 for the words as they are (got %d)" % width)
+    return width
+
+
+def packed_mod_words(params: WopbsParameters, width: int) -> int:
+    """words of one packed GLWE at `width` bits per word: (k+1) N width / 64 = (k+1) 8 width"""
+    return (params.k + 1) * params.N * _check_width(width) // 64
+
+
+def read_back_packed(packed: np.ndarray, params: WopbsParameters, width: int) -> np.ndarray:
+    """[G][(k+1) 8 width] switched GLWEs -> [G][(k+1)N] 64-bit words x' = v << (64 - width): field e of a GLWE sits at bits
+    [e width, (e+1) width) of its little-endian bit string.  width 64: the words themselves."""
+    width = _check_width(width)
+    packed = np.ascontiguousarray(packed, dtype=np.uint64)
+    if width == 64:
+        return packed
+    fields = (params.k + 1) * params.N
+    if packed.ndim != 2 or packed.shape[1] != fields * width // 64:
+        raise ValueError("a GLWE at width %d has %d words, got shape %s" % (width, fields * width // 64, packed.shape))
+    bit = np.arange(fields, dtype=np.uint64) * np.uint64(width)
+    word, off = (bit >> np.uint64(6)).astype(np.int64), bit & np.uint64(63)
+    straddles = off + np.uint64(width) > np.uint64(64)                     # then off > 0
+    v = packed[:, word] >> off
+    nxt = packed[:, np.minimum(word + 1, packed.shape[1] - 1)]             # the last field ends with the last word and never straddles
+    hi_shift = np.where(straddles, np.uint64(64) - off, np.uint64(0))
+    v = v | np.where(straddles, nxt << hi_shift, np.uint64(0))
+    return v << np.uint64(64 - width)
 
 
 def _param_shape(p: WopbsParameters) -> np.ndarray:
@@ -228,42 +310,61 @@ CIPHERTEXT_KINDS = {
     "round_keys": (11, 16, 8),  # [11][16][8][kN+1]                     Server::aes_key_expansion output ([13] / [15]: AES-192 / AES-256)
     "bytes": (8,),              # [n][8][kN+1]                          sbox / many_sbox inputs
     "packed": (),               # [G][(k+1)N]                           Server.pack output: N bits per GLWE ciphertext
+    "packed_mod": (),           # [G][(k+1) 8 width]                    Server.pack(width=w) output, 8 <= w <= 32: the width travels with the words
 }
 
 
-def _kind_tail(kind: str, params: WopbsParameters) -> tuple:
-    """the trailing axes of an array of this kind: LWE ciphertexts of kN+1 words, or (packed) GLWE ciphertexts of (k+1)N"""
+def _kind_tail(kind: str, params: WopbsParameters, width: int = 64) -> tuple:
+    """the trailing axes of an array of this kind: LWE ciphertexts of kN+1 words, or (packed) GLWE ciphertexts of (k+1)N, (k+1) 8 width switched"""
+    if kind == "packed_mod":
+        return (packed_mod_words(params, width),)
     return CIPHERTEXT_KINDS[kind] + (((params.k + 1) * params.N,) if kind == "packed" else (params.big1,))
 
 
-def _has_kind_shape(shape, kind: str, params: WopbsParameters) -> bool:
-    tail = _kind_tail(kind, params)
-    if kind == "packed":
+def _has_kind_shape(shape, kind: str, params: WopbsParameters, width: int = 64) -> bool:
+    tail = _kind_tail(kind, params, width)
+    if kind in ("packed", "packed_mod"):
         return len(shape) == 2 and shape[-1:] == tail
     if kind == "round_keys" and len(shape) >= 4 and shape[-4] in (13, 15):       # Nr + 1 round keys of AES-192 / AES-256
         return shape[-3:] == tail[1:]
     return shape[-len(tail):] == tail
 
 
-def save_ciphertexts(path, params: WopbsParameters, kind: str, words: np.ndarray) -> None:
+def _kind_width(kind: str, width) -> int:
+    """the width argument of save / load: the "packed_mod" kind needs one in 8..32, no other kind takes one"""
+    if kind != "packed_mod":
+        if width is not None:
+            raise ValueError("only the 'packed_mod' kind has a width")
+        return 64
+    if width is None or _check_width(width) == 64:
+        raise ValueError("the 'packed_mod' kind needs its width, 8..32 (64-bit words are the 'packed' kind)")
+    return int(width)
+
+
+def save_ciphertexts(path, params: WopbsParameters, kind: str, words: np.ndarray, width: int | None = None) -> None:
     if kind not in CIPHERTEXT_KINDS:
         raise ValueError("kind must be one of %s" % ", ".join(CIPHERTEXT_KINDS))
-    tail = _kind_tail(kind, params)
+    w = _kind_width(kind, width)
+    tail = _kind_tail(kind, params, w)
     a = np.ascontiguousarray(words, dtype=np.uint64)
-    if not _has_kind_shape(a.shape, kind, params):
+    if not _has_kind_shape(a.shape, kind, params, w):
         raise ValueError("a %r array must end in shape %r, got %r" % (kind, tail, a.shape))
-    np.savez(path, shape=_param_shape(params), kind=np.frombuffer(kind.encode().ljust(16, b"\0"), dtype=np.uint8), words=a)
+    extra = {"width": np.array([w], dtype=np.uint32)} if kind == "packed_mod" else {}
+    np.savez(path, shape=_param_shape(params), kind=np.frombuffer(kind.encode().ljust(16, b"\0"), dtype=np.uint8), words=a, **extra)
 
 
-def load_ciphertexts(path, params: WopbsParameters, kind: str) -> np.ndarray:
+def load_ciphertexts(path, params: WopbsParameters, kind: str, width: int | None = None) -> np.ndarray:
+    w = _kind_width(kind, width)
     with np.load(path, allow_pickle=False) as z:
         if list(map(int, z["shape"])) != list(map(int, _param_shape(params))):
             raise ValueError("ciphertext file was produced for a different parameter set")
         got = bytes(z["kind"]).rstrip(b"\0").decode()
         if got != kind:
             raise ValueError("ciphertext file holds %r, expected %r" % (got, kind))
+        if kind == "packed_mod" and ("width" not in z.files or z["width"].shape != (1,) or int(z["width"][0]) != w):
+            raise ValueError("ciphertext file holds words of width %s, expected %d" % (int(z["width"][0]) if "width" in z.files else "?", w))
         a = z["words"].astype(np.uint64)
-    if not _has_kind_shape(a.shape, kind, params):
+    if not _has_kind_shape(a.shape, kind, params, w):
         raise ValueError("ciphertext file has the wrong array shape")
     return a
 
@@ -288,7 +389,11 @@ class Client:
     for every encryption call come from ``os.urandom``.  An explicit integer ``seed`` is the TEST-ONLY deterministic mode
     (golden vectors, parity tests, synthetic bench data): all keys derive from that one number (at most 64 bits of entropy)
     and encryption call i is reproducible -- two processes with the same seed then produce the same masks and noise, which
-    is exactly what fixtures need and what real use must never do."""
+    is exactly what fixtures need and what real use must never do.
+
+    The ``encrypt_*_seeded`` methods give the same encryptions as ``SeededCiphertexts`` (public mask key, first index, bodies).  The
+    rule they keep: a (mask key, index) pair is used for one ciphertext only, under one secret key -- every seeded call draws a fresh
+    mask key from ``os.urandom`` (test mode: ``test_key(seed, 4, call counter)``), the noise comes from the secret per-call key."""
 
     def __init__(self, number_of_outputs: int = 1, iv: int = 0, key: int = 0,
                  params: WopbsParameters = PARAM_OPT, seed: int | None = None):
@@ -341,6 +446,39 @@ class Client:
         v = np.asarray(values, dtype=np.uint64).reshape(-1)
         bits = ((v[:, None] >> np.arange(8, dtype=np.uint64)[None, :]) & 1).astype(np.uint8)
         return self.encrypt_bits(bits)
+
+    # The same four as (public mask key, first index, bodies): 8 bytes per bit on the wire instead of 8 (kN + 1).  A (mask key, index) pair
+    # serves ONE ciphertext under ONE secret key, so every call draws a FRESH public mask key from os.urandom (deterministic test mode:
+    # test_key(seed, 4, call counter)); the noise comes from the secret per-call key, as in encrypt_bits.  Server.expand regenerates the masks.
+    def encrypt_bits_seeded(self, bits: np.ndarray, first_index: int = 0) -> SeededCiphertexts:
+        """encrypt_bits in seeded form: bodies of the shape of `bits`; ciphertext t of the flattened list uses mask index first_index + t"""
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        first_index = int(first_index)
+        if not 0 <= first_index < 1 << 64:
+            raise ValueError("first_index is a uint64")
+        bodies = np.empty(bits.shape, dtype=np.uint64)
+        self._enc_counter += 1
+        enc_key = test_key(self.test_seed, 3, self._enc_counter) if self.deterministic else random_key()        # SECRET
+        mask_key = test_key(self.test_seed, 4, self._enc_counter) if self.deterministic else random_key()       # PUBLIC, this call only
+        _load().fheaes_client_encrypt_bits_seeded(ctypes.byref(self._c), _u32(enc_key), _u32(mask_key), first_index, _u8(self.glwe_sk),
+                                                  self.params.glwe_noise_std, _u8(bits), bits.size, _u64(bodies))
+        return SeededCiphertexts(self.params, mask_key, first_index, bodies)
+
+    def encrypt_bytes_seeded(self, values, first_index: int = 0) -> SeededCiphertexts:
+        """encrypt_bytes in seeded form: bodies [len][8]"""
+        v = np.asarray(values, dtype=np.uint64).reshape(-1)
+        bits = ((v[:, None] >> np.arange(8, dtype=np.uint64)[None, :]) & 1).astype(np.uint8)
+        return self.encrypt_bits_seeded(bits, first_index)
+
+    def encrypt_u128_seeded(self, x: int, first_index: int = 0) -> SeededCiphertexts:
+        """one AES state / key in seeded form: bodies [16][8]"""
+        return self.encrypt_bytes_seeded(u128_to_bytes(x), first_index)
+
+    def encrypt_aes_key_seeded(self, key: bytes, first_index: int = 0) -> SeededCiphertexts:
+        """encrypt_aes_key in seeded form: bodies [len][8], 8 len(key) + 40 bytes in all (1,064 for AES-128 instead of 2 MB at PARAM_OPT)"""
+        if len(key) not in (16, 24, 32):
+            raise ValueError("an AES key has 16, 24 or 32 bytes, got %d" % len(key))
+        return self.encrypt_bytes_seeded(list(key), first_index)
 
     def trivial_bytes(self, values) -> np.ndarray:
         """noise-free "encryptions" of PUBLIC bytes that anyone can write down: mask 0, body = bit << 63; [..., 8, kN+1] for values
@@ -400,11 +538,12 @@ class Client:
         _load().fheaes_client_glwe_phase(ctypes.byref(self._c), _u8(self.glwe_sk), _u64(glwe), count, _u64(out))
         return out
 
-    def decrypt_packed(self, packed: np.ndarray, m: int, return_phase: bool = False):
+    def decrypt_packed(self, packed: np.ndarray, m: int, return_phase: bool = False, width: int = 64):
         """[G][(k+1)N] from Server.pack -> the m bits it holds (bit t: GLWE t // N, coefficient t % N), decoded like decrypt_bits
-        (message at the MSB, rounded); with `return_phase` also the m phases B - sum A_j S_j of those coefficients."""
+        (message at the MSB, rounded); with `return_phase` also the m phases B - sum A_j S_j of those coefficients.  `width` < 64: the
+        modulus-switched form [G][(k+1) 8 width] of Server.pack(width=...), read back to 64-bit words first."""
         p = self.params
-        packed = np.ascontiguousarray(packed, dtype=np.uint64)
+        packed = read_back_packed(packed, p, width)
         m = int(m)
         if packed.shape != ((m + p.N - 1) // p.N, (p.k + 1) * p.N):
             raise ValueError("%d bits are packed as [%d][%d] words, got shape %s" % (m, (m + p.N - 1) // p.N, (p.k + 1) * p.N, packed.shape))
@@ -412,9 +551,9 @@ class Client:
         bits = ((phase + np.uint64(1 << 62)) >> np.uint64(63)).astype(np.uint8)
         return (bits, phase) if return_phase else bits
 
-    def decrypt_packed_bytes(self, packed: np.ndarray, n_bytes: int) -> np.ndarray:
+    def decrypt_packed_bytes(self, packed: np.ndarray, n_bytes: int, width: int = 64) -> np.ndarray:
         """the packed form of [n_bytes][8][kN+1] (states, blocks of states: any array of bytes) -> uint8[n_bytes]"""
-        bits = self.decrypt_packed(packed, 8 * int(n_bytes)).reshape(-1, 8).astype(np.uint64)
+        bits = self.decrypt_packed(packed, 8 * int(n_bytes), width=width).reshape(-1, 8).astype(np.uint64)
         return (bits << np.arange(8, dtype=np.uint64)).sum(axis=-1).astype(np.uint8)
 
     # -- verification (client.rs:147-216) --------------------------------------

@@ -40,6 +40,7 @@
 #define MASK_TAG_KSK 3
 #define MASK_TAG_BSK 4
 #define MASK_TAG_PFPKSK 5
+#define MASK_TAG_LWE 6          /* seeded input ciphertexts (fheaes_expand_lwe_seeded) */
 
 static inline uint32_t rotl32(uint32_t x, int k) { return (x << k) | (x >> (32 - k)); }
 #define CHACHA_QR(a, b, c, d) \
@@ -263,6 +264,27 @@ void fheaes_client_encrypt_bits(const fheaes_params *p, const uint32_t *seed /*[
         for (int j = 0; j < big; ++j) { ct[j] = rng_next(&r); if (glwe_sk[j]) body += ct[j]; }
         body += (uint64_t)(bits[q] & 1) << 63;
         ct[big] = body;
+    }
+}
+
+/* The same encryptions as (public mask key, first index, bodies): ciphertext q of the call takes its kN mask words from the PUBLIC stream
+ * (mask_key, MASK_TAG_LWE, first_index + q) -- what fheaes_expand_lwe_seeded regenerates -- so only body_out [count] travels:
+ * body = noise + sum of the mask words at the set key positions + bit << 63, the noise from the SECRET per-call key `enc_key` as above.
+ * A (mask_key, index) pair must serve ONE ciphertext under ONE secret key (include/fheaes.h): the caller draws a fresh mask_key per call. */
+void fheaes_client_encrypt_bits_seeded(const fheaes_params *p, const uint32_t *enc_key /*[8]*/, const uint32_t *mask_key /*[8]*/, uint64_t first_index,
+                                       const uint8_t *glwe_sk, double sigma, const uint8_t *bits, uint64_t count, uint64_t *body_out)
+{
+    int big = (int)(p->glwe_dimension * NPOLY);
+#pragma omp parallel for schedule(static)
+    for (int64_t q = 0; q < (int64_t)count; ++q) {
+        rng_t r;
+        rng_seed(&r, enc_key, 6, (uint64_t)q);
+        mask_t mk;
+        mask_seed_ct(&mk, mask_key, MASK_TAG_LWE, first_index + (uint64_t)q);
+        uint64_t body = noise_word(&r, sigma);
+        for (int j = 0; j < big; ++j) if (glwe_sk[j]) body += mask_word(&mk, (uint64_t)j);
+        body += (uint64_t)(bits[q] & 1) << 63;
+        body_out[q] = body;
     }
 }
 

@@ -921,6 +921,94 @@ int fheaes_unpack_bits(fheaes_ctx *c, const uint64_t *glwe_in, uint64_t m, uint6
     return s.finish();
 }
 
+// ---- wire formats -----------------------------------------------------------------------------
+static bool mod_width_ok(uint32_t width) { return (width >= 8 && width <= 32) || width == 64; }
+
+static int check_mod_width(fheaes_ctx *c, uint32_t width)
+{
+    if (!mod_width_ok(width)) return c->fail(FHEAES_ERR_INVALID, "width must be in 8..32, or 64 for the words as they are (got %u)", width);
+    return FHEAES_OK;
+}
+
+int fheaes_expand_lwe_seeded(fheaes_ctx *c, const uint32_t *mask_key, uint64_t first_index, const uint64_t *bodies, uint64_t m, uint64_t *lwe_out,
+                             int memspace)
+{
+    CtxLock lock__(c);
+    if (!c) return FHEAES_ERR_INVALID;
+    if (m == 0) return FHEAES_OK;
+    if (!mask_key || !bodies || !lwe_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    const uint64_t in_bytes = m * 8, out_bytes = m * c->big1 * 8;
+    if (overlap(bodies, in_bytes, lwe_out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "bodies and lwe_out overlap (expansion is not in place)");
+    MaskKey mk;
+    memcpy(mk.k, mask_key, 32);
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    TRY(s.in(bodies, in_bytes, &bodies));
+    TRY(s.out(lwe_out, out_bytes, &lwe_out));
+    TRY(expand_lwe_dev(c, mk, first_index, bodies, m, lwe_out));
+    return s.finish();
+}
+
+size_t fheaes_packed_words_mod(const fheaes_ctx *c, uint64_t m, uint32_t width)
+{
+    if (!c || !mod_width_ok(width)) return 0;
+    return (size_t)((m + FHE_N - 1) / FHE_N) * c->k1 * (FHE_N / 64) * width;
+}
+
+int fheaes_packed_mod_switch(fheaes_ctx *c, const uint64_t *glwe_in, uint64_t n_glwe, uint32_t width, uint64_t *out, int memspace)
+{
+    CtxLock lock__(c);
+    if (!c) return FHEAES_ERR_INVALID;
+    TRY(check_mod_width(c, width));
+    if (n_glwe == 0) return FHEAES_OK;
+    if (!glwe_in || !out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    const uint64_t in_bytes = n_glwe * c->k1 * FHE_N * 8, out_bytes = in_bytes / 64 * width;
+    if (overlap(glwe_in, in_bytes, out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "glwe_in and out overlap (the switch is not in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    TRY(s.in(glwe_in, in_bytes, &glwe_in));
+    TRY(s.out(out, out_bytes, &out));
+    if (width == 64) HIP_TRY(c, hipMemcpyAsync(out, glwe_in, in_bytes, hipMemcpyDeviceToDevice, c->stream));
+    else TRY(mod_switch_dev(c, glwe_in, n_glwe, width, out));
+    return s.finish();
+}
+
+int fheaes_pack_bits_mod(fheaes_ctx *c, const uint64_t *lwe_in, uint64_t m, uint32_t width, uint64_t *out, int memspace)
+{
+    CtxLock lock__(c);
+    if (!c) return FHEAES_ERR_INVALID;
+    TRY(check_mod_width(c, width));
+    TRY(check_keys(c));
+    if (m == 0) return FHEAES_OK;
+    if (!lwe_in || !out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    const uint64_t in_bytes = m * c->big1 * 8, out_bytes = (uint64_t)fheaes_packed_words_mod(c, m, width) * 8;
+    if (overlap(lwe_in, in_bytes, out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "lwe_in and out overlap (packing is not in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    TRY(s.in(lwe_in, in_bytes, &lwe_in));
+    TRY(s.out(out, out_bytes, &out));
+    TRY(pack_dev(c, lwe_in, m, out, width));
+    return s.finish();
+}
+
+int fheaes_unpack_bits_mod(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint32_t width, uint64_t *lwe_out, int memspace)
+{
+    CtxLock lock__(c);
+    if (!c) return FHEAES_ERR_INVALID;
+    TRY(check_mod_width(c, width));
+    if (m == 0) return FHEAES_OK;
+    if (!in || !lwe_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    const uint64_t in_bytes = (uint64_t)fheaes_packed_words_mod(c, m, width) * 8, out_bytes = m * c->big1 * 8;
+    if (overlap(in, in_bytes, lwe_out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "in and lwe_out overlap (unpacking is not in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    TRY(s.in(in, in_bytes, &in));
+    TRY(s.out(lwe_out, out_bytes, &lwe_out));
+    if (width == 64) TRY(unpack_dev(c, in, m, lwe_out));
+    else TRY(unpack_mod_dev(c, in, m, width, lwe_out));
+    return s.finish();
+}
+
 // ---- measurement ------------------------------------------------------------------------------
 int fheaes_profile_enable(fheaes_ctx *c, int on)
 {

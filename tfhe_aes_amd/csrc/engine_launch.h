@@ -352,11 +352,23 @@ int launch_key_rows(fheaes_ctx *c, uint64_t *dst, uint64_t dst_stride, const uin
 // ---- packing (fheaes_pack_bits, fheaes_unpack_bits) ---------------------------------------------------------------------------
 static_assert(PACK_N == FHE_N && PACK_N % PACK_FOLD_ROWS == 0, "kern_linear.h's packing kernels are written for N = 512");
 
+// 64-bit GLWEs [n_glwe][(k+1)N] -> [n_glwe][(k+1) 8 width], device pointers, 8 <= width <= 32; the caller holds the StageScope
+static void launch_mod_switch(fheaes_ctx *c, const uint64_t *glwe, uint64_t n_glwe, uint32_t width, uint64_t *out)
+{
+    const uint32_t gsz = c->k1 * FHE_N;
+    const uint64_t total = n_glwe * (gsz / 64 * width);
+    hipLaunchKernelGGL(mod_switch_pack_kernel, dim3((unsigned)std::min<uint64_t>((total + 255) / 256, 65536)), dim3(256), 0, c->stream, glwe, n_glwe, gsz,
+                       width, out);
+}
+
 // in [m][kN+1] -> out [ceil(m/N)][(k+1)N], device pointers.  Chunks start on multiples of N bits, so a GLWE belongs to one chunk.
 // Key block k's switch of a chunk goes into ws_ggsw, the workspace K3 owns: (k+1)N words per bit where a GGSW level takes (k+1)^2 N,
 // so a workspace that fheaes_reserve (or an earlier WoPBS) has sized for b bits holds a chunk of up to 5b here and is not grown;
 // only a context that has less than one GLWE's worth of it allocates (for this call's bits, at most MAX_CHUNK_BITS).
-int pack_dev(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out)
+// width 8..32 (fheaes_pack_bits_mod): every chunk's GLWEs are folded into ws_tmp_a (at most MAX_CHUNK_BITS / N GLWEs; grown, as
+// ws_ggsw is, only by a call that needs more of it than any before: ensure() then synchronises the stream) and
+// switched from there into `out` [ceil(m/N)][(k+1) 8 width]; width 64: straight into `out`.
+int pack_dev(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out, uint32_t width = 64)
 {
     if (m == 0) return FHEAES_OK;
     const uint64_t gsz = (uint64_t)c->k1 * FHE_N;
@@ -366,15 +378,20 @@ int pack_dev(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out)
         TRY(ensure(c, c->ws_ggsw, chunk * gsz * 8));
     }
     chunk = std::min<uint64_t>(chunk, MAX_CHUNK_BITS);
+    if (width != 64) TRY(ensure(c, c->ws_tmp_a, (std::min<uint64_t>(chunk, m) + FHE_N - 1) / FHE_N * gsz * 8));
     uint64_t *ks = (uint64_t *)c->ws_ggsw.p;
     for (uint64_t t0 = 0; t0 < m; t0 += chunk) {
         const uint64_t mc = std::min<uint64_t>(chunk, m - t0), glwes = (mc + FHE_N - 1) / FHE_N;
         TRY(launch_pfpks(c, in + t0 * c->big1, mc, ks, gsz, (int)c->k));
-        uint64_t *o = out + t0 / FHE_N * gsz;
+        uint64_t *o = width == 64 ? out + t0 / FHE_N * gsz : (uint64_t *)c->ws_tmp_a.p;
         StageScope sc(c, FHEAES_STAGE_LINEAR, mc);
         HIP_TRY(c, hipMemsetAsync(o, 0, glwes * gsz * 8, c->stream));
         hipLaunchKernelGGL(pack_fold_kernel, dim3(FHE_N / PACK_FOLD_ROWS, c->k1, (unsigned)glwes), dim3(256), 0, c->stream, ks, mc, c->k1, o);
         HIP_TRY(c, hipGetLastError());
+        if (width != 64) {
+            launch_mod_switch(c, o, glwes, width, out + t0 / FHE_N * (gsz / 64 * width));
+            HIP_TRY(c, hipGetLastError());
+        }
     }
     return FHEAES_OK;
 }
@@ -387,6 +404,45 @@ int unpack_dev(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out)
         StageScope sc(c, FHEAES_STAGE_LINEAR, mc);
         hipLaunchKernelGGL(sample_extract_kernel, dim3((unsigned)((mc + UNPACK_BITS_PER_WG - 1) / UNPACK_BITS_PER_WG)), dim3(256), 0, c->stream,
                            in + t0 / FHE_N * (uint64_t)c->k1 * FHE_N, mc, c->k, out + t0 * c->big1);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return FHEAES_OK;
+}
+
+// fheaes_packed_mod_switch on device pointers, in chunks of MAX_CHUNK_BITS / N GLWEs
+int mod_switch_dev(fheaes_ctx *c, const uint64_t *in, uint64_t n_glwe, uint32_t width, uint64_t *out)
+{
+    const uint64_t gsz = (uint64_t)c->k1 * FHE_N, step = MAX_CHUNK_BITS / FHE_N;
+    for (uint64_t g0 = 0; g0 < n_glwe; g0 += step) {
+        const uint64_t gc = std::min<uint64_t>(step, n_glwe - g0);
+        StageScope sc(c, FHEAES_STAGE_LINEAR, gc * FHE_N);
+        launch_mod_switch(c, in + g0 * gsz, gc, width, out + g0 * (gsz / 64 * width));
+        HIP_TRY(c, hipGetLastError());
+    }
+    return FHEAES_OK;
+}
+
+// in [ceil(m/N)][(k+1) 8 width] -> out [m][kN+1], device pointers: unpack_dev reading width-bit fields
+int unpack_mod_dev(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint32_t width, uint64_t *out)
+{
+    for (uint64_t t0 = 0; t0 < m; t0 += MAX_CHUNK_BITS) {
+        const uint64_t mc = std::min<uint64_t>(MAX_CHUNK_BITS, m - t0);
+        StageScope sc(c, FHEAES_STAGE_LINEAR, mc);
+        hipLaunchKernelGGL(sample_extract_mod_kernel, dim3((unsigned)((mc + UNPACK_BITS_PER_WG - 1) / UNPACK_BITS_PER_WG)), dim3(256), 0, c->stream,
+                           in + t0 / FHE_N * (uint64_t)c->k1 * 8 * width, mc, c->k, width, out + t0 * c->big1);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return FHEAES_OK;
+}
+
+// bodies [m] -> out [m][kN+1], device pointers: ciphertext t carries the masks of index first_index + t (mod 2^64)
+int expand_lwe_dev(fheaes_ctx *c, const MaskKey &key, uint64_t first_index, const uint64_t *bodies, uint64_t m, uint64_t *out)
+{
+    for (uint64_t t0 = 0; t0 < m; t0 += MAX_CHUNK_BITS) {
+        const uint64_t mc = std::min<uint64_t>(MAX_CHUNK_BITS, m - t0);
+        StageScope sc(c, FHEAES_STAGE_LINEAR, mc);
+        hipLaunchKernelGGL(expand_lwe_kernel, dim3((unsigned)((mc * c->k + 3) / 4)), dim3(256), 0, c->stream, out + t0 * c->big1, bodies + t0, mc, c->k,
+                           first_index + t0, key);
         HIP_TRY(c, hipGetLastError());
     }
     return FHEAES_OK;

@@ -312,3 +312,103 @@ __global__ __launch_bounds__(256) void sample_extract_kernel(const uint64_t *pac
         if (threadIdx.x == 0) o[big] = glwe[(uint64_t)big + i];
     }
 }
+
+// ---- wire formats (include/fheaes.h): seeded input ciphertexts, modulus-switched packed outputs --------------------------------------
+// fheaes_expand_lwe_seeded: lwe[t] = [ mask words of ciphertext first + t | bodies[t] ], mask word j = 64-bit word j % 8 of ChaCha20
+// block j / 8 under (key, nonce = (EXPAND_LWE_TAG, q low 32, q high 32)), q = first + t: expand_masks_kernel's stream for the shape
+// mask_words = kN = 512 k, one body word.  A lane computes one block (8 words); the 64 blocks of a wave are one contiguous run of 512
+// words of ONE ciphertext (kN / 8 = 64 k blocks).  Stored lane by lane, every store instruction would touch 64 separate 64-byte runs;
+// the wave's blocks go through LDS instead and come back word e * 64 + lane, so that each of the 8 store instructions of a wave covers
+// one run of 512 bytes.  LDS rows have 9 words: the b64 writes of a half wave (word 9 lane + e) fall on 32 different bank pairs.  The
+// padding serves the writes only: a half wave reads words j + (j >> 3) of 32 consecutive j, that is 0..7, 9..16, 18..25, 27..34 past its
+// first, and 32..34 share bank pairs with 0..2 -- three 2-way conflicts in each of the 8 b64 reads, a few cycles next to the ~1,000
+// instructions of the block function, so no swizzle is spent on them.  A row of the output has kN + 1 words, so rows are 8-byte aligned
+// and no more: 8-byte stores.  One workgroup = 4 waves = 4 runs; nothing is read but the bodies.
+// A wave touches tile[wave] alone, so a wave-level wait for its LDS writes would do; the workgroup barrier is kept because it is the
+// plain form, and every wave must reach it: a wave past the last run (`live` false, the last workgroup of a launch) skips the block
+// function and the stores but returns only AFTER the barrier.
+#define EXPAND_LWE_TAG 6u            /* MASK_TAG_LWE of csrc/client.c */
+#define EXPAND_LWE_ROW 9             /* LDS words per block: 8 + 1 of padding */
+// bodies: [m]; lwe: [m][64 k * 8 + 1]; runs = m * k waves of work
+__global__ __launch_bounds__(256) void expand_lwe_kernel(uint64_t *lwe, const uint64_t *bodies, uint64_t m, uint32_t k, uint64_t first, MaskKey key)
+{
+    __shared__ uint64_t tile[4][64 * EXPAND_LWE_ROW];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t run = (uint64_t)blockIdx.x * 4 + wave;              // run r: blocks 64 (r % k) .. of ciphertext r / k
+    const bool live = run < m * k;
+    const uint64_t t = run / k;
+    const uint32_t part = (uint32_t)(run - t * k);
+    uint64_t *row = tile[wave];
+    if (live) {
+        const uint64_t q = first + t;
+        uint32_t w[16];
+        fheaes_chacha20_block(key, part * 64 + lane, EXPAND_LWE_TAG, (uint32_t)q, (uint32_t)(q >> 32), w);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) row[lane * EXPAND_LWE_ROW + e] = (uint64_t)w[2 * e] | ((uint64_t)w[2 * e + 1] << 32);
+    }
+    __syncthreads();
+    if (!live) return;
+    const uint32_t big = k * PACK_N;
+    uint64_t *o = lwe + t * (uint64_t)(big + 1) + (uint64_t)part * PACK_N;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const uint32_t j = e * 64 + lane;                              // word j of the run: block j / 8, word j % 8
+        o[j] = row[(j >> 3) * EXPAND_LWE_ROW + (j & 7)];
+    }
+    if (part == k - 1 && lane == 0) lwe[t * (uint64_t)(big + 1) + big] = bodies[t];
+}
+
+// fheaes_packed_mod_switch: word x of a packed GLWE -> the w-bit value v = ((x + 2^(63-w)) >> (64-w)) mod 2^w (the sum wraps in
+// uint64: words within 2^(63-w) of 2^64 round to 0), field e = jN + c at bits [e w, (e+1) w) of the GLWE's little-endian bit string.
+// One thread per OUTPUT word: it gathers the at most ceil(64 / w) + 1 fields that touch its 64 bits, so no two threads write one
+// word.  A GLWE is (k+1) N w / 64 = (k+1) 8 w whole words.  8 <= w <= 32.
+// glwe: [n_glwe][glwe_words]; out: [n_glwe][glwe_words * w / 64]
+__global__ __launch_bounds__(256) void mod_switch_pack_kernel(const uint64_t *glwe, uint64_t n_glwe, uint32_t glwe_words, uint32_t w, uint64_t *out)
+{
+    const uint32_t out_words = glwe_words / 64 * w;
+    const uint64_t total = n_glwe * out_words;
+    const uint64_t half = 1ull << (63 - w);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t g = i / out_words;
+        const uint32_t o = (uint32_t)(i - g * out_words);
+        const uint64_t *src = glwe + g * glwe_words;
+        const uint32_t bit0 = o * 64;                                  // < 2560 * 32: fits
+        const uint32_t e0 = bit0 / w, e1 = (bit0 + 63) / w;            // e1 <= glwe_words - 1: the bit string ends with the last field
+        uint64_t acc = 0;
+        for (uint32_t e = e0; e <= e1; ++e) {
+            const uint64_t v = (src[e] + half) >> (64 - w);
+            const uint32_t at = e * w;
+            acc |= at >= bit0 ? v << (at - bit0) : v >> (bit0 - at);
+        }
+        out[i] = acc;
+    }
+}
+
+// field e of a switched GLWE, read back: x' = v << (64 - w), from one or two words
+__device__ __forceinline__ uint64_t mod_field(const uint64_t *glwe, uint32_t e, uint32_t w)
+{
+    const uint32_t bit = e * w, word = bit >> 6, off = bit & 63;
+    uint64_t v = glwe[word] >> off;
+    if (off + w > 64) v |= glwe[word + 1] << (64 - off);               // the field straddles two words (off > 0 here)
+    return v << (64 - w);
+}
+
+// sample_extract_kernel reading the w-bit fields: word for word the extraction of the read-back GLWEs
+// in: [ceil(m / N)][(k + 1) 8 w]; lwe: [m][kN + 1]
+__global__ __launch_bounds__(256) void sample_extract_mod_kernel(const uint64_t *in, uint64_t m, uint32_t k, uint32_t w, uint64_t *lwe)
+{
+    const uint32_t big = k * PACK_N;
+    for (uint32_t u = 0; u < UNPACK_BITS_PER_WG; ++u) {
+        const uint64_t t = (uint64_t)blockIdx.x * UNPACK_BITS_PER_WG + u;
+        if (t >= m) return;
+        const uint32_t i = (uint32_t)(t & (PACK_N - 1));
+        const uint64_t *glwe = in + (t / PACK_N) * (uint64_t)(k + 1) * 8 * w;
+        uint64_t *o = lwe + t * (uint64_t)(big + 1);
+        for (uint32_t x = threadIdx.x; x < big; x += blockDim.x) {
+            const uint32_t c = x & (PACK_N - 1);
+            const uint64_t v = mod_field(glwe, (x - c) + ((i - c) & (PACK_N - 1)), w);
+            o[x] = c <= i ? v : (uint64_t)0 - v;
+        }
+        if (threadIdx.x == 0) o[big] = mod_field(glwe, big + i, w);
+    }
+}

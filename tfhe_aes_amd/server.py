@@ -24,7 +24,7 @@ import numpy as np
 
 from . import _native
 from .aes_clear import INV_SBOX, SBOX, mul2, mul3, mul9, mul11, mul13, mul14  # noqa: F401  (re-exported like sbox.rs)
-from .client import ServerKeys
+from .client import SeededCiphertexts, ServerKeys, packed_mod_words
 from .params import WopbsParameters
 
 
@@ -305,39 +305,73 @@ class Server:
         return self._many_out(round_keys, (n_blocks, 16, 8, self.params.big1), out)
 
     # ---- packed ciphertexts ------------------------------------------------------
-    def pack(self, ct, out=None):
+    def pack(self, ct, out=None, width: int = 64):
         """any [..., kN+1] array of one-bit LWE ciphertexts -> [G][(k+1)N], G = ceil(m / N) GLWE ciphertexts holding N = 512 bits each, in
         the memory space of `ct`: bit t of the flattened input sits in GLWE t // N, coefficient t % N (include/fheaes.h:
-        fheaes_pack_bits).  409.8 times smaller at PARAM_OPT; no key beyond the ones the Server holds; Client.decrypt_packed reads it."""
+        fheaes_pack_bits).  409.8 times smaller at PARAM_OPT; no key beyond the ones the Server holds; Client.decrypt_packed reads it.
+        `width` in 8..32: the words modulus-switched to `width` bits each, [G][(k+1) 8 width] (fheaes_pack_bits_mod; 16 is the width the
+        header's noise arithmetic clears for PARAM_OPT: another 4 times smaller); Client.decrypt_packed(..., width=) reads that."""
         p = self.params
         if int(ct.shape[-1]) != p.big1:
             raise ValueError("pack takes [..., kN+1] = [..., %d] words, got shape %s" % (p.big1, tuple(ct.shape)))
         m = 1
         for d in ct.shape[:-1]:
             m *= int(d)
-        shape = ((m + p.N - 1) // p.N, (p.k + 1) * p.N)
+        shape = ((m + p.N - 1) // p.N, packed_mod_words(p, width))
         if out is None:
             out = _empty_like(ct, shape)
         elif tuple(out.shape) != shape:
             raise ValueError("out must be %s, got %s" % (shape, tuple(out.shape)))
-        if m:
+        if m and width == 64:
             self.engine.pack_bits(ct, m, out)
+        elif m:
+            self.engine.pack_bits_mod(ct, m, width, out)
         return out
 
-    def unpack(self, packed, shape, out=None):
+    def unpack(self, packed, shape, out=None, width: int = 64):
         """the inverse shape: [G][(k+1)N] -> [*shape, kN+1] (sample extraction of coefficient t % N of GLWE t // N for bit t), LWE
-        ciphertexts under the big key that every entry point takes; `shape` may be an int (the number of bits)."""
+        ciphertexts under the big key that every entry point takes; `shape` may be an int (the number of bits).  `width` in 8..32:
+        `packed` is the switched form [G][(k+1) 8 width] and the extraction reads its fields (fheaes_unpack_bits_mod)."""
         p = self.params
         shape = (int(shape),) if isinstance(shape, int) else tuple(int(d) for d in shape)
         m = 1
         for d in shape:
             m *= d
-        if tuple(packed.shape) != ((m + p.N - 1) // p.N, (p.k + 1) * p.N):
-            raise ValueError("%d bits are packed as [%d][%d] words, got shape %s" % (m, (m + p.N - 1) // p.N, (p.k + 1) * p.N, tuple(packed.shape)))
+        gw = packed_mod_words(p, width)
+        if tuple(packed.shape) != ((m + p.N - 1) // p.N, gw):
+            raise ValueError("%d bits are packed as [%d][%d] words, got shape %s" % (m, (m + p.N - 1) // p.N, gw, tuple(packed.shape)))
         if out is None:
             out = _empty_like(packed, shape + (p.big1,))
-        if m:
+        if m and width == 64:
             self.engine.unpack_bits(packed, m, out)
+        elif m:
+            self.engine.unpack_bits_mod(packed, m, width, out)
+        return out
+
+    # ---- seeded input ciphertexts ------------------------------------------------
+    def expand(self, seeded: SeededCiphertexts, out=None):
+        """SeededCiphertexts (public mask key, first index, bodies [...]) -> the full ciphertexts [..., kN+1], the masks regenerated on the
+        GPU (fheaes_expand_lwe_seeded): word for word seeded.expand().  A host array, or -- when `out` is a resident tensor or the bodies
+        are one -- a resident tensor, enqueued on the engine's stream; needs no keys."""
+        p = self.params
+        if seeded.params != p:
+            raise ValueError("these ciphertexts were made for %s, the server runs %s" % (seeded.params.name, p.name))
+        bodies = seeded.bodies
+        shape = tuple(int(d) for d in bodies.shape) + (p.big1,)
+        if out is None:
+            out = _empty_like(bodies, shape)
+        elif tuple(out.shape) != shape:
+            raise ValueError("out must be %s, got %s" % (shape, tuple(out.shape)))
+        if isinstance(bodies, np.ndarray):
+            bodies = np.ascontiguousarray(bodies, dtype=np.uint64)
+            if not isinstance(out, np.ndarray):
+                bodies = _to_space(bodies, out)
+                self._inflight.append(bodies)             # device call: only enqueued, the copy of the bodies is still being read
+        m = 1
+        for d in shape[:-1]:
+            m *= d
+        if m:
+            self.engine.expand_lwe_seeded(seeded.mask_key, seeded.first_index, bodies, m, out)
         return out
 
     # README.md:57-59 spellings
@@ -492,7 +526,7 @@ class ServerGroup:
 
         return [shard_blocks(n_glwes, len(self.servers), i) for i in range(len(self.servers))]
 
-    def pack(self, ct):
+    def pack(self, ct, width: int = 64):
         """Server.pack, sharded on whole GLWEs (N bits = 4 AES blocks): context i packs GLWEs i * G / n .. of the flattened input, so the
         words are those of one context whatever the number of contexts"""
         p = self.params
@@ -500,30 +534,49 @@ class ServerGroup:
             raise ValueError("pack takes [..., kN+1] = [..., %d] words, got shape %s" % (p.big1, tuple(ct.shape)))
         flat = ct.reshape(-1, p.big1)
         m = int(flat.shape[0])
-        out = _empty_like(ct, ((m + p.N - 1) // p.N, (p.k + 1) * p.N))
+        out = _empty_like(ct, ((m + p.N - 1) // p.N, packed_mod_words(p, width)))
         jobs = []
         for lo, hi in self._glwe_shards(int(out.shape[0])):
             b0, b1 = lo * p.N, min(hi * p.N, m)
-            jobs.append(None if hi <= lo else (lambda s, lo=lo, hi=hi, b0=b0, b1=b1: s.pack(flat[b0:b1], out=out[lo:hi])))
+            jobs.append(None if hi <= lo else (lambda s, lo=lo, hi=hi, b0=b0, b1=b1: s.pack(flat[b0:b1], out=out[lo:hi], width=width)))
         self._run_shards(jobs)
         return out
 
-    def unpack(self, packed, shape):
+    def unpack(self, packed, shape, width: int = 64):
         """Server.unpack with the same split: context i extracts the bits of its GLWEs"""
         p = self.params
         shape = (int(shape),) if isinstance(shape, int) else tuple(int(d) for d in shape)
         m = 1
         for d in shape:
             m *= d
-        if tuple(packed.shape) != ((m + p.N - 1) // p.N, (p.k + 1) * p.N):
-            raise ValueError("%d bits are packed as [%d][%d] words, got shape %s" % (m, (m + p.N - 1) // p.N, (p.k + 1) * p.N, tuple(packed.shape)))
+        gw = packed_mod_words(p, width)
+        if tuple(packed.shape) != ((m + p.N - 1) // p.N, gw):
+            raise ValueError("%d bits are packed as [%d][%d] words, got shape %s" % (m, (m + p.N - 1) // p.N, gw, tuple(packed.shape)))
         out = _empty_like(packed, (m, p.big1))
         jobs = []
         for lo, hi in self._glwe_shards(int(packed.shape[0])):
             b0, b1 = lo * p.N, min(hi * p.N, m)
-            jobs.append(None if hi <= lo else (lambda s, lo=lo, hi=hi, b0=b0, b1=b1: s.unpack(packed[lo:hi], b1 - b0, out=out[b0:b1])))
+            jobs.append(None if hi <= lo else (lambda s, lo=lo, hi=hi, b0=b0, b1=b1: s.unpack(packed[lo:hi], b1 - b0, out=out[b0:b1], width=width)))
         self._run_shards(jobs)
         return out.reshape(shape + (p.big1,))
+
+    def expand(self, seeded: SeededCiphertexts):
+        """Server.expand, sharded on ciphertexts: context i expands ciphertexts i * G / n .. of the flattened list and passes
+        first_index + its offset, so the words are those of one context"""
+        import dataclasses
+
+        from .dist import shard_blocks
+
+        p = self.params
+        flat = seeded.bodies.reshape(-1)
+        m, g = int(flat.shape[0]), len(self.servers)
+        out = _empty_like(flat, (m, p.big1))
+        jobs = []
+        for lo, hi in (shard_blocks(m, g, i) for i in range(g)):
+            part = dataclasses.replace(seeded, first_index=(int(seeded.first_index) + lo) % (1 << 64), bodies=flat[lo:hi])
+            jobs.append(None if hi <= lo else (lambda s, part=part, lo=lo, hi=hi: s.expand(part, out=out[lo:hi])))
+        self._run_shards(jobs)
+        return out.reshape(tuple(int(d) for d in seeded.bodies.shape) + (p.big1,))
 
     def clone_info(self):
         """per cloned context: how its keys got there ({"path": "same_device" | "peer" | "staged", "bytes", "seconds"})"""
