@@ -405,6 +405,33 @@ int fheaes_k2_set_parking(fheaes_ctx *ctx, int claimed);
  * setting; with the pair denied the paired kernel's parking pool and owner words are not touched.  Per context: other contexts and
  * the plans of k = 1 (which has neither form) are unaffected.  Synchronises the context's stream. */
 int fheaes_k2_set_forms(fheaes_ctx *ctx, int allow_pair, int allow_home);
+/* How the block ciphers cut their work into blind-rotation launches.  fheaes_aes_encrypt, fheaes_aes_decrypt_equivalent (`steps` = Nr
+ * WoPBS per block) and fheaes_aes_decrypt (`steps` = 2 Nr - 1) on `n_blocks` blocks are `steps` x `n_blocks` block-rounds of 128 bits, and
+ * a round of block b needs only the round before it of the same block.  Round by round, every one of the `steps` launches ends in a partly
+ * filled generation of one workgroup per compute unit, which costs nearly a full one (16,384 bits on 256 CUs: 11 generations for 10.67 of
+ * work).  ROLLED, the block-rounds are taken as one stream in (step, block) order and cut into windows of `window_blocks` blocks whose bits
+ * are a whole number of six-ciphertext generations: only the call's last launch has a partial generation.  A window covers the end of one
+ * step and the start of the next; the words of every block are those of the round-by-round schedule.
+ * This is the decision, host logic only and DEVICE-INDEPENDENT like fheaes_k2_launch_plan: roll when the launch of the full batch
+ * (min(n_blocks x 128, 32,768) bits) takes the paired form, n_blocks x 128 bits are not whole generations of 6 x cu_count, and the rolled
+ * schedule has strictly fewer generations than the round-by-round one, both counted with fheaes_k2_launch_plan (a launch of up to 768 bits
+ * counts as one).  The window is the largest multiple of lcm(128, 6 cu_count) / 128 blocks (12 on 256 CUs, 57 on 304) that exceeds neither
+ * n_blocks nor 256 blocks.  `window_blocks` = 0: not rolled; then `launches` and `generations` are the round-by-round schedule's.  Rolled,
+ * `launches` = ceil(steps x n_blocks / window_blocks).  128 blocks, 10 steps, 256 CUs: window 120, 11 launches, 107 generations for 110.
+ * FHEAES_ERR_INVALID: a null output, n_blocks, steps or cu_count of 0. */
+int fheaes_aes_window_plan(uint64_t n_blocks, uint32_t steps, uint32_t cu_count, uint32_t k, uint64_t *window_blocks, uint64_t *launches,
+                           uint64_t *generations, uint64_t *generations_by_round);
+/* The window THIS context uses for `steps` WoPBS over `n_blocks` blocks: fheaes_aes_window_plan for its device's compute units and the form its
+ * launches really take (after the occupancy fallbacks and fheaes_k2_set_forms: a context without the paired kernel never rolls), or what
+ * fheaes_aes_set_window set.  0: round by round. */
+int fheaes_aes_context_window(fheaes_ctx *ctx, uint64_t n_blocks, uint32_t steps, uint64_t *window_blocks);
+/* `window_blocks` = 0 (default): automatic, as above.  FHEAES_AES_WINDOW_OFF: one launch per round, the schedule without windows, for
+ * word-exact comparison and same-process timing.  Any other value forces that window, clamped to n_blocks and to 256 blocks, whatever
+ * the form of the blind rotation: every window in 1..n_blocks is a correct schedule, so the small parameter set can exercise every
+ * shape of segment (tests/test_gpu_aes_windows.py).  Per context, like fheaes_k2_set_forms.  Synchronises the context's stream.  The
+ * public-block / CTR calls, the key expansion and fheaes_add_scalar are not windowed. */
+#define FHEAES_AES_WINDOW_OFF 0xFFFFFFFFu
+int fheaes_aes_set_window(fheaes_ctx *ctx, uint32_t window_blocks);
 /* Test hook of the claimed parking slots (tests/test_gpu_park_slots.py).  The pool is FHEAES_K2_PARK_SLOTS owner words, 128 per XCC
  * (0 = free, else 1 + the index of the owning workgroup).  `initial_owner` (host, FHEAES_K2_PARK_SLOTS words) non-NULL: every
  * claimed-mode paired launch starts from a copy of these words instead of zeros -- a nonzero word is a slot someone else owns for the

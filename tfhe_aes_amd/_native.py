@@ -16,6 +16,7 @@ from . import _build
 from .params import CParams, WopbsParameters
 
 HOST, DEVICE = 0, 1
+AES_WINDOW_OFF = 0xFFFFFFFF     # FHEAES_AES_WINDOW_OFF: fheaes_aes_set_window's "one launch per round"
 K2_PARK_SLOTS = 1024            # FHEAES_K2_PARK_SLOTS: owner words of the paired kernel's shared parking slots, 128 per XCC
 STAGES = ("keyswitch", "blind_rotate", "pfpks", "ggsw_fft", "vertical_packing", "linear")
 
@@ -93,6 +94,9 @@ SIGNATURES = {
                                         _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32), _c.c_char_p, _c.c_size_t]),
     "fheaes_k2_set_parking": (_c.c_int, [_ctx, _c.c_int]),
     "fheaes_k2_set_forms": (_c.c_int, [_ctx, _c.c_int, _c.c_int]),
+    "fheaes_aes_window_plan": (_c.c_int, [_c.c_uint64, _c.c_uint32, _c.c_uint32, _c.c_uint32, _u64p, _u64p, _u64p, _u64p]),
+    "fheaes_aes_context_window": (_c.c_int, [_ctx, _c.c_uint64, _c.c_uint32, _u64p]),
+    "fheaes_aes_set_window": (_c.c_int, [_ctx, _c.c_uint32]),
     "fheaes_k2_park_debug": (_c.c_int, [_ctx, _c.POINTER(_c.c_uint32), _c.c_int]),
     "fheaes_k2_park_read": (_c.c_int, [_ctx, _u64p, _u64p, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32), _c.c_uint64, _u64p]),
     "fheaes_version": (_c.c_char_p, []),
@@ -418,6 +422,16 @@ class Engine:
         refused occupancy query does; True restores "whatever the query allows", never more.  k2_plan reports what launches"""
         self._check(self._lib.fheaes_k2_set_forms(self._h, 1 if allow_pair else 0, 1 if allow_home else 0))
 
+    def aes_window(self, n_blocks: int, steps: int) -> int:
+        """the window, in blocks, this context cuts `steps` WoPBS over n_blocks blocks into (fheaes_aes_context_window); 0: round by round"""
+        w = _c.c_uint64()
+        self._check(self._lib.fheaes_aes_context_window(self._h, n_blocks, steps, _c.byref(w)))
+        return w.value
+
+    def aes_set_window(self, window_blocks: int = 0):
+        """fheaes_aes_set_window: 0 = automatic (default), AES_WINDOW_OFF = one launch per round, else that window forced (test hook)"""
+        self._check(self._lib.fheaes_aes_set_window(self._h, int(window_blocks)))
+
     def k2_park_debug(self, initial=None, record: bool = False):
         """test hook (fheaes_k2_park_debug): claimed-mode paired launches start from the owner words `initial` (K2_PARK_SLOTS words;
         nonzero = taken for the whole launch) instead of zeros, None restores the default; `record`: each such launch records
@@ -496,6 +510,15 @@ def aes_public_plan(blocks, key_bits: int = 128) -> list[int]:
     if rc != 0:
         raise FheAesError(rc, "fheaes_aes_public_plan: key_bits must be 128, 192 or 256")
     return [int(x) for x in out[:{128: 10, 192: 12, 256: 14}[key_bits]]]
+
+
+def aes_window_plan(n_blocks: int, steps: int, cu_count: int = 256, k: int = 4) -> dict:
+    """fheaes_aes_window_plan (host only, no GPU): {"window", "launches", "generations", "generations_by_round"}; window 0 = not rolled"""
+    w, la, g, gr = _c.c_uint64(), _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
+    rc = load_library().fheaes_aes_window_plan(n_blocks, steps, cu_count, k, _c.byref(w), _c.byref(la), _c.byref(g), _c.byref(gr))
+    if rc != 0:
+        raise FheAesError(rc, "fheaes_aes_window_plan: n_blocks, steps and cu_count must be at least 1")
+    return {"window": w.value, "launches": la.value, "generations": g.value, "generations_by_round": gr.value}
 
 
 def get_twiddles() -> np.ndarray:

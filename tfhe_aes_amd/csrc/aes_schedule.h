@@ -18,61 +18,113 @@ static int check_key_bits(fheaes_ctx *c, uint32_t key_bits)
     return FHEAES_OK;
 }
 
-static int aes_encrypt_dev(fheaes_ctx *c, const KeySets &rk, uint64_t *state, uint64_t n_blocks, int nr)
+// A block cipher is an initial AddRoundKey and a list of steps.  A step: a WoPBS with LUT set `set` on every state byte, then the linear
+// layer `table` over its n_luts outputs per byte plus round key `key_round` of the call's keys (< 0: none), written over the state.
+struct AesStep { int set; uint32_t n_luts; GatherTable table; int key_round; };
+struct AesSchedule {
+    int first_key_round = 0;
+    uint32_t max_luts = 0;
+    std::vector<AesStep> steps;
+    void add(int set, uint32_t n_luts, const GatherTable &t, int key_round) { steps.push_back({set, n_luts, t, key_round}); max_luts = std::max(max_luts, n_luts); }
+};
+
+static AesSchedule aes_encrypt_schedule(int nr)
 {
-    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
-    TRY(ensure(c, c->ws_vp, nbytes * 3 * bw * 8));
-    uint64_t *vp = (uint64_t *)c->ws_vp.p;
-    const GatherTable t_round = table_enc_round(), t_shift = table_shift_rows(false);
-    TRY(launch_add_bcast(c, state, rk, sw, n_blocks));                                   // server.rs:42
-    for (int round = 1; round < nr; ++round) {                                           // server.rs:44-57
-        TRY(many_sbox_dev(c, state, nbytes, LUTSET_ENC_ROUND, vp));
-        TRY(launch_gather(c, vp, 3, rk.round(round, sw), state, n_blocks, t_round));
-    }
-    TRY(many_sbox_dev(c, state, nbytes, LUTSET_SBOX, vp));                               // server.rs:59-63
-    TRY(launch_gather(c, vp, 1, rk.round(nr, sw), state, n_blocks, t_shift));
-    return FHEAES_OK;
+    AesSchedule s;
+    s.first_key_round = 0;                                                               // server.rs:42
+    for (int round = 1; round < nr; ++round) s.add(LUTSET_ENC_ROUND, 3, table_enc_round(), round);          // server.rs:44-57
+    s.add(LUTSET_SBOX, 1, table_shift_rows(false), nr);                                  // server.rs:59-63
+    return s;
 }
 
-static int aes_decrypt_dev(fheaes_ctx *c, const KeySets &rk, uint64_t *state, uint64_t n_blocks, int nr)
+// the reference's own schedule (server.rs:67-105): 2 Nr - 1 WoPBS per block
+static AesSchedule aes_decrypt_schedule(int nr)
 {
-    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
-    TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
-    uint64_t *vp = (uint64_t *)c->ws_vp.p;
-    const GatherTable t_inv = table_shift_rows(true), t_mix = table_dec_mix();
-    const KeySets no_key{nullptr, nullptr, 0};
-    TRY(launch_add_bcast(c, state, rk.round(nr, sw), sw, n_blocks));                     // server.rs:70
+    AesSchedule s;
+    s.first_key_round = nr;                                                              // server.rs:70
     for (int round = nr; round >= 2; --round) {                                          // server.rs:72-96
         // inv_shift_rows commutes with the bytewise S-Box: INV_SBOX first, then the permutation + round key
-        TRY(many_sbox_dev(c, state, nbytes, LUTSET_INV_SBOX, vp));
-        TRY(launch_gather(c, vp, 1, rk.round(round - 1, sw), state, n_blocks, t_inv));
-        TRY(many_sbox_dev(c, state, nbytes, LUTSET_DEC_MUL, vp));
-        TRY(launch_gather(c, vp, 4, no_key, state, n_blocks, t_mix));
+        s.add(LUTSET_INV_SBOX, 1, table_shift_rows(true), round - 1);
+        s.add(LUTSET_DEC_MUL, 4, table_dec_mix(), -1);
     }
-    TRY(many_sbox_dev(c, state, nbytes, LUTSET_INV_SBOX, vp));                           // server.rs:98-104
-    TRY(launch_gather(c, vp, 1, rk, state, n_blocks, t_inv));
-    return FHEAES_OK;
+    s.add(LUTSET_INV_SBOX, 1, table_shift_rows(true), 0);                                // server.rs:98-104
+    return s;
 }
 
 // The equivalent inverse cipher (FIPS-197 section 5.3.5, Fig. 15): InvMixColumns is linear, so IMC(InvS(x)) + IMC(w[r]) is one WoPBS
 // per byte with the composed tables {9, 11, 13, 14} * InvS[x] (LUTSET_DEC_EQ_ROUND), summed through the InvShiftRows-folded gather with
-// dw[r] = IMC(w[r]) as the round key: Nr WoPBS per block like aes_encrypt_dev, against the 2 Nr - 1 of aes_decrypt_dev (the reference's own
+// dw[r] = IMC(w[r]) as the round key: Nr WoPBS per block like encryption, against the 2 Nr - 1 of aes_decrypt_schedule (the reference's own
 // schedule, server.rs:67-105, which says at :86-89 that it almost doubles the time of encryption).  dw: fheaes_aes_decryption_round_keys.
-static int aes_decrypt_eq_dev(fheaes_ctx *c, const KeySets &dw, uint64_t *state, uint64_t n_blocks, int nr)
+static AesSchedule aes_decrypt_eq_schedule(int nr)
 {
-    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, nbytes = 16 * n_blocks;
-    TRY(ensure(c, c->ws_vp, nbytes * 4 * bw * 8));
+    AesSchedule s;
+    s.first_key_round = nr;
+    for (int round = nr - 1; round >= 1; --round) s.add(LUTSET_DEC_EQ_ROUND, 4, table_dec_eq_round(), round);   // 4 WoPBS outputs + dw[round] = 5
+    s.add(LUTSET_INV_SBOX, 1, table_shift_rows(true), 0);
+    return s;
+}
+
+// Runs a schedule over n blocks.  Window 0 (aes_context_window): step by step, one WoPBS over all blocks each.  Window w: the steps x n
+// block-rounds, in (step, block) order, are cut into launches of w; launch j covers stream indices [j w, j w + w), at most two segments:
+// blocks [b0, n) of step s and blocks [0, b1) of step s + 1, b1 <= b0.  K1 reads each segment from its place in the state into consecutive
+// rows of ws_small; K2, K3 and K4 run once over the window; K5 once, or per segment where the two steps' LUT sets differ (the second
+// segment's outputs lie behind the first's in ws_vp); the linear layer per segment, over the state in place.  Segments are whole blocks of
+// 128 ciphertexts, K1's tile.  No block is twice in a window (w <= n), so a launch reads only what the launches before it wrote.
+static int aes_run_dev(fheaes_ctx *c, const KeySets &rk, uint64_t *state, uint64_t n_blocks, const AesSchedule &sch)
+{
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, steps = sch.steps.size();
+    auto key_of = [&](const AesStep &st, uint64_t first_block) {
+        if (st.key_round < 0) return KeySets{nullptr, nullptr, 0};
+        return KeySets{rk.rk + (uint64_t)st.key_round * sw, rk.of_block ? rk.of_block + first_block : nullptr, rk.stride};
+    };
+    const uint64_t w = aes_context_window(c, n_blocks, steps);
+    TRY(ensure(c, c->ws_vp, (w ? w : n_blocks) * 16 * sch.max_luts * bw * 8));
     uint64_t *vp = (uint64_t *)c->ws_vp.p;
-    const GatherTable t_round = table_dec_eq_round(), t_inv = table_shift_rows(true);
-    TRY(launch_add_bcast(c, state, dw.round(nr, sw), sw, n_blocks));
-    for (int round = nr - 1; round >= 1; --round) {
-        TRY(many_sbox_dev(c, state, nbytes, LUTSET_DEC_EQ_ROUND, vp));
-        TRY(launch_gather(c, vp, 4, dw.round(round, sw), state, n_blocks, t_round));     // 4 WoPBS outputs + dw[round] = 5
+    TRY(launch_add_bcast(c, state, rk.round((uint64_t)sch.first_key_round, sw), sw, n_blocks));
+    if (w == 0) {
+        for (const AesStep &st : sch.steps) {
+            TRY(many_sbox_dev(c, state, 16 * n_blocks, st.set, vp));
+            TRY(launch_gather(c, vp, st.n_luts, key_of(st, 0), state, n_blocks, st.table));
+        }
+        return FHEAES_OK;
     }
-    TRY(many_sbox_dev(c, state, nbytes, LUTSET_INV_SBOX, vp));
-    TRY(launch_gather(c, vp, 1, dw, state, n_blocks, t_inv));
+    const uint64_t ggsw_words = (uint64_t)c->k1 * c->k1 * FHE_N, total = steps * n_blocks;     // cbs_level == 1
+    TRY(ensure_wopbs_ws(c, w * AES_BLOCK_BITS));
+    uint64_t *small = (uint64_t *)c->ws_small.p, *pbs = (uint64_t *)c->ws_pbs.p, *ggsw = (uint64_t *)c->ws_ggsw.p;
+    const double2 *ggswf = (const double2 *)c->ws_ggswf.p;
+    struct Segment { const AesStep *st; uint64_t first, blocks, row; uint64_t *vp; };            // row: its first block's place in the window
+    for (uint64_t i0 = 0; i0 < total; i0 += w) {
+        const uint64_t len = std::min<uint64_t>(w, total - i0), s = i0 / n_blocks, b0 = i0 % n_blocks, m = len * AES_BLOCK_BITS;
+        Segment seg[2] = {{&sch.steps[s], b0, std::min<uint64_t>(len, n_blocks - b0), 0, vp}, {}};
+        int n_seg = 1;
+        if (seg[0].blocks < len) {
+            seg[1] = {&sch.steps[s + 1], 0, len - seg[0].blocks, seg[0].blocks, vp + seg[0].blocks * 16 * seg[0].st->n_luts * bw};
+            n_seg = 2;
+        }
+        for (int g = 0; g < n_seg; ++g)
+            TRY(launch_keyswitch(c, state + seg[g].first * sw, seg[g].blocks * AES_BLOCK_BITS, small + seg[g].row * AES_BLOCK_BITS * (c->n + 1)));
+        TRY(launch_cbs_pbs(c, small, m, 1, pbs));
+        TRY(launch_pfpks(c, pbs, m, ggsw, ggsw_words));
+        TRY(launch_forward_fourier(c, ggsw, m * c->k1 * c->k1, (double2 *)c->ws_ggswf.p, FHEAES_STAGE_GGSW_FFT));
+        if (n_seg == 1 || seg[0].st->set == seg[1].st->set) {
+            const int set = seg[0].st->set;
+            TRY(launch_vertical_packing(c, ggswf, 16 * len, 8, c->lutset_d[set], (uint32_t)c->lutset_n[set], 0, vp));
+        } else {
+            for (int g = 0; g < n_seg; ++g) {
+                const int set = seg[g].st->set;
+                TRY(launch_vertical_packing(c, ggswf + seg[g].row * AES_BLOCK_BITS * (ggsw_words / 2), 16 * seg[g].blocks, 8, c->lutset_d[set],
+                                            (uint32_t)c->lutset_n[set], 0, seg[g].vp));
+            }
+        }
+        for (int g = 0; g < n_seg; ++g)
+            TRY(launch_gather(c, seg[g].vp, seg[g].st->n_luts, key_of(*seg[g].st, seg[g].first), state + seg[g].first * sw, seg[g].blocks, seg[g].st->table));
+    }
     return FHEAES_OK;
 }
+
+static int aes_encrypt_dev(fheaes_ctx *c, const KeySets &rk, uint64_t *state, uint64_t n_blocks, int nr) { return aes_run_dev(c, rk, state, n_blocks, aes_encrypt_schedule(nr)); }
+static int aes_decrypt_dev(fheaes_ctx *c, const KeySets &rk, uint64_t *state, uint64_t n_blocks, int nr) { return aes_run_dev(c, rk, state, n_blocks, aes_decrypt_schedule(nr)); }
+static int aes_decrypt_eq_dev(fheaes_ctx *c, const KeySets &dw, uint64_t *state, uint64_t n_blocks, int nr) { return aes_run_dev(c, dw, state, n_blocks, aes_decrypt_eq_schedule(nr)); }
 
 typedef int (*AesDevFn)(fheaes_ctx *, const KeySets &, uint64_t *, uint64_t, int);
 

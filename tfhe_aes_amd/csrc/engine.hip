@@ -107,6 +107,30 @@ int fheaes_k2_set_forms(fheaes_ctx *ctx, int allow_pair, int allow_home)
     ctx->k2_deny_home = allow_home == 0;
     return FHEAES_OK;
 }
+int fheaes_aes_window_plan(uint64_t n_blocks, uint32_t steps, uint32_t cu_count, uint32_t k, uint64_t *window_blocks, uint64_t *launches,
+                           uint64_t *generations, uint64_t *generations_by_round)
+{
+    if (!window_blocks || !launches || !generations || !generations_by_round || n_blocks == 0 || steps == 0 || cu_count == 0) return FHEAES_ERR_INVALID;
+    const AesWindowPlan pl = aes_window_plan(n_blocks, steps, cu_count, k + 1);
+    *window_blocks = pl.window; *launches = pl.launches; *generations = pl.generations; *generations_by_round = pl.generations_by_round;
+    return FHEAES_OK;
+}
+int fheaes_aes_context_window(fheaes_ctx *ctx, uint64_t n_blocks, uint32_t steps, uint64_t *window_blocks)
+{
+    if (!ctx) return FHEAES_ERR_INVALID;
+    CtxLock lock__(ctx);
+    if (!window_blocks) return ctx->fail(FHEAES_ERR_INVALID, "aes_context_window: null output");
+    *window_blocks = aes_context_window(ctx, n_blocks, steps);
+    return FHEAES_OK;
+}
+int fheaes_aes_set_window(fheaes_ctx *ctx, uint32_t window_blocks)
+{
+    if (!ctx) return FHEAES_ERR_INVALID;
+    CtxLock lock__(ctx);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->aes_window = window_blocks;
+    return FHEAES_OK;
+}
 int fheaes_k2_park_debug(fheaes_ctx *ctx, const uint32_t *initial_owner, int record)
 {
     if (!ctx) return FHEAES_ERR_INVALID;

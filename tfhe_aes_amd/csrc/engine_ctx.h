@@ -56,6 +56,7 @@ struct fheaes_ctx {
     // record {slot, XCC} per workgroup into ws_park_record; k2_park_record_n = grid of the last recorded launch since the hook was set
     bool k2_park_pattern = false, k2_park_record = false;
     uint64_t k2_park_record_n = 0;
+    uint32_t aes_window = 0;             // fheaes_aes_set_window: 0 = automatic (aes_window_plan), FHEAES_AES_WINDOW_OFF = one WoPBS per step, else forced
     // keys
     int8_t *ksk_frag = nullptr, *pfpksk_frag = nullptr;      // balanced key bytes in MFMA B-fragment order
     uint32_t ks_ksteps = 0, ks_coltiles = 0, pf_ksteps = 0, pf_coltiles = 0;

@@ -52,6 +52,58 @@ K2Plan k2_plan(uint64_t m, uint32_t cu_count, uint32_t k1, bool allow_pair = tru
     return pl;
 }
 
+// ---- how the block-rounds of an AES call are cut into blind-rotation launches (fheaes_aes_window_plan) ----------------------------
+// A block cipher call is `steps` WoPBS over each of n blocks of 128 bits, and a step of block b needs only the step before it of the same
+// block: the steps x n block-rounds are one stream in (step, block) order that may be cut anywhere.  Round by round, every step pays the
+// launch's last, partly filled generation; cut into windows that are a whole number of six-ciphertext generations, only the call's last
+// launch does.
+#define AES_BLOCK_BITS 128ull
+#define AES_WINDOW_MAX_BLOCKS (MAX_CHUNK_BITS / AES_BLOCK_BITS)
+struct AesWindowPlan { uint64_t window, launches, generations, generations_by_round; };      // window 0: not rolled, one WoPBS per step
+
+// generations of one workgroup per CU that a paired launch of m bits runs; a launch at or below the paired threshold counts as one
+uint64_t k2_generations(uint64_t m, uint32_t cu_count, uint32_t k1)
+{
+    if (m == 0) return 0;
+    if (m <= K2_PAIR_MIN_BITS) return 1;
+    const K2Plan pl = k2_plan(m, cu_count, k1);
+    return (pl.units_main + pl.units_tail + cu_count - 1) / cu_count;
+}
+
+// launches and generations of the stream cut into windows of w blocks (w <= n, w <= AES_WINDOW_MAX_BLOCKS)
+void aes_window_count(uint64_t n, uint64_t steps, uint64_t w, uint32_t cu_count, uint32_t k1, uint64_t *launches, uint64_t *generations)
+{
+    const uint64_t total = steps * n, full = total / w, rest = total % w;
+    *launches = full + (rest ? 1 : 0);
+    *generations = full * k2_generations(w * AES_BLOCK_BITS, cu_count, k1) + k2_generations(rest * AES_BLOCK_BITS, cu_count, k1);
+}
+
+// pair: the full batch's launch takes the paired form on the device in question (k2_launch: after the occupancy fallbacks and the hook)
+AesWindowPlan aes_window_plan(uint64_t n, uint64_t steps, uint32_t cu_count, uint32_t k1, bool allow_pair = true)
+{
+    AesWindowPlan pl{};
+    // round by round: every step is cut into chunks of MAX_CHUNK_BITS (wopbs_dev)
+    const uint64_t chunks = n / AES_WINDOW_MAX_BLOCKS, last = n % AES_WINDOW_MAX_BLOCKS;
+    pl.launches = steps * (chunks + (last ? 1 : 0));
+    pl.generations_by_round = steps * (chunks * k2_generations(MAX_CHUNK_BITS, cu_count, k1) + k2_generations(last * AES_BLOCK_BITS, cu_count, k1));
+    pl.generations = pl.generations_by_round;
+    if (n == 0 || steps == 0) return pl;
+    const uint64_t gen_bits = 6ull * cu_count;
+    if (k2_plan(std::min<uint64_t>(n * AES_BLOCK_BITS, MAX_CHUNK_BITS), cu_count, k1, allow_pair).form != 2) return pl;
+    if (n * AES_BLOCK_BITS % gen_bits == 0) return pl;
+    // the smallest block count whose bits are whole generations: lcm(128, 6 CUs) / 128 = 6 CUs / gcd(128, 6 CUs)
+    uint64_t g = AES_BLOCK_BITS, r = gen_bits;
+    while (r) { const uint64_t t = g % r; g = r; r = t; }
+    const uint64_t base = gen_bits / g;
+    const uint64_t w = std::min<uint64_t>(n, AES_WINDOW_MAX_BLOCKS) / base * base;
+    if (w == 0) return pl;
+    uint64_t launches, generations;
+    aes_window_count(n, steps, w, cu_count, k1, &launches, &generations);
+    if (generations >= pl.generations_by_round) return pl;
+    pl.window = w; pl.launches = launches; pl.generations = generations;
+    return pl;
+}
+
 // ---- kernel launchers ------------------------------------------------------------------------
 int launch_keyswitch(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out)
 {
@@ -195,6 +247,16 @@ K2Launch k2_launch(fheaes_ctx *c, uint64_t m)
         L.park_bytes = (size_t)L.grid * BR16_PARK_WORDS_PER_WG * 8;
     }
     return L;
+}
+
+// The window of this context for `steps` WoPBS over n blocks (fheaes_aes_context_window): what fheaes_aes_set_window forced, else
+// aes_window_plan for the form the full batch's launch really takes here.  0: one WoPBS per step.
+uint64_t aes_context_window(fheaes_ctx *c, uint64_t n, uint64_t steps)
+{
+    if (n == 0 || steps == 0 || c->aes_window == FHEAES_AES_WINDOW_OFF) return 0;
+    if (c->aes_window) return std::min<uint64_t>(c->aes_window, std::min<uint64_t>(n, AES_WINDOW_MAX_BLOCKS));
+    const bool pair = k2_launch(c, std::min<uint64_t>(n * AES_BLOCK_BITS, MAX_CHUNK_BITS)).pl.form == 2;
+    return aes_window_plan(n, steps, c->cu_count, c->k1, pair).window;
 }
 
 int launch_cbs_pbs(fheaes_ctx *c, const uint64_t *lwe_small, uint64_t m, uint32_t level, uint64_t *out)
