@@ -20,21 +20,14 @@ line (--out: also written there).
 """
 from __future__ import annotations
 
-import argparse
-import json
-import statistics
 import sys
-import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from tfhe_aes_amd import PARAM_OPT, _build, _native, aes_clear  # noqa: E402
-from tfhe_aes_amd.client import Client  # noqa: E402
+import measure
+from measure import block_bytes, host, to_dev
+from tfhe_aes_amd import PARAM_OPT, aes_clear
 
 # FIPS-197 appendix A.1 / A.2 / A.3
 KEYS = {128: bytes.fromhex("2b7e151628aed2a6abf7158809cf4f3c"),
@@ -44,50 +37,6 @@ NR = {128: 10, 192: 12, 256: 14}
 SIZES = (128, 192, 256)
 IV = 0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF
 MASK128 = (1 << 128) - 1
-
-
-def progress(msg: str) -> None:
-    """to stderr: the JSON line on stdout stays alone, and a long run shows that it is alive"""
-    print("[aes_key_sizes] " + msg, file=sys.stderr, flush=True)
-
-
-def to_dev(a: np.ndarray) -> torch.Tensor:
-    d = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-    torch.cuda.synchronize()
-    return d
-
-
-def host(d: torch.Tensor) -> np.ndarray:
-    return d.cpu().numpy().view(np.uint64)
-
-
-def block_bytes(values) -> np.ndarray:
-    return np.array([[(v >> (8 * (15 - b))) & 0xFF for b in range(16)] for v in values], dtype=np.uint8)
-
-
-def stage_ms(eng: _native.Engine, run) -> dict:
-    """one call of `run` with the per-stage profile on: {stage: ms}"""
-    eng.profile_enable(True)
-    eng.profile_reset()
-    run()
-    prof = eng.profile_read()
-    eng.profile_enable(False)
-    return {k: round(v["ms"], 3) for k, v in prof.items()}
-
-
-def timed_alternating(eng: _native.Engine, runs: dict, resets: dict, warmup: int, steps: int) -> dict:
-    """{key size: [seconds per timed call]}; every step runs the key sizes one after the other"""
-    out = {bits: [] for bits in runs}
-    for i in range(warmup + steps):
-        for bits, run in runs.items():
-            resets[bits]()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            run()
-            eng.synchronize()
-            if i >= warmup:
-                out[bits].append(time.perf_counter() - t0)
-    return out
 
 
 def ratios(rows: dict, expected: dict) -> None:
@@ -101,20 +50,11 @@ def ratios(rows: dict, expected: dict) -> None:
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--blocks", default="32,128")
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = measure.arg_parser(blocks="32,128").parse_args()
     batch_sizes = [int(x) for x in args.blocks.split(",")]
     p = PARAM_OPT
 
-    client = Client(1, IV, int.from_bytes(KEYS[128], "big"), params=p, seed=0xAE50001)
-    keys = client.server_keys()
-    eng = _native.Engine(p, device=0)
-    eng.upload_keys(keys.ksk, keys.bsk, keys.pfpksk)
-    del keys
+    client, eng = measure.session(0xAE50001, IV, int.from_bytes(KEYS[128], "big"))
 
     # the entry points: AES-128 through the ones without a key-size argument (the yardstick), the others through *_bits
     def entry(name, bits):
@@ -130,18 +70,18 @@ def main() -> int:
     clear_rk = {bits: aes_clear.expand_key(KEYS[bits]) for bits in SIZES}
 
     # ---- once per AES key: the expansion and the conversion to the equivalent inverse cipher's round keys ----
+    # every step of a loop runs the three key sizes one after the other
     per_key = {}
     for name, src, dst, want in (
             ("key_expansion", d_ek, d_rk, clear_rk),
             ("decryption_round_keys", d_rk, d_dw, {b: aes_clear.inv_mix_columns_round_keys(clear_rk[b]) for b in SIZES})):
-        runs = {b: (lambda b=b: entry("aes_" + name, b)(src[b], dst[b])) for b in SIZES}
-        ts = timed_alternating(eng, runs, {b: (lambda: None) for b in SIZES}, args.warmup, args.steps)
+        jobs = {b: ((lambda b=b: entry("aes_" + name, b)(src[b], dst[b])), lambda: None) for b in SIZES}
+        ts = measure.wall(eng, jobs, args.warmup, args.steps)
         rows = {}
         for b in SIZES:
             ok = bool(np.array_equal(client.decrypt_bytes(host(dst[b])), np.array(want[b], dtype=np.uint8)))
             all_ok = all_ok and ok
-            rows[b] = {"ms_median": round(1000 * statistics.median(ts[b]), 3), "ms_all": [round(1000 * t, 3) for t in ts[b]],
-                       "verified_vs_fips197": ok, "stages_ms": stage_ms(eng, runs[b])}
+            rows[b] = {**measure.row(ts[b]), "verified_vs_fips197": ok, "stages_ms": measure.stage_ms(measure.profiled(eng, jobs[b][0]))}
             if name == "key_expansion":
                 nk = NR[b] - 6
                 rows[b]["new_words"] = 4 * (NR[b] + 1) - nk
@@ -152,7 +92,7 @@ def main() -> int:
                 rows[b]["bit_cbs"] = 2 * (NR[b] - 1) * 128
         ratios(rows, None)                  # recorded without a target: neither is a multiple of one round
         per_key[name] = {str(b): rows[b] for b in SIZES}
-        progress("%s: %s ms" % (name, " / ".join("%.1f" % rows[b]["ms_median"] for b in SIZES)))
+        measure.progress("aes_key_sizes", "%s: %s ms" % (name, " / ".join("%.1f" % rows[b]["ms_median"] for b in SIZES)))
 
     # ---- per batch size: the three block operations ----
     results = {}
@@ -169,42 +109,31 @@ def main() -> int:
                 ("aes_encrypt", d_rk, {b: d_pt for b in SIZES}, want_ct, lambda nr: nr * 128),
                 ("aes_decrypt_equivalent", d_dw, d_ct, {b: want_pt for b in SIZES}, lambda nr: nr * 128),
                 ("aes_decrypt", d_rk, d_ct, {b: want_pt for b in SIZES}, lambda nr: (2 * nr - 1) * 128)):
-            runs = {b: (lambda b=b: entry(name, b)(keys_d[b], st[b], n)) for b in SIZES}
-            resets = {b: (lambda b=b: st[b].copy_(inputs[b])) for b in SIZES}
-            ts = timed_alternating(eng, runs, resets, args.warmup, args.steps)
+            jobs = {b: ((lambda b=b: entry(name, b)(keys_d[b], st[b], n)), (lambda b=b: st[b].copy_(inputs[b]))) for b in SIZES}
+            ts = measure.wall(eng, jobs, args.warmup, args.steps)
             rows = {}
             for b in SIZES:
                 got = client.decrypt_bytes(host(st[b]))
                 wrong = [i for i in range(n) if not np.array_equal(got[i], want[b][i])]
                 all_ok = all_ok and not wrong
-                med = statistics.median(ts[b])
-                rows[b] = {"blocks_per_s": round(n / med, 2), "ms_median": round(1000 * med, 3), "ms_all": [round(1000 * t, 3) for t in ts[b]],
-                           "bit_cbs_per_block": per_block(NR[b]), "blocks_verified": n - len(wrong), "wrong_blocks": wrong}
-                resets[b]()
-                torch.cuda.synchronize()
-                rows[b]["stages_ms"] = stage_ms(eng, runs[b])
+                rows[b] = {**measure.row(ts[b], n), "bit_cbs_per_block": per_block(NR[b]), "blocks_verified": n - len(wrong), "wrong_blocks": wrong,
+                           "stages_ms": measure.stage_ms(measure.profiled(eng, *jobs[b]))}
             ratios(rows, {b: per_block(NR[b]) / per_block(10) for b in SIZES})
             row_n[name] = {str(b): rows[b] for b in SIZES}
-            progress("%d blocks, %s: %s blocks/s, ratios %s" % (n, name, " / ".join("%.2f" % rows[b]["blocks_per_s"] for b in SIZES),
-                                                               " / ".join("%.3f" % rows[b]["ratio_to_128"] for b in SIZES)))
+            measure.progress("aes_key_sizes", "%d blocks, %s: %s blocks/s, ratios %s" % (
+                n, name, " / ".join("%.2f" % rows[b]["blocks_per_s"] for b in SIZES), " / ".join("%.3f" % rows[b]["ratio_to_128"] for b in SIZES)))
         results[str(n)] = row_n
         del d_pt, d_ct, st
 
-    line = {"tool": "aes_key_sizes", "params": p.name, "version": _native.load_library().fheaes_version().decode(),
-            "engine_src_sha256": _build.engine_source_hash(), "device": torch.cuda.get_device_name(0),
-            "steps": args.steps, "warmup": args.warmup, "all_verified": all_ok,
+    line = {**measure.header("aes_key_sizes", args), "all_verified": all_ok,
             "key_expansion": per_key["key_expansion"], "decryption_round_keys": per_key["decryption_round_keys"], "blocks": results,
             "note": "wall clock per call on resident tensors (call + synchronize), median of the timed steps, the key sizes alternating "
                     "inside every step; AES-128 runs through the entry points without a key-size argument; ratio_to_128 = ms_median / "
                     "ms_median of AES-128 in this run, expected = Nr / 10 (aes_decrypt: (2 Nr - 1) / 19), none for the two once-per-key operations; "
                     "stages_ms from one further profiled call (HIP events around every launch)"}
-    text = json.dumps(line)
-    print(text)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(text + "\n")
+    measure.emit(line, args.out)
     eng.close()
-    return 0 if all_ok else 1
+    return measure.exit_code(all_ok)
 
 
 if __name__ == "__main__":

@@ -19,37 +19,21 @@ other stages grew by no more than the spread of the `off` runs.  Prints one JSON
 """
 from __future__ import annotations
 
-import argparse
-import json
 import statistics
 import sys
-import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from tfhe_aes_amd import PARAM_OPT, _build, _native, aes_clear  # noqa: E402
-from tfhe_aes_amd.client import Client  # noqa: E402
+import measure
+from measure import block_bytes, host, to_dev
+from tfhe_aes_amd import PARAM_OPT, _native, aes_clear
 
 KEY = 0x2B7E151628AED2A6ABF7158809CF4F3C
 IV = 0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF
 MASK128 = (1 << 128) - 1
 SETTINGS = (("off", _native.AES_WINDOW_OFF), ("auto", 0))
 SHAPES = (("aes_encrypt", 128, 10), ("aes_encrypt", 32, 10), ("aes_decrypt", 32, 19))
-
-
-def to_dev(a: np.ndarray) -> torch.Tensor:
-    d = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-    torch.cuda.synchronize()
-    return d
-
-
-def host(d: torch.Tensor) -> np.ndarray:
-    return d.cpu().numpy().view(np.uint64)
 
 
 def k2_generation_costs(eng: _native.Engine, p, launches: int) -> dict:
@@ -59,15 +43,8 @@ def k2_generation_costs(eng: _native.Engine, p, launches: int) -> dict:
     for m in (1024, 4096, 16384):
         small = to_dev(rng.integers(0, 1 << 64, (m, p.n + 1), dtype=np.uint64))
         out = torch.empty((m, p.big1), dtype=torch.int64, device="cuda")
-        torch.cuda.synchronize()
-        ts = []
-        for i in range(launches + 1):
-            t0 = time.perf_counter()
-            eng.cbs_pbs_batch(small, out, m)
-            eng.synchronize()
-            if i:
-                ts.append(1000 * (time.perf_counter() - t0))
-        ms[m] = statistics.median(ts)
+        ts = measure.wall(eng, {m: (lambda: eng.cbs_pbs_batch(small, out, m), lambda: None)}, 1, launches)[m]      # a loop per size
+        ms[m] = 1000 * statistics.median(ts)
     g6 = (ms[16384] - ms[4096]) / 8
     g4 = ms[4096] - 2 * g6
     return {"ms_per_launch": {str(m): round(v, 3) for m, v in ms.items()}, "g6_ms": round(g6, 3), "g4_ms": round(g4, 3),
@@ -75,18 +52,10 @@ def k2_generation_costs(eng: _native.Engine, p, launches: int) -> dict:
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = measure.arg_parser().parse_args()
     p = PARAM_OPT
 
-    client = Client(1, IV, KEY, params=p, seed=0xAE50001)
-    keys = client.server_keys()
-    eng = _native.Engine(p, device=0)
-    eng.upload_keys(keys.ksk, keys.bsk, keys.pfpksk)
-    del keys
+    client, eng = measure.session(0xAE50001, IV, KEY)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     d_rk = torch.empty((11, 16, 8, p.big1), dtype=torch.int64, device="cuda")
     d_ek = to_dev(client.encrypt_u128(KEY))
@@ -104,42 +73,34 @@ def main() -> int:
         pts = [(IV + 0x9E3779B97F4A7C15 * i) & MASK128 for i in range(n)]
         cts = [aes_clear.aes128_encrypt_block(KEY, v) for v in pts]
         clear_in, clear_out = (pts, cts) if cipher == "aes_encrypt" else (cts, pts)
-        want = np.array([[(v >> (8 * (15 - b))) & 0xFF for b in range(16)] for v in clear_out], dtype=np.uint8)
+        want = block_bytes(clear_out)
         d_in = to_dev(np.stack([client.encrypt_u128(v) for v in clear_in]))
-        st = torch.empty_like(d_in)
         fn = getattr(eng, cipher)
         plan = _native.aes_window_plan(n, steps, cus, p.k)
         row = {"plan_at_%d_cus" % cus: plan}
-        times = {name: [] for name, _ in SETTINGS}
-        words = {}
-        for i in range(args.warmup + args.steps):
-            for name, setting in SETTINGS:                         # alternating inside one loop: both settings see the same clock drift
-                eng.aes_set_window(setting)
-                st.copy_(d_in)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                fn(d_rk, st, n)
-                eng.synchronize()
-                if i >= args.warmup:
-                    times[name].append(1000 * (time.perf_counter() - t0))
-                words[name] = host(st)
+        # a state per setting, so that each one's words outlast the other's calls; the reset of a job also makes its setting the engine's.
+        # off / auto alternate inside one loop: both settings see the same clock drift
+        st = {name: torch.empty_like(d_in) for name, _ in SETTINGS}
+        jobs = {}
         for name, setting in SETTINGS:
-            eng.aes_set_window(setting)
+            def run(name=name):
+                fn(d_rk, st[name], n)
+
+            def reset(name=name, setting=setting):
+                eng.aes_set_window(setting)
+                st[name].copy_(d_in)
+
+            jobs[name] = (run, reset)
+        times = measure.wall(eng, jobs, args.warmup, args.steps)
+        words = {name: host(st[name]) for name in jobs}                # read before the profiled calls overwrite them
+        for name in jobs:
+            prof = measure.profiled(eng, *jobs[name])
             window = eng.aes_window(n, steps)
-            st.copy_(d_in)
-            torch.cuda.synchronize()
-            eng.profile_enable(True)
-            eng.profile_reset()
-            fn(d_rk, st, n)
-            prof = eng.profile_read()
-            eng.profile_enable(False)
             got = client.decrypt_bytes(words[name])
             wrong = [b for b in range(n) if not np.array_equal(got[b], want[b])]
-            ts = times[name]
-            med = statistics.median(ts)
-            row[name] = {"window_blocks": window, "ms_median": round(med, 3), "ms_all": [round(t, 3) for t in ts], "blocks_per_s": round(1000 * n / med, 2),
+            row[name] = {"window_blocks": window, **measure.row(times[name], n),
                          "blocks_verified": n - len(wrong), "wrong_blocks": wrong, "k2_launches": prof["blind_rotate"]["launches"],
-                         "stages_ms": {k: round(v["ms"], 3) for k, v in prof.items()},
+                         "stages_ms": measure.stage_ms(prof),
                          "other_stages_ms": round(sum(v["ms"] for k, v in prof.items() if k != "blind_rotate"), 3)}
             all_ok = all_ok and not wrong
         eng.aes_set_window(0)
@@ -147,7 +108,7 @@ def main() -> int:
         row["gain"] = round(1 - row["auto"]["ms_median"] / row["off"]["ms_median"], 5)
         row["k2_stage_reduction_ms"] = round(row["off"]["stages_ms"]["blind_rotate"] - row["auto"]["stages_ms"]["blind_rotate"], 3)
         row["other_stages_growth_ms"] = round(row["auto"]["other_stages_ms"] - row["off"]["other_stages_ms"], 3)
-        row["off_spread_ms"] = round(max(times["off"]) - min(times["off"]), 3)
+        row["off_spread_ms"] = round(1000 * max(times["off"]) - 1000 * min(times["off"]), 3)
         all_ok = all_ok and row["same_words"]
         results["%s_%d" % (cipher, n)] = row
         del d_in, st
@@ -158,20 +119,14 @@ def main() -> int:
               "measured_k2_reduction_ms": head["k2_stage_reduction_ms"],
               "k2_reduction_ok": head["k2_stage_reduction_ms"] >= 0.8 * predicted,
               "other_stages_ok": head["other_stages_growth_ms"] <= head["off_spread_ms"]}
-    line = {"tool": "aes_windows", "params": p.name, "version": _native.load_library().fheaes_version().decode(),
-            "engine_src_sha256": _build.engine_source_hash(), "device": torch.cuda.get_device_name(0), "cu_count": cus,
-            "steps": args.steps, "warmup": args.warmup, "all_verified": all_ok, "k2_generations": gen, "shapes": results, "checks": checks,
+    line = {**measure.header("aes_windows", args), "cu_count": cus, "all_verified": all_ok, "k2_generations": gen, "shapes": results, "checks": checks,
             "note": "off / auto alternate inside one timed loop on resident tensors (call + synchronize), median of the timed steps; stages_ms "
                     "from one further profiled call each (HIP events around every launch); g6 = (t16384 - t4096) / 8, g4 = t4096 - 2 g6 from "
                     "blind-rotation launches in the same process; checks are for aes_encrypt at 128 blocks: the blind-rotation stage must shrink "
                     "by at least 0.8 x (9 g4 - 6 g6), the other stages together may grow by no more than the spread of the off runs"}
-    text = json.dumps(line)
-    print(text)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(text + "\n")
+    measure.emit(line, args.out)
     eng.close()
-    return 0 if all_ok else 1
+    return measure.exit_code(all_ok)
 
 
 if __name__ == "__main__":

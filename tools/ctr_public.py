@@ -25,21 +25,14 @@ points that existed before, measured here in the same loop:
 """
 from __future__ import annotations
 
-import argparse
-import json
-import statistics
 import sys
-import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from tfhe_aes_amd import PARAM_OPT, _build, _native, aes_clear  # noqa: E402
-from tfhe_aes_amd.client import Client  # noqa: E402
+import measure
+from measure import block_bytes, host, progress, to_dev
+from tfhe_aes_amd import PARAM_OPT, _native, aes_clear
 
 # SP 800-38A F.1.1 / F.1.3 / F.1.5
 KEYS = {128: bytes.fromhex("2b7e151628aed2a6abf7158809cf4f3c"),
@@ -50,41 +43,15 @@ SIZES = (128, 192, 256)
 IV = 0x00112233445566778899AABBCCDDEE00
 MASK128 = (1 << 128) - 1
 VARIANTS = ("ctr_aligned", "ctr_fa", "public_no_sharing", "aes_encrypt", "reference_iteration")
-
-
-def progress(msg: str) -> None:
-    print("[ctr_public] " + msg, file=sys.stderr, flush=True)
-
-
-def to_dev(a: np.ndarray) -> torch.Tensor:
-    d = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-    torch.cuda.synchronize()
-    return d
-
-
-def host(d: torch.Tensor) -> np.ndarray:
-    return d.cpu().numpy().view(np.uint64)
-
-
-def block_bytes(values) -> np.ndarray:
-    return np.array([[(v >> (8 * (15 - b))) & 0xFF for b in range(16)] for v in values], dtype=np.uint8)
+TOOL = "ctr_public"
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--blocks", default="128,32")
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = measure.arg_parser(blocks="128,32").parse_args()
     batch_sizes = [int(x) for x in args.blocks.split(",")]
     p = PARAM_OPT
 
-    client = Client(1, IV, int.from_bytes(KEYS[128], "big"), params=p, seed=0xAE50001)
-    keys = client.server_keys()
-    eng = _native.Engine(p, device=0)
-    eng.upload_keys(keys.ksk, keys.bsk, keys.pfpksk)
-    del keys
+    client, eng = measure.session(0xAE50001, IV, int.from_bytes(KEYS[128], "big"))
 
     d_rk, d_dw = {}, None
     for bits in SIZES:
@@ -132,50 +99,34 @@ def main() -> int:
     jobs[("aes_decryption_round_keys", 0, 128)] = (lambda: eng.aes_decryption_round_keys(d_rk[128], d_dw), lambda: None, d_dw, None, None)
 
     # ---- one timed loop, every job once per step ----
-    times = {k: [] for k in jobs}
-    for i in range(args.warmup + args.steps):
-        t_step = time.perf_counter()
-        for k, (run, reset, _, _, _) in jobs.items():
-            reset()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            run()
-            eng.synchronize()
-            if i >= args.warmup:
-                times[k].append(time.perf_counter() - t0)
-        progress("step %d of %d: %.1f s" % (i + 1, args.warmup + args.steps, time.perf_counter() - t_step))
+    times = measure.wall(eng, {k: j[:2] for k, j in jobs.items()}, args.warmup, args.steps,
+                         on_step=lambda i, of, s: progress(TOOL, "step %d of %d: %.1f s" % (i, of, s)))
 
     # ---- verify every block of every output, then one profiled call each ----
     all_ok = True
     rows = {}
     for k, (run, reset, out, want, public_blocks) in jobs.items():
         name, n, bits = k
-        med = statistics.median(times[k])
-        row = {"ms_median": round(1000 * med, 3), "ms_all": [round(1000 * t, 3) for t in times[k]]}
         if want is None:                                             # the round-key conversion
+            row = measure.row(times[k])
             ok = bool(np.array_equal(client.decrypt_bytes(host(out)),
                                      np.array(aes_clear.inv_mix_columns_round_keys(aes_clear.expand_key(KEYS[128])), dtype=np.uint8)))
             row["verified"] = ok
             all_ok = all_ok and ok
         else:
+            row = measure.row(times[k], n)
             got = client.decrypt_bytes(host(out))
             wrong = [i for i in range(n) if not np.array_equal(got[i], want[i])]
             all_ok = all_ok and not wrong
-            row.update({"blocks_per_s": round(n / med, 2), "blocks_verified": n - len(wrong), "wrong_blocks": wrong})
+            row.update({"blocks_verified": n - len(wrong), "wrong_blocks": wrong})
             plan = _native.aes_public_plan(public_blocks, bits) if public_blocks is not None else [16 * n] * NR[bits]
             row["bit_cbs"] = 8 * sum(plan) + (143 * n if name == "reference_iteration" else 0)     # add_scalar: 143 bit-CBS per block
             row["byte_wopbs_rounds_1_2"] = plan[:2]
-        reset()
-        torch.cuda.synchronize()
-        eng.profile_enable(True)
-        eng.profile_reset()
-        run()
-        prof = eng.profile_read()
-        eng.profile_enable(False)
-        row["stages_ms"] = {s: round(v["ms"], 3) for s, v in prof.items()}
+        prof = measure.profiled(eng, run, reset)
+        row["stages_ms"] = measure.stage_ms(prof)
         row["stages_units"] = {s: v["units"] for s, v in prof.items()}
         rows.setdefault(name, {}).setdefault(str(n), {})[str(bits)] = row
-        progress("%s, %d blocks, AES-%d: %.1f ms" % (name, n, bits, row["ms_median"]))
+        progress(TOOL, "%s, %d blocks, AES-%d: %.1f ms" % (name, n, bits, row["ms_median"]))
 
     check = None
     if 128 in batch_sizes and 32 in batch_sizes:
@@ -183,31 +134,22 @@ def main() -> int:
         proxy = {"aes_encrypt_128_blocks_ms": T("aes_encrypt", 128), "aes_encrypt_32_blocks_ms": T("aes_encrypt", 32),
                  "aes_decryption_round_keys_ms": T("aes_decryption_round_keys", 0)}
         pred = 0.8 * T("aes_encrypt", 128) + 0.1 * T("aes_encrypt", 32) + 0.5 * T("aes_decryption_round_keys", 0)
-        check = {"proxies": proxy, "predicted_ms": round(pred, 3), "measured_ms": T("ctr_aligned", 128),
-                 "ratio": round(T("ctr_aligned", 128) / pred, 4), "bound": 1.03, "within_bound": bool(T("ctr_aligned", 128) <= 1.03 * pred),
+        check = {"proxies": proxy, **measure.check(T("ctr_aligned", 128), pred, 1.03),
                  "no_sharing_ms": T("public_no_sharing", 128), "no_sharing_ratio_to_aes_encrypt": round(T("public_no_sharing", 128) / T("aes_encrypt", 128), 4),
                  "no_sharing_within_bound": bool(T("public_no_sharing", 128) <= 1.03 * T("aes_encrypt", 128)),
                  "share_of_aes_encrypt": round(T("ctr_aligned", 128) / T("aes_encrypt", 128), 4),
                  "share_of_reference_iteration": round(T("ctr_aligned", 128) / T("reference_iteration", 128), 4)}
-        progress("aes_ctr 128 aligned: %.1f ms, predicted %.1f ms, ratio %.4f; no sharing / aes_encrypt %.4f" % (
+        progress(TOOL, "aes_ctr 128 aligned: %.1f ms, predicted %.1f ms, ratio %.4f; no sharing / aes_encrypt %.4f" % (
             check["measured_ms"], pred, check["ratio"], check["no_sharing_ratio_to_aes_encrypt"]))
 
-    line = {"tool": "ctr_public", "params": p.name, "version": _native.load_library().fheaes_version().decode(),
-            "engine_src_sha256": _build.engine_source_hash(), "device": torch.cuda.get_device_name(0),
-            "steps": args.steps, "warmup": args.warmup, "all_verified": all_ok, "check": check, "variants": rows,
+    line = {**measure.header(TOOL, args), "all_verified": all_ok, "check": check, "variants": rows,
             "note": "wall clock per call on resident tensors (call + synchronize), median of the timed steps; every variant of every size "
                     "runs once in every step of one loop; rows are variants[name][blocks][key bits]; stages_ms / stages_units "
                     "(fheaes_profile_read: bits for the five WoPBS stages, blocks for the linear layers) from one further profiled call; "
                     "bit_cbs = bit circuit bootstraps of the call (8 x fheaes_aes_public_plan; 128 n per round for aes_encrypt; add_scalar 143 n)"}
-    text = json.dumps(line)
-    print(text)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(text + "\n")
+    measure.emit(line, args.out)
     eng.close()
-    if not all_ok:
-        return 1
-    return 0 if check is None or (check["within_bound"] and check["no_sharing_within_bound"]) else 2
+    return measure.exit_code(all_ok, check is None or (check["within_bound"] and check["no_sharing_within_bound"]))
 
 
 if __name__ == "__main__":

@@ -21,71 +21,35 @@ recorded from fheaes_k2_context_plan.
 """
 from __future__ import annotations
 
-import argparse
-import json
-import statistics
-import subprocess
 import sys
-import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from tfhe_aes_amd import PARAM_OPT, _build, _native, aes_clear  # noqa: E402
-from tfhe_aes_amd.client import Client  # noqa: E402
-from tfhe_aes_amd.server import Server, ctr_stream_blocks  # noqa: E402
+import measure
+from measure import block_bytes, check, host, progress, to_dev
+from tfhe_aes_amd import PARAM_OPT, _native, aes_clear
+from tfhe_aes_amd.client import Client
+from tfhe_aes_amd.server import Server, ctr_stream_blocks
 
 BASE = 0x00112233445566778899AABBCCDDEE00
 KX_N = (1, 8, 32)               # keys per batched expansion
 CONV_N = 14                     # 14 x 1,152 = 16,128 bits
 BOUND = 1.03
-
-
-def progress(msg: str) -> None:
-    print("[multi_key] " + msg, file=sys.stderr, flush=True)
-
-
-def to_dev(a: np.ndarray) -> torch.Tensor:
-    d = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-    torch.cuda.synchronize()
-    return d
-
-
-def host(d: torch.Tensor) -> np.ndarray:
-    return d.cpu().numpy().view(np.uint64)
-
-
-def block_bytes(values) -> np.ndarray:
-    return np.array([[(v >> (8 * (15 - b))) & 0xFF for b in range(16)] for v in values], dtype=np.uint8)
-
-
-def commit_id() -> str:
-    try:
-        return subprocess.run(["git", "-C", str(ROOT), "rev-parse", "HEAD"], capture_output=True, text=True, check=True).stdout.strip() + " + working tree"
-    except Exception:
-        return "unknown"
+TOOL = "multi_key"
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = measure.arg_parser()
     ap.add_argument("--commit", default=None, help="what the measured tree is (default: git rev-parse HEAD + working tree)")
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     p = PARAM_OPT
     rng = np.random.default_rng(0x3A17)
     aes_keys = [rng.bytes(16) for _ in range(max(KX_N))]
 
     client = Client(1, BASE, int.from_bytes(aes_keys[0], "big"), params=p, seed=0xAE50002)
-    keys = client.server_keys()
-    srv = Server(keys, device=0)
+    srv = Server(client.server_keys(), device=0)            # not measure.session: aes_ctr and aes_ctr_streams are timed through the Server
     eng = srv.engine
-    del keys
     eng.reserve(128 * 128)
     empty = lambda *shape: torch.empty(shape, dtype=torch.int64, device="cuda")  # noqa: E731
 
@@ -157,27 +121,17 @@ def main() -> int:
     assert plan == [248, 608] + [2048] * 8, plan
 
     # ---- one timed loop, every job once per step ----
-    times = {k: [] for k in jobs}
-    for i in range(args.warmup + args.steps):
-        t_step = time.perf_counter()
-        for k, (run, reset, _) in jobs.items():
-            reset()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            run()
-            eng.synchronize()
-            if i >= args.warmup:
-                times[k].append(time.perf_counter() - t0)
-        progress("step %d of %d: %.1f s" % (i + 1, args.warmup + args.steps, time.perf_counter() - t_step))
+    times = measure.wall(eng, {k: j[:2] for k, j in jobs.items()}, args.warmup, args.steps,
+                         on_step=lambda i, of, s: progress(TOOL, "step %d of %d: %.1f s" % (i, of, s)))
 
     all_ok = True
     rows = {}
     for k, (run, reset, verify) in jobs.items():
-        rows[k] = {"ms_median": round(1000 * statistics.median(times[k]), 3), "ms_all": [round(1000 * t, 3) for t in times[k]]}
+        rows[k] = measure.row(times[k])
         if verify is not None:
             rows[k]["verified"] = bool(verify())
             all_ok = all_ok and rows[k]["verified"]
-        progress("%s: %.2f ms%s" % (k, rows[k]["ms_median"], "" if verify is None else " verified=%s" % rows[k]["verified"]))
+        progress(TOOL, "%s: %.2f ms%s" % (k, rows[k]["ms_median"], "" if verify is None else " verified=%s" % rows[k]["verified"]))
     T = lambda k: rows[k]["ms_median"]  # noqa: E731
 
     # the linear stage of the two 128-block encryptions: one further profiled call each (HIP events around every launch, so kept out of the timed calls).
@@ -186,20 +140,10 @@ def main() -> int:
     # on top of that are 16 rows per layer for one key (cache) and up to one set per block for the keyed call
     linear_bytes = 49 * 16 * n_blocks * 8 * p.big1 * 8
     for k in ("aes_encrypt/128", "aes_encrypt_keyed/8x16"):
-        jobs[k][1]()
-        torch.cuda.synchronize()
-        eng.profile_enable(True)
-        eng.profile_reset()
-        jobs[k][0]()
-        prof = eng.profile_read()
-        eng.profile_enable(False)
-        rows[k]["stages_ms"] = {s: round(v["ms"], 3) for s, v in prof.items()}
+        prof = measure.profiled(eng, *jobs[k][:2])
+        rows[k]["stages_ms"] = measure.stage_ms(prof)
         rows[k]["linear_bytes"] = linear_bytes
         rows[k]["linear_TB_per_s"] = round(linear_bytes / (prof["linear"]["ms"] * 1e-3) / 1e12, 3)
-
-    def check(measured, predicted, bound):
-        return {"measured_ms": round(measured, 3), "predicted_ms": round(predicted, 3), "ratio": round(measured / predicted, 4), "bound": bound,
-                "within_bound": None if bound is None else bool(measured <= bound * predicted)}
 
     checks = {}
     for n in KX_N:
@@ -214,26 +158,19 @@ def main() -> int:
                                                          T("many_sbox/248") + T("many_sbox/608") + 7 * T("many_sbox/2048") + T("sbox/2048"), BOUND)
     checks["aes_ctr_streams_8x16_vs_8_aes_ctr_calls"] = check(T("aes_ctr_streams/8x16"), T("aes_ctr/8 calls of 16"), None)
     for name, c in checks.items():
-        progress("%s: %.2f / %.2f ms = %.4f%s" % (name, c["measured_ms"], c["predicted_ms"], c["ratio"],
+        progress(TOOL, "%s: %.2f / %.2f ms = %.4f%s" % (name, c["measured_ms"], c["predicted_ms"], c["ratio"],
                                                    "" if c["bound"] is None else " (bound %.2f: %s)" % (c["bound"], "ok" if c["within_bound"] else "MISSED")))
 
     launch_bits = sorted({32 * n for n in KX_N} | {CONV_N * 1152, 128 * 128, 8 * 248, 8 * 608})
-    line = {"tool": "multi_key", "params": p.name, "version": _native.load_library().fheaes_version().decode(), "commit": args.commit or commit_id(),
-            "engine_src_sha256": _build.engine_source_hash(), "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup,
+    line = {**measure.header(TOOL, args), "commit": args.commit or measure.commit_id(),
             "k2_kernels": {str(bits): eng.k2_plan(bits)["kernel"] for bits in launch_bits}, "streams_plan": plan,
             "all_verified": all_ok, "checks": checks, "rows": rows,
             "note": "wall clock per call on resident tensors (call + synchronize), median of the timed steps, AES-128; every row runs once in every "
                     "step of one loop; checks: measured against a yardstick made of entry points that existed before (bound null: reported only); "
                     "k2_kernels: fheaes_k2_context_plan's kernel per blind-rotation launch size in bits; linear_TB_per_s from one further profiled call"}
-    text = json.dumps(line)
-    print(text)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(text + "\n")
+    measure.emit(line, args.out)
     eng.close()
-    if not all_ok:
-        return 1
-    return 0 if all(c["within_bound"] is not False for c in checks.values()) else 2
+    return measure.exit_code(all_ok, all(c["within_bound"] is not False for c in checks.values()))
 
 
 if __name__ == "__main__":

@@ -21,57 +21,30 @@ the tool exit 1, a missed bound exit 2.
 """
 from __future__ import annotations
 
-import argparse
-import json
 import statistics
 import sys
 import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from tfhe_aes_amd import PARAM_OPT, _build, _native, aes_clear  # noqa: E402
-from tfhe_aes_amd.client import Client  # noqa: E402
+import measure
+from measure import host, progress, to_dev
+from tfhe_aes_amd import PARAM_OPT, aes_clear
 
 KEY = bytes.fromhex("2b7e151628aed2a6abf7158809cf4f3c")           # SP 800-38A F.1.1
 IV = 0x00112233445566778899AABBCCDDEE00
 N_BLOCKS = 128
-
-
-def progress(msg: str) -> None:
-    print("[pack_bits] " + msg, file=sys.stderr, flush=True)
-
-
-def to_dev(a: np.ndarray) -> torch.Tensor:
-    d = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-    torch.cuda.synchronize()
-    return d
-
-
-def host(d: torch.Tensor) -> np.ndarray:
-    return d.cpu().numpy().view(np.uint64)
+TOOL = "pack_bits"
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = measure.arg_parser(reps=10).parse_args()
     p = PARAM_OPT
     m = N_BLOCKS * 128
     gw, glwes = (p.k + 1) * p.N, m // p.N
 
-    client = Client(1, IV, int.from_bytes(KEY, "big"), params=p, seed=0xAE50001)
-    keys = client.server_keys()
-    eng = _native.Engine(p, device=0)
-    eng.upload_keys(keys.ksk, keys.bsk, keys.pfpksk)
-    del keys
+    client, eng = measure.session(0xAE50001, IV, int.from_bytes(KEY, "big"))
     eng.reserve(m)
 
     rng = np.random.default_rng(0x9AC4)
@@ -104,7 +77,7 @@ def main() -> int:
         if i >= args.warmup:
             wall["host_aes_ctr"].append(t1 - t0)
             wall["device_aes_ctr_pack_copy"].append(t2 - t1)
-        progress("way out, step %d of %d: host %.3f s, device + pack + copy %.3f s" % (i + 1, args.warmup + args.steps, t1 - t0, t2 - t1))
+        progress(TOOL, "way out, step %d of %d: host %.3f s, device + pack + copy %.3f s" % (i + 1, args.warmup + args.steps, t1 - t0, t2 - t1))
 
     # ---- verification ----
     ok_pack = client.decrypt_packed_bytes(h_packed, 16 * N_BLOCKS).tobytes() == plain
@@ -121,16 +94,12 @@ def main() -> int:
             a = glwe[g, :p.k][:, (i - c) % p.N]
             a[:, i + 1:] = np.uint64(0) - a[:, i + 1:]
             ok_unpack = ok_unpack and bool(np.array_equal(back[t, :p.big], a.reshape(-1))) and back[t, p.big] == glwe[g, p.k, i]
-    progress("verified: packed %s, host aes_ctr %s, unpacked %s" % (ok_pack, ok_host, ok_unpack))
+    progress(TOOL, "verified: packed %s, host aes_ctr %s, unpacked %s" % (ok_pack, ok_host, ok_unpack))
 
     # ---- the linear stage's rate: one profiled 128-block aes_encrypt ----
     d_state = d_ct.clone()
     torch.cuda.synchronize()
-    eng.profile_enable(True)
-    eng.profile_reset()
-    eng.aes_encrypt_bits(d_rk, 128, d_state, N_BLOCKS)
-    prof = eng.profile_read()
-    eng.profile_enable(False)
+    prof = measure.profiled(eng, lambda: eng.aes_encrypt_bits(d_rk, 128, d_state, N_BLOCKS))
     state_bytes = N_BLOCKS * 16 * 8 * p.big1 * 8
     # initial AddRoundKey (read + write), nine MixColumns layers (four terms read + one write; the round key stays in cache), the last
     # round's ShiftRows + AddRoundKey (one term read + one write)
@@ -142,39 +111,17 @@ def main() -> int:
     del d_state
 
     # ---- the bounded measurements: device events on a stream the engine shares with torch ----
-    stream = torch.cuda.Stream()
-    eng.set_stream(stream.cuda_stream)
     jobs = {"pack": lambda: eng.pack_bits(d_ct, m, d_packed),
             "unpack": lambda: eng.unpack_bits(d_packed, m, d_back),
             "pfpks_batch": lambda: eng.pfpks_batch(d_ct, d_ggsw, m)}
-    times = {k: [] for k in jobs}
-    for i in range(args.warmup + args.steps):
-        last = {}
-        for k, run in jobs.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            stream.synchronize()
-            a.record(stream)
-            for _ in range(args.reps):
-                run()
-            b.record(stream)
-            b.synchronize()
-            last[k] = a.elapsed_time(b) / args.reps
-            if i >= args.warmup:
-                times[k].append(last[k])
-        progress("step %d of %d: %s" % (i + 1, args.warmup + args.steps, ", ".join("%s %.3f ms" % kv for kv in last.items())))
-    stream.synchronize()
+    times = measure.events(eng, jobs, args.warmup, args.steps, args.reps, on_step=lambda i, of, last: progress(
+        TOOL, "step %d of %d: %s" % (i, of, ", ".join("%s %.3f ms" % kv for kv in last.items()))))
     ok_after = bool(np.array_equal(host(d_packed), h_packed)) and bool(np.array_equal(host(d_back), back))
 
     # per-stage split of one profiled pack and one profiled unpack
-    eng.profile_enable(True)
-    eng.profile_reset()
-    eng.pack_bits(d_ct, m, d_packed)
-    prof_pack = eng.profile_read()
-    eng.profile_reset()
-    eng.unpack_bits(d_packed, m, d_back)
-    prof_unpack = eng.profile_read()
-    eng.profile_enable(False)
-    eng.set_stream(None)
+    prof_pack = measure.profiled(eng, jobs["pack"])
+    prof_unpack = measure.profiled(eng, jobs["unpack"])
+    launched = lambda prof: measure.stage_ms({s: v for s, v in prof.items() if v["launches"]}, 4)  # noqa: E731
 
     med = {k: statistics.median(v) for k, v in times.items()}
     pack_ratio = med["pack"] / med["pfpks_batch"]
@@ -185,12 +132,9 @@ def main() -> int:
              "linear_stage_tb_per_s": round(linear_rate / 1e12, 3), "unpack_tb_per_s": round(unpack_bytes / (med["unpack"] * 1e-3) / 1e12, 3),
              "unpack_ratio": round(unpack_ratio, 4), "unpack_bound": 2.0, "unpack_within_bound": bool(unpack_ratio <= 2.0)}
     all_ok = ok_pack and ok_host and ok_unpack and ok_after
-    line = {"tool": "pack_bits", "params": p.name, "version": _native.load_library().fheaes_version().decode(),
-            "engine_src_sha256": _build.engine_source_hash(), "device": torch.cuda.get_device_name(0), "bits": m,
-            "steps": args.steps, "warmup": args.warmup, "reps": args.reps, "all_verified": all_ok, "check": check,
+    line = {**measure.header(TOOL, args), "bits": m, "reps": args.reps, "all_verified": all_ok, "check": check,
             "ms_all": {k: [round(t, 4) for t in v] for k, v in times.items()},
-            "pack_stages_ms": {s: round(v["ms"], 4) for s, v in prof_pack.items() if v["launches"]},
-            "unpack_stages_ms": {s: round(v["ms"], 4) for s, v in prof_unpack.items() if v["launches"]},
+            "pack_stages_ms": launched(prof_pack), "unpack_stages_ms": launched(prof_unpack),
             "fold_tb_per_s": round(m * gw * 8 / (prof_pack["linear"]["ms"] * 1e-3) / 1e12, 3),
             "way_out": {"lwe_bytes": state_bytes, "packed_bytes": glwes * gw * 8, "size_ratio": round(state_bytes / (glwes * gw * 8), 1),
                         "host_aes_ctr_s": round(statistics.median(wall["host_aes_ctr"]), 4),
@@ -202,15 +146,9 @@ def main() -> int:
                     "(bound 2); pack_stages_ms / unpack_stages_ms: fheaes_profile_read of one further profiled call (fold: its memset and "
                     "pack_fold_kernel under `linear`); way_out: wall clock, a host aes_ctr of 128 blocks against device aes_ctr + pack + "
                     "a host copy of the packed bytes"}
-    text = json.dumps(line)
-    print(text)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(text + "\n")
+    measure.emit(line, args.out)
     eng.close()
-    if not all_ok:
-        return 1
-    return 0 if check["pack_within_bound"] and check["unpack_within_bound"] else 2
+    return measure.exit_code(all_ok, check["pack_within_bound"] and check["unpack_within_bound"])
 
 
 if __name__ == "__main__":

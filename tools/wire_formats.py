@@ -22,58 +22,32 @@ read-back words: a wrong result makes the tool exit 1, a missed bound exit 2.
 """
 from __future__ import annotations
 
-import argparse
-import json
 import statistics
 import sys
 import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from tfhe_aes_amd import PARAM_OPT, _build, _native  # noqa: E402
-from tfhe_aes_amd.client import Client, read_back_packed  # noqa: E402
+import measure
+from measure import host, progress, to_dev
+from tfhe_aes_amd import PARAM_OPT
+from tfhe_aes_amd.client import read_back_packed
 
 N_KEYS = 128
 WIDTH = 16
 BOUNDS = {"expand": 6.0, "pack_mod": 1.05, "unpack_mod": 1.5}
-
-
-def progress(msg: str) -> None:
-    print("[wire_formats] " + msg, file=sys.stderr, flush=True)
-
-
-def to_dev(a: np.ndarray) -> torch.Tensor:
-    d = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-    torch.cuda.synchronize()
-    return d
-
-
-def host(d: torch.Tensor) -> np.ndarray:
-    return d.cpu().numpy().view(np.uint64)
+TOOL = "wire_formats"
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = measure.arg_parser(reps=10).parse_args()
     p = PARAM_OPT
     m = N_KEYS * 128
     gw, glwes = (p.k + 1) * p.N, m // p.N
     gw_mod = gw * WIDTH // 64
 
-    client = Client(params=p, seed=0xAE50001)
-    keys = client.server_keys()
-    eng = _native.Engine(p, device=0)
-    eng.upload_keys(keys.ksk, keys.bsk, keys.pfpksk)
-    del keys
+    client, eng = measure.session(0xAE50001)
     eng.reserve(m)
 
     rng = np.random.default_rng(0x31BE)
@@ -81,7 +55,7 @@ def main() -> int:
     seeded = client.encrypt_bytes_seeded(aes_keys.reshape(-1))               # bodies [2048][8]: 128 AES-128 keys
     t0 = time.perf_counter()
     full = seeded.expand()
-    progress("numpy expansion of %d ciphertexts: %.1f s" % (m, time.perf_counter() - t0))
+    progress(TOOL, "numpy expansion of %d ciphertexts: %.1f s" % (m, time.perf_counter() - t0))
 
     d_bodies = to_dev(seeded.bodies)
     d_lwe = torch.empty((m, p.big1), dtype=torch.int64, device="cuda")
@@ -111,7 +85,7 @@ def main() -> int:
         if i >= args.warmup:
             wall["host_call_on_expanded"].append(t1 - t0)
             wall["seeded_expand_then_device_call"].append(t2 - t1)
-        progress("way in, step %d of %d: host call on the expanded words %.4f s, seeded %.4f s" % (i + 1, args.warmup + args.steps, t1 - t0, t2 - t1))
+        progress(TOOL, "way in, step %d of %d: host call on the expanded words %.4f s, seeded %.4f s" % (i + 1, args.warmup + args.steps, t1 - t0, t2 - t1))
     ok_expand = bool(np.array_equal(host(d_lwe), full_flat)) and bool(np.array_equal(p64_host, p64_seeded)) and \
         client.decrypt_bytes(host(d_lwe).reshape(-1, 8, p.big1)).tobytes() == aes_keys.tobytes()
     del full, full_flat
@@ -135,33 +109,16 @@ def main() -> int:
     h = int(client.glwe_sk.sum())
     formula_std, bound = ((1 + h) / 12.0) ** 0.5 * 2.0 ** (64 - WIDTH), (1 + h) * 2.0 ** (63 - WIDTH)
     ok_noise = bool(np.abs(err).max() <= bound)
-    progress("verified: expansion %s, packing at %d bits %s, extraction %s, hard noise bound %s" % (ok_expand, WIDTH, ok_pack, ok_unpack, ok_noise))
+    progress(TOOL, "verified: expansion %s, packing at %d bits %s, extraction %s, hard noise bound %s" % (ok_expand, WIDTH, ok_pack, ok_unpack, ok_noise))
 
     # ---- the bounded measurements: device events on a stream the engine shares with torch ----
-    stream = torch.cuda.Stream()
-    eng.set_stream(stream.cuda_stream)
     jobs = {"unpack": lambda: eng.unpack_bits(d_p64, m, d_back),
             "expand": lambda: eng.expand_lwe_seeded(seeded.mask_key, seeded.first_index, d_bodies, m, d_lwe),
             "unpack_mod": lambda: eng.unpack_bits_mod(d_p16, m, WIDTH, d_back_mod),
             "pack": lambda: eng.pack_bits(d_lwe, m, d_p64),
             "pack_mod": lambda: eng.pack_bits_mod(d_lwe, m, WIDTH, d_p16)}
-    times = {k: [] for k in jobs}
-    for i in range(args.warmup + args.steps):
-        last = {}
-        for k, run in jobs.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            stream.synchronize()
-            a.record(stream)
-            for _ in range(args.reps):
-                run()
-            b.record(stream)
-            b.synchronize()
-            last[k] = a.elapsed_time(b) / args.reps
-            if i >= args.warmup:
-                times[k].append(last[k])
-        progress("step %d of %d: %s" % (i + 1, args.warmup + args.steps, ", ".join("%s %.4f ms" % kv for kv in last.items())))
-    stream.synchronize()
-    eng.set_stream(None)
+    times = measure.events(eng, jobs, args.warmup, args.steps, args.reps, on_step=lambda i, of, last: progress(
+        TOOL, "step %d of %d: %s" % (i, of, ", ".join("%s %.4f ms" % kv for kv in last.items()))))
     ok_after = bool(np.array_equal(host(d_p16), p16)) and bool(np.array_equal(host(d_p64), p64))
 
     med = {k: statistics.median(v) for k, v in times.items()}
@@ -171,9 +128,7 @@ def main() -> int:
     check.update({k + "_bound": BOUNDS[k] for k in ratios})
     check.update({k + "_within_bound": bool(ratios[k] <= BOUNDS[k]) for k in ratios})
     all_ok = ok_expand and ok_pack and ok_unpack and ok_noise and ok_after
-    line = {"tool": "wire_formats", "params": p.name, "version": _native.load_library().fheaes_version().decode(),
-            "engine_src_sha256": _build.engine_source_hash(), "device": torch.cuda.get_device_name(0), "bits": m, "width": WIDTH,
-            "steps": args.steps, "warmup": args.warmup, "reps": args.reps, "all_verified": all_ok, "check": check,
+    line = {**measure.header(TOOL, args), "bits": m, "width": WIDTH, "reps": args.reps, "all_verified": all_ok, "check": check,
             "ms": {k: round(v, 4) for k, v in med.items()}, "ms_all": {k: [round(t, 4) for t in v] for k, v in times.items()},
             "expand_tb_per_s": round(lwe_bytes / (med["expand"] * 1e-3) / 1e12, 3), "unpack_tb_per_s": round(lwe_bytes / (med["unpack"] * 1e-3) / 1e12, 3),
             "noise": {"h": h, "std_over_formula": round(float(err.std() / formula_std), 4), "max_over_hard_bound": round(float(np.abs(err).max() / bound), 4),
@@ -191,15 +146,9 @@ def main() -> int:
                     "expanded ciphertexts of 128 AES-128 keys (the engine's own upload of 268.6 MB, the pack, 655 KB back) against their "
                     "bodies copied to the device + fheaes_expand_lwe_seeded + the same pack on resident words + 655 KB back; noise: the error the "
                     "16-bit switch adds to the 16,384 phases against (1 + h) 2^(2(64-w)) / 12 and (1 + h) 2^(63-w)"}
-    text = json.dumps(line)
-    print(text)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(text + "\n")
+    measure.emit(line, args.out)
     eng.close()
-    if not all_ok:
-        return 1
-    return 0 if all(check[k + "_within_bound"] for k in ratios) else 2
+    return measure.exit_code(all_ok, all(check[k + "_within_bound"] for k in ratios))
 
 
 if __name__ == "__main__":
