@@ -350,6 +350,50 @@ int fheaes_pack_bits_mod(fheaes_ctx *ctx, const uint64_t *lwe_in, uint64_t m, ui
 /* sample extraction straight from the w-bit fields: word for word fheaes_unpack_bits of the read-back GLWEs (x' = v << (64-w)) */
 int fheaes_unpack_bits_mod(fheaes_ctx *ctx, const uint64_t *in, uint64_t m, uint32_t width, uint64_t *lwe_out, int memspace);
 
+/* ---- packed round keys --------------------------------------------------------- */
+/* The round keys are what a server keeps between requests, and in LWE form they are the fat object: [Nr+1][16][8][kN+1] is 23,079,936 /
+ * 27,276,288 / 31,472,640 bytes per AES-128 / 192 / 256 key at PARAM_OPT, 1.51 TB for FHEAES_MAX_KEYS AES-128 keys.  Packed, key i of a
+ * store is packed[i] = [G][(k+1)N] words, G = ceil((Nr+1) 128 / N) = 3 / 4 / 4 GLWEs: 61,440 / 81,920 / 81,920 bytes (375.6 / 333.0 /
+ * 384.2 times smaller), 4.03 GB for 65,536 AES-128 keys.  packed[i] is WORD FOR WORD what fheaes_pack_bits writes for slice i of the round
+ * keys flattened, m = (Nr+1) 128 bits: bit t = round * 128 + byte * 8 + bit (LSB first) lives in GLWE t / N, coefficient t % N; every key
+ * starts on a GLWE boundary, so a slice is a packed key set on its own (store, send, concatenate, shard it without its neighbours); the
+ * unused coefficients of a key's last GLWE are what fheaes_pack_bits leaves there (sums of nothing).  Decryption round keys
+ * (fheaes_aes_decryption_round_keys*) have the same shape and pack the same way; the caller knows which kind it holds, as with the LWE
+ * form.  64-bit words only.
+ *
+ * The *_keyed_packed calls read every round-key word from the store at the moment AddRoundKey needs it -- sample extraction of
+ * coefficient t % N (fheaes_unpack_bits' rule: a signed, reversed read of one polynomial per mask run) inside the linear layers -- so a
+ * key never exists in LWE form again once it is packed.  No new arithmetic: the words they write are, word for word, what the _keyed call
+ * writes when given fheaes_unpack_round_keys of the same store.
+ *
+ * Noise: a key word read from the packed form carries the key's noise plus the packing's (std 2^33.5 at PARAM_OPT against a nominal
+ * 2^56); it counts as NOMINAL for the noise guard, exactly as fheaes_unpack_bits outputs do, and the guard sees the counts of the
+ * unpacked schedules.  All of it is accounted under FHEAES_STAGE_LINEAR, the packing's matrix product under FHEAES_STAGE_PFPKS. */
+/* G: 3 / 4 / 4 for key_bits 128 / 192 / 256, 0 for anything else (host logic only, no context, no GPU) */
+uint32_t fheaes_round_keys_packed_glwes(uint32_t key_bits);
+/* round_keys [n_keys][Nr+1][16][8][kN+1] -> packed_out [n_keys][G][(k+1)N].  The K3 product runs over chunks of whole keys inside the
+ * workspace fheaes_pack_bits uses, the fold places each key's bits from its own GLWE boundary.  Needs uploaded keys (FHEAES_ERR_NOKEYS);
+ * n_keys as for the keyed calls; overlapping buffers are FHEAES_ERR_INVALID; FHEAES_DEVICE calls only enqueue. */
+int fheaes_pack_round_keys(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t *packed_out, int memspace);
+/* keys first_key .. first_key + n_keys of the store `packed` -> round_keys_out [n_keys][Nr+1][16][8][kN+1], slice j word for word
+ * fheaes_unpack_bits of packed[first_key + j].  No keys needed.  For migration, and the reference of the tests.  Only those keys' words
+ * are read.  Overlapping buffers are FHEAES_ERR_INVALID. */
+int fheaes_unpack_round_keys(fheaes_ctx *ctx, const uint64_t *packed, uint32_t key_bits, uint64_t first_key, uint64_t n_keys,
+                             uint64_t *round_keys_out, int memspace);
+/* fheaes_aes_encrypt_keyed / _decrypt_keyed / _decrypt_equivalent_keyed / fheaes_aes_public_keyed with a packed store
+ * [n_keys][G][(k+1)N] in place of round_keys.  The rules of their counterparts (key_of_block a HOST array, an entry >= n_keys
+ * FHEAES_ERR_INVALID, n_blocks = 0 FHEAES_OK, FHEAES_DEVICE only enqueues, the same windows), and a store that overlaps the state is
+ * FHEAES_ERR_INVALID.  One key (n_keys = 1, key_of_block all 0) serves where a single-key call would. */
+int fheaes_aes_encrypt_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys,
+                                    const uint32_t *key_of_block, uint64_t *state, uint64_t n_blocks, int memspace);
+int fheaes_aes_decrypt_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys,
+                                    const uint32_t *key_of_block, uint64_t *state, uint64_t n_blocks, int memspace);
+int fheaes_aes_decrypt_equivalent_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_dec_round_keys, uint32_t key_bits, uint64_t n_keys,
+                                               const uint32_t *key_of_block, uint64_t *state, uint64_t n_blocks, int memspace);
+int fheaes_aes_public_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys,
+                                   const uint32_t *key_of_block, const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks,
+                                   uint64_t *state_out, int memspace);
+
 /* ---- measurement --------------------------------------------------------------- */
 #define FHEAES_STAGE_KEYSWITCH 0
 #define FHEAES_STAGE_BLIND_ROTATE 1

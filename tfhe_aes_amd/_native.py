@@ -81,6 +81,13 @@ SIGNATURES = {
     "fheaes_packed_mod_switch": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_void_p, _c.c_int]),
     "fheaes_pack_bits_mod": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_void_p, _c.c_int]),
     "fheaes_unpack_bits_mod": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_void_p, _c.c_int]),
+    "fheaes_round_keys_packed_glwes": (_c.c_uint32, [_c.c_uint32]),
+    "fheaes_pack_round_keys": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_unpack_round_keys": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_encrypt_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _c.c_void_p, _c.c_uint64, _c.c_int]),
+    "fheaes_aes_decrypt_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _c.c_void_p, _c.c_uint64, _c.c_int]),
+    "fheaes_aes_decrypt_equivalent_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _c.c_void_p, _c.c_uint64, _c.c_int]),
+    "fheaes_aes_public_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _u64p, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_profile_enable": (_c.c_int, [_ctx, _c.c_int]),
     "fheaes_profile_reset": (_c.c_int, [_ctx]),
     "fheaes_profile_read": (_c.c_int, [_ctx, _c.c_int, _dp, _u64p, _u64p]),
@@ -351,15 +358,33 @@ class Engine:
     def aes_decrypt_equivalent_keyed(self, dec_round_keys, key_bits: int, n_keys: int, key_of_block, state, n_blocks: int):
         self._keyed(self._lib.fheaes_aes_decrypt_equivalent_keyed, dec_round_keys, key_bits, n_keys, key_of_block, state, n_blocks)
 
-    def aes_public_keyed(self, round_keys, key_bits: int, n_keys: int, key_of_block, blocks, data, state_out):
+    def aes_public_keyed(self, round_keys, key_bits: int, n_keys: int, key_of_block, blocks, data, state_out, packed: bool = False):
+        """`packed`: round_keys is a packed store [n_keys][G][(k+1)N] (fheaes_aes_public_keyed_packed)"""
         cnt = u128_pairs(blocks)
         kob = key_indices(key_of_block, len(cnt))
         dat = u128_pairs(data) if data is not None else None
         if dat is not None and len(dat) != len(cnt):
             raise ValueError("one data block per block expected")
-        self._check(self._lib.fheaes_aes_public_keyed(self._h, _ptr(round_keys)[0], key_bits, n_keys, kob.ctypes.data_as(_u32p), cnt.ctypes.data_as(_u64p),
-                                                      dat.ctypes.data_as(_u64p) if dat is not None else None, len(cnt), _ptr(state_out)[0],
-                                                      self._space(round_keys, state_out)))
+        fn = self._lib.fheaes_aes_public_keyed_packed if packed else self._lib.fheaes_aes_public_keyed
+        self._check(fn(self._h, _ptr(round_keys)[0], key_bits, n_keys, kob.ctypes.data_as(_u32p), cnt.ctypes.data_as(_u64p),
+                       dat.ctypes.data_as(_u64p) if dat is not None else None, len(cnt), _ptr(state_out)[0], self._space(round_keys, state_out)))
+
+    # packed round keys: a store [n_keys][G][(k+1)N], G = round_keys_packed_glwes(key_bits); the keyed calls read their key words from it
+    def pack_round_keys(self, round_keys, key_bits: int, n_keys: int, packed_out):
+        self._check(self._lib.fheaes_pack_round_keys(self._h, _ptr(round_keys)[0], key_bits, n_keys, _ptr(packed_out)[0], self._space(round_keys, packed_out)))
+
+    def unpack_round_keys(self, packed, key_bits: int, first_key: int, n_keys: int, round_keys_out):
+        self._check(self._lib.fheaes_unpack_round_keys(self._h, _ptr(packed)[0], key_bits, first_key, n_keys, _ptr(round_keys_out)[0],
+                                                       self._space(packed, round_keys_out)))
+
+    def aes_encrypt_keyed_packed(self, packed, key_bits: int, n_keys: int, key_of_block, state, n_blocks: int):
+        self._keyed(self._lib.fheaes_aes_encrypt_keyed_packed, packed, key_bits, n_keys, key_of_block, state, n_blocks)
+
+    def aes_decrypt_keyed_packed(self, packed, key_bits: int, n_keys: int, key_of_block, state, n_blocks: int):
+        self._keyed(self._lib.fheaes_aes_decrypt_keyed_packed, packed, key_bits, n_keys, key_of_block, state, n_blocks)
+
+    def aes_decrypt_equivalent_keyed_packed(self, packed, key_bits: int, n_keys: int, key_of_block, state, n_blocks: int):
+        self._keyed(self._lib.fheaes_aes_decrypt_equivalent_keyed_packed, packed, key_bits, n_keys, key_of_block, state, n_blocks)
 
     # -- packed ciphertexts: N bits per GLWE (include/fheaes.h) -------------------
     def packed_words(self, m: int) -> int:
@@ -500,6 +525,11 @@ def aes_public_plan_keyed(blocks, key_of_block, n_keys: int, key_bits: int = 128
     if rc != 0:
         raise FheAesError(rc, "fheaes_aes_public_plan_keyed: key_bits must be 128, 192 or 256, n_keys in 1..65536 and every key index below n_keys")
     return [int(x) for x in out[:{128: 10, 192: 12, 256: 14}[key_bits]]]
+
+
+def round_keys_packed_glwes(key_bits: int) -> int:
+    """GLWEs that hold one key's packed round keys: 3 / 4 / 4 for AES-128 / 192 / 256, 0 for anything else (host only, no GPU)"""
+    return int(load_library().fheaes_round_keys_packed_glwes(int(key_bits)))
 
 
 def aes_public_plan(blocks, key_bits: int = 128) -> list[int]:

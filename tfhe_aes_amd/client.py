@@ -254,6 +254,74 @@ def _param_shape(p: WopbsParameters) -> np.ndarray:
                      p.ks_level, p.pfks_base_log, p.pfks_level, p.cbs_base_log, p.cbs_level], dtype=np.uint32)
 
 
+# ---- packed round keys (include/fheaes.h, "packed round keys") ------------------------------------------------------------------------
+AES_ROUNDS = {128: 10, 192: 12, 256: 14}
+
+
+def packed_key_glwes(params: WopbsParameters, key_bits: int) -> int:
+    """G = ceil((Nr+1) 128 / N) GLWEs hold one key's round keys: 3 / 4 / 4 for AES-128 / 192 / 256 (fheaes_round_keys_packed_glwes)"""
+    if key_bits not in AES_ROUNDS:
+        raise ValueError("key_bits must be 128, 192 or 256, got %r" % (key_bits,))
+    return -(-(AES_ROUNDS[key_bits] + 1) * 128 // params.N)
+
+
+@dataclass
+class PackedRoundKeys:
+    """The round keys of n_keys AES keys of one size, packed: ``data`` is [n_keys][G][(k+1)N] words (a host array, or a resident tensor),
+    slice i word for word ``Server.pack`` of key i's round keys [Nr+1][16][8][kN+1] -- bit round * 128 + byte * 8 + bit in GLWE t // N,
+    coefficient t % N, every key on a GLWE boundary.  61,440 bytes per AES-128 key at PARAM_OPT against 23,079,936.  Every ``Server``
+    method that takes round keys takes this in their place and reads the key words from it; ``prk[i]`` / ``prk[a:b]`` are stores of their
+    own (views), ``PackedRoundKeys.concat`` joins stores.  Encryption and decryption round keys look alike: the caller knows which it holds."""
+    params: WopbsParameters
+    key_bits: int
+    data: object                   # uint64 ndarray or int64 tensor, [n_keys][G][(k+1)N]
+
+    def __post_init__(self):
+        want = (packed_key_glwes(self.params, self.key_bits), (self.params.k + 1) * self.params.N)
+        shape = tuple(int(d) for d in self.data.shape)
+        if len(shape) != 3 or shape[0] < 1 or shape[1:] != want:
+            raise ValueError("packed AES-%d round keys are [n_keys][%d][%d] words with n_keys >= 1, got shape %s" % ((self.key_bits,) + want + (shape,)))
+
+    @property
+    def n_keys(self) -> int:
+        return int(self.data.shape[0])
+
+    @property
+    def nbytes(self) -> int:
+        return 8 * self.n_keys * int(self.data.shape[1]) * int(self.data.shape[2])
+
+    def __len__(self) -> int:
+        return self.n_keys
+
+    def __getitem__(self, i) -> "PackedRoundKeys":
+        if isinstance(i, slice):
+            if i.step not in (None, 1):
+                raise ValueError("a slice of a packed store is a contiguous range of keys")
+            return PackedRoundKeys(self.params, self.key_bits, self.data[i])
+        i = int(i)
+        if not -self.n_keys <= i < self.n_keys:
+            raise IndexError("key %d of a store of %d" % (i, self.n_keys))
+        i %= self.n_keys
+        return PackedRoundKeys(self.params, self.key_bits, self.data[i:i + 1])
+
+    @staticmethod
+    def concat(stores) -> "PackedRoundKeys":
+        """one store holding the keys of `stores` in order: same parameter set, key size and memory space"""
+        stores = list(stores)
+        if not stores:
+            raise ValueError("nothing to concatenate")
+        first = stores[0]
+        if any(s.params != first.params or s.key_bits != first.key_bits for s in stores):
+            raise ValueError("stores of one parameter set and one key size concatenate, keys of several sizes do not share a store")
+        if all(isinstance(s.data, np.ndarray) for s in stores):
+            return PackedRoundKeys(first.params, first.key_bits, np.concatenate([s.data for s in stores]))
+        if any(isinstance(s.data, np.ndarray) for s in stores):
+            raise ValueError("all stores must live in the same memory space")
+        import torch
+
+        return PackedRoundKeys(first.params, first.key_bits, torch.cat([s.data for s in stores]))
+
+
 @dataclass
 class ServerKeys:
     """What ``client_encrypt`` hands to ``Server::new`` (client.rs:143): the evaluation keys."""
@@ -311,6 +379,7 @@ CIPHERTEXT_KINDS = {
     "bytes": (8,),              # [n][8][kN+1]                          sbox / many_sbox inputs
     "packed": (),               # [G][(k+1)N]                           Server.pack output: N bits per GLWE ciphertext
     "packed_mod": (),           # [G][(k+1) 8 width]                    Server.pack(width=w) output, 8 <= w <= 32: the width travels with the words
+    "packed_round_keys": (),    # [n_keys][G][(k+1)N]                   a PackedRoundKeys store: the key size travels with the words
 }
 
 
@@ -341,9 +410,22 @@ def _kind_width(kind: str, width) -> int:
     return int(width)
 
 
-def save_ciphertexts(path, params: WopbsParameters, kind: str, words: np.ndarray, width: int | None = None) -> None:
+def _save_packed_round_keys(path, params: WopbsParameters, prk) -> None:
+    if not isinstance(prk, PackedRoundKeys) or not isinstance(prk.data, np.ndarray):
+        raise ValueError("the 'packed_round_keys' kind saves a PackedRoundKeys on the host")
+    if prk.params != params:
+        raise ValueError("these keys were packed for %s, not %s" % (prk.params.name, params.name))
+    np.savez(path, shape=_param_shape(params), kind=np.frombuffer(b"packed_round_keys".ljust(24, b"\0"), dtype=np.uint8),
+             key_bits=np.array([prk.key_bits], dtype=np.uint32), words=np.ascontiguousarray(prk.data, dtype=np.uint64))
+
+
+def save_ciphertexts(path, params: WopbsParameters, kind: str, words, width: int | None = None) -> None:
+    """`words`: an array of the kind's shape; for "packed_round_keys" a PackedRoundKeys (its key size is recorded)"""
     if kind not in CIPHERTEXT_KINDS:
         raise ValueError("kind must be one of %s" % ", ".join(CIPHERTEXT_KINDS))
+    if kind == "packed_round_keys":
+        _kind_width(kind, width)
+        return _save_packed_round_keys(path, params, words)
     w = _kind_width(kind, width)
     tail = _kind_tail(kind, params, w)
     a = np.ascontiguousarray(words, dtype=np.uint64)
@@ -353,14 +435,24 @@ def save_ciphertexts(path, params: WopbsParameters, kind: str, words: np.ndarray
     np.savez(path, shape=_param_shape(params), kind=np.frombuffer(kind.encode().ljust(16, b"\0"), dtype=np.uint8), words=a, **extra)
 
 
-def load_ciphertexts(path, params: WopbsParameters, kind: str, width: int | None = None) -> np.ndarray:
+def load_ciphertexts(path, params: WopbsParameters, kind: str, width: int | None = None, key_bits: int | None = None):
+    """the array saved under `kind`; for "packed_round_keys" a PackedRoundKeys, and `key_bits` (if given) must be the recorded key size"""
     w = _kind_width(kind, width)
+    if key_bits is not None and kind != "packed_round_keys":
+        raise ValueError("only the 'packed_round_keys' kind has a key size")
     with np.load(path, allow_pickle=False) as z:
         if list(map(int, z["shape"])) != list(map(int, _param_shape(params))):
             raise ValueError("ciphertext file was produced for a different parameter set")
         got = bytes(z["kind"]).rstrip(b"\0").decode()
         if got != kind:
             raise ValueError("ciphertext file holds %r, expected %r" % (got, kind))
+        if kind == "packed_round_keys":
+            if "key_bits" not in z.files or z["key_bits"].shape != (1,):
+                raise ValueError("ciphertext file does not record the key size of its packed round keys")
+            have = int(z["key_bits"][0])
+            if key_bits is not None and have != int(key_bits):
+                raise ValueError("ciphertext file holds packed AES-%d round keys, expected AES-%d" % (have, int(key_bits)))
+            return PackedRoundKeys(params, have, z["words"].astype(np.uint64))      # the shape is checked against the key size there
         if kind == "packed_mod" and ("width" not in z.files or z["width"].shape != (1,) or int(z["width"][0]) != w):
             raise ValueError("ciphertext file holds words of width %s, expected %d" % (int(z["width"][0]) if "width" in z.files else "?", w))
         a = z["words"].astype(np.uint64)

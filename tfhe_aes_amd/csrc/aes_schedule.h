@@ -75,7 +75,7 @@ static int aes_run_dev(fheaes_ctx *c, const KeySets &rk, uint64_t *state, uint64
     const uint64_t bw = 8ull * c->big1, sw = 16 * bw, steps = sch.steps.size();
     auto key_of = [&](const AesStep &st, uint64_t first_block) {
         if (st.key_round < 0) return KeySets{nullptr, nullptr, 0};
-        return KeySets{rk.rk + (uint64_t)st.key_round * sw, rk.of_block ? rk.of_block + first_block : nullptr, rk.stride};
+        return rk.round((uint64_t)st.key_round, sw, first_block);
     };
     const uint64_t w = aes_context_window(c, n_blocks, steps);
     TRY(ensure(c, c->ws_vp, (w ? w : n_blocks) * 16 * sch.max_luts * bw * 8));
@@ -326,43 +326,47 @@ static void public_plan(const uint64_t *blocks, const uint64_t *data, const uint
 static_assert(FHEAES_MAX_KEYS == PUBLIC_MAX_KEYS, "fheaes.h's bound on n_keys is the key field of PUBLIC_HEAD");
 #define PUBLIC_MAX_BLOCKS (1ull << 26)      /* 16 n pool entries x 4 must fit a PUBLIC_TERM word */
 
-static int launch_public_round1(fheaes_ctx *c, const uint32_t *head, const uint64_t *rk0, uint64_t key_stride, uint64_t *out, uint64_t n_pool)
+static int launch_public_round1(fheaes_ctx *c, const uint32_t *head, const KeySets &rk0, uint64_t *out, uint64_t n_pool)
 {
     TRY(noise_guard(c, 1, "the initial AddRoundKey on public bytes"));          // a trivial ciphertext carries no noise
     StageScope sc(c, FHEAES_STAGE_LINEAR, (n_pool + 15) / 16);
     dim3 grid((8 * c->big1 + 1023) / 1024, (unsigned)std::min<uint64_t>(n_pool, 65535));
-    hipLaunchKernelGGL(public_round1_kernel, grid, dim3(256), 0, c->stream, head, rk0, key_stride, out, n_pool, c->big1);
+    if (rk0.packed_glwes) hipLaunchKernelGGL(public_round1_packed_kernel, grid, dim3(256), 0, c->stream, head, rk0.rk, rk0.stride, c->k, out, n_pool);
+    else hipLaunchKernelGGL(public_round1_kernel, grid, dim3(256), 0, c->stream, head, rk0.rk, rk0.stride, out, n_pool, c->big1);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
 
 static int launch_gather_indexed(fheaes_ctx *c, const uint64_t *pool, uint32_t n_luts, const uint32_t *head, const uint32_t *term, uint32_t terms,
-                                 const uint64_t *rk, uint64_t key_stride, uint64_t *out, uint64_t n_out)
+                                 const KeySets &rk, uint64_t *out, uint64_t n_out)
 {
     TRY(noise_guard(c, terms + 1u, "the indexed linear layer (MixColumns / ShiftRows + AddRoundKey over a pool)"));
     StageScope sc(c, FHEAES_STAGE_LINEAR, (n_out + 15) / 16);
     dim3 grid((8 * c->big1 + 1023) / 1024, (unsigned)std::min<uint64_t>(n_out, 65535));
-    hipLaunchKernelGGL(gather_add_indexed_kernel, grid, dim3(256), 0, c->stream, pool, n_luts, head, term, terms, rk, key_stride, out, n_out, c->big1);
+    if (rk.packed_glwes)
+        hipLaunchKernelGGL(gather_add_indexed_packed_kernel, grid, dim3(256), 0, c->stream, pool, n_luts, head, term, terms, rk.rk, rk.stride, rk.bit0, c->k, out, n_out);
+    else
+        hipLaunchKernelGGL(gather_add_indexed_kernel, grid, dim3(256), 0, c->stream, pool, n_luts, head, term, terms, rk.rk, rk.stride, out, n_out, c->big1);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
 
-// `out` [n_blocks][16][8][kN+1] doubles as the pool buffer: no pool has more than 16 n_blocks entries.  rk: [n_keys][Nr+1][16][8][kN+1],
-// the key of every pool entry is in its head word
-static int aes_public_dev(fheaes_ctx *c, const uint64_t *rk, const PublicPlan &pl, int nr, uint64_t *out)
+// `out` [n_blocks][16][8][kN+1] doubles as the pool buffer: no pool has more than 16 n_blocks entries.  rk: the call's sets of round keys
+// ([n_keys][Nr+1][16][8][kN+1] or a packed store); the key of every pool entry is in its head word, so rk.of_block is not read
+static int aes_public_dev(fheaes_ctx *c, const KeySets &rk, const PublicPlan &pl, int nr, uint64_t *out)
 {
-    const uint64_t bw = 8ull * c->big1, sw = 16 * bw, ks = (uint64_t)(nr + 1) * sw;
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw;
     // the index tables go through the context's pinned buffer (as add_scalar's counter bytes): the call only enqueues
     const size_t tab_bytes = pl.words.size() * sizeof(uint32_t);
     TRY(upload_pinned(c, tab_bytes, tab_bytes, [&](uint8_t *pin) { memcpy(pin, pl.words.data(), tab_bytes); }));
     const uint32_t *tab = (const uint32_t *)c->ws_misc.p;
     TRY(ensure(c, c->ws_vp, pl.max_vp_bytes_per_bw * bw * 8));               // the largest pool, not 16 n
     uint64_t *vp = (uint64_t *)c->ws_vp.p;
-    TRY(launch_public_round1(c, tab + pl.layers[0].head, rk, ks, out, pl.layers[0].n));
+    TRY(launch_public_round1(c, tab + pl.layers[0].head, rk.round(0, sw), out, pl.layers[0].n));
     for (int round = 1; round <= nr; ++round) {
         const PublicPlan::Layer &in = pl.layers[round - 1], &to = pl.layers[round];
         TRY(many_sbox_dev(c, out, in.n, round < nr ? LUTSET_ENC_ROUND : LUTSET_SBOX, vp));
-        TRY(launch_gather_indexed(c, vp, round < nr ? 3 : 1, tab + to.head, tab + to.term, to.terms, rk + (uint64_t)round * sw, ks, out, to.n));
+        TRY(launch_gather_indexed(c, vp, round < nr ? 3 : 1, tab + to.head, tab + to.term, to.terms, rk.round((uint64_t)round, sw), out, to.n));
     }
     return FHEAES_OK;
 }

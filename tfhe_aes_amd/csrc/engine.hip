@@ -645,21 +645,31 @@ static int check_key_of_block(fheaes_ctx *c, const uint32_t *key_of_block, uint6
     return FHEAES_OK;
 }
 
+// G GLWEs hold the (Nr+1) 128 bits of one key's round keys; 0: not an AES key size
+static uint32_t packed_key_glwes(uint32_t key_bits)
+{
+    const int nr = aes_rounds(key_bits);
+    return nr ? (uint32_t)(((uint64_t)(nr + 1) * AES_BLOCK_BITS + FHE_N - 1) / FHE_N) : 0;
+}
+
 // The three block ciphers.  key_of_block null: the single-key entry points (one set of round keys, no table); else block b runs under
 // round_keys[key_of_block[b]] of [n_keys][Nr+1][16][8][kN+1], the table going to the device through the pinned buffer (one key: no table either).
+// packed: round_keys is a packed store [n_keys][G][(k+1)N] (fheaes_pack_round_keys) and the linear layers read the key words from it.
 static int aes_crypt(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, uint64_t *state,
-                     uint64_t n_blocks, int memspace, AesDevFn dev)
+                     uint64_t n_blocks, int memspace, AesDevFn dev, bool packed = false)
 {
     TRY(check_keys(c));
     if (!round_keys || !state) return c->fail(FHEAES_ERR_INVALID, "null pointer");
     TRY(check_key_bits(c, key_bits));
     const int nr = aes_rounds(key_bits);
-    const uint64_t sw = 16ull * 8 * c->big1, ks = (uint64_t)(nr + 1) * sw;
+    const uint32_t glwes = packed ? packed_key_glwes(key_bits) : 0;
+    const uint64_t sw = 16ull * 8 * c->big1, ks = packed ? (uint64_t)glwes * c->k1 * FHE_N : (uint64_t)(nr + 1) * sw;
     if (key_of_block) {
         TRY(check_n_keys(c, n_keys));
         TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
         if (n_blocks == 0) return FHEAES_OK;
     }
+    if (packed && overlap(round_keys, n_keys * ks * 8, state, n_blocks * sw * 8)) return c->fail(FHEAES_ERR_INVALID, "the packed round keys and the state overlap");
     HIP_TRY(c, hipSetDevice(c->device));
     Staged s(c, memspace);
     TRY(s.in(round_keys, n_keys * ks * 8, &round_keys));
@@ -669,7 +679,7 @@ static int aes_crypt(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bit
         TRY(upload_pinned(c, n_blocks * sizeof(uint32_t), n_blocks * sizeof(uint32_t), [&](uint8_t *pin) { memcpy(pin, key_of_block, n_blocks * sizeof(uint32_t)); }));
         table = (const uint32_t *)c->ws_misc.p;
     }
-    TRY(dev(c, KeySets{round_keys, table, ks}, state, n_blocks, nr));
+    TRY(dev(c, KeySets{round_keys, table, ks, glwes}, state, n_blocks, nr));
     return s.finish();
 }
 
@@ -708,12 +718,12 @@ int fheaes_aes_decrypt_equivalent(fheaes_ctx *c, const uint64_t *dec_round_keys,
 }
 
 static int aes_crypt_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, uint64_t *state,
-                           uint64_t n_blocks, int memspace, AesDevFn dev)
+                           uint64_t n_blocks, int memspace, AesDevFn dev, bool packed = false)
 {
     CtxLock lock__(c);
     TRY(check_keys(c));
     if (!key_of_block) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    return aes_crypt(c, round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, dev);
+    return aes_crypt(c, round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, dev, packed);
 }
 
 int fheaes_aes_encrypt_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, uint64_t *state,
@@ -732,6 +742,24 @@ int fheaes_aes_decrypt_equivalent_keyed(fheaes_ctx *c, const uint64_t *dec_round
                                         uint64_t *state, uint64_t n_blocks, int memspace)
 {
     return aes_crypt_keyed(c, dec_round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_decrypt_eq_dev);
+}
+
+int fheaes_aes_encrypt_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
+                                    uint64_t *state, uint64_t n_blocks, int memspace)
+{
+    return aes_crypt_keyed(c, packed_round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_encrypt_dev, true);
+}
+
+int fheaes_aes_decrypt_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
+                                    uint64_t *state, uint64_t n_blocks, int memspace)
+{
+    return aes_crypt_keyed(c, packed_round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_decrypt_dev, true);
+}
+
+int fheaes_aes_decrypt_equivalent_keyed_packed(fheaes_ctx *c, const uint64_t *packed_dec_round_keys, uint32_t key_bits, uint64_t n_keys,
+                                               const uint32_t *key_of_block, uint64_t *state, uint64_t n_blocks, int memspace)
+{
+    return aes_crypt_keyed(c, packed_dec_round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_decrypt_eq_dev, true);
 }
 
 // the two per-key calls: n_keys sets in, n_keys sets out
@@ -819,18 +847,20 @@ int fheaes_add_scalar(fheaes_ctx *c, uint64_t *state, uint64_t n_blocks, const u
 
 // key_of_block null: every block under the one set `round_keys`
 static int aes_public(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, const uint64_t *blocks,
-                      const uint64_t *data, uint64_t n_blocks, uint64_t *state_out, int memspace)
+                      const uint64_t *data, uint64_t n_blocks, uint64_t *state_out, int memspace, bool packed = false)
 {
     const int nr = aes_rounds(key_bits);
+    const uint32_t glwes = packed ? packed_key_glwes(key_bits) : 0;
+    const uint64_t sw = 16ull * 8 * c->big1, ks = packed ? (uint64_t)glwes * c->k1 * FHE_N : (uint64_t)(nr + 1) * sw;
+    if (packed && overlap(round_keys, n_keys * ks * 8, state_out, n_blocks * sw * 8)) return c->fail(FHEAES_ERR_INVALID, "the packed round keys and state_out overlap");
     if (n_blocks > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %llu", (unsigned long long)PUBLIC_MAX_BLOCKS);
     HIP_TRY(c, hipSetDevice(c->device));
     PublicPlan pl;
     public_plan(blocks, data, key_of_block, n_blocks, nr, pl);
     Staged s(c, memspace);
-    const uint64_t sw = 16ull * 8 * c->big1;
-    TRY(s.in(round_keys, n_keys * (uint64_t)(nr + 1) * sw * 8, &round_keys));
+    TRY(s.in(round_keys, n_keys * ks * 8, &round_keys));
     TRY(s.out(state_out, n_blocks * sw * 8, &state_out));
-    TRY(aes_public_dev(c, round_keys, pl, nr, state_out));
+    TRY(aes_public_dev(c, KeySets{round_keys, nullptr, ks, glwes}, pl, nr, state_out));
     return s.finish();
 }
 
@@ -876,6 +906,19 @@ int fheaes_aes_public_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t 
     TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
     if (n_blocks == 0) return FHEAES_OK;
     return aes_public(c, round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace);
+}
+
+int fheaes_aes_public_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
+                                   const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
+{
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!packed_round_keys || !key_of_block || !blocks_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    TRY(check_n_keys(c, n_keys));
+    TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
+    if (n_blocks == 0) return FHEAES_OK;
+    return aes_public(c, packed_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, true);
 }
 
 static void plan_counts(const PublicPlan &pl, uint64_t n_blocks, int nr, uint64_t *unique_bytes_per_round)
@@ -942,6 +985,50 @@ int fheaes_unpack_bits(fheaes_ctx *c, const uint64_t *glwe_in, uint64_t m, uint6
     TRY(s.in(glwe_in, in_bytes, &glwe_in));
     TRY(s.out(lwe_out, out_bytes, &lwe_out));
     TRY(unpack_dev(c, glwe_in, m, lwe_out));
+    return s.finish();
+}
+
+// ---- packed round keys --------------------------------------------------------------------------
+uint32_t fheaes_round_keys_packed_glwes(uint32_t key_bits) { return packed_key_glwes(key_bits); }
+
+int fheaes_pack_round_keys(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t *packed_out, int memspace)
+{
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!round_keys || !packed_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    TRY(check_n_keys(c, n_keys));
+    const uint64_t m = (uint64_t)(aes_rounds(key_bits) + 1) * AES_BLOCK_BITS, glwes = packed_key_glwes(key_bits);
+    const uint64_t in_bytes = n_keys * m * c->big1 * 8, out_bytes = n_keys * glwes * c->k1 * FHE_N * 8;
+    if (overlap(round_keys, in_bytes, packed_out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "round_keys and packed_out overlap (packing is not in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    TRY(s.in(round_keys, in_bytes, &round_keys));
+    TRY(s.out(packed_out, out_bytes, &packed_out));
+    TRY(pack_keys_dev(c, round_keys, m, n_keys, packed_out));
+    return s.finish();
+}
+
+int fheaes_unpack_round_keys(fheaes_ctx *c, const uint64_t *packed, uint32_t key_bits, uint64_t first_key, uint64_t n_keys, uint64_t *round_keys_out,
+                             int memspace)
+{
+    CtxLock lock__(c);
+    if (!c) return FHEAES_ERR_INVALID;
+    if (!packed || !round_keys_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    TRY(check_n_keys(c, n_keys));
+    if (first_key > FHEAES_MAX_KEYS - n_keys)
+        return c->fail(FHEAES_ERR_INVALID, "keys %llu .. %llu lie beyond the %u a store can hold", (unsigned long long)first_key,
+                       (unsigned long long)(first_key + n_keys), (unsigned)FHEAES_MAX_KEYS);
+    const uint64_t m = (uint64_t)(aes_rounds(key_bits) + 1) * AES_BLOCK_BITS, key_words = (uint64_t)packed_key_glwes(key_bits) * c->k1 * FHE_N;
+    packed += first_key * key_words;                                                     // only the keys asked for are read (and staged)
+    const uint64_t in_bytes = n_keys * key_words * 8, out_bytes = n_keys * m * c->big1 * 8;
+    if (overlap(packed, in_bytes, round_keys_out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "packed and round_keys_out overlap (unpacking is not in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    TRY(s.in(packed, in_bytes, &packed));
+    TRY(s.out(round_keys_out, out_bytes, &round_keys_out));
+    TRY(unpack_keys_dev(c, packed, m, n_keys, round_keys_out));
     return s.finish();
 }
 

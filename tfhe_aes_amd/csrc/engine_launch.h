@@ -368,11 +368,20 @@ int noise_guard(fheaes_ctx *c, uint32_t level, const char *what)
 
 // The AES keys of a call: `rk` holds n sets of round keys `stride` words apart (slice i of [n_keys][Nr+1][16][8][kN+1]) and block b works
 // under set of_block[b] (a device table).  of_block null: one set for every block -- the single-key entry points, which upload no table.
+// packed_glwes = G > 0: `rk` is a packed store instead (fheaes_pack_round_keys: key i = G GLWEs at i * stride words, stride = G (k+1) N) and
+// `bit0` the first bit of the round in question; the launchers then take the packed-key kernels, which read the same words from there.
 struct KeySets {
     const uint64_t *rk;
     const uint32_t *of_block;
     uint64_t stride;
-    KeySets round(uint64_t r, uint64_t sw) const { return {rk + r * sw, of_block, stride}; }
+    uint32_t packed_glwes = 0, bit0 = 0;
+    // round r of every set; blocks from `first_block` on
+    KeySets round(uint64_t r, uint64_t sw, uint64_t first_block = 0) const
+    {
+        const uint32_t *of = of_block ? of_block + first_block : nullptr;
+        if (packed_glwes) return {rk, of, stride, packed_glwes, bit0 + (uint32_t)(r * AES_BLOCK_BITS)};
+        return {rk + r * sw, of, stride};
+    }
 };
 
 int launch_gather(fheaes_ctx *c, const uint64_t *src, uint32_t n_luts, const KeySets &k, uint64_t *out, uint64_t n_blocks, const GatherTable &t)
@@ -382,7 +391,10 @@ int launch_gather(fheaes_ctx *c, const uint64_t *src, uint32_t n_luts, const Key
     StageScope sc(c, FHEAES_STAGE_LINEAR, n_blocks);
     const uint32_t bw = 8 * c->big1;
     dim3 grid((bw + 1023) / 1024, 16, (unsigned)n_blocks);
-    hipLaunchKernelGGL(gather_add_kernel, grid, dim3(256), 0, c->stream, src, n_luts, k.rk, k.of_block, k.stride, out, n_blocks, bw, t);
+    if (k.rk && k.packed_glwes)
+        hipLaunchKernelGGL(gather_add_packed_kernel, grid, dim3(256), 0, c->stream, src, n_luts, k.rk, k.of_block, k.stride, k.bit0, c->k, out, n_blocks, bw, t);
+    else
+        hipLaunchKernelGGL(gather_add_kernel, grid, dim3(256), 0, c->stream, src, n_luts, k.rk, k.of_block, k.stride, out, n_blocks, bw, t);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
@@ -394,7 +406,10 @@ int launch_add_bcast(fheaes_ctx *c, uint64_t *dst, const KeySets &k, uint64_t wo
     StageScope sc(c, FHEAES_STAGE_LINEAR, n_blocks);
     const unsigned gx = (unsigned)std::min<uint64_t>((words_per_block + 255) / 256, 64);
     dim3 grid(gx, (unsigned)std::min<uint64_t>(n_blocks, std::max<uint64_t>(1, 16384 / gx)));
-    hipLaunchKernelGGL(add_bcast_kernel, grid, dim3(256), 0, c->stream, dst, k.rk, k.of_block, k.stride, words_per_block, n_blocks);
+    if (k.packed_glwes)
+        hipLaunchKernelGGL(add_bcast_packed_kernel, grid, dim3(256), 0, c->stream, dst, k.rk, k.of_block, k.stride, k.bit0, c->k, words_per_block, n_blocks);
+    else
+        hipLaunchKernelGGL(add_bcast_kernel, grid, dim3(256), 0, c->stream, dst, k.rk, k.of_block, k.stride, words_per_block, n_blocks);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
@@ -468,6 +483,41 @@ int unpack_dev(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out)
                            in + t0 / FHE_N * (uint64_t)c->k1 * FHE_N, mc, c->k, out + t0 * c->big1);
         HIP_TRY(c, hipGetLastError());
     }
+    return FHEAES_OK;
+}
+
+// fheaes_pack_round_keys on device pointers: in [n_keys][m][kN+1] -> out [n_keys][ceil(m/N)][(k+1)N], slice i word for word pack_dev of slice
+// i.  The keys' LWEs are contiguous, so key block k's switch runs over chunks of whole keys inside ws_ggsw under pack_dev's rule (grown only
+// by a context that holds less than one key's worth of it); pack_fold_kernel then folds each key of the chunk from its own GLWE boundary.
+int pack_keys_dev(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t n_keys, uint64_t *out)
+{
+    const uint64_t gsz = (uint64_t)c->k1 * FHE_N, glwes = (m + FHE_N - 1) / FHE_N, max_keys = MAX_CHUNK_BITS / m;
+    uint64_t chunk = c->ws_ggsw.bytes / (gsz * 8) / m;
+    if (chunk == 0) {
+        chunk = std::min<uint64_t>(n_keys, max_keys);
+        TRY(ensure(c, c->ws_ggsw, chunk * m * gsz * 8));
+    }
+    chunk = std::min<uint64_t>(chunk, max_keys);
+    uint64_t *ks = (uint64_t *)c->ws_ggsw.p;
+    for (uint64_t j0 = 0; j0 < n_keys; j0 += chunk) {
+        const uint64_t kc = std::min<uint64_t>(chunk, n_keys - j0);
+        TRY(launch_pfpks(c, in + j0 * m * c->big1, kc * m, ks, gsz, (int)c->k));
+        uint64_t *o = out + j0 * glwes * gsz;
+        StageScope sc(c, FHEAES_STAGE_LINEAR, kc * m);
+        HIP_TRY(c, hipMemsetAsync(o, 0, kc * glwes * gsz * 8, c->stream));
+        for (uint64_t j = 0; j < kc; ++j)
+            hipLaunchKernelGGL(pack_fold_kernel, dim3(FHE_N / PACK_FOLD_ROWS, c->k1, (unsigned)glwes), dim3(256), 0, c->stream, ks + j * m * gsz, m, c->k1,
+                               o + j * glwes * gsz);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return FHEAES_OK;
+}
+
+// fheaes_unpack_round_keys on device pointers: in [n_keys][ceil(m/N)][(k+1)N] -> out [n_keys][m][kN+1], unpack_dev key by key (m <= MAX_CHUNK_BITS)
+int unpack_keys_dev(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t n_keys, uint64_t *out)
+{
+    const uint64_t key_words = (m + FHE_N - 1) / FHE_N * c->k1 * FHE_N;
+    for (uint64_t j = 0; j < n_keys; ++j) TRY(unpack_dev(c, in + j * key_words, m, out + j * m * c->big1));
     return FHEAES_OK;
 }
 

@@ -313,6 +313,105 @@ __global__ __launch_bounds__(256) void sample_extract_kernel(const uint64_t *pac
     }
 }
 
+// ---- packed round keys (fheaes_pack_round_keys, fheaes_aes_*_keyed_packed) ---------------------------------------------------------
+// A store holds key j as G = ceil((Nr+1) 128 / N) GLWEs at j * key_words words, key_words = G (k+1) N: fheaes_pack_bits of the key's round
+// keys flattened, so bit t = round * 128 + byte * 8 + bit sits in GLWE t / N, coefficient t % N.  The four kernels below are
+// add_bcast_kernel, gather_add_kernel, public_round1_kernel and gather_add_indexed_kernel with the round-key word read from that form:
+// word w of the LWE of bit t is sample_extract_kernel's word, taken at the moment AddRoundKey needs it.  Consecutive lanes take
+// consecutive w, so the state and WoPBS-output streams stay forward; the key read alone runs backwards through one polynomial (a wave
+// reads one contiguous run, two where it wraps).  All offsets in 64 bits: key 65,535 of an AES-128 store at k = 4 starts at byte 4,026,470,400 (past 2^31; AES-192 / 256 stores pass 2^32).
+
+// word w (< kN + 1) of the LWE ciphertext of bit t of the key whose G GLWEs start at `key`
+__device__ __forceinline__ uint64_t packed_key_word(const uint64_t *key, uint32_t t, uint32_t w, uint32_t k)
+{
+    const uint32_t big = k * PACK_N, i = t & (PACK_N - 1);
+    const uint64_t *glwe = key + (uint64_t)(t / PACK_N) * (k + 1) * PACK_N;
+    if (w == big) return glwe[(uint64_t)big + i];
+    const uint32_t c = w & (PACK_N - 1);
+    const uint64_t v = glwe[(w - c) + ((i - c) & (PACK_N - 1))];
+    return c <= i ? v : (uint64_t)0 - v;
+}
+
+// add_bcast_kernel from a packed store: dst[blk][i] += word i % (kN+1) of bit bit0 + i / (kN+1) of key key_of_block[blk]; words_per_block = 128 (kN+1)
+__global__ __launch_bounds__(256) void add_bcast_packed_kernel(uint64_t *dst, const uint64_t *store, const uint32_t *key_of_block, uint64_t key_words,
+                                                               uint32_t bit0, uint32_t k, uint64_t words_per_block, uint64_t n_blocks)
+{
+    const uint32_t lwe_words = k * PACK_N + 1;
+    for (uint64_t blk = blockIdx.y; blk < n_blocks; blk += gridDim.y) {
+        const uint64_t *key = store + (key_of_block ? key_of_block[blk] * key_words : 0);
+        uint64_t *db = dst + blk * words_per_block;
+        for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words_per_block; i += (uint64_t)gridDim.x * blockDim.x) {
+            const uint32_t bit = (uint32_t)(i / lwe_words);
+            db[i] += packed_key_word(key, bit0 + bit, (uint32_t)(i - (uint64_t)bit * lwe_words), k);
+        }
+    }
+}
+
+// gather_add_kernel with the round key (never null here) read from a packed store; bit0 = round * 128; byte_words = 8 (kN+1)
+__global__ __launch_bounds__(256) void gather_add_packed_kernel(const uint64_t *src, uint32_t n_luts, const uint64_t *store, const uint32_t *key_of_block,
+                                                                uint64_t key_words, uint32_t bit0, uint32_t k, uint64_t *out, uint64_t n_blocks,
+                                                                uint32_t byte_words, const GatherTable tab)
+{
+    const uint64_t blk = blockIdx.z;
+    const uint32_t byte = blockIdx.y, lwe_words = k * PACK_N + 1;
+    const uint64_t *sb = src + blk * 16 * (uint64_t)n_luts * byte_words;
+    const uint64_t *key = store + (key_of_block ? key_of_block[blk] * key_words : 0);
+    uint64_t *ob = out + (blk * 16 + byte) * (uint64_t)byte_words;
+    for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
+        const uint32_t bit = w / lwe_words;
+        uint64_t v = packed_key_word(key, bit0 + byte * 8 + bit, w - bit * lwe_words, k);
+        for (int t = 0; t < tab.terms; ++t)
+            v += sb[((uint64_t)tab.src[byte][t] * n_luts + tab.lut[byte][t]) * byte_words + w];
+        ob[w] = v;
+    }
+}
+
+// public_round1_kernel from a packed store (round 0: bits 0..127 of each key)
+__global__ __launch_bounds__(256) void public_round1_packed_kernel(const uint32_t *head, const uint64_t *store, uint64_t key_words, uint32_t k, uint64_t *out,
+                                                                   uint64_t n_pool)
+{
+    const uint32_t lwe_words = k * PACK_N + 1, byte_words = 8 * lwe_words;
+    for (uint64_t u = blockIdx.y; u < n_pool; u += gridDim.y) {
+        const uint32_t h = head[u], pos = h & 15u, clear = (h >> 8) & 0xFFu;
+        const uint64_t *key = store + (h >> 16) * key_words;
+        uint64_t *ob = out + u * byte_words;
+        for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
+            const uint32_t bit = w / lwe_words, x = w - bit * lwe_words;
+            uint64_t v = packed_key_word(key, pos * 8 + bit, x, k);
+            if (x == lwe_words - 1) v += (uint64_t)((clear >> bit) & 1u) << 63;
+            ob[w] = v;
+        }
+    }
+}
+
+// gather_add_indexed_kernel from a packed store; bit0 = round * 128
+__global__ __launch_bounds__(256) void gather_add_indexed_packed_kernel(const uint64_t *pool, uint32_t n_luts, const uint32_t *head, const uint32_t *term,
+                                                                        uint32_t terms, const uint64_t *store, uint64_t key_words, uint32_t bit0, uint32_t k,
+                                                                        uint64_t *out, uint64_t n_out)
+{
+    const uint32_t lwe_words = k * PACK_N + 1, byte_words = 8 * lwe_words;
+    for (uint64_t u = blockIdx.y; u < n_out; u += gridDim.y) {
+        const uint32_t h = head[u], pos = h & 15u, clear = (h >> 8) & 0xFFu;
+        const uint64_t *key = store + (h >> 16) * key_words;
+        const uint64_t *s[4];                                    // terms <= 4; fully unrolled so that the pointers stay in registers
+#pragma unroll
+        for (uint32_t t = 0; t < 4; ++t) {
+            const uint32_t e = t < terms ? term[u * terms + t] : 0u;
+            s[t] = pool + ((uint64_t)(e >> 2) * n_luts + (e & 3u)) * byte_words;
+        }
+        uint64_t *ob = out + u * byte_words;
+        for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
+            const uint32_t bit = w / lwe_words, x = w - bit * lwe_words;
+            uint64_t v = packed_key_word(key, bit0 + pos * 8 + bit, x, k);
+#pragma unroll
+            for (uint32_t t = 0; t < 4; ++t)
+                if (t < terms) v += s[t][w];
+            if (x == lwe_words - 1) v += (uint64_t)((clear >> bit) & 1u) << 63;
+            ob[w] = v;
+        }
+    }
+}
+
 // ---- wire formats (include/fheaes.h): seeded input ciphertexts, modulus-switched packed outputs --------------------------------------
 // fheaes_expand_lwe_seeded: lwe[t] = [ mask words of ciphertext first + t | bodies[t] ], mask word j = 64-bit word j % 8 of ChaCha20
 // block j / 8 under (key, nonce = (EXPAND_LWE_TAG, q low 32, q high 32)), q = first + t: expand_masks_kernel's stream for the shape

@@ -6,7 +6,9 @@ Same names, argument meaning and error behaviour as
   and AES-256, which the reference does not have: the same methods read the key size from the leading axis of the key / round keys;
   plus aes_encrypt_public / aes_ctr: public blocks and SP 800-38A CTR with a PUBLIC nonce, every distinct S-Box input evaluated once;
   plus the *_many / *_keyed / aes_ctr_streams methods: many AES keys under one FHE key, round keys [n_keys][Nr+1][16][8][kN+1] and a key
-  index per block, word for word the single-key methods key by key)
+  index per block, word for word the single-key methods key by key; plus packed round keys: pack_round_keys / unpack_round_keys /
+  aes_key_expansion_packed, and a PackedRoundKeys -- 3 / 4 / 4 GLWEs per key -- wherever a method takes round keys, the key words read
+  from it inside the linear layers, word for word the same method on the unpacked store)
   /root/reference/src/server/sbox/sbox.rs     sbox, many_sbox, mul2 .. mul14
   /root/reference/src/server/sbox/many_wopbs.rs  many_wopbs_without_padding
   /root/reference/src/server/sbox/gen_lut.rs  gen_lut
@@ -24,7 +26,7 @@ import numpy as np
 
 from . import _native
 from .aes_clear import INV_SBOX, SBOX, mul2, mul3, mul9, mul11, mul13, mul14  # noqa: F401  (re-exported like sbox.rs)
-from .client import SeededCiphertexts, ServerKeys, packed_mod_words
+from .client import PackedRoundKeys, SeededCiphertexts, ServerKeys, packed_key_glwes, packed_mod_words
 from .params import WopbsParameters
 
 
@@ -88,6 +90,11 @@ def _many_key_bits(arr, what):
     if arr.ndim != 5 or int(arr.shape[0]) < 1:
         raise ValueError("%s of many keys must be [n_keys][11 | 13 | 15][16][8][kN+1] with n_keys >= 1, got shape %s" % (what, tuple(arr.shape)))
     return _key_bits(arr[0], ROUND_KEYS_TO_BITS, what), int(arr.shape[0])
+
+
+def _words(round_keys):
+    """the array behind round keys in either form: what says which memory space a call works in"""
+    return round_keys.data if isinstance(round_keys, PackedRoundKeys) else round_keys
 
 
 def ctr_stream_blocks(streams):
@@ -172,15 +179,19 @@ class Server:
 
     def aes_encrypt(self, encrypted_round_keys, state):
         """server.rs:39, in place.  state [16][8][kN+1] or a batch [B][16][8][kN+1]; 11 / 13 / 15 round keys: AES-128 / 192 / 256."""
-        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
+        if isinstance(encrypted_round_keys, PackedRoundKeys):
+            return self._one_packed(self.engine.aes_encrypt_keyed_packed, encrypted_round_keys, state, n_blocks)
+        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         self.engine.aes_encrypt_bits(encrypted_round_keys, bits, state, n_blocks)
         return state
 
     def aes_decrypt(self, encrypted_round_keys, state):
         """server.rs:67, in place; 11 / 13 / 15 round keys: AES-128 / 192 / 256."""
-        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
+        if isinstance(encrypted_round_keys, PackedRoundKeys):
+            return self._one_packed(self.engine.aes_decrypt_keyed_packed, encrypted_round_keys, state, n_blocks)
+        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         self.engine.aes_decrypt_bits(encrypted_round_keys, bits, state, n_blocks)
         return state
 
@@ -196,9 +207,24 @@ class Server:
     def aes_decrypt_equivalent(self, dec_round_keys, state):
         """the equivalent inverse cipher, in place: one WoPBS per round (Nr per block, as aes_encrypt) instead of aes_decrypt's two
         (server.rs:67-105, :86-89).  Same plaintext as aes_decrypt, other ciphertext words.  state [16][8][kN+1] or [B][16][8][kN+1]."""
-        bits = _key_bits(dec_round_keys, ROUND_KEYS_TO_BITS, "decryption round keys")
         n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
+        if isinstance(dec_round_keys, PackedRoundKeys):
+            return self._one_packed(self.engine.aes_decrypt_equivalent_keyed_packed, dec_round_keys, state, n_blocks)
+        bits = _key_bits(dec_round_keys, ROUND_KEYS_TO_BITS, "decryption round keys")
         self.engine.aes_decrypt_equivalent_bits(dec_round_keys, bits, state, n_blocks)
+        return state
+
+    def _check_packed(self, prk: PackedRoundKeys, one_key: bool = False) -> PackedRoundKeys:
+        if prk.params != self.params:
+            raise ValueError("these round keys were packed for %s, the server runs %s" % (prk.params.name, self.params.name))
+        if one_key and prk.n_keys != 1:
+            raise ValueError("a single-key method takes a store of one key (prk[i]); this one holds %d" % prk.n_keys)
+        return prk
+
+    def _one_packed(self, call, prk: PackedRoundKeys, state, n_blocks: int):
+        """a single-key cipher call from a one-key store: the keyed-packed entry point with every block under key 0"""
+        self._check_packed(prk, one_key=True)
+        call(prk.data, prk.key_bits, 1, [0] * n_blocks, state, n_blocks)
         return state
 
     def add_scalar(self, state, i):
@@ -214,8 +240,11 @@ class Server:
         """aes_encrypt of PUBLIC blocks (ints, or 16 `bytes` each) under encrypted round keys: a new [n][16][8][kN+1] (or `out`), in the memory
         space of the round keys, word for word aes_encrypt(round keys, Client.trivial_bytes(blocks)); every distinct S-Box input of
         the batch is evaluated once (include/fheaes.h: fheaes_aes_encrypt_public_bits)."""
-        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         blocks = list(blocks)
+        if isinstance(encrypted_round_keys, PackedRoundKeys):
+            self._check_packed(encrypted_round_keys, one_key=True)
+            return self.aes_encrypt_public_keyed(encrypted_round_keys, [0] * len(blocks), blocks, out=out)
+        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         out = self._public_out(encrypted_round_keys, len(blocks), out)
         self.engine.aes_encrypt_public_bits(encrypted_round_keys, bits, blocks, out)
         return out
@@ -223,6 +252,9 @@ class Server:
     def aes_ctr(self, encrypted_round_keys, iv, first_block: int, n_blocks: int, data=None, out=None):
         """SP 800-38A CTR with a PUBLIC nonce: block i = E_K((iv + first_block + i) mod 2^128) ^ data[i] as a new [n_blocks][16][8][kN+1]
         (data None: the keystream).  `iv`: an int or 16 bytes; `data`: n_blocks ints / 16-byte blocks, or one `bytes` of 16 n_blocks."""
+        if isinstance(encrypted_round_keys, PackedRoundKeys):
+            self._check_packed(encrypted_round_keys, one_key=True)
+            return self.aes_ctr_streams(encrypted_round_keys, [(0, iv, first_block, n_blocks, data)], out=out)
         bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         n_blocks, first_block = int(n_blocks), int(first_block)
         if n_blocks < 0 or first_block < 0:
@@ -265,8 +297,12 @@ class Server:
         self.engine.aes_decryption_round_keys_batch(round_keys, bits, n_keys, dw)
         return dw
 
-    def _keyed(self, call, round_keys, key_of_block, state):
-        bits, n_keys = _many_key_bits(round_keys, "round keys")
+    def _keyed(self, call, round_keys, key_of_block, state, packed_call=None):
+        if isinstance(round_keys, PackedRoundKeys):
+            prk = self._check_packed(round_keys)
+            call, round_keys, bits, n_keys = packed_call, prk.data, prk.key_bits, prk.n_keys
+        else:
+            bits, n_keys = _many_key_bits(round_keys, "round keys")
         if state.ndim != 4:
             raise ValueError("a keyed call works on a batch [n_blocks][16][8][kN+1]; wrap a single state as state[None]")
         call(round_keys, bits, n_keys, list(key_of_block), state, int(state.shape[0]))
@@ -275,21 +311,26 @@ class Server:
     def aes_encrypt_keyed(self, round_keys, key_of_block, state):
         """aes_encrypt with a key per block, in place: block b of state [n_blocks][16][8][kN+1] under round_keys[key_of_block[b]], the words
         aes_encrypt(round_keys[key_of_block[b]], ...) writes for it; every round is one WoPBS over all blocks."""
-        return self._keyed(self.engine.aes_encrypt_keyed, round_keys, key_of_block, state)
+        return self._keyed(self.engine.aes_encrypt_keyed, round_keys, key_of_block, state, self.engine.aes_encrypt_keyed_packed)
 
     def aes_decrypt_keyed(self, round_keys, key_of_block, state):
         """aes_decrypt with a key per block, in place."""
-        return self._keyed(self.engine.aes_decrypt_keyed, round_keys, key_of_block, state)
+        return self._keyed(self.engine.aes_decrypt_keyed, round_keys, key_of_block, state, self.engine.aes_decrypt_keyed_packed)
 
     def aes_decrypt_equivalent_keyed(self, dec_round_keys, key_of_block, state):
         """aes_decrypt_equivalent with a key per block, in place; dec_round_keys from aes_decryption_round_keys_many."""
-        return self._keyed(self.engine.aes_decrypt_equivalent_keyed, dec_round_keys, key_of_block, state)
+        return self._keyed(self.engine.aes_decrypt_equivalent_keyed, dec_round_keys, key_of_block, state, self.engine.aes_decrypt_equivalent_keyed_packed)
 
     def aes_encrypt_public_keyed(self, round_keys, key_of_block, blocks, data=None, out=None):
         """aes_encrypt_public with a key per block (and, as aes_ctr, clear `data` blocks folded into the last layer): a new
         [n][16][8][kN+1] (or `out`).  Equal S-Box inputs under the same key are evaluated once, equal blocks under different keys are not shared."""
-        bits, n_keys = _many_key_bits(round_keys, "round keys")
         blocks = list(blocks)
+        if isinstance(round_keys, PackedRoundKeys):
+            prk = self._check_packed(round_keys)
+            out = self._public_out(prk.data, len(blocks), out)
+            self.engine.aes_public_keyed(prk.data, prk.key_bits, prk.n_keys, list(key_of_block), blocks, _data_blocks(data, len(blocks)), out, packed=True)
+            return out
+        bits, n_keys = _many_key_bits(round_keys, "round keys")
         out = self._public_out(round_keys, len(blocks), out)
         self.engine.aes_public_keyed(round_keys, bits, n_keys, list(key_of_block), blocks, _data_blocks(data, len(blocks)), out)
         return out
@@ -303,6 +344,50 @@ class Server:
 
     def _public_out(self, round_keys, n_blocks: int, out):
         return self._many_out(round_keys, (n_blocks, 16, 8, self.params.big1), out)
+
+    # ---- packed round keys -------------------------------------------------------
+    def pack_round_keys(self, round_keys, out=None) -> PackedRoundKeys:
+        """round keys [Nr+1][16][8][kN+1] or [n_keys][Nr+1][16][8][kN+1] (encryption or decryption round keys) -> a PackedRoundKeys in the
+        same memory space: key i is pack(round_keys[i]) word for word, G = 3 / 4 / 4 GLWEs (fheaes_pack_round_keys).  `out`: where the
+        [n_keys][G][(k+1)N] words go (e.g. a slice of a larger store)."""
+        if round_keys.ndim == 4:
+            round_keys = round_keys[None]
+        bits, n_keys = _many_key_bits(round_keys, "round keys")
+        p = self.params
+        data = self._many_out(round_keys, (n_keys, packed_key_glwes(p, bits), (p.k + 1) * p.N), out)
+        self.engine.pack_round_keys(round_keys, bits, n_keys, data)
+        return PackedRoundKeys(p, bits, data)
+
+    def unpack_round_keys(self, prk: PackedRoundKeys, first: int = 0, count: int | None = None, out=None):
+        """keys first .. first + count of a store back in the LWE form [count][Nr+1][16][8][kN+1] (count None: to the end), slice j word for
+        word unpack(prk[first + j]): for migration and for tests; needs no keys (fheaes_unpack_round_keys)."""
+        self._check_packed(prk)
+        first = int(first)
+        count = prk.n_keys - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > prk.n_keys:
+            raise ValueError("keys %d .. %d of a store of %d" % (first, first + count, prk.n_keys))
+        rk = self._many_out(prk.data, (count, prk.key_bits // 32 + 7, 16, 8, self.params.big1), out)
+        self.engine.unpack_round_keys(prk.data, prk.key_bits, first, count, rk)
+        return rk
+
+    def aes_key_expansion_packed(self, keys, chunk: int = 256) -> PackedRoundKeys:
+        """aes_key_expansion_many followed by pack_round_keys, `chunk` keys at a time: the LWE form of more than `chunk` keys never exists
+        at once (23 MB a key at PARAM_OPT against 61 KB packed).  keys [n_keys][16 | 24 | 32][8][kN+1] -> a PackedRoundKeys of n_keys."""
+        if keys.ndim != 4 or int(keys.shape[0]) < 1:
+            raise ValueError("keys must be [n_keys][16 | 24 | 32][8][kN+1] with n_keys >= 1, got shape %s" % (tuple(keys.shape),))
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be at least one key")
+        bits = _key_bits(keys[0], KEY_BYTES_TO_BITS, "key", ndim=3)
+        p, n_keys = self.params, int(keys.shape[0])
+        data = _empty_like(keys, (n_keys, packed_key_glwes(p, bits), (p.k + 1) * p.N))
+        for lo in range(0, n_keys, chunk):
+            rk = self.aes_key_expansion_many(keys[lo:lo + chunk])
+            self.pack_round_keys(rk, out=data[lo:lo + chunk])
+            if not isinstance(rk, np.ndarray):
+                self.engine.synchronize()             # the chunk's LWE form is freed here: its readers must be done first
+            del rk
+        return PackedRoundKeys(p, bits, data)
 
     # ---- packed ciphertexts ------------------------------------------------------
     def pack(self, ct, out=None, width: int = 64):
@@ -456,7 +541,7 @@ class ServerGroup:
 
     def _fan_out_new(self, round_keys, n, fn):
         """the public-input calls produce a NEW [n][16][8][kN+1]: allocate it next to the round keys, let every context fill its shard"""
-        out = _empty_like(round_keys, (n, 16, 8, self.params.big1))
+        out = _empty_like(_words(round_keys), (n, 16, 8, self.params.big1))
         return self._fan_out(lambda s, shard, lo: fn(s, shard, lo, int(shard.shape[0])), out)
 
     def aes_encrypt_public(self, round_keys, blocks):
@@ -520,6 +605,24 @@ class ServerGroup:
     def aes_ctr_streams(self, round_keys, streams):
         key_of_block, blocks, data = ctr_stream_blocks(streams)
         return self.aes_encrypt_public_keyed(round_keys, key_of_block, blocks, data=data)
+
+    # packed round keys: a store is small, so every context reads the whole of it (as the keyed calls read all round keys); the cipher
+    # methods above take a PackedRoundKeys wherever they take round keys, since every context's Server does
+    def pack_round_keys(self, round_keys) -> PackedRoundKeys:
+        """packed on context 0; finished before returning, since a resident store is then read from the other contexts' streams"""
+        prk = self.servers[0].pack_round_keys(round_keys)
+        self.servers[0].synchronize()
+        return prk
+
+    def unpack_round_keys(self, prk: PackedRoundKeys, first: int = 0, count: int | None = None):
+        rk = self.servers[0].unpack_round_keys(prk, first, count)
+        self.servers[0].synchronize()
+        return rk
+
+    def aes_key_expansion_packed(self, keys, chunk: int = 256) -> PackedRoundKeys:
+        prk = self.servers[0].aes_key_expansion_packed(keys, chunk)
+        self.servers[0].synchronize()
+        return prk
 
     def _glwe_shards(self, n_glwes: int):
         from .dist import shard_blocks
