@@ -326,27 +326,16 @@ static void public_plan(const uint64_t *blocks, const uint64_t *data, const uint
 static_assert(FHEAES_MAX_KEYS == PUBLIC_MAX_KEYS, "fheaes.h's bound on n_keys is the key field of PUBLIC_HEAD");
 #define PUBLIC_MAX_BLOCKS (1ull << 26)      /* 16 n pool entries x 4 must fit a PUBLIC_TERM word */
 
-static int launch_public_round1(fheaes_ctx *c, const uint32_t *head, const KeySets &rk0, uint64_t *out, uint64_t n_pool)
-{
-    TRY(noise_guard(c, 1, "the initial AddRoundKey on public bytes"));          // a trivial ciphertext carries no noise
-    StageScope sc(c, FHEAES_STAGE_LINEAR, (n_pool + 15) / 16);
-    dim3 grid((8 * c->big1 + 1023) / 1024, (unsigned)std::min<uint64_t>(n_pool, 65535));
-    if (rk0.packed_glwes) hipLaunchKernelGGL(public_round1_packed_kernel, grid, dim3(256), 0, c->stream, head, rk0.rk, rk0.stride, c->k, out, n_pool);
-    else hipLaunchKernelGGL(public_round1_kernel, grid, dim3(256), 0, c->stream, head, rk0.rk, rk0.stride, out, n_pool, c->big1);
-    HIP_TRY(c, hipGetLastError());
-    return FHEAES_OK;
-}
-
+// terms == 0 (the pool of round 1): pool and term are not read, and the layer declares level 1 -- a trivial ciphertext carries no noise
 static int launch_gather_indexed(fheaes_ctx *c, const uint64_t *pool, uint32_t n_luts, const uint32_t *head, const uint32_t *term, uint32_t terms,
                                  const KeySets &rk, uint64_t *out, uint64_t n_out)
 {
-    TRY(noise_guard(c, terms + 1u, "the indexed linear layer (MixColumns / ShiftRows + AddRoundKey over a pool)"));
+    TRY(noise_guard(c, terms + 1u, terms ? "the indexed linear layer (MixColumns / ShiftRows + AddRoundKey over a pool)" : "the initial AddRoundKey on public bytes"));
     StageScope sc(c, FHEAES_STAGE_LINEAR, (n_out + 15) / 16);
     dim3 grid((8 * c->big1 + 1023) / 1024, (unsigned)std::min<uint64_t>(n_out, 65535));
-    if (rk.packed_glwes)
-        hipLaunchKernelGGL(gather_add_indexed_packed_kernel, grid, dim3(256), 0, c->stream, pool, n_luts, head, term, terms, rk.rk, rk.stride, rk.bit0, c->k, out, n_out);
-    else
-        hipLaunchKernelGGL(gather_add_indexed_kernel, grid, dim3(256), 0, c->stream, pool, n_luts, head, term, terms, rk.rk, rk.stride, out, n_out, c->big1);
+    with_keys(c, rk, [&](auto keys) {
+        hipLaunchKernelGGL(gather_add_indexed_kernel<decltype(keys)>, grid, dim3(256), 0, c->stream, pool, n_luts, head, term, terms, keys, out, n_out, c->big1);
+    });
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
@@ -362,10 +351,9 @@ static int aes_public_dev(fheaes_ctx *c, const KeySets &rk, const PublicPlan &pl
     const uint32_t *tab = (const uint32_t *)c->ws_misc.p;
     TRY(ensure(c, c->ws_vp, pl.max_vp_bytes_per_bw * bw * 8));               // the largest pool, not 16 n
     uint64_t *vp = (uint64_t *)c->ws_vp.p;
-    TRY(launch_public_round1(c, tab + pl.layers[0].head, rk.round(0, sw), out, pl.layers[0].n));
-    for (int round = 1; round <= nr; ++round) {
-        const PublicPlan::Layer &in = pl.layers[round - 1], &to = pl.layers[round];
-        TRY(many_sbox_dev(c, out, in.n, round < nr ? LUTSET_ENC_ROUND : LUTSET_SBOX, vp));
+    for (int round = 0; round <= nr; ++round) {                              // layer 0 is the pool of round 1: nothing to evaluate before it
+        const PublicPlan::Layer &to = pl.layers[round];
+        if (round > 0) TRY(many_sbox_dev(c, out, pl.layers[round - 1].n, round < nr ? LUTSET_ENC_ROUND : LUTSET_SBOX, vp));
         TRY(launch_gather_indexed(c, vp, round < nr ? 3 : 1, tab + to.head, tab + to.term, to.terms, rk.round((uint64_t)round, sw), out, to.n));
     }
     return FHEAES_OK;

@@ -652,6 +652,15 @@ static uint32_t packed_key_glwes(uint32_t key_bits)
     return nr ? (uint32_t)(((uint64_t)(nr + 1) * AES_BLOCK_BITS + FHE_N - 1) / FHE_N) : 0;
 }
 
+// The geometry of a cipher call's keys: words from one key to the next, in LWE form [Nr+1][16][8][kN+1] or in a packed store
+// [G][(k+1)N], and G (0: LWE form) -- KeySets' stride and packed_glwes
+struct KeyStore { uint64_t key_words; uint32_t glwes; };
+static KeyStore key_store(const fheaes_ctx *c, uint32_t key_bits, bool packed)
+{
+    if (packed) return {(uint64_t)packed_key_glwes(key_bits) * c->k1 * FHE_N, packed_key_glwes(key_bits)};
+    return {(uint64_t)(aes_rounds(key_bits) + 1) * 16 * 8 * c->big1, 0};
+}
+
 // The three block ciphers.  key_of_block null: the single-key entry points (one set of round keys, no table); else block b runs under
 // round_keys[key_of_block[b]] of [n_keys][Nr+1][16][8][kN+1], the table going to the device through the pinned buffer (one key: no table either).
 // packed: round_keys is a packed store [n_keys][G][(k+1)N] (fheaes_pack_round_keys) and the linear layers read the key words from it.
@@ -662,24 +671,24 @@ static int aes_crypt(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bit
     if (!round_keys || !state) return c->fail(FHEAES_ERR_INVALID, "null pointer");
     TRY(check_key_bits(c, key_bits));
     const int nr = aes_rounds(key_bits);
-    const uint32_t glwes = packed ? packed_key_glwes(key_bits) : 0;
-    const uint64_t sw = 16ull * 8 * c->big1, ks = packed ? (uint64_t)glwes * c->k1 * FHE_N : (uint64_t)(nr + 1) * sw;
+    const KeyStore ks = key_store(c, key_bits, packed);
+    const uint64_t sw = 16ull * 8 * c->big1, keys_bytes = n_keys * ks.key_words * 8;
     if (key_of_block) {
         TRY(check_n_keys(c, n_keys));
         TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
         if (n_blocks == 0) return FHEAES_OK;
     }
-    if (packed && overlap(round_keys, n_keys * ks * 8, state, n_blocks * sw * 8)) return c->fail(FHEAES_ERR_INVALID, "the packed round keys and the state overlap");
+    if (packed && overlap(round_keys, keys_bytes, state, n_blocks * sw * 8)) return c->fail(FHEAES_ERR_INVALID, "the packed round keys and the state overlap");
     HIP_TRY(c, hipSetDevice(c->device));
     Staged s(c, memspace);
-    TRY(s.in(round_keys, n_keys * ks * 8, &round_keys));
+    TRY(s.in(round_keys, keys_bytes, &round_keys));
     TRY(s.inout(state, n_blocks * sw * 8, &state));
     const uint32_t *table = nullptr;
     if (key_of_block && n_keys > 1) {
         TRY(upload_pinned(c, n_blocks * sizeof(uint32_t), n_blocks * sizeof(uint32_t), [&](uint8_t *pin) { memcpy(pin, key_of_block, n_blocks * sizeof(uint32_t)); }));
         table = (const uint32_t *)c->ws_misc.p;
     }
-    TRY(dev(c, KeySets{round_keys, table, ks, glwes}, state, n_blocks, nr));
+    TRY(dev(c, KeySets{round_keys, table, ks.key_words, ks.glwes}, state, n_blocks, nr));
     return s.finish();
 }
 
@@ -850,17 +859,17 @@ static int aes_public(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bi
                       const uint64_t *data, uint64_t n_blocks, uint64_t *state_out, int memspace, bool packed = false)
 {
     const int nr = aes_rounds(key_bits);
-    const uint32_t glwes = packed ? packed_key_glwes(key_bits) : 0;
-    const uint64_t sw = 16ull * 8 * c->big1, ks = packed ? (uint64_t)glwes * c->k1 * FHE_N : (uint64_t)(nr + 1) * sw;
-    if (packed && overlap(round_keys, n_keys * ks * 8, state_out, n_blocks * sw * 8)) return c->fail(FHEAES_ERR_INVALID, "the packed round keys and state_out overlap");
+    const KeyStore ks = key_store(c, key_bits, packed);
+    const uint64_t sw = 16ull * 8 * c->big1, keys_bytes = n_keys * ks.key_words * 8;
+    if (packed && overlap(round_keys, keys_bytes, state_out, n_blocks * sw * 8)) return c->fail(FHEAES_ERR_INVALID, "the packed round keys and state_out overlap");
     if (n_blocks > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %llu", (unsigned long long)PUBLIC_MAX_BLOCKS);
     HIP_TRY(c, hipSetDevice(c->device));
     PublicPlan pl;
     public_plan(blocks, data, key_of_block, n_blocks, nr, pl);
     Staged s(c, memspace);
-    TRY(s.in(round_keys, n_keys * ks * 8, &round_keys));
+    TRY(s.in(round_keys, keys_bytes, &round_keys));
     TRY(s.out(state_out, n_blocks * sw * 8, &state_out));
-    TRY(aes_public_dev(c, KeySets{round_keys, nullptr, ks, glwes}, pl, nr, state_out));
+    TRY(aes_public_dev(c, KeySets{round_keys, nullptr, ks.key_words, ks.glwes}, pl, nr, state_out));
     return s.finish();
 }
 

@@ -369,7 +369,8 @@ int noise_guard(fheaes_ctx *c, uint32_t level, const char *what)
 // The AES keys of a call: `rk` holds n sets of round keys `stride` words apart (slice i of [n_keys][Nr+1][16][8][kN+1]) and block b works
 // under set of_block[b] (a device table).  of_block null: one set for every block -- the single-key entry points, which upload no table.
 // packed_glwes = G > 0: `rk` is a packed store instead (fheaes_pack_round_keys: key i = G GLWEs at i * stride words, stride = G (k+1) N) and
-// `bit0` the first bit of the round in question; the launchers then take the packed-key kernels, which read the same words from there.
+// `bit0` the first bit of the round in question.  with_keys() is the one place that turns either form into the source type of the K6
+// kernels (kern_linear.h: LweKeys, PackedKeys), which read the same words from there; rk null (no round key) is an LweKeys without a base.
 struct KeySets {
     const uint64_t *rk;
     const uint32_t *of_block;
@@ -384,17 +385,23 @@ struct KeySets {
     }
 };
 
+// f(source): the round-key source of `k` for a K6 kernel template
+template <class F>
+static void with_keys(const fheaes_ctx *c, const KeySets &k, F &&f)
+{
+    if (k.packed_glwes) f(PackedKeys{k.rk, k.stride, k.bit0, c->k});
+    else f(LweKeys{k.rk, k.stride});
+}
+
 int launch_gather(fheaes_ctx *c, const uint64_t *src, uint32_t n_luts, const KeySets &k, uint64_t *out, uint64_t n_blocks, const GatherTable &t)
 {
     if (n_blocks == 0) return FHEAES_OK;
     TRY(noise_guard(c, (uint32_t)t.terms + (k.rk ? 1u : 0u), "the linear layer (MixColumns / ShiftRows + AddRoundKey)"));
     StageScope sc(c, FHEAES_STAGE_LINEAR, n_blocks);
-    const uint32_t bw = 8 * c->big1;
-    dim3 grid((bw + 1023) / 1024, 16, (unsigned)n_blocks);
-    if (k.rk && k.packed_glwes)
-        hipLaunchKernelGGL(gather_add_packed_kernel, grid, dim3(256), 0, c->stream, src, n_luts, k.rk, k.of_block, k.stride, k.bit0, c->k, out, n_blocks, bw, t);
-    else
-        hipLaunchKernelGGL(gather_add_kernel, grid, dim3(256), 0, c->stream, src, n_luts, k.rk, k.of_block, k.stride, out, n_blocks, bw, t);
+    dim3 grid((8 * c->big1 + 1023) / 1024, 16, (unsigned)n_blocks);
+    with_keys(c, k, [&](auto keys) {
+        hipLaunchKernelGGL(gather_add_kernel<decltype(keys)>, grid, dim3(256), 0, c->stream, src, n_luts, keys, k.of_block, out, n_blocks, c->big1, t);
+    });
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
@@ -406,10 +413,9 @@ int launch_add_bcast(fheaes_ctx *c, uint64_t *dst, const KeySets &k, uint64_t wo
     StageScope sc(c, FHEAES_STAGE_LINEAR, n_blocks);
     const unsigned gx = (unsigned)std::min<uint64_t>((words_per_block + 255) / 256, 64);
     dim3 grid(gx, (unsigned)std::min<uint64_t>(n_blocks, std::max<uint64_t>(1, 16384 / gx)));
-    if (k.packed_glwes)
-        hipLaunchKernelGGL(add_bcast_packed_kernel, grid, dim3(256), 0, c->stream, dst, k.rk, k.of_block, k.stride, k.bit0, c->k, words_per_block, n_blocks);
-    else
-        hipLaunchKernelGGL(add_bcast_kernel, grid, dim3(256), 0, c->stream, dst, k.rk, k.of_block, k.stride, words_per_block, n_blocks);
+    with_keys(c, k, [&](auto keys) {
+        hipLaunchKernelGGL(add_bcast_kernel<decltype(keys)>, grid, dim3(256), 0, c->stream, dst, keys, k.of_block, words_per_block, n_blocks, c->big1);
+    });
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }

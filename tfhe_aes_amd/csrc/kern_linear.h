@@ -6,6 +6,8 @@
 //   inv_shift_rows            src/server/decrypt/inv_shift_rows.rs:5-21
 //   add_round_key             src/server/server.rs:278-282
 // All of them are one "gather-add": out[blk][byte] = sum_t src[blk][tab.src[byte][t]][tab.lut[byte][t]] (+ rk[byte]).
+// The round key comes from a source type (LweKeys, PackedKeys below): every layer that adds one is ONE kernel template over that type,
+// so round keys in LWE form and in a packed store go through the same body.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,35 +18,120 @@ struct GatherTable {
     int8_t lut[16][4];      // which LUT output of that byte
 };
 
-// src: [n_blocks][16][n_luts][byte_words]; rk: [n_keys][key_stride words] with [16][byte_words] at its front, or null;
-// key_of_block: [n_blocks] or null (every block under rk's first key); out: [n_blocks][16][byte_words]
-__global__ __launch_bounds__(256) void gather_add_kernel(const uint64_t *src, uint32_t n_luts, const uint64_t *rk, const uint32_t *key_of_block,
-                                                         uint64_t key_stride, uint64_t *out, uint64_t n_blocks, uint32_t byte_words, const GatherTable tab)
+#define PACK_N 512           /* the polynomial size N the packing kernels and the packed key stores are written for */
+
+// ---- sample extraction: the one rule ---------------------------------------------------------------------------------------------------
+// The LWE of coefficient i of a GLWE (A_0 .. A_{k-1}, B): the blind rotation's extraction of coefficient 0, for any coefficient.
+//   mask word jN + c = A_j[i - c] (c <= i), -A_j[i - c + N] (c > i); body = B[i]
+// A GLWE is read through one of two readers: g[e] is its word e < (k+1) N.
+
+// 64-bit words
+struct GlweWords {
+    const uint64_t *p;
+    __device__ __forceinline__ GlweWords glwe(uint64_t g, uint32_t k) const { return {p + g * (k + 1) * PACK_N}; }
+    __device__ __forceinline__ uint64_t operator[](uint32_t e) const { return p[e]; }
+};
+
+// field e of a switched GLWE (mod_switch_pack_kernel), read back: x' = v << (64 - w), from one or two words
+__device__ __forceinline__ uint64_t mod_field(const uint64_t *glwe, uint32_t e, uint32_t w)
+{
+    const uint32_t bit = e * w, word = bit >> 6, off = bit & 63;
+    uint64_t v = glwe[word] >> off;
+    if (off + w > 64) v |= glwe[word + 1] << (64 - off);               // the field straddles two words (off > 0 here)
+    return v << (64 - w);
+}
+
+// width-bit fields: a GLWE is (k+1) 8 width words
+struct GlweFields {
+    const uint64_t *p;
+    uint32_t width;
+    __device__ __forceinline__ GlweFields glwe(uint64_t g, uint32_t k) const { return {p + g * (k + 1) * 8 * width, width}; }
+    __device__ __forceinline__ uint64_t operator[](uint32_t e) const { return mod_field(p, e, width); }
+};
+
+// word w (<= kN) of the LWE of coefficient i (< N) of `glwe`
+template <class Glwe>
+__device__ __forceinline__ uint64_t sample_extract_word(const Glwe &glwe, uint32_t i, uint32_t w, uint32_t k)
+{
+    const uint32_t big = k * PACK_N;
+    if (w == big) return glwe[big + i];
+    const uint32_t c = w & (PACK_N - 1);
+    const uint64_t v = glwe[(w - c) + ((i - c) & (PACK_N - 1))];
+    return c <= i ? v : (uint64_t)0 - v;
+}
+
+// ---- where a linear layer reads its round key ---------------------------------------------------------------------------------------------
+// Two by-value sources with the same two members: key(j), the source at key j of a block or pool entry, and word(p, w, lwe_words), word w
+// of state byte p of that key's round key ([16][8][lwe_words]; word(0, i, ..) for i < 128 lwe_words is word i of the whole round key).
+// The kernels below are templates over the source.  All offsets in 64 bits: key 65,535 of a packed AES-128 store at k = 4 starts at
+// byte 4,026,470,400 (past 2^31; AES-192 / 256 stores pass 2^32), and sets in LWE form are 2.9 MB apart and more.
+
+// LWE form: `base` is the round in question of key 0, [16][8][lwe_words]; key j's `stride` words further.  base null: no round key
+struct LweKeys {
+    const uint64_t *base;
+    uint64_t stride;
+    __device__ __forceinline__ bool none() const { return base == nullptr; }
+    __device__ __forceinline__ LweKeys key(uint64_t j) const { return {base + j * stride, stride}; }
+    __device__ __forceinline__ uint64_t word(uint32_t p, uint32_t w, uint32_t lwe_words) const { return base[(uint64_t)p * 8 * lwe_words + w]; }
+};
+
+// A packed store (fheaes_pack_round_keys) holds key j as G = ceil((Nr+1) 128 / N) GLWEs at j * key_words words, key_words = G (k+1) N:
+// fheaes_pack_bits of the key's round keys flattened, so bit t = round * 128 + byte * 8 + bit sits in GLWE t / N, coefficient t % N, and
+// bit0 = round * 128.  Word w of the LWE of bit t is sample_extract_kernel's word, taken at the moment AddRoundKey needs it.  Consecutive
+// lanes take consecutive w, so the state and WoPBS-output streams stay forward; the key read alone runs backwards through one polynomial
+// (a wave reads one contiguous run, two where it wraps).
+struct PackedKeys {
+    const uint64_t *store;
+    uint64_t key_words;
+    uint32_t bit0, k;
+    __device__ __forceinline__ bool none() const { return false; }
+    __device__ __forceinline__ PackedKeys key(uint64_t j) const { return {store + j * key_words, key_words, bit0, k}; }
+    __device__ __forceinline__ uint64_t word(uint32_t p, uint32_t w, uint32_t lwe_words) const
+    {
+        const uint32_t bit = w / lwe_words, t = bit0 + p * 8 + bit;
+        return sample_extract_word(GlweWords{store}.glwe(t / PACK_N, k), t & (PACK_N - 1), w - bit * lwe_words, k);
+    }
+};
+
+// src: [n_blocks][16][n_luts][byte_words], byte_words = 8 lwe_words; keys: the round key to add, or none; key_of_block: [n_blocks] or null
+// (every block under the first key); out: [n_blocks][16][byte_words]
+template <class Keys>
+__global__ __launch_bounds__(256) void gather_add_kernel(const uint64_t *src, uint32_t n_luts, const Keys keys, const uint32_t *key_of_block, uint64_t *out,
+                                                         uint64_t n_blocks, uint32_t lwe_words, const GatherTable tab)
 {
     const uint64_t blk = blockIdx.z;
-    const uint32_t byte = blockIdx.y;
+    const uint32_t byte = blockIdx.y, byte_words = 8 * lwe_words;
     const uint64_t *sb = src + blk * 16 * (uint64_t)n_luts * byte_words;
-    const uint64_t *kb = rk ? rk + (key_of_block ? key_of_block[blk] * key_stride : 0) + (uint64_t)byte * byte_words : nullptr;
+    const bool keyed = !keys.none();
+    const Keys key = keys.key(keyed && key_of_block ? key_of_block[blk] : 0);
     uint64_t *ob = out + (blk * 16 + byte) * (uint64_t)byte_words;
     for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
-        uint64_t v = kb ? kb[w] : 0;
+        uint64_t v = keyed ? key.word(byte, w, lwe_words) : 0;
         for (int t = 0; t < tab.terms; ++t)
             v += sb[((uint64_t)tab.src[byte][t] * n_luts + tab.lut[byte][t]) * byte_words + w];
         ob[w] = v;
     }
 }
 
-// dst[blk][i] += rk[key_of_block[blk]][i]  (add_round_key; key_of_block null: one key set for all blocks).  dst: [n_blocks][words_per_block];
-// rk: [n_keys][key_stride words], the round key at the front of each
-__global__ __launch_bounds__(256) void add_bcast_kernel(uint64_t *dst, const uint64_t *rk, const uint32_t *key_of_block, uint64_t key_stride,
-                                                        uint64_t words_per_block, uint64_t n_blocks)
+// dst[blk][i] += word i of the round key of key_of_block[blk]  (add_round_key; key_of_block null: one key for all blocks).
+// dst: [n_blocks][words_per_block], words_per_block = 128 lwe_words
+template <class Keys>
+__global__ __launch_bounds__(256) void add_bcast_kernel(uint64_t *dst, const Keys keys, const uint32_t *key_of_block, uint64_t words_per_block,
+                                                        uint64_t n_blocks, uint32_t lwe_words)
 {
     for (uint64_t blk = blockIdx.y; blk < n_blocks; blk += gridDim.y) {
-        const uint64_t *kb = rk + (key_of_block ? key_of_block[blk] * key_stride : 0);
+        const Keys key = keys.key(key_of_block ? key_of_block[blk] : 0);
         uint64_t *db = dst + blk * words_per_block;
         for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words_per_block; i += (uint64_t)gridDim.x * blockDim.x)
-            db[i] += kb[i];
+            db[i] += key.word(0, (uint32_t)i, lwe_words);
     }
+}
+
+// v + trivial(clear) at word w of a byte's [8][lwe_words] words: bit w / lwe_words of `clear`, << 63, on the body word of that bit
+__device__ __forceinline__ uint64_t add_trivial_bit(uint64_t v, uint32_t clear, uint32_t w, uint32_t lwe_words)
+{
+    const uint32_t bit = w / lwe_words;
+    return w - bit * lwe_words == lwe_words - 1 ? v + ((uint64_t)((clear >> bit) & 1u) << 63) : v;
 }
 
 // Rows of bytes moved between strided sets, one set per AES key: the word operations of the key expansion over all keys at once (RotWord,
@@ -64,10 +151,7 @@ __global__ __launch_bounds__(256) void key_rows_kernel(uint64_t *dst, uint64_t d
         for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
             uint64_t v = ab[w];
             if (bb) v += bb[w];
-            if (clear) {
-                const uint32_t bit = w / lwe_words;
-                if (w - bit * lwe_words == lwe_words - 1) v += (uint64_t)((clear >> bit) & 1u) << 63;
-            }
+            if (clear) v = add_trivial_bit(v, clear, w, lwe_words);
             ob[w] = v;
         }
     }
@@ -81,39 +165,22 @@ __global__ __launch_bounds__(256) void key_rows_kernel(uint64_t *dst, uint64_t d
 // and one uint32 per term says what to sum: WoPBS output `lut` of pool entry `src` of the round before
 #define PUBLIC_TERM(src, lut) (((uint32_t)(src) << 2) | (uint32_t)(lut))
 
-// Pool of round 1: out[u] = rk0[key_u][p_u] + trivial(v_u), i.e. the round key's words with ((v_u >> bit) & 1) << 63 added to each body:
-// word for word the initial AddRoundKey on a trivial ciphertext (mask 0, body = bit << 63) of v_u.
-// head: [n_pool]; rk0: [n_keys][key_stride words], [16][byte_words] at the front of each; out: [n_pool][byte_words]; byte_words = 8 * lwe_words
-__global__ __launch_bounds__(256) void public_round1_kernel(const uint32_t *head, const uint64_t *rk0, uint64_t key_stride, uint64_t *out, uint64_t n_pool,
-                                                            uint32_t lwe_words)
-{
-    const uint32_t byte_words = 8 * lwe_words;
-    for (uint64_t u = blockIdx.y; u < n_pool; u += gridDim.y) {
-        const uint32_t h = head[u], pos = h & 15u, clear = (h >> 8) & 0xFFu;
-        const uint64_t *kb = rk0 + (h >> 16) * key_stride + (uint64_t)pos * byte_words;
-        uint64_t *ob = out + u * byte_words;
-        for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
-            const uint32_t bit = w / lwe_words;
-            uint64_t v = kb[w];
-            if (w - bit * lwe_words == lwe_words - 1) v += (uint64_t)((clear >> bit) & 1u) << 63;
-            ob[w] = v;
-        }
-    }
-}
-
-// The linear layer between two pools, and from the last pool into the state: gather_add_kernel with the sources of every output
-// byte read from a table in device memory instead of being the same for every block.
+// The linear layer into a pool, and from the last pool into the state: gather_add_kernel with the sources of every output byte read
+// from a table in device memory instead of being the same for every block.
 //   out[u] = sum_{j < terms} pool[src_uj][lut_uj] + rk[key_u][p_u] + trivial(clear_u)
 // pool: [n_src][n_luts][byte_words] (WoPBS outputs of the round before); head: [n_out] PUBLIC_HEAD; term: [n_out][terms] PUBLIC_TERM;
-// rk: [n_keys][key_stride words], [16][byte_words] at the front of each; out: [n_out][byte_words].  clear_u is 0 except in CTR's last layer (the data byte).  Wrapping uint64 sums: any
-// order of the terms gives gather_add_kernel's words.
+// keys: the round key of this layer; out: [n_out][byte_words], byte_words = 8 lwe_words.  Wrapping uint64 sums: any order of the terms
+// gives gather_add_kernel's words.  clear_u is 0 except in two layers.  The pool of round 1 has terms == 0 (pool and term are not read)
+// and clear_u = the public byte: out[u] = rk0[key_u][p_u] + trivial(v_u), word for word the initial AddRoundKey on a trivial ciphertext
+// (mask 0, body = bit << 63) of v_u.  CTR's last layer adds the data byte.
+template <class Keys>
 __global__ __launch_bounds__(256) void gather_add_indexed_kernel(const uint64_t *pool, uint32_t n_luts, const uint32_t *head, const uint32_t *term,
-                                                                 uint32_t terms, const uint64_t *rk, uint64_t key_stride, uint64_t *out, uint64_t n_out, uint32_t lwe_words)
+                                                                 uint32_t terms, const Keys keys, uint64_t *out, uint64_t n_out, uint32_t lwe_words)
 {
     const uint32_t byte_words = 8 * lwe_words;
     for (uint64_t u = blockIdx.y; u < n_out; u += gridDim.y) {
         const uint32_t h = head[u], pos = h & 15u, clear = (h >> 8) & 0xFFu;
-        const uint64_t *kb = rk + (h >> 16) * key_stride + (uint64_t)pos * byte_words;
+        const Keys key = keys.key(h >> 16);
         const uint64_t *s[4];                                    // terms <= 4; fully unrolled so that the pointers stay in registers
 #pragma unroll
         for (uint32_t t = 0; t < 4; ++t) {
@@ -122,14 +189,11 @@ __global__ __launch_bounds__(256) void gather_add_indexed_kernel(const uint64_t 
         }
         uint64_t *ob = out + u * byte_words;
         for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
-            uint64_t v = kb[w];
+            uint64_t v = key.word(pos, w, lwe_words);
 #pragma unroll
             for (uint32_t t = 0; t < 4; ++t)
                 if (t < terms) v += s[t][w];
-            if (clear) {
-                const uint32_t bit = w / lwe_words;
-                if (w - bit * lwe_words == lwe_words - 1) v += (uint64_t)((clear >> bit) & 1u) << 63;
-            }
+            if (clear) v = add_trivial_bit(v, clear, w, lwe_words);
             ob[w] = v;
         }
     }
@@ -245,7 +309,6 @@ __global__ __launch_bounds__(256) void expand_masks_kernel(uint64_t *out, const 
 // for one (GLWE, polynomial): for fixed i the 512 rotated reads of a row are two contiguous runs, each thread keeps coefficients c and
 // c + 256, and the partial sums of the N / PACK_FOLD_ROWS workgroups of a polynomial meet in `packed` (zeroed by the launcher) with one
 // 64-bit atomic add per coefficient.  Wrapping integer sums: any order gives the same words.
-#define PACK_N 512
 #define PACK_FOLD_ROWS 32
 #define PACK_FOLD_UNROLL 8
 
@@ -289,127 +352,30 @@ __global__ __launch_bounds__(256) void pack_fold_kernel(const uint64_t *ks, uint
     atomicAdd(dst + c + 256, (unsigned long long)hi);
 }
 
-// Sample extraction of coefficient i = t % N of GLWE t / N: the blind rotation's extraction of coefficient 0, for any coefficient.
-//   mask word jN + c = A_j[i - c] (c <= i), -A_j[i - c + N] (c > i); body = B[i]
-// One workgroup per bit writes the kN + 1 words of its LWE in order; the reads run backwards through a polynomial that the N bits of a
-// GLWE share (20 KB, cache resident), so HBM sees the writes: 16,392 B per bit.
-// packed: [ceil(m / N)][k + 1][N]; lwe: [m][kN + 1]
+// Sample extraction of coefficient i = t % N of GLWE t / N (sample_extract_word).  One workgroup per bit writes the kN + 1 words of its
+// LWE in order; the reads run backwards through a polynomial that the N bits of a GLWE share (20 KB, cache resident), so HBM sees the
+// writes: 16,392 B per bit.
+// packed: the first of ceil(m / N) GLWEs, through either reader; lwe: [m][kN + 1]
 #define UNPACK_BITS_PER_WG 4
-__global__ __launch_bounds__(256) void sample_extract_kernel(const uint64_t *packed, uint64_t m, uint32_t k, uint64_t *lwe)
+template <class Glwe>
+__device__ __forceinline__ void sample_extract_bits(const Glwe packed, uint64_t m, uint32_t k, uint64_t *lwe)
 {
     const uint32_t big = k * PACK_N;
     for (uint32_t u = 0; u < UNPACK_BITS_PER_WG; ++u) {
         const uint64_t t = (uint64_t)blockIdx.x * UNPACK_BITS_PER_WG + u;
         if (t >= m) return;
         const uint32_t i = (uint32_t)(t & (PACK_N - 1));
-        const uint64_t *glwe = packed + (t / PACK_N) * (uint64_t)(k + 1) * PACK_N;
+        const Glwe glwe = packed.glwe(t / PACK_N, k);
         uint64_t *o = lwe + t * (uint64_t)(big + 1);
-        for (uint32_t w = threadIdx.x; w < big; w += blockDim.x) {
-            const uint32_t c = w & (PACK_N - 1);
-            const uint64_t v = glwe[(w - c) + ((i - c) & (PACK_N - 1))];
-            o[w] = c <= i ? v : (uint64_t)0 - v;
-        }
-        if (threadIdx.x == 0) o[big] = glwe[(uint64_t)big + i];
+        for (uint32_t w = threadIdx.x; w < big; w += blockDim.x) o[w] = sample_extract_word(glwe, i, w, k);
+        if (threadIdx.x == 0) o[big] = sample_extract_word(glwe, i, big, k);
     }
 }
 
-// ---- packed round keys (fheaes_pack_round_keys, fheaes_aes_*_keyed_packed) ---------------------------------------------------------
-// A store holds key j as G = ceil((Nr+1) 128 / N) GLWEs at j * key_words words, key_words = G (k+1) N: fheaes_pack_bits of the key's round
-// keys flattened, so bit t = round * 128 + byte * 8 + bit sits in GLWE t / N, coefficient t % N.  The four kernels below are
-// add_bcast_kernel, gather_add_kernel, public_round1_kernel and gather_add_indexed_kernel with the round-key word read from that form:
-// word w of the LWE of bit t is sample_extract_kernel's word, taken at the moment AddRoundKey needs it.  Consecutive lanes take
-// consecutive w, so the state and WoPBS-output streams stay forward; the key read alone runs backwards through one polynomial (a wave
-// reads one contiguous run, two where it wraps).  All offsets in 64 bits: key 65,535 of an AES-128 store at k = 4 starts at byte 4,026,470,400 (past 2^31; AES-192 / 256 stores pass 2^32).
-
-// word w (< kN + 1) of the LWE ciphertext of bit t of the key whose G GLWEs start at `key`
-__device__ __forceinline__ uint64_t packed_key_word(const uint64_t *key, uint32_t t, uint32_t w, uint32_t k)
+// packed: [ceil(m / N)][k + 1][N]
+__global__ __launch_bounds__(256) void sample_extract_kernel(const uint64_t *packed, uint64_t m, uint32_t k, uint64_t *lwe)
 {
-    const uint32_t big = k * PACK_N, i = t & (PACK_N - 1);
-    const uint64_t *glwe = key + (uint64_t)(t / PACK_N) * (k + 1) * PACK_N;
-    if (w == big) return glwe[(uint64_t)big + i];
-    const uint32_t c = w & (PACK_N - 1);
-    const uint64_t v = glwe[(w - c) + ((i - c) & (PACK_N - 1))];
-    return c <= i ? v : (uint64_t)0 - v;
-}
-
-// add_bcast_kernel from a packed store: dst[blk][i] += word i % (kN+1) of bit bit0 + i / (kN+1) of key key_of_block[blk]; words_per_block = 128 (kN+1)
-__global__ __launch_bounds__(256) void add_bcast_packed_kernel(uint64_t *dst, const uint64_t *store, const uint32_t *key_of_block, uint64_t key_words,
-                                                               uint32_t bit0, uint32_t k, uint64_t words_per_block, uint64_t n_blocks)
-{
-    const uint32_t lwe_words = k * PACK_N + 1;
-    for (uint64_t blk = blockIdx.y; blk < n_blocks; blk += gridDim.y) {
-        const uint64_t *key = store + (key_of_block ? key_of_block[blk] * key_words : 0);
-        uint64_t *db = dst + blk * words_per_block;
-        for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words_per_block; i += (uint64_t)gridDim.x * blockDim.x) {
-            const uint32_t bit = (uint32_t)(i / lwe_words);
-            db[i] += packed_key_word(key, bit0 + bit, (uint32_t)(i - (uint64_t)bit * lwe_words), k);
-        }
-    }
-}
-
-// gather_add_kernel with the round key (never null here) read from a packed store; bit0 = round * 128; byte_words = 8 (kN+1)
-__global__ __launch_bounds__(256) void gather_add_packed_kernel(const uint64_t *src, uint32_t n_luts, const uint64_t *store, const uint32_t *key_of_block,
-                                                                uint64_t key_words, uint32_t bit0, uint32_t k, uint64_t *out, uint64_t n_blocks,
-                                                                uint32_t byte_words, const GatherTable tab)
-{
-    const uint64_t blk = blockIdx.z;
-    const uint32_t byte = blockIdx.y, lwe_words = k * PACK_N + 1;
-    const uint64_t *sb = src + blk * 16 * (uint64_t)n_luts * byte_words;
-    const uint64_t *key = store + (key_of_block ? key_of_block[blk] * key_words : 0);
-    uint64_t *ob = out + (blk * 16 + byte) * (uint64_t)byte_words;
-    for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
-        const uint32_t bit = w / lwe_words;
-        uint64_t v = packed_key_word(key, bit0 + byte * 8 + bit, w - bit * lwe_words, k);
-        for (int t = 0; t < tab.terms; ++t)
-            v += sb[((uint64_t)tab.src[byte][t] * n_luts + tab.lut[byte][t]) * byte_words + w];
-        ob[w] = v;
-    }
-}
-
-// public_round1_kernel from a packed store (round 0: bits 0..127 of each key)
-__global__ __launch_bounds__(256) void public_round1_packed_kernel(const uint32_t *head, const uint64_t *store, uint64_t key_words, uint32_t k, uint64_t *out,
-                                                                   uint64_t n_pool)
-{
-    const uint32_t lwe_words = k * PACK_N + 1, byte_words = 8 * lwe_words;
-    for (uint64_t u = blockIdx.y; u < n_pool; u += gridDim.y) {
-        const uint32_t h = head[u], pos = h & 15u, clear = (h >> 8) & 0xFFu;
-        const uint64_t *key = store + (h >> 16) * key_words;
-        uint64_t *ob = out + u * byte_words;
-        for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
-            const uint32_t bit = w / lwe_words, x = w - bit * lwe_words;
-            uint64_t v = packed_key_word(key, pos * 8 + bit, x, k);
-            if (x == lwe_words - 1) v += (uint64_t)((clear >> bit) & 1u) << 63;
-            ob[w] = v;
-        }
-    }
-}
-
-// gather_add_indexed_kernel from a packed store; bit0 = round * 128
-__global__ __launch_bounds__(256) void gather_add_indexed_packed_kernel(const uint64_t *pool, uint32_t n_luts, const uint32_t *head, const uint32_t *term,
-                                                                        uint32_t terms, const uint64_t *store, uint64_t key_words, uint32_t bit0, uint32_t k,
-                                                                        uint64_t *out, uint64_t n_out)
-{
-    const uint32_t lwe_words = k * PACK_N + 1, byte_words = 8 * lwe_words;
-    for (uint64_t u = blockIdx.y; u < n_out; u += gridDim.y) {
-        const uint32_t h = head[u], pos = h & 15u, clear = (h >> 8) & 0xFFu;
-        const uint64_t *key = store + (h >> 16) * key_words;
-        const uint64_t *s[4];                                    // terms <= 4; fully unrolled so that the pointers stay in registers
-#pragma unroll
-        for (uint32_t t = 0; t < 4; ++t) {
-            const uint32_t e = t < terms ? term[u * terms + t] : 0u;
-            s[t] = pool + ((uint64_t)(e >> 2) * n_luts + (e & 3u)) * byte_words;
-        }
-        uint64_t *ob = out + u * byte_words;
-        for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < byte_words; w += gridDim.x * blockDim.x) {
-            const uint32_t bit = w / lwe_words, x = w - bit * lwe_words;
-            uint64_t v = packed_key_word(key, bit0 + pos * 8 + bit, x, k);
-#pragma unroll
-            for (uint32_t t = 0; t < 4; ++t)
-                if (t < terms) v += s[t][w];
-            if (x == lwe_words - 1) v += (uint64_t)((clear >> bit) & 1u) << 63;
-            ob[w] = v;
-        }
-    }
+    sample_extract_bits(GlweWords{packed}, m, k, lwe);
 }
 
 // ---- wire formats (include/fheaes.h): seeded input ciphertexts, modulus-switched packed outputs --------------------------------------
@@ -483,31 +449,9 @@ __global__ __launch_bounds__(256) void mod_switch_pack_kernel(const uint64_t *gl
     }
 }
 
-// field e of a switched GLWE, read back: x' = v << (64 - w), from one or two words
-__device__ __forceinline__ uint64_t mod_field(const uint64_t *glwe, uint32_t e, uint32_t w)
-{
-    const uint32_t bit = e * w, word = bit >> 6, off = bit & 63;
-    uint64_t v = glwe[word] >> off;
-    if (off + w > 64) v |= glwe[word + 1] << (64 - off);               // the field straddles two words (off > 0 here)
-    return v << (64 - w);
-}
-
 // sample_extract_kernel reading the w-bit fields: word for word the extraction of the read-back GLWEs
-// in: [ceil(m / N)][(k + 1) 8 w]; lwe: [m][kN + 1]
+// in: [ceil(m / N)][(k + 1) 8 w]
 __global__ __launch_bounds__(256) void sample_extract_mod_kernel(const uint64_t *in, uint64_t m, uint32_t k, uint32_t w, uint64_t *lwe)
 {
-    const uint32_t big = k * PACK_N;
-    for (uint32_t u = 0; u < UNPACK_BITS_PER_WG; ++u) {
-        const uint64_t t = (uint64_t)blockIdx.x * UNPACK_BITS_PER_WG + u;
-        if (t >= m) return;
-        const uint32_t i = (uint32_t)(t & (PACK_N - 1));
-        const uint64_t *glwe = in + (t / PACK_N) * (uint64_t)(k + 1) * 8 * w;
-        uint64_t *o = lwe + t * (uint64_t)(big + 1);
-        for (uint32_t x = threadIdx.x; x < big; x += blockDim.x) {
-            const uint32_t c = x & (PACK_N - 1);
-            const uint64_t v = mod_field(glwe, (x - c) + ((i - c) & (PACK_N - 1)), w);
-            o[x] = c <= i ? v : (uint64_t)0 - v;
-        }
-        if (threadIdx.x == 0) o[big] = mod_field(glwe, big + i, w);
-    }
+    sample_extract_bits(GlweFields{in, w}, m, k, lwe);
 }
