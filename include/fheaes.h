@@ -229,6 +229,27 @@ int fheaes_aes_ctr_bits(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t ke
 /* How many byte-WoPBS the two calls above run in each round for these blocks: unique_bytes_per_round[r - 1], r = 1..Nr (host logic only,
  * no context, no GPU; fheaes_aes_encrypt_bits runs 16 n_blocks in every round). */
 int fheaes_aes_public_plan(const uint64_t *blocks_hi_lo, uint64_t n_blocks, uint32_t key_bits, uint64_t *unique_bytes_per_round);
+/* The keystream of AES-GCM (SP 800-38D GCTR): fheaes_aes_ctr_bits with a 32-bit counter field.  Counter block i is icb with its low 32
+ * bits replaced by (low32(icb) + first_block + i) mod 2^32 (inc32); the upper 96 bits never change, so a batch may wrap.  For a 96-bit
+ * GCM IV the data blocks start at icb = IV || 00000002 (J0 = IV || 00000001 masks the tag).  GHASH and the tag are NOT computed: a
+ * product of two encrypted field elements is far above the five-term noise budget. */
+int fheaes_aes_ctr32_bits(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *icb_hi_lo, uint64_t first_block,
+                          const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace);
+/* The DECRYPTION direction of the public calls (AES-CBC data at rest, or any mode that deciphers public blocks): the equivalent inverse
+ * cipher (fheaes_aes_decrypt_equivalent_bits) on public blocks with the same sharing rule.  dec_round_keys [Nr+1][16][8][kN+1] are
+ * fheaes_aes_decryption_round_keys_bits' output.  The id of a round-1 input is (key, position, byte) -- the input is dw[Nr][p] +
+ * trivial(byte) -- and the id of a later one is (position, ids of its four sources (4 ((col - j) mod 4) + j, InvShiftRows folded in));
+ * a round is the 4-LUT {9, 11, 13, 14} InvS WoPBS over its pool and sums 4 outputs + dw[Nr - r], 5 terms as
+ * fheaes_aes_decrypt_equivalent_bits; the last layer is InvS through InvShiftRows + dw[0].  data_hi_lo (n_blocks pairs, may be NULL) is
+ * folded into the last layer as fheaes_aes_ctr_bits' data.  The result is, word for word, what fheaes_aes_decrypt_equivalent_bits writes
+ * for trivial ciphertexts of the blocks, with bit << 63 of the data added to the bodies.  Argument rules of fheaes_aes_encrypt_public_bits. */
+int fheaes_aes_decrypt_public_bits(fheaes_ctx *ctx, const uint64_t *dec_round_keys, uint32_t key_bits, const uint64_t *blocks_hi_lo,
+                                   const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace);
+/* SP 800-38A CBC decryption: block i = D_K(ct[i]) ^ (i ? ct[i-1] : iv), which is fheaes_aes_decrypt_public_bits with the ciphertext moved
+ * down by one block as its data.  iv_hi_lo: one (hi, lo) pair; ct_hi_lo: n_blocks pairs.  A caller continuing a stream passes the
+ * previous ciphertext block as iv.  Equal ciphertext blocks share their S-Boxes; CBC ENCRYPTION is serial and is not offered. */
+int fheaes_aes_cbc_decrypt_bits(fheaes_ctx *ctx, const uint64_t *dec_round_keys, uint32_t key_bits, const uint64_t *iv_hi_lo,
+                                const uint64_t *ct_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace);
 
 /* ---- many AES keys ---------------------------------------------------------------- */
 /* One FHE key pair, many AES keys (producers, sessions, rotated keys), each reaching the server encrypted under that FHE key: short
@@ -269,6 +290,16 @@ int fheaes_aes_public_keyed(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_
 /* fheaes_aes_public_plan for the call above (host logic only, no context, no GPU); with every key 0 it gives fheaes_aes_public_plan's counts. */
 int fheaes_aes_public_plan_keyed(const uint64_t *blocks_hi_lo, const uint32_t *key_of_block, uint64_t n_blocks, uint64_t n_keys,
                                  uint32_t key_bits, uint64_t *unique_bytes_per_round);
+/* fheaes_aes_decrypt_public_bits with a key per block (dec_round_keys [n_keys][Nr+1][16][8][kN+1]): word for word what
+ * fheaes_aes_decrypt_equivalent_keyed writes for trivial ciphertexts of the blocks, plus the data; several CBC streams under several keys
+ * are one call (the caller moves each stream's ciphertext down by one block for data_hi_lo). */
+int fheaes_aes_decrypt_public_keyed(fheaes_ctx *ctx, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t n_keys,
+                                    const uint32_t *key_of_block, const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks,
+                                    uint64_t *state_out, int memspace);
+/* How many byte-WoPBS the decryption-direction calls run in each round (host logic only, no context, no GPU).  key_of_block may be NULL:
+ * every block under key 0, the plan of fheaes_aes_decrypt_public_bits and fheaes_aes_cbc_decrypt_bits. */
+int fheaes_aes_decrypt_public_plan_keyed(const uint64_t *blocks_hi_lo, const uint32_t *key_of_block, uint64_t n_blocks, uint64_t n_keys,
+                                         uint32_t key_bits, uint64_t *unique_bytes_per_round);
 
 /* ---- packed ciphertexts --------------------------------------------------------- */
 /* Every entry point above hands its result out one LWE ciphertext per bit: kN + 1 words (16,392 bytes at PARAM_OPT) for one bit.  A
@@ -380,7 +411,7 @@ int fheaes_pack_round_keys(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t
  * are read.  Overlapping buffers are FHEAES_ERR_INVALID. */
 int fheaes_unpack_round_keys(fheaes_ctx *ctx, const uint64_t *packed, uint32_t key_bits, uint64_t first_key, uint64_t n_keys,
                              uint64_t *round_keys_out, int memspace);
-/* fheaes_aes_encrypt_keyed / _decrypt_keyed / _decrypt_equivalent_keyed / fheaes_aes_public_keyed with a packed store
+/* fheaes_aes_encrypt_keyed / _decrypt_keyed / _decrypt_equivalent_keyed / fheaes_aes_public_keyed / _decrypt_public_keyed with a packed store
  * [n_keys][G][(k+1)N] in place of round_keys.  The rules of their counterparts (key_of_block a HOST array, an entry >= n_keys
  * FHEAES_ERR_INVALID, n_blocks = 0 FHEAES_OK, FHEAES_DEVICE only enqueues, the same windows), and a store that overlaps the state is
  * FHEAES_ERR_INVALID.  One key (n_keys = 1, key_of_block all 0) serves where a single-key call would. */
@@ -393,6 +424,9 @@ int fheaes_aes_decrypt_equivalent_keyed_packed(fheaes_ctx *ctx, const uint64_t *
 int fheaes_aes_public_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys,
                                    const uint32_t *key_of_block, const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks,
                                    uint64_t *state_out, int memspace);
+int fheaes_aes_decrypt_public_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_dec_round_keys, uint32_t key_bits, uint64_t n_keys,
+                                           const uint32_t *key_of_block, const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo,
+                                           uint64_t n_blocks, uint64_t *state_out, int memspace);
 
 /* ---- measurement --------------------------------------------------------------- */
 #define FHEAES_STAGE_KEYSWITCH 0

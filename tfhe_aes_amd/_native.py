@@ -66,6 +66,9 @@ SIGNATURES = {
     "fheaes_aes_encrypt_public_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_ctr_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _c.c_uint64, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_public_plan": (_c.c_int, [_u64p, _c.c_uint64, _c.c_uint32, _u64p]),
+    "fheaes_aes_ctr32_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _c.c_uint64, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_decrypt_public_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_cbc_decrypt_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_key_expansion_batch": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_decryption_round_keys_batch": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_encrypt_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _c.c_void_p, _c.c_uint64, _c.c_int]),
@@ -73,6 +76,8 @@ SIGNATURES = {
     "fheaes_aes_decrypt_equivalent_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _c.c_void_p, _c.c_uint64, _c.c_int]),
     "fheaes_aes_public_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _u64p, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_public_plan_keyed": (_c.c_int, [_u64p, _u32p, _c.c_uint64, _c.c_uint64, _c.c_uint32, _u64p]),
+    "fheaes_aes_decrypt_public_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _u64p, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_decrypt_public_plan_keyed": (_c.c_int, [_u64p, _u32p, _c.c_uint64, _c.c_uint64, _c.c_uint32, _u64p]),
     "fheaes_packed_words": (_c.c_size_t, [_ctx, _c.c_uint64]),
     "fheaes_pack_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_unpack_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
@@ -88,6 +93,8 @@ SIGNATURES = {
     "fheaes_aes_decrypt_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _c.c_void_p, _c.c_uint64, _c.c_int]),
     "fheaes_aes_decrypt_equivalent_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _c.c_void_p, _c.c_uint64, _c.c_int]),
     "fheaes_aes_public_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _u64p, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_decrypt_public_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _u64p, _u64p, _c.c_uint64, _c.c_void_p,
+                                                          _c.c_int]),
     "fheaes_profile_enable": (_c.c_int, [_ctx, _c.c_int]),
     "fheaes_profile_reset": (_c.c_int, [_ctx]),
     "fheaes_profile_read": (_c.c_int, [_ctx, _c.c_int, _dp, _u64p, _u64p]),
@@ -328,14 +335,33 @@ class Engine:
         self._check(self._lib.fheaes_aes_encrypt_public_bits(self._h, _ptr(round_keys)[0], key_bits, cnt.ctypes.data_as(_u64p), len(cnt),
                                                              _ptr(state_out)[0], self._space(round_keys, state_out)))
 
-    def aes_ctr_bits(self, round_keys, key_bits: int, iv: int, first_block: int, data, n_blocks: int, state_out):
+    def aes_ctr_bits(self, round_keys, key_bits: int, iv: int, first_block: int, data, n_blocks: int, state_out, counter_bits: int = 128):
+        """counter_bits 128: SP 800-38A CTR (fheaes_aes_ctr_bits); 32: the counter field of GCM, `iv` being the initial counter block
+        (fheaes_aes_ctr32_bits)"""
+        if counter_bits not in (32, 128):
+            raise ValueError("counter_bits must be 32 or 128, got %r" % (counter_bits,))
         ivp = u128_pairs([iv])
         dat = u128_pairs(data) if data is not None else None
         if dat is not None and len(dat) != n_blocks:
             raise ValueError("one data block per counter block expected")
-        self._check(self._lib.fheaes_aes_ctr_bits(self._h, _ptr(round_keys)[0], key_bits, ivp.ctypes.data_as(_u64p), first_block,
-                                                  dat.ctypes.data_as(_u64p) if dat is not None else None, n_blocks, _ptr(state_out)[0],
-                                                  self._space(round_keys, state_out)))
+        fn = self._lib.fheaes_aes_ctr32_bits if counter_bits == 32 else self._lib.fheaes_aes_ctr_bits
+        self._check(fn(self._h, _ptr(round_keys)[0], key_bits, ivp.ctypes.data_as(_u64p), first_block,
+                       dat.ctypes.data_as(_u64p) if dat is not None else None, n_blocks, _ptr(state_out)[0], self._space(round_keys, state_out)))
+
+    # public blocks through the equivalent inverse cipher (dec_round_keys: aes_decryption_round_keys*), CBC decryption
+    def aes_decrypt_public_bits(self, dec_round_keys, key_bits: int, blocks, data, state_out):
+        cnt = u128_pairs(blocks)
+        dat = u128_pairs(data) if data is not None else None
+        if dat is not None and len(dat) != len(cnt):
+            raise ValueError("one data block per block expected")
+        self._check(self._lib.fheaes_aes_decrypt_public_bits(self._h, _ptr(dec_round_keys)[0], key_bits, cnt.ctypes.data_as(_u64p),
+                                                             dat.ctypes.data_as(_u64p) if dat is not None else None, len(cnt), _ptr(state_out)[0],
+                                                             self._space(dec_round_keys, state_out)))
+
+    def aes_cbc_decrypt_bits(self, dec_round_keys, key_bits: int, iv, ciphertext, state_out):
+        ivp, cnt = u128_pairs([iv]), u128_pairs(ciphertext)
+        self._check(self._lib.fheaes_aes_cbc_decrypt_bits(self._h, _ptr(dec_round_keys)[0], key_bits, ivp.ctypes.data_as(_u64p), cnt.ctypes.data_as(_u64p),
+                                                          len(cnt), _ptr(state_out)[0], self._space(dec_round_keys, state_out)))
 
     # many AES keys: round keys [n_keys][Nr+1][16][8][kN+1]; key_of_block (one key index per block) travels as a host uint32 array
     def aes_key_expansion_batch(self, keys, key_bits: int, n_keys: int, round_keys):
@@ -358,14 +384,19 @@ class Engine:
     def aes_decrypt_equivalent_keyed(self, dec_round_keys, key_bits: int, n_keys: int, key_of_block, state, n_blocks: int):
         self._keyed(self._lib.fheaes_aes_decrypt_equivalent_keyed, dec_round_keys, key_bits, n_keys, key_of_block, state, n_blocks)
 
-    def aes_public_keyed(self, round_keys, key_bits: int, n_keys: int, key_of_block, blocks, data, state_out, packed: bool = False):
-        """`packed`: round_keys is a packed store [n_keys][G][(k+1)N] (fheaes_aes_public_keyed_packed)"""
+    def aes_public_keyed(self, round_keys, key_bits: int, n_keys: int, key_of_block, blocks, data, state_out, packed: bool = False,
+                         inverse: bool = False):
+        """`packed`: round_keys is a packed store [n_keys][G][(k+1)N] (fheaes_aes_public_keyed_packed); `inverse`: the decryption
+        direction, round_keys being decryption round keys (fheaes_aes_decrypt_public_keyed / _packed)"""
         cnt = u128_pairs(blocks)
         kob = key_indices(key_of_block, len(cnt))
         dat = u128_pairs(data) if data is not None else None
         if dat is not None and len(dat) != len(cnt):
             raise ValueError("one data block per block expected")
-        fn = self._lib.fheaes_aes_public_keyed_packed if packed else self._lib.fheaes_aes_public_keyed
+        if inverse:
+            fn = self._lib.fheaes_aes_decrypt_public_keyed_packed if packed else self._lib.fheaes_aes_decrypt_public_keyed
+        else:
+            fn = self._lib.fheaes_aes_public_keyed_packed if packed else self._lib.fheaes_aes_public_keyed
         self._check(fn(self._h, _ptr(round_keys)[0], key_bits, n_keys, kob.ctypes.data_as(_u32p), cnt.ctypes.data_as(_u64p),
                        dat.ctypes.data_as(_u64p) if dat is not None else None, len(cnt), _ptr(state_out)[0], self._space(round_keys, state_out)))
 
@@ -525,6 +556,24 @@ def aes_public_plan_keyed(blocks, key_of_block, n_keys: int, key_bits: int = 128
     if rc != 0:
         raise FheAesError(rc, "fheaes_aes_public_plan_keyed: key_bits must be 128, 192 or 256, n_keys in 1..65536 and every key index below n_keys")
     return [int(x) for x in out[:{128: 10, 192: 12, 256: 14}[key_bits]]]
+
+
+def aes_decrypt_public_plan_keyed(blocks, key_of_block, n_keys: int, key_bits: int = 128) -> list[int]:
+    """byte-WoPBS per round (rounds 1..Nr) of aes_decrypt_public_keyed / aes_cbc_streams for these blocks; key_of_block None: one key
+    (fheaes_aes_decrypt_public_plan_keyed: host only, no GPU)"""
+    cnt = u128_pairs(blocks)
+    kob = key_indices(key_of_block, len(cnt)) if key_of_block is not None else None
+    out = np.zeros(14, dtype=np.uint64)
+    rc = load_library().fheaes_aes_decrypt_public_plan_keyed(cnt.ctypes.data_as(_u64p), kob.ctypes.data_as(_u32p) if kob is not None else None, len(cnt),
+                                                             n_keys, key_bits, out.ctypes.data_as(_u64p))
+    if rc != 0:
+        raise FheAesError(rc, "fheaes_aes_decrypt_public_plan_keyed: key_bits must be 128, 192 or 256, n_keys in 1..65536 and every key index below n_keys")
+    return [int(x) for x in out[:{128: 10, 192: 12, 256: 14}[key_bits]]]
+
+
+def aes_decrypt_public_plan(blocks, key_bits: int = 128) -> list[int]:
+    """byte-WoPBS per round (rounds 1..Nr) that aes_decrypt_public / aes_cbc_decrypt run for these blocks (host only, no GPU)"""
+    return aes_decrypt_public_plan_keyed(blocks, None, 1, key_bits)
 
 
 def round_keys_packed_glwes(key_bits: int) -> int:

@@ -116,9 +116,28 @@ def aes_encrypt_block(key, block: int) -> int:
     return _u128(a ^ b for a, b in zip(s, rk[nr]))
 
 
-def ctr_keystream(key, iv: int, first_block: int, n_blocks: int) -> list[int]:
-    """SP 800-38A CTR: keystream block i = E_K((iv + first_block + i) mod 2^128), i < n_blocks, as u128 (byte 0 = MSB)"""
-    return [aes_encrypt_block(key, (iv + first_block + i) % (1 << 128)) for i in range(n_blocks)]
+def counter_block(iv: int, i: int, counter_bits: int = 128) -> int:
+    """counter block i of SP 800-38A appendix B.1: the low counter_bits bits of iv incremented i times mod 2^counter_bits, the bits above
+    them unchanged (counter_bits = 32: inc32 of SP 800-38D)"""
+    if counter_bits not in (32, 128):
+        raise ValueError("counter_bits must be 32 or 128, got %r" % (counter_bits,))
+    m = 1 << counter_bits
+    return (iv & ~(m - 1)) | ((iv + i) & (m - 1))
+
+
+def ctr_keystream(key, iv: int, first_block: int, n_blocks: int, counter_bits: int = 128) -> list[int]:
+    """SP 800-38A CTR: keystream block i = E_K((iv + first_block + i) mod 2^128), i < n_blocks, as u128 (byte 0 = MSB); counter_bits = 32:
+    only the low 32 bits of iv count (the counter field of GCM)"""
+    return [aes_encrypt_block(key, counter_block(iv, first_block + i, counter_bits)) for i in range(n_blocks)]
+
+
+def gcm_keystream(key, iv: bytes, first_block: int, n_blocks: int) -> list[int]:
+    """SP 800-38D GCTR for a 96-bit IV: J0 = iv || 00000001, keystream block i (for data block first_block + i) = E_K(inc32^(first_block +
+    i + 1)(J0)); E_K(J0) itself masks the tag and is not part of it.  GHASH and the tag are not computed here."""
+    if len(iv) != 12:
+        raise ValueError("a 12-byte IV is expected (other lengths derive J0 with GHASH), got %d bytes" % len(iv))
+    j0 = int.from_bytes(bytes(iv) + b"\x00\x00\x00\x01", "big")
+    return ctr_keystream(key, j0, first_block + 1, n_blocks, counter_bits=32)
 
 
 def ctr_streams(keys, streams) -> list[int]:
@@ -143,6 +162,18 @@ def aes_decrypt_block(key, block: int) -> int:
         s = _mix(s, (14, 11, 13, 9))
     s = [INV_SBOX[b] for b in _inv_shift_rows(s)]
     return _u128(a ^ b for a, b in zip(s, rk[0]))
+
+
+def cbc_decrypt(key, iv: int, ciphertext) -> list[int]:
+    """SP 800-38A CBC decryption: P_i = D_K(C_i) ^ C_{i-1}, C_{-1} = iv; blocks as u128"""
+    ciphertext = list(ciphertext)
+    return [aes_decrypt_block(key, c) ^ prev for c, prev in zip(ciphertext, [iv] + ciphertext[:-1])]
+
+
+def cfb128_decrypt(key, iv: int, ciphertext) -> list[int]:
+    """SP 800-38A CFB-128 decryption: P_i = E_K(C_{i-1}) ^ C_i, C_{-1} = iv; blocks as u128"""
+    ciphertext = list(ciphertext)
+    return [aes_encrypt_block(key, prev) ^ c for c, prev in zip(ciphertext, [iv] + ciphertext[:-1])]
 
 
 def aes128_encrypt_block(key: int, block: int) -> int:

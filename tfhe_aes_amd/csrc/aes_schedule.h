@@ -239,8 +239,8 @@ static int add_scalar_dev(fheaes_ctx *c, uint64_t *state, uint64_t n_blocks, con
 }
 
 // ---- public blocks and CTR with a public nonce ------------------------------------------------
-// aes_encrypt on PUBLIC blocks (trivial ciphertexts) with every distinct S-Box input of the batch evaluated once.  A WoPBS is a
-// deterministic function of its input words, so two state bytes with word-equal inputs need one evaluation.  The rule that finds them
+// aes_encrypt -- or the equivalent inverse cipher, PublicDirection below; the rule is written out for encryption -- on PUBLIC blocks
+// (trivial ciphertexts) with every distinct S-Box input of the batch evaluated once.  A WoPBS is a deterministic function of its input words, so two state bytes with word-equal inputs need one evaluation.  The rule that finds them
 // is exact and runs on the host before anything is enqueued: every S-Box input gets an id, round by round,
 //   round 1:   id(b, p) = (key of b, p, byte p of block b)            -- the input is rk[key][0][p] + trivial(byte)
 //   round r+1: id(b, p) = (p, id_r(b, s_0), .., id_r(b, s_3))         -- s_j: the four sources of table_enc_round() for position p
@@ -269,11 +269,30 @@ struct PublicKey5Hash {
     }
 };
 
+// Which cipher the public blocks go through: the round gather and the last layer's, the LUT set and LUT count of the rounds and of the
+// last round, and which round key layer r = 0..Nr adds.  The rule above holds for either direction, with the direction's sources in
+// place of table_enc_round()'s and its first round key in place of rk[key][0].
+struct PublicDirection {
+    GatherTable round, last;
+    int round_set, last_set;
+    uint32_t round_luts, last_luts;
+    bool keys_descend;                                          // layer r adds round key Nr - r, not r
+    uint64_t key_round(int layer, int nr) const { return (uint64_t)(keys_descend ? nr - layer : layer); }
+};
+
+// aes_encrypt_schedule on pools
+static PublicDirection public_forward() { return {table_enc_round(), table_shift_rows(false), LUTSET_ENC_ROUND, LUTSET_SBOX, 3, 1, false}; }
+// aes_decrypt_eq_schedule on pools: rk is a set of decryption round keys dw, the pool of round 1 is dw[Nr][key][p] + trivial(byte), pool
+// r + 1 sums the four {9, 11, 13, 14} InvS outputs of table_dec_eq_round() plus dw[Nr - r] (5 terms for the noise guard, as
+// aes_decrypt_equivalent), the last layer is InvS through InvShiftRows plus dw[0] (plus CBC's clear chaining block)
+static PublicDirection public_inverse() { return {table_dec_eq_round(), table_shift_rows(true), LUTSET_DEC_EQ_ROUND, LUTSET_INV_SBOX, 4, 1, true}; }
+
 // blocks / data: n_blocks (hi, lo) pairs, data may be null; key_of_block: n_blocks key indices below PUBLIC_MAX_KEYS, or null (all 0)
-static void public_plan(const uint64_t *blocks, const uint64_t *data, const uint32_t *key_of_block, uint64_t n_blocks, int nr, PublicPlan &pl)
+static void public_plan(const PublicDirection &dir, const uint64_t *blocks, const uint64_t *data, const uint32_t *key_of_block, uint64_t n_blocks, int nr,
+                        PublicPlan &pl)
 {
     auto key_of = [&](uint64_t b) { return key_of_block ? key_of_block[b] : 0u; };
-    const GatherTable t_round = table_enc_round(), t_shift = table_shift_rows(false);
+    const GatherTable &t_round = dir.round, &t_shift = dir.last;
     const uint64_t nbytes = 16 * n_blocks;
     std::vector<uint32_t> id(nbytes), next(nbytes);
     pl.layers.clear(); pl.words.clear();
@@ -320,7 +339,7 @@ static void public_plan(const uint64_t *blocks, const uint64_t *data, const uint
         }
     }
     pl.max_vp_bytes_per_bw = 0;
-    for (int r = 1; r <= nr; ++r) pl.max_vp_bytes_per_bw = std::max<uint64_t>(pl.max_vp_bytes_per_bw, (uint64_t)pl.layers[r - 1].n * (r < nr ? 3 : 1));
+    for (int r = 1; r <= nr; ++r) pl.max_vp_bytes_per_bw = std::max<uint64_t>(pl.max_vp_bytes_per_bw, (uint64_t)pl.layers[r - 1].n * (r < nr ? dir.round_luts : dir.last_luts));
 }
 
 static_assert(FHEAES_MAX_KEYS == PUBLIC_MAX_KEYS, "fheaes.h's bound on n_keys is the key field of PUBLIC_HEAD");
@@ -342,7 +361,7 @@ static int launch_gather_indexed(fheaes_ctx *c, const uint64_t *pool, uint32_t n
 
 // `out` [n_blocks][16][8][kN+1] doubles as the pool buffer: no pool has more than 16 n_blocks entries.  rk: the call's sets of round keys
 // ([n_keys][Nr+1][16][8][kN+1] or a packed store); the key of every pool entry is in its head word, so rk.of_block is not read
-static int aes_public_dev(fheaes_ctx *c, const KeySets &rk, const PublicPlan &pl, int nr, uint64_t *out)
+static int aes_public_dev(fheaes_ctx *c, const PublicDirection &dir, const KeySets &rk, const PublicPlan &pl, int nr, uint64_t *out)
 {
     const uint64_t bw = 8ull * c->big1, sw = 16 * bw;
     // the index tables go through the context's pinned buffer (as add_scalar's counter bytes): the call only enqueues
@@ -353,8 +372,8 @@ static int aes_public_dev(fheaes_ctx *c, const KeySets &rk, const PublicPlan &pl
     uint64_t *vp = (uint64_t *)c->ws_vp.p;
     for (int round = 0; round <= nr; ++round) {                              // layer 0 is the pool of round 1: nothing to evaluate before it
         const PublicPlan::Layer &to = pl.layers[round];
-        if (round > 0) TRY(many_sbox_dev(c, out, pl.layers[round - 1].n, round < nr ? LUTSET_ENC_ROUND : LUTSET_SBOX, vp));
-        TRY(launch_gather_indexed(c, vp, round < nr ? 3 : 1, tab + to.head, tab + to.term, to.terms, rk.round((uint64_t)round, sw), out, to.n));
+        if (round > 0) TRY(many_sbox_dev(c, out, pl.layers[round - 1].n, round < nr ? dir.round_set : dir.last_set, vp));
+        TRY(launch_gather_indexed(c, vp, round < nr ? dir.round_luts : dir.last_luts, tab + to.head, tab + to.term, to.terms, rk.round(dir.key_round(round, nr), sw), out, to.n));
     }
     return FHEAES_OK;
 }

@@ -854,8 +854,8 @@ int fheaes_add_scalar(fheaes_ctx *c, uint64_t *state, uint64_t n_blocks, const u
     return s.finish();
 }
 
-// key_of_block null: every block under the one set `round_keys`
-static int aes_public(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, const uint64_t *blocks,
+// key_of_block null: every block under the one set `round_keys` (decryption round keys for public_inverse())
+static int aes_public(fheaes_ctx *c, const PublicDirection &dir, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, const uint64_t *blocks,
                       const uint64_t *data, uint64_t n_blocks, uint64_t *state_out, int memspace, bool packed = false)
 {
     const int nr = aes_rounds(key_bits);
@@ -865,11 +865,11 @@ static int aes_public(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bi
     if (n_blocks > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %llu", (unsigned long long)PUBLIC_MAX_BLOCKS);
     HIP_TRY(c, hipSetDevice(c->device));
     PublicPlan pl;
-    public_plan(blocks, data, key_of_block, n_blocks, nr, pl);
+    public_plan(dir, blocks, data, key_of_block, n_blocks, nr, pl);
     Staged s(c, memspace);
     TRY(s.in(round_keys, keys_bytes, &round_keys));
     TRY(s.out(state_out, n_blocks * sw * 8, &state_out));
-    TRY(aes_public_dev(c, KeySets{round_keys, nullptr, ks.key_words, ks.glwes}, pl, nr, state_out));
+    TRY(aes_public_dev(c, dir, KeySets{round_keys, nullptr, ks.key_words, ks.glwes}, pl, nr, state_out));
     return s.finish();
 }
 
@@ -881,7 +881,7 @@ int fheaes_aes_encrypt_public_bits(fheaes_ctx *c, const uint64_t *round_keys, ui
     if (!round_keys || !blocks_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
     TRY(check_key_bits(c, key_bits));
     if (n_blocks == 0) return FHEAES_OK;
-    return aes_public(c, round_keys, key_bits, 1, nullptr, blocks_hi_lo, nullptr, n_blocks, state_out, memspace);
+    return aes_public(c, public_forward(), round_keys, key_bits, 1, nullptr, blocks_hi_lo, nullptr, n_blocks, state_out, memspace);
 }
 
 int fheaes_aes_ctr_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *iv_hi_lo, uint64_t first_block,
@@ -901,7 +901,27 @@ int fheaes_aes_ctr_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_
         ctr[2 * i] = hi0 + (lo < lo0 ? 1 : 0);
         ctr[2 * i + 1] = lo;
     }
-    return aes_public(c, round_keys, key_bits, 1, nullptr, ctr.data(), data_hi_lo, n_blocks, state_out, memspace);
+    return aes_public(c, public_forward(), round_keys, key_bits, 1, nullptr, ctr.data(), data_hi_lo, n_blocks, state_out, memspace);
+}
+
+int fheaes_aes_ctr32_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *icb_hi_lo, uint64_t first_block,
+                          const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
+{
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!round_keys || !icb_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    if (n_blocks == 0) return FHEAES_OK;
+    if (n_blocks > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %llu", (unsigned long long)PUBLIC_MAX_BLOCKS);
+    // counter block i = icb with its low 32 bits replaced by (low32(icb) + first_block + i) mod 2^32 (SP 800-38D inc32; 38A B.1 with m = 32)
+    std::vector<uint64_t> ctr(2 * n_blocks);
+    const uint64_t top = icb_hi_lo[1] & ~0xFFFFFFFFull;
+    const uint32_t low0 = (uint32_t)icb_hi_lo[1] + (uint32_t)first_block;
+    for (uint64_t i = 0; i < n_blocks; ++i) {
+        ctr[2 * i] = icb_hi_lo[0];
+        ctr[2 * i + 1] = top | (uint32_t)(low0 + (uint32_t)i);
+    }
+    return aes_public(c, public_forward(), round_keys, key_bits, 1, nullptr, ctr.data(), data_hi_lo, n_blocks, state_out, memspace);
 }
 
 int fheaes_aes_public_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
@@ -914,7 +934,7 @@ int fheaes_aes_public_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t 
     TRY(check_n_keys(c, n_keys));
     TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
     if (n_blocks == 0) return FHEAES_OK;
-    return aes_public(c, round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace);
+    return aes_public(c, public_forward(), round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace);
 }
 
 int fheaes_aes_public_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
@@ -927,7 +947,60 @@ int fheaes_aes_public_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_k
     TRY(check_n_keys(c, n_keys));
     TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
     if (n_blocks == 0) return FHEAES_OK;
-    return aes_public(c, packed_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, true);
+    return aes_public(c, public_forward(), packed_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, true);
+}
+
+// ---- public blocks through the equivalent inverse cipher: the calls above with public_inverse() and decryption round keys ----
+int fheaes_aes_decrypt_public_bits(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo,
+                                   uint64_t n_blocks, uint64_t *state_out, int memspace)
+{
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!dec_round_keys || !blocks_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    if (n_blocks == 0) return FHEAES_OK;
+    return aes_public(c, public_inverse(), dec_round_keys, key_bits, 1, nullptr, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace);
+}
+
+static int aes_decrypt_public_keyed(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
+                                    const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace, bool packed)
+{
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!dec_round_keys || !key_of_block || !blocks_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    TRY(check_n_keys(c, n_keys));
+    TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
+    if (n_blocks == 0) return FHEAES_OK;
+    return aes_public(c, public_inverse(), dec_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, packed);
+}
+
+int fheaes_aes_decrypt_public_keyed(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
+                                    const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
+{
+    return aes_decrypt_public_keyed(c, dec_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, false);
+}
+
+int fheaes_aes_decrypt_public_keyed_packed(fheaes_ctx *c, const uint64_t *packed_dec_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
+                                           const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
+{
+    return aes_decrypt_public_keyed(c, packed_dec_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, true);
+}
+
+int fheaes_aes_cbc_decrypt_bits(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, const uint64_t *iv_hi_lo, const uint64_t *ct_hi_lo,
+                                uint64_t n_blocks, uint64_t *state_out, int memspace)
+{
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!dec_round_keys || !iv_hi_lo || !ct_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_key_bits(c, key_bits));
+    if (n_blocks == 0) return FHEAES_OK;
+    if (n_blocks > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %llu", (unsigned long long)PUBLIC_MAX_BLOCKS);
+    // P_i = D_K(C_i) ^ C_{i-1}, C_{-1} = iv (SP 800-38A 6.2): the chaining blocks are the ciphertext moved down by one block
+    std::vector<uint64_t> chain(2 * n_blocks);
+    chain[0] = iv_hi_lo[0]; chain[1] = iv_hi_lo[1];
+    memcpy(chain.data() + 2, ct_hi_lo, 2 * (n_blocks - 1) * sizeof(uint64_t));
+    return aes_public(c, public_inverse(), dec_round_keys, key_bits, 1, nullptr, ct_hi_lo, chain.data(), n_blocks, state_out, memspace);
 }
 
 static void plan_counts(const PublicPlan &pl, uint64_t n_blocks, int nr, uint64_t *unique_bytes_per_round)
@@ -940,7 +1013,7 @@ int fheaes_aes_public_plan(const uint64_t *blocks_hi_lo, uint64_t n_blocks, uint
     const int nr = aes_rounds(key_bits);
     if (!blocks_hi_lo || !unique_bytes_per_round || !nr || n_blocks > PUBLIC_MAX_BLOCKS) return FHEAES_ERR_INVALID;
     PublicPlan pl;
-    if (n_blocks) public_plan(blocks_hi_lo, nullptr, nullptr, n_blocks, nr, pl);
+    if (n_blocks) public_plan(public_forward(), blocks_hi_lo, nullptr, nullptr, n_blocks, nr, pl);
     plan_counts(pl, n_blocks, nr, unique_bytes_per_round);
     return FHEAES_OK;
 }
@@ -953,7 +1026,19 @@ int fheaes_aes_public_plan_keyed(const uint64_t *blocks_hi_lo, const uint32_t *k
         return FHEAES_ERR_INVALID;
     for (uint64_t b = 0; b < n_blocks; ++b) if (key_of_block[b] >= n_keys) return FHEAES_ERR_INVALID;
     PublicPlan pl;
-    if (n_blocks) public_plan(blocks_hi_lo, nullptr, key_of_block, n_blocks, nr, pl);
+    if (n_blocks) public_plan(public_forward(), blocks_hi_lo, nullptr, key_of_block, n_blocks, nr, pl);
+    plan_counts(pl, n_blocks, nr, unique_bytes_per_round);
+    return FHEAES_OK;
+}
+
+int fheaes_aes_decrypt_public_plan_keyed(const uint64_t *blocks_hi_lo, const uint32_t *key_of_block, uint64_t n_blocks, uint64_t n_keys, uint32_t key_bits,
+                                         uint64_t *unique_bytes_per_round)
+{
+    const int nr = aes_rounds(key_bits);
+    if (!blocks_hi_lo || !unique_bytes_per_round || !nr || n_blocks > PUBLIC_MAX_BLOCKS || n_keys == 0 || n_keys > FHEAES_MAX_KEYS) return FHEAES_ERR_INVALID;
+    if (key_of_block) for (uint64_t b = 0; b < n_blocks; ++b) if (key_of_block[b] >= n_keys) return FHEAES_ERR_INVALID;
+    PublicPlan pl;
+    if (n_blocks) public_plan(public_inverse(), blocks_hi_lo, nullptr, key_of_block, n_blocks, nr, pl);
     plan_counts(pl, n_blocks, nr, unique_bytes_per_round);
     return FHEAES_OK;
 }

@@ -5,6 +5,8 @@ Same names, argument meaning and error behaviour as
   (plus aes_decryption_round_keys / aes_decrypt_equivalent: the FIPS-197 section 5.3.5 equivalent inverse cipher; plus AES-192
   and AES-256, which the reference does not have: the same methods read the key size from the leading axis of the key / round keys;
   plus aes_encrypt_public / aes_ctr: public blocks and SP 800-38A CTR with a PUBLIC nonce, every distinct S-Box input evaluated once;
+  plus aes_decrypt_public / aes_cbc_decrypt / aes_cfb_decrypt / aes_gcm_ctr: the decryption direction of the public calls and the
+  modes whose decryption works on public blocks -- CBC, CFB-128 and the 32-bit counter of GCM;
   plus the *_many / *_keyed / aes_ctr_streams methods: many AES keys under one FHE key, round keys [n_keys][Nr+1][16][8][kN+1] and a key
   index per block, word for word the single-key methods key by key; plus packed round keys: pack_round_keys / unpack_round_keys /
   aes_key_expansion_packed, and a PackedRoundKeys -- 3 / 4 / 4 GLWEs per key -- wherever a method takes round keys, the key words read
@@ -97,9 +99,59 @@ def _words(round_keys):
     return round_keys.data if isinstance(round_keys, PackedRoundKeys) else round_keys
 
 
-def ctr_stream_blocks(streams):
+def _u128(v, what: str) -> int:
+    v = int.from_bytes(v, "big") if isinstance(v, (bytes, bytearray)) else int(v)
+    if not 0 <= v < 1 << 128:
+        raise ValueError("%s is a 128-bit value" % what)
+    return v
+
+
+def _cipher_blocks(ciphertext):
+    """a ciphertext as a list of blocks (ints or 16 bytes each); one `bytes` of whole blocks is cut into blocks"""
+    if isinstance(ciphertext, (bytes, bytearray)):
+        if len(ciphertext) % 16:
+            raise ValueError("a ciphertext of whole 16-byte blocks is expected, got %d bytes" % len(ciphertext))
+        return [bytes(ciphertext[i:i + 16]) for i in range(0, len(ciphertext), 16)]
+    return list(ciphertext)
+
+
+def _check_counter_bits(counter_bits):
+    if counter_bits not in (32, 128):
+        raise ValueError("counter_bits must be 32 (the counter field of GCM) or 128 (SP 800-38A), got %r" % (counter_bits,))
+
+
+def gcm_ctr_args(iv, data, n_blocks, first_block: int = 0):
+    """aes_gcm_ctr's arguments -> (J0 = iv || 00000001, n_blocks, data blocks or None)"""
+    if not isinstance(iv, (bytes, bytearray)) or len(iv) != 12:
+        raise ValueError("aes_gcm_ctr takes a 12-byte IV: any other length derives J0 with GHASH, which is not offered")
+    if int(first_block) < 0:
+        raise ValueError("first_block must be >= 0")
+    if n_blocks is None:
+        if data is None:
+            raise ValueError("n_blocks or data is needed")
+        data = _cipher_blocks(data)
+        n_blocks = len(data)
+    return int.from_bytes(bytes(iv) + b"\x00\x00\x00\x01", "big"), int(n_blocks), _data_blocks(data, int(n_blocks))
+
+
+def cbc_stream_blocks(streams):
+    """CBC streams (key_index, iv, ciphertext) -> (key per block, ciphertext blocks, chaining blocks): block i of a stream is chained with
+    block i - 1 of the same stream, the first with its iv"""
+    key_of_block, blocks, chain = [], [], []
+    for key_index, iv, ciphertext in streams:
+        ct = _cipher_blocks(ciphertext)
+        key_of_block += [int(key_index)] * len(ct)
+        blocks += ct
+        chain += ([_u128(iv, "iv")] + ct[:-1])[:len(ct)]
+    return key_of_block, blocks, chain
+
+
+def ctr_stream_blocks(streams, counter_bits: int = 128):
     """CTR streams (key_index, iv, first_block, n_blocks, data_or_None) -> (key per block, counter blocks, data blocks or None), the
-    counters (iv + first_block + i) mod 2^128 as aes_ctr builds them; a stream without data contributes zero blocks of data"""
+    counters (iv + first_block + i) mod 2^128 as aes_ctr builds them (counter_bits = 32: only the low 32 bits of iv count); a stream
+    without data contributes zero blocks of data"""
+    _check_counter_bits(counter_bits)
+    m = 1 << counter_bits
     key_of_block, blocks, data, any_data = [], [], [], False
     for key_index, iv, first_block, n_blocks, d in streams:
         n_blocks, first_block = int(n_blocks), int(first_block)
@@ -111,7 +163,7 @@ def ctr_stream_blocks(streams):
         d = _data_blocks(d, n_blocks)
         any_data = any_data or d is not None
         key_of_block += [int(key_index)] * n_blocks
-        blocks += [(iv + first_block + i) % (1 << 128) for i in range(n_blocks)]
+        blocks += [(iv & ~(m - 1)) | ((iv + first_block + i) & (m - 1)) for i in range(n_blocks)]
         data += [0] * n_blocks if d is None else d
     return key_of_block, blocks, data if any_data else None
 
@@ -249,12 +301,14 @@ class Server:
         self.engine.aes_encrypt_public_bits(encrypted_round_keys, bits, blocks, out)
         return out
 
-    def aes_ctr(self, encrypted_round_keys, iv, first_block: int, n_blocks: int, data=None, out=None):
+    def aes_ctr(self, encrypted_round_keys, iv, first_block: int, n_blocks: int, data=None, out=None, counter_bits: int = 128):
         """SP 800-38A CTR with a PUBLIC nonce: block i = E_K((iv + first_block + i) mod 2^128) ^ data[i] as a new [n_blocks][16][8][kN+1]
-        (data None: the keystream).  `iv`: an int or 16 bytes; `data`: n_blocks ints / 16-byte blocks, or one `bytes` of 16 n_blocks."""
+        (data None: the keystream).  `iv`: an int or 16 bytes; `data`: n_blocks ints / 16-byte blocks, or one `bytes` of 16 n_blocks.
+        counter_bits = 32: only the low 32 bits of `iv` count, mod 2^32, and the upper 96 never change (the counter field of GCM)."""
+        _check_counter_bits(counter_bits)
         if isinstance(encrypted_round_keys, PackedRoundKeys):
             self._check_packed(encrypted_round_keys, one_key=True)
-            return self.aes_ctr_streams(encrypted_round_keys, [(0, iv, first_block, n_blocks, data)], out=out)
+            return self.aes_ctr_streams(encrypted_round_keys, [(0, iv, first_block, n_blocks, data)], out=out, counter_bits=counter_bits)
         bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         n_blocks, first_block = int(n_blocks), int(first_block)
         if n_blocks < 0 or first_block < 0:
@@ -262,12 +316,62 @@ class Server:
         iv = int.from_bytes(iv, "big") if isinstance(iv, (bytes, bytearray)) else int(iv)
         if not 0 <= iv < 1 << 128:
             raise ValueError("iv is a 128-bit value")
-        if first_block >> 64:                    # the C ABI takes a 64-bit block index; the counter is mod 2^128 anyway
+        if counter_bits == 32:
+            first_block &= 2 ** 32 - 1           # the counter is mod 2^32
+        elif first_block >> 64:                  # the C ABI takes a 64-bit block index; the counter is mod 2^128 anyway
             iv, first_block = (iv + (first_block >> 64 << 64)) % (1 << 128), first_block & (2 ** 64 - 1)
         data = _data_blocks(data, n_blocks)
         out = self._public_out(encrypted_round_keys, n_blocks, out)
-        self.engine.aes_ctr_bits(encrypted_round_keys, bits, iv, first_block, data, n_blocks, out)
+        self.engine.aes_ctr_bits(encrypted_round_keys, bits, iv, first_block, data, n_blocks, out, counter_bits=counter_bits)
         return out
+
+    def aes_gcm_ctr(self, encrypted_round_keys, iv, data=None, n_blocks=None, first_block: int = 0, out=None):
+        """The CTR part of AES-GCM (SP 800-38D GCTR) for a 12-byte IV: J0 = iv || 00000001 and data block first_block + i is
+        E_K(inc32^(first_block + i + 1)(J0)) ^ data[i] (data None: n_blocks blocks of keystream).  GHASH and the tag are NOT computed: the
+        caller authenticates the ciphertext before it gets here, or not at all."""
+        j0, n_blocks, data = gcm_ctr_args(iv, data, n_blocks, first_block)
+        return self.aes_ctr(encrypted_round_keys, j0, int(first_block) + 1, n_blocks, data=data, out=out, counter_bits=32)
+
+    # ---- the decryption direction of the public calls: CBC and any mode that deciphers public blocks ----------
+    def aes_decrypt_public(self, dec_round_keys, blocks, data=None, out=None):
+        """aes_decrypt_equivalent of PUBLIC blocks (ints, or 16 `bytes` each) under encrypted decryption round keys
+        (aes_decryption_round_keys): a new [n][16][8][kN+1] (or `out`), word for word aes_decrypt_equivalent(dec_round_keys,
+        Client.trivial_bytes(blocks)) with the clear `data` blocks (as aes_ctr's) added in the last layer; every distinct S-Box input of the
+        batch is evaluated once (include/fheaes.h: fheaes_aes_decrypt_public_bits)."""
+        blocks = list(blocks)
+        if isinstance(dec_round_keys, PackedRoundKeys):
+            self._check_packed(dec_round_keys, one_key=True)
+            return self.aes_decrypt_public_keyed(dec_round_keys, [0] * len(blocks), blocks, data=data, out=out)
+        bits = _key_bits(dec_round_keys, ROUND_KEYS_TO_BITS, "decryption round keys")
+        data = _data_blocks(data, len(blocks))
+        out = self._public_out(dec_round_keys, len(blocks), out)
+        self.engine.aes_decrypt_public_bits(dec_round_keys, bits, blocks, data, out)
+        return out
+
+    def aes_cbc_decrypt(self, dec_round_keys, iv, ciphertext, out=None):
+        """SP 800-38A CBC decryption of a PUBLIC ciphertext: block i = D_K(C_i) ^ (i ? C_{i-1} : iv) as a new [n][16][8][kN+1].  `iv`: an
+        int or 16 bytes; `ciphertext`: ints / 16-byte blocks, or one `bytes` of whole blocks.  To continue a stream pass the last ciphertext
+        block of the part before as `iv`.  CBC encryption is serial (every block waits for the one before) and is not offered."""
+        ct = _cipher_blocks(ciphertext)
+        if isinstance(dec_round_keys, PackedRoundKeys):
+            self._check_packed(dec_round_keys, one_key=True)
+            return self.aes_cbc_streams(dec_round_keys, [(0, iv, ct)], out=out)
+        bits = _key_bits(dec_round_keys, ROUND_KEYS_TO_BITS, "decryption round keys")
+        out = self._public_out(dec_round_keys, len(ct), out)
+        self.engine.aes_cbc_decrypt_bits(dec_round_keys, bits, _u128(iv, "iv"), ct, out)
+        return out
+
+    def aes_cfb_decrypt(self, encrypted_round_keys, iv, ciphertext, out=None):
+        """SP 800-38A CFB-128 decryption of a PUBLIC ciphertext: block i = E_K(i ? C_{i-1} : iv) ^ C_i -- the FORWARD cipher on public
+        blocks, so it takes the encryption round keys: aes_encrypt_public_keyed with blocks [iv, C_0, ..] and data C."""
+        ct = _cipher_blocks(ciphertext)
+        blocks = ([_u128(iv, "iv")] + ct[:-1])[:len(ct)]
+        if isinstance(encrypted_round_keys, PackedRoundKeys):
+            rk = self._check_packed(encrypted_round_keys, one_key=True)
+        else:
+            _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
+            rk = encrypted_round_keys[None]
+        return self.aes_encrypt_public_keyed(rk, [0] * len(ct), blocks, data=ct, out=out)
 
     # ---- many AES keys under one FHE key ----------------------------------------------
     def aes_key_expansion_many(self, keys, out=None):
@@ -335,12 +439,34 @@ class Server:
         self.engine.aes_public_keyed(round_keys, bits, n_keys, list(key_of_block), blocks, _data_blocks(data, len(blocks)), out)
         return out
 
-    def aes_ctr_streams(self, round_keys, streams, out=None):
+    def aes_ctr_streams(self, round_keys, streams, out=None, counter_bits: int = 128):
         """several SP 800-38A CTR streams with PUBLIC nonces under several keys in one call: `streams` is a list of
         (key_index, iv, first_block, n_blocks, data_or_None), each as the arguments of aes_ctr; returns the streams' blocks concatenated in
-        order, [sum n_blocks][16][8][kN+1], each stream's word for word aes_ctr(round_keys[key_index], iv, first_block, n_blocks, data)."""
-        key_of_block, blocks, data = ctr_stream_blocks(streams)
+        order, [sum n_blocks][16][8][kN+1], each stream's word for word aes_ctr(round_keys[key_index], iv, first_block, n_blocks, data).
+        counter_bits as aes_ctr's, one value for all streams."""
+        key_of_block, blocks, data = ctr_stream_blocks(streams, counter_bits)
         return self.aes_encrypt_public_keyed(round_keys, key_of_block, blocks, data=data, out=out)
+
+    def aes_decrypt_public_keyed(self, dec_round_keys, key_of_block, blocks, data=None, out=None):
+        """aes_decrypt_public with a key per block; dec_round_keys from aes_decryption_round_keys_many, or a PackedRoundKeys of them."""
+        blocks = list(blocks)
+        if isinstance(dec_round_keys, PackedRoundKeys):
+            prk = self._check_packed(dec_round_keys)
+            words, bits, n_keys = prk.data, prk.key_bits, prk.n_keys
+        else:
+            words = dec_round_keys
+            bits, n_keys = _many_key_bits(dec_round_keys, "decryption round keys")
+        data = _data_blocks(data, len(blocks))
+        out = self._public_out(words, len(blocks), out)
+        self.engine.aes_public_keyed(words, bits, n_keys, list(key_of_block), blocks, data, out, packed=words is not dec_round_keys, inverse=True)
+        return out
+
+    def aes_cbc_streams(self, dec_round_keys, streams, out=None):
+        """several CBC ciphertexts under several keys in one call: `streams` is a list of (key_index, iv, ciphertext), each as the arguments
+        of aes_cbc_decrypt; returns the streams' blocks concatenated in order, each stream's word for word
+        aes_cbc_decrypt(dec_round_keys[key_index], iv, ciphertext)."""
+        key_of_block, blocks, chain = cbc_stream_blocks(streams)
+        return self.aes_decrypt_public_keyed(dec_round_keys, key_of_block, blocks, data=chain, out=out)
 
     def _public_out(self, round_keys, n_blocks: int, out):
         return self._many_out(round_keys, (n_blocks, 16, 8, self.params.big1), out)
@@ -549,12 +675,38 @@ class ServerGroup:
         blocks = list(blocks)
         return self._fan_out_new(round_keys, len(blocks), lambda s, shard, lo, k: s.aes_encrypt_public(round_keys, blocks[lo:lo + k], out=shard))
 
-    def aes_ctr(self, round_keys, iv, first_block: int, n_blocks: int, data=None):
+    def aes_ctr(self, round_keys, iv, first_block: int, n_blocks: int, data=None, counter_bits: int = 128):
         """Server.aes_ctr: context i takes the counter blocks of its shard (first_block + lo ..) and the matching data"""
+        _check_counter_bits(counter_bits)
         n_blocks = int(n_blocks)
         data = _data_blocks(data, n_blocks)
-        return self._fan_out_new(round_keys, n_blocks, lambda s, shard, lo, k: s.aes_ctr(round_keys, iv, int(first_block) + lo, k,
-                                                                                        None if data is None else data[lo:lo + k], out=shard))
+        return self._fan_out_new(round_keys, n_blocks, lambda s, shard, lo, k: s.aes_ctr(
+            round_keys, iv, int(first_block) + lo, k, None if data is None else data[lo:lo + k], out=shard, counter_bits=counter_bits))
+
+    def aes_gcm_ctr(self, round_keys, iv, data=None, n_blocks=None, first_block: int = 0):
+        """Server.aes_gcm_ctr: context i takes the data blocks first_block + lo .. of its shard"""
+        _, n_blocks, data = gcm_ctr_args(iv, data, n_blocks, first_block)
+        return self._fan_out_new(round_keys, n_blocks, lambda s, shard, lo, k: s.aes_gcm_ctr(
+            round_keys, iv, None if data is None else data[lo:lo + k], k, int(first_block) + lo, out=shard))
+
+    def aes_decrypt_public(self, dec_round_keys, blocks, data=None):
+        """Server.aes_decrypt_public, the blocks sharded contiguously; each context plans the sharing inside its own shard"""
+        blocks = list(blocks)
+        data = _data_blocks(data, len(blocks))
+        return self._fan_out_new(dec_round_keys, len(blocks), lambda s, shard, lo, k: s.aes_decrypt_public(
+            dec_round_keys, blocks[lo:lo + k], data=None if data is None else data[lo:lo + k], out=shard))
+
+    def aes_cbc_decrypt(self, dec_round_keys, iv, ciphertext):
+        """Server.aes_cbc_decrypt: a shard that starts at block lo > 0 chains its first block with C_{lo-1}"""
+        ct = _cipher_blocks(ciphertext)
+        return self._fan_out_new(dec_round_keys, len(ct), lambda s, shard, lo, k: s.aes_cbc_decrypt(
+            dec_round_keys, ct[lo - 1] if lo else iv, ct[lo:lo + k], out=shard))
+
+    def aes_cfb_decrypt(self, round_keys, iv, ciphertext):
+        """Server.aes_cfb_decrypt: a shard that starts at block lo > 0 enciphers C_{lo-1} first"""
+        ct = _cipher_blocks(ciphertext)
+        return self._fan_out_new(round_keys, len(ct), lambda s, shard, lo, k: s.aes_cfb_decrypt(
+            round_keys, ct[lo - 1] if lo else iv, ct[lo:lo + k], out=shard))
 
     def aes_key_expansion(self, key):
         return self.servers[0].aes_key_expansion(key)
@@ -602,9 +754,24 @@ class ServerGroup:
         return self._fan_out_new(round_keys, len(blocks), lambda s, shard, lo, k: s.aes_encrypt_public_keyed(
             round_keys, kob[lo:lo + k], blocks[lo:lo + k], data=None if data is None else data[lo:lo + k], out=shard))
 
-    def aes_ctr_streams(self, round_keys, streams):
-        key_of_block, blocks, data = ctr_stream_blocks(streams)
+    def aes_ctr_streams(self, round_keys, streams, counter_bits: int = 128):
+        key_of_block, blocks, data = ctr_stream_blocks(streams, counter_bits)
         return self.aes_encrypt_public_keyed(round_keys, key_of_block, blocks, data=data)
+
+    def aes_decrypt_public_keyed(self, dec_round_keys, key_of_block, blocks, data=None):
+        """Server.aes_decrypt_public_keyed, the blocks sharded contiguously; each context plans the sharing inside its own shard"""
+        kob, blocks = list(key_of_block), list(blocks)
+        data = _data_blocks(data, len(blocks))
+        if len(kob) != len(blocks):
+            raise ValueError("one key index per block expected")
+        return self._fan_out_new(dec_round_keys, len(blocks), lambda s, shard, lo, k: s.aes_decrypt_public_keyed(
+            dec_round_keys, kob[lo:lo + k], blocks[lo:lo + k], data=None if data is None else data[lo:lo + k], out=shard))
+
+    def aes_cbc_streams(self, dec_round_keys, streams):
+        """Server.aes_cbc_streams: the chaining blocks are built before the blocks are sharded, so a shard boundary inside a stream
+        chains with the block before it"""
+        key_of_block, blocks, chain = cbc_stream_blocks(streams)
+        return self.aes_decrypt_public_keyed(dec_round_keys, key_of_block, blocks, data=chain)
 
     # packed round keys: a store is small, so every context reads the whole of it (as the keyed calls read all round keys); the cipher
     # methods above take a PackedRoundKeys wherever they take round keys, since every context's Server does
