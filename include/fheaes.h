@@ -364,7 +364,9 @@ int fheaes_expand_lwe_seeded(fheaes_ctx *ctx, const uint32_t *mask_key, uint64_t
  *
  * Noise: each word moves by at most 2^(63-w), uniformly; the phase of a coefficient moves by a sum over the body and the h set key bits:
  *   variance (1 + h) 2^(2(64-w)) / 12,   hard bound (1 + h) 2^(63-w).
- * At PARAM_OPT (h about 1,024) and w = 16: std 2^51.2, bound 2^57.0 (below 2^58), against a WoPBS output noise below std 2^56 / max 2^59 and a decoding
+ * At PARAM_OPT (h about 1,024) and w = 16: std 2^51.2, bound 2^57.0 (below 2^58), against a WoPBS output noise of std 2^53.8 (2^54.3 for an AES
+ * output word, a fresh output plus a round-key word; derived from the parameter set in tests/noise_model.py, which the tests hold the oracle
+ * and the kernels to, eight sigma at most per word) and a decoding
  * margin of 2^62 -- w = 16 cannot flip a bit that was decodable with that room (the default of the Python layer).  Smaller widths are the
  * caller's arithmetic, as summed ciphertexts are for the noise guard; words carry no noise metadata.
  *
@@ -398,7 +400,7 @@ int fheaes_unpack_bits_mod(fheaes_ctx *ctx, const uint64_t *in, uint64_t m, uint
  * writes when given fheaes_unpack_round_keys of the same store.
  *
  * Noise: a key word read from the packed form carries the key's noise plus the packing's (std 2^33.5 at PARAM_OPT against a nominal
- * 2^56); it counts as NOMINAL for the noise guard, exactly as fheaes_unpack_bits outputs do, and the guard sees the counts of the
+ * 2^53.8, the WoPBS output noise of tests/noise_model.py); it counts as NOMINAL for the noise guard, exactly as fheaes_unpack_bits outputs do, and the guard sees the counts of the
  * unpacked schedules.  All of it is accounted under FHEAES_STAGE_LINEAR, the packing's matrix product under FHEAES_STAGE_PFPKS. */
 /* G: 3 / 4 / 4 for key_bits 128 / 192 / 256, 0 for anything else (host logic only, no context, no GPU) */
 uint32_t fheaes_round_keys_packed_glwes(uint32_t key_bits);

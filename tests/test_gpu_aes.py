@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import Kit, sha
-from gpu_support import dev, host, opt_server, toy_server  # noqa: F401
+from gpu_support import dev, host, opt_server, tc, toy_server  # noqa: F401
 from oracle import oracle as orc
 from tfhe_aes_amd import PARAM_TOY, aes_clear
 from tfhe_aes_amd.server import Server, gen_lut
@@ -273,3 +273,44 @@ def test_noise_guard_counts_what_the_schedule_sums(toy, toy_server):
     assert toy_server.engine.noise_level_seen() == (5, 5)
     toy_server.aes_decrypt(rk, c.encrypt_u128(1))
     assert toy_server.engine.noise_level_seen() == (5, 5)
+
+
+# ---- the counter add: every carry, the high word, the wrap ----------------------------------------------------------------------------------
+ALL_ONES = (1 << 128) - 1
+HIGH = (0x0123456789ABCDEF << 64) | 0x00FF00FF00FF00FF
+# (state, addend): a ripple through all sixteen bytes and the wrap mod 2^128, one and two past the top; a carry that stops at the fifth
+# byte; addends whose high word is not zero (the host fill of the `hi` bytes in add_scalar_dev); the addend 0
+ADD_CASES = [(ALL_ONES, 1), (ALL_ONES, 2), (0x00FFFFFFFF, 1), (0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF, 1 << 64),
+             (0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF, (1 << 127) | 1), (0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF, HIGH), (HIGH, 0)]
+
+
+@pytest.mark.parametrize("state,addend", ADD_CASES, ids=["ones+1", "ones+2", "ffffffff+1", "1<<64", "1<<127|1", "high", "zero"])
+def test_add_scalar_carries_high_words_and_wrap(toy, toy_server, tc, state, addend):
+    """Server.add_scalar on a host array and on a device tensor: the plaintext against Python integers, the words against the oracle"""
+    st = tc.encrypt_u128(state)
+    want = toy.oracle.add_scalar(st, addend)
+    assert tc.decrypt_u128(want) == (state + addend) & ALL_ONES
+    got = toy_server.add_scalar(st.copy(), addend)
+    assert tc.decrypt_u128(got) == (state + addend) & ALL_ONES
+    assert np.array_equal(got, want)
+    d_st = dev(st)
+    toy_server.add_scalar(d_st, addend)
+    toy_server.synchronize()
+    assert np.array_equal(host(d_st), want)
+
+
+def test_add_scalar_five_blocks_five_counters(toy, toy_server, tc):
+    """one batch of five blocks, five different counters: the byte tables are 5 entries long, so the carry slot sits behind a table whose
+    length is no multiple of 64, and every block has per-block LUTs of its own (counter_lut_kernel)"""
+    states = [ALL_ONES, 0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF, 0x00FFFFFFFF, HIGH, ALL_ONES]
+    addends = [2, HIGH, 1, (1 << 127) | 1, 1 << 64]
+    st = np.stack([tc.encrypt_u128(v) for v in states])
+    want = np.stack([toy.oracle.add_scalar(st[b], a) for b, a in enumerate(addends)])
+    got = toy_server.add_scalar(st.copy(), addends)
+    d_st = dev(st)
+    toy_server.add_scalar(d_st, addends)
+    toy_server.synchronize()
+    for b, (v, a) in enumerate(zip(states, addends)):
+        assert tc.decrypt_u128(got[b]) == (v + a) & ALL_ONES, b
+        assert np.array_equal(got[b], want[b]), b
+    assert np.array_equal(host(d_st), want)

@@ -75,6 +75,17 @@ def test_ctr_counter_add_param_opt(opt, opt_server):
     assert c.decrypt_u128(st[1]) == (IV + 0xFFFFFFFF) % (1 << 128)
 
 
+def test_ctr_counter_add_high_word_param_opt(opt, opt_server):
+    """a counter whose high word is not zero, with a carry out of the low word, at the reference's parameter set: the plaintext against
+    Python integers, the words against the oracle"""
+    c = opt.client
+    counter = (0x0123456789ABCDEF << 64) | 0x00FF00FF00FF00FF
+    st = c.encrypt_u128(IV)
+    got = opt_server.add_scalar(st.copy(), counter)
+    assert c.decrypt_u128(got) == (IV + counter) % (1 << 128)
+    assert np.array_equal(got, opt.oracle.add_scalar(st, counter))
+
+
 def test_1024_ctr_blocks_on_one_gpu(opt, opt_server):
     """BASELINE configs[3] total size (1,024 CTR blocks) on ONE GPU: 131,072 bits per round, processed in four
     workspace chunks; every block must decrypt to AES-CTR (the 8-GPU run shards the same stream 128 per GPU)."""
