@@ -149,6 +149,13 @@ int fheaes_forward_fourier_batch(fheaes_ctx *ctx, const uint64_t *polys_in, uint
 int fheaes_vertical_packing_batch(fheaes_ctx *ctx, const double *ggsw_fourier, uint64_t n_inputs, uint32_t bits,
                                   const uint64_t *luts, uint32_t n_luts, int lut_per_input, uint64_t *lwe_out, int memspace);
 
+/* K6  one linear layer alone: InvMixColumns as Server::aes_decrypt takes it (inv_mix_columns.rs:4-58), the four-term gather WITHOUT a
+ *     round key.  multiples [n_blocks][16][4][8][kN+1] = fheaes_many_sbox(.., inv = 1) of the state's bytes ({9x, 11x, 13x, 14x});
+ *     state_out [n_blocks][16][8][kN+1], byte 4 col + row = sum over j of (InvMixColumns[row][j] x) of byte 4 col + j, wrapping sums of
+ *     four words (declared to the noise guard as 4).  n_blocks <= 65,535; needs no keys; overlapping buffers are FHEAES_ERR_INVALID.
+ *     Accounted under FHEAES_STAGE_LINEAR (units: blocks).  The yardstick of the other K6 kernels (tools/xts.py). */
+int fheaes_inv_mix_columns_batch(fheaes_ctx *ctx, const uint64_t *multiples, uint64_t n_blocks, uint64_t *state_out, int memspace);
+
 /* ---- the plugin API of the path ------------------------------------------------ */
 /* many_wopbs_without_padding (many_wopbs.rs:31), batched over radix inputs.
  *   lwe_in [n_inputs][bits][kN+1], bits in {1..16}; luts as above; out [n_inputs][n_luts][bits][kN+1]. */
@@ -250,6 +257,57 @@ int fheaes_aes_decrypt_public_bits(fheaes_ctx *ctx, const uint64_t *dec_round_ke
  * previous ciphertext block as iv.  Equal ciphertext blocks share their S-Boxes; CBC ENCRYPTION is serial and is not offered. */
 int fheaes_aes_cbc_decrypt_bits(fheaes_ctx *ctx, const uint64_t *dec_round_keys, uint32_t key_bits, const uint64_t *iv_hi_lo,
                                 const uint64_t *ct_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace);
+/* XTS-AES decryption (IEEE 1619, SP 800-38E: disk images, volume snapshots, encrypted block storage) of a PUBLIC ciphertext under two
+ * encrypted keys: P_j = D_K1(C_j ^ T_j) ^ T_j with T_j = E_K2(tweak) * alpha^j in GF(2^128), j the block's index in its data unit.  As
+ * parallel as CBC decryption, but the per-block mask T_j is ENCRYPTED, so C_j ^ T_j is not public and the public path serves the tweak
+ * blocks only.
+ *
+ * The field: bit b (LSB first) of block byte p is degree 8p + b, which is the flattened [16][8] index of a state -- no permutation.
+ * Multiplication by alpha^j is linear over GF(2) and XOR of MSB-encoded bits is the wrapping add, so T * alpha^j is ONE gather: for
+ * 0 <= j <= 121 output bit i sums bit i - j (if i >= j) and bits 128 - j + m for m in {i, i-1, i-2, i-7} with 0 <= m < j (the bits
+ * shifted out, reduced once by x^128 = x^7 + x^2 + x + 1): distinct sources, at most 4.  (Beyond 121 a shifted-out bit is reduced
+ * twice: weight 5 at 122.)  The rows are applied to the base in one sum: doubling step by step adds a ciphertext to itself, which
+ * cancels the message but not the noise.
+ *
+ * Levels against FHEAES_MAX_NOISE_LEVEL = 5: E_K2(tweak) leaves the public call at 2 and an identity WoPBS makes it 1 (the ANCHOR of
+ * the unit); the gather gives T_j at up to 4.  Raw on both sides of the cipher that passes going in (4 + dw[Nr] = 5) and fails coming out
+ * (InvS + dw[0] + 4 = 6), so every T_j is refreshed by an identity WoPBS, 16 byte-WoPBS per block: 2 going in, 3 coming out, and
+ * 16 (Nr + 1) byte-WoPBS per block in all (176 for AES-128).  A unit longer than 120 blocks is cut into segments of 120: segment s
+ * gathers offsets 0 .. 119 from anchor s, and offset 120 as well when the call reaches beyond the segment: refreshed, that is anchor
+ * s + 1.  Block j takes offset j % 120 of segment j / 120; a unit costs ceil(blocks / 120) serial refreshes after its anchor's, and a
+ * segment that lies wholly before the call's first block yields its anchor only.
+ *
+ * dec_round_keys1: fheaes_aes_decryption_round_keys_bits of key 1; round_keys2: the plain expansion of key 2; both [Nr+1][16][8][kN+1];
+ * key_bits 128 or 256 (XTS-AES-128 / -256: two keys of that size; 192 is FHEAES_ERR_INVALID).  tweaks_hi_lo: n_units (hi, lo) pairs, the
+ * 16-byte tweak BLOCK of every unit as every clear block here: byte 0 the most significant byte of the u128 -- which is the LEAST
+ * significant byte of IEEE 1619's little-endian data-unit number.  ct_hi_lo: n_blocks pairs.  Block b of the call is block
+ * (first_block + b) % blocks_per_unit of unit (first_block + b) / blocks_per_unit, so a shard or a continued stream starts anywhere;
+ * n_units must cover the blocks named; blocks_per_unit is 1 .. 2^20 (the IEEE bound).  n_blocks = 0 is FHEAES_OK; null or overlapping
+ * buffers are FHEAES_ERR_INVALID; FHEAES_DEVICE calls only enqueue.  Equal tweaks share their S-Boxes by the public rule.  The result is
+ * word for word: fheaes_aes_encrypt_public_bits(round_keys2, tweaks), the identity WoPBS, the rows above as wrapping sums, the identity
+ * WoPBS chained through the anchors, + trivial(C), fheaes_aes_decrypt_equivalent_bits(dec_round_keys1), + T.
+ * Not offered: ciphertext stealing (whole blocks only), XTS encryption, a key per block or unit. */
+int fheaes_aes_xts_decrypt_bits(fheaes_ctx *ctx, const uint64_t *dec_round_keys1, const uint64_t *round_keys2, uint32_t key_bits,
+                                const uint64_t *tweaks_hi_lo, uint64_t n_units, uint64_t blocks_per_unit, uint64_t first_block,
+                                const uint64_t *ct_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace);
+/* The same with the two key sets as one-key packed stores (fheaes_pack_round_keys, below): word for word the call above on
+ * fheaes_unpack_round_keys of the stores. */
+int fheaes_aes_xts_decrypt_packed(fheaes_ctx *ctx, const uint64_t *packed_dec_round_keys1, const uint64_t *packed_round_keys2, uint32_t key_bits,
+                                  const uint64_t *tweaks_hi_lo, uint64_t n_units, uint64_t blocks_per_unit, uint64_t first_block,
+                                  const uint64_t *ct_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace);
+/* The raw gather alone (no refresh, no keys needed): out[u][t] = anchor[u] * alpha^(first_offset + t), anchor [n_units][128][kN+1],
+ * out [n_units][n_offsets][128][kN+1], first_offset + n_offsets - 1 <= 121 and n_offsets >= 1, else FHEAES_ERR_INVALID.  The largest row
+ * weight of the offsets is declared to the noise guard.  Accounted under FHEAES_STAGE_LINEAR (units: tweak blocks). */
+int fheaes_xts_tweaks(fheaes_ctx *ctx, const uint64_t *anchor, uint64_t n_units, uint32_t first_offset, uint32_t n_offsets, uint64_t *out,
+                      int memspace);
+/* The sources of output bit `bit` (< 128) of the multiplication by alpha^offset (offset <= 121): their count in *n_sources, their bit
+ * indices in sources_out[0 .. count), an array of 4 (host logic only, no context, no GPU). */
+int fheaes_xts_tweak_row(uint32_t offset, uint32_t bit, uint32_t *sources_out /* [4] */, uint32_t *n_sources);
+/* What fheaes_aes_xts_decrypt_bits runs for a call of this shape (host logic only): `segments` serial tweak refreshes after the anchors',
+ * tweak_refresh_bytes byte-WoPBS of identity refresh (16 per touched unit for its anchor, 16 per gathered tweak: one per block of the
+ * call and one per chained anchor), cipher_bytes = 16 Nr n_blocks, and the largest count the call declares to the noise guard. */
+int fheaes_aes_xts_plan(uint64_t n_units, uint64_t blocks_per_unit, uint64_t first_block, uint64_t n_blocks, uint32_t key_bits,
+                        uint64_t *segments, uint64_t *tweak_refresh_bytes, uint64_t *cipher_bytes, uint32_t *max_terms);
 
 /* ---- many AES keys ---------------------------------------------------------------- */
 /* One FHE key pair, many AES keys (producers, sessions, rotated keys), each reaching the server encrypted under that FHE key: short

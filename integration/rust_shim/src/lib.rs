@@ -106,6 +106,18 @@ extern "C" {
                                    blocks_hi_lo: *const u64, data_hi_lo: *const u64, n_blocks: u64, state_out: *mut u64, memspace: c_int) -> c_int;
     pub fn fheaes_aes_public_plan_keyed(blocks_hi_lo: *const u64, key_of_block: *const u32, n_blocks: u64, n_keys: u64, key_bits: u32,
                                         unique_bytes_per_round: *mut u64) -> c_int;
+    pub fn fheaes_inv_mix_columns_batch(ctx: *mut fheaes_ctx, multiples: *const u64, n_blocks: u64, state_out: *mut u64, memspace: c_int) -> c_int;
+    // XTS-AES decryption of a public ciphertext under two encrypted keys (decryption round keys of key 1, plain expansion of key 2)
+    pub fn fheaes_aes_xts_decrypt_bits(ctx: *mut fheaes_ctx, dec_round_keys1: *const u64, round_keys2: *const u64, key_bits: u32, tweaks_hi_lo: *const u64,
+                                       n_units: u64, blocks_per_unit: u64, first_block: u64, ct_hi_lo: *const u64, n_blocks: u64, state_out: *mut u64,
+                                       memspace: c_int) -> c_int;
+    pub fn fheaes_aes_xts_decrypt_packed(ctx: *mut fheaes_ctx, packed_dec_round_keys1: *const u64, packed_round_keys2: *const u64, key_bits: u32,
+                                         tweaks_hi_lo: *const u64, n_units: u64, blocks_per_unit: u64, first_block: u64, ct_hi_lo: *const u64, n_blocks: u64,
+                                         state_out: *mut u64, memspace: c_int) -> c_int;
+    pub fn fheaes_xts_tweaks(ctx: *mut fheaes_ctx, anchor: *const u64, n_units: u64, first_offset: u32, n_offsets: u32, out: *mut u64, memspace: c_int) -> c_int;
+    pub fn fheaes_xts_tweak_row(offset: u32, bit: u32, sources_out: *mut u32, n_sources: *mut u32) -> c_int;
+    pub fn fheaes_aes_xts_plan(n_units: u64, blocks_per_unit: u64, first_block: u64, n_blocks: u64, key_bits: u32, segments: *mut u64,
+                               tweak_refresh_bytes: *mut u64, cipher_bytes: *mut u64, max_terms: *mut u32) -> c_int;
     // packed ciphertexts: N = 512 bits per GLWE through key block k of the PFPKSK the context holds (no new key), and back
     pub fn fheaes_packed_words(ctx: *const fheaes_ctx, m: u64) -> usize;
     pub fn fheaes_pack_bits(ctx: *mut fheaes_ctx, lwe_in: *const u64, m: u64, glwe_out: *mut u64, memspace: c_int) -> c_int;

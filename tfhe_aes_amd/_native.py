@@ -47,6 +47,7 @@ SIGNATURES = {
     "fheaes_forward_fourier_batch": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_vertical_packing_batch": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_void_p, _c.c_uint32,
                                                  _c.c_int, _c.c_void_p, _c.c_int]),
+    "fheaes_inv_mix_columns_batch": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_wopbs_batch": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_int,
                                       _c.c_void_p, _c.c_int]),
     "fheaes_gen_lut": (_c.c_int, [_c.c_uint32, _u64p, _u64p]),
@@ -69,6 +70,13 @@ SIGNATURES = {
     "fheaes_aes_ctr32_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _c.c_uint64, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_decrypt_public_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_cbc_decrypt_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _u64p, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_xts_decrypt_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_uint32, _u64p, _c.c_uint64, _c.c_uint64, _c.c_uint64, _u64p, _c.c_uint64,
+                                               _c.c_void_p, _c.c_int]),
+    "fheaes_aes_xts_decrypt_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_uint32, _u64p, _c.c_uint64, _c.c_uint64, _c.c_uint64, _u64p, _c.c_uint64,
+                                                 _c.c_void_p, _c.c_int]),
+    "fheaes_xts_tweaks": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_int]),
+    "fheaes_xts_tweak_row": (_c.c_int, [_c.c_uint32, _c.c_uint32, _u32p, _u32p]),
+    "fheaes_aes_xts_plan": (_c.c_int, [_c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_uint32, _u64p, _u64p, _u64p, _u32p]),
     "fheaes_aes_key_expansion_batch": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_decryption_round_keys_batch": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_encrypt_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _c.c_void_p, _c.c_uint64, _c.c_int]),
@@ -272,6 +280,10 @@ class Engine:
         self._check(self._lib.fheaes_vertical_packing_batch(self._h, _ptr(ggsw_fourier)[0], n_inputs, bits, _ptr(luts)[0], n_luts,
                                                             int(bool(lut_per_input)), _ptr(lwe_out)[0], self._space(ggsw_fourier, luts, lwe_out)))
 
+    def inv_mix_columns_batch(self, multiples, n_blocks: int, state_out):
+        """K6 alone: InvMixColumns over many_sbox(.., inv=True) of a state's bytes, [n_blocks][16][4][8][kN+1] -> [n_blocks][16][8][kN+1]"""
+        self._check(self._lib.fheaes_inv_mix_columns_batch(self._h, _ptr(multiples)[0], n_blocks, _ptr(state_out)[0], self._space(multiples, state_out)))
+
     def wopbs_batch(self, lwe_in, n_inputs, bits, luts, n_luts, lut_per_input, lwe_out):
         self._check(self._lib.fheaes_wopbs_batch(self._h, _ptr(lwe_in)[0], n_inputs, bits, _ptr(luts)[0], n_luts, int(bool(lut_per_input)),
                                                  _ptr(lwe_out)[0], self._space(lwe_in, luts, lwe_out)))
@@ -362,6 +374,20 @@ class Engine:
         ivp, cnt = u128_pairs([iv]), u128_pairs(ciphertext)
         self._check(self._lib.fheaes_aes_cbc_decrypt_bits(self._h, _ptr(dec_round_keys)[0], key_bits, ivp.ctypes.data_as(_u64p), cnt.ctypes.data_as(_u64p),
                                                           len(cnt), _ptr(state_out)[0], self._space(dec_round_keys, state_out)))
+
+    # XTS-AES decryption: dec_round_keys1 (key 1, decryption round keys) and round_keys2 (key 2, plain expansion), or two one-key packed
+    # stores; `tweaks`: the 16-byte tweak block of units 0 .. as u128 (byte 0 = MSB), `ciphertext`: the blocks of the call
+    def aes_xts_decrypt_bits(self, dec_round_keys1, round_keys2, key_bits: int, tweaks, blocks_per_unit: int, first_block: int, ciphertext, state_out,
+                             packed: bool = False):
+        twk, cnt = u128_pairs(tweaks), u128_pairs(ciphertext)
+        fn = self._lib.fheaes_aes_xts_decrypt_packed if packed else self._lib.fheaes_aes_xts_decrypt_bits
+        self._check(fn(self._h, _ptr(dec_round_keys1)[0], _ptr(round_keys2)[0], key_bits, twk.ctypes.data_as(_u64p), len(twk), blocks_per_unit, first_block,
+                       cnt.ctypes.data_as(_u64p), len(cnt), _ptr(state_out)[0], self._space(dec_round_keys1, round_keys2, state_out)))
+
+    def xts_tweaks(self, anchor, n_units: int, first_offset: int, n_offsets: int, out):
+        """out[u][t] = anchor[u] * alpha^(first_offset + t), the raw gather (fheaes_xts_tweaks): anchor [n_units][128][kN+1], out
+        [n_units][n_offsets][128][kN+1]; needs no keys"""
+        self._check(self._lib.fheaes_xts_tweaks(self._h, _ptr(anchor)[0], n_units, first_offset, n_offsets, _ptr(out)[0], self._space(anchor, out)))
 
     # many AES keys: round keys [n_keys][Nr+1][16][8][kN+1]; key_of_block (one key index per block) travels as a host uint32 array
     def aes_key_expansion_batch(self, keys, key_bits: int, n_keys: int, round_keys):
@@ -574,6 +600,25 @@ def aes_decrypt_public_plan_keyed(blocks, key_of_block, n_keys: int, key_bits: i
 def aes_decrypt_public_plan(blocks, key_bits: int = 128) -> list[int]:
     """byte-WoPBS per round (rounds 1..Nr) that aes_decrypt_public / aes_cbc_decrypt run for these blocks (host only, no GPU)"""
     return aes_decrypt_public_plan_keyed(blocks, None, 1, key_bits)
+
+
+def xts_tweak_row(offset: int, bit: int) -> list[int]:
+    """the source bits whose sum is output bit `bit` of the multiplication by alpha^offset in GF(2^128), offset <= 121 (fheaes_xts_tweak_row:
+    host only, no GPU)"""
+    src, n = (_c.c_uint32 * 4)(), _c.c_uint32()
+    rc = load_library().fheaes_xts_tweak_row(offset, bit, src, _c.byref(n))
+    if rc != 0:
+        raise FheAesError(rc, "fheaes_xts_tweak_row: offset must be at most 121 and bit below 128")
+    return [int(x) for x in src[:n.value]]
+
+
+def aes_xts_plan(n_units: int, blocks_per_unit: int, first_block: int, n_blocks: int, key_bits: int = 128) -> dict:
+    """fheaes_aes_xts_plan (host only, no GPU): {"segments", "tweak_refresh_bytes", "cipher_bytes", "max_terms"} of an aes_xts_decrypt call"""
+    seg, ref, cip, terms = _c.c_uint64(), _c.c_uint64(), _c.c_uint64(), _c.c_uint32()
+    rc = load_library().fheaes_aes_xts_plan(n_units, blocks_per_unit, first_block, n_blocks, key_bits, _c.byref(seg), _c.byref(ref), _c.byref(cip), _c.byref(terms))
+    if rc != 0:
+        raise FheAesError(rc, "fheaes_aes_xts_plan: key_bits must be 128 or 256, blocks_per_unit in 1..2^20, and n_units cover the blocks")
+    return {"segments": seg.value, "tweak_refresh_bytes": ref.value, "cipher_bytes": cip.value, "max_terms": terms.value}
 
 
 def round_keys_packed_glwes(key_bits: int) -> int:

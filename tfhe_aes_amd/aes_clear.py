@@ -176,6 +176,49 @@ def cfb128_decrypt(key, iv: int, ciphertext) -> list[int]:
     return [aes_encrypt_block(key, prev) ^ c for c, prev in zip(ciphertext, [iv] + ciphertext[:-1])]
 
 
+def xts_tweak_block(sector: int) -> int:
+    """the 16-byte tweak block of IEEE 1619 for data-unit number `sector`, as a u128 with byte 0 the most significant: the number is written
+    little-endian, so its least significant byte is byte 0"""
+    if not 0 <= sector < 1 << 128:
+        raise ValueError("a data-unit number is a 128-bit value")
+    return int.from_bytes(sector.to_bytes(16, "little"), "big")
+
+
+def xts_mul_alpha(t: int, j: int = 1) -> int:
+    """t * alpha^j in GF(2^128) mod x^128 + x^7 + x^2 + x + 1, t the little-endian reading of the block (bit b of byte p = degree 8p + b)"""
+    for _ in range(j):
+        t <<= 1
+        if t >> 128:
+            t = (t & ((1 << 128) - 1)) ^ 0x87
+    return t
+
+
+def _xts(key1, key2, sector: int, data: bytes, first_block: int, cipher) -> bytes:
+    if len(key1) != len(key2) or len(key1) not in (16, 32):
+        raise ValueError("XTS-AES takes two keys of 16 or of 32 bytes")
+    if len(data) % 16:
+        raise ValueError("whole 16-byte blocks are expected (ciphertext stealing is not offered), got %d bytes" % len(data))
+    t = int.from_bytes(aes_encrypt_block(key2, xts_tweak_block(sector)).to_bytes(16, "big"), "little")
+    t = xts_mul_alpha(t, first_block)
+    out = bytearray()
+    for i in range(0, len(data), 16):
+        mask = int.from_bytes(t.to_bytes(16, "little"), "big")
+        out += (cipher(key1, int.from_bytes(data[i:i + 16], "big") ^ mask) ^ mask).to_bytes(16, "big")
+        t = xts_mul_alpha(t)
+    return bytes(out)
+
+
+def xts_encrypt(key1, key2, sector: int, data: bytes, first_block: int = 0) -> bytes:
+    """IEEE 1619 XTS-AES encryption of ONE data unit (whole blocks): C_j = E_K1(P_j ^ T_j) ^ T_j, T_j = E_K2(tweak) * alpha^j; `data` starts
+    at block first_block of the unit"""
+    return _xts(key1, key2, sector, data, first_block, aes_encrypt_block)
+
+
+def xts_decrypt(key1, key2, sector: int, data: bytes, first_block: int = 0) -> bytes:
+    """IEEE 1619 XTS-AES decryption of one data unit: P_j = D_K1(C_j ^ T_j) ^ T_j; first_block continues a stream inside the unit"""
+    return _xts(key1, key2, sector, data, first_block, aes_decrypt_block)
+
+
 def aes128_encrypt_block(key: int, block: int) -> int:
     return aes_encrypt_block(key, block)
 

@@ -1,5 +1,5 @@
 // aes_schedule.h -- the AES schedules of the reference's Server (src/server/server.rs:39-178) on device buffers: encryption, both
-// decryptions, the decryption round keys, the key expansion, add_scalar, and public blocks / CTR with a public nonce.
+// decryptions, the decryption round keys, the key expansion, add_scalar, public blocks / CTR with a public nonce, and XTS decryption.
 #pragma once
 
 static int many_sbox_dev(fheaes_ctx *c, const uint64_t *bytes, uint64_t n_bytes, int set, uint64_t *out)
@@ -375,5 +375,121 @@ static int aes_public_dev(fheaes_ctx *c, const PublicDirection &dir, const KeySe
         if (round > 0) TRY(many_sbox_dev(c, out, pl.layers[round - 1].n, round < nr ? dir.round_set : dir.last_set, vp));
         TRY(launch_gather_indexed(c, vp, round < nr ? dir.round_luts : dir.last_luts, tab + to.head, tab + to.term, to.terms, rk.round(dir.key_round(round, nr), sw), out, to.n));
     }
+    return FHEAES_OK;
+}
+
+// ---- XTS-AES decryption (IEEE 1619, SP 800-38E) -------------------------------------------------
+// P_j = D_K1(C_j ^ T_j) ^ T_j, T_j = E_K2(tweak) * alpha^j: the first mode here whose per-block mask is ENCRYPTED, so the public path does
+// not apply to the blocks -- only to the tweak blocks.  Levels against the guard's 5: E_K2(tweak) leaves the public call at 2 (S-Box output +
+// round key) and an identity WoPBS makes it 1: the ANCHOR of a data unit.  One gather (xts_tweak_kernel) gives T_j at up to 4 terms; used
+// raw on both sides of the cipher it would pass going in (4 + dw[Nr] = 5) but not coming out (InvS + dw[0] + 4 = 6), so every T_j is
+// refreshed by an identity WoPBS: 2 going in, 3 coming out.  A gather reaches offset 121, so a unit is cut into segments of XTS_SEGMENT
+// blocks: segment s gathers offsets 0 .. 120 from anchor s, and the refreshed offset 120 -- block 120 (s + 1)'s place, computed for this
+// alone -- is anchor s + 1.  Block j of a unit takes offset j % 120 of segment j / 120.
+#define XTS_SEGMENT 120u
+#define XTS_MAX_BLOCKS_PER_UNIT (1u << 20)      /* IEEE 1619 5.1: a data unit has at most 2^20 blocks */
+
+// The units a call touches fall into at most three classes of consecutive units with the same blocks [a, e): the first, the whole ones
+// between, the last.  Per segment every class is one gather, the classes' outputs lie one behind the other, and one WoPBS refreshes them.
+struct XtsGather { uint64_t unit0, units; uint32_t off0, n_off; uint64_t row0; int64_t anchor_row; uint64_t anchor_stride_rows; };   // rows: tweak blocks
+struct XtsPlan {
+    uint64_t unit0 = 0, units = 0;                      // the units the call touches: unit0 .. unit0 + units - 1
+    std::vector<std::vector<XtsGather>> segments;       // anchor_row < 0: the anchor is row `unit0` of the anchors of segment 0
+    std::vector<uint64_t> seg_row0, seg_rows;           // each segment's rows in the buffer of refreshed tweaks
+    uint64_t rows = 0;
+    std::vector<uint32_t> tweak_of_block;               // the row of every block of the call (want_table)
+};
+
+static bool xts_plan(uint64_t n_units, uint64_t bpu, uint64_t first_block, uint64_t n_blocks, bool want_table, XtsPlan &pl)
+{
+    if (bpu == 0 || bpu > XTS_MAX_BLOCKS_PER_UNIT || first_block + n_blocks < first_block) return false;
+    if (n_blocks == 0) return true;
+    const uint64_t last = first_block + n_blocks - 1, u0 = first_block / bpu, u1 = last / bpu;
+    if (u1 >= n_units) return false;
+    pl.unit0 = u0; pl.units = u1 - u0 + 1;
+    struct Class { uint64_t unit0, units, a, e; };      // unit0 counted from the first touched unit
+    std::vector<Class> cls;
+    auto add = [&](uint64_t unit0, uint64_t units, uint64_t a, uint64_t e) {
+        if (units == 0) return;
+        if (!cls.empty() && cls.back().a == a && cls.back().e == e) cls.back().units += units;      // a whole first or last unit joins the ones between
+        else cls.push_back({unit0, units, a, e});
+    };
+    add(0, 1, first_block % bpu, u1 == u0 ? last % bpu + 1 : bpu);
+    if (u1 > u0) { add(1, u1 - u0 - 1, 0, bpu); add(u1 - u0, 1, 0, last % bpu + 1); }
+    std::vector<uint64_t> prev_row0(cls.size(), 0);
+    std::vector<uint32_t> prev_lo(cls.size(), 0), prev_n(cls.size(), 0);
+    struct Place { uint64_t row0; uint32_t lo, n; };      // [class][segment]: where the class's tweaks of that segment start, and which offsets they are
+    std::vector<std::vector<Place>> place(cls.size());
+    for (uint64_t s = 0;; ++s) {
+        std::vector<XtsGather> gs;
+        const uint64_t seg0 = pl.rows;
+        for (size_t k = 0; k < cls.size(); ++k) {
+            const Class &q = cls[k];
+            const uint64_t segs = (q.e - 1) / XTS_SEGMENT + 1, sa = q.a / XTS_SEGMENT;
+            if (s >= segs) continue;
+            const uint32_t lo = s < sa ? XTS_SEGMENT : s == sa ? (uint32_t)(q.a % XTS_SEGMENT) : 0;
+            const uint32_t hi = s + 1 < segs ? XTS_SEGMENT : (uint32_t)((q.e - 1) % XTS_SEGMENT);
+            XtsGather g{q.unit0, q.units, lo, hi - lo + 1, pl.rows, -1, 1};
+            if (s > 0) { g.anchor_row = (int64_t)(prev_row0[k] + (XTS_SEGMENT - prev_lo[k])); g.anchor_stride_rows = prev_n[k]; }
+            prev_row0[k] = g.row0; prev_lo[k] = lo; prev_n[k] = g.n_off;
+            place[k].push_back({g.row0, lo, g.n_off});
+            pl.rows += g.units * g.n_off;
+            gs.push_back(g);
+        }
+        if (gs.empty()) break;
+        pl.seg_row0.push_back(seg0); pl.seg_rows.push_back(pl.rows - seg0);
+        pl.segments.push_back(std::move(gs));
+    }
+    if (pl.rows > 0xFFFFFFFFull) return false;
+    if (want_table) {
+        pl.tweak_of_block.resize(n_blocks);
+        for (uint64_t b = 0; b < n_blocks; ++b) {
+            const uint64_t g = first_block + b, u = g / bpu - u0, j = g % bpu;
+            size_t k = 0;
+            while (u >= cls[k].unit0 + cls[k].units) ++k;
+            const Place &at = place[k][j / XTS_SEGMENT];
+            pl.tweak_of_block[b] = (uint32_t)(at.row0 + (u - cls[k].unit0) * at.n + (j % XTS_SEGMENT - at.lo));
+        }
+    }
+    return true;
+}
+
+// rk2: the expanded key 2 (the tweak key, forward cipher on the public tweak blocks); dw1: the decryption round keys of key 1.
+// tweaks: the (hi, lo) pairs of units 0 .. ; ct: the n_blocks ciphertext blocks; out [n_blocks][16][8][kN+1].  Workspace: ws_tmp_a the
+// raw tweaks of one segment (and E_K2(tweak) first), ws_tmp_b the refreshed tweaks of the call, ws_tmp_c the anchors of segment 0.
+static int aes_xts_decrypt_dev(fheaes_ctx *c, const KeySets &dw1, const KeySets &rk2, int nr, const uint64_t *tweaks, const XtsPlan &pl, const uint64_t *ct,
+                               uint64_t n_blocks, uint64_t *out)
+{
+    const uint64_t tw = AES_BLOCK_BITS * c->big1;                           // words of one tweak block == of one state
+    uint64_t raw_rows = pl.units;
+    for (uint64_t r : pl.seg_rows) raw_rows = std::max(raw_rows, r);
+    TRY(ensure(c, c->ws_tmp_a, raw_rows * tw * 8));
+    TRY(ensure(c, c->ws_tmp_b, pl.rows * tw * 8));
+    TRY(ensure(c, c->ws_tmp_c, pl.units * tw * 8));
+    uint64_t *raw = (uint64_t *)c->ws_tmp_a.p, *fresh = (uint64_t *)c->ws_tmp_b.p, *anchor0 = (uint64_t *)c->ws_tmp_c.p;
+    {   // E_K2(tweak) of the touched units, equal tweaks shared by the public rule; refreshed: the anchors of segment 0
+        PublicPlan pp;
+        public_plan(public_forward(), tweaks + 2 * pl.unit0, nullptr, nullptr, pl.units, nr, pp);
+        TRY(aes_public_dev(c, public_forward(), rk2, pp, nr, raw));
+        TRY(many_sbox_dev(c, raw, 16 * pl.units, LUTSET_IDENTITY, anchor0));
+    }
+    for (size_t s = 0; s < pl.segments.size(); ++s) {
+        for (const XtsGather &g : pl.segments[s]) {
+            const uint64_t *anchor = g.anchor_row < 0 ? anchor0 + g.unit0 * tw : fresh + (uint64_t)g.anchor_row * tw;
+            TRY(launch_xts_tweaks(c, anchor, g.anchor_stride_rows * tw, g.units, g.off0, g.n_off, raw + (g.row0 - pl.seg_row0[s]) * tw));
+        }
+        TRY(many_sbox_dev(c, raw, 16 * pl.seg_rows[s], LUTSET_IDENTITY, fresh + pl.seg_row0[s] * tw));
+    }
+    // the table of tweak rows and the clear ciphertext bytes, through the pinned buffer (after the public call's tables: same stream)
+    const size_t tab_bytes = n_blocks * sizeof(uint32_t), all_bytes = tab_bytes + 16 * n_blocks;
+    TRY(upload_pinned(c, all_bytes, all_bytes, [&](uint8_t *pin) {
+        memcpy(pin, pl.tweak_of_block.data(), tab_bytes);
+        for (uint64_t b = 0; b < n_blocks; ++b) for (int p = 0; p < 16; ++p) pin[tab_bytes + 16 * b + p] = (uint8_t)u128_byte(ct + 2 * b, p);
+    }));
+    const uint32_t *tab = (const uint32_t *)c->ws_misc.p;
+    const uint8_t *clear = (const uint8_t *)c->ws_misc.p + tab_bytes;
+    TRY(launch_xts_whiten(c, out, nullptr, fresh, tab, clear, n_blocks, 1));                // trivial(C) + T: one nominal term; + dw[Nr] = 2 in the cipher
+    TRY(aes_run_dev(c, dw1, out, n_blocks, aes_decrypt_eq_schedule(nr)));
+    TRY(launch_xts_whiten(c, out, out, fresh, tab, nullptr, n_blocks, 3));                  // InvS output + dw[0] + T
     return FHEAES_OK;
 }

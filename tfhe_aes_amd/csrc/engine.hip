@@ -1043,6 +1043,118 @@ int fheaes_aes_decrypt_public_plan_keyed(const uint64_t *blocks_hi_lo, const uin
     return FHEAES_OK;
 }
 
+// K6 alone: the four-term gather without a round key (table_dec_mix(): InvMixColumns over the {9, 11, 13, 14} multiples), as
+// fheaes_aes_decrypt_bits and the round-key conversion launch it
+int fheaes_inv_mix_columns_batch(fheaes_ctx *c, const uint64_t *multiples, uint64_t n_blocks, uint64_t *state_out, int memspace)
+{
+    CtxLock lock__(c);
+    if (!c) return FHEAES_ERR_INVALID;
+    if (n_blocks == 0) return FHEAES_OK;
+    if (!multiples || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    if (n_blocks > 65535) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most 65,535 (one grid), got %llu", (unsigned long long)n_blocks);
+    const uint64_t out_bytes = n_blocks * 16 * 8 * c->big1 * 8, in_bytes = 4 * out_bytes;
+    if (overlap(multiples, in_bytes, state_out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "multiples and state_out overlap (the gather is not in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    TRY(s.in(multiples, in_bytes, &multiples));
+    TRY(s.out(state_out, out_bytes, &state_out));
+    TRY(launch_gather(c, multiples, 4, KeySets{nullptr, nullptr, 0}, state_out, n_blocks, table_dec_mix()));
+    return s.finish();
+}
+
+// ---- XTS-AES decryption -----------------------------------------------------------------------
+static int aes_xts_decrypt(fheaes_ctx *c, const uint64_t *dec_round_keys1, const uint64_t *round_keys2, uint32_t key_bits, const uint64_t *tweaks_hi_lo,
+                           uint64_t n_units, uint64_t blocks_per_unit, uint64_t first_block, const uint64_t *ct_hi_lo, uint64_t n_blocks, uint64_t *state_out,
+                           int memspace, bool packed)
+{
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!dec_round_keys1 || !round_keys2 || !tweaks_hi_lo || !ct_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    if (key_bits != 128 && key_bits != 256) return c->fail(FHEAES_ERR_INVALID, "XTS-AES has two keys of 128 or 256 bits each (key_bits %u)", key_bits);
+    if (blocks_per_unit == 0 || blocks_per_unit > XTS_MAX_BLOCKS_PER_UNIT)
+        return c->fail(FHEAES_ERR_INVALID, "blocks_per_unit must be in 1..%u (got %llu)", XTS_MAX_BLOCKS_PER_UNIT, (unsigned long long)blocks_per_unit);
+    if (n_blocks == 0) return FHEAES_OK;
+    XtsPlan pl;
+    if (!xts_plan(n_units, blocks_per_unit, first_block, n_blocks, true, pl))
+        return c->fail(FHEAES_ERR_INVALID, "blocks %llu .. of %llu units of %llu blocks: n_units must cover the blocks of the call (and their tweaks number below 2^32)",
+                       (unsigned long long)first_block, (unsigned long long)n_units, (unsigned long long)blocks_per_unit);
+    if (pl.units > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "a call touches at most %llu data units", (unsigned long long)PUBLIC_MAX_BLOCKS);
+    const int nr = aes_rounds(key_bits);
+    const KeyStore ks = key_store(c, key_bits, packed);
+    const uint64_t sw = 16ull * 8 * c->big1, keys_bytes = ks.key_words * 8, out_bytes = n_blocks * sw * 8;
+    if (overlap(dec_round_keys1, keys_bytes, state_out, out_bytes) || overlap(round_keys2, keys_bytes, state_out, out_bytes))
+        return c->fail(FHEAES_ERR_INVALID, "the round keys and state_out overlap");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    TRY(s.in(dec_round_keys1, keys_bytes, &dec_round_keys1));
+    TRY(s.in(round_keys2, keys_bytes, &round_keys2));
+    TRY(s.out(state_out, out_bytes, &state_out));
+    TRY(aes_xts_decrypt_dev(c, KeySets{dec_round_keys1, nullptr, ks.key_words, ks.glwes}, KeySets{round_keys2, nullptr, ks.key_words, ks.glwes}, nr, tweaks_hi_lo, pl,
+                            ct_hi_lo, n_blocks, state_out));
+    return s.finish();
+}
+
+int fheaes_aes_xts_decrypt_bits(fheaes_ctx *c, const uint64_t *dec_round_keys1, const uint64_t *round_keys2, uint32_t key_bits, const uint64_t *tweaks_hi_lo,
+                                uint64_t n_units, uint64_t blocks_per_unit, uint64_t first_block, const uint64_t *ct_hi_lo, uint64_t n_blocks, uint64_t *state_out,
+                                int memspace)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    return aes_xts_decrypt(c, dec_round_keys1, round_keys2, key_bits, tweaks_hi_lo, n_units, blocks_per_unit, first_block, ct_hi_lo, n_blocks, state_out, memspace, false);
+}
+
+int fheaes_aes_xts_decrypt_packed(fheaes_ctx *c, const uint64_t *packed_dec_round_keys1, const uint64_t *packed_round_keys2, uint32_t key_bits,
+                                  const uint64_t *tweaks_hi_lo, uint64_t n_units, uint64_t blocks_per_unit, uint64_t first_block, const uint64_t *ct_hi_lo,
+                                  uint64_t n_blocks, uint64_t *state_out, int memspace)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    return aes_xts_decrypt(c, packed_dec_round_keys1, packed_round_keys2, key_bits, tweaks_hi_lo, n_units, blocks_per_unit, first_block, ct_hi_lo, n_blocks, state_out,
+                           memspace, true);
+}
+
+int fheaes_xts_tweaks(fheaes_ctx *c, const uint64_t *anchor, uint64_t n_units, uint32_t first_offset, uint32_t n_offsets, uint64_t *out, int memspace)
+{
+    CtxLock lock__(c);
+    if (!c) return FHEAES_ERR_INVALID;
+    if (n_offsets == 0 || first_offset > XTS_MAX_OFFSET || n_offsets > XTS_MAX_OFFSET + 1 - first_offset)
+        return c->fail(FHEAES_ERR_INVALID, "XTS tweak offsets %u .. : one gather reaches offset %u at most and takes at least one", first_offset, XTS_MAX_OFFSET);
+    if (n_units == 0) return FHEAES_OK;
+    if (!anchor || !out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    const uint64_t tw = AES_BLOCK_BITS * c->big1, in_bytes = n_units * tw * 8, out_bytes = in_bytes * n_offsets;
+    if (overlap(anchor, in_bytes, out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "anchor and out overlap (the gather is not in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    TRY(s.in(anchor, in_bytes, &anchor));
+    TRY(s.out(out, out_bytes, &out));
+    TRY(launch_xts_tweaks(c, anchor, tw, n_units, first_offset, n_offsets, out));
+    return s.finish();
+}
+
+int fheaes_xts_tweak_row(uint32_t offset, uint32_t bit, uint32_t *sources_out, uint32_t *n_sources)
+{
+    if (offset > XTS_MAX_OFFSET || bit > 127 || !sources_out || !n_sources) return FHEAES_ERR_INVALID;
+    uint32_t s[4] = {0, 0, 0, 0};
+    *n_sources = xts_tweak_row(offset, bit, s);
+    memcpy(sources_out, s, sizeof s);
+    return FHEAES_OK;
+}
+
+int fheaes_aes_xts_plan(uint64_t n_units, uint64_t blocks_per_unit, uint64_t first_block, uint64_t n_blocks, uint32_t key_bits, uint64_t *segments,
+                        uint64_t *tweak_refresh_bytes, uint64_t *cipher_bytes, uint32_t *max_terms)
+{
+    if (!segments || !tweak_refresh_bytes || !cipher_bytes || !max_terms || (key_bits != 128 && key_bits != 256)) return FHEAES_ERR_INVALID;
+    XtsPlan pl;
+    if (!xts_plan(n_units, blocks_per_unit, first_block, n_blocks, false, pl)) return FHEAES_ERR_INVALID;
+    *segments = pl.segments.size();
+    *tweak_refresh_bytes = 16 * (pl.units + pl.rows);                   // the anchors of segment 0, then every gathered tweak
+    *cipher_bytes = 16ull * aes_rounds(key_bits) * n_blocks;
+    // what the call declares to the noise guard: the gather's largest row, 2 going into the cipher, 5 in its rounds, 3 coming out
+    uint32_t terms = n_blocks ? 5 : 0, s[4];
+    for (const auto &seg : pl.segments) for (const XtsGather &g : seg)
+        for (uint32_t j = g.off0; j < g.off0 + g.n_off; ++j) for (uint32_t i = 0; i < 128; ++i) terms = std::max(terms, xts_tweak_row(j, i, s));
+    *max_terms = terms;
+    return FHEAES_OK;
+}
+
 // ---- packing ----------------------------------------------------------------------------------
 size_t fheaes_packed_words(const fheaes_ctx *c, uint64_t m)
 {

@@ -432,6 +432,39 @@ int launch_key_rows(fheaes_ctx *c, uint64_t *dst, uint64_t dst_stride, const uin
     return FHEAES_OK;
 }
 
+// xts_tweak_kernel: offsets off0 .. off0 + n_off - 1 of n_units units.  The layer's largest row weight is what it declares to the noise
+// guard (at most 4: kern_linear.h); an offset beyond XTS_MAX_OFFSET would need a second reduction and is refused.  Units: tweak blocks.
+int launch_xts_tweaks(fheaes_ctx *c, const uint64_t *anchor, uint64_t anchor_stride, uint64_t n_units, uint32_t off0, uint32_t n_off, uint64_t *out)
+{
+    if (n_off == 0 || off0 > XTS_MAX_OFFSET || n_off > XTS_MAX_OFFSET + 1 - off0)
+        return c->fail(FHEAES_ERR_INVALID, "XTS tweak offsets %u .. %u: one gather reaches offset %u at most", off0, off0 + n_off - 1, XTS_MAX_OFFSET);
+    if (n_units == 0) return FHEAES_OK;
+    uint32_t weight = 0, s[4];
+    for (uint32_t j = off0; j < off0 + n_off; ++j)
+        for (uint32_t i = 0; i < 128; ++i) weight = std::max(weight, xts_tweak_row(j, i, s));
+    TRY(noise_guard(c, weight, "the XTS tweak layer (multiplication by alpha^j)"));
+    StageScope sc(c, FHEAES_STAGE_LINEAR, n_units * n_off);
+    const uint64_t rows = n_units * n_off * 128;
+    hipLaunchKernelGGL(xts_tweak_kernel, dim3((unsigned)std::min<uint64_t>(rows, 1u << 20)), dim3(256), 0, c->stream, anchor, anchor_stride, out, n_units, off0,
+                       n_off, c->big1);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
+// xts_whiten_kernel over n_blocks blocks; `level`: the nominal-noise ciphertexts one output word sums
+int launch_xts_whiten(fheaes_ctx *c, uint64_t *dst, const uint64_t *src, const uint64_t *tweaks, const uint32_t *tweak_of_block, const uint8_t *clear,
+                      uint64_t n_blocks, uint32_t level)
+{
+    if (n_blocks == 0) return FHEAES_OK;
+    TRY(noise_guard(c, level, "the XTS whitening (tweak + block)"));
+    StageScope sc(c, FHEAES_STAGE_LINEAR, n_blocks);
+    const unsigned gx = (unsigned)std::min<uint64_t>((128ull * c->big1 + 255) / 256, 64);
+    dim3 grid(gx, (unsigned)std::min<uint64_t>(n_blocks, std::max<uint64_t>(1, 16384 / gx)));
+    hipLaunchKernelGGL(xts_whiten_kernel, grid, dim3(256), 0, c->stream, dst, src, tweaks, tweak_of_block, clear, n_blocks, c->big1);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
 // ---- packing (fheaes_pack_bits, fheaes_unpack_bits) ---------------------------------------------------------------------------
 static_assert(PACK_N == FHE_N && PACK_N % PACK_FOLD_ROWS == 0, "kern_linear.h's packing kernels are written for N = 512");
 

@@ -5,6 +5,7 @@
 //   inv_mix_columns           src/server/decrypt/inv_mix_columns.rs:4-58
 //   inv_shift_rows            src/server/decrypt/inv_shift_rows.rs:5-21
 //   add_round_key             src/server/server.rs:278-282
+//   (no counterpart)          the XTS tweak layer: multiplication by alpha^j in GF(2^128), xts_tweak_kernel below
 // All of them are one "gather-add": out[blk][byte] = sum_t src[blk][tab.src[byte][t]][tab.lut[byte][t]] (+ rk[byte]).
 // The round key comes from a source type (LweKeys, PackedKeys below): every layer that adds one is ONE kernel template over that type,
 // so round keys in LWE form and in a packed store go through the same body.
@@ -132,6 +133,78 @@ __device__ __forceinline__ uint64_t add_trivial_bit(uint64_t v, uint32_t clear, 
 {
     const uint32_t bit = w / lwe_words;
     return w - bit * lwe_words == lwe_words - 1 ? v + ((uint64_t)((clear >> bit) & 1u) << 63) : v;
+}
+
+// ---- XTS (IEEE 1619): the tweak layer ---------------------------------------------------------------------------------------------------
+// T_j = T * alpha^j in GF(2^128) mod x^128 + x^7 + x^2 + x + 1.  Bit b (LSB first) of block byte p is degree 8p + b, the flattened
+// [16][8] index of a state, and the product is linear over GF(2): output bit i is the sum (XOR == wrapping add of the MSB encodings) of
+//   bit i - j                                     if i >= j
+//   bit 128 - j + m, m in {i, i-1, i-2, i-7}      if 0 <= m < j     (the j bits shifted out, reduced ONCE by x^128 = x^7 + x^2 + x + 1)
+// which holds while no shifted-out bit lands at degree 128 or above again: m + 7 <= 127 for every m < j, that is j <= 121.  The sources
+// of a row are distinct and at most 4 (i >= j leaves m < j <= i, so m = i is out).  Returns their count; sources[] are bit indices < 128.
+#define XTS_MAX_OFFSET 121u
+__host__ __device__ __forceinline__ uint32_t xts_tweak_row(uint32_t j, uint32_t i, uint32_t (&sources)[4])
+{
+    const uint32_t back[4] = {0, 1, 2, 7};
+    uint32_t n = 0;
+    if (i >= j) sources[n++] = i - j;
+#pragma unroll
+    for (uint32_t t = 0; t < 4; ++t)
+        if (i >= back[t] && i - back[t] < j && n < 4) sources[n++] = 128 - j + (i - back[t]);
+    return n;
+}
+
+// out[u][t][i][w] = sum over the row (off0 + t, i) of anchor[u][source][w]: the tweaks off0 .. off0 + n_off - 1 (all <= XTS_MAX_OFFSET)
+// of every unit from its anchor, each output bit gathered from the anchor in ONE sum (doubling step by step would add a ciphertext to
+// itself: the message cancels, the noise does not).  anchor: unit u's [128][lwe_words] at u * anchor_stride words; out:
+// [n_units][n_off][128][lwe_words].  One workgroup per output bit, lanes on consecutive w (rows of kN + 1 words are 8-byte aligned and no
+// more: 8-byte accesses); rows are taken in order, so the workgroups of a unit are adjacent in the grid and the up to 121 offsets that
+// re-read its anchor (2 MB at PARAM_OPT) find it in L2: HBM sees the 16,392 B per output bit that are written.  All offsets in 64 bits.
+__global__ __launch_bounds__(256) void xts_tweak_kernel(const uint64_t *anchor, uint64_t anchor_stride, uint64_t *out, uint64_t n_units, uint32_t off0,
+                                                        uint32_t n_off, uint32_t lwe_words)
+{
+    const uint64_t rows = n_units * n_off * 128;
+    for (uint64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+        const uint32_t i = (uint32_t)(r & 127);
+        const uint64_t ut = r >> 7, u = ut / n_off;
+        uint32_t s[4];
+        const uint32_t n = xts_tweak_row(off0 + (uint32_t)(ut - u * n_off), i, s);
+        const uint64_t *ab = anchor + u * anchor_stride;
+        const uint64_t *p[4];                                    // fully unrolled so that the pointers stay in registers
+#pragma unroll
+        for (uint32_t t = 0; t < 4; ++t) p[t] = ab + (uint64_t)(t < n ? s[t] : 0u) * lwe_words;
+        uint64_t *o = out + r * lwe_words;
+        for (uint32_t w = threadIdx.x; w < lwe_words; w += blockDim.x) {
+            uint64_t v = 0;
+#pragma unroll
+            for (uint32_t t = 0; t < 4; ++t)
+                if (t < n) v += p[t][w];
+            o[w] = v;
+        }
+    }
+}
+
+// XTS whitening, before and after the cipher: dst[b] = (src ? src[b] : 0) + tweaks[tweak_of_block[b]] + trivial(clear block b).
+// dst, src: [n_blocks][16][8][lwe_words] (src == dst: in place); tweaks: rows of 128 lwe_words words; clear: [n_blocks][16] bytes, or null
+__global__ __launch_bounds__(256) void xts_whiten_kernel(uint64_t *dst, const uint64_t *src, const uint64_t *tweaks, const uint32_t *tweak_of_block,
+                                                         const uint8_t *clear, uint64_t n_blocks, uint32_t lwe_words)
+{
+    const uint32_t byte_words = 8 * lwe_words;
+    const uint64_t words_per_block = 16ull * byte_words;
+    for (uint64_t blk = blockIdx.y; blk < n_blocks; blk += gridDim.y) {
+        const uint64_t *tb = tweaks + (uint64_t)tweak_of_block[blk] * words_per_block;
+        const uint64_t *sb = src ? src + blk * words_per_block : nullptr;
+        uint64_t *db = dst + blk * words_per_block;
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < words_per_block; i += gridDim.x * blockDim.x) {
+            uint64_t v = tb[i];
+            if (sb) v += sb[i];
+            if (clear) {
+                const uint32_t p = i / byte_words;
+                v = add_trivial_bit(v, clear[blk * 16 + p], i - p * byte_words, lwe_words);
+            }
+            db[i] = v;
+        }
+    }
 }
 
 // Rows of bytes moved between strided sets, one set per AES key: the word operations of the key expansion over all keys at once (RotWord,

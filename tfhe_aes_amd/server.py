@@ -7,6 +7,7 @@ Same names, argument meaning and error behaviour as
   plus aes_encrypt_public / aes_ctr: public blocks and SP 800-38A CTR with a PUBLIC nonce, every distinct S-Box input evaluated once;
   plus aes_decrypt_public / aes_cbc_decrypt / aes_cfb_decrypt / aes_gcm_ctr: the decryption direction of the public calls and the
   modes whose decryption works on public blocks -- CBC, CFB-128 and the 32-bit counter of GCM;
+  plus aes_xts_decrypt: XTS-AES (IEEE 1619) decryption of a public ciphertext, the per-block tweaks derived under encryption;
   plus the *_many / *_keyed / aes_ctr_streams methods: many AES keys under one FHE key, round keys [n_keys][Nr+1][16][8][kN+1] and a key
   index per block, word for word the single-key methods key by key; plus packed round keys: pack_round_keys / unpack_round_keys /
   aes_key_expansion_packed, and a PackedRoundKeys -- 3 / 4 / 4 GLWEs per key -- wherever a method takes round keys, the key words read
@@ -132,6 +133,25 @@ def gcm_ctr_args(iv, data, n_blocks, first_block: int = 0):
         data = _cipher_blocks(data)
         n_blocks = len(data)
     return int.from_bytes(bytes(iv) + b"\x00\x00\x00\x01", "big"), int(n_blocks), _data_blocks(data, int(n_blocks))
+
+
+def xts_args(sectors, ciphertext, unit_bytes: int, first_block: int):
+    """aes_xts_decrypt's arguments -> (data-unit numbers of units 0 .., blocks per unit, ciphertext blocks).  `sectors`: an int (the number
+    of unit 0, consecutive ones follow) or a list; the units are those the blocks first_block .. name"""
+    unit_bytes, first_block = int(unit_bytes), int(first_block)
+    if unit_bytes < 16 or unit_bytes % 16 or unit_bytes > 16 << 20:
+        raise ValueError("a data unit has 1 to 2^20 whole 16-byte blocks (ciphertext stealing is not offered), got %d bytes" % unit_bytes)
+    if first_block < 0:
+        raise ValueError("first_block must be >= 0")
+    ct = _cipher_blocks(ciphertext)
+    bpu = unit_bytes // 16
+    n_units = (first_block + len(ct) + bpu - 1) // bpu if ct else 0
+    if isinstance(sectors, int):
+        sectors = [sectors + u for u in range(n_units)]
+    sectors = [int(v) for v in sectors]
+    if len(sectors) < n_units:
+        raise ValueError("blocks %d .. %d lie in %d data units, %d sectors given" % (first_block, first_block + len(ct), n_units, len(sectors)))
+    return sectors, bpu, ct
 
 
 def cbc_stream_blocks(streams):
@@ -372,6 +392,35 @@ class Server:
             _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
             rk = encrypted_round_keys[None]
         return self.aes_encrypt_public_keyed(rk, [0] * len(ct), blocks, data=ct, out=out)
+
+    def aes_xts_decrypt(self, dec_round_keys1, round_keys2, sectors, ciphertext, unit_bytes: int = 512, first_block: int = 0, out=None):
+        """XTS-AES decryption (IEEE 1619) of a PUBLIC ciphertext under two encrypted keys: block b of the call is block (first_block + b) %
+        (unit_bytes / 16) of data unit (first_block + b) // (unit_bytes / 16), P = D_K1(C ^ T) ^ T with T = E_K2(sector) * alpha^block, as a
+        new [n][16][8][kN+1].  dec_round_keys1: aes_decryption_round_keys of key 1; round_keys2: the expansion of key 2 (AES-128 or AES-256,
+        both the same size; a PackedRoundKeys of one key for either).  `sectors`: the data-unit number of unit 0 (consecutive ones follow),
+        or a list, one per unit; `ciphertext`: bytes of whole blocks, or u128 blocks.  Every tweak costs one more identity WoPBS per byte:
+        16 (Nr + 1) byte-WoPBS per block (include/fheaes.h: fheaes_aes_xts_decrypt_bits).  Ciphertext stealing and XTS encryption are not offered."""
+        from .aes_clear import xts_tweak_block
+
+        sectors, bpu, ct = xts_args(sectors, ciphertext, unit_bytes, first_block)
+        tweaks = [xts_tweak_block(v) for v in sectors]          # IEEE 1619 writes the number little-endian: its low byte is byte 0 of the block
+        packed = [isinstance(k, PackedRoundKeys) for k in (dec_round_keys1, round_keys2)]
+        if any(packed):
+            if not all(packed):
+                # one call reads both key sets in one form: bring the LWE-form set to the other's
+                dec_round_keys1, round_keys2 = (k if isinstance(k, PackedRoundKeys) else self.pack_round_keys(k) for k in (dec_round_keys1, round_keys2))
+            k1, k2 = self._check_packed(dec_round_keys1, one_key=True), self._check_packed(round_keys2, one_key=True)
+            bits, bits2, w1, w2 = k1.key_bits, k2.key_bits, k1.data, k2.data
+        else:
+            bits = _key_bits(dec_round_keys1, ROUND_KEYS_TO_BITS, "decryption round keys")
+            bits2 = _key_bits(round_keys2, ROUND_KEYS_TO_BITS, "round keys")
+            w1, w2 = dec_round_keys1, round_keys2
+        if bits != bits2 or bits == 192:
+            raise ValueError("XTS-AES takes two keys of 128 or of 256 bits, got %d and %d" % (bits, bits2))
+        out = self._public_out(w1, len(ct), out)
+        if ct:
+            self.engine.aes_xts_decrypt_bits(w1, w2, bits, tweaks, bpu, int(first_block), ct, out, packed=any(packed))
+        return out
 
     # ---- many AES keys under one FHE key ----------------------------------------------
     def aes_key_expansion_many(self, keys, out=None):
@@ -707,6 +756,13 @@ class ServerGroup:
         ct = _cipher_blocks(ciphertext)
         return self._fan_out_new(round_keys, len(ct), lambda s, shard, lo, k: s.aes_cfb_decrypt(
             round_keys, ct[lo - 1] if lo else iv, ct[lo:lo + k], out=shard))
+
+    def aes_xts_decrypt(self, dec_round_keys1, round_keys2, sectors, ciphertext, unit_bytes: int = 512, first_block: int = 0):
+        """Server.aes_xts_decrypt: a shard at block lo passes first_block + lo and needs nothing from its neighbour (it derives its own
+        tweaks from the units' anchors)"""
+        units, _, ct = xts_args(sectors, ciphertext, unit_bytes, first_block)
+        return self._fan_out_new(dec_round_keys1, len(ct), lambda s, shard, lo, k: s.aes_xts_decrypt(
+            dec_round_keys1, round_keys2, units, ct[lo:lo + k], unit_bytes, int(first_block) + lo, out=shard))
 
     def aes_key_expansion(self, key):
         return self.servers[0].aes_key_expansion(key)
