@@ -488,6 +488,73 @@ int fheaes_aes_decrypt_public_keyed_packed(fheaes_ctx *ctx, const uint64_t *pack
                                            const uint32_t *key_of_block, const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo,
                                            uint64_t n_blocks, uint64_t *state_out, int memspace);
 
+/* ---- CBC-MAC chains and CCM decryption with its tag check --------------------------- */
+/* A CBC-MAC X_{i+1} = E_K(X_i ^ B_i) is block encryptions and XORs only, so -- unlike GHASH, a product of encrypted field elements -- it
+ * stays inside the noise budget: the first integrity result of the engine.  It is serial inside a stream and parallel across streams:
+ * the streams are sorted by chain length (descending, stable), step i of all live streams is ONE windowed cipher pass over a prefix of
+ * one state array, and one K6 launch (mac_link_kernel) links two passes.  Levels against FHEAES_MAX_NOISE_LEVEL = 5: a cipher or
+ * public-call output is 2; a link of public blocks enters AddRoundKey at 3; a link with an encrypted addend at X (2) + P (2) + round key
+ * = 5; the tag difference is 4; a caller's `enc` or `init` is counted as 2.
+ *
+ * Bounds: n_keys <= FHEAES_MAX_KEYS, n_streams <= FHEAES_MAC_MAX_STREAMS, a stream chains at most FHEAES_MAC_MAX_STREAM_BLOCKS blocks.
+ * Refused with FHEAES_ERR_INVALID before anything is launched: a NULL argument that is not optional, overlapping in and out buffers, a
+ * count above its bound, a key index >= n_keys, enc_bytes > 16, and for CCM a tag length outside {4, 6, .., 16} or flags bytes that do
+ * not describe a 7..13-byte nonce.  n_streams = 0 is FHEAES_OK and writes nothing; FHEAES_DEVICE calls only enqueue. */
+#define FHEAES_MAC_MAX_STREAMS (1u << 20)
+#define FHEAES_MAC_MAX_STREAM_BLOCKS (1u << 16)
+#define FHEAES_MAC_NONE 0xFFFFFFFFu
+/* mac_out[s] = X after stream s's stream_blocks[s] blocks, X_0 = init[s] (or zero), X_{i+1} = E_{K[key_of_stream[s]]}(X_i + block i), where
+ * block i = trivial(clear[b]) + the first enc_bytes[b] bytes of enc[b], b the block's index in the call (stream after stream, the caller's
+ * order).  round_keys [n_keys][Nr+1][16][8][kN+1]; key_of_stream, stream_blocks: HOST arrays of n_streams; clear: HOST bytes [blocks][16];
+ * enc [blocks][16][8][kN+1] with enc_bytes (HOST, [blocks], 0..16), both or neither; init [n_streams][16][8][kN+1] or NULL;
+ * mac_out [n_streams][16][8][kN+1].  A stream of 0 blocks yields its init (zero words without one).  Word for word: per step,
+ * fheaes_aes_encrypt_keyed on the wrapping sums of the live streams in sorted order. */
+int fheaes_aes_cbc_mac_keyed(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams,
+                             const uint32_t *key_of_stream, const uint32_t *stream_blocks, const uint8_t *clear, const uint64_t *enc,
+                             const uint8_t *enc_bytes, const uint64_t *init, uint64_t *mac_out, int memspace);
+/* The same with the keys in a packed store (fheaes_pack_round_keys). */
+int fheaes_aes_cbc_mac_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams,
+                                    const uint32_t *key_of_stream, const uint32_t *stream_blocks, const uint8_t *clear, const uint64_t *enc,
+                                    const uint8_t *enc_bytes, const uint64_t *init, uint64_t *mac_out, int memspace);
+/* AES-CCM decryption (SP 800-38C, RFC 3610) of n_streams PUBLIC messages, each under the encrypted key key_of_stream[s], with the tag
+ * compared under encryption.  The caller formats (SP 800-38C A.2, A.3); this call sees blocks, every clear block as (hi, lo) with byte 0
+ * the most significant byte of hi.  Per stream: head_blocks[s] = 1 + a blocks in head_hi_lo (B0, then the encoded, zero-padded AAD
+ * blocks), stream after stream; Ctr_0 in ctr0_hi_lo (its counter field zero: Ctr_i is Ctr_0 + i); payload_bytes[s] bytes of `ciphertext`
+ * (stream after stream, no padding); the received tag in tags[s][16], its first tag_bytes[s] = t bytes.  All of these are HOST arrays.
+ *   (a) one public call over [Ctr_1.. | B0 | Ctr_0] with data [C_1.. | 0 | 0] yields the plaintext blocks P, X_1 and S0;
+ *   (b) the CBC-MAC runs from X_1 over the a AAD blocks, then over the payload blocks with the encrypted P as addend, the last one with
+ *       its real bytes only; a stream with a = 0 and no payload has MAC X_1;
+ *   (c) diff = X_final + S0 + trivial(tag) on its first 8t rows, zero words beyond;
+ *   (d) one 8-bit WoPBS per byte of diff (LUT: byte != 0), then one 16-bit WoPBS per stream over those 16 bits (LUT: 1 on input 0).
+ * plaintext_out [sum of ceil(payload_bytes / 16)][16][8][kN+1], stream after stream, rows beyond a payload's length zero words (may be
+ * NULL when no stream has a payload); valid_out [n_streams][kN+1], row 0 of (d): an encryption of 1 iff the tag is right.  The plaintext is
+ * NOT gated on valid_out: a caller that releases it does so after reading the bit. */
+int fheaes_aes_ccm_open_keyed(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams,
+                              const uint32_t *key_of_stream, const uint32_t *head_blocks, const uint64_t *head_hi_lo, const uint64_t *ctr0_hi_lo,
+                              const uint64_t *payload_bytes, const uint8_t *ciphertext, const uint8_t *tags, const uint32_t *tag_bytes,
+                              uint64_t *plaintext_out, uint64_t *valid_out, int memspace);
+int fheaes_aes_ccm_open_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams,
+                                     const uint32_t *key_of_stream, const uint32_t *head_blocks, const uint64_t *head_hi_lo,
+                                     const uint64_t *ctr0_hi_lo, const uint64_t *payload_bytes, const uint8_t *ciphertext, const uint8_t *tags,
+                                     const uint32_t *tag_bytes, uint64_t *plaintext_out, uint64_t *valid_out, int memspace);
+/* K6 alone, one link of a chain (needs no keys): state[s] = (first ? (init ? init[s] : 0) : state[s]) + the first enc_bytes[s] bytes of
+ * enc[src_block[s]] (src_block[s] == FHEAES_MAC_NONE, or enc NULL: none) + trivial(clear[s]), for s < n_slots.  state, init
+ * [n_slots][16][8][kN+1]; enc [n_enc][16][8][kN+1]; src_block, enc_bytes, clear ([n_slots][16]): HOST arrays.  Declares to the noise guard
+ * what the link declares inside a chain (the level of the sum plus the round key that follows). */
+int fheaes_mac_link(fheaes_ctx *ctx, uint64_t *state, uint64_t n_slots, int first, const uint64_t *init, const uint64_t *enc, uint64_t n_enc,
+                    const uint32_t *src_block, const uint8_t *enc_bytes, const uint8_t *clear, int memspace);
+/* K6 alone, the XTS whitening (needs no keys): dst[b] = (src ? src[b] : 0) + tweaks[tweak_of_block[b]] + trivial(clear[b]), b < n_blocks;
+ * dst, src [n_blocks][16][8][kN+1] (src == dst: in place; NULL: none), tweaks [n_tweaks][16][8][kN+1], tweak_of_block (HOST, entries below
+ * n_tweaks), clear (HOST, [n_blocks][16], or NULL).  Declared to the noise guard as 3 with a src, 2 without.  The yardstick the link
+ * kernel is timed against (tools/ccm.py): the same traffic per output word. */
+int fheaes_xts_whiten(fheaes_ctx *ctx, uint64_t *dst, const uint64_t *src, const uint64_t *tweaks, uint64_t n_tweaks, const uint32_t *tweak_of_block,
+                      const uint8_t *clear, uint64_t n_blocks, int memspace);
+/* What a chain over streams of stream_blocks[s] blocks runs (host logic only): *steps cipher passes, n_active_out[i] live streams in pass i
+ * (n_active_out may be NULL; else n_active_cap >= *steps), *chained_blocks = their sum.  payload_blocks (NULL for a plain CBC-MAC): of a
+ * CCM stream's chain, how many blocks are payload; *public_blocks = 2 n_streams + their sum, the blocks of the CCM public call (0 for NULL). */
+int fheaes_aes_mac_plan(const uint32_t *stream_blocks, const uint32_t *payload_blocks, uint64_t n_streams, uint64_t *steps, uint64_t *n_active_out,
+                        uint64_t n_active_cap, uint64_t *public_blocks, uint64_t *chained_blocks);
+
 /* ---- measurement --------------------------------------------------------------- */
 #define FHEAES_STAGE_KEYSWITCH 0
 #define FHEAES_STAGE_BLIND_ROTATE 1

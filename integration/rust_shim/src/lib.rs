@@ -118,6 +118,9 @@ extern "C" {
     pub fn fheaes_xts_tweak_row(offset: u32, bit: u32, sources_out: *mut u32, n_sources: *mut u32) -> c_int;
     pub fn fheaes_aes_xts_plan(n_units: u64, blocks_per_unit: u64, first_block: u64, n_blocks: u64, key_bits: u32, segments: *mut u64,
                                tweak_refresh_bytes: *mut u64, cipher_bytes: *mut u64, max_terms: *mut u32) -> c_int;
+    // CBC-MAC chains and AES-CCM: the plan (host only); the calls themselves take host byte tables (uint8_t: *const u8) and are bound where used
+    pub fn fheaes_aes_mac_plan(stream_blocks: *const u32, payload_blocks: *const u32, n_streams: u64, steps: *mut u64, n_active_out: *mut u64, n_active_cap: u64,
+                               public_blocks: *mut u64, chained_blocks: *mut u64) -> c_int;
     // packed ciphertexts: N = 512 bits per GLWE through key block k of the PFPKSK the context holds (no new key), and back
     pub fn fheaes_packed_words(ctx: *const fheaes_ctx, m: u64) -> usize;
     pub fn fheaes_pack_bits(ctx: *mut fheaes_ctx, lwe_in: *const u64, m: u64, glwe_out: *mut u64, memspace: c_int) -> c_int;

@@ -1,0 +1,128 @@
+"""What the CCM tests share: the known answers as data, and the composition of entry points older than fheaes_aes_cbc_mac_keyed and
+fheaes_aes_ccm_open_keyed that the two calls must equal word for word -- aes_encrypt_public_keyed, aes_encrypt_keyed step by step on
+the live prefix, numpy wrapping adds, trivial bytes and many_wopbs_without_padding.  A plain module like xts.py: imported by name, not
+collected."""
+import numpy as np
+
+from tfhe_aes_amd import aes_clear
+from tfhe_aes_amd.server import gen_lut
+
+h = bytes.fromhex
+
+
+def run(lo, n):
+    return bytes(range(lo, lo + n))
+
+
+# key | nonce | aad | payload | t -> ciphertext || tag: SP 800-38C examples 1-3 and RFC 3610 packet vector 1
+VECTORS = {
+    "ex1": (run(0x40, 16), run(0x10, 7), run(0, 8), run(0x20, 4), 4, h("7162015b4dac255d")),
+    "ex2": (run(0x40, 16), run(0x10, 8), run(0, 16), run(0x20, 16), 6, h("d2a1f0e051ea5f62081a7792073d593d1fc64fbfaccd")),
+    "ex3": (run(0x40, 16), run(0x10, 12), run(0, 20), run(0x20, 24), 8,
+            h("e3b201a9f5b71a7a9b1ceaeccd97e70b6176aad9a4428aa5484392fbc1b09951")),
+    "rfc1": (run(0xC0, 16), h("00000003020100a0a1a2a3a4a5"), run(0, 8), run(8, 23), 8,
+             h("588c979a61c663d2f066d0c2c0f989806d5f6b61dac38417e8d12cfdf926e0")),
+}
+
+
+def message(key_index, name):
+    """a VECTORS entry as aes_ccm_decrypt takes it: (key_index, nonce, aad, ciphertext, tag)"""
+    _, nonce, aad, _, t, out = VECTORS[name]
+    return (key_index, nonce, aad, out[:-t], out[-t:])
+
+
+def own_message(key_index, key, nonce, aad, payload, t):
+    out = aes_clear.ccm_encrypt(key, nonce, aad, payload, t)
+    return (key_index, nonce, aad, out[:-t], out[-t:])
+
+
+def tag_luts():
+    """the two LUTs of the tag check: 8 bits -> byte != 0, 16 bits -> input == 0 (output bit 0; the other output bits are 0)"""
+    return gen_lut(2, 1, 512, 8, lambda x: x != 0), gen_lut(2, 1, 512, 16, lambda x: x == 0)
+
+
+def np_link(client, state, first, init, enc, src_block, enc_bytes, clear):
+    """mac_link_kernel in numpy: state [n][16][8][kN+1] -> the linked state (a new array)"""
+    lw = client.params.big1
+    n = len(state)
+    out = (np.zeros_like(state) if init is None else init.copy()) if first else state.copy()
+    out += client.trivial_bytes(np.asarray(clear, dtype=np.uint8).reshape(n, 16))
+    if enc is not None:
+        for s in range(n):
+            if src_block[s] != 0xFFFFFFFF and enc_bytes[s]:
+                out[s].reshape(128, lw)[:8 * enc_bytes[s]] += enc[src_block[s]].reshape(128, lw)[:8 * enc_bytes[s]]
+    return out
+
+
+def compose_mac(srv, client, rk, streams, init=None):
+    """fheaes_aes_cbc_mac_keyed out of older calls: `streams` of (key_index, blocks as u128, enc or None, enc_bytes or None); rk
+    [n_keys][Nr+1][16][8][kN+1] on the host.  The streams sorted by length (descending, stable); per step the live prefix gets its
+    blocks added and goes through aes_encrypt_keyed.  Returns [n][16][8][kN+1] in the caller's order."""
+    lw = client.params.big1
+    n = len(streams)
+    lens = [len(st[1]) for st in streams]
+    order = sorted(range(n), key=lambda s: -lens[s])
+    state = np.zeros((n, 16, 8, lw), dtype=np.uint64)
+    if init is not None:
+        state = np.stack([init[s] for s in order])
+    for i in range(max(lens, default=0)):
+        live = sum(1 for s in order if lens[s] > i)
+        assert all(lens[order[j]] > i for j in range(live))
+        for j in range(live):
+            key_index, blocks, enc, enc_bytes = streams[order[j]]
+            state[j] += client.trivial_bytes(list(int(blocks[i]).to_bytes(16, "big")))
+            if enc is not None:
+                k = 8 * (16 if enc_bytes is None else enc_bytes[i])
+                state[j].reshape(128, lw)[:k] += enc[i].reshape(128, lw)[:k]
+        sub = np.ascontiguousarray(state[:live])
+        srv.aes_encrypt_keyed(rk, [streams[order[j]][0] for j in range(live)], sub)
+        state[:live] = sub
+    out = np.empty_like(state)
+    for j, s in enumerate(order):
+        out[s] = state[j]
+    return out
+
+
+def compose(srv, client, rk, messages):
+    """fheaes_aes_ccm_open_keyed out of older calls, on host arrays: per message the public call over [B0, Ctr_0, Ctr_1..Ctr_m] with data
+    [none, none, C_1..C_m]; the chain from X_1 over the AAD blocks, then the payload blocks with P as the encrypted addend (the last with
+    its real bytes); diff = X + S0 + trivial(tag) on 8t rows; the two WoPBS.  Returns (plaintext, valid, block_of_message)."""
+    lw = client.params.big1
+    keys, blocks, data, where = [], [], [], []
+    for key_index, nonce, aad, ct, tag in messages:
+        b0, aad_blocks, ctr = aes_clear.ccm_blocks(nonce, aad, len(ct), len(tag))
+        padded = ct + bytes(-len(ct) % 16)
+        where.append((len(blocks), aad_blocks, len(ctr) - 1))
+        blocks += [b0] + ctr
+        data += [0, 0] + [int.from_bytes(padded[i:i + 16], "big") for i in range(0, len(padded), 16)]
+        keys += [key_index] * (1 + len(ctr))
+    pub = srv.aes_encrypt_public_keyed(rk, keys, blocks, data=data)
+    streams, init, s0, plain, at = [], [], [], [], [0]
+    for (key_index, nonce, aad, ct, tag), (b, aad_blocks, m) in zip(messages, where):
+        real = [min(16, len(ct) - 16 * i) for i in range(m)]
+        p = pub[b + 2:b + 2 + m].copy()
+        a = len(aad_blocks)
+        enc = np.concatenate([np.zeros((a, 16, 8, lw), dtype=np.uint64), p])
+        streams.append((key_index, aad_blocks + [0] * m, enc, [0] * a + real))
+        init.append(pub[b]); s0.append(pub[b + 1])
+        for i in range(m):
+            p[i].reshape(128, lw)[8 * real[i]:] = 0
+        plain.append(p)
+        at.append(at[-1] + m)
+    x = compose_mac(srv, client, rk, streams, init=np.stack(init))
+    n = len(messages)
+    diff = np.zeros((n, 128, lw), dtype=np.uint64)
+    for s, (_, _, _, _, tag) in enumerate(messages):
+        t = len(tag)
+        full = x[s] + s0[s] + client.trivial_bytes(list(tag) + [0] * (16 - t))
+        diff[s, :8 * t] = full.reshape(128, lw)[:8 * t]
+    ne0, eq0 = tag_luts()
+    w1 = srv.many_wopbs_without_padding(diff.reshape(16 * n, 8, lw), [ne0])
+    w2 = srv.many_wopbs_without_padding(np.ascontiguousarray(w1[:, 0, 0, :]).reshape(n, 16, lw), [eq0])
+    return np.concatenate(plain) if at[-1] else np.zeros((0, 16, 8, lw), dtype=np.uint64), np.ascontiguousarray(w2[:, 0, 0, :]), at
+
+
+def plaintext_of(client, plaintext, at, messages):
+    """the decrypted payload bytes of every message"""
+    dec = client.decrypt_bytes(plaintext).reshape(-1)
+    return [bytes(dec[16 * at[i]:16 * at[i] + len(m[3])].tolist()) for i, m in enumerate(messages)]

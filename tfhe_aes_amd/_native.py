@@ -16,6 +16,7 @@ from . import _build
 from .params import CParams, WopbsParameters
 
 HOST, DEVICE = 0, 1
+MAC_NONE = 0xFFFFFFFF           # FHEAES_MAC_NONE: "no block" in a src_block table of mac_link
 AES_WINDOW_OFF = 0xFFFFFFFF     # FHEAES_AES_WINDOW_OFF: fheaes_aes_set_window's "one launch per round"
 K2_PARK_SLOTS = 1024            # FHEAES_K2_PARK_SLOTS: owner words of the paired kernel's shared parking slots, 128 per XCC
 STAGES = ("keyswitch", "blind_rotate", "pfpks", "ggsw_fft", "vertical_packing", "linear")
@@ -23,6 +24,7 @@ STAGES = ("keyswitch", "blind_rotate", "pfpks", "ggsw_fft", "vertical_packing", 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _dp = ctypes.POINTER(ctypes.c_double)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
+_u8p = ctypes.POINTER(ctypes.c_uint8)
 _ctx = ctypes.c_void_p
 _c = ctypes
 
@@ -103,6 +105,17 @@ SIGNATURES = {
     "fheaes_aes_public_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _u64p, _u64p, _c.c_uint64, _c.c_void_p, _c.c_int]),
     "fheaes_aes_decrypt_public_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _u32p, _u64p, _u64p, _c.c_uint64, _c.c_void_p,
                                                           _c.c_int]),
+    "fheaes_aes_cbc_mac_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_uint64, _u32p, _u32p, _u8p, _c.c_void_p, _u8p, _c.c_void_p,
+                                            _c.c_void_p, _c.c_int]),
+    "fheaes_aes_cbc_mac_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_uint64, _u32p, _u32p, _u8p, _c.c_void_p, _u8p,
+                                                   _c.c_void_p, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_ccm_open_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_uint64, _u32p, _u32p, _u64p, _u64p, _u64p, _u8p, _u8p, _u32p,
+                                             _c.c_void_p, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_ccm_open_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_uint64, _u32p, _u32p, _u64p, _u64p, _u64p, _u8p, _u8p,
+                                                    _u32p, _c.c_void_p, _c.c_void_p, _c.c_int]),
+    "fheaes_mac_link": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_uint64, _u32p, _u8p, _u8p, _c.c_int]),
+    "fheaes_xts_whiten": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _u32p, _u8p, _c.c_uint64, _c.c_int]),
+    "fheaes_aes_mac_plan": (_c.c_int, [_u32p, _u32p, _c.c_uint64, _u64p, _u64p, _c.c_uint64, _u64p, _u64p]),
     "fheaes_profile_enable": (_c.c_int, [_ctx, _c.c_int]),
     "fheaes_profile_reset": (_c.c_int, [_ctx]),
     "fheaes_profile_read": (_c.c_int, [_ctx, _c.c_int, _dp, _u64p, _u64p]),
@@ -426,6 +439,66 @@ class Engine:
         self._check(fn(self._h, _ptr(round_keys)[0], key_bits, n_keys, kob.ctypes.data_as(_u32p), cnt.ctypes.data_as(_u64p),
                        dat.ctypes.data_as(_u64p) if dat is not None else None, len(cnt), _ptr(state_out)[0], self._space(round_keys, state_out)))
 
+    # CBC-MAC chains and CCM (include/fheaes.h): the per-stream tables are host arrays, the ciphertext arrays live in one memory space
+    def aes_cbc_mac_keyed(self, round_keys, key_bits: int, n_keys: int, key_of_stream, stream_blocks, clear, enc, enc_bytes, init, mac_out,
+                          packed: bool = False):
+        """stream s chains stream_blocks[s] blocks: `clear` [blocks][16] bytes, optionally plus the first enc_bytes[b] bytes of enc[b];
+        init [n_streams][16][8][kN+1] or None; mac_out [n_streams][16][8][kN+1]"""
+        sb = np.ascontiguousarray(np.asarray(stream_blocks, dtype=np.uint32).reshape(-1))
+        kos = key_indices(key_of_stream, len(sb))
+        clr = np.ascontiguousarray(np.asarray(clear, dtype=np.uint8).reshape(-1, 16))
+        if len(clr) != int(sb.sum()):
+            raise ValueError("%d clear blocks for streams of %d blocks in all" % (len(clr), int(sb.sum())))
+        eb = None
+        if enc is not None:
+            eb = np.ascontiguousarray(np.asarray(enc_bytes, dtype=np.uint8).reshape(-1))
+            if len(eb) != len(clr):
+                raise ValueError("one enc_bytes entry per block expected")
+        fn = self._lib.fheaes_aes_cbc_mac_keyed_packed if packed else self._lib.fheaes_aes_cbc_mac_keyed
+        self._check(fn(self._h, _ptr(round_keys)[0], key_bits, n_keys, len(sb), kos.ctypes.data_as(_u32p), sb.ctypes.data_as(_u32p), clr.ctypes.data_as(_u8p),
+                       _ptr(enc)[0], eb.ctypes.data_as(_u8p) if eb is not None else None, _ptr(init)[0], _ptr(mac_out)[0],
+                       self._space(round_keys, enc, init, mac_out)))
+
+    def aes_ccm_open_keyed(self, round_keys, key_bits: int, n_keys: int, key_of_stream, head_blocks, head, ctr0, payload_bytes, ciphertext, tags, tag_bytes,
+                           plaintext_out, valid_out, packed: bool = False):
+        """fheaes_aes_ccm_open_keyed / _packed: head_blocks[s] u128 blocks of `head` (B0, then the AAD blocks) per stream, ctr0 one u128 per
+        stream, payload_bytes[s] bytes of `ciphertext` per stream, tags [n][16] bytes with tag_bytes[s] real ones"""
+        hb = np.ascontiguousarray(np.asarray(head_blocks, dtype=np.uint32).reshape(-1))
+        kos = key_indices(key_of_stream, len(hb))
+        hd, c0 = u128_pairs(head), u128_pairs(ctr0)
+        pb = np.ascontiguousarray(np.asarray(payload_bytes, dtype=np.uint64).reshape(-1))
+        ct = np.frombuffer(bytes(ciphertext) + b"\x00", dtype=np.uint8)            # never an empty buffer
+        tg = np.ascontiguousarray(np.asarray(tags, dtype=np.uint8).reshape(-1, 16))
+        tb = np.ascontiguousarray(np.asarray(tag_bytes, dtype=np.uint32).reshape(-1))
+        if not (len(c0) == len(pb) == len(tg) == len(tb) == len(hb)) or len(hd) != int(hb.sum()) or len(ct) - 1 != int(pb.sum()):
+            raise ValueError("the per-stream arrays of a CCM call do not agree")
+        fn = self._lib.fheaes_aes_ccm_open_keyed_packed if packed else self._lib.fheaes_aes_ccm_open_keyed
+        self._check(fn(self._h, _ptr(round_keys)[0], key_bits, n_keys, len(hb), kos.ctypes.data_as(_u32p), hb.ctypes.data_as(_u32p), hd.ctypes.data_as(_u64p),
+                       c0.ctypes.data_as(_u64p), pb.ctypes.data_as(_u64p), ct.ctypes.data_as(_u8p), tg.ctypes.data_as(_u8p), tb.ctypes.data_as(_u32p),
+                       _ptr(plaintext_out)[0], _ptr(valid_out)[0], self._space(round_keys, plaintext_out, valid_out)))
+
+    def mac_link(self, state, first: bool, init, enc, src_block, enc_bytes, clear):
+        """K6 alone (fheaes_mac_link): state[s] = (first ? init[s] or 0 : state[s]) + the first enc_bytes[s] bytes of enc[src_block[s]]
+        (MAC_NONE: none) + trivial(clear[s]); state, init [n][16][8][kN+1], enc [n_enc][16][8][kN+1]; needs no keys"""
+        n = int(state.shape[0])
+        clr = np.ascontiguousarray(np.asarray(clear, dtype=np.uint8).reshape(n, 16))
+        src = eb = None
+        if enc is not None:
+            src = np.ascontiguousarray(np.asarray(src_block, dtype=np.uint32).reshape(n))
+            eb = np.ascontiguousarray(np.asarray(enc_bytes, dtype=np.uint8).reshape(n))
+        self._check(self._lib.fheaes_mac_link(self._h, _ptr(state)[0], n, int(bool(first)), _ptr(init)[0], _ptr(enc)[0], int(enc.shape[0]) if enc is not None else 0,
+                                              src.ctypes.data_as(_u32p) if src is not None else None, eb.ctypes.data_as(_u8p) if eb is not None else None,
+                                              clr.ctypes.data_as(_u8p), self._space(state, init, enc)))
+
+    def xts_whiten(self, dst, src, tweaks, tweak_of_block, clear):
+        """K6 alone (fheaes_xts_whiten): dst[b] = (src[b] or 0) + tweaks[tweak_of_block[b]] + trivial(clear[b]); src may be dst or None,
+        clear [n][16] bytes or None; needs no keys"""
+        n = int(dst.shape[0])
+        tab = key_indices(tweak_of_block, n)
+        clr = None if clear is None else np.ascontiguousarray(np.asarray(clear, dtype=np.uint8).reshape(n, 16))
+        self._check(self._lib.fheaes_xts_whiten(self._h, _ptr(dst)[0], _ptr(src)[0], _ptr(tweaks)[0], int(tweaks.shape[0]), tab.ctypes.data_as(_u32p),
+                                                clr.ctypes.data_as(_u8p) if clr is not None else None, n, self._space(dst, src, tweaks)))
+
     # packed round keys: a store [n_keys][G][(k+1)N], G = round_keys_packed_glwes(key_bits); the keyed calls read their key words from it
     def pack_round_keys(self, round_keys, key_bits: int, n_keys: int, packed_out):
         self._check(self._lib.fheaes_pack_round_keys(self._h, _ptr(round_keys)[0], key_bits, n_keys, _ptr(packed_out)[0], self._space(round_keys, packed_out)))
@@ -619,6 +692,23 @@ def aes_xts_plan(n_units: int, blocks_per_unit: int, first_block: int, n_blocks:
     if rc != 0:
         raise FheAesError(rc, "fheaes_aes_xts_plan: key_bits must be 128 or 256, blocks_per_unit in 1..2^20, and n_units cover the blocks")
     return {"segments": seg.value, "tweak_refresh_bytes": ref.value, "cipher_bytes": cip.value, "max_terms": terms.value}
+
+
+def aes_mac_plan(stream_blocks, payload_blocks=None) -> dict:
+    """fheaes_aes_mac_plan (host only, no GPU): what a CBC-MAC chain over streams of these lengths runs -- {"steps", "n_active" (live streams
+    per cipher pass), "chained_blocks" (their sum), "public_blocks" (2 n + the payload blocks of a CCM call; 0 without payload_blocks)}"""
+    sb = np.ascontiguousarray(np.asarray(stream_blocks, dtype=np.uint32).reshape(-1))
+    pb = None if payload_blocks is None else np.ascontiguousarray(np.asarray(payload_blocks, dtype=np.uint32).reshape(-1))
+    if pb is not None and len(pb) != len(sb):
+        raise ValueError("one payload block count per stream expected")
+    cap = int(sb.max()) if len(sb) else 0
+    act = np.zeros(max(cap, 1), dtype=np.uint64)
+    steps, pub, chained = _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
+    rc = load_library().fheaes_aes_mac_plan(sb.ctypes.data_as(_u32p), pb.ctypes.data_as(_u32p) if pb is not None else None, len(sb), _c.byref(steps),
+                                            act.ctypes.data_as(_u64p), len(act), _c.byref(pub), _c.byref(chained))
+    if rc != 0:
+        raise FheAesError(rc, "fheaes_aes_mac_plan: at most 2^20 streams of at most 2^16 blocks, payload blocks within them")
+    return {"steps": steps.value, "n_active": [int(x) for x in act[:steps.value]], "chained_blocks": chained.value, "public_blocks": pub.value}
 
 
 def round_keys_packed_glwes(key_bits: int) -> int:

@@ -219,6 +219,74 @@ def xts_decrypt(key1, key2, sector: int, data: bytes, first_block: int = 0) -> b
     return _xts(key1, key2, sector, data, first_block, aes_decrypt_block)
 
 
+def cbc_mac(key, blocks, init: int = 0) -> int:
+    """the raw CBC-MAC chain X_{i+1} = E_K(X_i ^ B_i) from X_0 = init over u128 blocks; no blocks: init"""
+    x = init
+    for b in blocks:
+        x = aes_encrypt_block(key, x ^ b)
+    return x
+
+
+CCM_TAG_LENGTHS = (4, 6, 8, 10, 12, 14, 16)
+
+
+def ccm_blocks(nonce: bytes, aad: bytes, payload_len: int, tag_len: int):
+    """SP 800-38C A.2 / A.3 formatting -> (B0, the encoded and zero-padded AAD blocks, the counter blocks Ctr_0 .. Ctr_m), all u128 with
+    byte 0 the most significant; m = ceil(payload_len / 16).  q = 15 - len(nonce), nonce of 7 .. 13 bytes, tag_len in 4, 6, .., 16; the
+    AAD length takes 2 bytes below 0xFF00, else FF FE and 4 bytes (the 10-byte form for 2^32 bytes and more is refused)"""
+    nonce, aad = bytes(nonce), bytes(aad)
+    if not 7 <= len(nonce) <= 13:
+        raise ValueError("a CCM nonce has 7 to 13 bytes, got %d" % len(nonce))
+    if tag_len not in CCM_TAG_LENGTHS:
+        raise ValueError("a CCM tag has 4, 6, .., 16 bytes, got %r" % (tag_len,))
+    q = 15 - len(nonce)
+    if payload_len < 0 or payload_len >> (8 * q):
+        raise ValueError("a payload of %d bytes does not fit the %d-byte length field" % (payload_len, q))
+    if len(aad) >= 1 << 32:
+        raise ValueError("the 10-byte AAD length form (2^32 bytes and more) is not offered")
+    b0 = bytes([64 * (len(aad) > 0) + 8 * ((tag_len - 2) // 2) + (q - 1)]) + nonce + payload_len.to_bytes(q, "big")
+    enc = b""
+    if aad:
+        enc = len(aad).to_bytes(2, "big") if len(aad) < 0xFF00 else b"\xff\xfe" + len(aad).to_bytes(4, "big")
+        enc += aad
+        enc += bytes(-len(enc) % 16)
+    m = (payload_len + 15) // 16
+    ctr = [int.from_bytes(bytes([q - 1]) + nonce + i.to_bytes(q, "big"), "big") for i in range(m + 1)]
+    return int.from_bytes(b0, "big"), [int.from_bytes(enc[i:i + 16], "big") for i in range(0, len(enc), 16)], ctr
+
+
+def _ccm_tag(key, b0: int, aad_blocks, payload: bytes, s0: int, tag_len: int) -> bytes:
+    padded = payload + bytes(-len(payload) % 16)
+    x = cbc_mac(key, [b0] + list(aad_blocks) + [int.from_bytes(padded[i:i + 16], "big") for i in range(0, len(padded), 16)])
+    return (x ^ s0).to_bytes(16, "big")[:tag_len]
+
+
+def _ccm_ctr(key, ctr, data: bytes) -> bytes:
+    out = bytearray()
+    for i in range(0, len(data), 16):
+        ks = aes_encrypt_block(key, ctr[1 + i // 16]).to_bytes(16, "big")
+        out += bytes(a ^ b for a, b in zip(data[i:i + 16], ks))
+    return bytes(out)
+
+
+def ccm_encrypt(key, nonce: bytes, aad: bytes, payload: bytes, tag_len: int) -> bytes:
+    """SP 800-38C 6.1 (RFC 3610): ciphertext || tag, the tag MSB_t(X_last ^ E_K(Ctr_0))"""
+    payload = bytes(payload)
+    b0, aad_blocks, ctr = ccm_blocks(nonce, aad, len(payload), tag_len)
+    return _ccm_ctr(key, ctr, payload) + _ccm_tag(key, b0, aad_blocks, payload, aes_encrypt_block(key, ctr[0]), tag_len)
+
+
+def ccm_decrypt(key, nonce: bytes, aad: bytes, ciphertext_and_tag: bytes, tag_len: int):
+    """SP 800-38C 6.2: the payload, or None where the tag does not verify"""
+    data = bytes(ciphertext_and_tag)
+    if tag_len not in CCM_TAG_LENGTHS or len(data) < tag_len:
+        raise ValueError("ciphertext || tag is shorter than its tag of %r bytes" % (tag_len,))
+    ct, tag = data[:-tag_len], data[-tag_len:]
+    b0, aad_blocks, ctr = ccm_blocks(nonce, aad, len(ct), tag_len)
+    payload = _ccm_ctr(key, ctr, ct)
+    return payload if _ccm_tag(key, b0, aad_blocks, payload, aes_encrypt_block(key, ctr[0]), tag_len) == tag else None
+
+
 def aes128_encrypt_block(key: int, block: int) -> int:
     return aes_encrypt_block(key, block)
 

@@ -493,3 +493,144 @@ static int aes_xts_decrypt_dev(fheaes_ctx *c, const KeySets &dw1, const KeySets 
     TRY(launch_xts_whiten(c, out, out, fresh, tab, nullptr, n_blocks, 3));                  // InvS output + dw[0] + T
     return FHEAES_OK;
 }
+
+// ---- CBC-MAC chains over many streams, and CCM decryption with its tag check (SP 800-38C, RFC 3610) ----------------------------------
+// X_{i+1} = E_K(X_i ^ B_i) is serial inside a stream and parallel across streams, and every block has its own key (KeySets.of_block), so
+// step i of ALL live streams is one ordinary windowed cipher pass.  The host sorts the streams by chain length, descending and stable: the
+// live set of step i is the prefix [0, n_active(i)) of one state array [n_streams][128][kN+1] and nothing is compacted.  Between two
+// passes one mac_link_kernel launch adds the step's blocks -- clear bytes as trivial ciphertexts, and encrypted addends byte-exact (a partial
+// last block adds its real bytes only).  Levels against the guard's 5: a cipher or public-call output is 2; a link of public blocks goes
+// into AddRoundKey at 2 + 1 = 3, a link of encrypted addends at X (2) + P (2) + round key = 5, the figure aes_decrypt_eq_schedule runs at;
+// a caller's addend or init counts as 2.
+#define MAC_MAX_STREAMS FHEAES_MAC_MAX_STREAMS
+#define MAC_MAX_STREAM_BLOCKS FHEAES_MAC_MAX_STREAM_BLOCKS
+static_assert(MAC_NONE == FHEAES_MAC_NONE && sizeof(MacSlot) == 32, "fheaes.h's 'none' is the kernel's, and a link record is 32 bytes");
+
+struct MacPlan {
+    std::vector<uint32_t> order, slot_of;       // sorted slot -> stream of the call, and back
+    std::vector<uint64_t> n_active;             // per chain step: the streams still running (a prefix of the slots)
+    uint64_t chained = 0;                       // cipher blocks of the whole chain: the sum of n_active
+};
+
+static void mac_plan(const uint32_t *len, uint64_t n, MacPlan &pl)
+{
+    pl.order.resize(n); pl.slot_of.resize(n);
+    for (uint64_t s = 0; s < n; ++s) pl.order[s] = (uint32_t)s;
+    std::stable_sort(pl.order.begin(), pl.order.end(), [&](uint32_t x, uint32_t y) { return len[x] > len[y]; });
+    for (uint64_t j = 0; j < n; ++j) pl.slot_of[pl.order[j]] = (uint32_t)j;
+    const uint32_t steps = n ? len[pl.order[0]] : 0;
+    pl.n_active.assign(steps, 0);
+    pl.chained = 0;
+    uint64_t live = n;
+    for (uint32_t i = 0; i < steps; ++i) {
+        while (live && len[pl.order[live - 1]] <= i) --live;
+        pl.n_active[i] = live;
+        pl.chained += live;
+    }
+}
+
+// What a chain uploads and runs: the key of every sorted slot, the link records of every step one behind the other (and behind them
+// whatever records the caller runs after the chain), and per step where its records start, how many slots it links and encrypts, and
+// the level it declares.  Step 0 links ALL slots from where the chain starts (a stream of length 0 keeps its start: it is copied, not
+// skipped); the later steps link their live prefix in place.
+struct MacChain {
+    std::vector<uint32_t> key_of_slot;
+    std::vector<MacSlot> slots;
+    struct Step { size_t first; uint64_t n_link, n_active; uint32_t level; };
+    std::vector<Step> steps;
+};
+
+static MacSlot mac_slot(uint32_t a, uint32_t b, uint32_t b_bytes, uint32_t out_bytes, const uint8_t *clear, uint32_t clear_bytes = 16)
+{
+    MacSlot r{a, b_bytes ? b : MAC_NONE, b_bytes, out_bytes, {}};
+    if (clear) memcpy(r.clear, clear, clear_bytes);
+    return r;
+}
+
+// stream s chains len[s] blocks: block i adds `clear` (16 bytes) and, where `enc` is given, the first enc_bytes bytes of block enc of the
+// addend buffer; block(s, i, clear16, &enc, &enc_bytes) says which.  start(s): the block of the start buffer stream s begins from, or
+// MAC_NONE (a zero state).
+template <class Block, class Start>
+static void mac_chain(const MacPlan &pl, const uint32_t *len, const uint32_t *key_of_stream, uint64_t n, Block block, Start start, MacChain &ch)
+{
+    ch.key_of_slot.resize(n);
+    for (uint64_t j = 0; j < n; ++j) ch.key_of_slot[j] = key_of_stream[pl.order[j]];
+    const size_t steps = std::max<size_t>(pl.n_active.size(), n ? 1 : 0);
+    for (size_t i = 0; i < steps; ++i) {
+        const uint64_t n_active = i < pl.n_active.size() ? pl.n_active[i] : 0, n_link = i == 0 ? n : n_active;
+        bool any_a = i > 0, any_b = false;
+        const size_t first = ch.slots.size();
+        for (uint64_t j = 0; j < n_link; ++j) {
+            const uint32_t s = pl.order[j], a = i == 0 ? start(s) : (uint32_t)j;
+            uint8_t clear[16] = {};
+            uint32_t enc = MAC_NONE, enc_bytes = 0;
+            if (len[s] > i) block(s, (uint32_t)i, clear, &enc, &enc_bytes);
+            if (enc == MAC_NONE) enc_bytes = 0;
+            any_a = any_a || a != MAC_NONE;
+            any_b = any_b || enc_bytes;
+            ch.slots.push_back(mac_slot(a, enc, enc_bytes, 16, clear));
+        }
+        ch.steps.push_back({first, n_link, n_active, (any_a ? 2u : 0u) + (any_b ? 2u : 0u) + 1u});
+    }
+}
+
+// Runs the chain over `state` [n_streams][128][kN+1] (sorted slots): start / enc are the buffers the records' a (step 0) and b index.
+// One upload for the whole call through the pinned buffer (FHEAES_DEVICE calls only enqueue); *recs: the records on the device.
+static int cbc_mac_dev(fheaes_ctx *c, const KeySets &rk, int nr, uint64_t n_keys, const MacChain &ch, const uint64_t *start, const uint64_t *enc, uint64_t *state,
+                       const MacSlot **recs)
+{
+    const size_t key_bytes = (ch.key_of_slot.size() * sizeof(uint32_t) + 31) / 32 * 32, rec_bytes = ch.slots.size() * sizeof(MacSlot);
+    TRY(upload_pinned(c, key_bytes + rec_bytes, key_bytes + rec_bytes, [&](uint8_t *pin) {
+        memcpy(pin, ch.key_of_slot.data(), ch.key_of_slot.size() * sizeof(uint32_t));
+        memcpy(pin + key_bytes, ch.slots.data(), rec_bytes);
+    }));
+    *recs = (const MacSlot *)((const uint8_t *)c->ws_misc.p + key_bytes);
+    KeySets keys = rk;
+    keys.of_block = n_keys > 1 ? (const uint32_t *)c->ws_misc.p : nullptr;
+    const AesSchedule sch = aes_encrypt_schedule(nr);
+    for (size_t i = 0; i < ch.steps.size(); ++i) {
+        const MacChain::Step &st = ch.steps[i];
+        TRY(launch_mac_link(c, state, i == 0 ? start : state, enc, *recs + st.first, st.n_link, st.level, "a CBC-MAC link (chaining value + block + the round key that follows)"));
+        if (st.n_active) TRY(aes_run_dev(c, keys, state, st.n_active, sch));
+    }
+    return FHEAES_OK;
+}
+
+// A CCM call on the host: the public batch is [the payload counters Ctr_1.. of every stream, stream after stream | B0 of every stream |
+// Ctr_0 of every stream] with data [C_1.. | none | none], so its outputs are the plaintext blocks P, then X_1, then S0.  The chain of
+// stream s runs from X_1 over its `aad` public blocks and then its payload blocks, whose addend is the encrypted P (the last one with its
+// real bytes).  Behind the chain's records: n_streams tag records (the caller's order) and the payload records that bring P to the output.
+struct CcmCall {
+    uint64_t n = 0, payload_blocks = 0;
+    std::vector<uint64_t> pub_blocks, pub_data;         // (hi, lo) pairs
+    std::vector<uint32_t> pub_key, len;
+    MacPlan plan;
+    MacChain chain;
+    size_t tag0 = 0, pt0 = 0;                           // where the tag and the payload records start
+};
+
+// ws_tmp_a: the public call's outputs; ws_tmp_b: the chain's state; ws_tmp_c: the tag difference, then the bits of the second WoPBS.
+// valid_out [n][kN+1]: row 0 of the second WoPBS.  The tag check: diff = X_final + S0 + trivial(tag) is zero on its first 8t rows iff the
+// tag is right (level 4); WoPBS 1 (8 bits, every byte of the 16: rows from 8t on are zero words) gives byte != 0, WoPBS 2 takes those 16
+// bits as one input and gives 1 on input 0.
+static int ccm_open_dev(fheaes_ctx *c, const KeySets &rk, int nr, uint64_t n_keys, const CcmCall &cc, const PublicPlan &pp, uint64_t *plaintext_out,
+                        uint64_t *valid_out)
+{
+    const uint64_t sw = AES_BLOCK_BITS * c->big1, n = cc.n, row = (uint64_t)c->big1 * 8;
+    TRY(ensure(c, c->ws_tmp_a, (cc.payload_blocks + 2 * n) * sw * 8));
+    TRY(ensure(c, c->ws_tmp_b, n * sw * 8));
+    TRY(ensure(c, c->ws_tmp_c, n * sw * 8));
+    TRY(ensure(c, c->ws_vp, n * sw * 8));
+    uint64_t *pub = (uint64_t *)c->ws_tmp_a.p, *state = (uint64_t *)c->ws_tmp_b.p, *diff = (uint64_t *)c->ws_tmp_c.p;
+    TRY(aes_public_dev(c, public_forward(), rk, pp, nr, pub));
+    const MacSlot *recs = nullptr;
+    TRY(cbc_mac_dev(c, rk, nr, n_keys, cc.chain, pub, pub, state, &recs));
+    TRY(launch_mac_link(c, diff, state, pub, recs + cc.tag0, n, 4, "the CCM tag difference (X + S0 + tag)"));
+    TRY(launch_mac_link(c, plaintext_out, nullptr, pub, recs + cc.pt0, cc.payload_blocks, 2, "the CCM plaintext"));
+    uint64_t *vp = (uint64_t *)c->ws_vp.p;
+    TRY(wopbs_dev(c, diff, 16 * n, 8, c->lut_tag_d[0], 1, 0, vp));
+    HIP_TRY(c, hipMemcpy2DAsync(diff, row, vp, 8 * row, row, 16 * n, hipMemcpyDeviceToDevice, c->stream));
+    TRY(wopbs_dev(c, diff, n, 16, c->lut_tag_d[1], 1, 0, vp));
+    HIP_TRY(c, hipMemcpy2DAsync(valid_out, row, vp, 16 * row, row, n, hipMemcpyDeviceToDevice, c->stream));
+    return FHEAES_OK;
+}

@@ -5,6 +5,7 @@
 // src/server/sbox/many_wopbs.rs:31-116): it owns the device copies of the keys, the workspace,
 // the precomputed AES LUT sets, and enqueues the kernels of kern_*.h on one HIP stream.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -244,6 +245,12 @@ int fheaes_create(const fheaes_params *params, int device, fheaes_ctx **out)
         if ((e = hipMalloc((void **)&c->lutset_d[s], h.size() * 8)) != hipSuccess) return bail("hipMalloc", e);
         if ((e = hipMemcpy(c->lutset_d[s], h.data(), h.size() * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail("hipMemcpy", e);
     }
+    for (int w = 0; w < 2; ++w) {        // the CCM tag check's two LUTs
+        std::vector<uint64_t> h;
+        build_tag_lut_host(w, h);
+        if ((e = hipMalloc((void **)&c->lut_tag_d[w], h.size() * 8)) != hipSuccess) return bail("hipMalloc", e);
+        if ((e = hipMemcpy(c->lut_tag_d[w], h.data(), h.size() * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail("hipMemcpy", e);
+    }
     *out = c;
     return FHEAES_OK;
 }
@@ -260,6 +267,7 @@ void fheaes_destroy(fheaes_ctx *c)
     if (c->pin) (void)hipHostFree(c->pin);
     if (c->pin_ev) (void)hipEventDestroy(c->pin_ev);
     for (int s = 0; s < LUTSET_COUNT; ++s) if (c->lutset_d[s]) (void)hipFree(c->lutset_d[s]);
+    for (uint64_t *p : c->lut_tag_d) if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;                            // every DevBuf of the context (workspace, staging) frees itself here
 }
@@ -1152,6 +1160,264 @@ int fheaes_aes_xts_plan(uint64_t n_units, uint64_t blocks_per_unit, uint64_t fir
     for (const auto &seg : pl.segments) for (const XtsGather &g : seg)
         for (uint32_t j = g.off0; j < g.off0 + g.n_off; ++j) for (uint32_t i = 0; i < 128; ++i) terms = std::max(terms, xts_tweak_row(j, i, s));
     *max_terms = terms;
+    return FHEAES_OK;
+}
+
+// K6 alone: the XTS whitening on caller buffers (the yardstick of the CBC-MAC link, tools/ccm.py)
+int fheaes_xts_whiten(fheaes_ctx *c, uint64_t *dst, const uint64_t *src, const uint64_t *tweaks, uint64_t n_tweaks, const uint32_t *tweak_of_block, const uint8_t *clear,
+                      uint64_t n_blocks, int memspace)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    if (n_blocks == 0) return FHEAES_OK;
+    if (!dst || !tweaks || !tweak_of_block) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    if (n_blocks > MAC_MAX_STREAMS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %u (got %llu)", MAC_MAX_STREAMS, (unsigned long long)n_blocks);
+    for (uint64_t b = 0; b < n_blocks; ++b)
+        if (tweak_of_block[b] >= n_tweaks)
+            return c->fail(FHEAES_ERR_INVALID, "tweak_of_block[%llu] = %u, but there are %llu tweaks", (unsigned long long)b, tweak_of_block[b], (unsigned long long)n_tweaks);
+    const uint64_t sw = 16ull * 8 * c->big1, bytes = n_blocks * sw * 8;
+    if (overlap(tweaks, n_tweaks * sw * 8, dst, bytes) || (src && src != dst && overlap(src, bytes, dst, bytes))) return c->fail(FHEAES_ERR_INVALID, "dst overlaps an input");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged st(c, memspace);
+    const bool in_place = src == dst;
+    if (in_place) TRY(st.inout(dst, bytes, &dst)); else TRY(st.out(dst, bytes, &dst));
+    if (in_place) src = dst; else if (src) TRY(st.in(src, bytes, &src));
+    TRY(st.in(tweaks, n_tweaks * sw * 8, &tweaks));
+    const size_t tab_bytes = n_blocks * sizeof(uint32_t), all_bytes = tab_bytes + (clear ? 16 * n_blocks : 0);
+    TRY(upload_pinned(c, all_bytes, all_bytes, [&](uint8_t *pin) {
+        memcpy(pin, tweak_of_block, tab_bytes);
+        if (clear) memcpy(pin + tab_bytes, clear, 16 * n_blocks);
+    }));
+    TRY(launch_xts_whiten(c, dst, src, tweaks, (const uint32_t *)c->ws_misc.p, clear ? (const uint8_t *)c->ws_misc.p + tab_bytes : nullptr, n_blocks, src ? 3 : 2));
+    return st.finish();
+}
+
+// ---- CBC-MAC chains and CCM decryption --------------------------------------------------------
+// what every call on streams checks first: the keys and the table that names one per stream
+static int check_streams(fheaes_ctx *c, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams, const uint32_t *key_of_stream)
+{
+    TRY(check_key_bits(c, key_bits));
+    TRY(check_n_keys(c, n_keys));
+    if (n_streams > MAC_MAX_STREAMS) return c->fail(FHEAES_ERR_INVALID, "n_streams must be at most %u (got %llu)", MAC_MAX_STREAMS, (unsigned long long)n_streams);
+    return check_key_of_block(c, key_of_stream, n_streams, n_keys);
+}
+
+static int aes_cbc_mac(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams, const uint32_t *key_of_stream,
+                       const uint32_t *stream_blocks, const uint8_t *clear, const uint64_t *enc, const uint8_t *enc_bytes, const uint64_t *init, uint64_t *mac_out,
+                       int memspace, bool packed)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!round_keys || !key_of_stream || !stream_blocks || !mac_out || (enc != nullptr) != (enc_bytes != nullptr)) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_streams(c, key_bits, n_keys, n_streams, key_of_stream));
+    std::vector<uint64_t> off(n_streams + 1, 0);
+    for (uint64_t s = 0; s < n_streams; ++s) {
+        if (stream_blocks[s] > MAC_MAX_STREAM_BLOCKS)
+            return c->fail(FHEAES_ERR_INVALID, "stream_blocks[%llu] = %u: a stream chains at most %u blocks", (unsigned long long)s, stream_blocks[s], MAC_MAX_STREAM_BLOCKS);
+        off[s + 1] = off[s] + stream_blocks[s];
+    }
+    const uint64_t total = off[n_streams];
+    if (total && !clear) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    if (total > 0xFFFFFFFEull) return c->fail(FHEAES_ERR_INVALID, "a call chains fewer than 2^32 - 1 blocks");
+    if (enc_bytes) for (uint64_t b = 0; b < total; ++b)
+        if (enc_bytes[b] > 16) return c->fail(FHEAES_ERR_INVALID, "enc_bytes[%llu] = %u: a block has 16 bytes", (unsigned long long)b, (unsigned)enc_bytes[b]);
+    if (n_streams == 0) return FHEAES_OK;
+    const int nr = aes_rounds(key_bits);
+    const KeyStore ks = key_store(c, key_bits, packed);
+    const uint64_t sw = 16ull * 8 * c->big1, keys_bytes = n_keys * ks.key_words * 8, out_bytes = n_streams * sw * 8;
+    if (overlap(round_keys, keys_bytes, mac_out, out_bytes) || (enc && overlap(enc, total * sw * 8, mac_out, out_bytes)) || (init && overlap(init, out_bytes, mac_out, out_bytes)))
+        return c->fail(FHEAES_ERR_INVALID, "mac_out overlaps an input");
+    MacPlan pl;
+    mac_plan(stream_blocks, n_streams, pl);
+    MacChain ch;
+    mac_chain(pl, stream_blocks, key_of_stream, n_streams, [&](uint32_t s, uint32_t i, uint8_t *clr, uint32_t *e, uint32_t *eb) {
+        const uint64_t b = off[s] + i;
+        memcpy(clr, clear + 16 * b, 16);
+        if (enc) { *e = (uint32_t)b; *eb = enc_bytes[b]; }
+    }, [&](uint32_t s) { return init ? s : MAC_NONE; }, ch);
+    const size_t out0 = ch.slots.size();                                   // behind the chain: the results in the caller's order
+    for (uint64_t s = 0; s < n_streams; ++s) ch.slots.push_back(mac_slot(pl.slot_of[s], MAC_NONE, 0, 16, nullptr));
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged st(c, memspace);
+    TRY(st.in(round_keys, keys_bytes, &round_keys));
+    if (enc) TRY(st.in(enc, total * sw * 8, &enc));
+    if (init) TRY(st.in(init, out_bytes, &init));
+    TRY(st.out(mac_out, out_bytes, &mac_out));
+    TRY(ensure(c, c->ws_tmp_b, out_bytes));
+    uint64_t *state = (uint64_t *)c->ws_tmp_b.p;
+    const MacSlot *recs = nullptr;
+    TRY(cbc_mac_dev(c, KeySets{round_keys, nullptr, ks.key_words, ks.glwes}, nr, n_keys, ch, init, enc, state, &recs));
+    TRY(launch_mac_link(c, mac_out, state, nullptr, recs + out0, n_streams, 2, "the CBC-MAC results in the caller's order"));
+    return st.finish();
+}
+
+int fheaes_aes_cbc_mac_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams, const uint32_t *key_of_stream,
+                             const uint32_t *stream_blocks, const uint8_t *clear, const uint64_t *enc, const uint8_t *enc_bytes, const uint64_t *init,
+                             uint64_t *mac_out, int memspace)
+{
+    return aes_cbc_mac(c, round_keys, key_bits, n_keys, n_streams, key_of_stream, stream_blocks, clear, enc, enc_bytes, init, mac_out, memspace, false);
+}
+
+int fheaes_aes_cbc_mac_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams,
+                                    const uint32_t *key_of_stream, const uint32_t *stream_blocks, const uint8_t *clear, const uint64_t *enc, const uint8_t *enc_bytes,
+                                    const uint64_t *init, uint64_t *mac_out, int memspace)
+{
+    return aes_cbc_mac(c, packed_round_keys, key_bits, n_keys, n_streams, key_of_stream, stream_blocks, clear, enc, enc_bytes, init, mac_out, memspace, true);
+}
+
+// K6 alone: one link of a chain on caller buffers (the kernel's test and measurement entry)
+int fheaes_mac_link(fheaes_ctx *c, uint64_t *state, uint64_t n_slots, int first, const uint64_t *init, const uint64_t *enc, uint64_t n_enc, const uint32_t *src_block,
+                    const uint8_t *enc_bytes, const uint8_t *clear, int memspace)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    if (n_slots == 0) return FHEAES_OK;
+    if (!state || !clear || (enc && (!src_block || !enc_bytes))) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    if (n_slots > MAC_MAX_STREAMS) return c->fail(FHEAES_ERR_INVALID, "n_slots must be at most %u (got %llu)", MAC_MAX_STREAMS, (unsigned long long)n_slots);
+    if (init && !first) return c->fail(FHEAES_ERR_INVALID, "init belongs to the first link of a chain");
+    const uint64_t sw = 16ull * 8 * c->big1, bytes = n_slots * sw * 8;
+    bool any_b = false;
+    std::vector<MacSlot> recs(n_slots);
+    for (uint64_t s = 0; s < n_slots; ++s) {
+        uint32_t b = MAC_NONE, eb = 0;
+        if (enc) {
+            if (enc_bytes[s] > 16) return c->fail(FHEAES_ERR_INVALID, "enc_bytes[%llu] = %u: a block has 16 bytes", (unsigned long long)s, (unsigned)enc_bytes[s]);
+            if (src_block[s] != MAC_NONE && src_block[s] >= n_enc)
+                return c->fail(FHEAES_ERR_INVALID, "src_block[%llu] = %u, but enc has %llu blocks", (unsigned long long)s, src_block[s], (unsigned long long)n_enc);
+            b = src_block[s]; eb = b == MAC_NONE ? 0 : enc_bytes[s];
+        }
+        any_b = any_b || eb;
+        recs[s] = mac_slot(first ? (init ? (uint32_t)s : MAC_NONE) : (uint32_t)s, b, eb, 16, clear + 16 * s);
+    }
+    if ((init && overlap(init, bytes, state, bytes)) || (enc && overlap(enc, n_enc * sw * 8, state, bytes))) return c->fail(FHEAES_ERR_INVALID, "state overlaps an input");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged st(c, memspace);
+    TRY(st.inout(state, bytes, &state));
+    if (init) TRY(st.in(init, bytes, &init));
+    if (enc) TRY(st.in(enc, n_enc * sw * 8, &enc));
+    const size_t rec_bytes = recs.size() * sizeof(MacSlot);
+    TRY(upload_pinned(c, rec_bytes, rec_bytes, [&](uint8_t *pin) { memcpy(pin, recs.data(), rec_bytes); }));
+    const uint32_t level = (!first || init ? 2u : 0u) + (any_b ? 2u : 0u) + 1u;
+    TRY(launch_mac_link(c, state, first ? init : state, enc, (const MacSlot *)c->ws_misc.p, n_slots, level, "a CBC-MAC link (chaining value + block + the round key that follows)"));
+    return st.finish();
+}
+
+static int aes_ccm_open(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams, const uint32_t *key_of_stream,
+                        const uint32_t *head_blocks, const uint64_t *head_hi_lo, const uint64_t *ctr0_hi_lo, const uint64_t *payload_bytes, const uint8_t *ciphertext,
+                        const uint8_t *tags, const uint32_t *tag_bytes, uint64_t *plaintext_out, uint64_t *valid_out, int memspace, bool packed)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!round_keys || !key_of_stream || !head_blocks || !head_hi_lo || !ctr0_hi_lo || !payload_bytes || !tags || !tag_bytes || !valid_out)
+        return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_streams(c, key_bits, n_keys, n_streams, key_of_stream));
+    const uint64_t n = n_streams;
+    CcmCall cc;
+    cc.n = n;
+    cc.len.resize(n);
+    std::vector<uint64_t> poff(n + 1, 0), hoff(n + 1, 0), boff(n + 1, 0);      // payload blocks, head blocks, payload bytes before stream s
+    for (uint64_t s = 0; s < n; ++s) {
+        const uint32_t t = tag_bytes[s], c0 = u128_byte(ctr0_hi_lo + 2 * s, 0);
+        if (t < 4 || t > 16 || (t & 1)) return c->fail(FHEAES_ERR_INVALID, "tag_bytes[%llu] = %u: a CCM tag has 4, 6, .., 16 bytes", (unsigned long long)s, t);
+        if (head_blocks[s] < 1 || head_blocks[s] > MAC_MAX_STREAM_BLOCKS)
+            return c->fail(FHEAES_ERR_INVALID, "head_blocks[%llu] = %u: B0 and at most %u AAD blocks", (unsigned long long)s, head_blocks[s], MAC_MAX_STREAM_BLOCKS - 1);
+        const uint32_t f0 = u128_byte(head_hi_lo + 2 * hoff[s], 0);
+        if (c0 < 1 || c0 > 7) return c->fail(FHEAES_ERR_INVALID, "stream %llu: the flags byte of Ctr_0 is q - 1 = %u; a nonce has 7..13 bytes (q = 2..8)", (unsigned long long)s, c0);
+        const uint32_t q = c0 + 1;
+        if ((f0 & 7) != c0 || ((f0 >> 3) & 7) != (t - 2) / 2 || f0 >= 128 || ((f0 >> 6) & 1) != (head_blocks[s] > 1 ? 1u : 0u))
+            return c->fail(FHEAES_ERR_INVALID, "stream %llu: the flags byte %#x of B0 does not say q = %u, t = %u, %s AAD", (unsigned long long)s, f0, q, t, head_blocks[s] > 1 ? "some" : "no");
+        if (q < 8 && ((ctr0_hi_lo[2 * s + 1] & ((1ull << (8 * q)) - 1)) != 0 || payload_bytes[s] >> (8 * q)))
+            return c->fail(FHEAES_ERR_INVALID, "stream %llu: the counter field of Ctr_0 must be zero and the payload shorter than 2^%u bytes", (unsigned long long)s, 8 * q);
+        if (q == 8 && ctr0_hi_lo[2 * s + 1] != 0) return c->fail(FHEAES_ERR_INVALID, "stream %llu: the counter field of Ctr_0 must be zero", (unsigned long long)s);
+        const uint64_t m = payload_bytes[s] / 16 + (payload_bytes[s] % 16 ? 1 : 0);
+        if (payload_bytes[s] > 16ull * MAC_MAX_STREAM_BLOCKS || head_blocks[s] - 1 + m > MAC_MAX_STREAM_BLOCKS)
+            return c->fail(FHEAES_ERR_INVALID, "stream %llu chains %llu blocks; at most %u", (unsigned long long)s, (unsigned long long)(head_blocks[s] - 1 + m), MAC_MAX_STREAM_BLOCKS);
+        cc.len[s] = (uint32_t)(head_blocks[s] - 1 + m);
+        poff[s + 1] = poff[s] + m; hoff[s + 1] = hoff[s] + head_blocks[s]; boff[s + 1] = boff[s] + payload_bytes[s];
+    }
+    if (n == 0) return FHEAES_OK;
+    const uint64_t M = poff[n], n_pub = M + 2 * n;
+    cc.payload_blocks = M;
+    if (M && (!ciphertext || !plaintext_out)) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    if (n_pub > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "a call has at most %llu public blocks", (unsigned long long)PUBLIC_MAX_BLOCKS);
+    const int nr = aes_rounds(key_bits);
+    const KeyStore ks = key_store(c, key_bits, packed);
+    const uint64_t sw = 16ull * 8 * c->big1, keys_bytes = n_keys * ks.key_words * 8, pt_bytes = M * sw * 8, valid_bytes = n * c->big1 * 8ull;
+    if (overlap(round_keys, keys_bytes, valid_out, valid_bytes) || (M && (overlap(round_keys, keys_bytes, plaintext_out, pt_bytes) || overlap(plaintext_out, pt_bytes, valid_out, valid_bytes))))
+        return c->fail(FHEAES_ERR_INVALID, "plaintext_out, valid_out and the round keys overlap");
+    // the public batch: [Ctr_1.. of every stream | B0 | Ctr_0], data [C_1.. | 0 | 0]
+    cc.pub_blocks.assign(2 * n_pub, 0); cc.pub_data.assign(2 * n_pub, 0); cc.pub_key.resize(n_pub);
+    for (uint64_t s = 0; s < n; ++s) {
+        for (uint64_t i = 0; i < poff[s + 1] - poff[s]; ++i) {
+            const uint64_t b = poff[s] + i, have = std::min<uint64_t>(16, payload_bytes[s] - 16 * i);
+            cc.pub_blocks[2 * b] = ctr0_hi_lo[2 * s]; cc.pub_blocks[2 * b + 1] = ctr0_hi_lo[2 * s + 1] + i + 1;
+            for (uint64_t p = 0; p < have; ++p) cc.pub_data[2 * b + (p >> 3)] |= (uint64_t)ciphertext[boff[s] + 16 * i + p] << (8 * (7 - (p & 7)));
+            cc.pub_key[b] = key_of_stream[s];
+        }
+        memcpy(&cc.pub_blocks[2 * (M + s)], head_hi_lo + 2 * hoff[s], 16);
+        memcpy(&cc.pub_blocks[2 * (M + n + s)], ctr0_hi_lo + 2 * s, 16);
+        cc.pub_key[M + s] = cc.pub_key[M + n + s] = key_of_stream[s];
+    }
+    mac_plan(cc.len.data(), n, cc.plan);
+    mac_chain(cc.plan, cc.len.data(), key_of_stream, n, [&](uint32_t s, uint32_t i, uint8_t *clr, uint32_t *e, uint32_t *eb) {
+        const uint32_t aad = head_blocks[s] - 1;
+        if (i < aad) { for (int p = 0; p < 16; ++p) clr[p] = (uint8_t)u128_byte(head_hi_lo + 2 * (hoff[s] + 1 + i), p); return; }
+        const uint64_t j = i - aad;
+        *e = (uint32_t)(poff[s] + j);
+        *eb = (uint32_t)std::min<uint64_t>(16, payload_bytes[s] - 16 * j);
+    }, [&](uint32_t s) { return (uint32_t)(M + s); }, cc.chain);
+    cc.tag0 = cc.chain.slots.size();
+    for (uint64_t s = 0; s < n; ++s) cc.chain.slots.push_back(mac_slot(cc.plan.slot_of[s], (uint32_t)(M + n + s), 16, tag_bytes[s], tags + 16 * s, tag_bytes[s]));
+    cc.pt0 = cc.chain.slots.size();
+    for (uint64_t s = 0; s < n; ++s)
+        for (uint64_t i = 0; i < poff[s + 1] - poff[s]; ++i)
+            cc.chain.slots.push_back(mac_slot(MAC_NONE, (uint32_t)(poff[s] + i), (uint32_t)std::min<uint64_t>(16, payload_bytes[s] - 16 * i), 16, nullptr));
+    PublicPlan pp;
+    public_plan(public_forward(), cc.pub_blocks.data(), cc.pub_data.data(), cc.pub_key.data(), n_pub, nr, pp);
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged st(c, memspace);
+    TRY(st.in(round_keys, keys_bytes, &round_keys));
+    if (M) TRY(st.out(plaintext_out, pt_bytes, &plaintext_out));
+    TRY(st.out(valid_out, valid_bytes, &valid_out));
+    TRY(ccm_open_dev(c, KeySets{round_keys, nullptr, ks.key_words, ks.glwes}, nr, n_keys, cc, pp, plaintext_out, valid_out));
+    return st.finish();
+}
+
+int fheaes_aes_ccm_open_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams, const uint32_t *key_of_stream,
+                              const uint32_t *head_blocks, const uint64_t *head_hi_lo, const uint64_t *ctr0_hi_lo, const uint64_t *payload_bytes, const uint8_t *ciphertext,
+                              const uint8_t *tags, const uint32_t *tag_bytes, uint64_t *plaintext_out, uint64_t *valid_out, int memspace)
+{
+    return aes_ccm_open(c, round_keys, key_bits, n_keys, n_streams, key_of_stream, head_blocks, head_hi_lo, ctr0_hi_lo, payload_bytes, ciphertext, tags, tag_bytes,
+                        plaintext_out, valid_out, memspace, false);
+}
+
+int fheaes_aes_ccm_open_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams,
+                                     const uint32_t *key_of_stream, const uint32_t *head_blocks, const uint64_t *head_hi_lo, const uint64_t *ctr0_hi_lo,
+                                     const uint64_t *payload_bytes, const uint8_t *ciphertext, const uint8_t *tags, const uint32_t *tag_bytes, uint64_t *plaintext_out,
+                                     uint64_t *valid_out, int memspace)
+{
+    return aes_ccm_open(c, packed_round_keys, key_bits, n_keys, n_streams, key_of_stream, head_blocks, head_hi_lo, ctr0_hi_lo, payload_bytes, ciphertext, tags, tag_bytes,
+                        plaintext_out, valid_out, memspace, true);
+}
+
+int fheaes_aes_mac_plan(const uint32_t *stream_blocks, const uint32_t *payload_blocks, uint64_t n_streams, uint64_t *steps, uint64_t *n_active_out, uint64_t n_active_cap,
+                        uint64_t *public_blocks, uint64_t *chained_blocks)
+{
+    if ((n_streams && !stream_blocks) || !steps || !public_blocks || !chained_blocks || n_streams > MAC_MAX_STREAMS) return FHEAES_ERR_INVALID;
+    uint64_t pub = payload_blocks ? 2 * n_streams : 0;
+    for (uint64_t s = 0; s < n_streams; ++s) {
+        if (stream_blocks[s] > MAC_MAX_STREAM_BLOCKS || (payload_blocks && payload_blocks[s] > stream_blocks[s])) return FHEAES_ERR_INVALID;
+        if (payload_blocks) pub += payload_blocks[s];
+    }
+    MacPlan pl;
+    mac_plan(stream_blocks, n_streams, pl);
+    if (n_active_out) {
+        if (n_active_cap < pl.n_active.size()) return FHEAES_ERR_INVALID;
+        for (size_t i = 0; i < pl.n_active.size(); ++i) n_active_out[i] = pl.n_active[i];
+    }
+    *steps = pl.n_active.size(); *public_blocks = pub; *chained_blocks = pl.chained;
     return FHEAES_OK;
 }
 

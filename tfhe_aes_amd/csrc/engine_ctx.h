@@ -67,6 +67,7 @@ struct fheaes_ctx {
     double2 *tw_d = nullptr;            // the transform's table T[17 k1 + b] = psi^(b (4 k1 + 1)) (fft_dev.h)
     uint64_t *lutset_d[LUTSET_COUNT] = {};
     int lutset_n[LUTSET_COUNT] = {};
+    uint64_t *lut_tag_d[2] = {};        // the CCM tag check (build_tag_lut_host): [0] 8 bits -> byte != 0, [1] 16 bits -> input == 0
     // workspace
     DevBuf ws_small, ws_pbs, ws_ggsw, ws_ggswf, ws_vp, ws_tmp_a, ws_tmp_b, ws_tmp_c, ws_luts, ws_misc, ws_digits, ws_park, ws_park_owner, ws_tree;
     DevBuf ws_park_pattern, ws_park_record;
@@ -217,8 +218,8 @@ struct Staged {
     fheaes_ctx *c;
     const bool host;
     int used = 0;
-    void *back_host = nullptr, *back_dev = nullptr;      // the output to copy back (host memory only)
-    size_t back_bytes = 0;
+    struct Back { void *host, *dev; size_t bytes; } back[2] = {};      // the outputs to copy back (host memory only)
+    int n_back = 0;
     Staged(fheaes_ctx *ctx, int memspace) : c(ctx), host(memspace != FHEAES_DEVICE) {}
     ~Staged() { if (host) (void)hipStreamSynchronize(c->stream); }      // host pointers are borrowed for the duration of the call only
     // *dev: where the kernels find argument p of `bytes` bytes
@@ -230,7 +231,10 @@ struct Staged {
         TRY(ensure(c, c->stage[used], bytes ? bytes : 8));
         *dev = (T *)c->stage[used++].p;
         if (read) HIP_TRY(c, hipMemcpyAsync((void *)*dev, p, bytes, hipMemcpyHostToDevice, c->stream));
-        if (written) { back_host = (void *)p; back_dev = (void *)*dev; back_bytes = bytes; }
+        if (written) {
+            if (n_back >= 2) return c->fail(FHEAES_ERR_INVALID, "internal: too many staged outputs");
+            back[n_back++] = {(void *)p, (void *)*dev, bytes};
+        }
         return FHEAES_OK;
     }
     template <class T> int in(const T *p, size_t bytes, const T **dev) { return arg(p, bytes, dev, true, false); }
@@ -239,7 +243,7 @@ struct Staged {
     int finish()
     {
         if (!host) return FHEAES_OK;
-        if (back_host) HIP_TRY(c, hipMemcpyAsync(back_host, back_dev, back_bytes, hipMemcpyDeviceToHost, c->stream));
+        for (int i = 0; i < n_back; ++i) HIP_TRY(c, hipMemcpyAsync(back[i].host, back[i].dev, back[i].bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return FHEAES_OK;
     }

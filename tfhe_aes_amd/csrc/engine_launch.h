@@ -465,6 +465,21 @@ int launch_xts_whiten(fheaes_ctx *c, uint64_t *dst, const uint64_t *src, const u
     return FHEAES_OK;
 }
 
+// mac_link_kernel over n_slots records (a device table); `level`: the nominal-noise ciphertexts one word sums where it is used next -- a
+// link that goes into the cipher counts the round key that aes_run_dev adds first.  In place (a == dst) only with records whose a is
+// their own slot: the callers build them so.  Units: blocks.
+int launch_mac_link(fheaes_ctx *c, uint64_t *dst, const uint64_t *a, const uint64_t *b, const MacSlot *slots, uint64_t n_slots, uint32_t level, const char *what)
+{
+    if (n_slots == 0) return FHEAES_OK;
+    TRY(noise_guard(c, level, what));
+    StageScope sc(c, FHEAES_STAGE_LINEAR, n_slots);
+    const unsigned gx = (unsigned)std::min<uint64_t>((128ull * c->big1 + 255) / 256, 64);
+    dim3 grid(gx, (unsigned)std::min<uint64_t>(n_slots, std::max<uint64_t>(1, 16384 / gx)));
+    hipLaunchKernelGGL(mac_link_kernel, grid, dim3(256), 0, c->stream, dst, a, b, slots, n_slots, c->big1);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
 // ---- packing (fheaes_pack_bits, fheaes_unpack_bits) ---------------------------------------------------------------------------
 static_assert(PACK_N == FHE_N && PACK_N % PACK_FOLD_ROWS == 0, "kern_linear.h's packing kernels are written for N = 512");
 

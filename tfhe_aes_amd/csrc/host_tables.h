@@ -117,6 +117,18 @@ int build_lutset_host(int which, std::vector<uint64_t> &out)
     return n;
 }
 
+// The two LUTs of the CCM tag check, one LUT each.  which = 0: 8 bits in, output bit 0 = (byte != 0); which = 1: 16 bits in (one per tag
+// byte), output bit 0 = (input == 0), the validity bit.  The other output bits are 0.  Returns the input width.
+uint32_t build_tag_lut_host(int which, std::vector<uint64_t> &out)
+{
+    const uint32_t nb = which ? 16 : 8;
+    std::vector<uint64_t> f((size_t)1 << nb);
+    for (size_t x = 0; x < f.size(); ++x) f[x] = which ? (x == 0) : (x != 0);
+    out.assign((size_t)nb * lut_row_words(nb), 0);
+    gen_lut_host(nb, f.data(), out.data());
+    return nb;
+}
+
 const int MC_ENC[4][4] = {{1, 2, 0, 0}, {0, 1, 2, 0}, {0, 0, 1, 2}, {2, 0, 0, 1}};
 const int MC_DEC[4][4] = {{3, 1, 2, 0}, {0, 3, 1, 2}, {2, 0, 3, 1}, {1, 2, 0, 3}};
 

@@ -207,6 +207,49 @@ __global__ __launch_bounds__(256) void xts_whiten_kernel(uint64_t *dst, const ui
     }
 }
 
+// ---- CBC-MAC (SP 800-38C CCM): the link between two chain steps -------------------------------------------------------------------------
+// One record per slot (a stream of the chain, or an output block): which block of `a` and of `b` it sums (MAC_NONE: none), how many
+// leading bytes of the `b` block are real (0..16: a partial last payload block contributes its real bytes, the zero padding nothing),
+// how many leading bytes of the output are written as sums (the rest are zero words: a truncated tag), and 16 clear bytes.
+#define MAC_NONE 0xFFFFFFFFu
+struct MacSlot {
+    uint32_t a, b;
+    uint32_t b_bytes, out_bytes;
+    uint8_t clear[16];
+};
+
+// dst[s][row] = row < 8 out_bytes[s] ? a[a_s][row] + (row < 8 b_bytes[s] ? b[b_s][row] : 0) + trivial(bit `row` of clear[s]) : 0 for every
+// slot s < n_slots; rows are [16][8], bit LSB first inside a byte, the trivial term is bit << 63 on the body word.  dst, a, b: blocks of
+// 128 lwe_words words; a null or a_s == MAC_NONE: no term (the first step of a chain without an init), and the same for b.  In place
+// (a == dst) where every a_s == s: a lane reads the word it writes.  With the records' indices this one body is the chain link (dst = a =
+// the state, b = the encrypted addends), the first link (a = where the chain starts), the tag difference (dst in the caller's order, a =
+// the state by sorted slot, b = S0, clear = the received tag, out_bytes = t) and the copies that put results in the caller's order.
+// Lanes on consecutive words, 8-byte accesses (rows of kN + 1 words are 8-byte aligned and no more); one launch whatever n_slots is.
+__global__ __launch_bounds__(256) void mac_link_kernel(uint64_t *dst, const uint64_t *a, const uint64_t *b, const MacSlot *slots, uint64_t n_slots,
+                                                       uint32_t lwe_words)
+{
+    const uint32_t byte_words = 8 * lwe_words;
+    const uint64_t words_per_block = 16ull * byte_words;
+    for (uint64_t s = blockIdx.y; s < n_slots; s += gridDim.y) {
+        const MacSlot *sl = slots + s;
+        const uint32_t ia = sl->a, ib = sl->b;
+        const uint64_t *ab = a && ia != MAC_NONE ? a + (uint64_t)ia * words_per_block : nullptr;
+        const uint64_t *bb = b && ib != MAC_NONE ? b + (uint64_t)ib * words_per_block : nullptr;
+        const uint32_t b_words = sl->b_bytes * byte_words, out_words = sl->out_bytes * byte_words;
+        uint64_t *db = dst + s * words_per_block;
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < words_per_block; i += gridDim.x * blockDim.x) {
+            uint64_t v = 0;
+            if (i < out_words) {
+                if (ab) v = ab[i];
+                if (bb && i < b_words) v += bb[i];
+                const uint32_t p = i / byte_words;
+                v = add_trivial_bit(v, sl->clear[p], i - p * byte_words, lwe_words);
+            }
+            db[i] = v;
+        }
+    }
+}
+
 // Rows of bytes moved between strided sets, one set per AES key: the word operations of the key expansion over all keys at once (RotWord,
 // w[i-1] or the SubWord result + w[i-Nk] + Rcon, placing refreshed words at their stride) and the strided copies of the round-key
 // conversion.  For key j and byte q < n_bytes:

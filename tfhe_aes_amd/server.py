@@ -8,6 +8,7 @@ Same names, argument meaning and error behaviour as
   plus aes_decrypt_public / aes_cbc_decrypt / aes_cfb_decrypt / aes_gcm_ctr: the decryption direction of the public calls and the
   modes whose decryption works on public blocks -- CBC, CFB-128 and the 32-bit counter of GCM;
   plus aes_xts_decrypt: XTS-AES (IEEE 1619) decryption of a public ciphertext, the per-block tweaks derived under encryption;
+  plus aes_cbc_mac_streams / aes_ccm_decrypt: CBC-MAC chains over many streams and AES-CCM decryption with an encrypted `valid` bit;
   plus the *_many / *_keyed / aes_ctr_streams methods: many AES keys under one FHE key, round keys [n_keys][Nr+1][16][8][kN+1] and a key
   index per block, word for word the single-key methods key by key; plus packed round keys: pack_round_keys / unpack_round_keys /
   aes_key_expansion_packed, and a PackedRoundKeys -- 3 / 4 / 4 GLWEs per key -- wherever a method takes round keys, the key words read
@@ -152,6 +153,42 @@ def xts_args(sectors, ciphertext, unit_bytes: int, first_block: int):
     if len(sectors) < n_units:
         raise ValueError("blocks %d .. %d lie in %d data units, %d sectors given" % (first_block, first_block + len(ct), n_units, len(sectors)))
     return sectors, bpu, ct
+
+
+def ccm_args(messages):
+    """aes_ccm_decrypt's messages (key_index, nonce, aad, ciphertext, tag) -> the per-stream arrays of the C call, which sees blocks: the
+    formatting (SP 800-38C A.2 / A.3: aes_clear.ccm_blocks) is done here.  A dict: key_of_stream, head_blocks (1 + AAD blocks), head (B0 and
+    the AAD blocks, stream after stream), ctr0, payload_bytes, ciphertext (concatenated), tags [n][16] (zero-padded), tag_bytes, and
+    block_of_message (where each message's plaintext blocks start in the output; its last entry is the total)"""
+    from .aes_clear import ccm_blocks
+
+    a = {"key_of_stream": [], "head_blocks": [], "head": [], "ctr0": [], "payload_bytes": [], "ciphertext": b"", "tags": [], "tag_bytes": [],
+         "block_of_message": [0]}
+    for key_index, nonce, aad, ciphertext, tag in messages:
+        ciphertext, tag = bytes(ciphertext), bytes(tag)
+        b0, aad_blocks, ctr = ccm_blocks(nonce, aad, len(ciphertext), len(tag))
+        a["key_of_stream"].append(int(key_index))
+        a["head_blocks"].append(1 + len(aad_blocks))
+        a["head"] += [b0] + aad_blocks
+        a["ctr0"].append(ctr[0])
+        a["payload_bytes"].append(len(ciphertext))
+        a["ciphertext"] += ciphertext
+        a["tags"].append(list(tag) + [0] * (16 - len(tag)))
+        a["tag_bytes"].append(len(tag))
+        a["block_of_message"].append(a["block_of_message"][-1] + len(ctr) - 1)
+    return a
+
+
+def _shards_by_cost(costs, g: int):
+    """whole streams to g contexts, contiguous and balanced by cost: a stream goes to the context in whose g-th of the total cost its
+    midpoint lies; shard i is [lo, hi), possibly empty"""
+    total, run, hi = sum(costs), 0, [0] * g
+    for s, c in enumerate(costs):
+        hi[min(g - 1, (2 * run + c) * g // (2 * total)) if total else 0] = s + 1
+        run += c
+    for i in range(1, g):
+        hi[i] = max(hi[i], hi[i - 1])
+    return [(hi[i - 1] if i else 0, hi[i]) for i in range(g)]
 
 
 def cbc_stream_blocks(streams):
@@ -517,6 +554,78 @@ class Server:
         key_of_block, blocks, chain = cbc_stream_blocks(streams)
         return self.aes_decrypt_public_keyed(dec_round_keys, key_of_block, blocks, data=chain, out=out)
 
+    # ---- CBC-MAC chains and CCM: the engine's integrity results --------------------------------
+    def _stream_keys(self, round_keys, what="round keys"):
+        if isinstance(round_keys, PackedRoundKeys):
+            prk = self._check_packed(round_keys)
+            return prk.data, prk.key_bits, prk.n_keys, True
+        if round_keys.ndim == 4:
+            round_keys = round_keys[None]
+        bits, n_keys = _many_key_bits(round_keys, what)
+        return round_keys, bits, n_keys, False
+
+    def aes_cbc_mac_streams(self, round_keys, streams, init=None, out=None):
+        """Raw CBC-MAC chains X_{i+1} = E_K(X_i ^ B_i) over many streams in one call: `streams` is a list of (key_index, blocks) or
+        (key_index, blocks, enc, enc_bytes) -- `blocks` the stream's PUBLIC blocks (u128 or 16 bytes each), `enc` an optional encrypted
+        addend [len(blocks)][16][8][kN+1] of which block i contributes its first enc_bytes[i] bytes (None: all 16).  `init`
+        [n_streams][16][8][kN+1]: where the chains start (None: zero).  Returns the final X of every stream, [n_streams][16][8][kN+1] (or
+        `out`), in the caller's order.  The streams are sorted by length; step i of all live streams is one cipher pass
+        (include/fheaes.h: fheaes_aes_cbc_mac_keyed).  round_keys: [n_keys][Nr+1][16][8][kN+1], one key's [Nr+1][16][8][kN+1], or a
+        PackedRoundKeys."""
+        words, bits, n_keys, packed = self._stream_keys(round_keys)
+        streams = [tuple(st) + (None, None) * (len(st) == 2) for st in streams]
+        keys, lens, clear, enc_bytes = [], [], [], []
+        any_enc = any(st[2] is not None for st in streams)
+        for key_index, blocks, enc, eb in streams:
+            blocks = _cipher_blocks(blocks)
+            keys.append(int(key_index)); lens.append(len(blocks))
+            clear += [list(_u128(b, "a block").to_bytes(16, "big")) for b in blocks]
+            if enc is None:
+                enc_bytes += [0] * len(blocks)
+            else:
+                if tuple(enc.shape) != (len(blocks), 16, 8, self.params.big1):
+                    raise ValueError("enc must be [%d][16][8][kN+1], got %s" % (len(blocks), tuple(enc.shape)))
+                eb = [16] * len(blocks) if eb is None else [int(x) for x in eb]
+                if len(eb) != len(blocks) or any(not 0 <= x <= 16 for x in eb):
+                    raise ValueError("enc_bytes: one count in 0..16 per block expected")
+                enc_bytes += eb
+        n = len(streams)
+        out = self._many_out(words, (n, 16, 8, self.params.big1), out)
+        if n == 0:
+            return out
+        enc_all = None
+        if any_enc:
+            enc_all = _empty_like(words, (max(sum(lens), 1), 16, 8, self.params.big1))
+            enc_all[...] = 0
+            at = 0
+            for (_, _, enc, _), k in zip(streams, lens):
+                if enc is not None and k:
+                    enc_all[at:at + k] = enc
+                at += k
+            if not isinstance(enc_all, np.ndarray):
+                import torch
+
+                torch.cuda.current_stream(enc_all.device).synchronize()       # torch filled it on its stream; the engine reads it on its own
+        self.engine.aes_cbc_mac_keyed(words, bits, n_keys, keys, lens, clear, enc_all, enc_bytes if any_enc else None, init, out, packed=packed)
+        return out
+
+    def aes_ccm_decrypt(self, round_keys, messages, out=None, valid_out=None):
+        """AES-CCM decryption (SP 800-38C, RFC 3610) of PUBLIC messages (key_index, nonce, aad, ciphertext, tag) under encrypted keys, the
+        tag compared under encryption.  Returns (plaintext [total_blocks][16][8][kN+1], valid [n][kN+1], block_of_message): message i's
+        plaintext is blocks block_of_message[i] .. block_of_message[i + 1], rows beyond its length zero words, and valid[i] decrypts
+        (Client.decrypt_bits) to 1 iff its tag verifies.  The plaintext is not gated on `valid`.  One public call (B0, the counters), a
+        CBC-MAC chain over all messages step by step, and two WoPBS for the comparison (include/fheaes.h: fheaes_aes_ccm_open_keyed).  The tag
+        length is len(tag) (4, 6, .., 16), the nonce has 7..13 bytes.  round_keys as aes_cbc_mac_streams'."""
+        words, bits, n_keys, packed = self._stream_keys(round_keys)
+        a = ccm_args(messages)
+        n, total = len(a["tag_bytes"]), a["block_of_message"][-1]
+        out = self._many_out(words, (total, 16, 8, self.params.big1), out)
+        valid_out = self._many_out(words, (n, self.params.big1), valid_out)
+        if n:
+            self.engine.aes_ccm_open_keyed(words, bits, n_keys, a["key_of_stream"], a["head_blocks"], a["head"], a["ctr0"], a["payload_bytes"], a["ciphertext"],
+                                           a["tags"], a["tag_bytes"], out if total else None, valid_out, packed=packed)
+        return out, valid_out, a["block_of_message"]
+
     def _public_out(self, round_keys, n_blocks: int, out):
         return self._many_out(round_keys, (n_blocks, 16, 8, self.params.big1), out)
 
@@ -828,6 +937,29 @@ class ServerGroup:
         chains with the block before it"""
         key_of_block, blocks, chain = cbc_stream_blocks(streams)
         return self.aes_decrypt_public_keyed(dec_round_keys, key_of_block, blocks, data=chain)
+
+    def aes_cbc_mac_streams(self, round_keys, streams, init=None):
+        """Server.aes_cbc_mac_streams: whole streams per context, contiguous and balanced by block count; a shard needs nothing from
+        its neighbours"""
+        streams = [tuple(st) for st in streams]
+        out = _empty_like(_words(round_keys), (len(streams), 16, 8, self.params.big1))
+        shards = _shards_by_cost([len(_cipher_blocks(st[1])) + 1 for st in streams], len(self.servers))
+        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_cbc_mac_streams(
+            round_keys, streams[lo:hi], init=None if init is None else init[lo:hi], out=out[lo:hi])) for lo, hi in shards])
+        return out
+
+    def aes_ccm_decrypt(self, round_keys, messages):
+        """Server.aes_ccm_decrypt: whole messages per context, contiguous and balanced by chained plus public block count"""
+        messages = [tuple(m) for m in messages]
+        a = ccm_args(messages)
+        at, n = a["block_of_message"], len(messages)
+        out = _empty_like(_words(round_keys), (at[-1], 16, 8, self.params.big1))
+        valid = _empty_like(_words(round_keys), (n, self.params.big1))
+        cost = [a["head_blocks"][i] - 1 + 2 * (at[i + 1] - at[i]) + 2 for i in range(n)]
+        shards = _shards_by_cost(cost, len(self.servers))
+        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_ccm_decrypt(
+            round_keys, messages[lo:hi], out=out[at[lo]:at[hi]], valid_out=valid[lo:hi])) for lo, hi in shards])
+        return out, valid, at
 
     # packed round keys: a store is small, so every context reads the whole of it (as the keyed calls read all round keys); the cipher
     # methods above take a PackedRoundKeys wherever they take round keys, since every context's Server does
