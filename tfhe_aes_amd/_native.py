@@ -355,38 +355,40 @@ class Engine:
         self._check(self._lib.fheaes_add_scalar(self._h, _ptr(state)[0], n_blocks, cnt.ctypes.data_as(_u64p), self._space(state)))
 
     # public blocks / CTR with a public nonce: clear 128-bit values travel as host (hi, lo) pairs, as add_scalar's counters
+    def _public(self, symbol: str, round_keys, key_bits: int, mid, n_blocks: int, state_out, data=None, data_per: str = "block", keys=None):
+        """The one marshaller of the public-block calls: fn(ctx, round_keys, key_bits, [n_keys, key_of_block,] *mid, n_blocks, state_out,
+        memspace).  `mid`: what the C signature has between the keys and n_blocks, in its order -- a list of 128-bit values goes as (hi, lo)
+        pairs, an int as it is, and DATA stands for the optional `data` (None: NULL, else one block per block of the call).  `keys`:
+        (n_keys, key_of_block) of a keyed call."""
+        args = [] if keys is None else [keys[0], key_indices(keys[1], n_blocks)]
+        for m in mid:
+            if m is DATA:
+                m = None if data is None else u128_pairs(data)
+                if m is not None and len(m) != n_blocks:
+                    raise ValueError("one data block per %s expected" % data_per)
+            elif not isinstance(m, int):
+                m = u128_pairs(m)
+            args.append(m)
+        ptrs = [m.ctypes.data_as(_u32p if m.dtype == np.uint32 else _u64p) if isinstance(m, np.ndarray) else m for m in args]
+        self._check(getattr(self._lib, symbol)(self._h, _ptr(round_keys)[0], key_bits, *ptrs, n_blocks, _ptr(state_out)[0], self._space(round_keys, state_out)))
+
     def aes_encrypt_public_bits(self, round_keys, key_bits: int, blocks, state_out):
-        cnt = u128_pairs(blocks)
-        self._check(self._lib.fheaes_aes_encrypt_public_bits(self._h, _ptr(round_keys)[0], key_bits, cnt.ctypes.data_as(_u64p), len(cnt),
-                                                             _ptr(state_out)[0], self._space(round_keys, state_out)))
+        self._public("fheaes_aes_encrypt_public_bits", round_keys, key_bits, [blocks], len(blocks), state_out)
 
     def aes_ctr_bits(self, round_keys, key_bits: int, iv: int, first_block: int, data, n_blocks: int, state_out, counter_bits: int = 128):
         """counter_bits 128: SP 800-38A CTR (fheaes_aes_ctr_bits); 32: the counter field of GCM, `iv` being the initial counter block
         (fheaes_aes_ctr32_bits)"""
         if counter_bits not in (32, 128):
             raise ValueError("counter_bits must be 32 or 128, got %r" % (counter_bits,))
-        ivp = u128_pairs([iv])
-        dat = u128_pairs(data) if data is not None else None
-        if dat is not None and len(dat) != n_blocks:
-            raise ValueError("one data block per counter block expected")
-        fn = self._lib.fheaes_aes_ctr32_bits if counter_bits == 32 else self._lib.fheaes_aes_ctr_bits
-        self._check(fn(self._h, _ptr(round_keys)[0], key_bits, ivp.ctypes.data_as(_u64p), first_block,
-                       dat.ctypes.data_as(_u64p) if dat is not None else None, n_blocks, _ptr(state_out)[0], self._space(round_keys, state_out)))
+        self._public("fheaes_aes_ctr32_bits" if counter_bits == 32 else "fheaes_aes_ctr_bits", round_keys, key_bits, [[iv], first_block, DATA], n_blocks, state_out,
+                     data=data, data_per="counter block")
 
     # public blocks through the equivalent inverse cipher (dec_round_keys: aes_decryption_round_keys*), CBC decryption
     def aes_decrypt_public_bits(self, dec_round_keys, key_bits: int, blocks, data, state_out):
-        cnt = u128_pairs(blocks)
-        dat = u128_pairs(data) if data is not None else None
-        if dat is not None and len(dat) != len(cnt):
-            raise ValueError("one data block per block expected")
-        self._check(self._lib.fheaes_aes_decrypt_public_bits(self._h, _ptr(dec_round_keys)[0], key_bits, cnt.ctypes.data_as(_u64p),
-                                                             dat.ctypes.data_as(_u64p) if dat is not None else None, len(cnt), _ptr(state_out)[0],
-                                                             self._space(dec_round_keys, state_out)))
+        self._public("fheaes_aes_decrypt_public_bits", dec_round_keys, key_bits, [blocks, DATA], len(blocks), state_out, data=data)
 
     def aes_cbc_decrypt_bits(self, dec_round_keys, key_bits: int, iv, ciphertext, state_out):
-        ivp, cnt = u128_pairs([iv]), u128_pairs(ciphertext)
-        self._check(self._lib.fheaes_aes_cbc_decrypt_bits(self._h, _ptr(dec_round_keys)[0], key_bits, ivp.ctypes.data_as(_u64p), cnt.ctypes.data_as(_u64p),
-                                                          len(cnt), _ptr(state_out)[0], self._space(dec_round_keys, state_out)))
+        self._public("fheaes_aes_cbc_decrypt_bits", dec_round_keys, key_bits, [[iv], ciphertext], len(ciphertext), state_out)
 
     # XTS-AES decryption: dec_round_keys1 (key 1, decryption round keys) and round_keys2 (key 2, plain expansion), or two one-key packed
     # stores; `tweaks`: the 16-byte tweak block of units 0 .. as u128 (byte 0 = MSB), `ciphertext`: the blocks of the call
@@ -427,17 +429,8 @@ class Engine:
                          inverse: bool = False):
         """`packed`: round_keys is a packed store [n_keys][G][(k+1)N] (fheaes_aes_public_keyed_packed); `inverse`: the decryption
         direction, round_keys being decryption round keys (fheaes_aes_decrypt_public_keyed / _packed)"""
-        cnt = u128_pairs(blocks)
-        kob = key_indices(key_of_block, len(cnt))
-        dat = u128_pairs(data) if data is not None else None
-        if dat is not None and len(dat) != len(cnt):
-            raise ValueError("one data block per block expected")
-        if inverse:
-            fn = self._lib.fheaes_aes_decrypt_public_keyed_packed if packed else self._lib.fheaes_aes_decrypt_public_keyed
-        else:
-            fn = self._lib.fheaes_aes_public_keyed_packed if packed else self._lib.fheaes_aes_public_keyed
-        self._check(fn(self._h, _ptr(round_keys)[0], key_bits, n_keys, kob.ctypes.data_as(_u32p), cnt.ctypes.data_as(_u64p),
-                       dat.ctypes.data_as(_u64p) if dat is not None else None, len(cnt), _ptr(state_out)[0], self._space(round_keys, state_out)))
+        symbol = ("fheaes_aes_decrypt_public_keyed" if inverse else "fheaes_aes_public_keyed") + ("_packed" if packed else "")
+        self._public(symbol, round_keys, key_bits, [blocks, DATA], len(blocks), state_out, data=data, keys=(n_keys, key_of_block))
 
     # CBC-MAC chains and CCM (include/fheaes.h): the per-stream tables are host arrays, the ciphertext arrays live in one memory space
     def aes_cbc_mac_keyed(self, round_keys, key_bits: int, n_keys: int, key_of_stream, stream_blocks, clear, enc, enc_bytes, init, mac_out,
@@ -616,6 +609,9 @@ class Engine:
         out = np.empty((p.pbs_level, p.k + 1, p.k + 1, 256, 2), dtype=np.float64)
         self._check(self._lib.fheaes_read_bsk_fourier(self._h, i, out.ctypes.data_as(_dp)))
         return out
+
+
+DATA = object()          # Engine._public: the place of the optional clear data blocks in a call's arguments
 
 
 def u128_pairs(values) -> np.ndarray:

@@ -12,6 +12,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -660,50 +661,62 @@ static uint32_t packed_key_glwes(uint32_t key_bits)
     return nr ? (uint32_t)(((uint64_t)(nr + 1) * AES_BLOCK_BITS + FHE_N - 1) / FHE_N) : 0;
 }
 
-// The geometry of a cipher call's keys: words from one key to the next, in LWE form [Nr+1][16][8][kN+1] or in a packed store
-// [G][(k+1)N], and G (0: LWE form) -- KeySets' stride and packed_glwes
-struct KeyStore { uint64_t key_words; uint32_t glwes; };
-static KeyStore key_store(const fheaes_ctx *c, uint32_t key_bits, bool packed)
+// The round keys of a cipher call.  What the caller says: `words`, n_keys sets of them for AES-`key_bits`, in LWE form
+// [n_keys][Nr+1][16][8][kN+1] or (`packed`) a store [n_keys][G][(k+1)N] of fheaes_pack_round_keys, and key_of[i] (HOST, n_of entries), the
+// set block or stream i works under -- null: the one set of a single-key entry point.  resolve_keys() refuses what is wrong with that and
+// fills in the rest: Nr, the words from one key to the next (KeySets' stride), G (0: LWE form) and the bytes the call reads.
+struct RoundKeys {
+    const uint64_t *words; uint32_t key_bits; uint64_t n_keys; const uint32_t *key_of; uint64_t n_of; bool packed;
+    int nr = 0; uint32_t glwes = 0; uint64_t key_words = 0, keys_bytes = 0;
+    bool overlaps(const void *p, uint64_t bytes) const { return overlap(words, keys_bytes, p, bytes); }
+    int stage(Staged &s) { return s.in(words, keys_bytes, &words); }
+    // of_block: the DEVICE copy of key_of (aes_crypt); null where the call's plan carries the key of every block
+    KeySets sets(const uint32_t *of_block = nullptr) const { return {words, of_block, key_words, glwes}; }
+};
+// max_streams: the bound on n_of of the calls on streams (it sits where they have always refused it, in front of the table's entries)
+static int resolve_keys(fheaes_ctx *c, RoundKeys &k, uint64_t max_streams = ~0ull)
 {
-    if (packed) return {(uint64_t)packed_key_glwes(key_bits) * c->k1 * FHE_N, packed_key_glwes(key_bits)};
-    return {(uint64_t)(aes_rounds(key_bits) + 1) * 16 * 8 * c->big1, 0};
+    TRY(check_key_bits(c, k.key_bits));
+    TRY(check_n_keys(c, k.n_keys));
+    if (k.n_of > max_streams) return c->fail(FHEAES_ERR_INVALID, "n_streams must be at most %llu (got %llu)", (unsigned long long)max_streams, (unsigned long long)k.n_of);
+    if (k.key_of) TRY(check_key_of_block(c, k.key_of, k.n_of, k.n_keys));
+    k.nr = aes_rounds(k.key_bits);
+    k.glwes = k.packed ? packed_key_glwes(k.key_bits) : 0;
+    k.key_words = k.packed ? (uint64_t)k.glwes * c->k1 * FHE_N : (uint64_t)(k.nr + 1) * 16 * 8 * c->big1;
+    k.keys_bytes = k.n_keys * k.key_words * 8;
+    return FHEAES_OK;
 }
 
-// The three block ciphers.  key_of_block null: the single-key entry points (one set of round keys, no table); else block b runs under
-// round_keys[key_of_block[b]] of [n_keys][Nr+1][16][8][kN+1], the table going to the device through the pinned buffer (one key: no table either).
-// packed: round_keys is a packed store [n_keys][G][(k+1)N] (fheaes_pack_round_keys) and the linear layers read the key words from it.
-static int aes_crypt(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, uint64_t *state,
-                     uint64_t n_blocks, int memspace, AesDevFn dev, bool packed = false)
+static RoundKeys one_key(const uint64_t *words, uint32_t key_bits, bool packed = false) { return {words, key_bits, 1, nullptr, 0, packed}; }
+
+// The three block ciphers, in place.  keyed: block b runs under set key_of[b], the table going to the device through the pinned buffer
+// (one key: no table); else the single-key entry points, one set and no table.
+static int aes_crypt(fheaes_ctx *c, RoundKeys k, bool keyed, uint64_t *state, uint64_t n_blocks, int memspace, AesDevFn dev)
 {
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
     TRY(check_keys(c));
-    if (!round_keys || !state) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    TRY(check_key_bits(c, key_bits));
-    const int nr = aes_rounds(key_bits);
-    const KeyStore ks = key_store(c, key_bits, packed);
-    const uint64_t sw = 16ull * 8 * c->big1, keys_bytes = n_keys * ks.key_words * 8;
-    if (key_of_block) {
-        TRY(check_n_keys(c, n_keys));
-        TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
-        if (n_blocks == 0) return FHEAES_OK;
-    }
-    if (packed && overlap(round_keys, keys_bytes, state, n_blocks * sw * 8)) return c->fail(FHEAES_ERR_INVALID, "the packed round keys and the state overlap");
+    if (!k.words || (keyed && !k.key_of) || !state) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(resolve_keys(c, k));
+    if (keyed && n_blocks == 0) return FHEAES_OK;
+    const uint64_t sw = 16ull * 8 * c->big1;
+    if (k.packed && k.overlaps(state, n_blocks * sw * 8)) return c->fail(FHEAES_ERR_INVALID, "the packed round keys and the state overlap");
     HIP_TRY(c, hipSetDevice(c->device));
     Staged s(c, memspace);
-    TRY(s.in(round_keys, keys_bytes, &round_keys));
+    TRY(k.stage(s));
     TRY(s.inout(state, n_blocks * sw * 8, &state));
     const uint32_t *table = nullptr;
-    if (key_of_block && n_keys > 1) {
-        TRY(upload_pinned(c, n_blocks * sizeof(uint32_t), n_blocks * sizeof(uint32_t), [&](uint8_t *pin) { memcpy(pin, key_of_block, n_blocks * sizeof(uint32_t)); }));
+    if (keyed && k.n_keys > 1) {
+        TRY(upload_pinned(c, n_blocks * sizeof(uint32_t), n_blocks * sizeof(uint32_t), [&](uint8_t *pin) { memcpy(pin, k.key_of, n_blocks * sizeof(uint32_t)); }));
         table = (const uint32_t *)c->ws_misc.p;
     }
-    TRY(dev(c, KeySets{round_keys, table, ks.key_words, ks.glwes}, state, n_blocks, nr));
+    TRY(dev(c, k.sets(table), state, n_blocks, k.nr));
     return s.finish();
 }
 
 int fheaes_aes_encrypt_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks, int memspace)
 {
-    CtxLock lock__(c);
-    return aes_crypt(c, round_keys, key_bits, 1, nullptr, state, n_blocks, memspace, aes_encrypt_dev);
+    return aes_crypt(c, one_key(round_keys, key_bits), false, state, n_blocks, memspace, aes_encrypt_dev);
 }
 
 int fheaes_aes_encrypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace)
@@ -713,8 +726,7 @@ int fheaes_aes_encrypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *stat
 
 int fheaes_aes_decrypt_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks, int memspace)
 {
-    CtxLock lock__(c);
-    return aes_crypt(c, round_keys, key_bits, 1, nullptr, state, n_blocks, memspace, aes_decrypt_dev);
+    return aes_crypt(c, one_key(round_keys, key_bits), false, state, n_blocks, memspace, aes_decrypt_dev);
 }
 
 int fheaes_aes_decrypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *state, uint64_t n_blocks, int memspace)
@@ -725,8 +737,7 @@ int fheaes_aes_decrypt(fheaes_ctx *c, const uint64_t *round_keys, uint64_t *stat
 int fheaes_aes_decrypt_equivalent_bits(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t *state, uint64_t n_blocks,
                                        int memspace)
 {
-    CtxLock lock__(c);
-    return aes_crypt(c, dec_round_keys, key_bits, 1, nullptr, state, n_blocks, memspace, aes_decrypt_eq_dev);
+    return aes_crypt(c, one_key(dec_round_keys, key_bits), false, state, n_blocks, memspace, aes_decrypt_eq_dev);
 }
 
 int fheaes_aes_decrypt_equivalent(fheaes_ctx *c, const uint64_t *dec_round_keys, uint64_t *state, uint64_t n_blocks, int memspace)
@@ -734,54 +745,47 @@ int fheaes_aes_decrypt_equivalent(fheaes_ctx *c, const uint64_t *dec_round_keys,
     return fheaes_aes_decrypt_equivalent_bits(c, dec_round_keys, 128, state, n_blocks, memspace);
 }
 
-static int aes_crypt_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, uint64_t *state,
-                           uint64_t n_blocks, int memspace, AesDevFn dev, bool packed = false)
-{
-    CtxLock lock__(c);
-    TRY(check_keys(c));
-    if (!key_of_block) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    return aes_crypt(c, round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, dev, packed);
-}
-
 int fheaes_aes_encrypt_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, uint64_t *state,
                              uint64_t n_blocks, int memspace)
 {
-    return aes_crypt_keyed(c, round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_encrypt_dev);
+    return aes_crypt(c, {round_keys, key_bits, n_keys, key_of_block, n_blocks, false}, true, state, n_blocks, memspace, aes_encrypt_dev);
 }
 
 int fheaes_aes_decrypt_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, uint64_t *state,
                              uint64_t n_blocks, int memspace)
 {
-    return aes_crypt_keyed(c, round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_decrypt_dev);
+    return aes_crypt(c, {round_keys, key_bits, n_keys, key_of_block, n_blocks, false}, true, state, n_blocks, memspace, aes_decrypt_dev);
 }
 
 int fheaes_aes_decrypt_equivalent_keyed(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
                                         uint64_t *state, uint64_t n_blocks, int memspace)
 {
-    return aes_crypt_keyed(c, dec_round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_decrypt_eq_dev);
+    return aes_crypt(c, {dec_round_keys, key_bits, n_keys, key_of_block, n_blocks, false}, true, state, n_blocks, memspace, aes_decrypt_eq_dev);
 }
 
 int fheaes_aes_encrypt_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
                                     uint64_t *state, uint64_t n_blocks, int memspace)
 {
-    return aes_crypt_keyed(c, packed_round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_encrypt_dev, true);
+    return aes_crypt(c, {packed_round_keys, key_bits, n_keys, key_of_block, n_blocks, true}, true, state, n_blocks, memspace, aes_encrypt_dev);
 }
 
 int fheaes_aes_decrypt_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
                                     uint64_t *state, uint64_t n_blocks, int memspace)
 {
-    return aes_crypt_keyed(c, packed_round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_decrypt_dev, true);
+    return aes_crypt(c, {packed_round_keys, key_bits, n_keys, key_of_block, n_blocks, true}, true, state, n_blocks, memspace, aes_decrypt_dev);
 }
 
 int fheaes_aes_decrypt_equivalent_keyed_packed(fheaes_ctx *c, const uint64_t *packed_dec_round_keys, uint32_t key_bits, uint64_t n_keys,
                                                const uint32_t *key_of_block, uint64_t *state, uint64_t n_blocks, int memspace)
 {
-    return aes_crypt_keyed(c, packed_dec_round_keys, key_bits, n_keys, key_of_block, state, n_blocks, memspace, aes_decrypt_eq_dev, true);
+    return aes_crypt(c, {packed_dec_round_keys, key_bits, n_keys, key_of_block, n_blocks, true}, true, state, n_blocks, memspace, aes_decrypt_eq_dev);
 }
 
 // the two per-key calls: n_keys sets in, n_keys sets out
 static int dec_round_keys(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t *dec_round_keys, int memspace)
 {
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
     TRY(check_keys(c));
     if (!round_keys || !dec_round_keys) return c->fail(FHEAES_ERR_INVALID, "null pointer");
     TRY(check_key_bits(c, key_bits));
@@ -799,7 +803,6 @@ static int dec_round_keys(fheaes_ctx *c, const uint64_t *round_keys, uint32_t ke
 
 int fheaes_aes_decryption_round_keys_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t *dec_round_keys_out, int memspace)
 {
-    CtxLock lock__(c);
     return dec_round_keys(c, round_keys, key_bits, 1, dec_round_keys_out, memspace);
 }
 
@@ -811,12 +814,13 @@ int fheaes_aes_decryption_round_keys(fheaes_ctx *c, const uint64_t *round_keys, 
 int fheaes_aes_decryption_round_keys_batch(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t *dec_round_keys_out,
                                            int memspace)
 {
-    CtxLock lock__(c);
     return dec_round_keys(c, round_keys, key_bits, n_keys, dec_round_keys_out, memspace);
 }
 
 static int key_expansion(fheaes_ctx *c, const uint64_t *key, uint32_t key_bits, uint64_t n_keys, uint64_t *round_keys, int memspace)
 {
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
     TRY(check_keys(c));
     if (!key || !round_keys) return c->fail(FHEAES_ERR_INVALID, "null pointer");
     TRY(check_key_bits(c, key_bits));
@@ -833,7 +837,6 @@ static int key_expansion(fheaes_ctx *c, const uint64_t *key, uint32_t key_bits, 
 
 int fheaes_aes_key_expansion_bits(fheaes_ctx *c, const uint64_t *key, uint32_t key_bits, uint64_t *round_keys, int memspace)
 {
-    CtxLock lock__(c);
     return key_expansion(c, key, key_bits, 1, round_keys, memspace);
 }
 
@@ -844,12 +847,12 @@ int fheaes_aes_key_expansion(fheaes_ctx *c, const uint64_t *key, uint64_t *round
 
 int fheaes_aes_key_expansion_batch(fheaes_ctx *c, const uint64_t *keys, uint32_t key_bits, uint64_t n_keys, uint64_t *round_keys, int memspace)
 {
-    CtxLock lock__(c);
     return key_expansion(c, keys, key_bits, n_keys, round_keys, memspace);
 }
 
 int fheaes_add_scalar(fheaes_ctx *c, uint64_t *state, uint64_t n_blocks, const uint64_t *counters_hi_lo, int memspace)
 {
+    if (!c) return FHEAES_ERR_INVALID;
     CtxLock lock__(c);
     TRY(check_keys(c));
     if (!state || !counters_hi_lo) return c->fail(FHEAES_ERR_INVALID, "null pointer");
@@ -862,153 +865,129 @@ int fheaes_add_scalar(fheaes_ctx *c, uint64_t *state, uint64_t n_blocks, const u
     return s.finish();
 }
 
-// key_of_block null: every block under the one set `round_keys` (decryption round keys for public_inverse())
-static int aes_public(fheaes_ctx *c, const PublicDirection &dir, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block, const uint64_t *blocks,
-                      const uint64_t *data, uint64_t n_blocks, uint64_t *state_out, int memspace, bool packed = false)
+// The public-block calls, all eight of them.  An entry point says which direction, whether every pointer it requires is there (have_args)
+// and what the blocks are: blocks_of(scratch) returns {blocks, data} -- the caller's own lists, or ones it builds in `scratch` (CTR, CBC),
+// which happens only once the call is known to run.  k.key_of null: every block under the one set (decryption round keys for public_inverse()).
+struct PublicBlocks { const uint64_t *blocks, *data; };
+using BlocksOf = std::function<PublicBlocks(std::vector<uint64_t> &)>;
+static BlocksOf given(const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo)
 {
-    const int nr = aes_rounds(key_bits);
-    const KeyStore ks = key_store(c, key_bits, packed);
-    const uint64_t sw = 16ull * 8 * c->big1, keys_bytes = n_keys * ks.key_words * 8;
-    if (packed && overlap(round_keys, keys_bytes, state_out, n_blocks * sw * 8)) return c->fail(FHEAES_ERR_INVALID, "the packed round keys and state_out overlap");
+    return [=](std::vector<uint64_t> &) { return PublicBlocks{blocks_hi_lo, data_hi_lo}; };
+}
+
+static int aes_public(fheaes_ctx *c, const PublicDirection &dir, RoundKeys k, bool have_args, const BlocksOf &blocks_of, uint64_t n_blocks, uint64_t *state_out, int memspace)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!have_args) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(resolve_keys(c, k));
+    if (n_blocks == 0) return FHEAES_OK;
+    const uint64_t sw = 16ull * 8 * c->big1;
+    if (k.packed && k.overlaps(state_out, n_blocks * sw * 8)) return c->fail(FHEAES_ERR_INVALID, "the packed round keys and state_out overlap");
     if (n_blocks > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %llu", (unsigned long long)PUBLIC_MAX_BLOCKS);
+    std::vector<uint64_t> scratch;
+    const PublicBlocks pb = blocks_of(scratch);
     HIP_TRY(c, hipSetDevice(c->device));
     PublicPlan pl;
-    public_plan(dir, blocks, data, key_of_block, n_blocks, nr, pl);
+    public_plan(dir, pb.blocks, pb.data, k.key_of, n_blocks, k.nr, pl);
     Staged s(c, memspace);
-    TRY(s.in(round_keys, keys_bytes, &round_keys));
+    TRY(k.stage(s));
     TRY(s.out(state_out, n_blocks * sw * 8, &state_out));
-    TRY(aes_public_dev(c, dir, KeySets{round_keys, nullptr, ks.key_words, ks.glwes}, pl, nr, state_out));
+    TRY(aes_public_dev(c, dir, k.sets(), pl, k.nr, state_out));
     return s.finish();
 }
 
 int fheaes_aes_encrypt_public_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *blocks_hi_lo, uint64_t n_blocks,
                                    uint64_t *state_out, int memspace)
 {
-    CtxLock lock__(c);
-    TRY(check_keys(c));
-    if (!round_keys || !blocks_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    TRY(check_key_bits(c, key_bits));
-    if (n_blocks == 0) return FHEAES_OK;
-    return aes_public(c, public_forward(), round_keys, key_bits, 1, nullptr, blocks_hi_lo, nullptr, n_blocks, state_out, memspace);
+    return aes_public(c, public_forward(), one_key(round_keys, key_bits), round_keys && blocks_hi_lo && state_out, given(blocks_hi_lo, nullptr), n_blocks, state_out, memspace);
+}
+
+// counter block i = iv with its low `width` bits replaced by (those bits + first_block + i) mod 2^width: SP 800-38A appendix B.1 with m = 128,
+// and with m = 32 the inc32 of SP 800-38D (iv being the initial counter block)
+static void ctr_blocks(const uint64_t *iv_hi_lo, uint64_t first_block, uint64_t n_blocks, uint32_t width, std::vector<uint64_t> &ctr)
+{
+    const uint64_t count_hi = width > 64 ? ~0ull >> (128 - width) : 0, count_lo = width >= 64 ? ~0ull : ~0ull >> (64 - width);
+    const uint64_t lo0 = iv_hi_lo[1] + first_block, hi0 = iv_hi_lo[0] + (lo0 < first_block ? 1 : 0);
+    ctr.resize(2 * n_blocks);
+    for (uint64_t i = 0; i < n_blocks; ++i) {
+        const uint64_t lo = lo0 + i, hi = hi0 + (lo < lo0 ? 1 : 0);
+        ctr[2 * i] = (iv_hi_lo[0] & ~count_hi) | (hi & count_hi);
+        ctr[2 * i + 1] = (iv_hi_lo[1] & ~count_lo) | (lo & count_lo);
+    }
+}
+
+static int aes_ctr(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *iv_hi_lo, uint64_t first_block, uint32_t width,
+                   const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
+{
+    return aes_public(c, public_forward(), one_key(round_keys, key_bits), round_keys && iv_hi_lo && state_out, [&](std::vector<uint64_t> &ctr) {
+        ctr_blocks(iv_hi_lo, first_block, n_blocks, width, ctr);
+        return PublicBlocks{ctr.data(), data_hi_lo};
+    }, n_blocks, state_out, memspace);
 }
 
 int fheaes_aes_ctr_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *iv_hi_lo, uint64_t first_block,
                         const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
 {
-    CtxLock lock__(c);
-    TRY(check_keys(c));
-    if (!round_keys || !iv_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    TRY(check_key_bits(c, key_bits));
-    if (n_blocks == 0) return FHEAES_OK;
-    if (n_blocks > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %llu", (unsigned long long)PUBLIC_MAX_BLOCKS);
-    // counter block i = (iv + first_block + i) mod 2^128 (SP 800-38A appendix B.1 with m = 128)
-    std::vector<uint64_t> ctr(2 * n_blocks);
-    const uint64_t lo0 = iv_hi_lo[1] + first_block, hi0 = iv_hi_lo[0] + (lo0 < first_block ? 1 : 0);
-    for (uint64_t i = 0; i < n_blocks; ++i) {
-        const uint64_t lo = lo0 + i;
-        ctr[2 * i] = hi0 + (lo < lo0 ? 1 : 0);
-        ctr[2 * i + 1] = lo;
-    }
-    return aes_public(c, public_forward(), round_keys, key_bits, 1, nullptr, ctr.data(), data_hi_lo, n_blocks, state_out, memspace);
+    return aes_ctr(c, round_keys, key_bits, iv_hi_lo, first_block, 128, data_hi_lo, n_blocks, state_out, memspace);
 }
 
 int fheaes_aes_ctr32_bits(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, const uint64_t *icb_hi_lo, uint64_t first_block,
                           const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
 {
-    CtxLock lock__(c);
-    TRY(check_keys(c));
-    if (!round_keys || !icb_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    TRY(check_key_bits(c, key_bits));
-    if (n_blocks == 0) return FHEAES_OK;
-    if (n_blocks > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %llu", (unsigned long long)PUBLIC_MAX_BLOCKS);
-    // counter block i = icb with its low 32 bits replaced by (low32(icb) + first_block + i) mod 2^32 (SP 800-38D inc32; 38A B.1 with m = 32)
-    std::vector<uint64_t> ctr(2 * n_blocks);
-    const uint64_t top = icb_hi_lo[1] & ~0xFFFFFFFFull;
-    const uint32_t low0 = (uint32_t)icb_hi_lo[1] + (uint32_t)first_block;
-    for (uint64_t i = 0; i < n_blocks; ++i) {
-        ctr[2 * i] = icb_hi_lo[0];
-        ctr[2 * i + 1] = top | (uint32_t)(low0 + (uint32_t)i);
-    }
-    return aes_public(c, public_forward(), round_keys, key_bits, 1, nullptr, ctr.data(), data_hi_lo, n_blocks, state_out, memspace);
+    return aes_ctr(c, round_keys, key_bits, icb_hi_lo, first_block, 32, data_hi_lo, n_blocks, state_out, memspace);
+}
+
+// the four keyed calls: forward or through the equivalent inverse cipher (decryption round keys), LWE-form keys or a packed store
+static int aes_public_keyed(fheaes_ctx *c, const PublicDirection &dir, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
+                            const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace, bool packed)
+{
+    return aes_public(c, dir, {round_keys, key_bits, n_keys, key_of_block, n_blocks, packed}, round_keys && key_of_block && blocks_hi_lo && state_out,
+                      given(blocks_hi_lo, data_hi_lo), n_blocks, state_out, memspace);
 }
 
 int fheaes_aes_public_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
                             const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
 {
-    CtxLock lock__(c);
-    TRY(check_keys(c));
-    if (!round_keys || !key_of_block || !blocks_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    TRY(check_key_bits(c, key_bits));
-    TRY(check_n_keys(c, n_keys));
-    TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
-    if (n_blocks == 0) return FHEAES_OK;
-    return aes_public(c, public_forward(), round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace);
+    return aes_public_keyed(c, public_forward(), round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, false);
 }
 
 int fheaes_aes_public_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
                                    const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
 {
-    CtxLock lock__(c);
-    TRY(check_keys(c));
-    if (!packed_round_keys || !key_of_block || !blocks_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    TRY(check_key_bits(c, key_bits));
-    TRY(check_n_keys(c, n_keys));
-    TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
-    if (n_blocks == 0) return FHEAES_OK;
-    return aes_public(c, public_forward(), packed_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, true);
+    return aes_public_keyed(c, public_forward(), packed_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, true);
 }
 
-// ---- public blocks through the equivalent inverse cipher: the calls above with public_inverse() and decryption round keys ----
 int fheaes_aes_decrypt_public_bits(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo,
                                    uint64_t n_blocks, uint64_t *state_out, int memspace)
 {
-    CtxLock lock__(c);
-    TRY(check_keys(c));
-    if (!dec_round_keys || !blocks_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    TRY(check_key_bits(c, key_bits));
-    if (n_blocks == 0) return FHEAES_OK;
-    return aes_public(c, public_inverse(), dec_round_keys, key_bits, 1, nullptr, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace);
-}
-
-static int aes_decrypt_public_keyed(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
-                                    const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace, bool packed)
-{
-    CtxLock lock__(c);
-    TRY(check_keys(c));
-    if (!dec_round_keys || !key_of_block || !blocks_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    TRY(check_key_bits(c, key_bits));
-    TRY(check_n_keys(c, n_keys));
-    TRY(check_key_of_block(c, key_of_block, n_blocks, n_keys));
-    if (n_blocks == 0) return FHEAES_OK;
-    return aes_public(c, public_inverse(), dec_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, packed);
+    return aes_public(c, public_inverse(), one_key(dec_round_keys, key_bits), dec_round_keys && blocks_hi_lo && state_out, given(blocks_hi_lo, data_hi_lo), n_blocks,
+                      state_out, memspace);
 }
 
 int fheaes_aes_decrypt_public_keyed(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
                                     const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
 {
-    return aes_decrypt_public_keyed(c, dec_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, false);
+    return aes_public_keyed(c, public_inverse(), dec_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, false);
 }
 
 int fheaes_aes_decrypt_public_keyed_packed(fheaes_ctx *c, const uint64_t *packed_dec_round_keys, uint32_t key_bits, uint64_t n_keys, const uint32_t *key_of_block,
                                            const uint64_t *blocks_hi_lo, const uint64_t *data_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
 {
-    return aes_decrypt_public_keyed(c, packed_dec_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, true);
+    return aes_public_keyed(c, public_inverse(), packed_dec_round_keys, key_bits, n_keys, key_of_block, blocks_hi_lo, data_hi_lo, n_blocks, state_out, memspace, true);
 }
 
 int fheaes_aes_cbc_decrypt_bits(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, const uint64_t *iv_hi_lo, const uint64_t *ct_hi_lo,
                                 uint64_t n_blocks, uint64_t *state_out, int memspace)
 {
-    CtxLock lock__(c);
-    TRY(check_keys(c));
-    if (!dec_round_keys || !iv_hi_lo || !ct_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    TRY(check_key_bits(c, key_bits));
-    if (n_blocks == 0) return FHEAES_OK;
-    if (n_blocks > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most %llu", (unsigned long long)PUBLIC_MAX_BLOCKS);
     // P_i = D_K(C_i) ^ C_{i-1}, C_{-1} = iv (SP 800-38A 6.2): the chaining blocks are the ciphertext moved down by one block
-    std::vector<uint64_t> chain(2 * n_blocks);
-    chain[0] = iv_hi_lo[0]; chain[1] = iv_hi_lo[1];
-    memcpy(chain.data() + 2, ct_hi_lo, 2 * (n_blocks - 1) * sizeof(uint64_t));
-    return aes_public(c, public_inverse(), dec_round_keys, key_bits, 1, nullptr, ct_hi_lo, chain.data(), n_blocks, state_out, memspace);
+    return aes_public(c, public_inverse(), one_key(dec_round_keys, key_bits), dec_round_keys && iv_hi_lo && ct_hi_lo && state_out, [&](std::vector<uint64_t> &chain) {
+        chain.resize(2 * n_blocks);
+        chain[0] = iv_hi_lo[0]; chain[1] = iv_hi_lo[1];
+        memcpy(chain.data() + 2, ct_hi_lo, 2 * (n_blocks - 1) * sizeof(uint64_t));
+        return PublicBlocks{ct_hi_lo, chain.data()};
+    }, n_blocks, state_out, memspace);
 }
 
 static void plan_counts(const PublicPlan &pl, uint64_t n_blocks, int nr, uint64_t *unique_bytes_per_round)
@@ -1055,8 +1034,8 @@ int fheaes_aes_decrypt_public_plan_keyed(const uint64_t *blocks_hi_lo, const uin
 // fheaes_aes_decrypt_bits and the round-key conversion launch it
 int fheaes_inv_mix_columns_batch(fheaes_ctx *c, const uint64_t *multiples, uint64_t n_blocks, uint64_t *state_out, int memspace)
 {
-    CtxLock lock__(c);
     if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
     if (n_blocks == 0) return FHEAES_OK;
     if (!multiples || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
     if (n_blocks > 65535) return c->fail(FHEAES_ERR_INVALID, "n_blocks must be at most 65,535 (one grid), got %llu", (unsigned long long)n_blocks);
@@ -1071,14 +1050,15 @@ int fheaes_inv_mix_columns_batch(fheaes_ctx *c, const uint64_t *multiples, uint6
 }
 
 // ---- XTS-AES decryption -----------------------------------------------------------------------
-static int aes_xts_decrypt(fheaes_ctx *c, const uint64_t *dec_round_keys1, const uint64_t *round_keys2, uint32_t key_bits, const uint64_t *tweaks_hi_lo,
-                           uint64_t n_units, uint64_t blocks_per_unit, uint64_t first_block, const uint64_t *ct_hi_lo, uint64_t n_blocks, uint64_t *state_out,
-                           int memspace, bool packed)
+// k1: the decryption round keys of key 1, k2: the round keys of key 2, both of one size and in one form
+static int aes_xts_decrypt(fheaes_ctx *c, RoundKeys k1, RoundKeys k2, const uint64_t *tweaks_hi_lo, uint64_t n_units, uint64_t blocks_per_unit, uint64_t first_block,
+                           const uint64_t *ct_hi_lo, uint64_t n_blocks, uint64_t *state_out, int memspace)
 {
+    if (!c) return FHEAES_ERR_INVALID;
     CtxLock lock__(c);
     TRY(check_keys(c));
-    if (!dec_round_keys1 || !round_keys2 || !tweaks_hi_lo || !ct_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    if (key_bits != 128 && key_bits != 256) return c->fail(FHEAES_ERR_INVALID, "XTS-AES has two keys of 128 or 256 bits each (key_bits %u)", key_bits);
+    if (!k1.words || !k2.words || !tweaks_hi_lo || !ct_hi_lo || !state_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    if (k1.key_bits != 128 && k1.key_bits != 256) return c->fail(FHEAES_ERR_INVALID, "XTS-AES has two keys of 128 or 256 bits each (key_bits %u)", k1.key_bits);
     if (blocks_per_unit == 0 || blocks_per_unit > XTS_MAX_BLOCKS_PER_UNIT)
         return c->fail(FHEAES_ERR_INVALID, "blocks_per_unit must be in 1..%u (got %llu)", XTS_MAX_BLOCKS_PER_UNIT, (unsigned long long)blocks_per_unit);
     if (n_blocks == 0) return FHEAES_OK;
@@ -1087,18 +1067,16 @@ static int aes_xts_decrypt(fheaes_ctx *c, const uint64_t *dec_round_keys1, const
         return c->fail(FHEAES_ERR_INVALID, "blocks %llu .. of %llu units of %llu blocks: n_units must cover the blocks of the call (and their tweaks number below 2^32)",
                        (unsigned long long)first_block, (unsigned long long)n_units, (unsigned long long)blocks_per_unit);
     if (pl.units > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "a call touches at most %llu data units", (unsigned long long)PUBLIC_MAX_BLOCKS);
-    const int nr = aes_rounds(key_bits);
-    const KeyStore ks = key_store(c, key_bits, packed);
-    const uint64_t sw = 16ull * 8 * c->big1, keys_bytes = ks.key_words * 8, out_bytes = n_blocks * sw * 8;
-    if (overlap(dec_round_keys1, keys_bytes, state_out, out_bytes) || overlap(round_keys2, keys_bytes, state_out, out_bytes))
-        return c->fail(FHEAES_ERR_INVALID, "the round keys and state_out overlap");
+    TRY(resolve_keys(c, k1));
+    TRY(resolve_keys(c, k2));
+    const uint64_t sw = 16ull * 8 * c->big1, out_bytes = n_blocks * sw * 8;
+    if (k1.overlaps(state_out, out_bytes) || k2.overlaps(state_out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "the round keys and state_out overlap");
     HIP_TRY(c, hipSetDevice(c->device));
     Staged s(c, memspace);
-    TRY(s.in(dec_round_keys1, keys_bytes, &dec_round_keys1));
-    TRY(s.in(round_keys2, keys_bytes, &round_keys2));
+    TRY(k1.stage(s));
+    TRY(k2.stage(s));
     TRY(s.out(state_out, out_bytes, &state_out));
-    TRY(aes_xts_decrypt_dev(c, KeySets{dec_round_keys1, nullptr, ks.key_words, ks.glwes}, KeySets{round_keys2, nullptr, ks.key_words, ks.glwes}, nr, tweaks_hi_lo, pl,
-                            ct_hi_lo, n_blocks, state_out));
+    TRY(aes_xts_decrypt_dev(c, k1.sets(), k2.sets(), k1.nr, tweaks_hi_lo, pl, ct_hi_lo, n_blocks, state_out));
     return s.finish();
 }
 
@@ -1106,23 +1084,22 @@ int fheaes_aes_xts_decrypt_bits(fheaes_ctx *c, const uint64_t *dec_round_keys1, 
                                 uint64_t n_units, uint64_t blocks_per_unit, uint64_t first_block, const uint64_t *ct_hi_lo, uint64_t n_blocks, uint64_t *state_out,
                                 int memspace)
 {
-    if (!c) return FHEAES_ERR_INVALID;
-    return aes_xts_decrypt(c, dec_round_keys1, round_keys2, key_bits, tweaks_hi_lo, n_units, blocks_per_unit, first_block, ct_hi_lo, n_blocks, state_out, memspace, false);
+    return aes_xts_decrypt(c, one_key(dec_round_keys1, key_bits), one_key(round_keys2, key_bits), tweaks_hi_lo, n_units, blocks_per_unit, first_block, ct_hi_lo, n_blocks,
+                           state_out, memspace);
 }
 
 int fheaes_aes_xts_decrypt_packed(fheaes_ctx *c, const uint64_t *packed_dec_round_keys1, const uint64_t *packed_round_keys2, uint32_t key_bits,
                                   const uint64_t *tweaks_hi_lo, uint64_t n_units, uint64_t blocks_per_unit, uint64_t first_block, const uint64_t *ct_hi_lo,
                                   uint64_t n_blocks, uint64_t *state_out, int memspace)
 {
-    if (!c) return FHEAES_ERR_INVALID;
-    return aes_xts_decrypt(c, packed_dec_round_keys1, packed_round_keys2, key_bits, tweaks_hi_lo, n_units, blocks_per_unit, first_block, ct_hi_lo, n_blocks, state_out,
-                           memspace, true);
+    return aes_xts_decrypt(c, one_key(packed_dec_round_keys1, key_bits, true), one_key(packed_round_keys2, key_bits, true), tweaks_hi_lo, n_units, blocks_per_unit,
+                           first_block, ct_hi_lo, n_blocks, state_out, memspace);
 }
 
 int fheaes_xts_tweaks(fheaes_ctx *c, const uint64_t *anchor, uint64_t n_units, uint32_t first_offset, uint32_t n_offsets, uint64_t *out, int memspace)
 {
-    CtxLock lock__(c);
     if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
     if (n_offsets == 0 || first_offset > XTS_MAX_OFFSET || n_offsets > XTS_MAX_OFFSET + 1 - first_offset)
         return c->fail(FHEAES_ERR_INVALID, "XTS tweak offsets %u .. : one gather reaches offset %u at most and takes at least one", first_offset, XTS_MAX_OFFSET);
     if (n_units == 0) return FHEAES_OK;
@@ -1193,24 +1170,18 @@ int fheaes_xts_whiten(fheaes_ctx *c, uint64_t *dst, const uint64_t *src, const u
 }
 
 // ---- CBC-MAC chains and CCM decryption --------------------------------------------------------
-// what every call on streams checks first: the keys and the table that names one per stream
-static int check_streams(fheaes_ctx *c, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams, const uint32_t *key_of_stream)
-{
-    TRY(check_key_bits(c, key_bits));
-    TRY(check_n_keys(c, n_keys));
-    if (n_streams > MAC_MAX_STREAMS) return c->fail(FHEAES_ERR_INVALID, "n_streams must be at most %u (got %llu)", MAC_MAX_STREAMS, (unsigned long long)n_streams);
-    return check_key_of_block(c, key_of_stream, n_streams, n_keys);
-}
-
-static int aes_cbc_mac(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams, const uint32_t *key_of_stream,
-                       const uint32_t *stream_blocks, const uint8_t *clear, const uint64_t *enc, const uint8_t *enc_bytes, const uint64_t *init, uint64_t *mac_out,
-                       int memspace, bool packed)
+// what every call on streams checks first, resolve_keys(.., MAC_MAX_STREAMS): the keys and the table that names one per stream
+// k.key_of: the key of every stream, k.n_of of them
+static int aes_cbc_mac(fheaes_ctx *c, RoundKeys k, const uint32_t *stream_blocks, const uint8_t *clear, const uint64_t *enc, const uint8_t *enc_bytes, const uint64_t *init,
+                       uint64_t *mac_out, int memspace)
 {
     if (!c) return FHEAES_ERR_INVALID;
     CtxLock lock__(c);
     TRY(check_keys(c));
-    if (!round_keys || !key_of_stream || !stream_blocks || !mac_out || (enc != nullptr) != (enc_bytes != nullptr)) return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    TRY(check_streams(c, key_bits, n_keys, n_streams, key_of_stream));
+    const uint64_t n_streams = k.n_of;
+    const uint32_t *key_of_stream = k.key_of;
+    if (!k.words || !key_of_stream || !stream_blocks || !mac_out || (enc != nullptr) != (enc_bytes != nullptr)) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(resolve_keys(c, k, MAC_MAX_STREAMS));
     std::vector<uint64_t> off(n_streams + 1, 0);
     for (uint64_t s = 0; s < n_streams; ++s) {
         if (stream_blocks[s] > MAC_MAX_STREAM_BLOCKS)
@@ -1223,10 +1194,8 @@ static int aes_cbc_mac(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_b
     if (enc_bytes) for (uint64_t b = 0; b < total; ++b)
         if (enc_bytes[b] > 16) return c->fail(FHEAES_ERR_INVALID, "enc_bytes[%llu] = %u: a block has 16 bytes", (unsigned long long)b, (unsigned)enc_bytes[b]);
     if (n_streams == 0) return FHEAES_OK;
-    const int nr = aes_rounds(key_bits);
-    const KeyStore ks = key_store(c, key_bits, packed);
-    const uint64_t sw = 16ull * 8 * c->big1, keys_bytes = n_keys * ks.key_words * 8, out_bytes = n_streams * sw * 8;
-    if (overlap(round_keys, keys_bytes, mac_out, out_bytes) || (enc && overlap(enc, total * sw * 8, mac_out, out_bytes)) || (init && overlap(init, out_bytes, mac_out, out_bytes)))
+    const uint64_t sw = 16ull * 8 * c->big1, out_bytes = n_streams * sw * 8;
+    if (k.overlaps(mac_out, out_bytes) || (enc && overlap(enc, total * sw * 8, mac_out, out_bytes)) || (init && overlap(init, out_bytes, mac_out, out_bytes)))
         return c->fail(FHEAES_ERR_INVALID, "mac_out overlaps an input");
     MacPlan pl;
     mac_plan(stream_blocks, n_streams, pl);
@@ -1240,14 +1209,14 @@ static int aes_cbc_mac(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_b
     for (uint64_t s = 0; s < n_streams; ++s) ch.slots.push_back(mac_slot(pl.slot_of[s], MAC_NONE, 0, 16, nullptr));
     HIP_TRY(c, hipSetDevice(c->device));
     Staged st(c, memspace);
-    TRY(st.in(round_keys, keys_bytes, &round_keys));
+    TRY(k.stage(st));
     if (enc) TRY(st.in(enc, total * sw * 8, &enc));
     if (init) TRY(st.in(init, out_bytes, &init));
     TRY(st.out(mac_out, out_bytes, &mac_out));
     TRY(ensure(c, c->ws_tmp_b, out_bytes));
     uint64_t *state = (uint64_t *)c->ws_tmp_b.p;
     const MacSlot *recs = nullptr;
-    TRY(cbc_mac_dev(c, KeySets{round_keys, nullptr, ks.key_words, ks.glwes}, nr, n_keys, ch, init, enc, state, &recs));
+    TRY(cbc_mac_dev(c, k.sets(), k.nr, k.n_keys, ch, init, enc, state, &recs));
     TRY(launch_mac_link(c, mac_out, state, nullptr, recs + out0, n_streams, 2, "the CBC-MAC results in the caller's order"));
     return st.finish();
 }
@@ -1256,14 +1225,14 @@ int fheaes_aes_cbc_mac_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t
                              const uint32_t *stream_blocks, const uint8_t *clear, const uint64_t *enc, const uint8_t *enc_bytes, const uint64_t *init,
                              uint64_t *mac_out, int memspace)
 {
-    return aes_cbc_mac(c, round_keys, key_bits, n_keys, n_streams, key_of_stream, stream_blocks, clear, enc, enc_bytes, init, mac_out, memspace, false);
+    return aes_cbc_mac(c, {round_keys, key_bits, n_keys, key_of_stream, n_streams, false}, stream_blocks, clear, enc, enc_bytes, init, mac_out, memspace);
 }
 
 int fheaes_aes_cbc_mac_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams,
                                     const uint32_t *key_of_stream, const uint32_t *stream_blocks, const uint8_t *clear, const uint64_t *enc, const uint8_t *enc_bytes,
                                     const uint64_t *init, uint64_t *mac_out, int memspace)
 {
-    return aes_cbc_mac(c, packed_round_keys, key_bits, n_keys, n_streams, key_of_stream, stream_blocks, clear, enc, enc_bytes, init, mac_out, memspace, true);
+    return aes_cbc_mac(c, {packed_round_keys, key_bits, n_keys, key_of_stream, n_streams, true}, stream_blocks, clear, enc, enc_bytes, init, mac_out, memspace);
 }
 
 // K6 alone: one link of a chain on caller buffers (the kernel's test and measurement entry)
@@ -1303,17 +1272,17 @@ int fheaes_mac_link(fheaes_ctx *c, uint64_t *state, uint64_t n_slots, int first,
     return st.finish();
 }
 
-static int aes_ccm_open(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams, const uint32_t *key_of_stream,
-                        const uint32_t *head_blocks, const uint64_t *head_hi_lo, const uint64_t *ctr0_hi_lo, const uint64_t *payload_bytes, const uint8_t *ciphertext,
-                        const uint8_t *tags, const uint32_t *tag_bytes, uint64_t *plaintext_out, uint64_t *valid_out, int memspace, bool packed)
+static int aes_ccm_open(fheaes_ctx *c, RoundKeys k, const uint32_t *head_blocks, const uint64_t *head_hi_lo, const uint64_t *ctr0_hi_lo, const uint64_t *payload_bytes,
+                        const uint8_t *ciphertext, const uint8_t *tags, const uint32_t *tag_bytes, uint64_t *plaintext_out, uint64_t *valid_out, int memspace)
 {
     if (!c) return FHEAES_ERR_INVALID;
     CtxLock lock__(c);
     TRY(check_keys(c));
-    if (!round_keys || !key_of_stream || !head_blocks || !head_hi_lo || !ctr0_hi_lo || !payload_bytes || !tags || !tag_bytes || !valid_out)
+    const uint64_t n = k.n_of;
+    const uint32_t *key_of_stream = k.key_of;
+    if (!k.words || !key_of_stream || !head_blocks || !head_hi_lo || !ctr0_hi_lo || !payload_bytes || !tags || !tag_bytes || !valid_out)
         return c->fail(FHEAES_ERR_INVALID, "null pointer");
-    TRY(check_streams(c, key_bits, n_keys, n_streams, key_of_stream));
-    const uint64_t n = n_streams;
+    TRY(resolve_keys(c, k, MAC_MAX_STREAMS));
     CcmCall cc;
     cc.n = n;
     cc.len.resize(n);
@@ -1342,10 +1311,8 @@ static int aes_ccm_open(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_
     cc.payload_blocks = M;
     if (M && (!ciphertext || !plaintext_out)) return c->fail(FHEAES_ERR_INVALID, "null pointer");
     if (n_pub > PUBLIC_MAX_BLOCKS) return c->fail(FHEAES_ERR_INVALID, "a call has at most %llu public blocks", (unsigned long long)PUBLIC_MAX_BLOCKS);
-    const int nr = aes_rounds(key_bits);
-    const KeyStore ks = key_store(c, key_bits, packed);
-    const uint64_t sw = 16ull * 8 * c->big1, keys_bytes = n_keys * ks.key_words * 8, pt_bytes = M * sw * 8, valid_bytes = n * c->big1 * 8ull;
-    if (overlap(round_keys, keys_bytes, valid_out, valid_bytes) || (M && (overlap(round_keys, keys_bytes, plaintext_out, pt_bytes) || overlap(plaintext_out, pt_bytes, valid_out, valid_bytes))))
+    const uint64_t sw = 16ull * 8 * c->big1, pt_bytes = M * sw * 8, valid_bytes = n * c->big1 * 8ull;
+    if (k.overlaps(valid_out, valid_bytes) || (M && (k.overlaps(plaintext_out, pt_bytes) || overlap(plaintext_out, pt_bytes, valid_out, valid_bytes))))
         return c->fail(FHEAES_ERR_INVALID, "plaintext_out, valid_out and the round keys overlap");
     // the public batch: [Ctr_1.. of every stream | B0 | Ctr_0], data [C_1.. | 0 | 0]
     cc.pub_blocks.assign(2 * n_pub, 0); cc.pub_data.assign(2 * n_pub, 0); cc.pub_key.resize(n_pub);
@@ -1375,13 +1342,13 @@ static int aes_ccm_open(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_
         for (uint64_t i = 0; i < poff[s + 1] - poff[s]; ++i)
             cc.chain.slots.push_back(mac_slot(MAC_NONE, (uint32_t)(poff[s] + i), (uint32_t)std::min<uint64_t>(16, payload_bytes[s] - 16 * i), 16, nullptr));
     PublicPlan pp;
-    public_plan(public_forward(), cc.pub_blocks.data(), cc.pub_data.data(), cc.pub_key.data(), n_pub, nr, pp);
+    public_plan(public_forward(), cc.pub_blocks.data(), cc.pub_data.data(), cc.pub_key.data(), n_pub, k.nr, pp);
     HIP_TRY(c, hipSetDevice(c->device));
     Staged st(c, memspace);
-    TRY(st.in(round_keys, keys_bytes, &round_keys));
+    TRY(k.stage(st));
     if (M) TRY(st.out(plaintext_out, pt_bytes, &plaintext_out));
     TRY(st.out(valid_out, valid_bytes, &valid_out));
-    TRY(ccm_open_dev(c, KeySets{round_keys, nullptr, ks.key_words, ks.glwes}, nr, n_keys, cc, pp, plaintext_out, valid_out));
+    TRY(ccm_open_dev(c, k.sets(), k.nr, k.n_keys, cc, pp, plaintext_out, valid_out));
     return st.finish();
 }
 
@@ -1389,8 +1356,8 @@ int fheaes_aes_ccm_open_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_
                               const uint32_t *head_blocks, const uint64_t *head_hi_lo, const uint64_t *ctr0_hi_lo, const uint64_t *payload_bytes, const uint8_t *ciphertext,
                               const uint8_t *tags, const uint32_t *tag_bytes, uint64_t *plaintext_out, uint64_t *valid_out, int memspace)
 {
-    return aes_ccm_open(c, round_keys, key_bits, n_keys, n_streams, key_of_stream, head_blocks, head_hi_lo, ctr0_hi_lo, payload_bytes, ciphertext, tags, tag_bytes,
-                        plaintext_out, valid_out, memspace, false);
+    return aes_ccm_open(c, {round_keys, key_bits, n_keys, key_of_stream, n_streams, false}, head_blocks, head_hi_lo, ctr0_hi_lo, payload_bytes, ciphertext, tags, tag_bytes,
+                        plaintext_out, valid_out, memspace);
 }
 
 int fheaes_aes_ccm_open_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams,
@@ -1398,8 +1365,8 @@ int fheaes_aes_ccm_open_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round
                                      const uint64_t *payload_bytes, const uint8_t *ciphertext, const uint8_t *tags, const uint32_t *tag_bytes, uint64_t *plaintext_out,
                                      uint64_t *valid_out, int memspace)
 {
-    return aes_ccm_open(c, packed_round_keys, key_bits, n_keys, n_streams, key_of_stream, head_blocks, head_hi_lo, ctr0_hi_lo, payload_bytes, ciphertext, tags, tag_bytes,
-                        plaintext_out, valid_out, memspace, true);
+    return aes_ccm_open(c, {packed_round_keys, key_bits, n_keys, key_of_stream, n_streams, true}, head_blocks, head_hi_lo, ctr0_hi_lo, payload_bytes, ciphertext, tags,
+                        tag_bytes, plaintext_out, valid_out, memspace);
 }
 
 int fheaes_aes_mac_plan(const uint32_t *stream_blocks, const uint32_t *payload_blocks, uint64_t n_streams, uint64_t *steps, uint64_t *n_active_out, uint64_t n_active_cap,

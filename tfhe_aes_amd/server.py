@@ -26,6 +26,8 @@ only allocates outputs and forwards.  README.md:57-59 of the reference spells th
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 
 from . import _native
@@ -89,16 +91,35 @@ def _data_blocks(data, n_blocks: int):
     return data
 
 
-def _many_key_bits(arr, what):
-    """(key size, n_keys) of [n_keys][Nr+1][16][8][kN+1]"""
-    if arr.ndim != 5 or int(arr.shape[0]) < 1:
-        raise ValueError("%s of many keys must be [n_keys][11 | 13 | 15][16][8][kN+1] with n_keys >= 1, got shape %s" % (what, tuple(arr.shape)))
-    return _key_bits(arr[0], ROUND_KEYS_TO_BITS, what), int(arr.shape[0])
+class RoundKeys(NamedTuple):
+    """a round-key argument as the library takes it: the array (which also says which memory space the call works in), the AES key size,
+    the number of keys, and whether the array is a packed store"""
+    words: object
+    key_bits: int
+    n_keys: int
+    packed: bool
 
 
-def _words(round_keys):
-    """the array behind round keys in either form: what says which memory space a call works in"""
-    return round_keys.data if isinstance(round_keys, PackedRoundKeys) else round_keys
+def resolve_round_keys(params, arg, what="round keys", many=False, lwe_only=False) -> RoundKeys:
+    """The one reading of a round-key argument, for Server and ServerGroup alike.  `arg` is [Nr+1][16][8][kN+1], [n_keys][Nr+1][16][8][kN+1]
+    or a PackedRoundKeys made for `params`.  many False: a single-key method -- one key's array, or a store that holds one key; True: a
+    keyed method -- the [n_keys] array or any store; None: either array, one key's read as [1][Nr+1][16][8][kN+1] (the calls on streams,
+    pack_round_keys).  lwe_only: the method converts LWE-form keys and a store is refused."""
+    if isinstance(arg, PackedRoundKeys):
+        if lwe_only:
+            raise ValueError("%s in the LWE form [Nr+1][16][8][kN+1] are expected, got a PackedRoundKeys" % what)
+        if arg.params != params:
+            raise ValueError("these round keys were packed for %s, the server runs %s" % (arg.params.name, params.name))
+        if many is False and arg.n_keys != 1:
+            raise ValueError("a single-key method takes a store of one key (prk[i]); this one holds %d" % arg.n_keys)
+        return RoundKeys(arg.data, arg.key_bits, arg.n_keys, True)
+    if many is False:
+        return RoundKeys(arg, _key_bits(arg, ROUND_KEYS_TO_BITS, what), 1, False)
+    if many is None and arg.ndim == 4:
+        arg = arg[None]
+    if arg.ndim != 5 or int(arg.shape[0]) < 1:
+        raise ValueError("%s of many keys must be [n_keys][11 | 13 | 15][16][8][kN+1] with n_keys >= 1, got shape %s" % (what, tuple(arg.shape)))
+    return RoundKeys(arg, _key_bits(arg[0], ROUND_KEYS_TO_BITS, what), int(arg.shape[0]), False)
 
 
 def _u128(v, what: str) -> int:
@@ -288,52 +309,38 @@ class Server:
 
     def aes_encrypt(self, encrypted_round_keys, state):
         """server.rs:39, in place.  state [16][8][kN+1] or a batch [B][16][8][kN+1]; 11 / 13 / 15 round keys: AES-128 / 192 / 256."""
-        n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
-        if isinstance(encrypted_round_keys, PackedRoundKeys):
-            return self._one_packed(self.engine.aes_encrypt_keyed_packed, encrypted_round_keys, state, n_blocks)
-        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
-        self.engine.aes_encrypt_bits(encrypted_round_keys, bits, state, n_blocks)
-        return state
+        return self._one_key(self.engine.aes_encrypt_bits, self.engine.aes_encrypt_keyed_packed, self._round_keys(encrypted_round_keys), state)
 
     def aes_decrypt(self, encrypted_round_keys, state):
         """server.rs:67, in place; 11 / 13 / 15 round keys: AES-128 / 192 / 256."""
-        n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
-        if isinstance(encrypted_round_keys, PackedRoundKeys):
-            return self._one_packed(self.engine.aes_decrypt_keyed_packed, encrypted_round_keys, state, n_blocks)
-        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
-        self.engine.aes_decrypt_bits(encrypted_round_keys, bits, state, n_blocks)
-        return state
+        return self._one_key(self.engine.aes_decrypt_bits, self.engine.aes_decrypt_keyed_packed, self._round_keys(encrypted_round_keys), state)
 
     def aes_decryption_round_keys(self, round_keys):
         """round keys [Nr+1][16][8][kN+1] -> the equivalent inverse cipher's (FIPS-197 section 5.3.5): w[0], InvMixColumns(w[1..Nr-1])
         refreshed to nominal noise, w[Nr].  Once per AES key (2 x 128 (Nr - 1) bit circuit bootstraps: 2 x 1,152 at AES-128); feeds
         aes_decrypt_equivalent."""
-        bits = _key_bits(round_keys, ROUND_KEYS_TO_BITS, "round keys")
+        k = self._round_keys(round_keys, lwe_only=True)
         dw = _empty_like(round_keys, tuple(round_keys.shape))
-        self.engine.aes_decryption_round_keys_bits(round_keys, bits, dw)
+        self.engine.aes_decryption_round_keys_bits(k.words, k.key_bits, dw)
         return dw
 
     def aes_decrypt_equivalent(self, dec_round_keys, state):
         """the equivalent inverse cipher, in place: one WoPBS per round (Nr per block, as aes_encrypt) instead of aes_decrypt's two
         (server.rs:67-105, :86-89).  Same plaintext as aes_decrypt, other ciphertext words.  state [16][8][kN+1] or [B][16][8][kN+1]."""
+        return self._one_key(self.engine.aes_decrypt_equivalent_bits, self.engine.aes_decrypt_equivalent_keyed_packed,
+                             self._round_keys(dec_round_keys, "decryption round keys"), state)
+
+    def _round_keys(self, arg, what="round keys", many=False, lwe_only=False) -> RoundKeys:
+        return resolve_round_keys(self.params, arg, what, many, lwe_only)
+
+    def _one_key(self, call, packed_call, k: RoundKeys, state):
+        """a single-key cipher call, in place: the single-key entry point, or from a one-key store the keyed-packed one with every block
+        under key 0"""
         n_blocks = 1 if state.ndim == 3 else int(state.shape[0])
-        if isinstance(dec_round_keys, PackedRoundKeys):
-            return self._one_packed(self.engine.aes_decrypt_equivalent_keyed_packed, dec_round_keys, state, n_blocks)
-        bits = _key_bits(dec_round_keys, ROUND_KEYS_TO_BITS, "decryption round keys")
-        self.engine.aes_decrypt_equivalent_bits(dec_round_keys, bits, state, n_blocks)
-        return state
-
-    def _check_packed(self, prk: PackedRoundKeys, one_key: bool = False) -> PackedRoundKeys:
-        if prk.params != self.params:
-            raise ValueError("these round keys were packed for %s, the server runs %s" % (prk.params.name, self.params.name))
-        if one_key and prk.n_keys != 1:
-            raise ValueError("a single-key method takes a store of one key (prk[i]); this one holds %d" % prk.n_keys)
-        return prk
-
-    def _one_packed(self, call, prk: PackedRoundKeys, state, n_blocks: int):
-        """a single-key cipher call from a one-key store: the keyed-packed entry point with every block under key 0"""
-        self._check_packed(prk, one_key=True)
-        call(prk.data, prk.key_bits, 1, [0] * n_blocks, state, n_blocks)
+        if k.packed:
+            packed_call(k.words, k.key_bits, 1, [0] * n_blocks, state, n_blocks)
+        else:
+            call(k.words, k.key_bits, state, n_blocks)
         return state
 
     def add_scalar(self, state, i):
@@ -349,13 +356,11 @@ class Server:
         """aes_encrypt of PUBLIC blocks (ints, or 16 `bytes` each) under encrypted round keys: a new [n][16][8][kN+1] (or `out`), in the memory
         space of the round keys, word for word aes_encrypt(round keys, Client.trivial_bytes(blocks)); every distinct S-Box input of
         the batch is evaluated once (include/fheaes.h: fheaes_aes_encrypt_public_bits)."""
-        blocks = list(blocks)
-        if isinstance(encrypted_round_keys, PackedRoundKeys):
-            self._check_packed(encrypted_round_keys, one_key=True)
-            return self.aes_encrypt_public_keyed(encrypted_round_keys, [0] * len(blocks), blocks, out=out)
-        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
-        out = self._public_out(encrypted_round_keys, len(blocks), out)
-        self.engine.aes_encrypt_public_bits(encrypted_round_keys, bits, blocks, out)
+        blocks, k = list(blocks), self._round_keys(encrypted_round_keys)
+        if k.packed:
+            return self._public_keyed(k, [0] * len(blocks), blocks, None, out)
+        out = self._public_out(k.words, len(blocks), out)
+        self.engine.aes_encrypt_public_bits(k.words, k.key_bits, blocks, out)
         return out
 
     def aes_ctr(self, encrypted_round_keys, iv, first_block: int, n_blocks: int, data=None, out=None, counter_bits: int = 128):
@@ -363,10 +368,9 @@ class Server:
         (data None: the keystream).  `iv`: an int or 16 bytes; `data`: n_blocks ints / 16-byte blocks, or one `bytes` of 16 n_blocks.
         counter_bits = 32: only the low 32 bits of `iv` count, mod 2^32, and the upper 96 never change (the counter field of GCM)."""
         _check_counter_bits(counter_bits)
-        if isinstance(encrypted_round_keys, PackedRoundKeys):
-            self._check_packed(encrypted_round_keys, one_key=True)
+        k = self._round_keys(encrypted_round_keys)
+        if k.packed:
             return self.aes_ctr_streams(encrypted_round_keys, [(0, iv, first_block, n_blocks, data)], out=out, counter_bits=counter_bits)
-        bits = _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
         n_blocks, first_block = int(n_blocks), int(first_block)
         if n_blocks < 0 or first_block < 0:
             raise ValueError("n_blocks and first_block must be >= 0")
@@ -378,8 +382,8 @@ class Server:
         elif first_block >> 64:                  # the C ABI takes a 64-bit block index; the counter is mod 2^128 anyway
             iv, first_block = (iv + (first_block >> 64 << 64)) % (1 << 128), first_block & (2 ** 64 - 1)
         data = _data_blocks(data, n_blocks)
-        out = self._public_out(encrypted_round_keys, n_blocks, out)
-        self.engine.aes_ctr_bits(encrypted_round_keys, bits, iv, first_block, data, n_blocks, out, counter_bits=counter_bits)
+        out = self._public_out(k.words, n_blocks, out)
+        self.engine.aes_ctr_bits(k.words, k.key_bits, iv, first_block, data, n_blocks, out, counter_bits=counter_bits)
         return out
 
     def aes_gcm_ctr(self, encrypted_round_keys, iv, data=None, n_blocks=None, first_block: int = 0, out=None):
@@ -395,14 +399,12 @@ class Server:
         (aes_decryption_round_keys): a new [n][16][8][kN+1] (or `out`), word for word aes_decrypt_equivalent(dec_round_keys,
         Client.trivial_bytes(blocks)) with the clear `data` blocks (as aes_ctr's) added in the last layer; every distinct S-Box input of the
         batch is evaluated once (include/fheaes.h: fheaes_aes_decrypt_public_bits)."""
-        blocks = list(blocks)
-        if isinstance(dec_round_keys, PackedRoundKeys):
-            self._check_packed(dec_round_keys, one_key=True)
-            return self.aes_decrypt_public_keyed(dec_round_keys, [0] * len(blocks), blocks, data=data, out=out)
-        bits = _key_bits(dec_round_keys, ROUND_KEYS_TO_BITS, "decryption round keys")
+        blocks, k = list(blocks), self._round_keys(dec_round_keys, "decryption round keys")
+        if k.packed:
+            return self._public_keyed(k, [0] * len(blocks), blocks, data, out, inverse=True)
         data = _data_blocks(data, len(blocks))
-        out = self._public_out(dec_round_keys, len(blocks), out)
-        self.engine.aes_decrypt_public_bits(dec_round_keys, bits, blocks, data, out)
+        out = self._public_out(k.words, len(blocks), out)
+        self.engine.aes_decrypt_public_bits(k.words, k.key_bits, blocks, data, out)
         return out
 
     def aes_cbc_decrypt(self, dec_round_keys, iv, ciphertext, out=None):
@@ -410,12 +412,11 @@ class Server:
         int or 16 bytes; `ciphertext`: ints / 16-byte blocks, or one `bytes` of whole blocks.  To continue a stream pass the last ciphertext
         block of the part before as `iv`.  CBC encryption is serial (every block waits for the one before) and is not offered."""
         ct = _cipher_blocks(ciphertext)
-        if isinstance(dec_round_keys, PackedRoundKeys):
-            self._check_packed(dec_round_keys, one_key=True)
+        k = self._round_keys(dec_round_keys, "decryption round keys")
+        if k.packed:
             return self.aes_cbc_streams(dec_round_keys, [(0, iv, ct)], out=out)
-        bits = _key_bits(dec_round_keys, ROUND_KEYS_TO_BITS, "decryption round keys")
-        out = self._public_out(dec_round_keys, len(ct), out)
-        self.engine.aes_cbc_decrypt_bits(dec_round_keys, bits, _u128(iv, "iv"), ct, out)
+        out = self._public_out(k.words, len(ct), out)
+        self.engine.aes_cbc_decrypt_bits(k.words, k.key_bits, _u128(iv, "iv"), ct, out)
         return out
 
     def aes_cfb_decrypt(self, encrypted_round_keys, iv, ciphertext, out=None):
@@ -423,12 +424,7 @@ class Server:
         blocks, so it takes the encryption round keys: aes_encrypt_public_keyed with blocks [iv, C_0, ..] and data C."""
         ct = _cipher_blocks(ciphertext)
         blocks = ([_u128(iv, "iv")] + ct[:-1])[:len(ct)]
-        if isinstance(encrypted_round_keys, PackedRoundKeys):
-            rk = self._check_packed(encrypted_round_keys, one_key=True)
-        else:
-            _key_bits(encrypted_round_keys, ROUND_KEYS_TO_BITS, "round keys")
-            rk = encrypted_round_keys[None]
-        return self.aes_encrypt_public_keyed(rk, [0] * len(ct), blocks, data=ct, out=out)
+        return self._public_keyed(self._round_keys(encrypted_round_keys), [0] * len(ct), blocks, ct, out)
 
     def aes_xts_decrypt(self, dec_round_keys1, round_keys2, sectors, ciphertext, unit_bytes: int = 512, first_block: int = 0, out=None):
         """XTS-AES decryption (IEEE 1619) of a PUBLIC ciphertext under two encrypted keys: block b of the call is block (first_block + b) %
@@ -441,22 +437,15 @@ class Server:
 
         sectors, bpu, ct = xts_args(sectors, ciphertext, unit_bytes, first_block)
         tweaks = [xts_tweak_block(v) for v in sectors]          # IEEE 1619 writes the number little-endian: its low byte is byte 0 of the block
-        packed = [isinstance(k, PackedRoundKeys) for k in (dec_round_keys1, round_keys2)]
-        if any(packed):
-            if not all(packed):
-                # one call reads both key sets in one form: bring the LWE-form set to the other's
-                dec_round_keys1, round_keys2 = (k if isinstance(k, PackedRoundKeys) else self.pack_round_keys(k) for k in (dec_round_keys1, round_keys2))
-            k1, k2 = self._check_packed(dec_round_keys1, one_key=True), self._check_packed(round_keys2, one_key=True)
-            bits, bits2, w1, w2 = k1.key_bits, k2.key_bits, k1.data, k2.data
-        else:
-            bits = _key_bits(dec_round_keys1, ROUND_KEYS_TO_BITS, "decryption round keys")
-            bits2 = _key_bits(round_keys2, ROUND_KEYS_TO_BITS, "round keys")
-            w1, w2 = dec_round_keys1, round_keys2
-        if bits != bits2 or bits == 192:
-            raise ValueError("XTS-AES takes two keys of 128 or of 256 bits, got %d and %d" % (bits, bits2))
-        out = self._public_out(w1, len(ct), out)
+        if isinstance(dec_round_keys1, PackedRoundKeys) != isinstance(round_keys2, PackedRoundKeys):
+            # one call reads both key sets in one form: bring the LWE-form set to the other's
+            dec_round_keys1, round_keys2 = (k if isinstance(k, PackedRoundKeys) else self.pack_round_keys(k) for k in (dec_round_keys1, round_keys2))
+        k1, k2 = self._round_keys(dec_round_keys1, "decryption round keys"), self._round_keys(round_keys2)
+        if k1.key_bits != k2.key_bits or k1.key_bits == 192:
+            raise ValueError("XTS-AES takes two keys of 128 or of 256 bits, got %d and %d" % (k1.key_bits, k2.key_bits))
+        out = self._public_out(k1.words, len(ct), out)
         if ct:
-            self.engine.aes_xts_decrypt_bits(w1, w2, bits, tweaks, bpu, int(first_block), ct, out, packed=any(packed))
+            self.engine.aes_xts_decrypt_bits(k1.words, k2.words, k1.key_bits, tweaks, bpu, int(first_block), ct, out, packed=k1.packed)
         return out
 
     # ---- many AES keys under one FHE key ----------------------------------------------
@@ -482,20 +471,16 @@ class Server:
     def aes_decryption_round_keys_many(self, round_keys, out=None):
         """[n_keys][Nr+1][16][8][kN+1] -> the equivalent inverse cipher's round keys of every key (or `out`), the middle bytes of all keys in
         one batch; slice i is aes_decryption_round_keys(round_keys[i]) word for word."""
-        bits, n_keys = _many_key_bits(round_keys, "round keys")
+        k = self._round_keys(round_keys, many=True, lwe_only=True)
         dw = self._many_out(round_keys, tuple(round_keys.shape), out)
-        self.engine.aes_decryption_round_keys_batch(round_keys, bits, n_keys, dw)
+        self.engine.aes_decryption_round_keys_batch(k.words, k.key_bits, k.n_keys, dw)
         return dw
 
-    def _keyed(self, call, round_keys, key_of_block, state, packed_call=None):
-        if isinstance(round_keys, PackedRoundKeys):
-            prk = self._check_packed(round_keys)
-            call, round_keys, bits, n_keys = packed_call, prk.data, prk.key_bits, prk.n_keys
-        else:
-            bits, n_keys = _many_key_bits(round_keys, "round keys")
+    def _keyed(self, call, round_keys, key_of_block, state, packed_call):
+        k = self._round_keys(round_keys, many=True)
         if state.ndim != 4:
             raise ValueError("a keyed call works on a batch [n_blocks][16][8][kN+1]; wrap a single state as state[None]")
-        call(round_keys, bits, n_keys, list(key_of_block), state, int(state.shape[0]))
+        (packed_call if k.packed else call)(k.words, k.key_bits, k.n_keys, list(key_of_block), state, int(state.shape[0]))
         return state
 
     def aes_encrypt_keyed(self, round_keys, key_of_block, state):
@@ -514,15 +499,14 @@ class Server:
     def aes_encrypt_public_keyed(self, round_keys, key_of_block, blocks, data=None, out=None):
         """aes_encrypt_public with a key per block (and, as aes_ctr, clear `data` blocks folded into the last layer): a new
         [n][16][8][kN+1] (or `out`).  Equal S-Box inputs under the same key are evaluated once, equal blocks under different keys are not shared."""
+        return self._public_keyed(self._round_keys(round_keys, many=True), key_of_block, blocks, data, out)
+
+    def _public_keyed(self, k: RoundKeys, key_of_block, blocks, data, out, inverse: bool = False):
+        """the public blocks under k's keys, forward or (`inverse`, k being decryption round keys) through the equivalent inverse cipher"""
         blocks = list(blocks)
-        if isinstance(round_keys, PackedRoundKeys):
-            prk = self._check_packed(round_keys)
-            out = self._public_out(prk.data, len(blocks), out)
-            self.engine.aes_public_keyed(prk.data, prk.key_bits, prk.n_keys, list(key_of_block), blocks, _data_blocks(data, len(blocks)), out, packed=True)
-            return out
-        bits, n_keys = _many_key_bits(round_keys, "round keys")
-        out = self._public_out(round_keys, len(blocks), out)
-        self.engine.aes_public_keyed(round_keys, bits, n_keys, list(key_of_block), blocks, _data_blocks(data, len(blocks)), out)
+        data = _data_blocks(data, len(blocks))
+        out = self._public_out(k.words, len(blocks), out)
+        self.engine.aes_public_keyed(k.words, k.key_bits, k.n_keys, list(key_of_block), blocks, data, out, packed=k.packed, inverse=inverse)
         return out
 
     def aes_ctr_streams(self, round_keys, streams, out=None, counter_bits: int = 128):
@@ -535,17 +519,7 @@ class Server:
 
     def aes_decrypt_public_keyed(self, dec_round_keys, key_of_block, blocks, data=None, out=None):
         """aes_decrypt_public with a key per block; dec_round_keys from aes_decryption_round_keys_many, or a PackedRoundKeys of them."""
-        blocks = list(blocks)
-        if isinstance(dec_round_keys, PackedRoundKeys):
-            prk = self._check_packed(dec_round_keys)
-            words, bits, n_keys = prk.data, prk.key_bits, prk.n_keys
-        else:
-            words = dec_round_keys
-            bits, n_keys = _many_key_bits(dec_round_keys, "decryption round keys")
-        data = _data_blocks(data, len(blocks))
-        out = self._public_out(words, len(blocks), out)
-        self.engine.aes_public_keyed(words, bits, n_keys, list(key_of_block), blocks, data, out, packed=words is not dec_round_keys, inverse=True)
-        return out
+        return self._public_keyed(self._round_keys(dec_round_keys, "decryption round keys", many=True), key_of_block, blocks, data, out, inverse=True)
 
     def aes_cbc_streams(self, dec_round_keys, streams, out=None):
         """several CBC ciphertexts under several keys in one call: `streams` is a list of (key_index, iv, ciphertext), each as the arguments
@@ -555,15 +529,6 @@ class Server:
         return self.aes_decrypt_public_keyed(dec_round_keys, key_of_block, blocks, data=chain, out=out)
 
     # ---- CBC-MAC chains and CCM: the engine's integrity results --------------------------------
-    def _stream_keys(self, round_keys, what="round keys"):
-        if isinstance(round_keys, PackedRoundKeys):
-            prk = self._check_packed(round_keys)
-            return prk.data, prk.key_bits, prk.n_keys, True
-        if round_keys.ndim == 4:
-            round_keys = round_keys[None]
-        bits, n_keys = _many_key_bits(round_keys, what)
-        return round_keys, bits, n_keys, False
-
     def aes_cbc_mac_streams(self, round_keys, streams, init=None, out=None):
         """Raw CBC-MAC chains X_{i+1} = E_K(X_i ^ B_i) over many streams in one call: `streams` is a list of (key_index, blocks) or
         (key_index, blocks, enc, enc_bytes) -- `blocks` the stream's PUBLIC blocks (u128 or 16 bytes each), `enc` an optional encrypted
@@ -572,7 +537,7 @@ class Server:
         `out`), in the caller's order.  The streams are sorted by length; step i of all live streams is one cipher pass
         (include/fheaes.h: fheaes_aes_cbc_mac_keyed).  round_keys: [n_keys][Nr+1][16][8][kN+1], one key's [Nr+1][16][8][kN+1], or a
         PackedRoundKeys."""
-        words, bits, n_keys, packed = self._stream_keys(round_keys)
+        words, bits, n_keys, packed = self._round_keys(round_keys, many=None)
         streams = [tuple(st) + (None, None) * (len(st) == 2) for st in streams]
         keys, lens, clear, enc_bytes = [], [], [], []
         any_enc = any(st[2] is not None for st in streams)
@@ -616,7 +581,7 @@ class Server:
         (Client.decrypt_bits) to 1 iff its tag verifies.  The plaintext is not gated on `valid`.  One public call (B0, the counters), a
         CBC-MAC chain over all messages step by step, and two WoPBS for the comparison (include/fheaes.h: fheaes_aes_ccm_open_keyed).  The tag
         length is len(tag) (4, 6, .., 16), the nonce has 7..13 bytes.  round_keys as aes_cbc_mac_streams'."""
-        words, bits, n_keys, packed = self._stream_keys(round_keys)
+        words, bits, n_keys, packed = self._round_keys(round_keys, many=None)
         a = ccm_args(messages)
         n, total = len(a["tag_bytes"]), a["block_of_message"][-1]
         out = self._many_out(words, (total, 16, 8, self.params.big1), out)
@@ -634,18 +599,15 @@ class Server:
         """round keys [Nr+1][16][8][kN+1] or [n_keys][Nr+1][16][8][kN+1] (encryption or decryption round keys) -> a PackedRoundKeys in the
         same memory space: key i is pack(round_keys[i]) word for word, G = 3 / 4 / 4 GLWEs (fheaes_pack_round_keys).  `out`: where the
         [n_keys][G][(k+1)N] words go (e.g. a slice of a larger store)."""
-        if round_keys.ndim == 4:
-            round_keys = round_keys[None]
-        bits, n_keys = _many_key_bits(round_keys, "round keys")
-        p = self.params
-        data = self._many_out(round_keys, (n_keys, packed_key_glwes(p, bits), (p.k + 1) * p.N), out)
-        self.engine.pack_round_keys(round_keys, bits, n_keys, data)
-        return PackedRoundKeys(p, bits, data)
+        k, p = self._round_keys(round_keys, many=None, lwe_only=True), self.params
+        data = self._many_out(k.words, (k.n_keys, packed_key_glwes(p, k.key_bits), (p.k + 1) * p.N), out)
+        self.engine.pack_round_keys(k.words, k.key_bits, k.n_keys, data)
+        return PackedRoundKeys(p, k.key_bits, data)
 
     def unpack_round_keys(self, prk: PackedRoundKeys, first: int = 0, count: int | None = None, out=None):
         """keys first .. first + count of a store back in the LWE form [count][Nr+1][16][8][kN+1] (count None: to the end), slice j word for
         word unpack(prk[first + j]): for migration and for tests; needs no keys (fheaes_unpack_round_keys)."""
-        self._check_packed(prk)
+        self._round_keys(prk, many=True)
         first = int(first)
         count = prk.n_keys - first if count is None else int(count)
         if first < 0 or count < 1 or first + count > prk.n_keys:
@@ -819,58 +781,65 @@ class ServerGroup:
     def aes_decrypt_equivalent(self, dec_round_keys, state):
         return self._fan_out(lambda s, shard, lo: s.aes_decrypt_equivalent(dec_round_keys, shard), state)
 
-    def add_scalar(self, state, counters):
-        counters = list(counters)
-        return self._fan_out(lambda s, shard, lo: s.add_scalar(shard, counters[lo:lo + int(shard.shape[0])]), state)
+    def _fan_out_lists(self, call, state, *per_block):
+        """shard these per-block lists with the output: call(server, shard of `state`, the same slice of every list -- None stays None)"""
+        return self._fan_out(lambda s, shard, lo: call(s, shard, *(None if a is None else a[lo:lo + int(shard.shape[0])] for a in per_block)), state)
 
-    def _fan_out_new(self, round_keys, n, fn):
-        """the public-input calls produce a NEW [n][16][8][kN+1]: allocate it next to the round keys, let every context fill its shard"""
-        out = _empty_like(_words(round_keys), (n, 16, 8, self.params.big1))
-        return self._fan_out(lambda s, shard, lo: fn(s, shard, lo, int(shard.shape[0])), out)
+    def add_scalar(self, state, counters):
+        return self._fan_out_lists(lambda s, shard, cnt: s.add_scalar(shard, cnt), state, list(counters))
+
+    _round_keys = Server._round_keys
+
+    def _new_out(self, k: RoundKeys, *shape):
+        """what a call returns as a NEW array: allocated next to the round keys, every context filling its shard"""
+        return _empty_like(k.words, shape + (self.params.big1,))
+
+    def _fan_out_new(self, k: RoundKeys, n, fn):
+        """the public-input calls produce a new [n][16][8][kN+1]"""
+        return self._fan_out(lambda s, shard, lo: fn(s, shard, lo, int(shard.shape[0])), self._new_out(k, n, 16, 8))
 
     def aes_encrypt_public(self, round_keys, blocks):
         """Server.aes_encrypt_public, the blocks sharded contiguously; each context plans the sharing inside its own shard"""
         blocks = list(blocks)
-        return self._fan_out_new(round_keys, len(blocks), lambda s, shard, lo, k: s.aes_encrypt_public(round_keys, blocks[lo:lo + k], out=shard))
+        return self._fan_out_lists(lambda s, shard, b: s.aes_encrypt_public(round_keys, b, out=shard), self._new_out(self._round_keys(round_keys), len(blocks), 16, 8), blocks)
 
     def aes_ctr(self, round_keys, iv, first_block: int, n_blocks: int, data=None, counter_bits: int = 128):
         """Server.aes_ctr: context i takes the counter blocks of its shard (first_block + lo ..) and the matching data"""
         _check_counter_bits(counter_bits)
         n_blocks = int(n_blocks)
         data = _data_blocks(data, n_blocks)
-        return self._fan_out_new(round_keys, n_blocks, lambda s, shard, lo, k: s.aes_ctr(
+        return self._fan_out_new(self._round_keys(round_keys), n_blocks, lambda s, shard, lo, k: s.aes_ctr(
             round_keys, iv, int(first_block) + lo, k, None if data is None else data[lo:lo + k], out=shard, counter_bits=counter_bits))
 
     def aes_gcm_ctr(self, round_keys, iv, data=None, n_blocks=None, first_block: int = 0):
         """Server.aes_gcm_ctr: context i takes the data blocks first_block + lo .. of its shard"""
         _, n_blocks, data = gcm_ctr_args(iv, data, n_blocks, first_block)
-        return self._fan_out_new(round_keys, n_blocks, lambda s, shard, lo, k: s.aes_gcm_ctr(
+        return self._fan_out_new(self._round_keys(round_keys), n_blocks, lambda s, shard, lo, k: s.aes_gcm_ctr(
             round_keys, iv, None if data is None else data[lo:lo + k], k, int(first_block) + lo, out=shard))
 
     def aes_decrypt_public(self, dec_round_keys, blocks, data=None):
         """Server.aes_decrypt_public, the blocks sharded contiguously; each context plans the sharing inside its own shard"""
         blocks = list(blocks)
-        data = _data_blocks(data, len(blocks))
-        return self._fan_out_new(dec_round_keys, len(blocks), lambda s, shard, lo, k: s.aes_decrypt_public(
-            dec_round_keys, blocks[lo:lo + k], data=None if data is None else data[lo:lo + k], out=shard))
+        out = self._new_out(self._round_keys(dec_round_keys, "decryption round keys"), len(blocks), 16, 8)
+        return self._fan_out_lists(lambda s, shard, b, d: s.aes_decrypt_public(dec_round_keys, b, data=d, out=shard), out, blocks, _data_blocks(data, len(blocks)))
 
     def aes_cbc_decrypt(self, dec_round_keys, iv, ciphertext):
         """Server.aes_cbc_decrypt: a shard that starts at block lo > 0 chains its first block with C_{lo-1}"""
         ct = _cipher_blocks(ciphertext)
-        return self._fan_out_new(dec_round_keys, len(ct), lambda s, shard, lo, k: s.aes_cbc_decrypt(
+        return self._fan_out_new(self._round_keys(dec_round_keys, "decryption round keys"), len(ct), lambda s, shard, lo, k: s.aes_cbc_decrypt(
             dec_round_keys, ct[lo - 1] if lo else iv, ct[lo:lo + k], out=shard))
 
     def aes_cfb_decrypt(self, round_keys, iv, ciphertext):
         """Server.aes_cfb_decrypt: a shard that starts at block lo > 0 enciphers C_{lo-1} first"""
         ct = _cipher_blocks(ciphertext)
-        return self._fan_out_new(round_keys, len(ct), lambda s, shard, lo, k: s.aes_cfb_decrypt(
+        return self._fan_out_new(self._round_keys(round_keys), len(ct), lambda s, shard, lo, k: s.aes_cfb_decrypt(
             round_keys, ct[lo - 1] if lo else iv, ct[lo:lo + k], out=shard))
 
     def aes_xts_decrypt(self, dec_round_keys1, round_keys2, sectors, ciphertext, unit_bytes: int = 512, first_block: int = 0):
         """Server.aes_xts_decrypt: a shard at block lo passes first_block + lo and needs nothing from its neighbour (it derives its own
         tweaks from the units' anchors)"""
         units, _, ct = xts_args(sectors, ciphertext, unit_bytes, first_block)
-        return self._fan_out_new(dec_round_keys1, len(ct), lambda s, shard, lo, k: s.aes_xts_decrypt(
+        return self._fan_out_new(self._round_keys(dec_round_keys1, "decryption round keys"), len(ct), lambda s, shard, lo, k: s.aes_xts_decrypt(
             dec_round_keys1, round_keys2, units, ct[lo:lo + k], unit_bytes, int(first_block) + lo, out=shard))
 
     def aes_key_expansion(self, key):
@@ -894,43 +863,38 @@ class ServerGroup:
         return self._fan_out_keys(keys, out, lambda s, part, o: s.aes_key_expansion_many(part, out=o))
 
     def aes_decryption_round_keys_many(self, round_keys):
-        _many_key_bits(round_keys, "round keys")
+        self._round_keys(round_keys, many=True, lwe_only=True)
         out = _empty_like(round_keys, tuple(round_keys.shape))
         return self._fan_out_keys(round_keys, out, lambda s, part, o: s.aes_decryption_round_keys_many(part, out=o))
 
     def aes_encrypt_keyed(self, round_keys, key_of_block, state):
-        kob = list(key_of_block)
-        return self._fan_out(lambda s, shard, lo: s.aes_encrypt_keyed(round_keys, kob[lo:lo + int(shard.shape[0])], shard), state)
+        return self._fan_out_lists(lambda s, shard, kob: s.aes_encrypt_keyed(round_keys, kob, shard), state, list(key_of_block))
 
     def aes_decrypt_keyed(self, round_keys, key_of_block, state):
-        kob = list(key_of_block)
-        return self._fan_out(lambda s, shard, lo: s.aes_decrypt_keyed(round_keys, kob[lo:lo + int(shard.shape[0])], shard), state)
+        return self._fan_out_lists(lambda s, shard, kob: s.aes_decrypt_keyed(round_keys, kob, shard), state, list(key_of_block))
 
     def aes_decrypt_equivalent_keyed(self, dec_round_keys, key_of_block, state):
-        kob = list(key_of_block)
-        return self._fan_out(lambda s, shard, lo: s.aes_decrypt_equivalent_keyed(dec_round_keys, kob[lo:lo + int(shard.shape[0])], shard), state)
+        return self._fan_out_lists(lambda s, shard, kob: s.aes_decrypt_equivalent_keyed(dec_round_keys, kob, shard), state, list(key_of_block))
 
-    def aes_encrypt_public_keyed(self, round_keys, key_of_block, blocks, data=None):
-        """Server.aes_encrypt_public_keyed, the blocks sharded contiguously; each context plans the sharing inside its own shard"""
+    def _fan_out_public_keyed(self, method, round_keys, what, key_of_block, blocks, data):
+        """Server.aes_encrypt_public_keyed / aes_decrypt_public_keyed, the blocks sharded contiguously; each context plans the sharing
+        inside its own shard"""
         kob, blocks = list(key_of_block), list(blocks)
         data = _data_blocks(data, len(blocks))
         if len(kob) != len(blocks):
             raise ValueError("one key index per block expected")
-        return self._fan_out_new(round_keys, len(blocks), lambda s, shard, lo, k: s.aes_encrypt_public_keyed(
-            round_keys, kob[lo:lo + k], blocks[lo:lo + k], data=None if data is None else data[lo:lo + k], out=shard))
+        out = self._new_out(self._round_keys(round_keys, what, many=True), len(blocks), 16, 8)
+        return self._fan_out_lists(lambda s, shard, k, b, d: method(s, round_keys, k, b, data=d, out=shard), out, kob, blocks, data)
+
+    def aes_encrypt_public_keyed(self, round_keys, key_of_block, blocks, data=None):
+        return self._fan_out_public_keyed(Server.aes_encrypt_public_keyed, round_keys, "round keys", key_of_block, blocks, data)
 
     def aes_ctr_streams(self, round_keys, streams, counter_bits: int = 128):
         key_of_block, blocks, data = ctr_stream_blocks(streams, counter_bits)
         return self.aes_encrypt_public_keyed(round_keys, key_of_block, blocks, data=data)
 
     def aes_decrypt_public_keyed(self, dec_round_keys, key_of_block, blocks, data=None):
-        """Server.aes_decrypt_public_keyed, the blocks sharded contiguously; each context plans the sharing inside its own shard"""
-        kob, blocks = list(key_of_block), list(blocks)
-        data = _data_blocks(data, len(blocks))
-        if len(kob) != len(blocks):
-            raise ValueError("one key index per block expected")
-        return self._fan_out_new(dec_round_keys, len(blocks), lambda s, shard, lo, k: s.aes_decrypt_public_keyed(
-            dec_round_keys, kob[lo:lo + k], blocks[lo:lo + k], data=None if data is None else data[lo:lo + k], out=shard))
+        return self._fan_out_public_keyed(Server.aes_decrypt_public_keyed, dec_round_keys, "decryption round keys", key_of_block, blocks, data)
 
     def aes_cbc_streams(self, dec_round_keys, streams):
         """Server.aes_cbc_streams: the chaining blocks are built before the blocks are sharded, so a shard boundary inside a stream
@@ -942,7 +906,7 @@ class ServerGroup:
         """Server.aes_cbc_mac_streams: whole streams per context, contiguous and balanced by block count; a shard needs nothing from
         its neighbours"""
         streams = [tuple(st) for st in streams]
-        out = _empty_like(_words(round_keys), (len(streams), 16, 8, self.params.big1))
+        out = self._new_out(self._round_keys(round_keys, many=None), len(streams), 16, 8)
         shards = _shards_by_cost([len(_cipher_blocks(st[1])) + 1 for st in streams], len(self.servers))
         self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_cbc_mac_streams(
             round_keys, streams[lo:hi], init=None if init is None else init[lo:hi], out=out[lo:hi])) for lo, hi in shards])
@@ -953,8 +917,8 @@ class ServerGroup:
         messages = [tuple(m) for m in messages]
         a = ccm_args(messages)
         at, n = a["block_of_message"], len(messages)
-        out = _empty_like(_words(round_keys), (at[-1], 16, 8, self.params.big1))
-        valid = _empty_like(_words(round_keys), (n, self.params.big1))
+        k = self._round_keys(round_keys, many=None)
+        out, valid = self._new_out(k, at[-1], 16, 8), self._new_out(k, n)
         cost = [a["head_blocks"][i] - 1 + 2 * (at[i + 1] - at[i]) + 2 for i in range(n)]
         shards = _shards_by_cost(cost, len(self.servers))
         self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_ccm_decrypt(

@@ -25,6 +25,12 @@ of well under a millisecond.
 A missed bound makes the tool exit 2.
 
     python tools/ccm.py [--steps 5] [--warmup 1] [--reps 20] [--out profiles/ccm.json]
+
+--host-path: instead of all that, the HOST side of two small calls at PARAM_TOY, where the kernels take so little that the entry point's own
+work shows: Server.aes_ctr on 4 blocks and Server.aes_cbc_mac_streams on 3 streams of 2 blocks, resident tensors, measure.wall.  --lib PATH
+loads that libfheaes.so instead of the tree's, so that two builds can be run in alternating processes of one call and compared.
+
+    python tools/ccm.py --host-path [--lib path/to/libfheaes.so] [--steps 50] [--warmup 5]
 """
 from __future__ import annotations
 
@@ -42,8 +48,49 @@ N_KEYS, N_MSG, AAD_BYTES, PAYLOAD_BYTES, TAG_BYTES, STEPS_OF_CHAIN = 8, 64, 8, 3
 TOOL = "ccm"
 
 
+def host_path(args) -> int:
+    import ctypes
+
+    from tfhe_aes_amd import PARAM_TOY
+    from tfhe_aes_amd.client import Client
+    from tfhe_aes_amd.server import Server
+
+    if args.lib:
+        lib = ctypes.CDLL(args.lib)
+        for name, (res, argtypes) in _native.SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, argtypes
+        _native._lib = lib                                   # what load_library() hands to every Engine of this process
+    client = Client(1, 0, 0, params=PARAM_TOY, seed=0xC0DE)
+    server = Server(client.server_keys(), device=0)
+    key = bytes(range(16))
+    d_rk = server.aes_key_expansion(to_dev(client.encrypt_aes_key(key)))
+    server.synchronize()
+    streams = [(0, [17 * s + i for i in range(2)]) for s in range(3)]
+    got = {}
+    nothing = lambda: None  # noqa: E731
+    jobs = {"aes_ctr_4_blocks": (lambda: got.update(ctr=server.aes_ctr(d_rk, 5, 0, 4)), nothing),
+            "aes_cbc_mac_3_streams_of_2_blocks": (lambda: got.update(mac=server.aes_cbc_mac_streams(d_rk, streams)), nothing)}
+    times = measure.wall(server.engine, jobs, args.warmup, args.steps)
+    ok = np.array_equal(client.decrypt_bytes(host(got["ctr"])), measure.block_bytes([aes_clear.aes_encrypt_block(key, 5 + i) for i in range(4)]))
+    for s, (_, blocks) in enumerate(streams):
+        x = 0
+        for b in blocks:
+            x = aes_clear.aes_encrypt_block(key, x ^ b)
+        ok = ok and np.array_equal(client.decrypt_bytes(host(got["mac"][s])), measure.block_bytes([x])[0])
+    line = {"tool": TOOL, "mode": "host-path", "params": PARAM_TOY.name, "lib": args.lib or "the tree's", "version": _native.load_library().fheaes_version().decode(),
+            "steps": args.steps, "warmup": args.warmup, "all_verified": bool(ok), "variants": {k: measure.row(t) for k, t in times.items()}}
+    measure.emit(line, args.out)
+    return measure.exit_code(bool(ok))
+
+
 def main() -> int:
-    args = measure.arg_parser(reps=20).parse_args()
+    ap = measure.arg_parser(reps=20)
+    ap.add_argument("--host-path", action="store_true")
+    ap.add_argument("--lib", default=None)
+    args = ap.parse_args()
+    if args.host_path:
+        return host_path(args)
     p, n = PARAM_OPT, N_MSG
     client, eng = measure.session(0xAE5CC01)
     rng = np.random.default_rng(0x38C)
