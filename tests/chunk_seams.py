@@ -7,6 +7,13 @@ constant that changes turns a seam test red instead of into a one-chunk test.
   2 GiB of CMUX-tree workspace per WoPBS chunk of inputs wider than 9 bits
   8,192 workgroups x 16 polynomials per pass of forward_fourier_kernel
   256 blocks per pass of add_bcast_kernel at the toy set (16,384 / 64 workgroups in y)
+
+and of the later modes (test_gpu_chunk_seams_modes.py, pinned without a GPU by test_chunk_seams_modes_cpu.py):
+
+  256 blocks or slots per pass of xts_whiten_kernel and mac_link_kernel: the same 16,384 / 64 (SLOTS_PER_PASS)
+  2^20 workgroups = 8,192 tweak blocks per pass of xts_tweak_kernel (TWEAK_ROWS_PER_PASS)
+  128 inputs per chunk of the 16-bit tag WoPBS of a CCM call: 2^24 bytes of CMUX tree each (TAG_TREE_CHUNK); 256 messages per chunk of
+  its 8-bit one (TAG_BYTE_CHUNK)
 """
 import numpy as np
 
@@ -49,6 +56,52 @@ FOURIER_DISTINCT = 1024
 BLOCKS = 257                                         # 32,896 bits a step; block 256 is the second pass of add_bcast_kernel
 WINDOW = 200
 PUBLIC_BLOCKS = 300                                  # pools of 4,800 bytes = 38,400 bits
+
+
+# F. the later modes: XTS, CCM and the keyed public calls ---------------------------------------------------------------------------------
+BIG1_TOY = 513                                       # k N + 1 words of an LWE ciphertext at PARAM_TOY
+CHUNK_BYTES = MAX_CHUNK_BITS // 8                    # 4,096 bytes per chunk of a byte WoPBS: 256 blocks
+
+
+def slots_per_pass(big1: int) -> int:
+    """blocks (xts_whiten_kernel) or slots (mac_link_kernel) per grid pass: gridDim.y is capped at 16,384 / gx, gx the workgroups of 256
+    lanes over the 128 big1 words of a block, at most 64"""
+    return 16384 // min(64, -(-128 * big1 // 256))
+
+
+SLOTS_PER_PASS = slots_per_pass(BIG1_TOY)            # 256
+TWEAK_ROWS_PER_PASS = (1 << 20) // 128               # 8,192 tweak blocks: one workgroup per row of kN + 1 words, 2^20 workgroups
+TAG_TREE_CHUNK = (2 << 30) // (1 * 16 * (1 << 7) * 2 * N * 8)       # 128 inputs: one LUT, 16 bits, 2^7 GLWEs of 8 KB per output bit at k = 1
+TAG_BYTE_CHUNK = MAX_CHUNK_BITS // 8 // 16           # 256 messages: 16 bytes of tag difference each
+
+# 1. fheaes_xts_whiten alone and 2. fheaes_mac_link alone: one block or slot behind the pass
+WHITEN_BLOCKS, WHITEN_TWEAKS = SLOTS_PER_PASS + 1, 5
+LINK_SLOTS, LINK_ENC = SLOTS_PER_PASS + 1, SLOTS_PER_PASS + 3
+MAC_NONE = 0xFFFFFFFF
+
+# 3. fheaes_xts_tweaks: 68 units of 122 offsets are 8,296 tweak blocks = 1,061,888 rows; 67 units stay below 2^20
+TWEAK_UNITS, TWEAK_OFFSETS = 68, 122
+TWEAK_BLOCKS = TWEAK_UNITS * TWEAK_OFFSETS
+TWEAK_SEAM = divmod(TWEAK_ROWS_PER_PASS, TWEAK_OFFSETS)     # (unit 67, offset 18): the first tweak block of the second pass
+
+# 4. XTS-AES decryption: blocks 121 .. 486 of four units of 122 blocks
+XTS_SEGMENT = 120
+XTS_BPU, XTS_FIRST, XTS_BLOCKS = 122, 121, 366
+XTS_SECTORS = (0x0123456789, 7, (1 << 64) - 2, 1 << 100)
+XTS_ALONE = (0, 1, 255, 256, 365)
+
+# 5. CCM: 257 messages under 3 keys; position -> (AAD bytes, payload bytes, tag bytes) of the long ones, the rest (0, 0, 8)
+CCM_MESSAGES, CCM_KEYS = 257, 3
+CCM_LONG = {0: (3, 16, 4), 127: (40, 40, 16), 128: (14, 21, 8), 255: (20, 16, 16), 256: (30, 5, 10)}
+CCM_BAD = sorted({1, 127, 129, 255, 256} | set(range(37, CCM_MESSAGES, 37)))   # and every 37th: position 0 is valid, position 256 is not
+CCM_BAD_CIPHERTEXT = 256                             # a ciphertext bit there; a bit of the last compared tag byte at the others
+MAC_STREAMS = 257
+MAC_LENGTHS = {0: 3, 255: 0, 256: 3}                 # the rest chain one block
+MAC_ALONE = (0, 1, 255, 256)
+
+# 6. keyed public calls: PUBLIC_BLOCKS blocks under 3 keys
+PUBLIC_KEYS, PUBLIC_SEED = 3, 0xE1E
+PUBLIC_ALONE = (0, 255, 256, PUBLIC_BLOCKS - 1)
 
 
 def chunks(total: int, chunk: int) -> int:
@@ -129,3 +182,111 @@ def window_launches(n_blocks: int, steps: int, window: int):
 def public_pool_round_1(blocks) -> int:
     """distinct (position, byte value) pairs of the blocks: the pool of round 1, at most 16 x 256 whatever the batch"""
     return len({(p, (int(b) >> (8 * (15 - p))) & 0xFF) for b in blocks for p in range(16)})
+
+
+# ---- F. the later modes ------------------------------------------------------------------------------------------------------------------
+def wopbs_chunks(n_inputs: int, bits: int, n_luts: int, k1: int) -> int:
+    """the chunks wopbs_dev cuts n_inputs into: MAX_CHUNK_BITS // bits inputs each, and above 9 bits no more inputs than keep the CMUX tree
+    (n_luts x bits x 2^(bits - 9) GLWEs of k1 N words per input) within 2 GiB; k1 = k + 1"""
+    chunk = max(1, MAX_CHUNK_BITS // bits)
+    if bits > 9:
+        chunk = max(1, min(chunk, (2 << 30) // (n_luts * bits * (1 << (bits - 9)) * k1 * N * 8)))
+    return chunks(n_inputs, chunk) if n_inputs else 0
+
+
+def byte_wopbs(n_bytes: int):
+    """(launches, units) of the key switch of one byte WoPBS over n_bytes bytes: chunks of 4,096 bytes, a unit per bit"""
+    return wopbs_chunks(n_bytes, 8, 1, 2), 8 * n_bytes
+
+
+def whiten_table(n: int = WHITEN_BLOCKS, rows: int = WHITEN_TWEAKS):
+    """tweak_of_block: (7 b + 3) mod 5, not monotone; block 256 takes a row that block 0 and block 255 do not"""
+    tab = [(7 * b + 3) % rows for b in range(n)]
+    assert tab[SLOTS_PER_PASS] not in (tab[0], tab[SLOTS_PER_PASS - 1]) and set(tab) == set(range(rows))
+    return tab
+
+
+def link_tables(n: int = LINK_SLOTS, n_enc: int = LINK_ENC):
+    """(src_block, enc_bytes) of the link over 257 slots: slot 256 reads block 0 and slot 0 block 258, slot 255 has no block; enc_bytes
+    cycles through 0, 1, 15 and 16, with 5 at slot 256"""
+    src = [(5 * s + 2) % n_enc for s in range(n)]
+    src[SLOTS_PER_PASS], src[0], src[SLOTS_PER_PASS - 1] = 0, n_enc - 1, MAC_NONE
+    eb = [(0, 1, 15, 16)[s % 4] for s in range(n)]
+    eb[SLOTS_PER_PASS] = 5
+    return src, eb
+
+
+def xts_segment_rows(bpu: int = XTS_BPU, first_block: int = XTS_FIRST, n_blocks: int = XTS_BLOCKS):
+    """(touched units, tweak rows of every segment) of an XTS call by the segment rule: per unit and segment the offsets of the call's
+    blocks there, and offset 120 -- the next segment's anchor -- where the unit's last block lies in a later segment"""
+    blocks = range(first_block, first_block + n_blocks)
+    units = sorted({g // bpu for g in blocks})
+    rows = []
+    for u in units:
+        mine = [g % bpu for g in blocks if g // bpu == u]
+        for s in range(max(mine) // XTS_SEGMENT + 1):
+            if s == len(rows):
+                rows.append(0)
+            rows[s] += len({j % XTS_SEGMENT for j in mine if j // XTS_SEGMENT == s}) + (1 if max(mine) // XTS_SEGMENT > s else 0)
+    return len(units), rows
+
+
+def xts_keyswitch(public_plan, bpu: int = XTS_BPU, first_block: int = XTS_FIRST, n_blocks: int = XTS_BLOCKS, nr: int = 10):
+    """{part: (launches, units)} of the key switch of an XTS call round by round (AES_WINDOW_OFF).  public rounds: one WoPBS per round
+    over the pool of the tweak blocks (public_plan: the pool sizes, aes_public_plan of those blocks); refresh: the anchors of segment 0,
+    then one identity WoPBS per segment over its rows; cipher: nr WoPBS over the call's blocks"""
+    units, rows = xts_segment_rows(bpu, first_block, n_blocks)
+    parts = {"public_rounds": [byte_wopbs(n) for n in public_plan],
+             "refresh": [byte_wopbs(16 * units)] + [byte_wopbs(16 * r) for r in rows],
+             "cipher": [byte_wopbs(16 * n_blocks)] * nr}
+    return {name: (sum(l for l, _ in v), sum(u for _, u in v)) for name, v in parts.items()}
+
+
+def total(parts):
+    """(launches, units) summed over the parts of xts_keyswitch / ccm_keyswitch"""
+    return sum(l for l, _ in parts.values()), sum(u for _, u in parts.values())
+
+
+def ccm_shape(i: int):
+    """(key index, AAD bytes, payload bytes, tag bytes) of message i: the key changes across 128 and across 256"""
+    return ((i * 2 + i // 128) % CCM_KEYS,) + CCM_LONG.get(i, (0, 0, 8))
+
+
+def ccm_stream_blocks():
+    """(chain length, payload blocks) of every message: the AAD with its 2-byte length in whole blocks, then the payload blocks"""
+    out = []
+    for i in range(CCM_MESSAGES):
+        _, aad, payload, _ = ccm_shape(i)
+        out.append(((2 + aad + 15) // 16 * (aad > 0) + (payload + 15) // 16, (payload + 15) // 16))
+    return [a for a, _ in out], [b for _, b in out]
+
+
+def live_prefixes(lengths):
+    """n_active of a chain: the streams longer than i, for every step i"""
+    return [sum(1 for v in lengths if v > i) for i in range(max(lengths, default=0))]
+
+
+def chain_keyswitch(n_active, nr: int = 10):
+    """(launches, units) of the cipher passes of a chain round by round: nr WoPBS over the live prefix of every step"""
+    parts = [byte_wopbs(16 * a) for a in n_active for _ in range(nr)]
+    return sum(l for l, _ in parts), sum(u for _, u in parts)
+
+
+def ccm_keyswitch(public_plan, n_active, n: int = CCM_MESSAGES, nr: int = 10):
+    """{part: (launches, units)} of the key switch of a CCM call round by round: the public rounds over their pools, the chain, the 8-bit
+    tag WoPBS over 16 n bytes and the 16-bit one over n inputs"""
+    pub = [byte_wopbs(v) for v in public_plan]
+    return {"public_rounds": (sum(l for l, _ in pub), sum(u for _, u in pub)), "chain": chain_keyswitch(n_active, nr),
+            "tag_bytes": byte_wopbs(16 * n), "tag_tree": (wopbs_chunks(n, 16, 1, 2), 16 * n)}
+
+
+def mac_lengths():
+    return [MAC_LENGTHS.get(s, 1) for s in range(MAC_STREAMS)]
+
+
+def public_keyed_blocks():
+    """(blocks, key of every block, data blocks) of the keyed public calls: random, and the same for both directions"""
+    rng = np.random.default_rng(PUBLIC_SEED)
+    blocks = [int.from_bytes(rng.bytes(16), "big") for _ in range(PUBLIC_BLOCKS)]
+    data = [int.from_bytes(rng.bytes(16), "big") for _ in range(PUBLIC_BLOCKS)]
+    return blocks, [int(k) for k in rng.integers(0, PUBLIC_KEYS, PUBLIC_BLOCKS)], data
