@@ -6,9 +6,12 @@
 """
 from __future__ import annotations
 
+import fcntl
 import os
 import shutil
 import subprocess
+import sys
+import tempfile
 from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
@@ -73,30 +76,72 @@ def unit_flags(unit: str):
 
 
 def engine_flags():
-    """flags of a SINGLE-UNIT developer build (`hipcc <these> -o lib.so csrc/engine.hip`, as tools/ablate_k2.py does it): engine.hip alone
+    """flags of a SINGLE-UNIT developer build (`hipcc <these> -o lib.so csrc/engine.hip`, as build_variant does it): engine.hip alone
     is then a complete library, every kernel in it compiled under the scheduler setting of the "engine" unit"""
     return _common_flags() + ["-shared"] + NO_POST_RA_SCHED
 
 
-def build_engine(force: bool = False, extra=()) -> Path:
-    # this file is a dependency too: it holds the compile flags (a library built before a flag changed must not be reused)
-    if force or _stale(ENGINE_SO, ENGINE_SOURCES + ENGINE_HEADERS + [Path(__file__)]):
-        BUILD_DIR.mkdir(exist_ok=True)
+def fresh(target: Path, deps, make, force: bool = False) -> Path:
+    """`target`, rebuilt first if it is older than one of `deps` (or `force`): make(tmpdir) builds a new file in a directory of its own
+    and returns it, and a rename puts it in place, so a reader only ever meets a complete file and a failed make leaves the old one.
+    One process builds at a time (build/lock, next to the temp directories); one that waited takes what the other built."""
+    target = Path(target)
+    if not force and not _stale(target, deps):
+        return target
+    BUILD_DIR.mkdir(exist_ok=True)
+    with open(BUILD_DIR / "lock", "w") as lock:
+        try:
+            fcntl.flock(lock, fcntl.LOCK_EX | fcntl.LOCK_NB)
+        except BlockingIOError:
+            print("[build] waiting for another process to finish building %s" % target.name, file=sys.stderr, flush=True)
+            fcntl.flock(lock, fcntl.LOCK_EX)
+        if force or _stale(target, deps):         # looked at again under the lock: the process this one waited for may have just built
+            tmp = Path(tempfile.mkdtemp(prefix=target.name + ".", dir=BUILD_DIR))
+            try:
+                built = make(tmp)
+                if os.stat(built).st_dev != os.stat(target.parent).st_dev:      # a target on another file system: a rename cannot cross
+                    built = shutil.copy(built, target.with_name(target.name + ".new"))
+                os.replace(built, target)
+            finally:
+                shutil.rmtree(tmp, ignore_errors=True)
+    return target
+
+
+def build_engine(force: bool = False) -> Path:
+    def make(tmp: Path) -> Path:
         objs = []
         for src, unit in zip(ENGINE_SOURCES, ("engine", "keyswitch")):
-            obj = BUILD_DIR / (src.stem + ".o")
-            _run([hipcc_path()] + unit_flags(unit) + list(extra) + ["-c", "-o", str(obj), str(src)])
-            objs.append(str(obj))
-        _run([hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(ENGINE_SO)] + objs)
-    return ENGINE_SO
+            objs.append(str(tmp / (src.stem + ".o")))
+            _run([hipcc_path()] + unit_flags(unit) + ["-c", "-o", objs[-1], str(src)])
+        _run([hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(tmp / ENGINE_SO.name)] + objs)
+        return tmp / ENGINE_SO.name
+
+    # this file is a dependency too: it holds the compile flags (a library built before a flag changed must not be reused)
+    return fresh(ENGINE_SO, ENGINE_SOURCES + ENGINE_HEADERS + [Path(__file__)], make, force)
 
 
 def build_client(force: bool = False) -> Path:
     src = CSRC / "client.c"
-    if force or _stale(CLIENT_SO, [src, ROOT / "include" / "fheaes.h"]):
+
+    def make(tmp: Path) -> Path:
         _run(["gcc", "-O3", "-mavx2", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-fPIC",
-              "-shared", "-std=gnu11", "-Wall", "-o", str(CLIENT_SO), str(src), "-lm"])
-    return CLIENT_SO
+              "-shared", "-std=gnu11", "-Wall", "-o", str(tmp / CLIENT_SO.name), str(src), "-lm"])
+        return tmp / CLIENT_SO.name
+
+    return fresh(CLIENT_SO, [src, ROOT / "include" / "fheaes.h"], make, force)
+
+
+def build_variant(out_path, defines=()) -> Path:
+    """the single-unit developer build (engine_flags()) of engine.hip with `defines` (knobs of csrc/knobs.h) as out_path: always built,
+    through a temp file next to out_path, and marked -DFHEAES_DEV_BUILD, so that an Engine refuses it unless told allow_dev_build"""
+    out_path = Path(out_path)
+    tmp = out_path.with_name("%s.%d.tmp" % (out_path.name, os.getpid()))
+    try:
+        _run([hipcc_path()] + engine_flags() + ["-DFHEAES_DEV_BUILD"] + list(defines) + ["-o", str(tmp), str(ENGINE_SOURCES[0])])
+        os.replace(tmp, out_path)
+    finally:
+        tmp.unlink(missing_ok=True)
+    return out_path
 
 
 def engine_source_hash() -> str:

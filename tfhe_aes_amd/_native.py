@@ -137,7 +137,7 @@ SIGNATURES = {
     "fheaes_version": (_c.c_char_p, []),
 }
 
-_lib = None
+_libs = {}          # resolved path of a library -> its bound CDLL
 
 
 def header_symbols() -> list[str]:
@@ -147,12 +147,15 @@ def header_symbols() -> list[str]:
     return sorted(set(re.findall(r"\b(fheaes_[a-z0-9_]+)\s*\(", text)))
 
 
-def load_library(build: bool = True):
-    """dlopen libfheaes.so (building it in-tree first if needed) and bind every declared symbol."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    path = _build.build_engine() if build else _build.ENGINE_SO
+def load_library(build: bool = True, path=None, partial: bool = False):
+    """dlopen a library and bind the declared symbols, once per resolved path.  path None: the product's libfheaes.so, built in-tree
+    first if needed; a given path is loaded as it is, never built.  partial: bind the symbols the library has and skip the rest (an
+    older build in an A/B run); without it a missing symbol is an AttributeError naming it."""
+    if path is None:
+        path = _build.build_engine() if build else _build.ENGINE_SO
+    path = Path(path).resolve()
+    if path in _libs:
+        return _libs[path]
     try:
         # PyTorch-ROCm ships its own libamdhip64; two HIP runtimes in one process cannot both own the
         # GPU ("No HIP GPUs are available" in whichever comes second).  Loading torch first makes
@@ -160,13 +163,15 @@ def load_library(build: bool = True):
         import torch  # noqa: F401
     except ImportError:
         pass
-    if not Path(path).exists():
-        raise RuntimeError("libfheaes.so is missing: run __graft_entry__.build() (hipcc --offload-arch=gfx950)")
+    if not path.exists():
+        raise RuntimeError("%s is missing: run __graft_entry__.build() (hipcc --offload-arch=gfx950)" % path.name)
     lib = ctypes.CDLL(str(path))
     for name, (res, args) in SIGNATURES.items():
+        if partial and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)      # AttributeError if the library does not export it
         fn.restype, fn.argtypes = res, args
-    _lib = lib
+    _libs[path] = lib
     return lib
 
 
@@ -192,9 +197,10 @@ def _ptr(x):
 class Engine:
     """Owns one ``fheaes_ctx``.  Thin: argument marshalling and error translation only."""
 
-    def __init__(self, params: WopbsParameters, device: int = 0, allow_dev_build: bool = False):
+    def __init__(self, params: WopbsParameters, device: int = 0, allow_dev_build: bool = False, library=None):
+        """library: the path of another build of libfheaes.so to run this context on (an A/B run); None: the product's"""
         self.params = params
-        self._lib = load_library()
+        self._lib = load_library() if library is None else load_library(path=library, partial=True)
         self._h = _ctx()
         # a library built with developer knobs (csrc/knobs.h: possibly a wrong-result ablation) says so in its version string
         version = (self._lib.fheaes_version() or b"").decode()

@@ -1,22 +1,22 @@
 """Developer tool: time the blind-rotation kernel (K2) for builds with phases compiled out.
-Builds variants of libfheaes.so into gpurun_out/abl/ and times fheaes_cbs_pbs_batch on M resident bits.
-usage: python tools/ablate_k2.py [M] [name,name,... | so:<path of a prebuilt library>]"""
-import ctypes
-import subprocess
+Builds variants of libfheaes.so (_build.build_variant) into its output directory (`out` in main()) and times Engine.cbs_pbs_batch on M resident bits; every
+variant is an engine of its own in this one process, on the same keys.
+usage: python tools/ablate_k2.py [M] [name,name,... | so:<path of a prebuilt library>]
+HBM-side counters of the variants, once this has built them (the first failing pass ends the loop):
+  for v in base nopark; do bash tools/pmc_passes.sh k2 <outdir>/$v <that directory>/libfheaes_$v.so || break; done
+  (K2_PARKING=private in front for the runtime variant parkwg, on the product library)"""
+import hashlib
 import sys
 import time
 from pathlib import Path
 
 import numpy as np
+import torch
 
-sys.path.insert(0, ".")
-import torch  # noqa: E402,F401  (HIP runtime first, see _native.load_library)
-
-sys.path.insert(0, "tools")
-from gpu_power import Sampler, fmt  # noqa: E402
-
-from tfhe_aes_amd import PARAM_OPT, _build, _native  # noqa: E402
-from tfhe_aes_amd.client import Client  # noqa: E402
+import measure  # noqa: F401  (puts the repository root on sys.path)
+from gpu_power import Sampler, fmt
+from tfhe_aes_amd import PARAM_OPT, _build, _native
+from tfhe_aes_amd.client import Client
 
 # Every flag is a knob of csrc/knobs.h: per-phase proxies of the paired blind rotation (WRONG results, timing only) and the phase stamps.
 VARIANTS = {
@@ -34,7 +34,7 @@ VARIANTS = {
 
 RUNS = 4
 # variants that are a runtime setting of the context, not a build
-RUNTIME = {"parkwg": lambda lib, h: lib.fheaes_k2_set_parking(h, 0)}
+RUNTIME = {"parkwg": lambda eng: eng.k2_set_parking(False)}
 
 
 def main():
@@ -51,37 +51,26 @@ def main():
         if name.startswith("so:"):                      # an already built library (A/B against an older build on the same box)
             so = Path(name[3:])
         else:
-            so = out / ("libfheaes_%s.so" % name)
-            cmd = [_build.hipcc_path()] + _build.engine_flags() + ["-DFHEAES_DEV_BUILD"] + VARIANTS[name] + ["-o", str(so), str(_build.ENGINE_SOURCES[0])]
-            subprocess.run(cmd, check=True, capture_output=True)
-        lib = ctypes.CDLL(str(so))
-        for fn, (res, args) in _native.SIGNATURES.items():
-            if not hasattr(lib, fn):                    # an older library (so:...) may lack entry points added since
-                continue
-            f = getattr(lib, fn)
-            f.restype, f.argtypes = res, args
-        h = ctypes.c_void_p()
-        cp = p.c_struct()
-        assert lib.fheaes_create(ctypes.byref(cp), 0, ctypes.byref(h)) == 0
-        assert lib.fheaes_upload_keys(h, keys.ksk.ctypes.data, keys.bsk.ctypes.data, keys.pfpksk.ctypes.data, 0) == 0
+            so = _build.build_variant(out / ("libfheaes_%s.so" % name), VARIANTS[name])
+        eng = _native.Engine(p, device=0, allow_dev_build=True, library=so)      # an older library (so:...) may lack entry points added since
+        eng.upload_keys(keys.ksk, keys.bsk, keys.pfpksk)
         if name in RUNTIME:
-            assert RUNTIME[name](lib, h) == 0
+            RUNTIME[name](eng)
         d_in = torch.from_numpy(small.view(np.int64)).cuda()
         d_out = torch.empty((M, p.big1), dtype=torch.int64, device="cuda")
         torch.cuda.synchronize()
         ts = []
-        assert lib.fheaes_cbs_pbs_batch(h, d_in.data_ptr(), M, 1, d_out.data_ptr(), 1) == 0      # warm-up (workspace, clocks)
-        lib.fheaes_synchronize(h)
+        eng.cbs_pbs_batch(d_in, d_out, M)               # warm-up (workspace, clocks)
+        eng.synchronize()
         with Sampler(period=0.01) as smp:                      # socket power / shader clock while the timed launches run
             for _ in range(RUNS):
                 t = time.perf_counter()
-                assert lib.fheaes_cbs_pbs_batch(h, d_in.data_ptr(), M, 1, d_out.data_ptr(), 1) == 0
-                lib.fheaes_synchronize(h)
+                eng.cbs_pbs_batch(d_in, d_out, M)
+                eng.synchronize()
                 ts.append(time.perf_counter() - t)
-        import hashlib
         digest = hashlib.sha256(d_out.cpu().numpy().tobytes()).hexdigest()[:12]      # equal digests = bit-identical outputs (real variants must match base)
         print("%-16s M=%d  %.1f ms  (runs: %s)  out %s  %s" % (name, M, 1e3 * min(ts), " ".join("%.1f" % (1e3 * x) for x in ts), digest, fmt(smp.summary())), flush=True)
-        lib.fheaes_destroy(h)
+        eng.close()
 
 
 if __name__ == "__main__":

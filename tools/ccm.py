@@ -49,20 +49,12 @@ TOOL = "ccm"
 
 
 def host_path(args) -> int:
-    import ctypes
-
     from tfhe_aes_amd import PARAM_TOY
     from tfhe_aes_amd.client import Client
     from tfhe_aes_amd.server import Server
 
-    if args.lib:
-        lib = ctypes.CDLL(args.lib)
-        for name, (res, argtypes) in _native.SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, argtypes
-        _native._lib = lib                                   # what load_library() hands to every Engine of this process
     client = Client(1, 0, 0, params=PARAM_TOY, seed=0xC0DE)
-    server = Server(client.server_keys(), device=0)
+    server = Server(client.server_keys(), device=0, engine=_native.Engine(PARAM_TOY, device=0, library=args.lib))
     key = bytes(range(16))
     d_rk = server.aes_key_expansion(to_dev(client.encrypt_aes_key(key)))
     server.synchronize()
@@ -78,7 +70,7 @@ def host_path(args) -> int:
         for b in blocks:
             x = aes_clear.aes_encrypt_block(key, x ^ b)
         ok = ok and np.array_equal(client.decrypt_bytes(host(got["mac"][s])), measure.block_bytes([x])[0])
-    line = {"tool": TOOL, "mode": "host-path", "params": PARAM_TOY.name, "lib": args.lib or "the tree's", "version": _native.load_library().fheaes_version().decode(),
+    line = {"tool": TOOL, "mode": "host-path", "params": PARAM_TOY.name, "lib": args.lib or "the tree's", "version": server.engine._lib.fheaes_version().decode(),
             "steps": args.steps, "warmup": args.warmup, "all_verified": bool(ok), "variants": {k: measure.row(t) for k, t in times.items()}}
     measure.emit(line, args.out)
     return measure.exit_code(bool(ok))

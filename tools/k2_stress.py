@@ -13,22 +13,16 @@ An optional last argument `so:<path>` loads another build of libfheaes.so.
 import hashlib
 import sys
 import time
-from pathlib import Path
 
 import numpy as np
+import torch
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-import torch  # noqa: E402
-
-from tfhe_aes_amd import PARAM_OPT, _native  # noqa: E402
-from tfhe_aes_amd.aes_clear import aes128_encrypt_block  # noqa: E402
-from tfhe_aes_amd.client import Client  # noqa: E402
+import measure
+from tfhe_aes_amd import PARAM_OPT
+from tfhe_aes_amd.aes_clear import aes128_encrypt_block
 
 args = [a for a in sys.argv[1:] if not a.startswith("so:")]
-for a in sys.argv[1:]:
-    if a.startswith("so:"):
-        _alt = Path(a[3:]).resolve()
-        _native._build.build_engine = lambda *x, **k: _alt
+library = next((a[3:] for a in sys.argv[1:] if a.startswith("so:")), None)
 mode = args[0] if args else "k2"
 p = PARAM_OPT
 IV = 0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF
@@ -43,11 +37,8 @@ def say(*a):
     print(*a, flush=True)
 
 
-c = Client(128, IV, KEY, params=p, seed=0xAE50001)
-keys = c.server_keys()
-E = _native.Engine(p, allow_dev_build=True)
-E.upload_keys(keys.ksk, keys.bsk, keys.pfpksk)
-say("library:", (_native.load_library().fheaes_version() or b"").decode())
+c, E = measure.session(0xAE50001, IV, KEY, library=library, allow_dev_build=True)
+say("library:", (E._lib.fheaes_version() or b"").decode())
 
 if mode == "k2":
     rounds = int(args[1]) if len(args) > 1 else 10

@@ -1,21 +1,16 @@
 """Developer tool: small-batch latencies (one block round, key expansion, counter add) at PARAM_OPT."""
-import sys
 import time
 
 import numpy as np
+import torch
 
-sys.path.insert(0, ".")
-import torch  # noqa: F401,E402
-
-from oracle import oracle as orc  # noqa: E402
-from tfhe_aes_amd import PARAM_OPT, _native  # noqa: E402
-from tfhe_aes_amd.client import Client  # noqa: E402
+import measure
+from oracle import oracle as orc
+from tfhe_aes_amd import PARAM_OPT
 
 p = PARAM_OPT
-c = Client(1, 0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF, 0x2B7E151628AED2A6ABF7158809CF4F3C, params=p, seed=0xAE50001)
+c, E = measure.session(0xAE50001, 0xF0F1F2F3F4F5F6F7F8F9FAFBFCFDFEFF, 0x2B7E151628AED2A6ABF7158809CF4F3C)
 keys, st, ek = c.client_encrypt()
-E = _native.Engine(p)
-E.upload_keys(keys.ksk, keys.bsk, keys.pfpksk)
 x = torch.from_numpy(c.encrypt_bytes(list(range(16))).view(np.int64)).cuda()
 out = torch.empty((16, 3, 8, p.big1), dtype=torch.int64, device="cuda")
 torch.cuda.synchronize()

@@ -57,11 +57,12 @@ def block_bytes(values) -> np.ndarray:
 
 
 # ---- session ---------------------------------------------------------------------------------------------------------------------------
-def session(seed: int, iv: int = 0, key: int = 0):
-    """(client, engine with the client's evaluation keys uploaded) at PARAM_OPT on device 0"""
+def session(seed: int, iv: int = 0, key: int = 0, library=None, allow_dev_build: bool = False):
+    """(client, engine with the client's evaluation keys uploaded) at PARAM_OPT on device 0; library: the path of another build of
+    libfheaes.so for the engine (_native.Engine), allow_dev_build: let it be a developer build"""
     client = Client(1, iv, key, params=PARAM_OPT, seed=seed)
     keys = client.server_keys()
-    eng = _native.Engine(PARAM_OPT, device=0)
+    eng = _native.Engine(PARAM_OPT, device=0, allow_dev_build=allow_dev_build, library=library)
     eng.upload_keys(keys.ksk, keys.bsk, keys.pfpksk)
     return client, eng
 

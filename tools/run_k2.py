@@ -1,28 +1,20 @@
 """Developer tool: run the blind-rotation stage (K2) alone on M resident bits, for rocprofv3 counter passes.
 usage: python3 tools/run_k2.py [M] [launches] [developer build of libfheaes.so to profile instead of the product's]"""
+import os
 import sys
 import time
-from pathlib import Path
 
 import numpy as np
+import torch
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-import torch  # noqa: E402
+import measure
+from tfhe_aes_amd import PARAM_OPT
 
-from tfhe_aes_amd import PARAM_OPT, _native  # noqa: E402
-from tfhe_aes_amd.client import Client  # noqa: E402
-
-if len(sys.argv) > 3:                      # a variant built by tools/ablate_k2.py (gpurun_out/abl/*.so)
-    _alt = Path(sys.argv[3]).resolve()
-    _native._build.build_engine = lambda *a, **k: _alt
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 launches = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 p = PARAM_OPT
-c = Client(1, 1, 2, params=p, seed=0xAE50001)
-keys = c.server_keys()
-E = _native.Engine(p, allow_dev_build=True)
-E.upload_keys(keys.ksk, keys.bsk, keys.pfpksk)
-import os  # noqa: E402
+# a trailing path: a variant built by tools/ablate_k2.py or any other build, instead of the product's
+_, E = measure.session(0xAE50001, 1, 2, library=sys.argv[3] if len(sys.argv) > 3 else None, allow_dev_build=True)
 if os.environ.get("K2_PARKING") == "private":          # one private parking slot per workgroup instead of the claimed pool
     E.k2_set_parking(False)
 rng = np.random.default_rng(0)

@@ -11,24 +11,17 @@ the GPU's power / clock / temperature at that moment.
 import hashlib
 import sys
 import time
-from pathlib import Path
 
 import numpy as np
+import torch
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-sys.path.insert(0, str(Path(__file__).resolve().parent))
-import torch  # noqa: E402
-
-from tfhe_aes_amd import PARAM_OPT, _native  # noqa: E402
-from tfhe_aes_amd.aes_clear import SBOX, mul2, mul3  # noqa: E402
-from tfhe_aes_amd.client import Client  # noqa: E402
-from tfhe_aes_amd.server import gen_lut  # noqa: E402
+import measure
+from tfhe_aes_amd import PARAM_OPT
+from tfhe_aes_amd.aes_clear import SBOX, mul2, mul3
+from tfhe_aes_amd.server import gen_lut
 
 args = [a for a in sys.argv[1:] if not a.startswith("so:")]
-for a in sys.argv[1:]:
-    if a.startswith("so:"):
-        _alt = Path(a[3:]).resolve()
-        _native._build.build_engine = lambda *x, **k: _alt
+library = next((a[3:] for a in sys.argv[1:] if a.startswith("so:")), None)
 seconds = float(args[0]) if args else 90.0
 stages = args[1] if len(args) > 1 else "12345"
 p = PARAM_OPT
@@ -47,11 +40,8 @@ def smi():
         return {"err": str(e)[:60]}
 
 
-c = Client(1, 1, 2, params=p, seed=0xAE50001)
-keys = c.server_keys()
-E = _native.Engine(p, allow_dev_build=True)
-E.upload_keys(keys.ksk, keys.bsk, keys.pfpksk)
-say("library:", (_native.load_library().fheaes_version() or b"").decode(), " K2 plan:", E.k2_plan(M))
+c, E = measure.session(0xAE50001, 1, 2, library=library, allow_dev_build=True)
+say("library:", (E._lib.fheaes_version() or b"").decode(), " K2 plan:", E.k2_plan(M))
 rng = np.random.default_rng(11)
 x = torch.from_numpy(c.encrypt_bits(rng.integers(0, 2, M).astype(np.uint8)).view(np.int64)).cuda()
 luts = torch.from_numpy(np.stack([gen_lut(2, 1, 512, 8, f) for f in (lambda v: SBOX[v], lambda v: mul2(SBOX[v]), lambda v: mul3(SBOX[v]))]).view(np.int64)).cuda()
