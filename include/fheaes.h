@@ -555,6 +555,56 @@ int fheaes_xts_whiten(fheaes_ctx *ctx, uint64_t *dst, const uint64_t *src, const
 int fheaes_aes_mac_plan(const uint32_t *stream_blocks, const uint32_t *payload_blocks, uint64_t n_streams, uint64_t *steps, uint64_t *n_active_out,
                         uint64_t n_active_cap, uint64_t *public_blocks, uint64_t *chained_blocks);
 
+/* ---- CMAC --------------------------------------------------------------------------------- */
+/* AES-CMAC (SP 800-38B, RFC 4493) of PUBLIC messages under encrypted keys: the MIC of LoRaWAN, AUTOSAR SecOC, the OMAC of EAX, the S2V of
+ * SIV, CTR + CMAC as encrypt-then-MAC.  A CMAC is the CBC-MAC above whose last block also gets a subkey added: K1 = L x under a whole
+ * last block, K2 = L x^2 under one padded with 0x80 00.., in GF(2^128) mod x^128 + x^7 + x^2 + x + 1 with L = E_K(0^128).  All blocks
+ * are public, so no decryption precedes the tag check.  Levels against FHEAES_MAX_NOISE_LEVEL = 5: L leaves the public call at 2 and an
+ * identity WoPBS makes it 1; one gather gives K1 at 2 and K2 at 3; a second identity WoPBS makes both 1, counted as a chain counts every
+ * encrypted addend, 2: the last link is X (2) + subkey (2) + round key = 5, the tag difference 2.  Both refreshes are needed: a raw K2
+ * from a raw L would be 2 * 3, an unrefreshed K2 from a refreshed L 2 + 3 + 1 = 6.  48 byte-WoPBS per key, against 16 Nr per chained block.
+ *
+ * Bounds and refusals as in the section above: a NULL argument that is not optional, overlapping in and out buffers, a count above its
+ * bound, a key index >= n_keys, a tag length outside 4..16, key_bits not 128 / 192 / 256 and a message of more than
+ * 16 * FHEAES_MAC_MAX_STREAM_BLOCKS bytes are FHEAES_ERR_INVALID before anything is launched, and the outputs are untouched.
+ * n_streams = 0 is FHEAES_OK and writes nothing; FHEAES_DEVICE calls only enqueue. */
+/* The sources of output bit `bit` (flattened [16][8] index: byte p, bit b LSB first, is 8p + b -- degree 8 (15 - p) + b of the field
+ * element, where XTS has 8p + b) of L x^(which + 1), which = 0: K1, 1: K2.  At most 2 and 3 distinct sources; sources_out has room for 3.
+ * Host logic only.  which > 1 or bit > 127: FHEAES_ERR_INVALID. */
+int fheaes_cmac_subkey_row(uint32_t which, uint32_t bit, uint32_t *sources_out, uint32_t *n_sources);
+/* K6 alone, the raw gather (needs no keys): out[key][which][i] = the wrapping sum over fheaes_cmac_subkey_row(which, i) of l[key][source].
+ * l [n_keys][128][kN+1], out [n_keys][2][128][kN+1], both subkeys of all keys from one launch.  Declares row weight 3 to the noise guard. */
+int fheaes_cmac_double(fheaes_ctx *ctx, const uint64_t *l, uint64_t n_keys, uint64_t *out, int memspace);
+/* subkeys_out [n_keys][2][16][8][kN+1]: K1 and K2 of every key.  Word for word: fheaes_aes_public_keyed on one zero block per key, the
+ * identity WoPBS on its 16 n_keys bytes, fheaes_cmac_double, the identity WoPBS on its 32 n_keys bytes. */
+int fheaes_aes_cmac_subkeys_keyed(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t *subkeys_out,
+                                  int memspace);
+int fheaes_aes_cmac_subkeys_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys,
+                                         uint64_t *subkeys_out, int memspace);
+/* The CMAC of n_streams public messages, stream s under key key_of_stream[s], and -- with tags -- its comparison under encryption.
+ * subkeys: what fheaes_aes_cmac_subkeys_keyed gave for these keys, or NULL: they are derived here, only for the keys some stream names,
+ * and the words do not depend on which.  HOST arrays: key_of_stream, message_bytes, data (the messages' bytes, stream after stream, no
+ * padding; may be NULL when every message is empty), tags [n_streams][16] with tag_bytes [n_streams] (the first t = 4..16 bytes of the
+ * tag are compared), or both NULL.
+ *   (a) the blocks: n = max(1, ceil(bytes / 16)); a last block that is whole takes K1, else it is padded with 0x80 00.. and takes K2
+ *       (the empty message: one block 0x80 00.. with K2);
+ *   (b) fheaes_aes_cbc_mac_keyed with those blocks as `clear`, each stream's last block carrying its subkey as `enc` with enc_bytes = 16
+ *       (0 elsewhere), init NULL;
+ *   (c) with tags, diff = X + trivial(tag) on its first 8t rows, zero words beyond;
+ *   (d) the two comparison WoPBS of fheaes_aes_ccm_open_keyed's step (d) on diff.
+ * mac_out [n_streams][16][8][kN+1]: the full T of every stream (truncation is the caller's); required without tags, may be NULL with them.
+ * valid_out [n_streams][kN+1]: an encryption of 1 iff the tag is right; required with tags, must be NULL without them.  EAX's OMAC^t is
+ * this CMAC over [t]_128 || M and needs nothing more. */
+int fheaes_aes_cmac_keyed(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint64_t *subkeys,
+                          uint64_t n_streams, const uint32_t *key_of_stream, const uint64_t *message_bytes, const uint8_t *data,
+                          const uint8_t *tags, const uint32_t *tag_bytes, uint64_t *mac_out, uint64_t *valid_out, int memspace);
+int fheaes_aes_cmac_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, const uint64_t *subkeys,
+                                 uint64_t n_streams, const uint32_t *key_of_stream, const uint64_t *message_bytes, const uint8_t *data,
+                                 const uint8_t *tags, const uint32_t *tag_bytes, uint64_t *mac_out, uint64_t *valid_out, int memspace);
+/* What a CMAC call over messages of these lengths runs (host logic only): *steps cipher passes, *chained_blocks cipher blocks in all,
+ * *padded_streams streams whose last block takes K2. */
+int fheaes_aes_cmac_plan(const uint64_t *message_bytes, uint64_t n_streams, uint64_t *steps, uint64_t *chained_blocks, uint64_t *padded_streams);
+
 /* ---- measurement --------------------------------------------------------------- */
 #define FHEAES_STAGE_KEYSWITCH 0
 #define FHEAES_STAGE_BLIND_ROTATE 1

@@ -116,6 +116,15 @@ SIGNATURES = {
     "fheaes_mac_link": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_uint64, _u32p, _u8p, _u8p, _c.c_int]),
     "fheaes_xts_whiten": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _u32p, _u8p, _c.c_uint64, _c.c_int]),
     "fheaes_aes_mac_plan": (_c.c_int, [_u32p, _u32p, _c.c_uint64, _u64p, _u64p, _c.c_uint64, _u64p, _u64p]),
+    "fheaes_cmac_subkey_row": (_c.c_int, [_c.c_uint32, _c.c_uint32, _u32p, _u32p]),
+    "fheaes_cmac_double": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_cmac_subkeys_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_cmac_subkeys_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_cmac_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_uint64, _u32p, _u64p, _u8p, _u8p, _u32p, _c.c_void_p,
+                                         _c.c_void_p, _c.c_int]),
+    "fheaes_aes_cmac_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_uint64, _u32p, _u64p, _u8p, _u8p, _u32p,
+                                                _c.c_void_p, _c.c_void_p, _c.c_int]),
+    "fheaes_aes_cmac_plan": (_c.c_int, [_u64p, _c.c_uint64, _u64p, _u64p, _u64p]),
     "fheaes_profile_enable": (_c.c_int, [_ctx, _c.c_int]),
     "fheaes_profile_reset": (_c.c_int, [_ctx]),
     "fheaes_profile_read": (_c.c_int, [_ctx, _c.c_int, _dp, _u64p, _u64p]),
@@ -489,6 +498,36 @@ class Engine:
                                               src.ctypes.data_as(_u32p) if src is not None else None, eb.ctypes.data_as(_u8p) if eb is not None else None,
                                               clr.ctypes.data_as(_u8p), self._space(state, init, enc)))
 
+    # CMAC (include/fheaes.h): the subkeys [n_keys][2][16][8][kN+1], the messages as host bytes
+    def cmac_double(self, l, n_keys: int, out):
+        """K6 alone (fheaes_cmac_double): out[key][which] = l[key] * x^(which + 1) in CMAC's byte order, the raw gather: l
+        [n_keys][128][kN+1], out [n_keys][2][128][kN+1]; needs no keys"""
+        self._check(self._lib.fheaes_cmac_double(self._h, _ptr(l)[0], n_keys, _ptr(out)[0], self._space(l, out)))
+
+    def aes_cmac_subkeys_keyed(self, round_keys, key_bits: int, n_keys: int, subkeys_out, packed: bool = False):
+        fn = self._lib.fheaes_aes_cmac_subkeys_keyed_packed if packed else self._lib.fheaes_aes_cmac_subkeys_keyed
+        self._check(fn(self._h, _ptr(round_keys)[0], key_bits, n_keys, _ptr(subkeys_out)[0], self._space(round_keys, subkeys_out)))
+
+    def aes_cmac_keyed(self, round_keys, key_bits: int, n_keys: int, subkeys, key_of_stream, message_bytes, data, tags, tag_bytes, mac_out, valid_out,
+                       packed: bool = False):
+        """fheaes_aes_cmac_keyed / _packed: message_bytes[s] bytes of `data` per stream; tags [n][16] bytes with tag_bytes[s] real ones, or
+        both None; subkeys [n_keys][2][16][8][kN+1] or None (derived in the call)"""
+        mb = np.ascontiguousarray(np.asarray(message_bytes, dtype=np.uint64).reshape(-1))
+        kos = key_indices(key_of_stream, len(mb))
+        dt = np.frombuffer(bytes(data) + b"\x00", dtype=np.uint8)                  # never an empty buffer
+        if len(dt) - 1 != int(mb.sum()) or (tags is None) != (tag_bytes is None):
+            raise ValueError("the per-stream arrays of a CMAC call do not agree")
+        tg = tb = None
+        if tags is not None:
+            tg = np.ascontiguousarray(np.asarray(tags, dtype=np.uint8).reshape(-1, 16))
+            tb = np.ascontiguousarray(np.asarray(tag_bytes, dtype=np.uint32).reshape(-1))
+            if not len(tg) == len(tb) == len(mb):
+                raise ValueError("the per-stream arrays of a CMAC call do not agree")
+        fn = self._lib.fheaes_aes_cmac_keyed_packed if packed else self._lib.fheaes_aes_cmac_keyed
+        self._check(fn(self._h, _ptr(round_keys)[0], key_bits, n_keys, _ptr(subkeys)[0], len(mb), kos.ctypes.data_as(_u32p), mb.ctypes.data_as(_u64p),
+                       dt.ctypes.data_as(_u8p), tg.ctypes.data_as(_u8p) if tg is not None else None, tb.ctypes.data_as(_u32p) if tb is not None else None,
+                       _ptr(mac_out)[0], _ptr(valid_out)[0], self._space(round_keys, subkeys, mac_out, valid_out)))
+
     def xts_whiten(self, dst, src, tweaks, tweak_of_block, clear):
         """K6 alone (fheaes_xts_whiten): dst[b] = (src[b] or 0) + tweaks[tweak_of_block[b]] + trivial(clear[b]); src may be dst or None,
         clear [n][16] bytes or None; needs no keys"""
@@ -711,6 +750,27 @@ def aes_mac_plan(stream_blocks, payload_blocks=None) -> dict:
     if rc != 0:
         raise FheAesError(rc, "fheaes_aes_mac_plan: at most 2^20 streams of at most 2^16 blocks, payload blocks within them")
     return {"steps": steps.value, "n_active": [int(x) for x in act[:steps.value]], "chained_blocks": chained.value, "public_blocks": pub.value}
+
+
+def cmac_subkey_row(which: int, bit: int) -> list[int]:
+    """the source bits whose sum is output bit `bit` of L * x^(which + 1) in CMAC's big-endian byte order, which 0 (K1) or 1 (K2)
+    (fheaes_cmac_subkey_row: host only, no GPU)"""
+    src, n = (_c.c_uint32 * 3)(), _c.c_uint32()
+    rc = load_library().fheaes_cmac_subkey_row(which, bit, src, _c.byref(n))
+    if rc != 0:
+        raise FheAesError(rc, "fheaes_cmac_subkey_row: which must be 0 or 1 and bit below 128")
+    return [int(x) for x in src[:n.value]]
+
+
+def aes_cmac_plan(message_bytes) -> dict:
+    """fheaes_aes_cmac_plan (host only, no GPU): what a CMAC call over messages of these lengths runs -- {"steps" (cipher passes),
+    "chained_blocks" (cipher blocks in all), "padded_streams" (streams whose last block takes K2)}"""
+    mb = np.ascontiguousarray(np.asarray(message_bytes, dtype=np.uint64).reshape(-1))
+    steps, chained, padded = _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
+    rc = load_library().fheaes_aes_cmac_plan(mb.ctypes.data_as(_u64p), len(mb), _c.byref(steps), _c.byref(chained), _c.byref(padded))
+    if rc != 0:
+        raise FheAesError(rc, "fheaes_aes_cmac_plan: at most 2^20 streams of at most 16 * 2^16 bytes")
+    return {"steps": steps.value, "chained_blocks": chained.value, "padded_streams": padded.value}
 
 
 def round_keys_packed_glwes(key_bits: int) -> int:

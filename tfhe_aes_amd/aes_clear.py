@@ -287,6 +287,44 @@ def ccm_decrypt(key, nonce: bytes, aad: bytes, ciphertext_and_tag: bytes, tag_le
     return payload if _ccm_tag(key, b0, aad_blocks, payload, aes_encrypt_block(key, ctr[0]), tag_len) == tag else None
 
 
+def _cmac_double(v: int) -> int:
+    """v * x in GF(2^128) mod x^128 + x^7 + x^2 + x + 1, the block a big-endian integer (SP 800-38B 6.1: shift left, R_128 = 0x87)"""
+    v <<= 1
+    return (v ^ 0x87) & ((1 << 128) - 1) if v >> 128 else v
+
+
+def cmac_subkeys(key):
+    """SP 800-38B 6.1 (RFC 4493 2.3): (K1, K2) = (L x, L x^2), L = E_K(0^128), as u128"""
+    k1 = _cmac_double(aes_encrypt_block(key, 0))
+    return k1, _cmac_double(k1)
+
+
+def cmac_blocks(msg: bytes):
+    """SP 800-38B 6.2 -> (blocks, which): the n = max(1, ceil(len / 16)) u128 blocks of a message (byte 0 most significant) and the subkey
+    its last block takes -- 0 (K1) for a whole last block, 1 (K2) for one padded with 0x80 00..; the empty message is the one block
+    0x80 00.. with K2"""
+    msg = bytes(msg)
+    which = 0 if msg and len(msg) % 16 == 0 else 1
+    if which:
+        msg += b"\x80" + bytes(-(len(msg) + 1) % 16)
+    return [int.from_bytes(msg[i:i + 16], "big") for i in range(0, len(msg), 16)], which
+
+
+def cmac(key, msg: bytes, tag_len: int = 16) -> bytes:
+    """AES-CMAC (SP 800-38B 6.2, RFC 4493) for any of the three key sizes: MSB_tag_len of the CBC-MAC whose last block also gets its subkey"""
+    if not 1 <= tag_len <= 16:
+        raise ValueError("a CMAC tag has 1 to 16 bytes, got %r" % (tag_len,))
+    blocks, which = cmac_blocks(msg)
+    blocks[-1] ^= cmac_subkeys(key)[which]
+    return cbc_mac(key, blocks).to_bytes(16, "big")[:tag_len]
+
+
+def cmac_verify(key, msg: bytes, tag: bytes) -> bool:
+    """SP 800-38B 6.3: whether `tag` is the first len(tag) bytes of the CMAC of msg"""
+    tag = bytes(tag)
+    return 1 <= len(tag) <= 16 and cmac(key, msg, len(tag)) == tag
+
+
 def aes128_encrypt_block(key: int, block: int) -> int:
     return aes_encrypt_block(key, block)
 

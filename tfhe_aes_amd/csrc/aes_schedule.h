@@ -609,14 +609,26 @@ struct CcmCall {
     size_t tag0 = 0, pt0 = 0;                           // where the tag and the payload records start
 };
 
+// The tag check of CCM and CMAC.  diff [n][128][kN+1] is zero on its first 8t rows iff the tag is right, and zero words from row 8t on;
+// WoPBS 1 (8 bits, every byte of the 16) gives byte != 0, WoPBS 2 takes those 16 bits as one input and gives 1 on input 0.  valid_out
+// [n][kN+1]: row 0 of the second WoPBS.  diff is overwritten (the bits of the second WoPBS); ws_vp (n states, the caller's) holds both outputs.
+static int tag_check_dev(fheaes_ctx *c, uint64_t *diff, uint64_t n, uint64_t *valid_out)
+{
+    const uint64_t row = (uint64_t)c->big1 * 8;
+    uint64_t *vp = (uint64_t *)c->ws_vp.p;
+    TRY(wopbs_dev(c, diff, 16 * n, 8, c->lut_tag_d[0], 1, 0, vp));
+    HIP_TRY(c, hipMemcpy2DAsync(diff, row, vp, 8 * row, row, 16 * n, hipMemcpyDeviceToDevice, c->stream));
+    TRY(wopbs_dev(c, diff, n, 16, c->lut_tag_d[1], 1, 0, vp));
+    HIP_TRY(c, hipMemcpy2DAsync(valid_out, row, vp, 16 * row, row, n, hipMemcpyDeviceToDevice, c->stream));
+    return FHEAES_OK;
+}
+
 // ws_tmp_a: the public call's outputs; ws_tmp_b: the chain's state; ws_tmp_c: the tag difference, then the bits of the second WoPBS.
-// valid_out [n][kN+1]: row 0 of the second WoPBS.  The tag check: diff = X_final + S0 + trivial(tag) is zero on its first 8t rows iff the
-// tag is right (level 4); WoPBS 1 (8 bits, every byte of the 16: rows from 8t on are zero words) gives byte != 0, WoPBS 2 takes those 16
-// bits as one input and gives 1 on input 0.
+// diff = X_final + S0 + trivial(tag) on its first 8t rows (level 4), then tag_check_dev.
 static int ccm_open_dev(fheaes_ctx *c, const KeySets &rk, int nr, uint64_t n_keys, const CcmCall &cc, const PublicPlan &pp, uint64_t *plaintext_out,
                         uint64_t *valid_out)
 {
-    const uint64_t sw = AES_BLOCK_BITS * c->big1, n = cc.n, row = (uint64_t)c->big1 * 8;
+    const uint64_t sw = AES_BLOCK_BITS * c->big1, n = cc.n;
     TRY(ensure(c, c->ws_tmp_a, (cc.payload_blocks + 2 * n) * sw * 8));
     TRY(ensure(c, c->ws_tmp_b, n * sw * 8));
     TRY(ensure(c, c->ws_tmp_c, n * sw * 8));
@@ -627,10 +639,64 @@ static int ccm_open_dev(fheaes_ctx *c, const KeySets &rk, int nr, uint64_t n_key
     TRY(cbc_mac_dev(c, rk, nr, n_keys, cc.chain, pub, pub, state, &recs));
     TRY(launch_mac_link(c, diff, state, pub, recs + cc.tag0, n, 4, "the CCM tag difference (X + S0 + tag)"));
     TRY(launch_mac_link(c, plaintext_out, nullptr, pub, recs + cc.pt0, cc.payload_blocks, 2, "the CCM plaintext"));
-    uint64_t *vp = (uint64_t *)c->ws_vp.p;
-    TRY(wopbs_dev(c, diff, 16 * n, 8, c->lut_tag_d[0], 1, 0, vp));
-    HIP_TRY(c, hipMemcpy2DAsync(diff, row, vp, 8 * row, row, 16 * n, hipMemcpyDeviceToDevice, c->stream));
-    TRY(wopbs_dev(c, diff, n, 16, c->lut_tag_d[1], 1, 0, vp));
-    HIP_TRY(c, hipMemcpy2DAsync(valid_out, row, vp, 16 * row, row, n, hipMemcpyDeviceToDevice, c->stream));
+    return tag_check_dev(c, diff, n, valid_out);
+}
+
+// ---- CMAC over many streams (SP 800-38B, RFC 4493) -----------------------------------------------------------------------------------------
+// T = the CBC-MAC of the message whose last block also gets a subkey added: K1 = L x under a whole last block, K2 = L x^2 under a padded
+// one, L = E_K(0^128).  Every block is public, so the chain above runs as it is with the subkey as the last block's encrypted addend: the
+// records' b is 2 * key + which into the subkey array.  Levels against the guard's 5: L leaves the public call at 2, an identity WoPBS
+// makes it 1; the gather (cmac_subkey_kernel) gives K1 at 2 and K2 at 3; a second identity WoPBS makes both 1, counted -- as every
+// addend of a chain -- as 2: the last link is X (2) + subkey (2) + round key = 5.  Without the second refresh it would be 2 + 3 + 1 = 6,
+// and without the first K2 alone would be 2 * 3.  48 byte-WoPBS per key, against 16 Nr per chained block.
+
+// The subkeys of keys key_of[0 .. m) of rk, out [m][2][16][8][kN+1].  Workspace: ws_tmp_a E_K(0) of the m keys,
+// ws_tmp_c L, ws_tmp_b the raw subkeys -- ensured by the caller for m, m and 2m states; out may be ws_tmp_a.
+static int cmac_subkeys_dev(fheaes_ctx *c, const KeySets &rk, int nr, const uint32_t *key_of, uint64_t m, uint64_t *out)
+{
+    uint64_t *enc0 = (uint64_t *)c->ws_tmp_a.p, *l = (uint64_t *)c->ws_tmp_c.p, *raw = (uint64_t *)c->ws_tmp_b.p;
+    const std::vector<uint64_t> zero(2 * m, 0);
+    PublicPlan pp;
+    public_plan(public_forward(), zero.data(), nullptr, key_of, m, nr, pp);
+    TRY(aes_public_dev(c, public_forward(), rk, pp, nr, enc0));
+    TRY(many_sbox_dev(c, enc0, 16 * m, LUTSET_IDENTITY, l));
+    TRY(launch_cmac_double(c, l, m, raw));
+    TRY(many_sbox_dev(c, raw, 32 * m, LUTSET_IDENTITY, out));
     return FHEAES_OK;
+}
+
+// A CMAC call on the host: len[s] chain blocks per stream, the chain's records and, behind them, n records that bring the MACs to the
+// caller's order (mac0; only where the call returns them) and n tag-difference records (tag0; only with tags).  used: the keys some
+// stream names, ascending -- the subkeys a call without the caller's own derives, in this order.
+struct CmacCall {
+    uint64_t n = 0;
+    std::vector<uint32_t> len, used;
+    MacPlan plan;
+    MacChain chain;
+    size_t mac0 = 0, tag0 = 0;
+};
+
+// the chain blocks of a message of `bytes` bytes (SP 800-38B 6.2: the empty message is one padded block)
+static uint64_t cmac_blocks(uint64_t bytes) { return bytes ? (bytes + 15) / 16 : 1; }
+
+// subkeys: the caller's [n_keys][2][16][8][kN+1], or null: derived for cc.used into ws_tmp_a.  ws_tmp_b: the chain's state; ws_tmp_c: the
+// tag difference.  diff = X + trivial(tag) on its first 8t rows (level 2), then tag_check_dev.  mac_out, valid_out: either may be null.
+static int cmac_dev(fheaes_ctx *c, const KeySets &rk, int nr, uint64_t n_keys, const CmacCall &cc, const uint64_t *subkeys, uint64_t *mac_out, uint64_t *valid_out)
+{
+    const uint64_t sw = AES_BLOCK_BITS * c->big1, n = cc.n, m = subkeys ? 0 : cc.used.size();
+    TRY(ensure(c, c->ws_tmp_a, 2 * m * sw * 8));
+    TRY(ensure(c, c->ws_tmp_b, std::max(2 * m, n) * sw * 8));
+    TRY(ensure(c, c->ws_tmp_c, std::max(m, n) * sw * 8));
+    if (valid_out) TRY(ensure(c, c->ws_vp, n * sw * 8));
+    if (!subkeys) {
+        TRY(cmac_subkeys_dev(c, rk, nr, cc.used.data(), m, (uint64_t *)c->ws_tmp_a.p));
+        subkeys = (const uint64_t *)c->ws_tmp_a.p;
+    }
+    uint64_t *state = (uint64_t *)c->ws_tmp_b.p, *diff = (uint64_t *)c->ws_tmp_c.p;
+    const MacSlot *recs = nullptr;
+    TRY(cbc_mac_dev(c, rk, nr, n_keys, cc.chain, nullptr, subkeys, state, &recs));
+    if (mac_out) TRY(launch_mac_link(c, mac_out, state, nullptr, recs + cc.mac0, n, 2, "the CMACs in the caller's order"));
+    if (!valid_out) return FHEAES_OK;
+    TRY(launch_mac_link(c, diff, state, nullptr, recs + cc.tag0, n, 2, "the CMAC tag difference (T + tag)"));
+    return tag_check_dev(c, diff, n, valid_out);
 }

@@ -1388,6 +1388,160 @@ int fheaes_aes_mac_plan(const uint32_t *stream_blocks, const uint32_t *payload_b
     return FHEAES_OK;
 }
 
+// ---- CMAC -------------------------------------------------------------------------------------
+int fheaes_cmac_subkey_row(uint32_t which, uint32_t bit, uint32_t *sources_out, uint32_t *n_sources)
+{
+    if (which > 1 || bit > 127 || !sources_out || !n_sources) return FHEAES_ERR_INVALID;
+    uint32_t s[3] = {0, 0, 0};
+    *n_sources = cmac_subkey_row(which, bit, s);
+    memcpy(sources_out, s, sizeof s);
+    return FHEAES_OK;
+}
+
+int fheaes_cmac_double(fheaes_ctx *c, const uint64_t *l, uint64_t n_keys, uint64_t *out, int memspace)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    if (n_keys == 0) return FHEAES_OK;
+    TRY(check_n_keys(c, n_keys));
+    if (!l || !out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    const uint64_t in_bytes = n_keys * AES_BLOCK_BITS * c->big1 * 8, out_bytes = 2 * in_bytes;
+    if (overlap(l, in_bytes, out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "l and out overlap (the gather is not in place)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    TRY(s.in(l, in_bytes, &l));
+    TRY(s.out(out, out_bytes, &out));
+    TRY(launch_cmac_double(c, l, n_keys, out));
+    return s.finish();
+}
+
+static int aes_cmac_subkeys(fheaes_ctx *c, RoundKeys k, uint64_t *subkeys_out, int memspace)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    if (!k.words || !subkeys_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(resolve_keys(c, k));
+    const uint64_t sw = 16ull * 8 * c->big1, out_bytes = 2 * k.n_keys * sw * 8;
+    if (k.overlaps(subkeys_out, out_bytes)) return c->fail(FHEAES_ERR_INVALID, "the round keys and subkeys_out overlap");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged st(c, memspace);
+    TRY(k.stage(st));
+    TRY(st.out(subkeys_out, out_bytes, &subkeys_out));
+    TRY(ensure(c, c->ws_tmp_a, k.n_keys * sw * 8));
+    TRY(ensure(c, c->ws_tmp_b, 2 * k.n_keys * sw * 8));
+    TRY(ensure(c, c->ws_tmp_c, k.n_keys * sw * 8));
+    std::vector<uint32_t> all(k.n_keys);
+    for (uint64_t j = 0; j < k.n_keys; ++j) all[j] = (uint32_t)j;
+    TRY(cmac_subkeys_dev(c, k.sets(), k.nr, all.data(), k.n_keys, subkeys_out));
+    return st.finish();
+}
+
+int fheaes_aes_cmac_subkeys_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t *subkeys_out, int memspace)
+{
+    return aes_cmac_subkeys(c, {round_keys, key_bits, n_keys, nullptr, 0, false}, subkeys_out, memspace);
+}
+
+int fheaes_aes_cmac_subkeys_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t *subkeys_out, int memspace)
+{
+    return aes_cmac_subkeys(c, {packed_round_keys, key_bits, n_keys, nullptr, 0, true}, subkeys_out, memspace);
+}
+
+// k.key_of: the key of every stream, k.n_of of them
+static int aes_cmac(fheaes_ctx *c, RoundKeys k, const uint64_t *subkeys, const uint64_t *message_bytes, const uint8_t *data, const uint8_t *tags, const uint32_t *tag_bytes,
+                    uint64_t *mac_out, uint64_t *valid_out, int memspace)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    const uint64_t n = k.n_of;
+    const uint32_t *key_of_stream = k.key_of;
+    if (!k.words || !key_of_stream || !message_bytes || (tags != nullptr) != (tag_bytes != nullptr) || (tags ? !valid_out : !mac_out))
+        return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    if (!tags && valid_out) return c->fail(FHEAES_ERR_INVALID, "valid_out without tags: there is nothing to compare");
+    TRY(resolve_keys(c, k, MAC_MAX_STREAMS));
+    CmacCall cc;
+    cc.n = n;
+    cc.len.resize(n);
+    std::vector<uint64_t> boff(n + 1, 0);                                   // message bytes before stream s
+    uint64_t total = 0;
+    for (uint64_t s = 0; s < n; ++s) {
+        if (message_bytes[s] > 16ull * MAC_MAX_STREAM_BLOCKS)
+            return c->fail(FHEAES_ERR_INVALID, "message_bytes[%llu] = %llu: a stream chains at most %u blocks", (unsigned long long)s, (unsigned long long)message_bytes[s],
+                           MAC_MAX_STREAM_BLOCKS);
+        if (tags && (tag_bytes[s] < 4 || tag_bytes[s] > 16))
+            return c->fail(FHEAES_ERR_INVALID, "tag_bytes[%llu] = %u: a CMAC tag is compared on 4..16 bytes", (unsigned long long)s, tag_bytes[s]);
+        cc.len[s] = (uint32_t)cmac_blocks(message_bytes[s]);
+        boff[s + 1] = boff[s] + message_bytes[s];
+        total += cc.len[s];
+    }
+    if (boff[n] && !data) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    if (total > 0xFFFFFFFEull) return c->fail(FHEAES_ERR_INVALID, "a call chains fewer than 2^32 - 1 blocks");
+    if (n == 0) return FHEAES_OK;
+    const uint64_t sw = 16ull * 8 * c->big1, mac_bytes = n * sw * 8, valid_bytes = n * c->big1 * 8ull, sub_bytes = 2 * k.n_keys * sw * 8;
+    if ((mac_out && (k.overlaps(mac_out, mac_bytes) || (subkeys && overlap(subkeys, sub_bytes, mac_out, mac_bytes)))) ||
+        (valid_out && (k.overlaps(valid_out, valid_bytes) || (subkeys && overlap(subkeys, sub_bytes, valid_out, valid_bytes)))) ||
+        (mac_out && valid_out && overlap(mac_out, mac_bytes, valid_out, valid_bytes)))
+        return c->fail(FHEAES_ERR_INVALID, "mac_out, valid_out, the subkeys and the round keys overlap");
+    // where a stream's subkeys are: the caller's array has every key's, a derived one those of the keys in use
+    std::vector<uint32_t> at(k.n_keys, MAC_NONE);
+    for (uint64_t s = 0; s < n; ++s) at[key_of_stream[s]] = 0;
+    for (uint64_t j = 0; j < k.n_keys; ++j)
+        if (subkeys) at[j] = (uint32_t)j;
+        else if (at[j] != MAC_NONE) { at[j] = (uint32_t)cc.used.size(); cc.used.push_back((uint32_t)j); }
+    mac_plan(cc.len.data(), n, cc.plan);
+    mac_chain(cc.plan, cc.len.data(), key_of_stream, n, [&](uint32_t s, uint32_t i, uint8_t *clr, uint32_t *e, uint32_t *eb) {
+        const uint64_t have = std::min<uint64_t>(16, message_bytes[s] - std::min<uint64_t>(message_bytes[s], 16ull * i));
+        if (have) memcpy(clr, data + boff[s] + 16ull * i, have);
+        if (i + 1 < cc.len[s]) return;
+        if (have < 16) clr[have] = 0x80;                                     // the padded last block takes K2, the whole one K1
+        *e = 2 * at[key_of_stream[s]] + (have < 16 ? 1u : 0u);
+        *eb = 16;
+    }, [&](uint32_t) { return MAC_NONE; }, cc.chain);
+    cc.mac0 = cc.chain.slots.size();
+    if (mac_out) for (uint64_t s = 0; s < n; ++s) cc.chain.slots.push_back(mac_slot(cc.plan.slot_of[s], MAC_NONE, 0, 16, nullptr));
+    cc.tag0 = cc.chain.slots.size();
+    if (tags) for (uint64_t s = 0; s < n; ++s) cc.chain.slots.push_back(mac_slot(cc.plan.slot_of[s], MAC_NONE, 0, tag_bytes[s], tags + 16 * s, tag_bytes[s]));
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged st(c, memspace);
+    TRY(k.stage(st));
+    if (subkeys) TRY(st.in(subkeys, sub_bytes, &subkeys));
+    if (mac_out) TRY(st.out(mac_out, mac_bytes, &mac_out));
+    if (valid_out) TRY(st.out(valid_out, valid_bytes, &valid_out));
+    TRY(cmac_dev(c, k.sets(), k.nr, k.n_keys, cc, subkeys, mac_out, valid_out));
+    return st.finish();
+}
+
+int fheaes_aes_cmac_keyed(fheaes_ctx *c, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, const uint64_t *subkeys, uint64_t n_streams,
+                          const uint32_t *key_of_stream, const uint64_t *message_bytes, const uint8_t *data, const uint8_t *tags, const uint32_t *tag_bytes,
+                          uint64_t *mac_out, uint64_t *valid_out, int memspace)
+{
+    return aes_cmac(c, {round_keys, key_bits, n_keys, key_of_stream, n_streams, false}, subkeys, message_bytes, data, tags, tag_bytes, mac_out, valid_out, memspace);
+}
+
+int fheaes_aes_cmac_keyed_packed(fheaes_ctx *c, const uint64_t *packed_round_keys, uint32_t key_bits, uint64_t n_keys, const uint64_t *subkeys, uint64_t n_streams,
+                                 const uint32_t *key_of_stream, const uint64_t *message_bytes, const uint8_t *data, const uint8_t *tags, const uint32_t *tag_bytes,
+                                 uint64_t *mac_out, uint64_t *valid_out, int memspace)
+{
+    return aes_cmac(c, {packed_round_keys, key_bits, n_keys, key_of_stream, n_streams, true}, subkeys, message_bytes, data, tags, tag_bytes, mac_out, valid_out, memspace);
+}
+
+int fheaes_aes_cmac_plan(const uint64_t *message_bytes, uint64_t n_streams, uint64_t *steps, uint64_t *chained_blocks, uint64_t *padded_streams)
+{
+    if ((n_streams && !message_bytes) || !steps || !chained_blocks || !padded_streams || n_streams > MAC_MAX_STREAMS) return FHEAES_ERR_INVALID;
+    std::vector<uint32_t> len(n_streams);
+    uint64_t padded = 0;
+    for (uint64_t s = 0; s < n_streams; ++s) {
+        if (message_bytes[s] > 16ull * MAC_MAX_STREAM_BLOCKS) return FHEAES_ERR_INVALID;
+        len[s] = (uint32_t)cmac_blocks(message_bytes[s]);
+        padded += message_bytes[s] == 0 || message_bytes[s] % 16 != 0;
+    }
+    MacPlan pl;
+    mac_plan(len.data(), n_streams, pl);
+    *steps = pl.n_active.size(); *chained_blocks = pl.chained; *padded_streams = padded;
+    return FHEAES_OK;
+}
+
 // ---- packing ----------------------------------------------------------------------------------
 size_t fheaes_packed_words(const fheaes_ctx *c, uint64_t m)
 {

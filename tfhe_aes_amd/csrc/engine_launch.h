@@ -480,6 +480,18 @@ int launch_mac_link(fheaes_ctx *c, uint64_t *dst, const uint64_t *a, const uint6
     return FHEAES_OK;
 }
 
+// cmac_subkey_kernel: K1 and K2 of n_keys keys from their L.  It declares the largest row weight, 3 (K2's: kern_linear.h).  Units: keys.
+int launch_cmac_double(fheaes_ctx *c, const uint64_t *l, uint64_t n_keys, uint64_t *out)
+{
+    if (n_keys == 0) return FHEAES_OK;
+    static_assert(256ull * FHEAES_MAX_KEYS <= 0x7FFFFFFFull, "the rows of FHEAES_MAX_KEYS keys are one grid dimension");
+    TRY(noise_guard(c, 3, "the CMAC subkey layer (multiplication by x and x^2)"));
+    StageScope sc(c, FHEAES_STAGE_LINEAR, n_keys);
+    hipLaunchKernelGGL(cmac_subkey_kernel, dim3((unsigned)(n_keys * 256)), dim3(256), 0, c->stream, l, out, c->big1);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
 // ---- packing (fheaes_pack_bits, fheaes_unpack_bits) ---------------------------------------------------------------------------
 static_assert(PACK_N == FHE_N && PACK_N % PACK_FOLD_ROWS == 0, "kern_linear.h's packing kernels are written for N = 512");
 

@@ -6,6 +6,7 @@
 //   inv_shift_rows            src/server/decrypt/inv_shift_rows.rs:5-21
 //   add_round_key             src/server/server.rs:278-282
 //   (no counterpart)          the XTS tweak layer: multiplication by alpha^j in GF(2^128), xts_tweak_kernel below
+//   (no counterpart)          the CMAC subkeys: multiplication by x and x^2 in the big-endian byte order, cmac_subkey_kernel below
 // All of them are one "gather-add": out[blk][byte] = sum_t src[blk][tab.src[byte][t]][tab.lut[byte][t]] (+ rk[byte]).
 // The round key comes from a source type (LweKeys, PackedKeys below): every layer that adds one is ONE kernel template over that type,
 // so round keys in LWE form and in a packed store go through the same body.
@@ -247,6 +248,52 @@ __global__ __launch_bounds__(256) void mac_link_kernel(uint64_t *dst, const uint
             }
             db[i] = v;
         }
+    }
+}
+
+// ---- CMAC (SP 800-38B, RFC 4493): the subkeys --------------------------------------------------------------------------------------------
+// K1 = L * x and K2 = L * x^2 in GF(2^128) mod x^128 + x^7 + x^2 + x + 1, L = E_K(0^128): the XTS arithmetic in the other byte order.  A
+// CMAC block is a big-endian integer, so bit b (LSB first) of block byte p -- flattened [16][8] index i = 8p + b -- is degree
+// 8 (15 - p) + b where XTS has 8p + b.  The map between index and degree is its own inverse.
+__host__ __device__ __forceinline__ uint32_t cmac_bit_degree(uint32_t i) { return (120u - (i & ~7u)) | (i & 7u); }
+
+// The sources of output bit i of L * x^(which + 1), which in {0: K1, 1: K2}: xts_tweak_row's rule for j = which + 1 on degrees, mapped back
+// to indices.  With j <= 2 only the degrees 0, 1, 2, 3, 7 and 8 receive reduction terms, one or two each: the sources are distinct, at
+// most 2 for K1 and 3 for K2 (131 and 134 ones in the two 128 x 128 matrices).  Returns their count; sources[] are indices < 128.
+__host__ __device__ __forceinline__ uint32_t cmac_subkey_row(uint32_t which, uint32_t i, uint32_t (&sources)[3])
+{
+    const uint32_t back[4] = {0, 1, 2, 7};
+    const uint32_t j = which + 1, d = cmac_bit_degree(i);
+    uint32_t n = 0;
+    if (d >= j) sources[n++] = cmac_bit_degree(d - j);
+#pragma unroll
+    for (uint32_t t = 0; t < 4; ++t)
+        if (d >= back[t] && d - back[t] < j && n < 3) sources[n++] = cmac_bit_degree(128 - j + (d - back[t]));
+    return n;
+}
+
+// out[key][which][i][w] = sum over the row (which, i) of l[key][source][w]: both subkeys of every key in ONE launch, each output bit
+// gathered from L in one sum (K2 is not a doubling of the computed K1, for the reason given above xts_tweak_kernel).  l:
+// [n_keys][128][lwe_words]; out: [n_keys][2][128][lwe_words].  One workgroup per output row and the grid IS the rows -- 256 n_keys, 2^24 at
+// FHEAES_MAX_KEYS keys, inside one grid dimension: there is no second pass.  Lanes on consecutive w, 8-byte accesses as above; rows are
+// taken in order, so the 256 workgroups of a key are adjacent in the grid and re-read its L (2 MB at PARAM_OPT) from L2.  All offsets in
+// 64 bits.
+__global__ __launch_bounds__(256) void cmac_subkey_kernel(const uint64_t *l, uint64_t *out, uint32_t lwe_words)
+{
+    const uint64_t r = blockIdx.x;
+    uint32_t s[3];
+    const uint32_t n = cmac_subkey_row((uint32_t)(r >> 7) & 1u, (uint32_t)(r & 127), s);
+    const uint64_t *lb = l + (r >> 8) * 128 * lwe_words;
+    const uint64_t *p[3];                                        // fully unrolled so that the pointers stay in registers
+#pragma unroll
+    for (uint32_t t = 0; t < 3; ++t) p[t] = lb + (uint64_t)(t < n ? s[t] : 0u) * lwe_words;
+    uint64_t *o = out + r * lwe_words;
+    for (uint32_t w = threadIdx.x; w < lwe_words; w += blockDim.x) {
+        uint64_t v = 0;
+#pragma unroll
+        for (uint32_t t = 0; t < 3; ++t)
+            if (t < n) v += p[t][w];
+        o[w] = v;
     }
 }
 

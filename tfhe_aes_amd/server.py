@@ -200,6 +200,31 @@ def ccm_args(messages):
     return a
 
 
+def cmac_args(messages):
+    """aes_cmac_streams' (key_index, message) or aes_cmac_verify's (key_index, message, tag) -> the per-stream arrays of the C call, which
+    pads the blocks itself.  A dict: key_of_stream, message_bytes, data (the messages concatenated), chain_blocks (max(1, ceil(len / 16))
+    per stream) and, where the entries carry tags, tags [n][16] (zero-padded) and tag_bytes -- else both None"""
+    a = {"key_of_stream": [], "message_bytes": [], "data": b"", "chain_blocks": [], "tags": None, "tag_bytes": None}
+    messages = [tuple(m) for m in messages]
+    if len({len(m) for m in messages}) > 1 or any(len(m) not in (2, 3) for m in messages):
+        raise ValueError("every entry is (key_index, message), or every entry is (key_index, message, tag)")
+    if messages and len(messages[0]) == 3:
+        a["tags"], a["tag_bytes"] = [], []
+    for m in messages:
+        msg = bytes(m[1])
+        a["key_of_stream"].append(int(m[0]))
+        a["message_bytes"].append(len(msg))
+        a["data"] += msg
+        a["chain_blocks"].append(max(1, (len(msg) + 15) // 16))
+        if len(m) == 3:
+            tag = bytes(m[2])
+            if not 4 <= len(tag) <= 16:
+                raise ValueError("a CMAC tag is compared on 4 to 16 bytes, got %d" % len(tag))
+            a["tags"].append(list(tag) + [0] * (16 - len(tag)))
+            a["tag_bytes"].append(len(tag))
+    return a
+
+
 def _shards_by_cost(costs, g: int):
     """whole streams to g contexts, contiguous and balanced by cost: a stream goes to the context in whose g-th of the total cost its
     midpoint lies; shard i is [lo, hi), possibly empty"""
@@ -591,6 +616,54 @@ class Server:
                                            a["tags"], a["tag_bytes"], out if total else None, valid_out, packed=packed)
         return out, valid_out, a["block_of_message"]
 
+    # ---- CMAC: the MAC of public messages under encrypted keys, and its check -------------------
+    def aes_cmac_subkeys(self, round_keys, out=None):
+        """The CMAC subkeys (SP 800-38B 6.1) of every key: [n_keys][2][16][8][kN+1] (or `out`), [j][0] = K1 = L x and [j][1] = K2 = L x^2
+        with L = E_K(0^128), both refreshed -- 48 byte-WoPBS per key on top of the public call on one zero block
+        (include/fheaes.h: fheaes_aes_cmac_subkeys_keyed).  Derive them once per key set and pass them to aes_cmac_streams /
+        aes_cmac_verify as `subkeys`.  round_keys as aes_cbc_mac_streams'."""
+        words, bits, n_keys, packed = self._round_keys(round_keys, many=None)
+        out = self._many_out(words, (n_keys, 2, 16, 8, self.params.big1), out)
+        self.engine.aes_cmac_subkeys_keyed(words, bits, n_keys, out, packed=packed)
+        return out
+
+    def _cmac(self, round_keys, a, subkeys, mac_out, valid_out):
+        words, bits, n_keys, packed = self._round_keys(round_keys, many=None)
+        if subkeys is not None and tuple(subkeys.shape) != (n_keys, 2, 16, 8, self.params.big1):
+            raise ValueError("subkeys must be [%d][2][16][8][kN+1] (aes_cmac_subkeys of these round keys), got %s" % (n_keys, tuple(subkeys.shape)))
+        if a["key_of_stream"]:
+            self.engine.aes_cmac_keyed(words, bits, n_keys, subkeys, a["key_of_stream"], a["message_bytes"], a["data"], a["tags"], a["tag_bytes"], mac_out, valid_out,
+                                       packed=packed)
+
+    def aes_cmac_streams(self, round_keys, streams, subkeys=None, out=None):
+        """AES-CMAC (SP 800-38B, RFC 4493) of PUBLIC messages under encrypted keys: `streams` is a list of (key_index, message_bytes).
+        Returns the encrypted tags, the full T of every stream, [n][16][8][kN+1] (or `out`) in the caller's order; a truncated tag is
+        its leading bytes.  The CBC-MAC chain of aes_cbc_mac_streams over the padded blocks, each stream's last block with K1 (whole) or
+        K2 (padded) as its encrypted addend (include/fheaes.h: fheaes_aes_cmac_keyed).  subkeys: aes_cmac_subkeys(round_keys), or None:
+        derived in the call for the keys in use.  EAX's OMAC^t is this CMAC over [t]_128 || M and needs nothing more.  round_keys as
+        aes_cbc_mac_streams'."""
+        a = cmac_args(streams)
+        if a["tags"] is not None:
+            raise ValueError("aes_cmac_streams takes (key_index, message); a tag is checked by aes_cmac_verify")
+        words = self._round_keys(round_keys, many=None).words
+        out = self._many_out(words, (len(a["key_of_stream"]), 16, 8, self.params.big1), out)
+        self._cmac(round_keys, a, subkeys, out, None)
+        return out
+
+    def aes_cmac_verify(self, round_keys, messages, subkeys=None, valid_out=None):
+        """The CMAC tag check under encryption: `messages` is a list of (key_index, message, tag) with a tag of 4..16 bytes, compared with
+        the leading bytes of the CMAC.  Returns valid [n][kN+1] (or `valid_out`): valid[i] decrypts (Client.decrypt_bits) to 1 iff
+        message i's tag verifies.  All blocks are public, so no decryption precedes the check: the chain of aes_cmac_streams, then the
+        two comparison WoPBS of aes_ccm_decrypt.  EAX's OMAC^t is this CMAC over [t]_128 || M and needs nothing more.  subkeys and
+        round_keys as aes_cmac_streams'."""
+        a = cmac_args(messages)
+        if messages and a["tags"] is None:
+            raise ValueError("aes_cmac_verify takes (key_index, message, tag)")
+        words = self._round_keys(round_keys, many=None).words
+        valid_out = self._many_out(words, (len(a["key_of_stream"]), self.params.big1), valid_out)
+        self._cmac(round_keys, a, subkeys, None, valid_out)
+        return valid_out
+
     def _public_out(self, round_keys, n_blocks: int, out):
         return self._many_out(round_keys, (n_blocks, 16, 8, self.params.big1), out)
 
@@ -924,6 +997,34 @@ class ServerGroup:
         self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_ccm_decrypt(
             round_keys, messages[lo:hi], out=out[at[lo]:at[hi]], valid_out=valid[lo:hi])) for lo, hi in shards])
         return out, valid, at
+
+    def aes_cmac_subkeys(self, round_keys):
+        """derived on context 0; finished before returning, since the subkeys are then read from the other contexts' streams"""
+        sub = self.servers[0].aes_cmac_subkeys(round_keys)
+        self.servers[0].synchronize()
+        return sub
+
+    def _cmac_shards(self, entries):
+        """whole streams per context, contiguous and balanced by chain blocks"""
+        return _shards_by_cost(cmac_args(entries)["chain_blocks"], len(self.servers))
+
+    def aes_cmac_streams(self, round_keys, streams, subkeys=None):
+        """Server.aes_cmac_streams: whole streams per context, contiguous and balanced by chain blocks; a context without `subkeys` derives
+        those of its own shard's keys (the same words on every context).  EAX's OMAC^t is this CMAC over [t]_128 || M and needs nothing
+        more."""
+        streams = [tuple(st) for st in streams]
+        out = self._new_out(self._round_keys(round_keys, many=None), len(streams), 16, 8)
+        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_cmac_streams(round_keys, streams[lo:hi], subkeys=subkeys, out=out[lo:hi]))
+                          for lo, hi in self._cmac_shards(streams)])
+        return out
+
+    def aes_cmac_verify(self, round_keys, messages, subkeys=None):
+        """Server.aes_cmac_verify, sharded as aes_cmac_streams.  EAX's OMAC^t is this CMAC over [t]_128 || M and needs nothing more."""
+        messages = [tuple(m) for m in messages]
+        valid = self._new_out(self._round_keys(round_keys, many=None), len(messages))
+        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_cmac_verify(round_keys, messages[lo:hi], subkeys=subkeys, valid_out=valid[lo:hi]))
+                          for lo, hi in self._cmac_shards(messages)])
+        return valid
 
     # packed round keys: a store is small, so every context reads the whole of it (as the keyed calls read all round keys); the cipher
     # methods above take a PackedRoundKeys wherever they take round keys, since every context's Server does
