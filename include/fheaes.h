@@ -605,6 +605,52 @@ int fheaes_aes_cmac_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_round_k
  * *padded_streams streams whose last block takes K2. */
 int fheaes_aes_cmac_plan(const uint64_t *message_bytes, uint64_t n_streams, uint64_t *steps, uint64_t *chained_blocks, uint64_t *padded_streams);
 
+/* ---- AES key unwrap ----------------------------------------------------------------------- */
+/* The AES Key Unwrap of RFC 3394 / SP 800-38F (JWE's A128KW / A256KW, CMS, PKCS#11 CKM_AES_KEY_WRAP, KMIP) under encrypted
+ * key-encryption keys (KEKs): wrapped keys -- PUBLIC data, 8 (n + 1) bytes for a payload of n semiblocks of 8 bytes -- in, the encrypted
+ * payloads and an encrypted `valid` bit per key out.  The owner sends each KEK under FHE once; after that session keys come straight
+ * from the key store and go into fheaes_aes_key_expansion_batch.  With C[0..n] the wrapped semiblocks, step s = 0 .. 6n - 1 works on
+ * register i_s = n - s % n under the counter t_s = 6n - s:  B = D_KEK((A ^ t_s) | R[i_s]), A = MSB64(B), R[i_s] = LSB64(B), from
+ * A = C[0], R[i] = C[i]; the payload is R[1..n], valid iff A == A6A6A6A6A6A6A6A6.  Serial inside a key and parallel across keys: step s of
+ * ALL keys is one K6 launch (kw_link_kernel) and one windowed pass of the equivalent inverse cipher.  Levels against
+ * FHEAES_MAX_NOISE_LEVEL = 5: a cipher output is 2, a step's input enters AddRoundKey at 3, the raw payload is 2 and an identity WoPBS
+ * makes it fresh; the difference A + A6.. enters the tag check at 2.
+ *
+ * Bounds: 2..8 semiblocks (payloads of 16..64 bytes: AES keys of all three sizes, XTS key pairs, HMAC keys), one value per call; at most
+ * FHEAES_KW_MAX_KEYS keys per call (a key takes 2.1 MB of state at PARAM_OPT and 1.05 MB per semiblock twice over, registers and output:
+ * 4,096 keys of 8 semiblocks are about 77 GB beside the evaluation keys).  Refused with FHEAES_ERR_INVALID before anything is launched,
+ * the outputs untouched: a NULL argument that is not optional, semiblocks outside 2..8, n_keys > FHEAES_KW_MAX_KEYS, n_keks outside
+ * 1..FHEAES_MAX_KEYS, a KEK index >= n_keks, key_bits not 128 / 192 / 256, step > 6 semiblocks, overlapping buffers.  n_keys = 0 is
+ * FHEAES_OK and writes nothing; FHEAES_DEVICE calls only enqueue.  Out: RFC 5649 padding (KWP), wrapping, mixed payload lengths in one
+ * call, gating the payload on `valid`, payloads above 64 bytes. */
+#define FHEAES_KW_MIN_SEMIBLOCKS 2
+#define FHEAES_KW_MAX_SEMIBLOCKS 8
+#define FHEAES_KW_MAX_KEYS 4096
+/* dec_round_keys: what fheaes_aes_decryption_round_keys_batch gave for the n_keks KEKs (AES-key_bits); kek_of_key: HOST [n_keys], the KEK of
+ * every wrapped key, may be NULL when n_keks == 1; wrapped: HOST bytes [n_keys][8 (semiblocks + 1)].  keys_out [n_keys][8 semiblocks][8][kN+1]:
+ * the payloads, fresh ciphertexts in the layout fheaes_aes_key_expansion_batch takes, NOT gated on valid_out; valid_out [n_keys][kN+1]: an
+ * encryption of 1 iff the integrity constant is right.  Word for word: for s = 0 .. 6n - 1, fheaes_kw_link(s) and
+ * fheaes_aes_decrypt_equivalent_keyed on the n_keys states under kek_of_key; fheaes_kw_link(6n); fheaes_wopbs_batch with the identity LUT
+ * on the 8 n n_keys bytes of regs; step (d) of fheaes_aes_ccm_open_keyed on the state. */
+int fheaes_aes_kw_unwrap_keyed(fheaes_ctx *ctx, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t n_keks, uint64_t n_keys,
+                               const uint32_t *kek_of_key, uint32_t semiblocks, const uint8_t *wrapped, uint64_t *keys_out, uint64_t *valid_out,
+                               int memspace);
+int fheaes_aes_kw_unwrap_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_dec_round_keys, uint32_t key_bits, uint64_t n_keks, uint64_t n_keys,
+                                      const uint32_t *kek_of_key, uint32_t semiblocks, const uint8_t *wrapped, uint64_t *keys_out,
+                                      uint64_t *valid_out, int memspace);
+/* K6 alone, one link of the unwrap (needs no keys), step = 0 .. 6 semiblocks.  state [n_keys][16][8][kN+1]: A on rows 0..63, the register
+ * at work on rows 64..127; regs [n_keys][8 semiblocks][8][kN+1]: register i on bytes 8 (i-1) .. 8 i - 1.
+ *   step 0 (load):      regs = trivial(C[1..n]), state = trivial(C[0] ^ t_0) | trivial(C[n]); `wrapped` (HOST) is read here alone and may be
+ *                       NULL otherwise
+ *   0 < step < 6n:      regs[i_{step-1}] <- state rows 64..127 <- regs[i_step]; state rows 0..63 += trivial(t_step)
+ *   step 6n (unload):   regs[1] <- state rows 64..127 <- zero words; state rows 0..63 += trivial(A6 x 8)
+ * In place.  Declares to the noise guard the level of the sum plus the round key that follows: 1, 3 and 2. */
+int fheaes_kw_link(fheaes_ctx *ctx, uint64_t *state, uint64_t *regs, uint64_t n_keys, uint32_t semiblocks, uint32_t step, const uint8_t *wrapped,
+                   int memspace);
+/* What an unwrap call runs (host logic only): *steps = 6 n cipher passes, *cipher_blocks = 6 n n_keys, *byte_wopbs = 16 Nr 6 n n_keys (the
+ * cipher) + 8 n n_keys (the refresh of the payload) + 16 n_keys (the first WoPBS of the tag check). */
+int fheaes_aes_kw_plan(uint32_t key_bits, uint32_t semiblocks, uint64_t n_keys, uint64_t *steps, uint64_t *cipher_blocks, uint64_t *byte_wopbs);
+
 /* ---- measurement --------------------------------------------------------------- */
 #define FHEAES_STAGE_KEYSWITCH 0
 #define FHEAES_STAGE_BLIND_ROTATE 1

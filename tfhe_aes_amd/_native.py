@@ -17,6 +17,7 @@ from .params import CParams, WopbsParameters
 
 HOST, DEVICE = 0, 1
 MAC_NONE = 0xFFFFFFFF           # FHEAES_MAC_NONE: "no block" in a src_block table of mac_link
+KW_MIN_SEMIBLOCKS, KW_MAX_SEMIBLOCKS, KW_MAX_KEYS = 2, 8, 4096      # FHEAES_KW_*: a wrapped key's payload in 8-byte semiblocks, keys per unwrap call
 AES_WINDOW_OFF = 0xFFFFFFFF     # FHEAES_AES_WINDOW_OFF: fheaes_aes_set_window's "one launch per round"
 K2_PARK_SLOTS = 1024            # FHEAES_K2_PARK_SLOTS: owner words of the paired kernel's shared parking slots, 128 per XCC
 STAGES = ("keyswitch", "blind_rotate", "pfpks", "ggsw_fft", "vertical_packing", "linear")
@@ -125,6 +126,12 @@ SIGNATURES = {
     "fheaes_aes_cmac_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_uint64, _u32p, _u64p, _u8p, _u8p, _u32p,
                                                 _c.c_void_p, _c.c_void_p, _c.c_int]),
     "fheaes_aes_cmac_plan": (_c.c_int, [_u64p, _c.c_uint64, _u64p, _u64p, _u64p]),
+    "fheaes_aes_kw_unwrap_keyed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_uint64, _u32p, _c.c_uint32, _u8p, _c.c_void_p, _c.c_void_p,
+                                              _c.c_int]),
+    "fheaes_aes_kw_unwrap_keyed_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint32, _c.c_uint64, _c.c_uint64, _u32p, _c.c_uint32, _u8p, _c.c_void_p,
+                                                     _c.c_void_p, _c.c_int]),
+    "fheaes_kw_link": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_uint32, _u8p, _c.c_int]),
+    "fheaes_aes_kw_plan": (_c.c_int, [_c.c_uint32, _c.c_uint32, _c.c_uint64, _u64p, _u64p, _u64p]),
     "fheaes_profile_enable": (_c.c_int, [_ctx, _c.c_int]),
     "fheaes_profile_reset": (_c.c_int, [_ctx]),
     "fheaes_profile_read": (_c.c_int, [_ctx, _c.c_int, _dp, _u64p, _u64p]),
@@ -528,6 +535,32 @@ class Engine:
                        dt.ctypes.data_as(_u8p), tg.ctypes.data_as(_u8p) if tg is not None else None, tb.ctypes.data_as(_u32p) if tb is not None else None,
                        _ptr(mac_out)[0], _ptr(valid_out)[0], self._space(round_keys, subkeys, mac_out, valid_out)))
 
+    # AES key unwrap (include/fheaes.h): the wrapped keys as host bytes [n_keys][8 (n + 1)], the KEKs' decryption round keys
+    def kw_link(self, state, regs, semiblocks: int, step: int, wrapped=None):
+        """K6 alone (fheaes_kw_link): link `step` = 0 .. 6n of the unwrap on state [n_keys][16][8][kN+1] and regs [n_keys][8 n][8][kN+1], in
+        place; wrapped [n_keys][8 (n + 1)] bytes, read by step 0 alone; needs no keys"""
+        n_keys = int(state.shape[0])
+        wr = None
+        if wrapped is not None:
+            wr = wrapped_bytes(wrapped, semiblocks)
+            if len(wr) != n_keys:
+                raise ValueError("one wrapped key per state expected: %d for %d" % (len(wr), n_keys))
+        self._check(self._lib.fheaes_kw_link(self._h, _ptr(state)[0], _ptr(regs)[0], n_keys, semiblocks, step, wr.ctypes.data_as(_u8p) if wr is not None else None,
+                                             self._space(state, regs)))
+
+    def aes_kw_unwrap_keyed(self, dec_round_keys, key_bits: int, n_keks: int, kek_of_key, semiblocks: int, wrapped, keys_out, valid_out,
+                            packed: bool = False):
+        """fheaes_aes_kw_unwrap_keyed / _packed: wrapped [n_keys][8 (semiblocks + 1)] bytes, kek_of_key one KEK index per key or None (one
+        KEK); keys_out [n_keys][8 semiblocks][8][kN+1], valid_out [n_keys][kN+1]"""
+        wr = wrapped_bytes(wrapped, semiblocks)
+        n_keys = len(wr)
+        kok = key_indices(kek_of_key, n_keys) if kek_of_key is not None else None
+        if n_keys == 0:
+            wr = np.zeros((1, 8 * (semiblocks + 1)), dtype=np.uint8)              # never an empty buffer
+        fn = self._lib.fheaes_aes_kw_unwrap_keyed_packed if packed else self._lib.fheaes_aes_kw_unwrap_keyed
+        self._check(fn(self._h, _ptr(dec_round_keys)[0], key_bits, n_keks, n_keys, kok.ctypes.data_as(_u32p) if kok is not None else None, semiblocks,
+                       wr.ctypes.data_as(_u8p), _ptr(keys_out)[0], _ptr(valid_out)[0], self._space(dec_round_keys, keys_out, valid_out)))
+
     def xts_whiten(self, dst, src, tweaks, tweak_of_block, clear):
         """K6 alone (fheaes_xts_whiten): dst[b] = (src[b] or 0) + tweaks[tweak_of_block[b]] + trivial(clear[b]); src may be dst or None,
         clear [n][16] bytes or None; needs no keys"""
@@ -686,6 +719,18 @@ def key_indices(key_of_block, n_blocks: int) -> np.ndarray:
     return out
 
 
+def wrapped_bytes(wrapped, semiblocks: int) -> np.ndarray:
+    """wrapped keys -- byte strings of 8 (semiblocks + 1) bytes each, or a uint8 array of them -- as the host array [n_keys][8 (semiblocks + 1)]
+    of the C ABI"""
+    size = 8 * (semiblocks + 1)
+    if not isinstance(wrapped, np.ndarray):
+        wrapped = [bytes(w) for w in wrapped]
+        if any(len(w) != size for w in wrapped):
+            raise ValueError("a wrapped key of %d semiblocks has %d bytes" % (semiblocks, size))
+        wrapped = np.frombuffer(b"".join(wrapped), dtype=np.uint8)
+    return np.ascontiguousarray(np.asarray(wrapped, dtype=np.uint8).reshape(-1, size))
+
+
 def aes_public_plan_keyed(blocks, key_of_block, n_keys: int, key_bits: int = 128) -> list[int]:
     """aes_public_plan for aes_encrypt_public_keyed / aes_ctr_streams: the id of a round-1 input is (key, position, byte), so equal blocks
     under different keys share nothing (fheaes_aes_public_plan_keyed: host only, no GPU)"""
@@ -771,6 +816,16 @@ def aes_cmac_plan(message_bytes) -> dict:
     if rc != 0:
         raise FheAesError(rc, "fheaes_aes_cmac_plan: at most 2^20 streams of at most 16 * 2^16 bytes")
     return {"steps": steps.value, "chained_blocks": chained.value, "padded_streams": padded.value}
+
+
+def aes_kw_plan(key_bits: int, semiblocks: int, n_keys: int) -> dict:
+    """fheaes_aes_kw_plan (host only, no GPU): what unwrapping n_keys keys of `semiblocks` semiblocks under AES-key_bits KEKs runs --
+    {"steps" (cipher passes, 6 n), "cipher_blocks" (6 n n_keys), "byte_wopbs" (the cipher's, the payload's refresh, the tag check's first)}"""
+    steps, blocks, wopbs = _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
+    rc = load_library().fheaes_aes_kw_plan(key_bits, semiblocks, n_keys, _c.byref(steps), _c.byref(blocks), _c.byref(wopbs))
+    if rc != 0:
+        raise FheAesError(rc, "fheaes_aes_kw_plan: key_bits 128 / 192 / 256, %d..%d semiblocks, at most %d keys" % (KW_MIN_SEMIBLOCKS, KW_MAX_SEMIBLOCKS, KW_MAX_KEYS))
+    return {"steps": steps.value, "cipher_blocks": blocks.value, "byte_wopbs": wopbs.value}
 
 
 def round_keys_packed_glwes(key_bits: int) -> int:

@@ -325,6 +325,41 @@ def cmac_verify(key, msg: bytes, tag: bytes) -> bool:
     return 1 <= len(tag) <= 16 and cmac(key, msg, len(tag)) == tag
 
 
+KW_ICV = 0xA6A6A6A6A6A6A6A6      # RFC 3394 2.2.3.1: the default initial value, the integrity check of the unwrap
+
+
+def _kw_semiblocks(data: bytes, lo: int, what: str):
+    data = bytes(data)
+    if len(data) % 8 or not lo <= len(data) // 8 <= lo + 6:
+        raise ValueError("%s has %d..%d bytes in whole semiblocks of 8, got %d" % (what, 8 * lo, 8 * (lo + 6), len(data)))
+    return [int.from_bytes(data[i:i + 8], "big") for i in range(0, len(data), 8)]
+
+
+def key_wrap(kek, data: bytes) -> bytes:
+    """AES Key Wrap (RFC 3394 2.2.1, SP 800-38F KW) of a payload of n = 2..8 semiblocks of 8 bytes under a KEK of 16 / 24 / 32 bytes:
+    8 (n + 1) bytes.  For j = 0..5, i = 1..n: B = E_KEK(A | R[i]); A = MSB64(B) ^ (n j + i); R[i] = LSB64(B)"""
+    r = [KW_ICV] + _kw_semiblocks(data, 2, "a payload to wrap")
+    n = len(r) - 1
+    for j in range(6):
+        for i in range(1, n + 1):
+            b = aes_encrypt_block(kek, (r[0] << 64) | r[i])
+            r[0], r[i] = (b >> 64) ^ (n * j + i), b & ((1 << 64) - 1)
+    return b"".join(v.to_bytes(8, "big") for v in r)
+
+
+def key_unwrap(kek, wrapped: bytes):
+    """AES Key Unwrap (RFC 3394 2.2.2) -> (ok, data): the n = len / 8 - 1 payload semiblocks, and whether A came out as A6A6A6A6A6A6A6A6.
+    The payload is returned either way -- Server.aes_key_unwrap does not gate it on `valid` either.  For j = 5..0, i = n..1:
+    B = D_KEK((A ^ (n j + i)) | R[i]); A = MSB64(B); R[i] = LSB64(B)"""
+    r = _kw_semiblocks(wrapped, 3, "a wrapped key")
+    n = len(r) - 1
+    for j in range(5, -1, -1):
+        for i in range(n, 0, -1):
+            b = aes_decrypt_block(kek, ((r[0] ^ (n * j + i)) << 64) | r[i])
+            r[0], r[i] = b >> 64, b & ((1 << 64) - 1)
+    return r[0] == KW_ICV, b"".join(v.to_bytes(8, "big") for v in r[1:])
+
+
 def aes128_encrypt_block(key: int, block: int) -> int:
     return aes_encrypt_block(key, block)
 

@@ -700,3 +700,32 @@ static int cmac_dev(fheaes_ctx *c, const KeySets &rk, int nr, uint64_t n_keys, c
     TRY(launch_mac_link(c, diff, state, nullptr, recs + cc.tag0, n, 2, "the CMAC tag difference (T + tag)"));
     return tag_check_dev(c, diff, n, valid_out);
 }
+
+// ---- AES key unwrap over many keys (RFC 3394, SP 800-38F) ----------------------------------------------------------------------------------
+// Wrapped keys are public data; the key-encryption keys (KEKs) are encrypted.  6n block decryptions per key, serial inside a key and
+// parallel across keys -- the shape of the chains above, with every chain of the same length, so nothing is sorted or compacted: step s of
+// ALL keys is one kw_link_kernel launch and one windowed pass of the equivalent inverse cipher, key j under KEK kek_of[j]
+// (KeySets.of_block).  Levels against the guard's 5: a cipher output is 2, a step's input goes into AddRoundKey at 2 + 1 = 3; the raw key
+// out of the last step is 2, and an identity WoPBS (the one XTS and CMAC use) makes it fresh, a valid argument of the key expansion, where
+// the raw key words become round key 0 and count as 1; the tag difference goes into the first tag WoPBS at 2.
+
+// wrapped: the device table [n_keys][8 (n + 1)]; dw: the KEKs' decryption round keys, of_block set where there is more than one.
+// ws_tmp_a: the register file, ws_tmp_b: the state, ws_vp: the cipher's and the tag check's outputs -- all had before the first launch.
+// keys_out [n_keys][8 n][8][kN+1], NOT gated on valid_out [n_keys][kN+1].
+static int kw_unwrap_dev(fheaes_ctx *c, const KeySets &dw, int nr, const uint8_t *wrapped, uint32_t n, uint64_t n_keys, uint64_t *keys_out, uint64_t *valid_out)
+{
+    const uint64_t bw = 8ull * c->big1, sw = 16 * bw;
+    const AesSchedule sch = aes_decrypt_eq_schedule(nr);
+    const uint64_t w = aes_context_window(c, n_keys, sch.steps.size());
+    TRY(ensure(c, c->ws_tmp_a, n_keys * 8 * n * bw * 8));
+    TRY(ensure(c, c->ws_tmp_b, n_keys * sw * 8));
+    TRY(ensure(c, c->ws_vp, std::max<uint64_t>((w ? w : n_keys) * 16 * sch.max_luts * bw * 8, n_keys * sw * 8)));
+    uint64_t *regs = (uint64_t *)c->ws_tmp_a.p, *state = (uint64_t *)c->ws_tmp_b.p;
+    for (uint32_t s = 0; s < 6 * n; ++s) {
+        TRY(launch_kw_link(c, state, regs, wrapped, n_keys, n, s));
+        TRY(aes_run_dev(c, dw, state, n_keys, sch));
+    }
+    TRY(launch_kw_link(c, state, regs, wrapped, n_keys, n, 6 * n));
+    TRY(many_sbox_dev(c, regs, 8ull * n * n_keys, LUTSET_IDENTITY, keys_out));
+    return tag_check_dev(c, state, n_keys, valid_out);
+}

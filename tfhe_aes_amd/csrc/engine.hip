@@ -1542,6 +1542,96 @@ int fheaes_aes_cmac_plan(const uint64_t *message_bytes, uint64_t n_streams, uint
     return FHEAES_OK;
 }
 
+// ---- AES key unwrap ---------------------------------------------------------------------------
+static_assert(KW_MIN_SEMIBLOCKS == FHEAES_KW_MIN_SEMIBLOCKS && KW_MAX_SEMIBLOCKS == FHEAES_KW_MAX_SEMIBLOCKS, "fheaes.h's bounds on a wrapped key are the kernel's");
+
+static int check_kw_shape(fheaes_ctx *c, uint32_t semiblocks, uint64_t n_keys)
+{
+    if (semiblocks < KW_MIN_SEMIBLOCKS || semiblocks > KW_MAX_SEMIBLOCKS)
+        return c->fail(FHEAES_ERR_INVALID, "semiblocks must be in %u..%u (got %u)", KW_MIN_SEMIBLOCKS, KW_MAX_SEMIBLOCKS, semiblocks);
+    if (n_keys > FHEAES_KW_MAX_KEYS) return c->fail(FHEAES_ERR_INVALID, "a call unwraps at most %u keys (got %llu)", (unsigned)FHEAES_KW_MAX_KEYS, (unsigned long long)n_keys);
+    return FHEAES_OK;
+}
+
+// K6 alone: one link of the unwrap on caller buffers (the kernel's test and measurement entry)
+int fheaes_kw_link(fheaes_ctx *c, uint64_t *state, uint64_t *regs, uint64_t n_keys, uint32_t semiblocks, uint32_t step, const uint8_t *wrapped, int memspace)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    TRY(check_kw_shape(c, semiblocks, n_keys));
+    if (step > 6 * semiblocks) return c->fail(FHEAES_ERR_INVALID, "step must be in 0..%u for %u semiblocks (got %u)", 6 * semiblocks, semiblocks, step);
+    if (!state || !regs || (step == 0 && !wrapped)) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    if (n_keys == 0) return FHEAES_OK;
+    const uint64_t bw = 8ull * c->big1, state_bytes = n_keys * 16 * bw * 8, regs_bytes = n_keys * 8 * semiblocks * bw * 8;
+    if (overlap(state, state_bytes, regs, regs_bytes)) return c->fail(FHEAES_ERR_INVALID, "state and regs overlap");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged st(c, memspace);
+    if (step == 0) {                                                         // the load writes every word of both
+        TRY(st.out(state, state_bytes, &state));
+        TRY(st.out(regs, regs_bytes, &regs));
+        const size_t bytes = n_keys * 8 * (semiblocks + 1);
+        TRY(upload_pinned(c, bytes, bytes, [&](uint8_t *pin) { memcpy(pin, wrapped, bytes); }));
+    } else {
+        TRY(st.inout(state, state_bytes, &state));
+        TRY(st.inout(regs, regs_bytes, &regs));
+    }
+    TRY(launch_kw_link(c, state, regs, step == 0 ? (const uint8_t *)c->ws_misc.p : nullptr, n_keys, semiblocks, step));
+    return st.finish();
+}
+
+// k: the KEKs' decryption round keys; k.key_of: the KEK of every wrapped key (null: the one KEK), k.n_of of them
+static int aes_kw_unwrap(fheaes_ctx *c, RoundKeys k, uint32_t semiblocks, const uint8_t *wrapped, uint64_t *keys_out, uint64_t *valid_out, int memspace)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    TRY(check_keys(c));
+    const uint64_t n_keys = k.n_of;
+    if (!k.words || !wrapped || !keys_out || !valid_out || (!k.key_of && k.n_keys != 1)) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    TRY(check_kw_shape(c, semiblocks, n_keys));
+    TRY(resolve_keys(c, k));
+    if (n_keys == 0) return FHEAES_OK;
+    const uint64_t bw = 8ull * c->big1, out_bytes = n_keys * 8 * semiblocks * bw * 8, valid_bytes = n_keys * c->big1 * 8ull;
+    if (k.overlaps(keys_out, out_bytes) || k.overlaps(valid_out, valid_bytes) || overlap(keys_out, out_bytes, valid_out, valid_bytes))
+        return c->fail(FHEAES_ERR_INVALID, "keys_out, valid_out and the round keys overlap");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged st(c, memspace);
+    TRY(k.stage(st));
+    TRY(st.out(keys_out, out_bytes, &keys_out));
+    TRY(st.out(valid_out, valid_bytes, &valid_out));
+    // one upload: the KEK of every key (more than one KEK only), then the wrapped bytes
+    const bool table = k.n_keys > 1;
+    const size_t tab_bytes = table ? (n_keys * sizeof(uint32_t) + 31) / 32 * 32 : 0, data_bytes = n_keys * 8 * (semiblocks + 1);
+    TRY(upload_pinned(c, tab_bytes + data_bytes, tab_bytes + data_bytes, [&](uint8_t *pin) {
+        if (table) memcpy(pin, k.key_of, n_keys * sizeof(uint32_t));
+        memcpy(pin + tab_bytes, wrapped, data_bytes);
+    }));
+    const uint8_t *misc = (const uint8_t *)c->ws_misc.p;
+    TRY(kw_unwrap_dev(c, k.sets(table ? (const uint32_t *)misc : nullptr), k.nr, misc + tab_bytes, semiblocks, n_keys, keys_out, valid_out));
+    return st.finish();
+}
+
+int fheaes_aes_kw_unwrap_keyed(fheaes_ctx *c, const uint64_t *dec_round_keys, uint32_t key_bits, uint64_t n_keks, uint64_t n_keys, const uint32_t *kek_of_key,
+                               uint32_t semiblocks, const uint8_t *wrapped, uint64_t *keys_out, uint64_t *valid_out, int memspace)
+{
+    return aes_kw_unwrap(c, {dec_round_keys, key_bits, n_keks, kek_of_key, n_keys, false}, semiblocks, wrapped, keys_out, valid_out, memspace);
+}
+
+int fheaes_aes_kw_unwrap_keyed_packed(fheaes_ctx *c, const uint64_t *packed_dec_round_keys, uint32_t key_bits, uint64_t n_keks, uint64_t n_keys,
+                                      const uint32_t *kek_of_key, uint32_t semiblocks, const uint8_t *wrapped, uint64_t *keys_out, uint64_t *valid_out, int memspace)
+{
+    return aes_kw_unwrap(c, {packed_dec_round_keys, key_bits, n_keks, kek_of_key, n_keys, true}, semiblocks, wrapped, keys_out, valid_out, memspace);
+}
+
+int fheaes_aes_kw_plan(uint32_t key_bits, uint32_t semiblocks, uint64_t n_keys, uint64_t *steps, uint64_t *cipher_blocks, uint64_t *byte_wopbs)
+{
+    const uint64_t nr = (uint64_t)aes_rounds(key_bits), n = semiblocks;
+    if (!nr || n < KW_MIN_SEMIBLOCKS || n > KW_MAX_SEMIBLOCKS || n_keys > FHEAES_KW_MAX_KEYS || !steps || !cipher_blocks || !byte_wopbs) return FHEAES_ERR_INVALID;
+    *steps = 6 * n;
+    *cipher_blocks = 6 * n * n_keys;
+    *byte_wopbs = 16 * nr * 6 * n * n_keys + 8 * n * n_keys + 16 * n_keys;
+    return FHEAES_OK;
+}
+
 // ---- packing ----------------------------------------------------------------------------------
 size_t fheaes_packed_words(const fheaes_ctx *c, uint64_t m)
 {

@@ -480,6 +480,24 @@ int launch_mac_link(fheaes_ctx *c, uint64_t *dst, const uint64_t *a, const uint6
     return FHEAES_OK;
 }
 
+// kw_link_kernel: link `step` = 0 .. 6n of n_keys keys of n semiblocks; `wrapped` (a device table) is read by the load alone.  What it
+// declares is the level of the sum plus the round key that aes_run_dev adds next: the load leaves trivial ciphertexts (0 + 1), a shuffle
+// a cipher output (2 + 1), the unload the tag difference and the raw key, cipher outputs both (2).  Units: keys.
+int launch_kw_link(fheaes_ctx *c, uint64_t *state, uint64_t *regs, const uint8_t *wrapped, uint64_t n_keys, uint32_t n, uint32_t step)
+{
+    if (n_keys == 0) return FHEAES_OK;
+    const bool load = step == 0, unload = step == 6 * n;
+    TRY(noise_guard(c, load ? 1 : unload ? 2 : 3, load ? "the key-unwrap load (public semiblocks + the round key that follows)"
+                                                  : unload ? "the key-unwrap unload (A + the integrity constant, the raw key)"
+                                                           : "a key-unwrap link (cipher output + counter + the round key that follows)"));
+    StageScope sc(c, FHEAES_STAGE_LINEAR, n_keys);
+    const unsigned gx = (unsigned)std::min<uint64_t>((128ull * c->big1 + 255) / 256, 64);
+    dim3 grid(gx, (unsigned)std::min<uint64_t>(n_keys, std::max<uint64_t>(1, 16384 / gx)));
+    hipLaunchKernelGGL(kw_link_kernel, grid, dim3(256), 0, c->stream, state, regs, wrapped, n_keys, n, step, c->big1);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
 // cmac_subkey_kernel: K1 and K2 of n_keys keys from their L.  It declares the largest row weight, 3 (K2's: kern_linear.h).  Units: keys.
 int launch_cmac_double(fheaes_ctx *c, const uint64_t *l, uint64_t n_keys, uint64_t *out)
 {

@@ -7,7 +7,8 @@
 //   add_round_key             src/server/server.rs:278-282
 //   (no counterpart)          the XTS tweak layer: multiplication by alpha^j in GF(2^128), xts_tweak_kernel below
 //   (no counterpart)          the CMAC subkeys: multiplication by x and x^2 in the big-endian byte order, cmac_subkey_kernel below
-// All of them are one "gather-add": out[blk][byte] = sum_t src[blk][tab.src[byte][t]][tab.lut[byte][t]] (+ rk[byte]).
+//   (no counterpart)          the key-unwrap link (RFC 3394): half blocks moved between a state and a register file, kw_link_kernel below
+// All of them but the last are one "gather-add": out[blk][byte] = sum_t src[blk][tab.src[byte][t]][tab.lut[byte][t]] (+ rk[byte]).
 // The round key comes from a source type (LweKeys, PackedKeys below): every layer that adds one is ONE kernel template over that type,
 // so round keys in LWE form and in a packed store go through the same body.
 #pragma once
@@ -247,6 +248,56 @@ __global__ __launch_bounds__(256) void mac_link_kernel(uint64_t *dst, const uint
                 v = add_trivial_bit(v, sl->clear[p], i - p * byte_words, lwe_words);
             }
             db[i] = v;
+        }
+    }
+}
+
+// ---- AES key unwrap (RFC 3394, SP 800-38F): the link between two steps ------------------------------------------------------------------
+// Unwrapping C[0..n] (n + 1 semiblocks of 8 bytes, 2 <= n <= 8) is 6n block decryptions chained through 64-bit halves.  Step
+// s = 0 .. 6n - 1 works on register i_s = n - s % n under the counter t_s = 6n - s (the RFC's t = n j + i, j = 5 .. 0, i = n .. 1):
+//   B = D_KEK((A ^ t_s) | R[i_s]);  A = MSB64(B);  R[i_s] = LSB64(B)
+// from A = C[0], R[i] = C[i]; the key is R[1..n], valid iff A == A6A6A6A6A6A6A6A6.  t_s is a big-endian 64-bit integer, so it lands in
+// block byte 7 (6n <= 48).
+#define KW_MIN_SEMIBLOCKS 2u
+#define KW_MAX_SEMIBLOCKS 8u
+__host__ __device__ __forceinline__ uint32_t kw_register(uint32_t n, uint32_t s) { return n - s % n; }      // i_s, 1 .. n
+__host__ __device__ __forceinline__ uint32_t kw_counter(uint32_t n, uint32_t s) { return 6 * n - s; }       // t_s, 6n .. 1
+
+// Link s = 0 .. 6n of every key.  state: [n_keys][16][8][lwe_words], A on rows 0..63 and the register at work on rows 64..127; regs:
+// [n_keys][8 n][8][lwe_words], register i on bytes 8 (i-1) .. 8 i - 1, so that after the last link regs IS the unwrapped key in the layout
+// of the key expansion.  wrapped: [n_keys][8 (n + 1)] bytes, read by the load alone.  With half = 64 lwe_words words:
+//   s = 0, load:        regs = trivial(C[1..n]); state rows 0..63 = trivial(C[0] ^ t_0), rows 64..127 = trivial(C[n])
+//   0 < s < 6n, shuffle: regs[i_{s-1}] <- state rows 64..127 <- regs[i_s]; state rows 0..63 += trivial(t_s)
+//   s = 6n, unload:     regs[1] <- state rows 64..127 <- zero words; state rows 0..63 += trivial(A6 x 8): the state is then the `diff` of
+//                       the tag check, zero on its first 64 rows iff the key is valid and zero words beyond
+// i_{s-1} != i_s since n >= 2, and every lane reads the words it overwrites before it writes them: the link runs in place.  The trivial
+// terms are bit << 63 on body words (add_trivial_bit).  Lanes on consecutive words, 8-byte accesses (rows of kN + 1 words are 8-byte aligned
+// and no more); one launch whatever n_keys is, the keys beyond the grid's y taken by the loop.  All offsets in 64 bits.
+__global__ __launch_bounds__(256) void kw_link_kernel(uint64_t *state, uint64_t *regs, const uint8_t *wrapped, uint64_t n_keys, uint32_t n, uint32_t s,
+                                                      uint32_t lwe_words)
+{
+    const uint32_t byte_words = 8 * lwe_words, half = 8 * byte_words, steps = 6 * n;
+    const bool load = s == 0, unload = s == steps;
+    const uint32_t t = unload ? 0u : kw_counter(n, s);
+    const uint32_t r_in = unload ? 0u : kw_register(n, s) - 1, r_out = load ? 0u : kw_register(n, s - 1) - 1;   // registers from 0
+    for (uint64_t key = blockIdx.y; key < n_keys; key += gridDim.y) {
+        uint64_t *sb = state + key * 2 * half, *rb = regs + key * (uint64_t)n * half;
+        const uint8_t *c = load ? wrapped + key * 8 * (n + 1) : nullptr;
+        const uint32_t words = load ? (n + 2) * half : 2 * half;                // the load also fills every register
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < words; i += gridDim.x * blockDim.x) {
+            const uint32_t p = i / byte_words, w = i - p * byte_words;          // byte p of [A | the register at work | regs]
+            if (i < half) {
+                const uint32_t clear = (unload ? 0xA6u : p == 7 ? t : 0u) ^ (load ? c[p] : 0u);
+                sb[i] = add_trivial_bit(load ? 0 : sb[i], clear, w, lwe_words);
+            } else if (load) {
+                if (i < 2 * half) sb[i] = add_trivial_bit(0, c[8 * n + (p - 8)], w, lwe_words);
+                else rb[i - 2 * half] = add_trivial_bit(0, c[8 + (p - 16)], w, lwe_words);
+            } else {
+                const uint32_t j = i - half;
+                const uint64_t back = sb[i], next = unload ? 0 : rb[(uint64_t)r_in * half + j];
+                rb[(uint64_t)r_out * half + j] = back;
+                sb[i] = next;
+            }
         }
     }
 }

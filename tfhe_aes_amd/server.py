@@ -225,6 +225,28 @@ def cmac_args(messages):
     return a
 
 
+def kw_args(wrapped, kek_of_key=None, n_keks: int = 1):
+    """aes_key_unwrap's wrapped keys (byte strings of ONE length, 8 (n + 1) bytes for n = 2..8 semiblocks: RFC 3394) and the KEK index of
+    every key -> the arrays of the C call.  A dict: semiblocks (n; 2 for an empty list), wrapped (uint8 [n_keys][8 (n + 1)]) and kek_of_key
+    (a list of n_keys indices below n_keks, or None where there is one KEK and no list was given)"""
+    wrapped = [bytes(w) for w in wrapped]
+    sizes = {len(w) for w in wrapped}
+    if len(sizes) > 1:
+        raise ValueError("one call unwraps keys of one length, got lengths %s" % sorted(sizes))
+    size = sizes.pop() if sizes else 8 * (_native.KW_MIN_SEMIBLOCKS + 1)
+    n = size // 8 - 1
+    if size % 8 or not _native.KW_MIN_SEMIBLOCKS <= n <= _native.KW_MAX_SEMIBLOCKS:
+        raise ValueError("a wrapped key has 8 (n + 1) bytes for n = %d..%d semiblocks, got %d bytes" % (_native.KW_MIN_SEMIBLOCKS, _native.KW_MAX_SEMIBLOCKS, size))
+    if kek_of_key is None:
+        if n_keks != 1:
+            raise ValueError("kek_of_key says which of the %d KEKs wraps every key" % n_keks)
+    else:
+        kek_of_key = [int(k) for k in kek_of_key]
+        if len(kek_of_key) != len(wrapped) or any(not 0 <= k < n_keks for k in kek_of_key):
+            raise ValueError("kek_of_key holds one index below %d per wrapped key" % n_keks)
+    return {"semiblocks": n, "wrapped": np.frombuffer(b"".join(wrapped), dtype=np.uint8).reshape(len(wrapped), size), "kek_of_key": kek_of_key}
+
+
 def _shards_by_cost(costs, g: int):
     """whole streams to g contexts, contiguous and balanced by cost: a stream goes to the context in whose g-th of the total cost its
     midpoint lies; shard i is [lo, hi), possibly empty"""
@@ -664,6 +686,51 @@ class Server:
         self._cmac(round_keys, a, subkeys, None, valid_out)
         return valid_out
 
+    # ---- AES key unwrap: wrapped AES keys in, encrypted keys out ---------------------------------
+    def aes_key_unwrap(self, kek_dec_round_keys, wrapped, kek_of_key=None, out=None, valid_out=None):
+        """The AES Key Unwrap of RFC 3394 / SP 800-38F under encrypted key-encryption keys: `wrapped` is a list of byte strings of one
+        length, 8 (n + 1) bytes for a payload of n = 2..8 semiblocks -- public data, straight from a key store.  Returns (keys, valid):
+        keys [n_keys][8 n][8][kN+1] (or `out`), the payloads as fresh ciphertexts -- for n = 2, 3, 4 an argument of aes_key_expansion_many
+        -- NOT gated on valid; valid [n_keys][kN+1] (or `valid_out`), valid[i] decrypting (Client.decrypt_bits) to 1 iff key i's
+        integrity constant is right.  kek_dec_round_keys: aes_decryption_round_keys(_many) of one KEK or of many, or a PackedRoundKeys of
+        them; kek_of_key: the KEK of every wrapped key, optional with one KEK.  6 n passes of the equivalent inverse cipher over all keys
+        (include/fheaes.h: fheaes_aes_kw_unwrap_keyed), one C call per FHEAES_KW_MAX_KEYS keys."""
+        k = self._round_keys(kek_dec_round_keys, "KEK decryption round keys", many=None)
+        a = kw_args(wrapped, kek_of_key, k.n_keys)
+        n, n_keys, cap = a["semiblocks"], len(a["wrapped"]), _native.KW_MAX_KEYS
+        out = self._many_out(k.words, (n_keys, 8 * n, 8, self.params.big1), out)
+        valid_out = self._many_out(k.words, (n_keys, self.params.big1), valid_out)
+        for lo in range(0, n_keys, cap):
+            kok = a["kek_of_key"][lo:lo + cap] if a["kek_of_key"] is not None else None
+            self.engine.aes_kw_unwrap_keyed(k.words, k.key_bits, k.n_keys, kok, n, a["wrapped"][lo:lo + cap], out[lo:lo + cap], valid_out[lo:lo + cap],
+                                            packed=k.packed)
+        return out, valid_out
+
+    def aes_key_unwrap_packed(self, kek_dec_round_keys, wrapped, kek_of_key=None, chunk: int = 256):
+        """aes_key_unwrap followed by aes_key_expansion_packed, `chunk` keys at a time, for payloads of 16, 24 and 32 bytes (AES keys):
+        returns (a PackedRoundKeys of the unwrapped keys, valid [n_keys][kN+1]), both in the caller's order.  Neither the unwrapped keys
+        nor their round keys in LWE form exist for more than `chunk` keys at once."""
+        k = self._round_keys(kek_dec_round_keys, "KEK decryption round keys", many=None)
+        a = kw_args(wrapped, kek_of_key, k.n_keys)
+        n_keys, bits, chunk = len(a["wrapped"]), 64 * a["semiblocks"], int(chunk)
+        if bits not in ROUND_KEYS_TO_BITS.values() or n_keys < 1:
+            raise ValueError("at least one wrapped AES key (a payload of 16, 24 or 32 bytes) expected")
+        if chunk < 1:
+            raise ValueError("chunk must be at least one key")
+        p = self.params
+        data = _empty_like(k.words, (n_keys, packed_key_glwes(p, bits), (p.k + 1) * p.N))
+        valid = _empty_like(k.words, (n_keys, p.big1))
+        for lo in range(0, n_keys, chunk):
+            kok = a["kek_of_key"][lo:lo + chunk] if a["kek_of_key"] is not None else None
+            keys, _ = self.aes_key_unwrap(kek_dec_round_keys, [bytes(w) for w in a["wrapped"][lo:lo + chunk]], kok, valid_out=valid[lo:lo + chunk])
+            data[lo:lo + chunk] = self.aes_key_expansion_packed(keys, chunk).data
+            if not isinstance(data, np.ndarray):
+                import torch
+
+                torch.cuda.current_stream(data.device).synchronize()     # the copy ran on torch's stream; the engine reads `data` on its own
+            del keys
+        return PackedRoundKeys(p, bits, data), valid
+
     def _public_out(self, round_keys, n_blocks: int, out):
         return self._many_out(round_keys, (n_blocks, 16, 8, self.params.big1), out)
 
@@ -1025,6 +1092,50 @@ class ServerGroup:
         self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_cmac_verify(round_keys, messages[lo:hi], subkeys=subkeys, valid_out=valid[lo:hi]))
                           for lo, hi in self._cmac_shards(messages)])
         return valid
+
+    def _kw_shards(self, n_keys: int):
+        """whole wrapped keys per context, contiguous: every chain has the same length"""
+        from .dist import shard_blocks
+
+        return [shard_blocks(n_keys, len(self.servers), i) for i in range(len(self.servers))]
+
+    def aes_key_unwrap(self, kek_dec_round_keys, wrapped, kek_of_key=None):
+        """Server.aes_key_unwrap: whole keys per context, contiguous; every context reads all KEKs.  Returns (keys, valid)."""
+        k = self._round_keys(kek_dec_round_keys, "KEK decryption round keys", many=None)
+        a = kw_args(wrapped, kek_of_key, k.n_keys)
+        wrapped, kok = [bytes(w) for w in a["wrapped"]], a["kek_of_key"]
+        keys, valid = self._new_out(k, len(wrapped), 8 * a["semiblocks"], 8), self._new_out(k, len(wrapped))
+        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_key_unwrap(kek_dec_round_keys, wrapped[lo:hi], None if kok is None else kok[lo:hi],
+                                                                                          out=keys[lo:hi], valid_out=valid[lo:hi]))
+                          for lo, hi in self._kw_shards(len(wrapped))])
+        return keys, valid
+
+    def aes_key_unwrap_packed(self, kek_dec_round_keys, wrapped, kek_of_key=None, chunk: int = 256):
+        """Server.aes_key_unwrap_packed with whole keys per context: every context unwraps, expands and packs its shard `chunk` keys at a
+        time; the store and `valid` are put together in the caller's order.  Returns (PackedRoundKeys, valid)."""
+        k = self._round_keys(kek_dec_round_keys, "KEK decryption round keys", many=None)
+        a = kw_args(wrapped, kek_of_key, k.n_keys)
+        wrapped, kok = [bytes(w) for w in a["wrapped"]], a["kek_of_key"]
+        parts = [None] * len(self.servers)
+
+        def job(i, lo, hi):
+            def run(s):
+                parts[i] = s.aes_key_unwrap_packed(kek_dec_round_keys, wrapped[lo:hi], None if kok is None else kok[lo:hi], chunk)
+            return run
+
+        shards = self._kw_shards(len(wrapped))
+        if not wrapped:
+            raise ValueError("at least one wrapped AES key (a payload of 16, 24 or 32 bytes) expected")
+        self._run_shards([None if hi <= lo else job(i, lo, hi) for i, (lo, hi) in enumerate(shards)])
+        parts = [x for x in parts if x is not None]
+        if isinstance(k.words, np.ndarray):
+            data, valid = np.concatenate([x[0].data for x in parts]), np.concatenate([x[1] for x in parts])
+        else:
+            import torch
+
+            data, valid = torch.cat([x[0].data for x in parts]), torch.cat([x[1] for x in parts])
+            torch.cuda.current_stream(data.device).synchronize()
+        return PackedRoundKeys(self.params, parts[0][0].key_bits, data), valid
 
     # packed round keys: a store is small, so every context reads the whole of it (as the keyed calls read all round keys); the cipher
     # methods above take a PackedRoundKeys wherever they take round keys, since every context's Server does
