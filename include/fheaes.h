@@ -528,7 +528,7 @@ int fheaes_aes_cbc_mac_keyed_packed(fheaes_ctx *ctx, const uint64_t *packed_roun
  *   (d) one 8-bit WoPBS per byte of diff (LUT: byte != 0), then one 16-bit WoPBS per stream over those 16 bits (LUT: 1 on input 0).
  * plaintext_out [sum of ceil(payload_bytes / 16)][16][8][kN+1], stream after stream, rows beyond a payload's length zero words (may be
  * NULL when no stream has a payload); valid_out [n_streams][kN+1], row 0 of (d): an encryption of 1 iff the tag is right.  The plaintext is
- * NOT gated on valid_out: a caller that releases it does so after reading the bit. */
+ * NOT gated on valid_out: a caller that releases it does so after reading the bit, or gates it first (fheaes_gate_bits). */
 int fheaes_aes_ccm_open_keyed(fheaes_ctx *ctx, const uint64_t *round_keys, uint32_t key_bits, uint64_t n_keys, uint64_t n_streams,
                               const uint32_t *key_of_stream, const uint32_t *head_blocks, const uint64_t *head_hi_lo, const uint64_t *ctr0_hi_lo,
                               const uint64_t *payload_bytes, const uint8_t *ciphertext, const uint8_t *tags, const uint32_t *tag_bytes,
@@ -622,7 +622,7 @@ int fheaes_aes_cmac_plan(const uint64_t *message_bytes, uint64_t n_streams, uint
  * the outputs untouched: a NULL argument that is not optional, semiblocks outside 2..8, n_keys > FHEAES_KW_MAX_KEYS, n_keks outside
  * 1..FHEAES_MAX_KEYS, a KEK index >= n_keks, key_bits not 128 / 192 / 256, step > 6 semiblocks, overlapping buffers.  n_keys = 0 is
  * FHEAES_OK and writes nothing; FHEAES_DEVICE calls only enqueue.  Out: RFC 5649 padding (KWP), wrapping, mixed payload lengths in one
- * call, gating the payload on `valid`, payloads above 64 bytes. */
+ * call, payloads above 64 bytes.  Gating the payload on `valid`: fheaes_gate_bits below. */
 #define FHEAES_KW_MIN_SEMIBLOCKS 2
 #define FHEAES_KW_MAX_SEMIBLOCKS 8
 #define FHEAES_KW_MAX_KEYS 4096
@@ -651,6 +651,49 @@ int fheaes_kw_link(fheaes_ctx *ctx, uint64_t *state, uint64_t *regs, uint64_t n_
  * cipher) + 8 n n_keys (the refresh of the payload) + 16 n_keys (the first WoPBS of the tag check). */
 int fheaes_aes_kw_plan(uint32_t key_bits, uint32_t semiblocks, uint64_t n_keys, uint64_t *steps, uint64_t *cipher_blocks, uint64_t *byte_wopbs);
 
+/* ---- the gate: ciphertexts times an encrypted bit ----------------------------------------- */
+/* SP 800-38C and RFC 3394 forbid releasing a plaintext or a key whose check failed, and a server under FHE cannot branch on `valid`: it
+ * multiplies the result by `valid` under encryption.  The gate is one single-level external product with a zero "else" branch,
+ * out = GGSW(g) (x) in, in the circuit bootstrap's gadget (base 2^15, one level): one circuit bootstrap (K1, K2, K3, K4) per GATE and one
+ * external product per ciphertext (gate_kernel, kern_gate.h), where the composition of older calls -- a 9-bit WoPBS per byte with the bit
+ * as ninth input -- costs nine circuit bootstraps per BYTE.  Two forms: LWE ciphertexts [m][kN+1], each embedded on load into the GLWE
+ * whose coefficient 0 it is and extracted again on store, and packed GLWEs [G][(k+1)N] of fheaes_pack_bits, 512 bits per product.
+ *
+ * Runs: bits_of_gate (HOST, n_gates entries) says how many CONSECUTIVE ciphertexts (GLWE form: GLWEs) each gate multiplies; a gate of 0
+ * is allowed; the runs must add up to m.  In place (out == in) is allowed: every ciphertext is read before it is written, by the one
+ * workgroup that owns it.  Refused with FHEAES_ERR_INVALID before anything is launched, the outputs untouched: a NULL context or a NULL
+ * argument of a call with m > 0, runs that do not add up to m, a form other than 0 / 1, n_gates >= 2^32, `out` overlapping `in` without
+ * being `in`, `out` overlapping the gates or GGSWs.  m = 0 is FHEAES_OK and writes nothing; FHEAES_DEVICE calls only enqueue.
+ * FHEAES_ERR_NOKEYS: the two calls that bootstrap, without evaluation keys.  Kernel time is accounted under
+ * FHEAES_STAGE_VERTICAL_PACKING (units: bits, or GLWEs x N for the GLWE form).
+ *
+ * Noise: words carry no level between calls and the noise guard counts linear layers only, so fheaes_noise_level_seen is unaffected.
+ * The rule for a caller's own count: a gated ciphertext KEEPS THE LEVEL OF ITS INPUT.  What a gate adds is derived in tests/gate_model.py
+ * and measured in tests/test_gpu_gate.py: the rounding of the input to 15 bits (zero under a gate of 0) plus
+ * (k+1) N digits times a GGSW row, no more than one of the eight or more CMUX iterations every WoPBS output already carries.
+ * Out: a select between two arrays, gating on the negation of a bit, modulus-switched packed input (gate before
+ * fheaes_packed_mod_switch), keeping a gate's GGSW from call to call. */
+#define FHEAES_GATE_LWE 0
+#define FHEAES_GATE_GLWE 1
+/* The kernel alone, on caller-made Fourier GGSWs [n_gates][1][k+1][k+1][256][2] -- the layout fheaes_vertical_packing_batch takes, e.g.
+ * the four stage calls on the bits.  Needs no keys.  form FHEAES_GATE_LWE: in / out [m][kN+1]; FHEAES_GATE_GLWE: [m][(k+1)N].  A caller
+ * who gates several arrays on the same bits bootstraps them once and calls this for each. */
+int fheaes_gate_ggsw(fheaes_ctx *ctx, const double *ggsw_fourier, uint64_t n_gates, const uint64_t *bits_of_gate, const uint64_t *in, uint64_t m,
+                     int form, uint64_t *out, int memspace);
+/* gates_lwe [n_gates][kN+1]: encryptions of 0 / 1 at the bit encoding (a `valid_out`).  Word for word: fheaes_keyswitch_batch,
+ * fheaes_cbs_pbs_batch at level 1, fheaes_pfpks_batch and fheaes_forward_fourier_batch on the gates, then fheaes_gate_ggsw -- the front
+ * half of a WoPBS, in its workspaces, the gates cut into chunks of 32,768 by its rule (a chunk's runs are gated before the next chunk's
+ * GGSWs replace it). */
+int fheaes_gate_bits(fheaes_ctx *ctx, const uint64_t *gates_lwe, uint64_t n_gates, const uint64_t *bits_of_gate, const uint64_t *lwe_in, uint64_t m,
+                     uint64_t *lwe_out, int memspace);
+/* The same on packed GLWEs: glwes_of_gate counts GLWEs, glwe_in / glwe_out [n_glwe][(k+1)N]. */
+int fheaes_gate_packed(fheaes_ctx *ctx, const uint64_t *gates_lwe, uint64_t n_gates, const uint64_t *glwes_of_gate, const uint64_t *glwe_in,
+                       uint64_t n_glwe, uint64_t *glwe_out, int memspace);
+/* The grid a gate call launches (host logic only): *instances_per_workgroup = R, the largest R with R (k+1) <= 16 lane groups that the
+ * kernels are built for (3 at k = 4, 8 at k = 1); *workgroups = the sum over the gates of ceil(run / R) -- workgroups never mix gates.
+ * k other than 4 or 1, or a NULL argument: FHEAES_ERR_INVALID. */
+int fheaes_gate_plan(const uint64_t *bits_of_gate, uint64_t n_gates, uint32_t k, uint64_t *workgroups, uint32_t *instances_per_workgroup);
+
 /* ---- measurement --------------------------------------------------------------- */
 #define FHEAES_STAGE_KEYSWITCH 0
 #define FHEAES_STAGE_BLIND_ROTATE 1
@@ -660,7 +703,8 @@ int fheaes_aes_kw_plan(uint32_t key_bits, uint32_t semiblocks, uint64_t n_keys, 
 #define FHEAES_STAGE_LINEAR 5
 #define FHEAES_STAGE_COUNT 6
 /* When enabled every kernel launch is bracketed by HIP events on the launch stream.  fheaes_pack_bits accounts its matrix product under
- * FHEAES_STAGE_PFPKS and its fold under FHEAES_STAGE_LINEAR, fheaes_unpack_bits its extraction under FHEAES_STAGE_LINEAR (units: bits). */
+ * FHEAES_STAGE_PFPKS and its fold under FHEAES_STAGE_LINEAR, fheaes_unpack_bits its extraction under FHEAES_STAGE_LINEAR (units: bits);
+ * the gate calls account gate_kernel under FHEAES_STAGE_VERTICAL_PACKING. */
 int fheaes_profile_enable(fheaes_ctx *ctx, int on);
 int fheaes_profile_reset(fheaes_ctx *ctx);
 /* synchronises, then returns accumulated kernel time, launches and units (bits or polys) of a stage */

@@ -19,6 +19,7 @@ HOST, DEVICE = 0, 1
 MAC_NONE = 0xFFFFFFFF           # FHEAES_MAC_NONE: "no block" in a src_block table of mac_link
 KW_MIN_SEMIBLOCKS, KW_MAX_SEMIBLOCKS, KW_MAX_KEYS = 2, 8, 4096      # FHEAES_KW_*: a wrapped key's payload in 8-byte semiblocks, keys per unwrap call
 AES_WINDOW_OFF = 0xFFFFFFFF     # FHEAES_AES_WINDOW_OFF: fheaes_aes_set_window's "one launch per round"
+GATE_LWE, GATE_GLWE = 0, 1       # FHEAES_GATE_*: the input form of fheaes_gate_ggsw
 K2_PARK_SLOTS = 1024            # FHEAES_K2_PARK_SLOTS: owner words of the paired kernel's shared parking slots, 128 per XCC
 STAGES = ("keyswitch", "blind_rotate", "pfpks", "ggsw_fft", "vertical_packing", "linear")
 
@@ -132,6 +133,10 @@ SIGNATURES = {
                                                      _c.c_void_p, _c.c_int]),
     "fheaes_kw_link": (_c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_uint32, _u8p, _c.c_int]),
     "fheaes_aes_kw_plan": (_c.c_int, [_c.c_uint32, _c.c_uint32, _c.c_uint64, _u64p, _u64p, _u64p]),
+    "fheaes_gate_ggsw": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _u64p, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_void_p, _c.c_int]),
+    "fheaes_gate_bits": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _u64p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_gate_packed": (_c.c_int, [_ctx, _c.c_void_p, _c.c_uint64, _u64p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_int]),
+    "fheaes_gate_plan": (_c.c_int, [_u64p, _c.c_uint64, _c.c_uint32, _u64p, _u32p]),
     "fheaes_profile_enable": (_c.c_int, [_ctx, _c.c_int]),
     "fheaes_profile_reset": (_c.c_int, [_ctx]),
     "fheaes_profile_read": (_c.c_int, [_ctx, _c.c_int, _dp, _u64p, _u64p]),
@@ -597,6 +602,28 @@ class Engine:
     def unpack_bits(self, glwe_in, m: int, lwe_out):
         self._check(self._lib.fheaes_unpack_bits(self._h, _ptr(glwe_in)[0], m, _ptr(lwe_out)[0], self._space(glwe_in, lwe_out)))
 
+    # -- the gate: ciphertexts times an encrypted bit (include/fheaes.h) --
+    @staticmethod
+    def _runs(runs):
+        r = np.ascontiguousarray(np.asarray(runs, dtype=np.uint64).reshape(-1))
+        return r, r.ctypes.data_as(_u64p)
+
+    def gate_ggsw(self, ggsw_fourier, runs, ct_in, m: int, form: int, ct_out):
+        """the kernel alone on caller-made Fourier GGSWs [n_gates][1][k+1][k+1][256][2]; form GATE_LWE / GATE_GLWE; ct_out may be ct_in"""
+        r, rp = self._runs(runs)
+        self._check(self._lib.fheaes_gate_ggsw(self._h, _ptr(ggsw_fourier)[0], r.size, rp, _ptr(ct_in)[0], m, form, _ptr(ct_out)[0],
+                                               self._space(ggsw_fourier, ct_in, ct_out)))
+
+    def gate_bits(self, gates_lwe, runs, lwe_in, m: int, lwe_out):
+        r, rp = self._runs(runs)
+        self._check(self._lib.fheaes_gate_bits(self._h, _ptr(gates_lwe)[0], r.size, rp, _ptr(lwe_in)[0], m, _ptr(lwe_out)[0],
+                                               self._space(gates_lwe, lwe_in, lwe_out)))
+
+    def gate_packed(self, gates_lwe, runs, glwe_in, n_glwe: int, glwe_out):
+        r, rp = self._runs(runs)
+        self._check(self._lib.fheaes_gate_packed(self._h, _ptr(gates_lwe)[0], r.size, rp, _ptr(glwe_in)[0], n_glwe, _ptr(glwe_out)[0],
+                                                 self._space(gates_lwe, glwe_in, glwe_out)))
+
     # -- wire formats: seeded input ciphertexts, modulus-switched packed outputs (include/fheaes.h) --
     def expand_lwe_seeded(self, mask_key, first_index: int, bodies, m: int, lwe_out):
         """lwe_out[t] = [mask words of ciphertext first_index + t | bodies[t]]; mask_key: the public 256-bit key, 8 uint32 on the host"""
@@ -826,6 +853,17 @@ def aes_kw_plan(key_bits: int, semiblocks: int, n_keys: int) -> dict:
     if rc != 0:
         raise FheAesError(rc, "fheaes_aes_kw_plan: key_bits 128 / 192 / 256, %d..%d semiblocks, at most %d keys" % (KW_MIN_SEMIBLOCKS, KW_MAX_SEMIBLOCKS, KW_MAX_KEYS))
     return {"steps": steps.value, "cipher_blocks": blocks.value, "byte_wopbs": wopbs.value}
+
+
+def gate_plan(runs, k: int) -> dict:
+    """fheaes_gate_plan (host only, no GPU): the grid a gate call over these runs launches at GLWE dimension k --
+    {"workgroups", "instances_per_workgroup"}"""
+    r = np.ascontiguousarray(np.asarray(runs, dtype=np.uint64).reshape(-1))
+    wgs, per = _c.c_uint64(), _c.c_uint32()
+    rc = load_library().fheaes_gate_plan(r.ctypes.data_as(_u64p), r.size, k, _c.byref(wgs), _c.byref(per))
+    if rc != 0:
+        raise FheAesError(rc, "fheaes_gate_plan: k must be 4 or 1")
+    return {"workgroups": wgs.value, "instances_per_workgroup": per.value}
 
 
 def round_keys_packed_glwes(key_bits: int) -> int:

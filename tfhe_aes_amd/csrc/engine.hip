@@ -23,6 +23,7 @@
 #include "fheaes.h"
 #include "fft_dev.h"
 #include "kern_extprod.h"
+#include "kern_gate.h"
 #include "kern_blindrot_latency.h"
 #include "kern_blindrot16.h"
 #include "kern_blindrot_pair.h"
@@ -1629,6 +1630,93 @@ int fheaes_aes_kw_plan(uint32_t key_bits, uint32_t semiblocks, uint64_t n_keys, 
     *steps = 6 * n;
     *cipher_blocks = 6 * n * n_keys;
     *byte_wopbs = 16 * nr * 6 * n * n_keys + 8 * n * n_keys + 16 * n_keys;
+    return FHEAES_OK;
+}
+
+// ---- the gate: ciphertexts times an encrypted bit ------------------------------------------------
+static_assert(GATE_LWE == FHEAES_GATE_LWE && GATE_GLWE == FHEAES_GATE_GLWE, "fheaes.h's input forms are the kernel's");
+
+// ggsw_fourier: caller-made GGSWs (fheaes_gate_ggsw), else gates_lwe: the bits, circuit-bootstrapped here in wopbs_dev's workspaces and by its
+// chunk rule (the front half of wopbs_dev: K1, K2 at level 1, K3, K4), each chunk's GGSWs gating that chunk's runs before the next overwrites them
+static int gate_call(fheaes_ctx *c, bool boot, const double *ggsw_fourier, const uint64_t *gates_lwe, uint64_t n_gates, const uint64_t *bits_of_gate, const uint64_t *in,
+                     uint64_t m, int form, uint64_t *out, int memspace)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    if (boot) TRY(check_keys(c));
+    if (form != GATE_LWE && form != GATE_GLWE) return c->fail(FHEAES_ERR_INVALID, "form must be 0 (LWE) or 1 (GLWE), got %d", form);
+    if (n_gates && !bits_of_gate) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    if (n_gates > 0xFFFFFFFFull) return c->fail(FHEAES_ERR_INVALID, "a call takes at most 2^32 - 1 gates (got %llu)", (unsigned long long)n_gates);
+    const uint32_t R = gate_r(c->k1);
+    const uint64_t chunk = boot ? MAX_CHUNK_BITS : 0;
+    std::vector<GateWg> wgs;
+    std::vector<uint64_t> chunk_end;
+    uint64_t n_wgs = 0, total = 0;
+    for (uint64_t g = 0; g < n_gates; ++g) {
+        if (bits_of_gate[g] > m - total) { total = ~0ull; break; }
+        total += bits_of_gate[g];
+    }
+    if (total != m) return c->fail(FHEAES_ERR_INVALID, "the runs of bits_of_gate do not add up to m = %llu", (unsigned long long)m);
+    if (m == 0) return FHEAES_OK;
+    if (!in || !out || (boot ? !gates_lwe : !ggsw_fourier)) return c->fail(FHEAES_ERR_INVALID, "null pointer");
+    const uint64_t ggsw_words = (uint64_t)c->k1 * c->k1 * FHE_N, inst_words = form == GATE_GLWE ? (uint64_t)c->k1 * FHE_N : c->big1;
+    const uint64_t bytes = m * inst_words * 8, gate_bytes = n_gates * (boot ? c->big1 : ggsw_words) * 8;
+    const void *gates = boot ? (const void *)gates_lwe : (const void *)ggsw_fourier;
+    if (out != in && overlap(in, bytes, out, bytes)) return c->fail(FHEAES_ERR_INVALID, "in and out overlap without being the same buffer");
+    if (overlap(gates, gate_bytes, out, bytes)) return c->fail(FHEAES_ERR_INVALID, "out overlaps the gates");
+    gate_table(bits_of_gate, n_gates, R, chunk, &wgs, &chunk_end, &n_wgs);
+    HIP_TRY(c, hipSetDevice(c->device));
+    Staged s(c, memspace);
+    if (boot) TRY(s.in(gates_lwe, gate_bytes, &gates_lwe));
+    else TRY(s.in(ggsw_fourier, gate_bytes, &ggsw_fourier));
+    if (out == in) { TRY(s.inout(out, bytes, &out)); in = out; }
+    else { TRY(s.in(in, bytes, &in)); TRY(s.out(out, bytes, &out)); }
+    const size_t tab_bytes = wgs.size() * sizeof(GateWg);
+    TRY(upload_pinned(c, tab_bytes, tab_bytes, [&](uint8_t *pin) { memcpy(pin, wgs.data(), tab_bytes); }));
+    const GateWg *tab = (const GateWg *)c->ws_misc.p;
+    if (!boot) {
+        TRY(launch_gate(c, (const double2 *)ggsw_fourier, tab, n_wgs, m, form, in, out));
+        return s.finish();
+    }
+    TRY(ensure_wopbs_ws(c, std::min<uint64_t>(n_gates, chunk)));
+    uint64_t wg0 = 0;
+    for (uint64_t g0 = 0, ci = 0; g0 < n_gates; g0 += chunk, ++ci) {
+        const uint64_t gc = std::min<uint64_t>(chunk, n_gates - g0);
+        TRY(launch_keyswitch(c, gates_lwe + g0 * c->big1, gc, (uint64_t *)c->ws_small.p));
+        TRY(launch_cbs_pbs(c, (const uint64_t *)c->ws_small.p, gc, 1, (uint64_t *)c->ws_pbs.p));
+        TRY(launch_pfpks(c, (const uint64_t *)c->ws_pbs.p, gc, (uint64_t *)c->ws_ggsw.p, ggsw_words));
+        TRY(launch_forward_fourier(c, (const uint64_t *)c->ws_ggsw.p, gc * c->k1 * c->k1, (double2 *)c->ws_ggswf.p, FHEAES_STAGE_GGSW_FFT));
+        uint64_t units = 0;
+        for (uint64_t g = g0; g < g0 + gc; ++g) units += bits_of_gate[g];
+        TRY(launch_gate(c, (const double2 *)c->ws_ggswf.p, tab + wg0, chunk_end[ci] - wg0, units, form, in, out));
+        wg0 = chunk_end[ci];
+    }
+    return s.finish();
+}
+
+int fheaes_gate_ggsw(fheaes_ctx *c, const double *ggsw_fourier, uint64_t n_gates, const uint64_t *bits_of_gate, const uint64_t *in, uint64_t m, int form,
+                     uint64_t *out, int memspace)
+{
+    return gate_call(c, false, ggsw_fourier, nullptr, n_gates, bits_of_gate, in, m, form, out, memspace);
+}
+
+int fheaes_gate_bits(fheaes_ctx *c, const uint64_t *gates_lwe, uint64_t n_gates, const uint64_t *bits_of_gate, const uint64_t *lwe_in, uint64_t m,
+                     uint64_t *lwe_out, int memspace)
+{
+    return gate_call(c, true, nullptr, gates_lwe, n_gates, bits_of_gate, lwe_in, m, GATE_LWE, lwe_out, memspace);
+}
+
+int fheaes_gate_packed(fheaes_ctx *c, const uint64_t *gates_lwe, uint64_t n_gates, const uint64_t *glwes_of_gate, const uint64_t *glwe_in, uint64_t n_glwe,
+                       uint64_t *glwe_out, int memspace)
+{
+    return gate_call(c, true, nullptr, gates_lwe, n_gates, glwes_of_gate, glwe_in, n_glwe, GATE_GLWE, glwe_out, memspace);
+}
+
+int fheaes_gate_plan(const uint64_t *bits_of_gate, uint64_t n_gates, uint32_t k, uint64_t *workgroups, uint32_t *instances_per_workgroup)
+{
+    if ((n_gates && !bits_of_gate) || (k != 4 && k != 1) || !workgroups || !instances_per_workgroup) return FHEAES_ERR_INVALID;
+    *instances_per_workgroup = gate_r(k + 1);
+    gate_table(bits_of_gate, n_gates, *instances_per_workgroup, 0, nullptr, nullptr, workgroups);
     return FHEAES_OK;
 }
 

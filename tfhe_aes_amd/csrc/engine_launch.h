@@ -355,6 +355,50 @@ int launch_vertical_packing(fheaes_ctx *c, const double2 *ggswf, uint64_t n_inpu
     return FHEAES_OK;
 }
 
+// ---- the gate (kern_gate.h): out = GGSW_g (x) in ---------------------------------------------------------------------------------
+#define GATE_MAX_GRID 65536ull         /* workgroups per launch of gate_kernel; a larger table is cut into several launches */
+// instances per workgroup: R K1 <= 16 lane groups
+uint32_t gate_r(uint32_t k1) { return k1 == 5 ? 3 : 8; }
+
+// The caller's runs (bits_of_gate[g] consecutive instances under gate g) as the kernel's workgroup table: every gate's run cut into
+// workgroups of up to R instances, a gate of 0 instances none.  `chunk` > 0: the gates are bootstrapped `chunk` at a time into one
+// workspace, so an entry names its gate inside its chunk, and chunk_end[c] is the number of workgroups of chunks 0..c.
+// Returns the sum of the runs.
+uint64_t gate_table(const uint64_t *bits_of_gate, uint64_t n_gates, uint32_t R, uint64_t chunk, std::vector<GateWg> *wgs, std::vector<uint64_t> *chunk_end,
+                    uint64_t *n_wgs)
+{
+    uint64_t first = 0, count = 0;
+    for (uint64_t g = 0; g < n_gates; ++g) {
+        const uint64_t run = bits_of_gate[g];
+        if (wgs)
+            for (uint64_t i = 0; i < run; i += R)
+                wgs->push_back({first + i, (uint32_t)(chunk ? g % chunk : g), (uint32_t)std::min<uint64_t>(R, run - i)});
+        count += (run + R - 1) / R;
+        first += run;
+        if (chunk_end && chunk && ((g + 1) % chunk == 0 || g + 1 == n_gates)) chunk_end->push_back(count);
+    }
+    *n_wgs = count;
+    return first;
+}
+
+// workgroups wg0 .. wg0 + n_wgs - 1 of the device table `wgs` over the Fourier GGSWs `ggswf` (the gates the table's entries index);
+// form GATE_LWE / GATE_GLWE.  Accounted under vertical packing; units: bits, or GLWEs x N.
+int launch_gate(fheaes_ctx *c, const double2 *ggswf, const GateWg *wgs, uint64_t n_wgs, uint64_t units, int form, const uint64_t *in, uint64_t *out)
+{
+    if (n_wgs == 0) return FHEAES_OK;
+    StageScope sc(c, FHEAES_STAGE_VERTICAL_PACKING, form == GATE_GLWE ? units * FHE_N : units);
+    const bool k4 = c->k1 == 5;
+    void (*const kernel)(GateArgs) = form == GATE_GLWE ? (k4 ? gate_kernel<5, 15, 3, GATE_GLWE> : gate_kernel<2, 15, 8, GATE_GLWE>)
+                                                       : (k4 ? gate_kernel<5, 15, 3, GATE_LWE> : gate_kernel<2, 15, 8, GATE_LWE>);
+    for (uint64_t w0 = 0; w0 < n_wgs; w0 += GATE_MAX_GRID) {
+        GateArgs a{};
+        a.ggsw = ggswf; a.tw = c->tw_d; a.wgs = wgs + w0; a.in = in; a.out = out;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<uint64_t>(GATE_MAX_GRID, n_wgs - w0)), dim3(EP_THREADS), 0, c->stream, a);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return FHEAES_OK;
+}
+
 // static schedule assertion (NOT runtime noise tracking: words carry no metadata): every linear layer of the engine's own AES schedule
 // declares here how many WoPBS outputs it sums per word; a table that would sum more than tfhe-rs' noise-asserts allow is refused
 int noise_guard(fheaes_ctx *c, uint32_t level, const char *what)

@@ -621,11 +621,13 @@ class Server:
         self.engine.aes_cbc_mac_keyed(words, bits, n_keys, keys, lens, clear, enc_all, enc_bytes if any_enc else None, init, out, packed=packed)
         return out
 
-    def aes_ccm_decrypt(self, round_keys, messages, out=None, valid_out=None):
+    def aes_ccm_decrypt(self, round_keys, messages, out=None, valid_out=None, gate: bool = False):
         """AES-CCM decryption (SP 800-38C, RFC 3610) of PUBLIC messages (key_index, nonce, aad, ciphertext, tag) under encrypted keys, the
         tag compared under encryption.  Returns (plaintext [total_blocks][16][8][kN+1], valid [n][kN+1], block_of_message): message i's
         plaintext is blocks block_of_message[i] .. block_of_message[i + 1], rows beyond its length zero words, and valid[i] decrypts
-        (Client.decrypt_bits) to 1 iff its tag verifies.  The plaintext is not gated on `valid`.  One public call (B0, the counters), a
+        (Client.decrypt_bits) to 1 iff its tag verifies.  gate=False: the plaintext is not gated on `valid`; gate=True: the rows of message i
+        are multiplied by valid[i] (Server.gate, in place) before they are returned, so a forged message decrypts to zeros, as SP 800-38C
+        asks; same shapes, `valid` as before.  One public call (B0, the counters), a
         CBC-MAC chain over all messages step by step, and two WoPBS for the comparison (include/fheaes.h: fheaes_aes_ccm_open_keyed).  The tag
         length is len(tag) (4, 6, .., 16), the nonce has 7..13 bytes.  round_keys as aes_cbc_mac_streams'."""
         words, bits, n_keys, packed = self._round_keys(round_keys, many=None)
@@ -636,6 +638,9 @@ class Server:
         if n:
             self.engine.aes_ccm_open_keyed(words, bits, n_keys, a["key_of_stream"], a["head_blocks"], a["head"], a["ctr0"], a["payload_bytes"], a["ciphertext"],
                                            a["tags"], a["tag_bytes"], out if total else None, valid_out, packed=packed)
+            if gate and total:
+                at = a["block_of_message"]
+                self.gate(out, valid_out, [128 * (at[i + 1] - at[i]) for i in range(n)], out=out)
         return out, valid_out, a["block_of_message"]
 
     # ---- CMAC: the MAC of public messages under encrypted keys, and its check -------------------
@@ -687,12 +692,13 @@ class Server:
         return valid_out
 
     # ---- AES key unwrap: wrapped AES keys in, encrypted keys out ---------------------------------
-    def aes_key_unwrap(self, kek_dec_round_keys, wrapped, kek_of_key=None, out=None, valid_out=None):
+    def aes_key_unwrap(self, kek_dec_round_keys, wrapped, kek_of_key=None, out=None, valid_out=None, gate: bool = False):
         """The AES Key Unwrap of RFC 3394 / SP 800-38F under encrypted key-encryption keys: `wrapped` is a list of byte strings of one
         length, 8 (n + 1) bytes for a payload of n = 2..8 semiblocks -- public data, straight from a key store.  Returns (keys, valid):
         keys [n_keys][8 n][8][kN+1] (or `out`), the payloads as fresh ciphertexts -- for n = 2, 3, 4 an argument of aes_key_expansion_many
-        -- NOT gated on valid; valid [n_keys][kN+1] (or `valid_out`), valid[i] decrypting (Client.decrypt_bits) to 1 iff key i's
-        integrity constant is right.  kek_dec_round_keys: aes_decryption_round_keys(_many) of one KEK or of many, or a PackedRoundKeys of
+        -- NOT gated on valid unless gate=True, which multiplies key i's payload by valid[i] (Server.gate, in place): a tampered blob then
+        yields the all-zero payload, as RFC 3394 asks; valid [n_keys][kN+1] (or `valid_out`), valid[i] decrypting (Client.decrypt_bits) to
+        1 iff key i's integrity constant is right.  kek_dec_round_keys: aes_decryption_round_keys(_many) of one KEK or of many, or a PackedRoundKeys of
         them; kek_of_key: the KEK of every wrapped key, optional with one KEK.  6 n passes of the equivalent inverse cipher over all keys
         (include/fheaes.h: fheaes_aes_kw_unwrap_keyed), one C call per FHEAES_KW_MAX_KEYS keys."""
         k = self._round_keys(kek_dec_round_keys, "KEK decryption round keys", many=None)
@@ -704,12 +710,15 @@ class Server:
             kok = a["kek_of_key"][lo:lo + cap] if a["kek_of_key"] is not None else None
             self.engine.aes_kw_unwrap_keyed(k.words, k.key_bits, k.n_keys, kok, n, a["wrapped"][lo:lo + cap], out[lo:lo + cap], valid_out[lo:lo + cap],
                                             packed=k.packed)
+        if gate and n_keys:
+            self.gate(out, valid_out, out=out)
         return out, valid_out
 
-    def aes_key_unwrap_packed(self, kek_dec_round_keys, wrapped, kek_of_key=None, chunk: int = 256):
+    def aes_key_unwrap_packed(self, kek_dec_round_keys, wrapped, kek_of_key=None, chunk: int = 256, gate: bool = False):
         """aes_key_unwrap followed by aes_key_expansion_packed, `chunk` keys at a time, for payloads of 16, 24 and 32 bytes (AES keys):
         returns (a PackedRoundKeys of the unwrapped keys, valid [n_keys][kN+1]), both in the caller's order.  Neither the unwrapped keys
-        nor their round keys in LWE form exist for more than `chunk` keys at once."""
+        nor their round keys in LWE form exist for more than `chunk` keys at once.  gate=True gates every key on its `valid` BEFORE the
+        expansion: a tampered blob's store entry is then the round keys of the all-zero key."""
         k = self._round_keys(kek_dec_round_keys, "KEK decryption round keys", many=None)
         a = kw_args(wrapped, kek_of_key, k.n_keys)
         n_keys, bits, chunk = len(a["wrapped"]), 64 * a["semiblocks"], int(chunk)
@@ -722,7 +731,7 @@ class Server:
         valid = _empty_like(k.words, (n_keys, p.big1))
         for lo in range(0, n_keys, chunk):
             kok = a["kek_of_key"][lo:lo + chunk] if a["kek_of_key"] is not None else None
-            keys, _ = self.aes_key_unwrap(kek_dec_round_keys, [bytes(w) for w in a["wrapped"][lo:lo + chunk]], kok, valid_out=valid[lo:lo + chunk])
+            keys, _ = self.aes_key_unwrap(kek_dec_round_keys, [bytes(w) for w in a["wrapped"][lo:lo + chunk]], kok, valid_out=valid[lo:lo + chunk], gate=gate)
             data[lo:lo + chunk] = self.aes_key_expansion_packed(keys, chunk).data
             if not isinstance(data, np.ndarray):
                 import torch
@@ -774,6 +783,55 @@ class Server:
                 self.engine.synchronize()             # the chunk's LWE form is freed here: its readers must be done first
             del rk
         return PackedRoundKeys(p, bits, data)
+
+    # ---- the gate: ciphertexts times an encrypted bit -------------------------------------------
+    def _gate_runs(self, valid, m: int, runs, what: str):
+        if valid.ndim != 2 or int(valid.shape[1]) != self.params.big1:
+            raise ValueError("valid must be [n_gates][kN+1] = [n_gates][%d] words, got shape %s" % (self.params.big1, tuple(valid.shape)))
+        n_gates = int(valid.shape[0])
+        if runs is None:
+            if n_gates == 0 or m % n_gates:
+                raise ValueError("%d %s do not divide into equal runs under %d gates: pass the runs" % (m, what, n_gates))
+            return [m // n_gates] * n_gates
+        runs = [int(r) for r in runs]
+        if len(runs) != n_gates or any(r < 0 for r in runs) or sum(runs) != m:
+            raise ValueError("one run per gate, adding up to %d %s, expected" % (m, what))
+        return runs
+
+    def gate(self, ct, valid, bits_of_gate=None, out=None):
+        """ct [..., kN+1] times the encrypted bits valid [n_gates][kN+1]: gate g multiplies the next bits_of_gate[g] ciphertexts of the
+        flattened `ct` (None: equal runs of m / n_gates), so a gated bit decrypts to valid * bit -- what releases a plaintext or a key
+        only if its check passed, without the server learning which.  One circuit bootstrap per gate and one external product per
+        ciphertext (include/fheaes.h: fheaes_gate_bits); a gated ciphertext keeps the noise level of its input.  Returns a new array of
+        ct's shape, or `out`, which may be `ct` itself (in place)."""
+        p = self.params
+        if int(ct.shape[-1]) != p.big1:
+            raise ValueError("gate takes [..., kN+1] = [..., %d] words, got shape %s" % (p.big1, tuple(ct.shape)))
+        m = 1
+        for d in ct.shape[:-1]:
+            m *= int(d)
+        runs = self._gate_runs(valid, m, bits_of_gate, "ciphertexts")
+        out = self._many_out(ct, tuple(ct.shape), out)
+        if m:
+            self.engine.gate_bits(valid, runs, ct, m, out)
+        return out
+
+    def gate_packed(self, packed, valid, glwes_of_gate=None, out=None):
+        """Server.gate on packed GLWEs [G][(k+1)N] (Server.pack at width 64, a PackedRoundKeys' data): gate g multiplies the next
+        glwes_of_gate[g] GLWEs, all N bits of each, by valid[g] -- one external product per 512 bits (fheaes_gate_packed).  Gate before
+        a modulus switch, not after."""
+        p = self.params
+        gw = (p.k + 1) * p.N
+        if int(packed.shape[-1]) != gw:
+            raise ValueError("gate_packed takes [..., (k+1)N] = [..., %d] words, got shape %s" % (gw, tuple(packed.shape)))
+        g = 1
+        for d in packed.shape[:-1]:
+            g *= int(d)
+        runs = self._gate_runs(valid, g, glwes_of_gate, "GLWEs")
+        out = self._many_out(packed, tuple(packed.shape), out)
+        if g:
+            self.engine.gate_packed(valid, runs, packed, g, out)
+        return out
 
     # ---- packed ciphertexts ------------------------------------------------------
     def pack(self, ct, out=None, width: int = 64):
@@ -1052,8 +1110,9 @@ class ServerGroup:
             round_keys, streams[lo:hi], init=None if init is None else init[lo:hi], out=out[lo:hi])) for lo, hi in shards])
         return out
 
-    def aes_ccm_decrypt(self, round_keys, messages):
-        """Server.aes_ccm_decrypt: whole messages per context, contiguous and balanced by chained plus public block count"""
+    def aes_ccm_decrypt(self, round_keys, messages, gate: bool = False):
+        """Server.aes_ccm_decrypt: whole messages per context, contiguous and balanced by chained plus public block count; with gate=True
+        every context gates its own messages"""
         messages = [tuple(m) for m in messages]
         a = ccm_args(messages)
         at, n = a["block_of_message"], len(messages)
@@ -1062,7 +1121,7 @@ class ServerGroup:
         cost = [a["head_blocks"][i] - 1 + 2 * (at[i + 1] - at[i]) + 2 for i in range(n)]
         shards = _shards_by_cost(cost, len(self.servers))
         self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_ccm_decrypt(
-            round_keys, messages[lo:hi], out=out[at[lo]:at[hi]], valid_out=valid[lo:hi])) for lo, hi in shards])
+            round_keys, messages[lo:hi], out=out[at[lo]:at[hi]], valid_out=valid[lo:hi], gate=gate)) for lo, hi in shards])
         return out, valid, at
 
     def aes_cmac_subkeys(self, round_keys):
@@ -1099,18 +1158,19 @@ class ServerGroup:
 
         return [shard_blocks(n_keys, len(self.servers), i) for i in range(len(self.servers))]
 
-    def aes_key_unwrap(self, kek_dec_round_keys, wrapped, kek_of_key=None):
-        """Server.aes_key_unwrap: whole keys per context, contiguous; every context reads all KEKs.  Returns (keys, valid)."""
+    def aes_key_unwrap(self, kek_dec_round_keys, wrapped, kek_of_key=None, gate: bool = False):
+        """Server.aes_key_unwrap: whole keys per context, contiguous; every context reads all KEKs and, with gate=True, gates its own
+        keys.  Returns (keys, valid)."""
         k = self._round_keys(kek_dec_round_keys, "KEK decryption round keys", many=None)
         a = kw_args(wrapped, kek_of_key, k.n_keys)
         wrapped, kok = [bytes(w) for w in a["wrapped"]], a["kek_of_key"]
         keys, valid = self._new_out(k, len(wrapped), 8 * a["semiblocks"], 8), self._new_out(k, len(wrapped))
         self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_key_unwrap(kek_dec_round_keys, wrapped[lo:hi], None if kok is None else kok[lo:hi],
-                                                                                          out=keys[lo:hi], valid_out=valid[lo:hi]))
+                                                                                          out=keys[lo:hi], valid_out=valid[lo:hi], gate=gate))
                           for lo, hi in self._kw_shards(len(wrapped))])
         return keys, valid
 
-    def aes_key_unwrap_packed(self, kek_dec_round_keys, wrapped, kek_of_key=None, chunk: int = 256):
+    def aes_key_unwrap_packed(self, kek_dec_round_keys, wrapped, kek_of_key=None, chunk: int = 256, gate: bool = False):
         """Server.aes_key_unwrap_packed with whole keys per context: every context unwraps, expands and packs its shard `chunk` keys at a
         time; the store and `valid` are put together in the caller's order.  Returns (PackedRoundKeys, valid)."""
         k = self._round_keys(kek_dec_round_keys, "KEK decryption round keys", many=None)
@@ -1120,7 +1180,7 @@ class ServerGroup:
 
         def job(i, lo, hi):
             def run(s):
-                parts[i] = s.aes_key_unwrap_packed(kek_dec_round_keys, wrapped[lo:hi], None if kok is None else kok[lo:hi], chunk)
+                parts[i] = s.aes_key_unwrap_packed(kek_dec_round_keys, wrapped[lo:hi], None if kok is None else kok[lo:hi], chunk, gate=gate)
             return run
 
         shards = self._kw_shards(len(wrapped))
@@ -1154,6 +1214,27 @@ class ServerGroup:
         prk = self.servers[0].aes_key_expansion_packed(keys, chunk)
         self.servers[0].synchronize()
         return prk
+
+    def _fan_out_gates(self, method, ct, valid, runs, unit_words: int):
+        """whole gates per context, contiguous and balanced by run length: context i gates the rows of its gates, out of place"""
+        flat = ct.reshape(-1, unit_words)
+        runs = self.servers[0]._gate_runs(valid, int(flat.shape[0]), runs, "rows")
+        out = _empty_like(ct, tuple(flat.shape))
+        at = [0]
+        for r in runs:
+            at.append(at[-1] + r)
+        shards = _shards_by_cost([r + 1 for r in runs], len(self.servers))
+        self._run_shards([None if at[hi] <= at[lo] else (lambda s, lo=lo, hi=hi: getattr(s, method)(flat[at[lo]:at[hi]], valid[lo:hi], runs[lo:hi], out=out[at[lo]:at[hi]]))
+                          for lo, hi in shards])
+        return out.reshape(tuple(ct.shape))
+
+    def gate(self, ct, valid, bits_of_gate=None):
+        """Server.gate, sharded on whole gates; the words are those of one context whatever the number of contexts"""
+        return self._fan_out_gates("gate", ct, valid, bits_of_gate, self.params.big1)
+
+    def gate_packed(self, packed, valid, glwes_of_gate=None):
+        """Server.gate_packed, sharded on whole gates"""
+        return self._fan_out_gates("gate_packed", packed, valid, glwes_of_gate, (self.params.k + 1) * self.params.N)
 
     def _glwe_shards(self, n_glwes: int):
         from .dist import shard_blocks
