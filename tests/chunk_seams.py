@@ -14,6 +14,13 @@ and of the later modes (test_gpu_chunk_seams_modes.py, pinned without a GPU by t
   2^20 workgroups = 8,192 tweak blocks per pass of xts_tweak_kernel (TWEAK_ROWS_PER_PASS)
   128 inputs per chunk of the 16-bit tag WoPBS of a CCM call: 2^24 bytes of CMUX tree each (TAG_TREE_CHUNK); 256 messages per chunk of
   its 8-bit one (TAG_BYTE_CHUNK)
+
+and of the calls that came after those (test_gpu_chunk_seams_calls.py, pinned without a GPU by test_chunk_seams_calls_cpu.py; part G):
+
+  257 keys, streams or wrapped keys: one block behind the 4,096 bytes of a byte WoPBS chunk and the 256 slots of a link's grid pass, in
+  the CMAC subkey derivation, the CMAC chain with its tag check, and the key unwrap
+  65,536 workgroups per launch of gate_kernel (GATE_MAX_GRID), 8 instances a workgroup at k = 1; MAX_CHUNK_BITS gates per circuit
+  bootstrap of a gate call
 """
 import numpy as np
 
@@ -290,3 +297,127 @@ def public_keyed_blocks():
     blocks = [int.from_bytes(rng.bytes(16), "big") for _ in range(PUBLIC_BLOCKS)]
     data = [int.from_bytes(rng.bytes(16), "big") for _ in range(PUBLIC_BLOCKS)]
     return blocks, [int(k) for k in rng.integers(0, PUBLIC_KEYS, PUBLIC_BLOCKS)], data
+
+
+# ---- G. the later calls: CMAC, key unwrap and the gate -------------------------------------------------------------------------------------
+# (test_gpu_chunk_seams_calls.py, pinned without a GPU by test_chunk_seams_calls_cpu.py.)  The rules restated:
+#   a byte WoPBS takes CHUNK_BYTES = 4,096 bytes a chunk: 256 blocks, so 257 keys or streams put one block behind the seam
+#   mac_link_kernel and kw_link_kernel take SLOTS_PER_PASS = 256 slots or keys a grid pass; cmac_subkey_kernel one workgroup per output row
+#   gate_kernel takes GATE_MAX_GRID = 65,536 workgroups a launch, GATE_R = 8 instances a workgroup at k = 1, and a bootstrapped gate call
+#   MAX_CHUNK_BITS gates a chunk, whose GGSWs lie at g mod MAX_CHUNK_BITS of one workspace
+GATE_MAX_GRID = 65536
+GATE_R = 8                                           # instances per workgroup at PARAM_TOY (k = 1); 3 at k = 4
+CALL_ALONE = (0, 1, 255, 256)                        # the streams and wrapped keys that also run alone
+
+# A. CMAC subkeys of 257 keys, the SP 800-38B key the one behind the seam
+CMAC_KEYS = 257
+CMAC_VECTOR_KEY = 256
+CMAC_KEYS_ALONE = (0, 127, 128, 255, 256)
+
+# B. CMAC tags and verification: 257 streams under a store of 259 keys, two of them never named
+CMAC_STORE_KEYS = 259
+CMAC_UNNAMED = (5, 130)
+CMAC_STREAMS = 257
+CMAC_LENGTHS = {0: 48, 100: 17, 255: 0, 256: 48}     # the rest one block: 16 bytes (K1) at even streams, 1..15 bytes (K2) at odd ones
+CMAC_BAD = sorted({1, 127, 129, 255, 256} | set(range(41, CMAC_STREAMS, 41)))    # position 0 verifies, 255 and 256 do not
+CMAC_BAD_MESSAGE = 256                               # a message bit there; a bit of the last compared tag byte at the others
+
+# C. key unwrap: 257 wrapped AES-128 keys (n = 2 semiblocks) under 3 KEKs, RFC 3394 4.1 at key 256 under KEK 0
+KW_KEYS, KW_KEKS, KW_SEMIBLOCKS = 257, 3, 2
+KW_VECTOR_KEY = 256
+KW_BAD = sorted({1, 127, 129, 255} | set(range(37, KW_KEYS, 37)))     # keys 0 and 256 are valid, key 255 is not
+KW_WRONG_KEK = 128                                   # a valid blob named under another KEK than the one that wrapped it
+
+# D. gate_kernel behind GATE_MAX_GRID: gate 0 ends in workgroup 65,536, the first of the second launch, with 3 instances
+GATE_GRID_RUNS = [GATE_R * GATE_MAX_GRID + 3, 0, 9, 1]
+GATE_ROW_PERIOD = 7                                  # the rows of test_gpu_gate._inputs, coprime to GATE_R: every phase in a workgroup
+
+# E. both gate seams in one bootstrapped call: 32,769 gates, chunk 1 of 65,537 workgroups, chunk 2 of gate 32,768 alone with two
+GATE_BOOT_GATES = MAX_CHUNK_BITS + 1
+GATE_BOOT_HEAD = GATE_R * (MAX_CHUNK_BITS + 3)       # gate 0: 32,771 workgroups
+GATE_BOOT_TAIL = (1, 1, 0, 9)                        # gates 32,765 .. 32,768
+
+
+def gate_table(runs, R: int = GATE_R, chunk: int = 0):
+    """(first instance, gate, instances) of every workgroup: a run cut into workgroups of up to R instances, a run of 0 none; chunk > 0:
+    the gate as its place in the chunk's workspace"""
+    out, first = [], 0
+    for g, run in enumerate(runs):
+        out += [(first + i, g % chunk if chunk else g, min(R, run - i)) for i in range(0, run, R)]
+        first += run
+    return out
+
+
+def gate_workgroups(runs, R: int = GATE_R) -> int:
+    return sum(-(-int(r) // R) for r in runs)
+
+
+def gate_launches(runs, R: int = GATE_R, chunk: int = 0):
+    """the kernel launches of every launch_gate of a call: one launch_gate for all runs, or (chunk > 0) one per chunk of gates"""
+    runs = list(runs)
+    parts = [runs] if not chunk else [runs[g0:g0 + chunk] for g0 in range(0, len(runs), chunk)]
+    return [chunks(gate_workgroups(part, R), GATE_MAX_GRID) for part in parts]
+
+
+def gate_boot_runs(head: int = GATE_BOOT_HEAD):
+    """the runs of E: gate 0 `head` instances, gate 32,767 none, gate 32,768 nine, every other gate one"""
+    runs = [1] * GATE_BOOT_GATES
+    runs[0] = head
+    runs[-4:] = GATE_BOOT_TAIL
+    return runs
+
+
+def gate_packed_runs():
+    """the runs of E in the GLWE form: one GLWE a gate, none under gate 32,767, two under gate 32,768"""
+    runs = [1] * GATE_BOOT_GATES
+    runs[-2:] = [0, 2]
+    return runs
+
+
+def cmac_key_of_stream(s: int) -> int:
+    """a permutation of the 257 named keys of the store of 259 (257 is prime): the keys are not in stream order"""
+    named = [k for k in range(CMAC_STORE_KEYS) if k not in CMAC_UNNAMED]
+    return named[(100 * s + 7) % len(named)]
+
+
+def cmac_message_bytes(s: int) -> int:
+    return CMAC_LENGTHS.get(s, 16 if s % 2 == 0 else 1 + s % 15)
+
+
+def cmac_tag_bytes(s: int) -> int:
+    return 4 + s % 13
+
+
+def cmac_chain_blocks():
+    return [max(1, -(-cmac_message_bytes(s) // 16)) for s in range(CMAC_STREAMS)]
+
+
+def cmac_keyswitch(public_plan, n_derived: int, n_active, n_verified: int = 0, nr: int = 10):
+    """{part: (launches, units)} of the key switch of a CMAC call round by round.  With n_derived keys whose subkeys the call derives: the
+    public rounds over their pools (public_plan: aes_public_plan_keyed of one zero block per key), the identity WoPBS over the 16 bytes
+    of every L and the one over the 32 bytes of every raw K1 | K2.  The chain over its live prefixes.  With n_verified tags: the 8-bit tag
+    WoPBS over 16 bytes a stream and the 16-bit one over one input a stream"""
+    parts = {"chain": chain_keyswitch(n_active, nr)}
+    if n_derived:
+        pub = [byte_wopbs(v) for v in public_plan]
+        parts["public_rounds"] = (sum(l for l, _ in pub), sum(u for _, u in pub))
+        parts["refresh_l"], parts["refresh_k"] = byte_wopbs(16 * n_derived), byte_wopbs(32 * n_derived)
+    if n_verified:
+        parts["tag_bytes"], parts["tag_tree"] = byte_wopbs(16 * n_verified), (wopbs_chunks(n_verified, 16, 1, 2), 16 * n_verified)
+    return parts
+
+
+def kw_kek_of_key():
+    """(j + 1) mod 3: the KEK of key j is not that of key j - 128; key 256 takes KEK 0, which keys 0 and 255 do not"""
+    return [(j + 1) % KW_KEKS for j in range(KW_KEYS - 1)] + [0]
+
+
+def kw_keyswitch(n_keys: int = KW_KEYS, n: int = KW_SEMIBLOCKS, nr: int = 10, window: int = 0):
+    """{part: (launches, units)} of the key switch of a key unwrap: 6 n passes of the equivalent inverse cipher over all keys (round by
+    round, or window > 0: in windows of that many blocks), the identity WoPBS over the 8 n payload bytes of every key, the two tag WoPBS"""
+    if window:
+        cipher = (6 * n * window_launches(n_keys, nr, min(window, n_keys))[1], 6 * n * nr * 128 * n_keys)
+    else:
+        cipher = (6 * n * nr * byte_wopbs(16 * n_keys)[0], 6 * n * nr * byte_wopbs(16 * n_keys)[1])
+    return {"cipher": cipher, "refresh": byte_wopbs(8 * n * n_keys), "tag_bytes": byte_wopbs(16 * n_keys),
+            "tag_tree": (wopbs_chunks(n_keys, 16, 1, 2), 16 * n_keys)}

@@ -1,6 +1,7 @@
 """What the key-unwrap tests share: the six vectors of RFC 3394 section 4 as data, the link of the unwrap (kw_link_kernel) restated in
-numpy as moves plus 1 << 63 on body words, and the composition of older entry points that fheaes_aes_kw_unwrap_keyed must equal word for
-word.  A plain module like cmac.py: imported by name, not collected."""
+numpy as moves plus 1 << 63 on body words, the composition of older entry points that fheaes_aes_kw_unwrap_keyed must equal word for
+word, and the clear key wrap of many keys at once in numpy (wrap_many), for the tests that need hundreds of blobs.  A plain module like
+cmac.py: imported by name, not collected."""
 import numpy as np
 
 import ccm
@@ -73,6 +74,47 @@ def np_link(state, regs, n, s, wrapped):
             st[64:] = 0
             add_trivial(st[:64], ICV.to_bytes(8, "big"))
     return state, regs
+
+
+def _xtime(v):
+    return ((v << 1) ^ np.where(v & 0x80, 0x1B, 0)) & 0xFF
+
+
+def np_encrypt_blocks(round_keys, blocks):
+    """AES encryption (FIPS-197 Fig. 5) of many blocks at once in numpy: round_keys [n][Nr+1][16] and blocks [n][16], bytes as integers ->
+    [n][16].  What a test uses where hundreds of aes_clear.aes_encrypt_block calls would be its cost; held to aes_clear by
+    test_chunk_seams_calls_cpu.py"""
+    from tfhe_aes_amd import aes_clear
+
+    sbox = np.array(aes_clear.SBOX, dtype=np.int64)
+    shift = np.array([(i + 4 * (i % 4)) % 16 for i in range(16)])          # ShiftRows on the column-major state
+    rk = np.asarray(round_keys, dtype=np.int64)
+    s = np.asarray(blocks, dtype=np.int64) ^ rk[:, 0]
+    nr = rk.shape[1] - 1
+    for rnd in range(1, nr + 1):
+        s = sbox[s][:, shift]
+        if rnd < nr:
+            c = s.reshape(-1, 4, 4)
+            every = c[:, :, 0:1] ^ c[:, :, 1:2] ^ c[:, :, 2:3] ^ c[:, :, 3:4]
+            s = (c ^ every ^ _xtime(c ^ np.roll(c, -1, axis=2))).reshape(-1, 16)
+        s = s ^ rk[:, rnd]
+    return s
+
+
+def wrap_many(keks, kek_of_key, payloads):
+    """aes_clear.key_wrap of payloads[j] under keks[kek_of_key[j]] for all j at once (payloads of one length): a list of byte strings"""
+    from tfhe_aes_amd import aes_clear
+
+    expanded = np.array([aes_clear.expand_key(k) for k in keks], dtype=np.int64)
+    rk = expanded[np.asarray(kek_of_key)]
+    r = np.array([list(d) for d in payloads], dtype=np.int64).reshape(len(payloads), -1, 8)
+    n = r.shape[1]
+    a = np.tile(np.array(list(ICV.to_bytes(8, "big")), dtype=np.int64), (len(payloads), 1))
+    for j in range(6):
+        for i in range(n):
+            b = np_encrypt_blocks(rk, np.concatenate([a, r[:, i]], axis=1))
+            a, r[:, i] = b[:, :8] ^ np.array(list((n * j + i + 1).to_bytes(8, "big")), dtype=np.int64), b[:, 8:]
+    return [bytes(x.tolist()) + bytes(y.reshape(-1).tolist()) for x, y in zip(a, r)]
 
 
 def compose_unwrap(server, tc, dec_rk, kek_of_key, wrapped):
