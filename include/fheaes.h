@@ -20,6 +20,13 @@
  *     context's stream and NOT synchronised: call fheaes_synchronize()).
  *   - per-call pointers are borrowed for the duration of the call; keys are copied into
  *     HBM by fheaes_upload_keys() and owned by the context (server.rs:32-35 takes keys by value).
+ *     The HOST side arrays of a FHEAES_DEVICE call (key indices, counters, clear blocks and bytes, runs, a mask key) are consumed
+ *     before the call returns -- the tables among them copied into the context's one pinned buffer, from which the stream uploads
+ *     them -- so the caller may change or free them at once; the resident arrays are read and written when the stream gets there.  That pinned buffer is shared by
+ *     the calls of a context: a call that needs it waits (on the host) for the previous upload out of it, not for the kernels
+ *     that read the table.  A call that uploads a second table (XTS, the MAC chains, CCM, CMAC, the key unwrap) therefore waits for
+ *     its own first upload, and so for whatever the stream still has in front of it: it enqueues all its work, but returns only
+ *     when the stream has reached it (tests/test_gpu_async_contract.py, tests/test_gpu_workspace_state.py).
  */
 #ifndef FHEAES_H
 #define FHEAES_H
@@ -791,6 +798,35 @@ int fheaes_k2_park_debug(fheaes_ctx *ctx, const uint32_t *initial_owner, int rec
  * words or NULL; `record_n` receives the number of records, that launch's grid, or 0).  A `record_cap` below it is FHEAES_ERR_INVALID. */
 int fheaes_k2_park_read(fheaes_ctx *ctx, uint64_t *fallbacks, uint64_t *violations, uint32_t *owner_out, uint32_t *record_out,
                         uint64_t record_cap, uint64_t *record_n);
+/* Test hooks of the workspace state (tests/test_gpu_workspace_state.py): no call may depend on what an earlier call left in the scratch
+ * the calls of a context share, on where that scratch lay, or on how large it was.  The FHEAES_WS_BUFFERS scratch buffers are the
+ * grow-only workspaces and the four staging buffers of host-memspace calls; the keys, the twiddles, the LUT sets, the pinned upload
+ * buffer and the parking owner words, pattern and record of fheaes_k2_park_debug / _read (state that persists by design) are not among
+ * them and are never touched.  Every buffer has a class, and a class a fill pattern under which a stale read yields wrong words and
+ * never a wild address:
+ *   FHEAES_WS_F64     only ever doubles                      every double the quiet NaN 0x7FF87FF87FF87FF8
+ *   FHEAES_WS_WORDS   torus words, digits, accumulators      every byte 0xA5
+ *   FHEAES_WS_TABLES  index tables and staged arguments      every 32-bit word 1: as an index entry 1, in range wherever there are two
+ *                                                            of a thing; as a word or a byte non-zero (the last size % 4 bytes: 0xA5)
+ * fheaes_workspace_info: buffer `index` (>= FHEAES_WS_BUFFERS: FHEAES_ERR_INVALID) -- its name, current size in bytes (0: never grown, or
+ * released), class, the 8 bytes at offset 0 and its last whole 8-byte word (offset (bytes / 8 - 1) * 8); a buffer of fewer than 8 bytes
+ * reports its bytes zero-extended in both, an empty one 0.  Any out-pointer may be NULL.  Synchronises the context's stream first.
+ * fheaes_workspace_poison: takes the context's lock and synchronises its stream; FHEAES_WS_POISON_FILL overwrites every buffer over its
+ * whole current size with the pattern of its class (hipMemset*Async on the context's stream, then synchronised: no kernel);
+ * FHEAES_WS_POISON_RELEASE frees every buffer and sets its size to 0, so that the next call grows everything from nothing, as on a fresh
+ * context but without a new key upload.  *bytes_out (may be NULL): the bytes filled or freed.  Any other mode is FHEAES_ERR_INVALID. */
+#define FHEAES_WS_BUFFERS 17
+#define FHEAES_WS_F64 0
+#define FHEAES_WS_WORDS 1
+#define FHEAES_WS_TABLES 2
+#define FHEAES_WS_PATTERN_F64_HALF 0x7FF87FF8u
+#define FHEAES_WS_PATTERN_WORDS 0xA5
+#define FHEAES_WS_PATTERN_TABLES 1u
+#define FHEAES_WS_POISON_FILL 0
+#define FHEAES_WS_POISON_RELEASE 1
+int fheaes_workspace_info(fheaes_ctx *ctx, uint32_t index, char *name_out, size_t name_cap, uint64_t *bytes_out, int *class_out,
+                          uint64_t *first_word_out, uint64_t *last_word_out);
+int fheaes_workspace_poison(fheaes_ctx *ctx, int mode, uint64_t *bytes_out);
 const char *fheaes_version(void);
 
 #ifdef __cplusplus

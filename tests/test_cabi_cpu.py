@@ -59,6 +59,29 @@ def test_park_slot_hooks_reject_a_null_context():
     assert lib.fheaes_k2_park_read(None, None, None, None, None, 0, None) == -1
 
 
+def test_workspace_hooks_and_set_stream_reject_a_null_context():
+    lib = _native.load_library()
+    u64 = ctypes.c_uint64
+    name, nbytes, cls, first, last = ctypes.create_string_buffer(32), u64(), ctypes.c_int(), u64(), u64()
+    for index in (0, _native.WS_BUFFERS - 1, _native.WS_BUFFERS):
+        assert lib.fheaes_workspace_info(None, index, name, len(name), ctypes.byref(nbytes), ctypes.byref(cls), ctypes.byref(first), ctypes.byref(last)) == -1
+    assert lib.fheaes_workspace_info(None, 0, None, 0, None, None, None, None) == -1
+    for mode in (_native.WS_POISON_FILL, _native.WS_POISON_RELEASE, 2, -1):
+        assert lib.fheaes_workspace_poison(None, mode, ctypes.byref(nbytes)) == -1
+    assert lib.fheaes_workspace_poison(None, _native.WS_POISON_FILL, None) == -1
+    assert lib.fheaes_set_stream(None, None) == -1
+    assert lib.fheaes_set_stream(None, ctypes.c_void_p(0x1000)) == -1
+
+
+def test_workspace_constants_of_the_binding_are_the_header_s():
+    text = (_build.ROOT / "include" / "fheaes.h").read_text()
+    defines = dict(line.split()[1:3] for line in text.splitlines() if line.startswith("#define FHEAES_WS_"))
+    assert int(defines["FHEAES_WS_BUFFERS"]) == _native.WS_BUFFERS
+    assert [int(defines["FHEAES_WS_" + c.upper()]) for c in _native.WS_CLASSES] == [0, 1, 2]
+    assert (int(defines["FHEAES_WS_POISON_FILL"]), int(defines["FHEAES_WS_POISON_RELEASE"])) == (_native.WS_POISON_FILL, _native.WS_POISON_RELEASE)
+    assert defines["FHEAES_WS_PATTERN_F64_HALF"] == "0x7FF87FF8u" and defines["FHEAES_WS_PATTERN_WORDS"] == "0xA5" and defines["FHEAES_WS_PATTERN_TABLES"] == "1u"
+
+
 def test_no_gpu_means_failure_not_fallback():
     import torch
 

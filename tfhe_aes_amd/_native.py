@@ -21,6 +21,9 @@ KW_MIN_SEMIBLOCKS, KW_MAX_SEMIBLOCKS, KW_MAX_KEYS = 2, 8, 4096      # FHEAES_KW_
 AES_WINDOW_OFF = 0xFFFFFFFF     # FHEAES_AES_WINDOW_OFF: fheaes_aes_set_window's "one launch per round"
 GATE_LWE, GATE_GLWE = 0, 1       # FHEAES_GATE_*: the input form of fheaes_gate_ggsw
 K2_PARK_SLOTS = 1024            # FHEAES_K2_PARK_SLOTS: owner words of the paired kernel's shared parking slots, 128 per XCC
+WS_BUFFERS = 17                 # FHEAES_WS_BUFFERS: the scratch buffers fheaes_workspace_info lists
+WS_CLASSES = ("f64", "words", "tables")                  # FHEAES_WS_F64 / _WORDS / _TABLES
+WS_POISON_FILL, WS_POISON_RELEASE = 0, 1                 # FHEAES_WS_POISON_*: the modes of fheaes_workspace_poison
 STAGES = ("keyswitch", "blind_rotate", "pfpks", "ggsw_fft", "vertical_packing", "linear")
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -155,6 +158,8 @@ SIGNATURES = {
     "fheaes_aes_set_window": (_c.c_int, [_ctx, _c.c_uint32]),
     "fheaes_k2_park_debug": (_c.c_int, [_ctx, _c.POINTER(_c.c_uint32), _c.c_int]),
     "fheaes_k2_park_read": (_c.c_int, [_ctx, _u64p, _u64p, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32), _c.c_uint64, _u64p]),
+    "fheaes_workspace_info": (_c.c_int, [_ctx, _c.c_uint32, _c.c_char_p, _c.c_size_t, _u64p, _c.POINTER(_c.c_int), _u64p, _u64p]),
+    "fheaes_workspace_poison": (_c.c_int, [_ctx, _c.c_int, _u64p]),
     "fheaes_version": (_c.c_char_p, []),
 }
 
@@ -708,6 +713,23 @@ class Engine:
         self._check(self._lib.fheaes_k2_park_read(self._h, _c.byref(fb), _c.byref(vi), owner.ctypes.data_as(u32p), rec.ctypes.data_as(u32p),
                                                   n.value, _c.byref(n)))
         return {"fallbacks": fb.value, "violations": vi.value, "owner": owner, "record": rec[:n.value]}
+
+    def workspace_info(self) -> list[dict]:
+        """test hook (fheaes_workspace_info): the context's scratch buffers, each {"name", "bytes", "class": one of WS_CLASSES, "first",
+        "last": its first and last 8-byte words}; synchronises the stream"""
+        out = []
+        for i in range(WS_BUFFERS):
+            name, nbytes, cls, first, last = _c.create_string_buffer(32), _c.c_uint64(), _c.c_int(), _c.c_uint64(), _c.c_uint64()
+            self._check(self._lib.fheaes_workspace_info(self._h, i, name, len(name), _c.byref(nbytes), _c.byref(cls), _c.byref(first), _c.byref(last)))
+            out.append({"name": name.value.decode(), "bytes": nbytes.value, "class": WS_CLASSES[cls.value], "first": first.value, "last": last.value})
+        return out
+
+    def workspace_poison(self, mode: int = WS_POISON_FILL) -> int:
+        """test hook (fheaes_workspace_poison): WS_POISON_FILL overwrites every scratch buffer with the pattern of its class,
+        WS_POISON_RELEASE frees them all (the next call grows everything from nothing); returns the bytes filled or freed"""
+        n = _c.c_uint64()
+        self._check(self._lib.fheaes_workspace_poison(self._h, int(mode), _c.byref(n)))
+        return n.value
 
     def read_bsk_fourier(self, i: int) -> np.ndarray:
         p = self.params

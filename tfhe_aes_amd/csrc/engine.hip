@@ -316,6 +316,89 @@ int fheaes_reserve(fheaes_ctx *c, uint64_t max_bits)
     return FHEAES_OK;
 }
 
+// ---- test hooks of the workspace state (tests/test_gpu_workspace_state.py) ----------------------------------------------------
+// The scratch a call may grow, overwrite or free between two other calls: every ws_* buffer but the parking owner words, pattern and
+// record (state: counters and hooks that persist across launches by design), and the four staging buffers.  Keys, twiddles, LUT
+// sets and the pinned buffer are not scratch and are not listed.  The class says what a stale read of the poisoned buffer gives:
+// a NaN (buffers that only ever hold doubles), a wrong word (torus words, digits, accumulators), or -- index tables and staged
+// arguments -- entry 1 of whatever the index selects, which is in range wherever there are two of a thing.
+namespace {
+
+struct WsEntry { const char *name; DevBuf fheaes_ctx::*buf; int stage; int cls; };
+const WsEntry WS_TABLE[FHEAES_WS_BUFFERS] = {
+    {"ws_small", &fheaes_ctx::ws_small, -1, FHEAES_WS_WORDS},   {"ws_pbs", &fheaes_ctx::ws_pbs, -1, FHEAES_WS_WORDS},
+    {"ws_ggsw", &fheaes_ctx::ws_ggsw, -1, FHEAES_WS_WORDS},     {"ws_ggswf", &fheaes_ctx::ws_ggswf, -1, FHEAES_WS_F64},
+    {"ws_vp", &fheaes_ctx::ws_vp, -1, FHEAES_WS_WORDS},         {"ws_tmp_a", &fheaes_ctx::ws_tmp_a, -1, FHEAES_WS_WORDS},
+    {"ws_tmp_b", &fheaes_ctx::ws_tmp_b, -1, FHEAES_WS_WORDS},   {"ws_tmp_c", &fheaes_ctx::ws_tmp_c, -1, FHEAES_WS_WORDS},
+    {"ws_luts", &fheaes_ctx::ws_luts, -1, FHEAES_WS_WORDS},     {"ws_misc", &fheaes_ctx::ws_misc, -1, FHEAES_WS_TABLES},
+    {"ws_digits", &fheaes_ctx::ws_digits, -1, FHEAES_WS_WORDS}, {"ws_park", &fheaes_ctx::ws_park, -1, FHEAES_WS_WORDS},
+    {"ws_tree", &fheaes_ctx::ws_tree, -1, FHEAES_WS_WORDS},
+    {"stage[0]", nullptr, 0, FHEAES_WS_TABLES}, {"stage[1]", nullptr, 1, FHEAES_WS_TABLES},
+    {"stage[2]", nullptr, 2, FHEAES_WS_TABLES}, {"stage[3]", nullptr, 3, FHEAES_WS_TABLES},
+};
+DevBuf *ws_buf(fheaes_ctx *c, const WsEntry &e) { return e.stage >= 0 ? &c->stage[e.stage] : &(c->*(e.buf)); }
+
+}  // namespace
+
+int fheaes_workspace_info(fheaes_ctx *c, uint32_t index, char *name_out, size_t name_cap, uint64_t *bytes_out, int *class_out,
+                          uint64_t *first_word_out, uint64_t *last_word_out)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    if (index >= FHEAES_WS_BUFFERS) return c->fail(FHEAES_ERR_INVALID, "workspace_info: index %u, the context has %d scratch buffers", index, FHEAES_WS_BUFFERS);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const WsEntry &e = WS_TABLE[index];
+    const DevBuf &b = *ws_buf(c, e);
+    if (name_out && name_cap) { std::strncpy(name_out, e.name, name_cap - 1); name_out[name_cap - 1] = 0; }
+    if (bytes_out) *bytes_out = b.bytes;
+    if (class_out) *class_out = e.cls;
+    // the 8 bytes at offset 0 and the last whole 8-byte word at an aligned offset; a buffer of fewer than 8 bytes: its bytes, zero-extended
+    uint64_t first = 0, last = 0;
+    if (b.p && b.bytes) {
+        const size_t take = std::min<size_t>(8, b.bytes), last_off = b.bytes >= 8 ? (b.bytes / 8 - 1) * 8 : 0;
+        if (first_word_out) HIP_TRY(c, hipMemcpy(&first, b.p, take, hipMemcpyDeviceToHost));
+        if (last_word_out) HIP_TRY(c, hipMemcpy(&last, (const char *)b.p + last_off, take, hipMemcpyDeviceToHost));
+    }
+    if (first_word_out) *first_word_out = first;
+    if (last_word_out) *last_word_out = last;
+    return FHEAES_OK;
+}
+
+int fheaes_workspace_poison(fheaes_ctx *c, int mode, uint64_t *bytes_out)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    if (mode != FHEAES_WS_POISON_FILL && mode != FHEAES_WS_POISON_RELEASE)
+        return c->fail(FHEAES_ERR_INVALID, "workspace_poison: mode must be FHEAES_WS_POISON_FILL (0) or FHEAES_WS_POISON_RELEASE (1), got %d", mode);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint64_t total = 0;
+    for (const WsEntry &e : WS_TABLE) {
+        DevBuf &b = *ws_buf(c, e);
+        if (!b.p || !b.bytes) continue;
+        total += b.bytes;
+        if (mode == FHEAES_WS_POISON_RELEASE) {
+            HIP_TRY(c, hipFree(b.p));
+            b.p = nullptr; b.bytes = 0;
+            continue;
+        }
+        const size_t words = b.bytes / 4, tail = b.bytes % 4;
+        if (e.cls == FHEAES_WS_WORDS) {
+            HIP_TRY(c, hipMemsetAsync(b.p, FHEAES_WS_PATTERN_WORDS, b.bytes, c->stream));
+            continue;
+        }
+        // 32-bit fills: a quiet NaN whose two halves are equal, or the index 1; what is left of a size that is no multiple of 4 gets
+        // the words' byte (a double buffer has none; a table's last bytes are read as bytes only, and must not be zero)
+        const uint32_t v = e.cls == FHEAES_WS_F64 ? FHEAES_WS_PATTERN_F64_HALF : FHEAES_WS_PATTERN_TABLES;
+        if (words) HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)b.p, (int)v, words, c->stream));
+        if (tail) HIP_TRY(c, hipMemsetAsync((char *)b.p + words * 4, FHEAES_WS_PATTERN_WORDS, tail, c->stream));
+    }
+    if (mode == FHEAES_WS_POISON_FILL) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (bytes_out) *bytes_out = total;
+    return FHEAES_OK;
+}
+
 // Both uploads end in the same three conversions of the standard-domain words staged in HBM: KSK / PFPKSK -> balanced int8
 // byte planes in MFMA fragment order, BSK -> Fourier.  `seeded`: the caller passed bodies only and the masks are
 // regenerated on the GPU from the public 256-bit mask key (ChaCha20 stream of csrc/client.c) -- 0.19 GB over PCIe / xGMI

@@ -619,6 +619,8 @@ class Server:
 
                 torch.cuda.current_stream(enc_all.device).synchronize()       # torch filled it on its stream; the engine reads it on its own
         self.engine.aes_cbc_mac_keyed(words, bits, n_keys, keys, lens, clear, enc_all, enc_bytes if any_enc else None, init, out, packed=packed)
+        if enc_all is not None and not isinstance(enc_all, np.ndarray):
+            self._inflight.append(enc_all)            # device call: only enqueued, the gathered addends are still to be read
         return out
 
     def aes_ccm_decrypt(self, round_keys, messages, out=None, valid_out=None, gate: bool = False):
