@@ -83,10 +83,10 @@ def compose_mac(srv, client, rk, streams, init=None):
     return out
 
 
-def compose(srv, client, rk, messages):
-    """fheaes_aes_ccm_open_keyed out of older calls, on host arrays: per message the public call over [B0, Ctr_0, Ctr_1..Ctr_m] with data
+def compose_chain(srv, client, rk, messages):
+    """the first half of compose, on host arrays: per message the public call over [B0, Ctr_0, Ctr_1..Ctr_m] with data
     [none, none, C_1..C_m]; the chain from X_1 over the AAD blocks, then the payload blocks with P as the encrypted addend (the last with
-    its real bytes); diff = X + S0 + trivial(tag) on 8t rows; the two WoPBS.  Returns (plaintext, valid, block_of_message)."""
+    its real bytes).  Returns (X [n][16][8][kN+1], S0 as a list of [16][8][kN+1], the plaintext blocks per message, block_of_message)."""
     lw = client.params.big1
     keys, blocks, data, where = [], [], [], []
     for key_index, nonce, aad, ct, tag in messages:
@@ -109,7 +109,14 @@ def compose(srv, client, rk, messages):
             p[i].reshape(128, lw)[8 * real[i]:] = 0
         plain.append(p)
         at.append(at[-1] + m)
-    x = compose_mac(srv, client, rk, streams, init=np.stack(init))
+    return compose_mac(srv, client, rk, streams, init=np.stack(init)), s0, plain, at
+
+
+def compose(srv, client, rk, messages):
+    """fheaes_aes_ccm_open_keyed out of older calls, on host arrays: compose_chain; diff = X + S0 + trivial(tag) on 8t rows; the two
+    WoPBS.  Returns (plaintext, valid, block_of_message)."""
+    lw = client.params.big1
+    x, s0, plain, at = compose_chain(srv, client, rk, messages)
     n = len(messages)
     diff = np.zeros((n, 128, lw), dtype=np.uint64)
     for s, (_, _, _, _, tag) in enumerate(messages):
@@ -120,6 +127,17 @@ def compose(srv, client, rk, messages):
     w1 = srv.many_wopbs_without_padding(diff.reshape(16 * n, 8, lw), [ne0])
     w2 = srv.many_wopbs_without_padding(np.ascontiguousarray(w1[:, 0, 0, :]).reshape(n, 16, lw), [eq0])
     return np.concatenate(plain) if at[-1] else np.zeros((0, 16, 8, lw), dtype=np.uint64), np.ascontiguousarray(w2[:, 0, 0, :]), at
+
+
+def tag_difference(srv, client, rk, messages):
+    """What the first tag WoPBS decides on, for messages whose tags have 16 bytes: X + S0 + trivial(tag), [n][16][8][kN+1], summed by
+    the link kernel (Engine.mac_link) on compose_chain's outputs.  A right tag makes every word an encryption of 0."""
+    assert all(len(m[4]) == 16 for m in messages)
+    x, s0, _, _ = compose_chain(srv, client, rk, messages)
+    n = len(messages)
+    diff = np.ascontiguousarray(x)
+    srv.engine.mac_link(diff, False, None, np.stack(s0), list(range(n)), [16] * n, [list(m[4]) for m in messages])
+    return diff
 
 
 def plaintext_of(client, plaintext, at, messages):

@@ -241,7 +241,10 @@ class NoiseModel:
         the trivial LUT polynomials (first_cmux) is LEFT OUT: its differences are 0 or 2^63 in the body and 0 in the masks, exact on the
         gadget's grid, so it has no rounding term, and its other two terms are below wopbs_left_out().  So
             (width - 1) cmux(0)  +  popcount(x without that bit) (cmux(1) - cmux(0)).
-        The result depends on x: the gadget's rounding enters only where the GGSW holds a 1."""
+        The result depends on x: the gadget's rounding enters only where the GGSW holds a 1.
+        It holds for an output row whose table is NOT constant.  Where every entry of a row is 0 (rows 1..15 of the tag check's 16-bit
+        LUT, ccm.tag_luts) all LUT polynomials are zero, every CMUX difference is zero, its digits are zero and the transform of zeros
+        is zero: the output is the exact zero ciphertext, mask and body, with no error at all.  Such rows sit outside the model."""
         x = np.asarray(x, dtype=np.int64)
         keep = x & ~np.int64(1 << self.first_cmux(width))
         ones = np.zeros(x.shape, dtype=np.float64)
@@ -284,7 +287,8 @@ class NoiseModel:
         h = lambda v: 0.5 * math.log2(v)
         return {"k1": h(self.k1()), "modswitch": h(self.modswitch()), "extprod0": h(self.extprod(0)), "extprod1": h(self.extprod(1)),
                 "k2": h(self.k2()), "pfks": h(self.pfks()), "k3_carried": h(self.k3_carried()), "cmux0": h(self.cmux(0)),
-                "cmux1": h(self.cmux(1)), "wopbs8": h(self.wopbs_mean(8)), "aes_out": h(2 * self.wopbs_mean(8))}
+                "cmux1": h(self.cmux(1)), "wopbs8": h(self.wopbs_mean(8)), "aes_out": h(2 * self.wopbs_mean(8)),
+                "wopbs16": h(self.wopbs_mean(16)), "wopbs16_x0": h(self.wopbs(16, 0))}
 
 
 # ---- the checker --------------------------------------------------------------------------------------------------------------------------
@@ -379,6 +383,20 @@ def aes_output_variance(model, key, ciphertexts):
     ct = np.array([u128_to_bytes(v) for v in ciphertexts], dtype=np.int64)
     inv = np.array(aes_clear.INV_SBOX, dtype=np.int64)
     return (model.wopbs(8, inv[ct ^ w]) + model.wopbs(8, w)[None, :])[:, :, None]
+
+
+def tag_difference_variance(model, key, x, s0):
+    """[16][1]: the variance of every word of byte p of X + S0 + trivial(tag), what the first WoPBS of a tag check decides on; x, s0 the
+    clear 128-bit values.  X and S0 are cipher outputs under ONE key, each a fresh S-Box output plus the word of the last round key at
+    its position (aes_output_variance) -- and that round-key word is the same ciphertext in both, so the sum carries its error twice:
+    e_X + e_S0 + 2 e_rk, variance V_X + V_S0 + 4 V_rk.  That is the two aes_output_variance sums, which count V_rk once each, plus
+    2 V_rk; the trivial tag adds nothing.  The message survives (2 bit 2^63 = 0), the doubled error does not cancel.  Returns (the
+    variance, the two sums alone): the oracle leaves the band of the second at PARAM_TOY (test_noise_model_cpu.py: 1.59 over 1,024 words)."""
+    from tfhe_aes_amd import aes_clear
+
+    w = np.array(aes_clear.expand_key(key)[-1], dtype=np.int64)
+    two_sums = aes_output_variance(model, key, [x])[0] + aes_output_variance(model, key, [s0])[0]
+    return two_sums + 2.0 * model.wopbs(8, w)[:, None], two_sums
 
 
 def k3_errors(client, ggsw_rows, bits):

@@ -1,13 +1,14 @@
 """CBC-MAC chains and AES-CCM decryption on the MI355X.  The link kernel alone (fheaes_mac_link) on edge words inside guard rows against
 numpy; fheaes_aes_cbc_mac_keyed and fheaes_aes_ccm_open_keyed word for word against ccm.compose_mac / ccm.compose -- entry points older
 than the two calls -- so every comparison is array_equal; plaintexts, MACs and validity bits from aes_clear and the SP 800-38C / RFC 3610
-vectors.  The noise of a MAC word is held to tests/noise_model.py."""
+vectors.  The noise of a MAC word is held to tests/noise_model.py.  The last section runs one call at PARAM_OPT: the verdicts, the
+plaintexts, the gated form, the composition word for word, and the noise of the tag difference that the first tag WoPBS decides on."""
 import numpy as np
 import pytest
 
 import ccm
 import noise_model as nm
-from gpu_support import SENTINEL, dev, guarded, guards_intact, host, settled, tc, toy_server  # noqa: F401
+from gpu_support import SENTINEL, dev, guarded, guards_intact, host, oc, opt_server, settled, tc, toy_server  # noqa: F401
 from tfhe_aes_amd import _native, aes_clear
 from tfhe_aes_amd.server import Server, ServerGroup
 
@@ -352,3 +353,88 @@ def test_toy_errors_leave_the_outputs_untouched(toy, toy_server, tc, keys):
         assert e.value.code == -2
     finally:
         fresh.close()
+
+
+# ---- one call at PARAM_OPT -------------------------------------------------------------------------------------------------------------------
+# The `valid` bit is the one result a caller cannot check after decryption, and PARAM_OPT is where the guard's limit of 5 and the decision
+# in front of K2 carry weight (34.6 sigma for a five-term sum; PARAM_TOY's noise is 2^-30 / 2^-50 and decides nothing).
+OPT_VALID = [1, 1, 1, 0]
+
+
+def _opt_messages():
+    """examples 1 and 2 under their key, the RFC vector under its key, and example 1 again with one bit of its tag flipped"""
+    k, nonce, aad, ct, tag = ccm.message(0, "ex1")
+    return [ccm.message(0, "ex1"), ccm.message(0, "ex2"), ccm.message(1, "rfc1"), (k, nonce, aad, ct, tag[:3] + bytes([tag[3] ^ 0x01]))]
+
+
+@pytest.fixture(scope="module")
+def opt_keys(opt_server, oc):
+    return opt_server.aes_key_expansion_many(np.stack([oc.encrypt_aes_key(k) for k in (KEY_A, KEY_B)]))
+
+
+def opt_case(opt_server, opt_keys):
+    if "opt" not in _results:
+        _results["opt"] = opt_server.aes_ccm_decrypt(opt_keys, _opt_messages())
+    return _results["opt"]
+
+
+def test_opt_ccm_verdicts_plaintexts_and_the_composition(opt, opt_server, oc, opt_keys):
+    p = opt.params
+    messages = _opt_messages()
+    pt, ok, at = opt_case(opt_server, opt_keys)
+    assert at == [0, 1, 2, 4, 5] and pt.shape == (5, 16, 8, p.big1) and ok.shape == (4, p.big1)
+    assert oc.decrypt_bits(ok).tolist() == OPT_VALID
+    assert ccm.plaintext_of(oc, pt, at, messages) == [ccm.VECTORS[v][3] for v in ("ex1", "ex2", "rfc1", "ex1")]
+    want_pt, want_ok, want_at = ccm.compose(opt_server, oc, opt_keys, messages)
+    assert want_at == at
+    assert np.array_equal(pt, want_pt), "%d plaintext words differ" % int((pt != want_pt).sum())
+    assert np.array_equal(ok, want_ok), "%d valid words differ" % int((ok != want_ok).sum())
+
+
+def test_opt_ccm_gated(opt, opt_server, oc, opt_keys):
+    """gate=True: the forged message's plaintext decrypts to zero bytes, the other three as before, `valid` word for word what it was"""
+    messages = _opt_messages()
+    pt, ok, at = opt_case(opt_server, opt_keys)
+    g_pt, g_ok, g_at = opt_server.aes_ccm_decrypt(opt_keys, messages, gate=True)
+    assert g_at == at and np.array_equal(g_ok, ok) and oc.decrypt_bits(g_ok).tolist() == OPT_VALID
+    assert ccm.plaintext_of(oc, g_pt, at, messages) == [ccm.VECTORS["ex1"][3], ccm.VECTORS["ex2"][3], ccm.VECTORS["rfc1"][3], bytes(4)]
+    assert not oc.decrypt_bytes(g_pt[at[3]:]).any()
+    assert ccm.plaintext_of(oc, pt, at, messages)[3] == ccm.VECTORS["ex1"][3]                     # ungated: it was there
+
+
+def test_opt_noise_levels(opt, oc):
+    """the payload link's X (2) + P (2) + the round key = 5 is the guard's limit at the parameter set the limit was made for"""
+    srv = Server(opt.keys, device=0)
+    try:
+        assert srv.engine.noise_level_seen() == (0, 5)
+        rk = srv.aes_key_expansion_many(np.stack([oc.encrypt_aes_key(KEY_A)]))
+        _, ok, _ = srv.aes_ccm_decrypt(rk, [ccm.message(0, "ex1")])
+        assert srv.engine.noise_level_seen() == (5, 5)
+    finally:
+        srv.engine.close()
+    assert oc.decrypt_bits(ok).tolist() == [1]
+
+
+def test_opt_tag_difference_noise(opt, opt_server, oc):
+    """What the first tag WoPBS decides on, X + S0 + tag (level 4), for four messages with 16-byte tags under four keys: 64 bytes, no
+    round-key word shared between two messages; the outputs of one byte share its GGSWs, so the bytes are counted (64).  The variance
+    is noise_model.tag_difference_variance: the two aes_output_variance sums and the round-key word's term twice more, because X and
+    S0 of one message add the SAME round-key ciphertext.  Every WoPBS term leaves its first CMUX out; the round key's is carried
+    twice, so the bound of what is left out is (1 + 1 + 4) wopbs_left_out().  The ratio against the two sums alone is printed."""
+    M = nm.NoiseModel.of_client(opt.client)
+    ks = [bytes(np.random.default_rng(0xCC70 + i).integers(0, 256, 16, dtype=np.uint8).tolist()) for i in range(4)]
+    rk = opt_server.aes_key_expansion_many(np.stack([oc.encrypt_aes_key(k) for k in ks]))
+    messages = [ccm.own_message(i, ks[i], ccm.run(0x10 + i, 13), b"", ccm.run(0x20 + 16 * i, 16), 16) for i in range(4)]
+    diff = ccm.tag_difference(opt_server, oc, rk, messages)
+    err, vals = nm.wopbs_error(oc, diff)
+    assert not vals.any()                                                                         # the tags are right: X + S0 + tag = 0
+    var, two_sums = [], []
+    for (k, nonce, aad, ct, tag), key in zip(messages, ks):
+        s0 = aes_clear.aes_encrypt_block(key, aes_clear.ccm_blocks(nonce, aad, len(ct), 16)[2][0])
+        v, t = nm.tag_difference_variance(M, key, _u128(tag) ^ s0, s0)
+        var.append(v); two_sums.append(t)
+    var, two_sums = np.stack(var), np.stack(two_sums)
+    print("tag difference opt: mean(err^2) over the two aes_output_variance sums alone: %.3f" % float(np.mean(err.astype(np.float64) ** 2 / two_sums)))
+    n = M.wopbs_independent(64, 8)
+    assert n == 64 and err.shape == (4, 16, 8) and nm.rejects_doubling(n)
+    nm.assert_noise(err, var, n, "tag difference opt", left_out=6 * M.wopbs_left_out())

@@ -1,13 +1,14 @@
 """AES-CMAC on the MI355X.  The subkey gather alone (fheaes_cmac_double) on edge words inside guard rows against numpy sums over
 fheaes_cmac_subkey_row; fheaes_aes_cmac_subkeys_keyed and fheaes_aes_cmac_keyed word for word against cmac.compose_subkeys,
 ccm.compose_mac and cmac.compose_verify -- entry points older than the calls, plus the gather -- so every comparison is array_equal;
-subkeys, tags and validity bits from aes_clear and the SP 800-38B / RFC 4493 vectors."""
+subkeys, tags and validity bits from aes_clear and the SP 800-38B / RFC 4493 vectors.  The last section runs the subkeys, the tags and
+the tag check once at PARAM_OPT, and holds the noise of a MAC word there to tests/noise_model.py."""
 import numpy as np
 import pytest
 
 import ccm
 import cmac
-from gpu_support import SENTINEL, dev, guarded, guards_intact, host, settled, tc, toy_server  # noqa: F401
+from gpu_support import SENTINEL, dev, guarded, guards_intact, host, oc, opt_server, settled, tc, toy_server  # noqa: F401
 from tfhe_aes_amd import _native, aes_clear
 from tfhe_aes_amd.server import Server, ServerGroup
 
@@ -269,3 +270,62 @@ def test_toy_errors_leave_the_outputs_untouched(toy, toy_server, tc, keys):
         assert e.value.code == -2
     finally:
         fresh.close()
+
+
+# ---- one call at PARAM_OPT -------------------------------------------------------------------------------------------------------------------
+def _flip(data, i, bit=0x01):
+    return data[:i] + bytes([data[i] ^ bit]) + data[i + 1:]
+
+
+@pytest.fixture(scope="module")
+def opt_keys(opt_server, oc):
+    """round keys of the RFC 4493 key and of the SP 800-38B AES-256 key, and the subkeys of the first"""
+    many = lambda k: opt_server.aes_key_expansion_many(np.stack([oc.encrypt_aes_key(k)]))
+    rk = many(KEY_V)
+    return {"128": rk, "256": many(cmac.VECTORS[256][0]), "sub": opt_server.aes_cmac_subkeys(rk)}
+
+
+def test_opt_subkeys_and_tags_are_the_vectors(opt, opt_server, oc, opt_keys):
+    """the subkeys against the doubling in GF(2^128); the four RFC 4493 messages (0, 16, 40 and 64 bytes: K2, K1, K2, K1, chains of 1 to
+    4 steps) in one call under the AES-128 key, and the 40-byte message under the AES-256 key"""
+    _, k1, k2, tags = cmac.VECTORS[128]
+    l = aes_clear.aes_encrypt_block(KEY_V, 0)
+    assert l == _u128(cmac.L_128)
+    assert [_u128(b) for b in _dec_blocks(oc, opt_keys["sub"])] == [cmac.double(l), cmac.double(l, 2)] == [_u128(k1), _u128(k2)]
+    got = opt_server.aes_cmac_streams(opt_keys["128"], [(0, cmac.MESSAGE[:n]) for n in cmac.LENGTHS], subkeys=opt_keys["sub"])
+    assert got.shape == (4, 16, 8, opt.params.big1)
+    assert _dec_blocks(oc, got) == list(tags)
+    got256 = opt_server.aes_cmac_streams(opt_keys["256"], [(0, cmac.MESSAGE[:40])])                # its subkeys derived in the call
+    assert _dec_blocks(oc, got256) == [cmac.VECTORS[256][3][2]]
+
+
+def test_opt_verification(opt, opt_server, oc, opt_keys):
+    """the four messages with their full tags, one tag cut to 4 bytes, and one whose last compared bit is flipped"""
+    tags = cmac.VECTORS[128][3]
+    messages = [(0, cmac.MESSAGE[:n], t) for n, t in zip(cmac.LENGTHS, tags)]
+    messages += [(0, cmac.MESSAGE[:40], tags[2][:4]), (0, cmac.MESSAGE[:16], _flip(tags[1], 15, 0x01))]
+    want_bits = [1, 1, 1, 1, 1, 0]
+    assert [int(aes_clear.cmac_verify(KEY_V, msg, t)) for _, msg, t in messages] == want_bits
+    ok = opt_server.aes_cmac_verify(opt_keys["128"], messages, subkeys=opt_keys["sub"])
+    assert ok.shape == (6, opt.params.big1) and oc.decrypt_bits(ok).tolist() == want_bits
+    want = cmac.compose_verify(opt_server, oc, opt_keys["128"], messages, opt_keys["sub"])
+    assert np.array_equal(ok, want), "%d valid words differ" % int((ok != want).sum())
+
+
+def test_opt_mac_output_noise(opt, opt_server, oc):
+    """test_gpu_ccm.py::test_toy_mac_output_noise at PARAM_OPT: four one-block streams under four keys, 64 bytes, no round-key word
+    shared.  The words of one byte share its GGSWs, whose carried errors lead at PARAM_OPT, so the bytes are counted: 64."""
+    import noise_model as nm
+
+    M = nm.NoiseModel.of_client(opt.client)
+    ks = [bytes(np.random.default_rng(0xACE0 + i).integers(0, 256, 16, dtype=np.uint8).tolist()) for i in range(4)]
+    rk = opt_server.aes_key_expansion_many(np.stack([oc.encrypt_aes_key(k) for k in ks]))
+    blocks = [0x0123456789ABCDEF << (16 * i) for i in range(4)]
+    got = opt_server.aes_cbc_mac_streams(rk, [(i, [blocks[i]]) for i in range(4)])
+    want = [aes_clear.cbc_mac(ks[i], [blocks[i]]) for i in range(4)]
+    err, vals = nm.wopbs_error(oc, got)
+    assert [_u128(bytes(b.tolist())) for b in vals] == want
+    var = np.concatenate([nm.aes_output_variance(M, ks[i], [want[i]]) for i in range(4)])
+    n = M.wopbs_independent(64, 8)
+    assert n == 64 and err.size == 512 and nm.rejects_doubling(n)
+    nm.assert_noise(err, var, n, "CMAC output opt", left_out=2 * M.wopbs_left_out())

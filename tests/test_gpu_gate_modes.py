@@ -1,13 +1,14 @@
 """gate=True on the MI355X at PARAM_TOY: aes_ccm_decrypt, aes_key_unwrap and aes_key_unwrap_packed release a plaintext or a key only
 under its own `valid` bit.  The words are Server.gate applied to the gate=False result, a forged message's plaintext and a tampered
 blob's key decrypt to zeros, `valid` is what it was, and a ServerGroup of two contexts gives the same words.  That gate=False writes
-what it always wrote is the older tests' business (test_gpu_ccm.py, test_gpu_keywrap.py)."""
+what it always wrote is the older tests' business (test_gpu_ccm.py, test_gpu_keywrap.py).  The last test runs the gated key unwrap
+once at PARAM_OPT."""
 import numpy as np
 import pytest
 
 import ccm
 import keywrap
-from gpu_support import dev, guarded, guards_intact, host, tc, toy_server  # noqa: F401
+from gpu_support import dev, guarded, guards_intact, host, oc, opt_server, tc, toy_server  # noqa: F401
 from tfhe_aes_amd import aes_clear
 from tfhe_aes_amd.server import ServerGroup
 
@@ -94,3 +95,20 @@ def test_unwrapped_keys_are_gated_on_valid(toy, toy_server, tc):
     assert np.array_equal(q_store.data, store.data) and np.array_equal(q_sok, ok)
     assert np.array_equal(q_packed, toy_server.gate_packed(want_store.data, ok))
     assert not tc.decrypt_packed_bytes(q_packed[1], 11 * 16).any()                                # the second store entry, gated away whole
+
+
+# ---- one call at PARAM_OPT -------------------------------------------------------------------------------------------------------------------
+def test_opt_unwrapped_keys_are_gated_on_valid(opt, opt_server, oc):
+    """RFC 3394 vector 4.1 and a copy with one bit flipped, gate=True on resident tensors (the ungated call: test_gpu_keywrap.py; CCM's
+    gated form at PARAM_OPT: test_gpu_ccm.py).  The gate's circuit bootstrap decides on `valid`, a 16-bit WoPBS output."""
+    kek, payload, right = V41
+    bad = _flip(right, 23, 0x80)
+    assert [int(aes_clear.key_unwrap(kek, w)[0]) for w in (right, bad)] == [1, 0]
+    d_rk = opt_server.aes_key_expansion(dev(oc.encrypt_aes_key(kek)))
+    d_dw = opt_server.aes_decryption_round_keys(d_rk)
+    keys, valid = opt_server.aes_key_unwrap(d_dw, [right, bad], gate=True)
+    opt_server.synchronize()
+    assert keys.is_cuda and tuple(keys.shape) == (2, 16, 8, opt.params.big1)
+    assert oc.decrypt_bits(host(valid)).tolist() == [1, 0]
+    assert [bytes(k.tolist()) for k in oc.decrypt_bytes(host(keys))] == [payload, bytes(16)]
+    assert aes_clear.key_unwrap(kek, bad)[1] != bytes(16)                                         # ungated, a key would be there

@@ -18,6 +18,9 @@ Each shape is ONE launch into rows [2 : 2 + m] of a sentinel-filled device tenso
 The same guard rows for the ragged tiles of K1, K3, K4, K5 and the CMUX tree, against what the same call returns through host arrays
 (which test_gpu_stages.py and test_gpu_aes.py pin against the oracle).
 
+The CMUX tree at k = 4 (cmux_level_kernel<5,15,3>) at the depths the tag check runs, 12, 13 and 16 bits, inside guard rows and word for
+word against the oracle (opt.oracle.wopbs_batch): the last section.
+
 Wall time on an MI355X (pytest --durations=0): NOT MEASURED YET, see DESIGN.md section 5, "Launch shapes and fallback forms under test".
 """
 import numpy as np
@@ -279,3 +282,67 @@ def test_cmux_tree_11bit_stays_inside_its_output(opt):
     E.wopbs_batch(dev(x), 2, nb, dev(luts), 1, False, out)
     E.synchronize()
     assert guards_intact(buf) and np.array_equal(host(out), want) and want.any()
+
+
+# ---- the CMUX tree at k = 4, word for word against the oracle ----------------------------------------------------------------------------
+# cmux_level_kernel<5,15,3> at every depth the product uses: a job is (instance, node), a workgroup carries R = 3 of them, an inner
+# level reads ((inst * 2 nodes_out + 2 node) * K1 + p) * N of one half of ws_tree and writes the other, and the root is handed to
+# vertical_packing_kernel<5,15,3> from the half the last level wrote.  Two inputs per case, chosen so that together they take both
+# branches at every tree level; Engine.wopbs_batch on device tensors inside guard rows; every word against opt.oracle.wopbs_batch.
+def _random_table_lut(width, seed):
+    from tfhe_aes_amd.server import gen_lut
+
+    table = np.random.default_rng(seed).integers(0, 1 << width, 1 << width)
+    return table, gen_lut(2, 1, 512, width, lambda v: int(table[v]))
+
+
+def _cmux_tree_case(opt, width, vals, luts, per_input, fs):
+    """luts [n_sets][n_luts][width][2^width]; fs[set][lut]: the clear functions.  Returns the engine's words [2][n_luts][width][kN+1]."""
+    p, E, c = opt.params, opt.engine(), opt.client
+    high = ((1 << width) - 1) & ~0x1FF
+    assert (vals[0] ^ vals[1]) & high == high                              # the two inputs differ in every bit that drives a tree level
+    n_luts = luts.shape[1]
+    x = c.encrypt_bits(np.array([[(v >> j) & 1 for j in range(width)] for v in vals], dtype=np.uint8))
+    rows = 2 * n_luts * width
+    buf, out = guarded(rows, p.big1)
+    E.wopbs_batch(dev(x), 2, width, dev(luts if per_input else luts[0]), n_luts, per_input, out)
+    E.synchronize()
+    got = host(out).reshape(2, n_luts, width, p.big1)
+    assert guards_intact(buf)
+    want = opt.oracle.wopbs_batch(x, luts if per_input else luts[0], lut_per_input=per_input)
+    diff = np.argwhere((got != want).any(axis=-1))
+    assert diff.size == 0, "%d words differ, first at (input, LUT, output bit) %s" % (int((got != want).sum()), diff[0].tolist())
+    dec = c.decrypt_bits(got)
+    for i, v in enumerate(vals):
+        for li in range(n_luts):
+            assert int(sum(int(dec[i, li, j]) << j for j in range(width))) == fs[i if per_input else 0][li](v), (v, li)
+    return got
+
+
+# width, n_luts, per input, the two inputs.  Jobs per input and level: 12 bits 48, 24, 12 (whole workgroups, root in half 0); with two
+# LUTs 96, 48, 24 and the leaves read set = input; 13 bits 104, 52, 26, 13 (ragged at every level, root in half 1); 16 bits 1,024 ..
+# 16 over 7 levels, all ragged, root in half 0.
+@pytest.mark.parametrize("width,n_luts,per_input,vals", [(12, 1, False, (0xBA5, 0x5C2)), (12, 2, True, (0x3A5, 0xDC2)), (13, 1, False, (0x15A5, 0x0BC2)),
+                                                         (16, 1, False, (0xA5A5, 0x5BC2))])
+def test_cmux_tree_at_k4_is_the_oracle(opt, width, n_luts, per_input, vals):
+    sets = []
+    for s in range(2 if per_input else 1):
+        sets.append([_random_table_lut(width, 0x7EE0 + 64 * width + 8 * s + li) for li in range(n_luts)])
+    luts = np.stack([np.stack([lut for _, lut in one]) for one in sets])
+    for one in sets:
+        for table, _ in one:
+            assert all(len(set(((table >> j) & 1).tolist())) == 2 for j in range(width))       # no constant output row
+    fs = [[lambda v, t=table: int(t[v]) for table, _ in one] for one in sets]
+    got = _cmux_tree_case(opt, width, vals, luts, per_input, fs)
+    assert got.any(axis=-1).all()
+
+
+def test_cmux_tree_16bit_tag_lut_at_k4_is_the_oracle(opt):
+    """the engine's own 16-bit LUT (tag_check_dev's second WoPBS: input == 0) on 0 and 0xFFFF, branch 0 and branch 1 at all 7 levels,
+    the verdicts 1 and 0.  Output rows 1..15 of that LUT are constant zero: their ciphertexts are exact zero words."""
+    import ccm
+
+    eq0 = ccm.tag_luts()[1]
+    assert eq0.shape == (16, 1 << 16) and eq0[0].any() and not eq0[1:].any()
+    got = _cmux_tree_case(opt, 16, (0, 0xFFFF), eq0[None, None], False, [[lambda v: int(v == 0)]])
+    assert got[:, 0, 0].any(axis=-1).all() and not got[:, 0, 1:].any()

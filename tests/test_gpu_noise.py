@@ -116,21 +116,58 @@ def test_wopbs_sweep(which, name, request):
     nm.assert_noise(err, M.wopbs(8, np.arange(256))[:, None, None], n, "WoPBS %s, %s" % (which, name), left_out=M.wopbs_left_out())
 
 
+def wide_outputs(srv, c, width, inputs, table=None, lut=None):
+    """`inputs` values of `width` bits, 0 and 2^width - 1 among them, through one LUT: a random table whose every output row is
+    non-constant (the default), or `lut` with its clear `table`: (errors [inputs][1][width], the inputs, the output words)"""
+    rng = np.random.default_rng(width)
+    if lut is None:
+        table = rng.integers(0, 1 << width, 1 << width)
+        lut = gen_lut(2, 1, 512, width, lambda v: int(table[v]))
+    vals = rng.integers(0, 1 << width, inputs)
+    vals[:2] = (0, (1 << width) - 1)
+    bits = ((vals[:, None] >> np.arange(width)) & 1).astype(np.uint8)
+    out = srv.many_wopbs_without_padding(c.encrypt_bits(bits), [lut])
+    err, got = nm.wopbs_error(c, out)
+    assert got[:, 0].tolist() == np.asarray(table)[vals].tolist()
+    return err, vals, out
+
+
 @pytest.mark.parametrize("width", [10, 12])
 def test_wide_inputs(toy, toy_server, tc, width):
     """wider than log2 N: the CMUXes of the tree count, and the CMUX on the trivial LUT polynomials is the tree's first"""
     M = model_of(toy)
-    rng = np.random.default_rng(width)
-    table = rng.integers(0, 1 << width, 1 << width)
-    vals = rng.integers(0, 1 << width, 32)
-    vals[:2] = (0, (1 << width) - 1)
-    bits = ((vals[:, None] >> np.arange(width)) & 1).astype(np.uint8)
-    lut = gen_lut(2, 1, 512, width, lambda v: int(table[v]))
-    err, got = nm.wopbs_error(tc, toy_server.many_wopbs_without_padding(tc.encrypt_bits(bits), [lut]))
-    assert got[:, 0].tolist() == table[vals].tolist()
+    err, vals, _ = wide_outputs(toy_server, tc, width, 32)
     n = M.wopbs_independent(32, width, width)
     assert n == 32 * width and nm.rejects_doubling(n)
     nm.assert_noise(err, M.wopbs(width, vals)[:, None, None], n, "WoPBS toy, %d bits" % width, left_out=M.wopbs_left_out())
+
+
+@pytest.mark.parametrize("width", [10, 12, 16])
+def test_wide_inputs_param_opt(opt, opt_server, oc, width):
+    """The same at PARAM_OPT (cmux_level_kernel<5,15,3>), up to the 16 bits of the tag check: 64 inputs, all output rows of a random
+    table.  The outputs of one input share its GGSWs, so the inputs are counted.  At 16 bits the 64 inputs need 2.7 GB of tree and the
+    engine cuts the call at its 2 GiB bound: two chunks."""
+    M = model_of(opt)
+    err, vals, _ = wide_outputs(opt_server, oc, width, 64)
+    n = M.wopbs_independent(64, width, width)
+    assert n == 64 and err.shape == (64, 1, width) and nm.rejects_doubling(n)
+    nm.assert_noise(err, M.wopbs(width, vals)[:, None, None], n, "WoPBS opt, %d bits" % width, left_out=M.wopbs_left_out())
+
+
+def test_tag_lut_row_0_param_opt(opt, opt_server, oc):
+    """The verdict of a tag check: output row 0 of the engine's 16-bit LUT (input == 0), the one term a gate's circuit bootstrap decides
+    on.  Rows 1..15 of that LUT are constant zero, come out as exact zero ciphertexts and sit outside the model (NoiseModel.wopbs)."""
+    import ccm
+
+    M = model_of(opt)
+    eq0 = ccm.tag_luts()[1]
+    table = np.zeros(1 << 16, dtype=np.int64)
+    table[0] = 1
+    err, vals, out = wide_outputs(opt_server, oc, 16, 64, table=table, lut=eq0)
+    assert out[:, :, 0].any(axis=-1).all() and not out[:, :, 1:].any()
+    n = M.wopbs_independent(64, 1, 16)
+    assert n == 64 and nm.rejects_doubling(n)
+    nm.assert_noise(err[:, :, :1], M.wopbs(16, vals)[:, None, None], n, "WoPBS opt, tag LUT row 0", left_out=M.wopbs_left_out())
 
 
 # ---- AES ----------------------------------------------------------------------------------------------------------------------------------

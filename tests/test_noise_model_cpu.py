@@ -22,6 +22,8 @@ from tfhe_aes_amd.server import gen_lut
 GPU_CASES = {
     "K1": 4096, "K2 opt": 2100, "K2 toy": 300, "K3": 64, "sweep toy": 256 * 8, "sweep opt": 256, "wide 10": 32 * 10, "wide 12": 32 * 12,
     "AES output": 128, "key expansion toy": 208 * 8, "key expansion opt": 208, "equivalent inverse toy": 256 * 8, "equivalent inverse opt": 256,
+    # PARAM_OPT, where the outputs of one input share its GGSWs: 64 inputs, or 64 bytes of 4 blocks under 4 keys
+    "wide 10 opt": 64, "wide 12 opt": 64, "wide 16 opt": 64, "tag LUT row 0 opt": 64, "CMAC output opt": 64, "tag difference opt": 64,
 }
 
 
@@ -92,6 +94,10 @@ def test_outputs_that_share_their_ggsws_count_once_where_that_matters(tm, om):
     assert tm.wopbs_independent(208, 8) == GPU_CASES["key expansion toy"] and om.wopbs_independent(208, 8) == GPU_CASES["key expansion opt"]
     assert tm.wopbs_independent(32, 12, 12) == GPU_CASES["wide 12"] and tm.wopbs_independent(32, 10, 10) == GPU_CASES["wide 10"]
     assert 7 * tm.cmux(0) / tm.wopbs_mean(8) < 0.05 and 0.55 < 7 * om.cmux(0) / om.wopbs_mean(8) < 0.7
+    for width in (10, 12, 16):
+        assert om.wopbs_independent(64, width, width) == GPU_CASES["wide %d opt" % width]
+    assert om.wopbs_independent(64, 1, 16) == GPU_CASES["tag LUT row 0 opt"]
+    assert om.wopbs_independent(64, 8) == GPU_CASES["CMAC output opt"] == GPU_CASES["tag difference opt"]
 
 
 @pytest.mark.parametrize("name", sorted(GPU_CASES))
@@ -135,9 +141,9 @@ def test_checker_weighs_each_sample_and_bounds_the_worst():
 
 # ---- closed values: a change to the model shows in review ---------------------------------------------------------------------------------
 TOY_LOG2 = {"k1": 54.22, "modswitch": 54.11, "extprod0": 27.52, "extprod1": 27.63, "k2": 29.85, "pfks": 29.50, "k3_carried": 30.56,
-            "cmux0": 48.24, "cmux1": 51.23, "wopbs8": 52.15, "aes_out": 52.65}
+            "cmux0": 48.24, "cmux1": 51.23, "wopbs8": 52.15, "aes_out": 52.65, "wopbs16": 52.70, "wopbs16_x0": 50.19}
 OPT_LOG2 = {"k1": 56.20, "modswitch": 56.41, "extprod0": 29.17, "extprod1": 29.22, "k2": 33.89, "pfks": 29.01, "k3_carried": 33.90,
-            "cmux0": 52.11, "cmux1": 52.66, "wopbs8": 53.84, "aes_out": 54.34}
+            "cmux0": 52.11, "cmux1": 52.66, "wopbs8": 53.84, "aes_out": 54.34, "wopbs16": 54.39, "wopbs16_x0": 54.06}
 
 
 def test_closed_values_param_toy(tm):
@@ -160,6 +166,8 @@ def test_closed_values_param_opt(om):
     # a five-term sum (MixColumns and the round key), K1 and the modulus switch in front of K2's decision
     assert (om.h_small, om.h_polys) == (338, (263, 246, 248, 259))
     assert 33 < om.decision_margin() < 36
+    # a gate's circuit bootstrap decides on `valid`, a 16-bit output: 15 CMUXes' worth of noise per term still leaves 32.7 sigma
+    assert 32 < om.decision_margin(5, 16) < 33.5 < om.decision_margin(5, 12) < 34.2
 
 
 # ---- PARAM_TOY through the oracle, stage by stage -----------------------------------------------------------------------------------------
@@ -321,3 +329,25 @@ def test_aes_output_toy(toy, tm, tc):
     assert c.decrypt_u128(out) == want
     err, _ = nm.wopbs_error(c, out[None])
     nm.assert_noise(err, nm.aes_output_variance(tm, c.key, [want]), 128, "AES output toy", left_out=2 * tm.wopbs_left_out())
+
+
+def test_tag_difference_toy(toy, tm, tc):
+    """X + S0 + trivial(tag) of a tag check through the oracle: two cipher outputs under one key share the last round key's ciphertexts,
+    whose error the sum carries twice (noise_model.tag_difference_variance).  Four keys, two blocks each: 512 independent words at
+    PARAM_TOY, enough for the band to refuse the two aes_output_variance sums alone, which count that word once each."""
+    c, O = tc, toy.oracle
+    errs, var, two_sums = [], [], []
+    for i in range(4):
+        key = bytes(np.random.default_rng(0xCC70 + i).integers(0, 256, 16, dtype=np.uint8).tolist())
+        rk = O.aes_key_expansion(c.encrypt_aes_key(key))
+        b1, b2 = 0x1111 * (i + 1), 0x0123456789ABCDEF << (8 * i)
+        x, s0 = aes_clear.aes_encrypt_block(key, b1), aes_clear.aes_encrypt_block(key, b2)
+        diff = O.aes_encrypt(rk, c.encrypt_u128(b1)) + O.aes_encrypt(rk, c.encrypt_u128(b2)) + c.trivial_bytes(list((x ^ s0).to_bytes(16, "big")))
+        e, vals = nm.wopbs_error(c, diff[None])
+        assert not vals.any()
+        v, t = nm.tag_difference_variance(tm, key, x, s0)
+        errs.append(e[0]); var.append(v); two_sums.append(t)
+    err = np.stack(errs)
+    nm.assert_noise(err, np.stack(var), 512, "tag difference toy", left_out=6 * tm.wopbs_left_out())
+    with pytest.raises(AssertionError):
+        nm.assert_noise(err, np.stack(two_sums), 512, "tag difference toy, the round key counted once per output", left_out=4 * tm.wopbs_left_out())
