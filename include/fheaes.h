@@ -701,6 +701,45 @@ int fheaes_gate_packed(fheaes_ctx *ctx, const uint64_t *gates_lwe, uint64_t n_ga
  * k other than 4 or 1, or a NULL argument: FHEAES_ERR_INVALID. */
 int fheaes_gate_plan(const uint64_t *bits_of_gate, uint64_t n_gates, uint32_t k, uint64_t *workgroups, uint32_t *instances_per_workgroup);
 
+/* ---- audit --------------------------------------------------------------------- */
+/* A server holds no secret key and cannot decrypt what it computed: a wrong word leaves the engine as a well-formed ciphertext.  The audit
+ * is the check it can run.  The engine is deterministic and every blind-rotation form writes the same words, so S sampled rows of a
+ * blind-rotation launch are run again through the latency form (kern_blindrot_latency.h: it parks nothing and shares no slot pool, owner
+ * words or generation plan with the throughput forms) and compared on the device, bit for bit.  A difference is a defect of the engine or
+ * of the machine, never noise.  Off by default; covers the blind rotation only (DESIGN.md says what is caught and what is not).
+ * None of these calls takes data arrays or a memspace.
+ *
+ * fheaes_audit_set: `rows` = 0 (default) turns the audit off and frees its buffers; `rows` in 1..FHEAES_AUDIT_MAX_ROWS (one latency-form
+ * workgroup per row) turns it on: every blind-rotation launch of this context of m >= `min_bits` bits -- the WoPBS of every call, the
+ * gate, fheaes_cbs_pbs_batch -- is then audited on S = min(rows, m) rows, behind the launch on the same stream; the host waits for nothing
+ * and FHEAES_DEVICE calls still only enqueue.  Takes the context's lock, synchronises its stream, allocates the audit's buffers (an audited
+ * call never allocates; they are state that persists by design, like the parking owner words, and not among the FHEAES_WS_BUFFERS), zeroes
+ * the counters and the launch number, and drops a pending fheaes_audit_debug.  With profiling on the audit's time counts into
+ * FHEAES_STAGE_BLIND_ROTATE's total_ms; `launches` and `units` count the product launch only.  Per context, like fheaes_k2_set_forms.
+ * `rows` > FHEAES_AUDIT_MAX_ROWS or a NULL context: FHEAES_ERR_INVALID. */
+#define FHEAES_AUDIT_MAX_ROWS 256
+#define FHEAES_AUDIT_RECORDS 16
+int fheaes_audit_set(fheaes_ctx *ctx, uint32_t rows, uint64_t min_bits, uint64_t seed);
+/* Host logic only, no context, no GPU: the S = min(rows, m) rows, ascending, that audited launch number `launch` (0 for the first one after
+ * fheaes_audit_set) of m bits checks under `seed`; the kernels compute the same.  Stratified: sample s lies in the stratum
+ * [floor(s m / S), floor((s + 1) m / S)) at offset mix(seed, launch, s) mod (stratum length), with
+ *   mix(seed, l, s) = sm(sm(seed + l) + s)     and sm = splitmix64, all arithmetic mod 2^64:
+ *   sm(x):  x += 0x9E3779B97F4A7C15;  x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;  x = (x ^ x >> 27) * 0x94D049BB133111EB;  return x ^ x >> 31
+ * So any run of 2 ceil(m / S) - 1 consecutive wrong rows holds a whole stratum and is always caught, and W scattered wrong rows are caught
+ * with probability about 1 - (1 - S / m)^W.  m = 0, rows = 0, rows > FHEAES_AUDIT_MAX_ROWS or a NULL `rows_out`: FHEAES_ERR_INVALID. */
+int fheaes_audit_rows(uint64_t seed, uint64_t launch, uint64_t m, uint32_t rows, uint64_t *rows_out);
+/* Synchronises, then reads the counters since the last fheaes_audit_set: audited launches, rows compared, rows that differed (sticky until
+ * the next fheaes_audit_set), and the records of the first FHEAES_AUDIT_RECORDS wrong rows -- `records_out`: [record_cap][5] words or NULL,
+ * each {launch, row, first differing word, that word of the product launch, that word of the audit}; `record_n` receives their number.  Any
+ * out-pointer may be NULL; a `record_cap` below the number of records is FHEAES_ERR_INVALID.  Audit off: all zero. */
+int fheaes_audit_read(fheaes_ctx *ctx, uint64_t *launches, uint64_t *rows_checked, uint64_t *rows_wrong, uint64_t *records_out, uint64_t record_cap,
+                      uint64_t *record_n);
+/* Test hook, one shot (tests/test_gpu_audit.py): the next audited launch XORs `xor_mask` (non-zero) into word `word` (<= kN) of row `row` of
+ * its output, after the product kernel and before the audit, in a one-thread kernel on the stream; a `row` beyond that launch's m drops
+ * the hook without a write.  One wrong word in the caller's own result and nothing else.  A zero mask, a word beyond kN or a NULL context:
+ * FHEAES_ERR_INVALID. */
+int fheaes_audit_debug(fheaes_ctx *ctx, uint64_t row, uint32_t word, uint64_t xor_mask);
+
 /* ---- measurement --------------------------------------------------------------- */
 #define FHEAES_STAGE_KEYSWITCH 0
 #define FHEAES_STAGE_BLIND_ROTATE 1

@@ -21,6 +21,7 @@ KW_MIN_SEMIBLOCKS, KW_MAX_SEMIBLOCKS, KW_MAX_KEYS = 2, 8, 4096      # FHEAES_KW_
 AES_WINDOW_OFF = 0xFFFFFFFF     # FHEAES_AES_WINDOW_OFF: fheaes_aes_set_window's "one launch per round"
 GATE_LWE, GATE_GLWE = 0, 1       # FHEAES_GATE_*: the input form of fheaes_gate_ggsw
 K2_PARK_SLOTS = 1024            # FHEAES_K2_PARK_SLOTS: owner words of the paired kernel's shared parking slots, 128 per XCC
+AUDIT_MAX_ROWS, AUDIT_RECORDS = 256, 16      # FHEAES_AUDIT_*: sampled rows per audited launch, records of wrong rows kept
 WS_BUFFERS = 17                 # FHEAES_WS_BUFFERS: the scratch buffers fheaes_workspace_info lists
 WS_CLASSES = ("f64", "words", "tables")                  # FHEAES_WS_F64 / _WORDS / _TABLES
 WS_POISON_FILL, WS_POISON_RELEASE = 0, 1                 # FHEAES_WS_POISON_*: the modes of fheaes_workspace_poison
@@ -158,6 +159,10 @@ SIGNATURES = {
     "fheaes_aes_set_window": (_c.c_int, [_ctx, _c.c_uint32]),
     "fheaes_k2_park_debug": (_c.c_int, [_ctx, _c.POINTER(_c.c_uint32), _c.c_int]),
     "fheaes_k2_park_read": (_c.c_int, [_ctx, _u64p, _u64p, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32), _c.c_uint64, _u64p]),
+    "fheaes_audit_set": (_c.c_int, [_ctx, _c.c_uint32, _c.c_uint64, _c.c_uint64]),
+    "fheaes_audit_rows": (_c.c_int, [_c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_uint32, _u64p]),
+    "fheaes_audit_read": (_c.c_int, [_ctx, _u64p, _u64p, _u64p, _u64p, _c.c_uint64, _u64p]),
+    "fheaes_audit_debug": (_c.c_int, [_ctx, _c.c_uint64, _c.c_uint32, _c.c_uint64]),
     "fheaes_workspace_info": (_c.c_int, [_ctx, _c.c_uint32, _c.c_char_p, _c.c_size_t, _u64p, _c.POINTER(_c.c_int), _u64p, _u64p]),
     "fheaes_workspace_poison": (_c.c_int, [_ctx, _c.c_int, _u64p]),
     "fheaes_version": (_c.c_char_p, []),
@@ -714,6 +719,28 @@ class Engine:
                                                   n.value, _c.byref(n)))
         return {"fallbacks": fb.value, "violations": vi.value, "owner": owner, "record": rec[:n.value]}
 
+    def audit_set(self, rows: int, min_bits: int = 0, seed: int = 0):
+        """fheaes_audit_set: rows 0 = off; else every blind-rotation launch of this context of at least min_bits bits is re-run on
+        min(rows, m) sampled rows through the latency form and compared on the device; zeroes the counters and the launch number"""
+        self._check(self._lib.fheaes_audit_set(self._h, int(rows), int(min_bits), int(seed) & (2 ** 64 - 1)))
+
+    @staticmethod
+    def audit_rows(seed: int, launch: int, m: int, rows: int) -> list[int]:
+        """the rows that audited launch number `launch` of m bits checks under `seed` (fheaes_audit_rows: host only, no GPU)"""
+        return audit_rows(seed, launch, m, rows)
+
+    def audit_read(self) -> dict:
+        """{"launches", "rows_checked", "rows_wrong": the counters since audit_set, "records": uint64[n][5] = (launch, row, first differing
+        word, word of the product launch, word of the audit) of the first AUDIT_RECORDS wrong rows}; synchronises the stream"""
+        la, ch, wr, n = _c.c_uint64(), _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
+        rec = np.zeros((AUDIT_RECORDS, 5), dtype=np.uint64)
+        self._check(self._lib.fheaes_audit_read(self._h, _c.byref(la), _c.byref(ch), _c.byref(wr), rec.ctypes.data_as(_u64p), AUDIT_RECORDS, _c.byref(n)))
+        return {"launches": la.value, "rows_checked": ch.value, "rows_wrong": wr.value, "records": rec[:n.value]}
+
+    def audit_debug(self, row: int, word: int, xor_mask: int):
+        """test hook (fheaes_audit_debug), one shot: the next audited launch XORs xor_mask into word `word` of row `row` of its output"""
+        self._check(self._lib.fheaes_audit_debug(self._h, int(row), int(word), int(xor_mask)))
+
     def workspace_info(self) -> list[dict]:
         """test hook (fheaes_workspace_info): the context's scratch buffers, each {"name", "bytes", "class": one of WS_CLASSES, "first",
         "last": its first and last 8-byte words}; synchronises the stream"""
@@ -886,6 +913,15 @@ def gate_plan(runs, k: int) -> dict:
     if rc != 0:
         raise FheAesError(rc, "fheaes_gate_plan: k must be 4 or 1")
     return {"workgroups": wgs.value, "instances_per_workgroup": per.value}
+
+
+def audit_rows(seed: int, launch: int, m: int, rows: int) -> list[int]:
+    """fheaes_audit_rows (host only, no GPU): the min(rows, m) rows, ascending, that audited launch number `launch` of m bits checks"""
+    out = np.zeros(max(min(int(rows), int(m)), 1), dtype=np.uint64)
+    rc = load_library().fheaes_audit_rows(int(seed) & (2 ** 64 - 1), int(launch), int(m), int(rows), out.ctypes.data_as(_u64p))
+    if rc != 0:
+        raise FheAesError(rc, "fheaes_audit_rows: m at least 1 and rows in 1..%d" % AUDIT_MAX_ROWS)
+    return [int(x) for x in out]
 
 
 def round_keys_packed_glwes(key_bits: int) -> int:

@@ -27,6 +27,7 @@
 #include "kern_blindrot_latency.h"
 #include "kern_blindrot16.h"
 #include "kern_blindrot_pair.h"
+#include "kern_audit.h"
 #include "ks_launch.h"                 // kern_keyswitch.h: the kernels themselves, or (two-unit product build) their argument block + launch functions
 #include "kern_linear.h"
 
@@ -172,6 +173,68 @@ int fheaes_k2_park_read(fheaes_ctx *ctx, uint64_t *fallbacks, uint64_t *violatio
     if (record_out && ctx->k2_park_record_n)
         HIP_TRY(ctx, hipMemcpy(record_out, ctx->ws_park_record.p, ctx->k2_park_record_n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (record_n) *record_n = ctx->k2_park_record_n;
+    return FHEAES_OK;
+}
+// ---- the audit (kern_audit.h, launch_audit) -----------------------------------------------------------------------------------------
+int fheaes_audit_set(fheaes_ctx *ctx, uint32_t rows, uint64_t min_bits, uint64_t seed)
+{
+    if (!ctx) return FHEAES_ERR_INVALID;
+    CtxLock lock__(ctx);
+    if (rows > AUDIT_MAX_ROWS) return ctx->fail(FHEAES_ERR_INVALID, "audit_set: at most %d rows per launch (got %u)", AUDIT_MAX_ROWS, rows);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->audit_rows = 0;                 // off until everything below has succeeded
+    ctx->audit_hook = false;
+    ctx->audit_launch = 0;
+    if (rows == 0) {
+        for (DevBuf *b : {&ctx->audit_in, &ctx->audit_out, &ctx->audit_state})
+            if (b->p) { HIP_TRY(ctx, hipFree(b->p)); b->p = nullptr; b->bytes = 0; }
+        return FHEAES_OK;
+    }
+    // for FHEAES_AUDIT_MAX_ROWS rows whatever `rows` is: a later fheaes_audit_set with more rows moves nothing
+    TRY(ensure(ctx, ctx->audit_in, (size_t)AUDIT_MAX_ROWS * (ctx->n + 1) * 8));
+    TRY(ensure(ctx, ctx->audit_out, (size_t)AUDIT_MAX_ROWS * ctx->big1 * 8));
+    TRY(ensure(ctx, ctx->audit_state, AUDIT_STATE_WORDS * 8));
+    HIP_TRY(ctx, hipMemset(ctx->audit_state.p, 0, AUDIT_STATE_WORDS * 8));
+    ctx->audit_min_bits = min_bits;
+    ctx->audit_seed = seed;
+    ctx->audit_rows = rows;
+    return FHEAES_OK;
+}
+int fheaes_audit_rows(uint64_t seed, uint64_t launch, uint64_t m, uint32_t rows, uint64_t *rows_out)
+{
+    if (!rows_out || m == 0 || rows == 0 || rows > AUDIT_MAX_ROWS) return FHEAES_ERR_INVALID;
+    const uint32_t S = (uint32_t)std::min<uint64_t>(rows, m);
+    for (uint32_t s = 0; s < S; ++s) rows_out[s] = audit_row(seed, launch, m, S, s);
+    return FHEAES_OK;
+}
+int fheaes_audit_read(fheaes_ctx *ctx, uint64_t *launches, uint64_t *rows_checked, uint64_t *rows_wrong, uint64_t *records_out, uint64_t record_cap,
+                      uint64_t *record_n)
+{
+    if (!ctx) return FHEAES_ERR_INVALID;
+    CtxLock lock__(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t st[AUDIT_STATE_WORDS] = {};            // audit off: all zero
+    if (ctx->audit_state.p) HIP_TRY(ctx, hipMemcpy(st, ctx->audit_state.p, sizeof st, hipMemcpyDeviceToHost));
+    const uint64_t n = std::min<uint64_t>(st[AUDIT_ST_WRONG], AUDIT_RECORDS);
+    if (records_out && record_cap < n)
+        return ctx->fail(FHEAES_ERR_INVALID, "audit_read: %llu records do not fit record_cap = %llu", (unsigned long long)n, (unsigned long long)record_cap);
+    if (launches) *launches = st[AUDIT_ST_LAUNCHES];
+    if (rows_checked) *rows_checked = st[AUDIT_ST_CHECKED];
+    if (rows_wrong) *rows_wrong = st[AUDIT_ST_WRONG];
+    if (records_out && n) std::memcpy(records_out, st + AUDIT_ST_RECORDS, n * AUDIT_RECORD_WORDS * 8);
+    if (record_n) *record_n = n;
+    return FHEAES_OK;
+}
+int fheaes_audit_debug(fheaes_ctx *ctx, uint64_t row, uint32_t word, uint64_t xor_mask)
+{
+    if (!ctx) return FHEAES_ERR_INVALID;
+    CtxLock lock__(ctx);
+    if (xor_mask == 0 || word >= ctx->big1)
+        return ctx->fail(FHEAES_ERR_INVALID, "audit_debug: a non-zero mask and a word in 0..%u (got mask %#llx, word %u)", ctx->big, (unsigned long long)xor_mask, word);
+    ctx->audit_hook = true;
+    ctx->audit_hook_row = row; ctx->audit_hook_word = word; ctx->audit_hook_mask = xor_mask;
     return FHEAES_OK;
 }
 const char *fheaes_version(void) { return FHEAES_VERSION_STR; }

@@ -57,6 +57,16 @@ struct fheaes_ctx {
     bool k2_park_pattern = false, k2_park_record = false;
     uint64_t k2_park_record_n = 0;
     uint32_t aes_window = 0;             // fheaes_aes_set_window: 0 = automatic (aes_window_plan), FHEAES_AES_WINDOW_OFF = one WoPBS per step, else forced
+    // the audit (fheaes_audit_set, kern_audit.h): audit_rows > 0 = every blind-rotation launch of at least audit_min_bits is re-run on
+    // min(audit_rows, m) sampled rows through the latency form; audit_launch = audited launches since fheaes_audit_set.  The buffers are
+    // allocated there and never by a launch; like the parking owner words they are state, not scratch (not among FHEAES_WS_BUFFERS)
+    uint32_t audit_rows = 0;
+    uint64_t audit_min_bits = 0, audit_seed = 0, audit_launch = 0;
+    DevBuf audit_in, audit_out, audit_state;
+    // test hook (fheaes_audit_debug), one shot: the next audited launch XORs audit_hook_mask into word audit_hook_word of row audit_hook_row
+    bool audit_hook = false;
+    uint64_t audit_hook_row = 0, audit_hook_mask = 0;
+    uint32_t audit_hook_word = 0;
     // keys
     int8_t *ksk_frag = nullptr, *pfpksk_frag = nullptr;      // balanced key bytes in MFMA B-fragment order
     uint32_t ks_ksteps = 0, ks_coltiles = 0, pf_ksteps = 0, pf_coltiles = 0;

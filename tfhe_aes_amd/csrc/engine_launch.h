@@ -259,6 +259,35 @@ uint64_t aes_context_window(fheaes_ctx *c, uint64_t n, uint64_t steps)
     return aes_window_plan(n, steps, c->cu_count, c->k1, pair).window;
 }
 
+// The audit of one blind-rotation launch (kern_audit.h), behind it on the same stream and inside its StageScope: the time counts into the
+// stage, `launches` and `units` count the product launch alone.  `prod`: the product launch's arguments -- its input, output, row count and
+// the three constants are the audit's; whatever form it took, the sampled rows go through the latency form, which parks nothing.
+// Nothing is allocated here (fheaes_audit_set did) and the host waits for nothing: a mismatch is learnt from fheaes_audit_read.
+static_assert(FHEAES_AUDIT_MAX_ROWS == AUDIT_MAX_ROWS && FHEAES_AUDIT_RECORDS == AUDIT_RECORDS, "include/fheaes.h and kern_audit.h disagree");
+static_assert(AUDIT_MAX_ROWS <= LATENCY_BATCH_BITS, "the audit's rows are one latency-form launch");
+int launch_audit(fheaes_ctx *c, const ExtProdArgs &prod)
+{
+    const uint64_t m = prod.count, launch = c->audit_launch++;
+    const uint32_t S = (uint32_t)std::min<uint64_t>(c->audit_rows, m);
+    if (c->audit_hook) {
+        c->audit_hook = false;                       // one shot; a row beyond this launch's is dropped without a write
+        if (c->audit_hook_row < m)
+            hipLaunchKernelGGL(audit_tamper_kernel, dim3(1), dim3(1), 0, c->stream, prod.out, c->big1, c->audit_hook_row, c->audit_hook_word, c->audit_hook_mask);
+    }
+    uint64_t *const in = (uint64_t *)c->audit_in.p, *const out = (uint64_t *)c->audit_out.p;
+    hipLaunchKernelGGL(audit_gather_kernel, dim3(S), dim3(AUDIT_THREADS), 0, c->stream, prod.lwe_in, c->n + 1, c->audit_seed, launch, m, S, in);
+    ExtProdArgs a{};
+    a.ggsw = prod.ggsw; a.tw = prod.tw; a.iters = prod.iters;
+    a.tv_const = prod.tv_const; a.body_shift = prod.body_shift; a.post_add = prod.post_add;
+    a.lwe_in = in; a.out = out; a.count = S;
+    void (*const latency)(ExtProdArgs) = c->k1 == 5 ? blind_rotate_latency_kernel<5, 5, 8> : blind_rotate_latency_kernel<2, 5, 8>;
+    hipLaunchKernelGGL(latency, dim3(S), dim3(BL_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(audit_compare_kernel, dim3(S), dim3(AUDIT_THREADS), 0, c->stream, prod.out, out, c->big1, c->audit_seed, launch, m, S,
+                       (uint64_t *)c->audit_state.p);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
 int launch_cbs_pbs(fheaes_ctx *c, const uint64_t *lwe_small, uint64_t m, uint32_t level, uint64_t *out)
 {
     if (m == 0) return FHEAES_OK;
@@ -307,6 +336,7 @@ int launch_cbs_pbs(fheaes_ctx *c, const uint64_t *lwe_small, uint64_t m, uint32_
 #endif
     hipLaunchKernelGGL(L.kernel, dim3(L.grid), dim3(L.threads), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
+    if (c->audit_rows && m >= c->audit_min_bits) TRY(launch_audit(c, a));
     return FHEAES_OK;
 }
 

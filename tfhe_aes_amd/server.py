@@ -26,6 +26,8 @@ only allocates outputs and forwards.  README.md:57-59 of the reference spells th
 """
 from __future__ import annotations
 
+import dataclasses
+import os
 from typing import NamedTuple
 
 import numpy as np
@@ -291,6 +293,40 @@ def ctr_stream_blocks(streams, counter_bits: int = 128):
         blocks += [(iv & ~(m - 1)) | ((iv + first_block + i) & (m - 1)) for i in range(n_blocks)]
         data += [0] * n_blocks if d is None else d
     return key_of_block, blocks, data if any_data else None
+
+
+class AuditRecord(NamedTuple):
+    """one wrong row the audit found: audited launch number, row of that launch, first differing word, that word as the product launch
+    wrote it (`got`) and as the latency form wrote it (`want`); `device`: the context's device (ServerGroup), None on a Server"""
+    launch: int
+    row: int
+    word: int
+    got: int
+    want: int
+    device: int | None = None
+
+
+@dataclasses.dataclass
+class AuditReport:
+    """counters of the audit since Server.audit(): audited blind-rotation launches, rows compared, rows that differed, and the records
+    of the first wrong rows (_native.AUDIT_RECORDS per context at most)"""
+    launches: int = 0
+    rows_checked: int = 0
+    rows_wrong: int = 0
+    records: list = dataclasses.field(default_factory=list)
+
+
+class AuditMismatch(_native.FheAesError):
+    """the audit found rows of a blind-rotation launch that the latency form computes differently: a defect of the engine or of the
+    machine, and some result since Server.audit() is wrong.  `report`: the AuditReport, `records`: its records"""
+
+    def __init__(self, report: AuditReport):
+        first = report.records[0] if report.records else None
+        super().__init__(-3, "the audit found %d wrong rows in %d checked over %d launches%s" % (
+            report.rows_wrong, report.rows_checked, report.launches,
+            "" if first is None else "; first: launch %d row %d word %d, %#018x for %#018x" % (first.launch, first.row, first.word, first.got, first.want)))
+        self.report = report
+        self.records = report.records
 
 
 class Server:
@@ -909,6 +945,27 @@ class Server:
     aes_encryption = aes_encrypt
     aes_decryption = aes_decrypt
 
+    # ---- the audit: a check of the blind rotation that needs no secret key (fheaes_audit_set) -------------------------------------------
+    def audit(self, rows: int = 64, min_bits: int = 0, seed: int | None = None):
+        """Re-run `rows` sampled rows (0: off; at most _native.AUDIT_MAX_ROWS) of every blind-rotation launch of at least min_bits bits
+        through the latency form and compare on the GPU, bit for bit; `seed` None draws 64 bits from os.urandom.  Zeroes the counters.
+        Nothing waits for the comparison: ask audit_report() / audit_check() once the results matter."""
+        if seed is None:
+            seed = int.from_bytes(os.urandom(8), "little")
+        self.engine.audit_set(rows, min_bits, seed)
+
+    def audit_report(self) -> AuditReport:
+        """synchronises, then the counters and records since audit()"""
+        r = self.engine.audit_read()
+        return AuditReport(r["launches"], r["rows_checked"], r["rows_wrong"], [AuditRecord(*(int(x) for x in rec)) for rec in r["records"]])
+
+    def audit_check(self) -> AuditReport:
+        """audit_report(), raising AuditMismatch (with the records) if any row since audit() differed"""
+        report = self.audit_report()
+        if report.rows_wrong:
+            raise AuditMismatch(report)
+        return report
+
     def synchronize(self):
         self.engine.synchronize()
         self._inflight.clear()
@@ -926,6 +983,7 @@ class ServerGroup:
         if not devices:
             raise ValueError("at least one device")
         self.params = keys.params
+        self.devices = tuple(int(d) for d in devices)
         self.servers = [Server(keys, device=devices[0])]
         for d in devices[1:]:
             self.servers.append(Server(None, device=d, clone_from=self.servers[0]))
@@ -1298,3 +1356,25 @@ class ServerGroup:
     def clone_info(self):
         """per cloned context: how its keys got there ({"path": "same_device" | "peer" | "staged", "bytes", "seconds"})"""
         return [s.engine.clone_info() for s in self.servers[1:]]
+
+    def audit(self, rows: int = 64, min_bits: int = 0, seed: int | None = None):
+        """Server.audit on every context, each under a seed of its own: drawn from os.urandom, or -- a given `seed` -- seed + the context's index"""
+        for i, s in enumerate(self.servers):
+            s.audit(rows, min_bits, None if seed is None else (int(seed) + i) % (1 << 64))
+
+    def audit_report(self) -> AuditReport:
+        """the contexts' counters summed, their records tagged with the device"""
+        total = AuditReport()
+        for d, s in zip(self.devices, self.servers):
+            r = s.audit_report()
+            total.launches += r.launches
+            total.rows_checked += r.rows_checked
+            total.rows_wrong += r.rows_wrong
+            total.records += [rec._replace(device=d) for rec in r.records]
+        return total
+
+    def audit_check(self) -> AuditReport:
+        report = self.audit_report()
+        if report.rows_wrong:
+            raise AuditMismatch(report)
+        return report
