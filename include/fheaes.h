@@ -138,7 +138,8 @@ int fheaes_reserve(fheaes_ctx *ctx, uint64_t max_bits);
  *     big -> small per bit.  in [m][kN+1] -> out [m][n+1]. */
 int fheaes_keyswitch_batch(fheaes_ctx *ctx, const uint64_t *lwe_in, uint64_t m, uint64_t *lwe_out, int memspace);
 /* K2  the PBS inside circuit_bootstrap_boolean (many_wopbs.rs:253), CBS level `level` (1-based):
- *     in [m][n+1] -> out [m][kN+1] = LWE of bit * 2^(64 - cbs_base_log*level). */
+ *     in [m][n+1] -> out [m][kN+1] = LWE of bit * 2^(64 - cbs_base_log*level).  A batch of more than 65,536 bits is cut into
+ *     launches of that many (one launch's parking space is one buffer below 2 GiB); up to that size it is one launch, as before. */
 int fheaes_cbs_pbs_batch(fheaes_ctx *ctx, const uint64_t *lwe_small, uint64_t m, uint32_t level, uint64_t *lwe_out, int memspace);
 /* K3  the k+1 private functional packing keyswitches of circuit_bootstrap_boolean:
  *     in [m][kN+1] -> out [m][k+1][(k+1)N]  (one GGSW level, standard domain). */

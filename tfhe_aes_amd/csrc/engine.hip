@@ -682,7 +682,12 @@ int fheaes_cbs_pbs_batch(fheaes_ctx *c, const uint64_t *lwe_small, uint64_t m, u
     Staged s(c, memspace);
     TRY(s.in(lwe_small, m * (c->n + 1) * 8, &lwe_small));
     TRY(s.out(lwe_out, m * c->big1 * 8, &lwe_out));
-    TRY(launch_cbs_pbs(c, lwe_small, m, level, lwe_out));
+    // one launch parks 64 KB per workgroup in ONE raw buffer of less than 2^31 bytes (launch_cbs_pbs refuses more): a batch beyond
+    // K2_CALL_MAX_BITS is cut into launches of that many bits, as the WoPBS cuts its own at MAX_CHUNK_BITS
+    for (uint64_t t0 = 0; t0 < m; t0 += K2_CALL_MAX_BITS) {
+        const uint64_t mc = std::min<uint64_t>(K2_CALL_MAX_BITS, m - t0);
+        TRY(launch_cbs_pbs(c, lwe_small + t0 * (c->n + 1), mc, level, lwe_out + t0 * c->big1));
+    }
     return s.finish();
 }
 

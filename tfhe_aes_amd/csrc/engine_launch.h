@@ -3,6 +3,7 @@
 #pragma once
 
 #define MAX_CHUNK_BITS 32768ull
+#define K2_CALL_MAX_BITS 65536ull      /* bits per blind-rotation launch of fheaes_cbs_pbs_batch: at most 32,768 workgroups' parking, 64 KB each */
 #define MAX_WOPBS_BITS 16u            /* widest radix input of many_wopbs_without_padding (LUT of 2^16 entries per output bit) */
 
 namespace {
