@@ -42,6 +42,26 @@ extern "C" {
 #define FHEAES_ERR_INVALID -1  /* bad argument / shape / parameter set */
 #define FHEAES_ERR_NOKEYS -2   /* evaluation before fheaes_upload_keys */
 #define FHEAES_ERR_DEVICE -3   /* HIP runtime error (message in last_error) */
+/* FHEAES_ERR_NOMEM: the device refused an allocation of the context, in the middle of a call -- the workspace grows at request time, and
+ * on a device that the caller's own arrays fill, the engine's hipMalloc is the one that fails.  Every device allocation of a live
+ * context goes through one function (ctx_malloc, csrc/engine_ctx.h): the workspaces, the staging buffers of host-memspace calls, the
+ * parking slab and owner words, the audit's buffers, the key images and staging arrays of the uploads, the images of fheaes_clone_keys
+ * (reported on the destination).  Out: fheaes_create, which fails as a whole with FHEAES_ERR_DEVICE before there is a context, and the
+ * pinned HOST buffer of the table uploads.  What a caller may rely on after -4 (tests/test_gpu_alloc_failures.py):
+ *   - the message names the bytes asked for ("hipMalloc(N bytes): ...");
+ *   - the call has enqueued whatever preceded the failed allocation, and nothing after it: no kernel, copy or memset is ever issued on
+ *     the buffer that was refused (its size reads 0);
+ *   - arrays the call writes, in place or not, hold unspecified words (a host-memspace call copies nothing back: the caller's host
+ *     output is untouched); arrays it only reads are untouched;
+ *   - the context stays usable and keeps its keys: the same call after memory has been freed returns the words of a call that never
+ *     failed, whatever the failed one left in the workspace, and the next call that succeeds is not reported as failed -- the runtime's
+ *     error state is read away where the refusal is met;
+ *   - a failed fheaes_upload_keys / _seeded / fheaes_clone_keys leaves the context WITHOUT keys, also where it had some: the next
+ *     evaluation is FHEAES_ERR_NOKEYS until an upload or a clone succeeds; the source of a failed clone is unharmed;
+ *   - a failed fheaes_audit_set leaves the audit off; a failed fheaes_reserve leaves what it had grown so far;
+ *   - profile counters: a stage counts a launch when its launcher is entered, before the launcher's own allocation, so after a failed
+ *     call `launches` and `units` may include one launch per stage that never happened.  They are defined again after
+ *     fheaes_profile_reset. */
 #define FHEAES_ERR_NOMEM -4
 
 #define FHEAES_HOST 0
@@ -867,6 +887,14 @@ int fheaes_k2_park_read(fheaes_ctx *ctx, uint64_t *fallbacks, uint64_t *violatio
 int fheaes_workspace_info(fheaes_ctx *ctx, uint32_t index, char *name_out, size_t name_cap, uint64_t *bytes_out, int *class_out,
                           uint64_t *first_word_out, uint64_t *last_word_out);
 int fheaes_workspace_poison(fheaes_ctx *ctx, int mode, uint64_t *bytes_out);
+/* Test hook of FHEAES_ERR_NOMEM (tests/test_gpu_alloc_failures.py), one shot.  `fail_nth` = n > 0: the n-th device allocation this
+ * context makes from now on (see FHEAES_ERR_NOMEM for what counts) is put to the runtime with twice the device's total memory
+ * (hipMemGetInfo) in place of its size: the refusal, and the error state it leaves, are the runtime's own, and nothing is reserved.
+ * `fail_nth` = 0 disarms.  Either way *seen_out (may be NULL) receives the number of allocations the context has made since the hook
+ * was last set, the refused one included -- arming far ahead counts a call's allocations -- and the count starts again from 0.  The
+ * message of the refused call names the allocation's own size.  Takes the context's lock and synchronises its stream.  A NULL
+ * context: FHEAES_ERR_INVALID. */
+int fheaes_alloc_debug(fheaes_ctx *ctx, uint64_t fail_nth, uint64_t *seen_out);
 const char *fheaes_version(void);
 
 #ifdef __cplusplus

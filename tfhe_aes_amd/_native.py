@@ -165,6 +165,7 @@ SIGNATURES = {
     "fheaes_audit_debug": (_c.c_int, [_ctx, _c.c_uint64, _c.c_uint32, _c.c_uint64]),
     "fheaes_workspace_info": (_c.c_int, [_ctx, _c.c_uint32, _c.c_char_p, _c.c_size_t, _u64p, _c.POINTER(_c.c_int), _u64p, _u64p]),
     "fheaes_workspace_poison": (_c.c_int, [_ctx, _c.c_int, _u64p]),
+    "fheaes_alloc_debug": (_c.c_int, [_ctx, _c.c_uint64, _u64p]),
     "fheaes_version": (_c.c_char_p, []),
 }
 
@@ -756,6 +757,13 @@ class Engine:
         WS_POISON_RELEASE frees them all (the next call grows everything from nothing); returns the bytes filled or freed"""
         n = _c.c_uint64()
         self._check(self._lib.fheaes_workspace_poison(self._h, int(mode), _c.byref(n)))
+        return n.value
+
+    def alloc_debug(self, fail_nth: int = 0) -> int:
+        """test hook (fheaes_alloc_debug), one shot: the fail_nth-th device allocation this context makes from now on is refused by the
+        runtime (FheAesError.code -4); 0 disarms.  Returns the allocations made since the hook was last set, and counts from 0 again"""
+        n = _c.c_uint64()
+        self._check(self._lib.fheaes_alloc_debug(self._h, int(fail_nth), _c.byref(n)))
         return n.value
 
     def read_bsk_fourier(self, i: int) -> np.ndarray:

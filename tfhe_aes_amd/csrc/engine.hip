@@ -379,6 +379,19 @@ int fheaes_reserve(fheaes_ctx *c, uint64_t max_bits)
     return FHEAES_OK;
 }
 
+// ---- test hook of the allocations (tests/test_gpu_alloc_failures.py): ctx_malloc, engine_ctx.h ------------------------------------
+int fheaes_alloc_debug(fheaes_ctx *c, uint64_t fail_nth, uint64_t *seen_out)
+{
+    if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (seen_out) *seen_out = c->alloc_seen;
+    c->alloc_seen = 0;
+    c->alloc_fail_nth = fail_nth;
+    return FHEAES_OK;
+}
+
 // ---- test hooks of the workspace state (tests/test_gpu_workspace_state.py) ----------------------------------------------------
 // The scratch a call may grow, overwrite or free between two other calls: every ws_* buffer but the parking owner words, pattern and
 // record (state: counters and hooks that persist across launches by design), and the four staging buffers.  Keys, twiddles, LUT
@@ -479,9 +492,9 @@ static int upload_keys_impl(fheaes_ctx *c, const uint64_t *ksk, const uint64_t *
     c->pf_ksteps = (rows3 + KS_KSTEP - 1) / KS_KSTEP; c->pf_coltiles = (ncol3 + 15) / 16;
     const size_t frag1 = (size_t)c->ks_ksteps * c->ks_coltiles * 8 * 1024;
     const size_t frag3 = (size_t)c->k1 * c->pf_ksteps * c->pf_coltiles * 8 * 1024;
-    if (!c->ksk_frag) HIP_TRY(c, hipMalloc((void **)&c->ksk_frag, frag1));
-    if (!c->pfpksk_frag) HIP_TRY(c, hipMalloc((void **)&c->pfpksk_frag, frag3));
-    if (!c->bskf) HIP_TRY(c, hipMalloc((void **)&c->bskf, bw * 8));
+    if (!c->ksk_frag) TRY(ctx_malloc(c, (void **)&c->ksk_frag, frag1));
+    if (!c->pfpksk_frag) TRY(ctx_malloc(c, (void **)&c->pfpksk_frag, frag3));
+    if (!c->bskf) TRY(ctx_malloc(c, (void **)&c->bskf, bw * 8));
     c->ksk_frag_bytes = frag1; c->pfpksk_frag_bytes = frag3; c->bskf_bytes = bw * 8;
     // stage the standard-domain words in HBM (largest key first), transform, free
     void *tmp = nullptr, *tmp_body = nullptr;
@@ -492,10 +505,10 @@ static int upload_keys_impl(fheaes_ctx *c, const uint64_t *ksk, const uint64_t *
     const uint64_t tags[3] = {3, 4, 5};                                  // MASK_TAG_* of csrc/client.c
     size_t body_max = 0;
     for (int i = 0; i < 3; ++i) body_max = std::max(body_max, (size_t)cts[i] * body_w[i]);
-    if (memspace != FHEAES_DEVICE || seeded) HIP_TRY(c, hipMalloc(&tmp, tmp_words * 8));
+    if (memspace != FHEAES_DEVICE || seeded) TRY(ctx_malloc(c, &tmp, tmp_words * 8));
     if (seeded && memspace != FHEAES_DEVICE) {
-        hipError_t me = hipMalloc(&tmp_body, body_max * 8);
-        if (me != hipSuccess) { (void)hipFree(tmp); return c->fail(FHEAES_ERR_NOMEM, "hipMalloc(%zu): %s", body_max * 8, hipGetErrorString(me)); }
+        const int me = ctx_malloc(c, &tmp_body, body_max * 8);
+        if (me != FHEAES_OK) { (void)hipFree(tmp); return me; }
     }
     hipError_t copy_err = hipSuccess;
     // which: 0 KSK, 1 BSK, 2 PFPKSK; returns the device pointer of the full standard-domain key
@@ -600,10 +613,7 @@ int fheaes_clone_keys(fheaes_ctx *dst, fheaes_ctx *src)
         {(void **)&dst->bskf, src->bskf, src->bskf_bytes, &dst->bskf_bytes}};
     for (auto &g : img) {
         if (*g.d && *g.have != g.bytes) { HIP_TRY(dst, hipStreamSynchronize(dst->stream)); HIP_TRY(dst, hipFree(*g.d)); *g.d = nullptr; }
-        if (!*g.d) {
-            hipError_t e = hipMalloc(g.d, g.bytes);
-            if (e != hipSuccess) { *g.d = nullptr; return dst->fail(FHEAES_ERR_NOMEM, "hipMalloc(%zu bytes): %s", g.bytes, hipGetErrorString(e)); }
-        }
+        if (!*g.d) TRY(ctx_malloc(dst, g.d, g.bytes));
         *g.have = g.bytes;
         if (dst->device == src->device) HIP_TRY(dst, hipMemcpyAsync(*g.d, g.s, g.bytes, hipMemcpyDeviceToDevice, dst->stream));
         else HIP_TRY(dst, hipMemcpyPeerAsync(*g.d, dst->device, g.s, src->device, g.bytes, dst->stream));

@@ -67,6 +67,9 @@ struct fheaes_ctx {
     bool audit_hook = false;
     uint64_t audit_hook_row = 0, audit_hook_mask = 0;
     uint32_t audit_hook_word = 0;
+    // test hook (fheaes_alloc_debug), one shot: alloc_seen counts the device allocations ctx_malloc has been asked for since the hook was
+    // last set; the alloc_fail_nth-th of them (0: none) goes to the runtime with a size it must refuse
+    uint64_t alloc_seen = 0, alloc_fail_nth = 0;
     // keys
     int8_t *ksk_frag = nullptr, *pfpksk_frag = nullptr;      // balanced key bytes in MFMA B-fragment order
     uint32_t ks_ksteps = 0, ks_coltiles = 0, pf_ksteps = 0, pf_coltiles = 0;
@@ -128,12 +131,37 @@ struct CtxLock {
 
 namespace {
 
+// The one place where a live context allocates device memory, and where a refused allocation becomes FHEAES_ERR_NOMEM (the contract is
+// at FHEAES_ERR_NOMEM in include/fheaes.h).  In: ensure() -- every workspace, staging, parking and audit buffer --, the key images and
+// staging arrays of upload_keys_impl, the images of fheaes_clone_keys (counted on the destination).  Out: fheaes_create (there is no
+// context yet: it fails as a whole, FHEAES_ERR_DEVICE), the pinned HOST buffer of upload_pinned, the developer build's StampReport.
+// Refused: *p is null, the message names the bytes asked for, and the runtime's last error is read away -- it outlives the call that
+// caused it, and the next launcher's HIP_TRY(hipGetLastError()) on this thread would report a launch that succeeded as failed.
+// Under fheaes_alloc_debug the chosen allocation asks the runtime for twice the device's total memory instead: the refusal, and the
+// error state it leaves behind, are the runtime's own.
+int ctx_malloc(fheaes_ctx *c, void **p, size_t bytes)
+{
+    size_t ask = bytes;
+    *p = nullptr;
+    if (++c->alloc_seen == c->alloc_fail_nth) {
+        c->alloc_fail_nth = 0;
+        size_t free_bytes = 0, total_bytes = 0;
+        HIP_TRY(c, hipMemGetInfo(&free_bytes, &total_bytes));
+        ask = 2 * total_bytes;
+    }
+    const hipError_t e = hipMalloc(p, ask);
+    if (e == hipSuccess) return FHEAES_OK;
+    *p = nullptr;
+    (void)hipGetLastError();
+    if (ask != bytes) return c->fail(FHEAES_ERR_NOMEM, "hipMalloc(%zu bytes): %s (fheaes_alloc_debug: the runtime was asked for %zu)", bytes, hipGetErrorString(e), ask);
+    return c->fail(FHEAES_ERR_NOMEM, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
+}
+
 int ensure(fheaes_ctx *c, DevBuf &b, size_t bytes)
 {
     if (b.bytes >= bytes) return FHEAES_OK;
     if (b.p) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipFree(b.p)); b.p = nullptr; b.bytes = 0; }
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e != hipSuccess) { b.p = nullptr; return c->fail(FHEAES_ERR_NOMEM, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); }
+    TRY(ctx_malloc(c, &b.p, bytes));
     b.bytes = bytes;
     return FHEAES_OK;
 }
