@@ -11,7 +11,7 @@ constant that changes turns a seam test red instead of into a one-chunk test.
 and of the later modes (test_gpu_chunk_seams_modes.py, pinned without a GPU by test_chunk_seams_modes_cpu.py):
 
   256 blocks or slots per pass of xts_whiten_kernel and mac_link_kernel: the same 16,384 / 64 (SLOTS_PER_PASS)
-  2^20 workgroups = 8,192 tweak blocks per pass of xts_tweak_kernel (TWEAK_ROWS_PER_PASS)
+  2^20 workgroups = 8,192 tweak blocks per pass of bit_rows_kernel<XtsRows> (TWEAK_ROWS_PER_PASS)
   128 inputs per chunk of the 16-bit tag WoPBS of a CCM call: 2^24 bytes of CMUX tree each (TAG_TREE_CHUNK); 256 messages per chunk of
   its 8-bit one (TAG_BYTE_CHUNK)
 
@@ -302,7 +302,7 @@ def public_keyed_blocks():
 # ---- G. the later calls: CMAC, key unwrap and the gate -------------------------------------------------------------------------------------
 # (test_gpu_chunk_seams_calls.py, pinned without a GPU by test_chunk_seams_calls_cpu.py.)  The rules restated:
 #   a byte WoPBS takes CHUNK_BYTES = 4,096 bytes a chunk: 256 blocks, so 257 keys or streams put one block behind the seam
-#   mac_link_kernel and kw_link_kernel take SLOTS_PER_PASS = 256 slots or keys a grid pass; cmac_subkey_kernel one workgroup per output row
+#   mac_link_kernel and kw_link_kernel take SLOTS_PER_PASS = 256 slots or keys a grid pass; bit_rows_kernel<CmacRows> one workgroup per output row
 #   gate_kernel takes GATE_MAX_GRID = 65,536 workgroups a launch, GATE_R = 8 instances a workgroup at k = 1, and a bootstrapped gate call
 #   MAX_CHUNK_BITS gates a chunk, whose GGSWs lie at g mod MAX_CHUNK_BITS of one workspace
 GATE_MAX_GRID = 65536

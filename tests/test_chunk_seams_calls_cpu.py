@@ -36,7 +36,7 @@ def test_257_keys_put_one_key_behind_every_seam_of_the_subkey_call():
     parts = cs.cmac_keyswitch(plan, m, [])
     assert _launches(parts) == {"chain": 0, "public_rounds": 20, "refresh_l": 2, "refresh_k": 3}
     assert 16 * m - cs.CHUNK_BYTES == 16 and 32 * m - 2 * cs.CHUNK_BYTES == 32    # key 256 alone in the last chunk of both refreshes
-    assert 256 * m == 65792                                                     # workgroups of cmac_subkey_kernel
+    assert 256 * m == 65792                                                     # workgroups of bit_rows_kernel<CmacRows>
     one_less = cs.cmac_keyswitch(_subkey_plan(m - 1), m - 1, [])
     assert _launches(one_less) == {"chain": 0, "public_rounds": 10, "refresh_l": 1, "refresh_k": 2}
 

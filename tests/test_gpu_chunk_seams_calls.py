@@ -76,7 +76,7 @@ def _subkey_plan(m):
 def test_cmac_subkeys_of_257_keys(toy, tc, store259):
     """cmac_subkeys_dev over 257 keys: the public call on 257 zero blocks that share nothing (pools of 4,112 entries in every round, round
     1 included, the key in the head word), the identity WoPBS over 4,112 bytes of L (2 chunks, key 256 alone in the second),
-    cmac_subkey_kernel over 65,792 workgroups and the identity WoPBS over 8,224 bytes of K1 | K2 (3 chunks), on workspace pointers taken
+    bit_rows_kernel<CmacRows> over 65,792 workgroups and the identity WoPBS over 8,224 bytes of K1 | K2 (3 chunks), on workspace pointers taken
     before the calls that may grow workspaces.  Keys 0, 127, 128, 255 and 256 alone on a one-key slice give the same words; all 514
     subkeys decrypt to aes_clear's, index 256 to the K1 and K2 of SP 800-38B D.1"""
     p, m = toy.params, cs.CMAC_KEYS

@@ -1,7 +1,7 @@
 """The chunk seams of the later modes, at PARAM_TOY: XTS-AES decryption, AES-CCM with its tag check, CBC-MAC chains and the public calls
 with a key per pool entry, each run once across the seams test_gpu_chunk_seams.py was written before (tests/chunk_seams.py, part F, has
 the shapes and why each is the smallest that crosses; test_chunk_seams_modes_cpu.py pins them without a GPU).  The seams: the 256 blocks
-or slots of one grid pass of xts_whiten_kernel and mac_link_kernel, the 2^20 workgroups of xts_tweak_kernel, the 4,096 bytes of one chunk
+or slots of one grid pass of xts_whiten_kernel and mac_link_kernel, the 2^20 workgroups of bit_rows_kernel<XtsRows>, the 4,096 bytes of one chunk
 of a byte WoPBS inside aes_xts_decrypt_dev, ccm_open_dev, cbc_mac_dev and aes_public_dev, and the 128 inputs of one chunk of the 16-bit
 tag WoPBS.  The house rules of the older file hold: a context of its own per test, resident outputs between sentinel guard rows, every
 word comparison array_equal / torch.equal on uint64 words, data that differs on both sides of every seam, and the crossing asserted from
@@ -171,7 +171,7 @@ def _tweak_sources():
 
 
 def test_xts_tweaks_second_pass_behind_the_grid_cap(toy):
-    """launch_xts_tweaks / xts_tweak_kernel: the grid is capped at 2^20 workgroups = 8,192 tweak blocks and the rows from 2^20 on come
+    """launch_xts_tweaks / bit_rows_kernel<XtsRows>: the grid is capped at 2^20 workgroups = 8,192 tweak blocks and the rows from 2^20 on come
     from the `r += gridDim.x` loop.  68 units x 122 offsets = 8,296 tweak blocks = 1,061,888 rows is the smallest shape that crosses (67
     units stay below); the second pass starts at unit 67, offset 18.  4.36 GB of output stay on the GPU: every unit is compared there with
     the wrapping sum of index_select over the source lists of xts.rows(j), and unit 0 and offsets 17..19 of unit 67 -- and the device

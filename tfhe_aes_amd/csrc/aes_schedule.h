@@ -90,7 +90,7 @@ static int aes_run_dev(fheaes_ctx *c, const KeySets &rk, uint64_t *state, uint64
     }
     const uint64_t ggsw_words = (uint64_t)c->k1 * c->k1 * FHE_N, total = steps * n_blocks;     // cbs_level == 1
     TRY(ensure_wopbs_ws(c, w * AES_BLOCK_BITS));
-    uint64_t *small = (uint64_t *)c->ws_small.p, *pbs = (uint64_t *)c->ws_pbs.p, *ggsw = (uint64_t *)c->ws_ggsw.p;
+    uint64_t *small = (uint64_t *)c->ws_small.p;
     const double2 *ggswf = (const double2 *)c->ws_ggswf.p;
     struct Segment { const AesStep *st; uint64_t first, blocks, row; uint64_t *vp; };            // row: its first block's place in the window
     for (uint64_t i0 = 0; i0 < total; i0 += w) {
@@ -103,9 +103,7 @@ static int aes_run_dev(fheaes_ctx *c, const KeySets &rk, uint64_t *state, uint64
         }
         for (int g = 0; g < n_seg; ++g)
             TRY(launch_keyswitch(c, state + seg[g].first * sw, seg[g].blocks * AES_BLOCK_BITS, small + seg[g].row * AES_BLOCK_BITS * (c->n + 1)));
-        TRY(launch_cbs_pbs(c, small, m, 1, pbs));
-        TRY(launch_pfpks(c, pbs, m, ggsw, ggsw_words));
-        TRY(launch_forward_fourier(c, ggsw, m * c->k1 * c->k1, (double2 *)c->ws_ggswf.p, FHEAES_STAGE_GGSW_FFT));
+        TRY(cbs_from_small(c, m));
         if (n_seg == 1 || seg[0].st->set == seg[1].st->set) {
             const int set = seg[0].st->set;
             TRY(launch_vertical_packing(c, ggswf, 16 * len, 8, c->lutset_d[set], (uint32_t)c->lutset_n[set], 0, vp));
@@ -381,7 +379,7 @@ static int aes_public_dev(fheaes_ctx *c, const PublicDirection &dir, const KeySe
 // ---- XTS-AES decryption (IEEE 1619, SP 800-38E) -------------------------------------------------
 // P_j = D_K1(C_j ^ T_j) ^ T_j, T_j = E_K2(tweak) * alpha^j: the first mode here whose per-block mask is ENCRYPTED, so the public path does
 // not apply to the blocks -- only to the tweak blocks.  Levels against the guard's 5: E_K2(tweak) leaves the public call at 2 (S-Box output +
-// round key) and an identity WoPBS makes it 1: the ANCHOR of a data unit.  One gather (xts_tweak_kernel) gives T_j at up to 4 terms; used
+// round key) and an identity WoPBS makes it 1: the ANCHOR of a data unit.  One gather (bit_rows_kernel<XtsRows>) gives T_j at up to 4 terms; used
 // raw on both sides of the cipher it would pass going in (4 + dw[Nr] = 5) but not coming out (InvS + dw[0] + 4 = 6), so every T_j is
 // refreshed by an identity WoPBS: 2 going in, 3 coming out.  A gather reaches offset 121, so a unit is cut into segments of XTS_SEGMENT
 // blocks: segment s gathers offsets 0 .. 120 from anchor s, and the refreshed offset 120 -- block 120 (s + 1)'s place, computed for this
@@ -646,7 +644,7 @@ static int ccm_open_dev(fheaes_ctx *c, const KeySets &rk, int nr, uint64_t n_key
 // T = the CBC-MAC of the message whose last block also gets a subkey added: K1 = L x under a whole last block, K2 = L x^2 under a padded
 // one, L = E_K(0^128).  Every block is public, so the chain above runs as it is with the subkey as the last block's encrypted addend: the
 // records' b is 2 * key + which into the subkey array.  Levels against the guard's 5: L leaves the public call at 2, an identity WoPBS
-// makes it 1; the gather (cmac_subkey_kernel) gives K1 at 2 and K2 at 3; a second identity WoPBS makes both 1, counted -- as every
+// makes it 1; the gather (bit_rows_kernel<CmacRows>) gives K1 at 2 and K2 at 3; a second identity WoPBS makes both 1, counted -- as every
 // addend of a chain -- as 2: the last link is X (2) + subkey (2) + round key = 5.  Without the second refresh it would be 2 + 3 + 1 = 6,
 // and without the first K2 alone would be 2 * 3.  48 byte-WoPBS per key, against 16 Nr per chained block.
 

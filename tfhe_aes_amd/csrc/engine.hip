@@ -350,8 +350,8 @@ size_t fheaes_key_words(const fheaes_ctx *c, int which)
 
 int fheaes_set_stream(fheaes_ctx *c, void *hip_stream)
 {
-    CtxLock lock__(c);
     if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     return FHEAES_OK;
@@ -359,16 +359,16 @@ int fheaes_set_stream(fheaes_ctx *c, void *hip_stream)
 
 int fheaes_synchronize(fheaes_ctx *c)
 {
-    CtxLock lock__(c);
     if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return FHEAES_OK;
 }
 
 int fheaes_reserve(fheaes_ctx *c, uint64_t max_bits)
 {
-    CtxLock lock__(c);
     if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
     HIP_TRY(c, hipSetDevice(c->device));
     uint64_t bits = std::min<uint64_t>(max_bits, MAX_CHUNK_BITS);
     TRY(ensure_wopbs_ws(c, bits));
@@ -1798,7 +1798,7 @@ int fheaes_aes_kw_plan(uint32_t key_bits, uint32_t semiblocks, uint64_t n_keys, 
 static_assert(GATE_LWE == FHEAES_GATE_LWE && GATE_GLWE == FHEAES_GATE_GLWE, "fheaes.h's input forms are the kernel's");
 
 // ggsw_fourier: caller-made GGSWs (fheaes_gate_ggsw), else gates_lwe: the bits, circuit-bootstrapped here in wopbs_dev's workspaces and by its
-// chunk rule (the front half of wopbs_dev: K1, K2 at level 1, K3, K4), each chunk's GGSWs gating that chunk's runs before the next overwrites them
+// chunk rule (cbs_bits: K1, K2 at level 1, K3, K4), each chunk's GGSWs gating that chunk's runs before the next overwrites them
 static int gate_call(fheaes_ctx *c, bool boot, const double *ggsw_fourier, const uint64_t *gates_lwe, uint64_t n_gates, const uint64_t *bits_of_gate, const uint64_t *in,
                      uint64_t m, int form, uint64_t *out, int memspace)
 {
@@ -1843,10 +1843,7 @@ static int gate_call(fheaes_ctx *c, bool boot, const double *ggsw_fourier, const
     uint64_t wg0 = 0;
     for (uint64_t g0 = 0, ci = 0; g0 < n_gates; g0 += chunk, ++ci) {
         const uint64_t gc = std::min<uint64_t>(chunk, n_gates - g0);
-        TRY(launch_keyswitch(c, gates_lwe + g0 * c->big1, gc, (uint64_t *)c->ws_small.p));
-        TRY(launch_cbs_pbs(c, (const uint64_t *)c->ws_small.p, gc, 1, (uint64_t *)c->ws_pbs.p));
-        TRY(launch_pfpks(c, (const uint64_t *)c->ws_pbs.p, gc, (uint64_t *)c->ws_ggsw.p, ggsw_words));
-        TRY(launch_forward_fourier(c, (const uint64_t *)c->ws_ggsw.p, gc * c->k1 * c->k1, (double2 *)c->ws_ggswf.p, FHEAES_STAGE_GGSW_FFT));
+        TRY(cbs_bits(c, gates_lwe + g0 * c->big1, gc));
         uint64_t units = 0;
         for (uint64_t g = g0; g < g0 + gc; ++g) units += bits_of_gate[g];
         TRY(launch_gate(c, (const double2 *)c->ws_ggswf.p, tab + wg0, chunk_end[ci] - wg0, units, form, in, out));
@@ -1890,6 +1887,7 @@ size_t fheaes_packed_words(const fheaes_ctx *c, uint64_t m)
 
 int fheaes_pack_bits(fheaes_ctx *c, const uint64_t *lwe_in, uint64_t m, uint64_t *glwe_out, int memspace)
 {
+    if (!c) return FHEAES_ERR_INVALID;
     CtxLock lock__(c);
     TRY(check_keys(c));
     if (m == 0) return FHEAES_OK;
@@ -1906,8 +1904,8 @@ int fheaes_pack_bits(fheaes_ctx *c, const uint64_t *lwe_in, uint64_t m, uint64_t
 
 int fheaes_unpack_bits(fheaes_ctx *c, const uint64_t *glwe_in, uint64_t m, uint64_t *lwe_out, int memspace)
 {
-    CtxLock lock__(c);
     if (!c) return FHEAES_ERR_INVALID;
+    CtxLock lock__(c);
     if (m == 0) return FHEAES_OK;
     if (!glwe_in || !lwe_out) return c->fail(FHEAES_ERR_INVALID, "null pointer");
     const uint64_t in_bytes = (uint64_t)fheaes_packed_words(c, m) * 8, out_bytes = m * c->big1 * 8;

@@ -481,13 +481,21 @@ int launch_gather(fheaes_ctx *c, const uint64_t *src, uint32_t n_luts, const Key
     return FHEAES_OK;
 }
 
+// The grid of the block-row kernels (add_bcast_kernel, xts_whiten_kernel, mac_link_kernel, kw_link_kernel): x over the words of an item, at
+// most 64 workgroups; y over the n items, at most 16384 / x of them per pass -- 256 at both parameter sets, the SLOTS_PER_PASS of
+// tests/chunk_seams.py; the kernels' loops take the items beyond.
+dim3 block_rows_grid(uint64_t words_per_item, uint64_t n)
+{
+    const unsigned gx = (unsigned)std::min<uint64_t>((words_per_item + 255) / 256, 64);
+    return dim3(gx, (unsigned)std::min<uint64_t>(n, std::max<uint64_t>(1, 16384 / gx)));
+}
+
 int launch_add_bcast(fheaes_ctx *c, uint64_t *dst, const KeySets &k, uint64_t words_per_block, uint64_t n_blocks)
 {
     if (n_blocks == 0) return FHEAES_OK;
     TRY(noise_guard(c, 2, "the initial AddRoundKey"));
     StageScope sc(c, FHEAES_STAGE_LINEAR, n_blocks);
-    const unsigned gx = (unsigned)std::min<uint64_t>((words_per_block + 255) / 256, 64);
-    dim3 grid(gx, (unsigned)std::min<uint64_t>(n_blocks, std::max<uint64_t>(1, 16384 / gx)));
+    const dim3 grid = block_rows_grid(words_per_block, n_blocks);
     with_keys(c, k, [&](auto keys) {
         hipLaunchKernelGGL(add_bcast_kernel<decltype(keys)>, grid, dim3(256), 0, c->stream, dst, keys, k.of_block, words_per_block, n_blocks, c->big1);
     });
@@ -507,7 +515,7 @@ int launch_key_rows(fheaes_ctx *c, uint64_t *dst, uint64_t dst_stride, const uin
     return FHEAES_OK;
 }
 
-// xts_tweak_kernel: offsets off0 .. off0 + n_off - 1 of n_units units.  The layer's largest row weight is what it declares to the noise
+// bit_rows_kernel over XtsRows: offsets off0 .. off0 + n_off - 1 of n_units units.  The layer's largest row weight is what it declares to the noise
 // guard (at most 4: kern_linear.h); an offset beyond XTS_MAX_OFFSET would need a second reduction and is refused.  Units: tweak blocks.
 int launch_xts_tweaks(fheaes_ctx *c, const uint64_t *anchor, uint64_t anchor_stride, uint64_t n_units, uint32_t off0, uint32_t n_off, uint64_t *out)
 {
@@ -520,8 +528,8 @@ int launch_xts_tweaks(fheaes_ctx *c, const uint64_t *anchor, uint64_t anchor_str
     TRY(noise_guard(c, weight, "the XTS tweak layer (multiplication by alpha^j)"));
     StageScope sc(c, FHEAES_STAGE_LINEAR, n_units * n_off);
     const uint64_t rows = n_units * n_off * 128;
-    hipLaunchKernelGGL(xts_tweak_kernel, dim3((unsigned)std::min<uint64_t>(rows, 1u << 20)), dim3(256), 0, c->stream, anchor, anchor_stride, out, n_units, off0,
-                       n_off, c->big1);
+    hipLaunchKernelGGL(bit_rows_kernel<XtsRows>, dim3((unsigned)std::min<uint64_t>(rows, 1u << 20)), dim3(256), 0, c->stream,
+                       XtsRows{anchor, anchor_stride, n_off, off0}, out, rows, c->big1);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
@@ -533,8 +541,7 @@ int launch_xts_whiten(fheaes_ctx *c, uint64_t *dst, const uint64_t *src, const u
     if (n_blocks == 0) return FHEAES_OK;
     TRY(noise_guard(c, level, "the XTS whitening (tweak + block)"));
     StageScope sc(c, FHEAES_STAGE_LINEAR, n_blocks);
-    const unsigned gx = (unsigned)std::min<uint64_t>((128ull * c->big1 + 255) / 256, 64);
-    dim3 grid(gx, (unsigned)std::min<uint64_t>(n_blocks, std::max<uint64_t>(1, 16384 / gx)));
+    const dim3 grid = block_rows_grid(128ull * c->big1, n_blocks);
     hipLaunchKernelGGL(xts_whiten_kernel, grid, dim3(256), 0, c->stream, dst, src, tweaks, tweak_of_block, clear, n_blocks, c->big1);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
@@ -548,8 +555,7 @@ int launch_mac_link(fheaes_ctx *c, uint64_t *dst, const uint64_t *a, const uint6
     if (n_slots == 0) return FHEAES_OK;
     TRY(noise_guard(c, level, what));
     StageScope sc(c, FHEAES_STAGE_LINEAR, n_slots);
-    const unsigned gx = (unsigned)std::min<uint64_t>((128ull * c->big1 + 255) / 256, 64);
-    dim3 grid(gx, (unsigned)std::min<uint64_t>(n_slots, std::max<uint64_t>(1, 16384 / gx)));
+    const dim3 grid = block_rows_grid(128ull * c->big1, n_slots);
     hipLaunchKernelGGL(mac_link_kernel, grid, dim3(256), 0, c->stream, dst, a, b, slots, n_slots, c->big1);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
@@ -566,21 +572,21 @@ int launch_kw_link(fheaes_ctx *c, uint64_t *state, uint64_t *regs, const uint8_t
                                                   : unload ? "the key-unwrap unload (A + the integrity constant, the raw key)"
                                                            : "a key-unwrap link (cipher output + counter + the round key that follows)"));
     StageScope sc(c, FHEAES_STAGE_LINEAR, n_keys);
-    const unsigned gx = (unsigned)std::min<uint64_t>((128ull * c->big1 + 255) / 256, 64);
-    dim3 grid(gx, (unsigned)std::min<uint64_t>(n_keys, std::max<uint64_t>(1, 16384 / gx)));
+    const dim3 grid = block_rows_grid(128ull * c->big1, n_keys);
     hipLaunchKernelGGL(kw_link_kernel, grid, dim3(256), 0, c->stream, state, regs, wrapped, n_keys, n, step, c->big1);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
 
-// cmac_subkey_kernel: K1 and K2 of n_keys keys from their L.  It declares the largest row weight, 3 (K2's: kern_linear.h).  Units: keys.
+// bit_rows_kernel over CmacRows: K1 and K2 of n_keys keys from their L.  It declares the largest row weight, 3 (K2's: kern_linear.h).  The
+// grid IS the rows -- 256 n_keys, 2^24 at FHEAES_MAX_KEYS keys, inside one grid dimension: the kernel's loop runs once.  Units: keys.
 int launch_cmac_double(fheaes_ctx *c, const uint64_t *l, uint64_t n_keys, uint64_t *out)
 {
     if (n_keys == 0) return FHEAES_OK;
     static_assert(256ull * FHEAES_MAX_KEYS <= 0x7FFFFFFFull, "the rows of FHEAES_MAX_KEYS keys are one grid dimension");
     TRY(noise_guard(c, 3, "the CMAC subkey layer (multiplication by x and x^2)"));
     StageScope sc(c, FHEAES_STAGE_LINEAR, n_keys);
-    hipLaunchKernelGGL(cmac_subkey_kernel, dim3((unsigned)(n_keys * 256)), dim3(256), 0, c->stream, l, out, c->big1);
+    hipLaunchKernelGGL(bit_rows_kernel<CmacRows>, dim3((unsigned)(n_keys * 256)), dim3(256), 0, c->stream, CmacRows{l, c->big1}, out, n_keys * 256, c->big1);
     HIP_TRY(c, hipGetLastError());
     return FHEAES_OK;
 }
@@ -738,6 +744,24 @@ int ensure_wopbs_ws(fheaes_ctx *c, uint64_t bits)
     return FHEAES_OK;
 }
 
+// The circuit bootstrap's front half behind K1: the m small LWEs of ws_small -> m Fourier GGSWs in ws_ggswf (K2 at level 1, K3, K4, through
+// ws_pbs and ws_ggsw; ensure_wopbs_ws has sized all four for m bits)
+int cbs_from_small(fheaes_ctx *c, uint64_t m)
+{
+    const uint64_t ggsw_words = (uint64_t)c->k1 * c->k1 * FHE_N;    // cbs_level == 1
+    TRY(launch_cbs_pbs(c, (const uint64_t *)c->ws_small.p, m, 1, (uint64_t *)c->ws_pbs.p));
+    TRY(launch_pfpks(c, (const uint64_t *)c->ws_pbs.p, m, (uint64_t *)c->ws_ggsw.p, ggsw_words));
+    TRY(launch_forward_fourier(c, (const uint64_t *)c->ws_ggsw.p, m * c->k1 * c->k1, (double2 *)c->ws_ggswf.p, FHEAES_STAGE_GGSW_FFT));
+    return FHEAES_OK;
+}
+
+// the whole front half of m contiguous bits: in [m][kN+1] -> K1 -> cbs_from_small
+int cbs_bits(fheaes_ctx *c, const uint64_t *in, uint64_t m)
+{
+    TRY(launch_keyswitch(c, in, m, (uint64_t *)c->ws_small.p));
+    return cbs_from_small(c, m);
+}
+
 int wopbs_dev(fheaes_ctx *c, const uint64_t *lwe_in, uint64_t n_inputs, uint32_t bits, const uint64_t *luts, uint32_t n_luts,
               int per_input, uint64_t *lwe_out)
 {
@@ -751,16 +775,10 @@ int wopbs_dev(fheaes_ctx *c, const uint64_t *lwe_in, uint64_t n_inputs, uint32_t
         chunk_inputs = std::max<uint64_t>(1, std::min<uint64_t>(chunk_inputs, (2ull << 30) / per_input));
     }
     const uint64_t W = lut_row_words(bits);
-    const uint64_t ggsw_words = (uint64_t)c->k1 * c->k1 * FHE_N;    // cbs_level == 1
     TRY(ensure_wopbs_ws(c, std::min<uint64_t>(n_inputs, chunk_inputs) * bits));
     for (uint64_t i0 = 0; i0 < n_inputs; i0 += chunk_inputs) {
         const uint64_t ni = std::min<uint64_t>(chunk_inputs, n_inputs - i0);
-        const uint64_t m = ni * bits;
-        const uint64_t *in = lwe_in + i0 * bits * c->big1;
-        TRY(launch_keyswitch(c, in, m, (uint64_t *)c->ws_small.p));
-        TRY(launch_cbs_pbs(c, (const uint64_t *)c->ws_small.p, m, 1, (uint64_t *)c->ws_pbs.p));
-        TRY(launch_pfpks(c, (const uint64_t *)c->ws_pbs.p, m, (uint64_t *)c->ws_ggsw.p, ggsw_words));
-        TRY(launch_forward_fourier(c, (const uint64_t *)c->ws_ggsw.p, m * c->k1 * c->k1, (double2 *)c->ws_ggswf.p, FHEAES_STAGE_GGSW_FFT));
+        TRY(cbs_bits(c, lwe_in + i0 * bits * c->big1, ni * bits));
         const uint64_t *l = per_input ? luts + i0 * n_luts * bits * W : luts;
         TRY(launch_vertical_packing(c, (const double2 *)c->ws_ggswf.p, ni, bits, l, n_luts, per_input, lwe_out + i0 * n_luts * bits * c->big1));
     }

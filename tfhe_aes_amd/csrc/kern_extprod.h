@@ -1,6 +1,7 @@
 // kern_extprod.h -- what the external-product kernels share, and the ones that are not the blind rotation:
 //   shared  ExtProdArgs, ep_key_load, ep_load_table, EP_STAMP, EP_THREADS / EP_GROUPS: used by K2, the blind rotation of the
-//           circuit-bootstrap PBS, whose three forms are kern_blindrot_latency.h, kern_blindrot16.h and kern_blindrot_pair.h
+//           circuit-bootstrap PBS, whose three forms are kern_blindrot_latency.h, kern_blindrot16.h and kern_blindrot_pair.h;
+//           ep_product_once, the single-level external product of cmux_level_kernel and of gate_kernel (kern_gate.h)
 //   K5      vertical packing = CMUX blind rotation over the LUT + sample extract: vertical_packing_kernel,
 //           and cmux_level_kernel, the CMUX tree in front of it for inputs wider than 9 bits
 //   K4      torus polynomials -> Fourier domain (BSK upload, ggsw.fill_with_forward_fourier, 8 a14): forward_fourier_kernel
@@ -61,6 +62,66 @@ __device__ __forceinline__ double2 ep_key_load(__amdgpu_buffer_rsrc_t rsrc, unsi
     d.x = __longlong_as_double((long long)(((unsigned long long)v[1] << 32) | v[0]));
     d.y = __longlong_as_double((long long)(((unsigned long long)v[3] << 32) | v[2]));
     return d;
+}
+
+// One single-level external product of a workgroup's R instances with ONE GGSW, in the lane mapping above: the body of
+// cmux_level_kernel and of gate_kernel (kern_gate.h).  On entry xr / xi hold the digits of the lane group's polynomial; the GGSW is
+// number `which` of ggsws ([..][K1][K1][256], the same one for the whole workgroup; a GGSW is 16 KB and more, so 32 bits count them); on
+// return xr / xi hold the group's product polynomial.  The GGSW row p = 0..K1-1 is one fma chain, per column the four fmas in this
+// order; key elements come through plain loads, their address formed only where the multiply-accumulate starts (formed by the caller it
+// costs the kernels a register).  The caller places a workgroup barrier in front (tables visible; what it read before may be overwritten
+// after the call).
+template <int K1, int R>
+__device__ __forceinline__ void ep_product_once(double (&xr)[16], double (&xi)[16], const double2 *ggsws, const uint32_t which, double *lds,
+                                                const double2 *tw, double *tile, const int tid, const int b)
+{
+    nega_fwd(xr, xi, tw, tile, b);
+#pragma unroll
+    for (int k2 = 0; k2 < 16; ++k2) {
+        double2 v; v.x = xr[k2]; v.y = xi[k2];
+        *reinterpret_cast<double2 *>(tile + 2 * (b + 16 * k2)) = v;
+    }
+    __syncthreads();
+    // multiply-accumulate role: thread tid owns Fourier point tid
+    double fr[R][K1], fi[R][K1];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int c = 0; c < K1; ++c) { fr[r][c] = 0.0; fi[r][c] = 0.0; }
+    const double2 *G = ggsws + (size_t)which * (size_t)(K1 * K1 * FHE_H) + tid;
+#pragma unroll
+    for (int p = 0; p < K1; ++p) {
+        double2 bv[K1];
+#pragma unroll
+        for (int c = 0; c < K1; ++c) bv[c] = G[(size_t)(p * K1 + c) * FHE_H];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const double2 d = *reinterpret_cast<const double2 *>(lds + (r * K1 + p) * GROUP_TILE_DOUBLES + 2 * tid);
+#pragma unroll
+            for (int c = 0; c < K1; ++c) {
+                fr[r][c] = __builtin_fma(d.x, bv[c].x, fr[r][c]);
+                fr[r][c] = __builtin_fma(-d.y, bv[c].y, fr[r][c]);
+                fi[r][c] = __builtin_fma(d.x, bv[c].y, fi[r][c]);
+                fi[r][c] = __builtin_fma(d.y, bv[c].x, fi[r][c]);
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int c = 0; c < K1; ++c) {
+            double2 v; v.x = fr[r][c]; v.y = fi[r][c];
+            *reinterpret_cast<double2 *>(lds + (r * K1 + c) * GROUP_TILE_DOUBLES + 2 * tid) = v;
+        }
+    __syncthreads();
+#pragma unroll
+    for (int k2 = 0; k2 < 16; ++k2) {
+        double2 v = *reinterpret_cast<const double2 *>(tile + 2 * (b + 16 * k2));
+        xr[k2] = v.x; xi[k2] = v.y;
+    }
+    wave_lds_sync();
+    nega_inv(xr, xi, tw, tile, b);
 }
 
 #ifdef EP_STAMPS
@@ -286,7 +347,7 @@ __global__ __launch_bounds__(EP_THREADS, EP_MIN_WAVES) void vertical_packing_ker
 // binary tree of CMUXes (bit 9 at the leaves), then the blind rotation over bits 0..8 selects the coefficient.  One launch per
 // tree level: job = (instance, node) computes  out = ct0 + GGSW_bit (x) (ct1 - ct0)  with ct0 / ct1 = children 2*node, 2*node+1
 // (leaf level: trivial GLWEs of LUT polynomials).  Same lane mapping and arithmetic as one iteration of the kernel above with
-// one decomposition level.  Not on the AES path (8- and 9-bit inputs only); it completes many_wopbs_without_padding.
+// one decomposition level; the product is ep_product_once.  Not on the AES path (8- and 9-bit inputs only); it completes many_wopbs_without_padding.
 struct CmuxArgs {
     const double2 *ggsw;        // Fourier GGSWs [n_inputs][bits][K1][K1][256]
     const double2 *tw;          // [FHE_TW_ENTRIES] the transform's one table (fft_dev.h)
@@ -349,53 +410,7 @@ __global__ __launch_bounds__(EP_THREADS, 2) void cmux_level_kernel(const CmuxArg
         }
     }
     __syncthreads();   // tables visible
-    nega_fwd(xr, xi, tw, tile, b);
-#pragma unroll
-    for (int k2 = 0; k2 < 16; ++k2) {
-        double2 v; v.x = xr[k2]; v.y = xi[k2];
-        *reinterpret_cast<double2 *>(tile + 2 * (b + 16 * k2)) = v;
-    }
-    __syncthreads();
-    // multiply-accumulate role: thread tid owns Fourier point tid
-    double fr[R][K1], fi[R][K1];
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int c = 0; c < K1; ++c) { fr[r][c] = 0.0; fi[r][c] = 0.0; }
-    const double2 *G = A.ggsw + ((size_t)input * A.bits + A.bit) * (size_t)(K1 * K1 * FHE_H) + tid;
-#pragma unroll
-    for (int p = 0; p < K1; ++p) {
-        double2 bv[K1];
-#pragma unroll
-        for (int c = 0; c < K1; ++c) bv[c] = G[(size_t)(p * K1 + c) * FHE_H];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const double2 d = *reinterpret_cast<const double2 *>(lds + (r * K1 + p) * GROUP_TILE_DOUBLES + 2 * tid);
-#pragma unroll
-            for (int c = 0; c < K1; ++c) {
-                fr[r][c] = __builtin_fma(d.x, bv[c].x, fr[r][c]);
-                fr[r][c] = __builtin_fma(-d.y, bv[c].y, fr[r][c]);
-                fi[r][c] = __builtin_fma(d.x, bv[c].y, fi[r][c]);
-                fi[r][c] = __builtin_fma(d.y, bv[c].x, fi[r][c]);
-            }
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int c = 0; c < K1; ++c) {
-            double2 v; v.x = fr[r][c]; v.y = fi[r][c];
-            *reinterpret_cast<double2 *>(lds + (r * K1 + c) * GROUP_TILE_DOUBLES + 2 * tid) = v;
-        }
-    __syncthreads();
-#pragma unroll
-    for (int k2 = 0; k2 < 16; ++k2) {
-        double2 v = *reinterpret_cast<const double2 *>(tile + 2 * (b + 16 * k2));
-        xr[k2] = v.x; xi[k2] = v.y;
-    }
-    wave_lds_sync();
-    nega_inv(xr, xi, tw, tile, b);
+    ep_product_once<K1, R>(xr, xi, A.ggsw, (uint32_t)(input * A.bits + A.bit), lds, tw, tile, tid, b);
     if (valid) {
         uint64_t *o = A.out + ((inst * A.nodes_out + node) * K1 + p_own) * FHE_N;
 #pragma unroll

@@ -2,9 +2,8 @@
 // encrypted bit g that a circuit bootstrap turned into a Fourier GGSW: what multiplies a plaintext, a key or a whole packed GLWE by the
 // `valid` bit of a tag check (fheaes_gate_ggsw, fheaes_gate_bits, fheaes_gate_packed).
 //
-// The lane mapping, the transform, the decomposition and the multiply-accumulate order are those of cmux_level_kernel (kern_extprod.h)
-// with ct0 = 0: 16 lane-groups of 16, group g < R*K1 owns polynomial g % K1 of instance g / K1; fma chain over the GGSW row p = 0..K1-1,
-// per column the four fmas in that kernel's order.  All R instances of a workgroup share ONE gate, so each GGSW element fetched serves
+// The product itself is ep_product_once (kern_extprod.h), the one cmux_level_kernel calls, here with ct0 = 0: 16 lane-groups of 16, group
+// g < R*K1 owns polynomial g % K1 of instance g / K1.  All R instances of a workgroup share ONE gate, so each GGSW element fetched serves
 // R instances; which gate, which instances and how many (<= R) come from a table the host builds from the caller's runs (GateWg).
 //
 // Two input forms:
@@ -89,53 +88,7 @@ __global__ __launch_bounds__(EP_THREADS, 2) void gate_kernel(const GateArgs A)
         }
     }
     __syncthreads();   // tables visible; every row of the workgroup has been read (in place)
-    nega_fwd(xr, xi, tw, tile, b);
-#pragma unroll
-    for (int k2 = 0; k2 < 16; ++k2) {
-        double2 v; v.x = xr[k2]; v.y = xi[k2];
-        *reinterpret_cast<double2 *>(tile + 2 * (b + 16 * k2)) = v;
-    }
-    __syncthreads();
-    // multiply-accumulate role: thread tid owns Fourier point tid
-    double fr[R][K1], fi[R][K1];
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int c = 0; c < K1; ++c) { fr[r][c] = 0.0; fi[r][c] = 0.0; }
-    const double2 *G = A.ggsw + (size_t)W.gate * (size_t)(K1 * K1 * FHE_H) + tid;
-#pragma unroll
-    for (int p = 0; p < K1; ++p) {
-        double2 bv[K1];
-#pragma unroll
-        for (int c = 0; c < K1; ++c) bv[c] = G[(size_t)(p * K1 + c) * FHE_H];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const double2 d = *reinterpret_cast<const double2 *>(lds + (r * K1 + p) * GROUP_TILE_DOUBLES + 2 * tid);
-#pragma unroll
-            for (int c = 0; c < K1; ++c) {
-                fr[r][c] = __builtin_fma(d.x, bv[c].x, fr[r][c]);
-                fr[r][c] = __builtin_fma(-d.y, bv[c].y, fr[r][c]);
-                fi[r][c] = __builtin_fma(d.x, bv[c].y, fi[r][c]);
-                fi[r][c] = __builtin_fma(d.y, bv[c].x, fi[r][c]);
-            }
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int c = 0; c < K1; ++c) {
-            double2 v; v.x = fr[r][c]; v.y = fi[r][c];
-            *reinterpret_cast<double2 *>(lds + (r * K1 + c) * GROUP_TILE_DOUBLES + 2 * tid) = v;
-        }
-    __syncthreads();
-#pragma unroll
-    for (int k2 = 0; k2 < 16; ++k2) {
-        double2 v = *reinterpret_cast<const double2 *>(tile + 2 * (b + 16 * k2));
-        xr[k2] = v.x; xi[k2] = v.y;
-    }
-    wave_lds_sync();
-    nega_inv(xr, xi, tw, tile, b);
+    ep_product_once<K1, R>(xr, xi, A.ggsw, W.gate, lds, tw, tile, tid, b);
     if (!valid) return;
     if (FORM == GATE_LWE) {
         // sample extract coefficient 0 (sample_extract_kernel's rule at i = 0)

@@ -5,8 +5,8 @@
 //   inv_mix_columns           src/server/decrypt/inv_mix_columns.rs:4-58
 //   inv_shift_rows            src/server/decrypt/inv_shift_rows.rs:5-21
 //   add_round_key             src/server/server.rs:278-282
-//   (no counterpart)          the XTS tweak layer: multiplication by alpha^j in GF(2^128), xts_tweak_kernel below
-//   (no counterpart)          the CMAC subkeys: multiplication by x and x^2 in the big-endian byte order, cmac_subkey_kernel below
+//   (no counterpart)          the XTS tweak layer: multiplication by alpha^j in GF(2^128), bit_rows_kernel over XtsRows below
+//   (no counterpart)          the CMAC subkeys: multiplication by x and x^2 in the big-endian byte order, bit_rows_kernel over CmacRows below
 //   (no counterpart)          the key-unwrap link (RFC 3394): half blocks moved between a state and a register file, kw_link_kernel below
 // All of them but the last are one "gather-add": out[blk][byte] = sum_t src[blk][tab.src[byte][t]][tab.lut[byte][t]] (+ rk[byte]).
 // The round key comes from a source type (LweKeys, PackedKeys below): every layer that adds one is ONE kernel template over that type,
@@ -156,35 +156,48 @@ __host__ __device__ __forceinline__ uint32_t xts_tweak_row(uint32_t j, uint32_t 
     return n;
 }
 
-// out[u][t][i][w] = sum over the row (off0 + t, i) of anchor[u][source][w]: the tweaks off0 .. off0 + n_off - 1 (all <= XTS_MAX_OFFSET)
-// of every unit from its anchor, each output bit gathered from the anchor in ONE sum (doubling step by step would add a ciphertext to
-// itself: the message cancels, the noise does not).  anchor: unit u's [128][lwe_words] at u * anchor_stride words; out:
-// [n_units][n_off][128][lwe_words].  One workgroup per output bit, lanes on consecutive w (rows of kN + 1 words are 8-byte aligned and no
-// more: 8-byte accesses); rows are taken in order, so the workgroups of a unit are adjacent in the grid and the up to 121 offsets that
-// re-read its anchor (2 MB at PARAM_OPT) find it in L2: HBM sees the 16,392 B per output bit that are written.  All offsets in 64 bits.
-__global__ __launch_bounds__(256) void xts_tweak_kernel(const uint64_t *anchor, uint64_t anchor_stride, uint64_t *out, uint64_t n_units, uint32_t off0,
-                                                        uint32_t n_off, uint32_t lwe_words)
+// ---- bit-row gathers: out row r = the sum of at most 4 source rows of ONE block of 128 rows ------------------------------------------------------
+// The XTS tweaks and the CMAC subkeys.  Which block and which rows comes from a by-value rule type with one member,
+//   n = rows.row(r, block, sources):  block = the source block's [128][lwe_words], sources[0..n-1] = its rows to sum, n <= Rows::MAX_SOURCES
+// out: [n_rows][lwe_words].  Each output bit is gathered from its block in ONE sum (doubling step by step would add a ciphertext to itself:
+// the message cancels, the noise does not).  One workgroup per output bit, lanes on consecutive w (rows of kN + 1 words are 8-byte aligned
+// and no more: 8-byte accesses); rows are taken in order, so the workgroups that read one block are adjacent in the grid and re-read it
+// (2 MB at PARAM_OPT) from L2: HBM sees the 16,392 B per output bit that are written.  All offsets in 64 bits.
+template <class Rows>
+__global__ __launch_bounds__(256) void bit_rows_kernel(const Rows rows, uint64_t *out, uint64_t n_rows, uint32_t lwe_words)
 {
-    const uint64_t rows = n_units * n_off * 128;
-    for (uint64_t r = blockIdx.x; r < rows; r += gridDim.x) {
-        const uint32_t i = (uint32_t)(r & 127);
-        const uint64_t ut = r >> 7, u = ut / n_off;
-        uint32_t s[4];
-        const uint32_t n = xts_tweak_row(off0 + (uint32_t)(ut - u * n_off), i, s);
-        const uint64_t *ab = anchor + u * anchor_stride;
-        const uint64_t *p[4];                                    // fully unrolled so that the pointers stay in registers
+    for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const uint64_t *block;
+        uint32_t s[Rows::MAX_SOURCES];
+        const uint32_t n = rows.row(r, block, s);
+        const uint64_t *p[Rows::MAX_SOURCES];                    // fully unrolled so that the pointers stay in registers
 #pragma unroll
-        for (uint32_t t = 0; t < 4; ++t) p[t] = ab + (uint64_t)(t < n ? s[t] : 0u) * lwe_words;
+        for (uint32_t t = 0; t < Rows::MAX_SOURCES; ++t) p[t] = block + (uint64_t)(t < n ? s[t] : 0u) * lwe_words;
         uint64_t *o = out + r * lwe_words;
         for (uint32_t w = threadIdx.x; w < lwe_words; w += blockDim.x) {
             uint64_t v = 0;
 #pragma unroll
-            for (uint32_t t = 0; t < 4; ++t)
+            for (uint32_t t = 0; t < Rows::MAX_SOURCES; ++t)
                 if (t < n) v += p[t][w];
             o[w] = v;
         }
     }
 }
+
+// out[u][t][i] = the row (off0 + t, i) of xts_tweak_row over anchor[u]: the tweaks off0 .. off0 + n_off - 1 (all <= XTS_MAX_OFFSET) of every
+// unit from its anchor, unit u's [128][lwe_words] at u * anchor_stride words.  The up to 121 offsets of a unit re-read its anchor.
+struct XtsRows {
+    static constexpr uint32_t MAX_SOURCES = 4;
+    const uint64_t *anchor;
+    uint64_t anchor_stride;
+    uint32_t n_off, off0;
+    __device__ __forceinline__ uint32_t row(uint64_t r, const uint64_t *&block, uint32_t (&sources)[4]) const
+    {
+        const uint64_t ut = r >> 7, u = ut / n_off;
+        block = anchor + u * anchor_stride;
+        return xts_tweak_row(off0 + (uint32_t)(ut - u * n_off), (uint32_t)(r & 127), sources);
+    }
+};
 
 // XTS whitening, before and after the cipher: dst[b] = (src ? src[b] : 0) + tweaks[tweak_of_block[b]] + trivial(clear block b).
 // dst, src: [n_blocks][16][8][lwe_words] (src == dst: in place); tweaks: rows of 128 lwe_words words; clear: [n_blocks][16] bytes, or null
@@ -323,30 +336,19 @@ __host__ __device__ __forceinline__ uint32_t cmac_subkey_row(uint32_t which, uin
     return n;
 }
 
-// out[key][which][i][w] = sum over the row (which, i) of l[key][source][w]: both subkeys of every key in ONE launch, each output bit
-// gathered from L in one sum (K2 is not a doubling of the computed K1, for the reason given above xts_tweak_kernel).  l:
-// [n_keys][128][lwe_words]; out: [n_keys][2][128][lwe_words].  One workgroup per output row and the grid IS the rows -- 256 n_keys, 2^24 at
-// FHEAES_MAX_KEYS keys, inside one grid dimension: there is no second pass.  Lanes on consecutive w, 8-byte accesses as above; rows are
-// taken in order, so the 256 workgroups of a key are adjacent in the grid and re-read its L (2 MB at PARAM_OPT) from L2.  All offsets in
-// 64 bits.
-__global__ __launch_bounds__(256) void cmac_subkey_kernel(const uint64_t *l, uint64_t *out, uint32_t lwe_words)
-{
-    const uint64_t r = blockIdx.x;
-    uint32_t s[3];
-    const uint32_t n = cmac_subkey_row((uint32_t)(r >> 7) & 1u, (uint32_t)(r & 127), s);
-    const uint64_t *lb = l + (r >> 8) * 128 * lwe_words;
-    const uint64_t *p[3];                                        // fully unrolled so that the pointers stay in registers
-#pragma unroll
-    for (uint32_t t = 0; t < 3; ++t) p[t] = lb + (uint64_t)(t < n ? s[t] : 0u) * lwe_words;
-    uint64_t *o = out + r * lwe_words;
-    for (uint32_t w = threadIdx.x; w < lwe_words; w += blockDim.x) {
-        uint64_t v = 0;
-#pragma unroll
-        for (uint32_t t = 0; t < 3; ++t)
-            if (t < n) v += p[t][w];
-        o[w] = v;
+// out[key][which][i] = the row (which, i) of cmac_subkey_row over l[key]: both subkeys of every key in ONE launch of bit_rows_kernel (K2 is
+// not a doubling of the computed K1, for the reason given there).  l: [n_keys][128][lwe_words]; out: [n_keys][2][128][lwe_words], 256 rows
+// per key.
+struct CmacRows {
+    static constexpr uint32_t MAX_SOURCES = 3;
+    const uint64_t *l;
+    uint32_t lwe_words;
+    __device__ __forceinline__ uint32_t row(uint64_t r, const uint64_t *&block, uint32_t (&sources)[3]) const
+    {
+        block = l + (r >> 8) * 128 * lwe_words;
+        return cmac_subkey_row((uint32_t)(r >> 7) & 1u, (uint32_t)(r & 127), sources);
     }
-}
+};
 
 // Rows of bytes moved between strided sets, one set per AES key: the word operations of the key expansion over all keys at once (RotWord,
 // w[i-1] or the SubWord result + w[i-Nk] + Rcon, placing refreshed words at their stride) and the strided copies of the round-key

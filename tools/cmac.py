@@ -20,7 +20,7 @@ makes the tool exit 1.
 1.03 is the margin every composed call here was given against a prediction from older entry points; what the call adds is K6 launches
 of well under a millisecond.
 
-    (b)  cmac_subkey_kernel on 64 keys (fheaes_cmac_double: 128 blocks out) against xts_tweak_kernel on 64 units and offsets 1 and 2
+    (b)  bit_rows_kernel<CmacRows> on 64 keys (fheaes_cmac_double: 128 blocks out) against bit_rows_kernel<XtsRows> on 64 units and offsets 1 and 2
          (fheaes_xts_tweaks: 128 blocks out, the same rows in the other byte order), device events around --reps calls of each,
          alternating; bound 1.5.
 

@@ -15,7 +15,7 @@ Every block of every output is decrypted with the client key and compared with a
 
 1.03 is the margin every earlier entry point of this kind was given against a prediction from older entry points.
 
-    (b)  xts_tweak_kernel over 128 tweak blocks (fheaes_xts_tweaks, 4 units x 32 offsets) against gather_add_kernel with a four-term table
+    (b)  bit_rows_kernel<XtsRows> over 128 tweak blocks (fheaes_xts_tweaks, 4 units x 32 offsets) against gather_add_kernel with a four-term table
          and no key over the same number of output bytes (fheaes_inv_mix_columns_batch on 128 blocks), device events around --reps
          calls of each, alternating; bound 1.5.
 
