@@ -1101,7 +1101,10 @@ class ServerGroup:
             dec_round_keys1, round_keys2, units, ct[lo:lo + k], unit_bytes, int(first_block) + lo, out=shard))
 
     def aes_key_expansion(self, key):
-        return self.servers[0].aes_key_expansion(key)
+        """expanded on context 0; finished before returning, since device round keys are then read from the other contexts' streams"""
+        rk = self.servers[0].aes_key_expansion(key)
+        self.servers[0].synchronize()
+        return rk
 
     # many AES keys: the keyed calls shard on blocks, every context reading the whole set of round keys; the per-key calls shard on keys
     def _fan_out_keys(self, arr, out, fn):
