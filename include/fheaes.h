@@ -727,7 +727,8 @@ int fheaes_gate_plan(const uint64_t *bits_of_gate, uint64_t n_gates, uint32_t k,
  * is the check it can run.  The engine is deterministic and every blind-rotation form writes the same words, so S sampled rows of a
  * blind-rotation launch are run again through the latency form (kern_blindrot_latency.h: it parks nothing and shares no slot pool, owner
  * words or generation plan with the throughput forms) and compared on the device, bit for bit.  A difference is a defect of the engine or
- * of the machine, never noise.  Off by default; covers the blind rotation only (DESIGN.md says what is caught and what is not).
+ * of the machine, never noise.  Off by default; these four calls cover the blind rotation, the
+ * section after them the two key switches (DESIGN.md says what is caught and what is not).
  * None of these calls takes data arrays or a memspace.
  *
  * fheaes_audit_set: `rows` = 0 (default) turns the audit off and frees its buffers; `rows` in 1..FHEAES_AUDIT_MAX_ROWS (one latency-form
@@ -760,6 +761,40 @@ int fheaes_audit_read(fheaes_ctx *ctx, uint64_t *launches, uint64_t *rows_checke
  * the hook without a write.  One wrong word in the caller's own result and nothing else.  A zero mask, a word beyond kN or a NULL context:
  * FHEAES_ERR_INVALID. */
 int fheaes_audit_debug(fheaes_ctx *ctx, uint64_t row, uint32_t word, uint64_t xor_mask);
+
+/* ---- audit of the key switches ----------------------------------------------------- */
+/* The same check for the two integer stages, K1 (the LWE key switch, FHEAES_STAGE_KEYSWITCH) and K3 (the private functional packing key
+ * switch, FHEAES_STAGE_PFPKS).  Both are an exact integer matrix product mod 2^64, so any order of evaluation gives the same words: S sampled
+ * rows of every launch are computed again by a plain form (kern_audit.h: the digits recomputed from the input words, the key words
+ * recombined from the resident byte planes, one 64-bit multiply-add per term -- no matrix cores, no digit planes, no LDS-DMA) and compared
+ * on the device, bit for bit.  Each stage has its own rows, seed, counters, records, launch number and hook; the launch number counts that
+ * stage's audited launches alone, so the rows the blind rotation's audit samples do not depend on whether the key switches are audited.
+ * `stage` = FHEAES_STAGE_BLIND_ROTATE: the first three calls ARE fheaes_audit_set / _read / _debug and share their state.  Any other stage,
+ * a NULL context or `rows` > FHEAES_AUDIT_MAX_ROWS: FHEAES_ERR_INVALID.
+ *
+ * fheaes_audit_stage_set: as fheaes_audit_set -- `rows` = 0 turns the stage's audit off and frees its buffers (fheaes_destroy frees them
+ * too); else every launch of the stage of m >= `min_rows` rows is audited on S = min(rows, m) rows, the rows fheaes_audit_rows(seed,
+ * launch, m, rows) names: the WoPBS chunks and round windows of every call, the gate's bootstrap, fheaes_keyswitch_batch,
+ * fheaes_pfpks_batch, and the single-block launches of fheaes_pack_bits, fheaes_pack_bits_mod and fheaes_pack_round_keys.  The only place
+ * that allocates (the gathered rows of the plain form and the state: two allocations; refused: FHEAES_ERR_NOMEM and the stage is off); an
+ * audited call allocates nothing and the host waits for nothing.  Zeroes the stage's counters and launch number, drops its pending hook.
+ * With profiling on the audit's time counts into the stage's total_ms; `launches` and `units` count the product launch only.
+ * fheaes_audit_stage_read: as fheaes_audit_read.  A record is {launch, row, word, that word of the product launch, that word of the plain
+ * form}; `word` is the offset among the words the launch wrote for the row: the column for K1, z (k+1) N + o for key block z of K3 (o
+ * alone in a single-block launch).
+ * fheaes_audit_stage_debug: test hook, one shot, as fheaes_audit_debug: the stage's next audited launch XORs `xor_mask` into word `word` of
+ * row `row` of its output; a row or a word beyond that launch's drops the hook without a write.  A zero mask or a `word` beyond the
+ * stage's widest row (n + 1 words for K1, (k+1)^2 N for K3): FHEAES_ERR_INVALID. */
+int fheaes_audit_stage_set(fheaes_ctx *ctx, int stage, uint32_t rows, uint64_t min_rows, uint64_t seed);
+int fheaes_audit_stage_read(fheaes_ctx *ctx, int stage, uint64_t *launches, uint64_t *rows_checked, uint64_t *rows_wrong, uint64_t *records_out,
+                            uint64_t record_cap, uint64_t *record_n);
+int fheaes_audit_stage_debug(fheaes_ctx *ctx, int stage, uint64_t row, uint32_t word, uint64_t xor_mask);
+/* Test and tool hook: the plain form alone over all m rows of lwe_in [m][kN+1], in groups of FHEAES_AUDIT_MAX_ROWS rows, no product launch,
+ * no workspace, nothing counted under any stage.  DEVICE pointers only (it takes no memspace and stages nothing): it only enqueues on the
+ * context's stream, as a FHEAES_DEVICE call does.  `stage` = FHEAES_STAGE_KEYSWITCH: `block` = -1, out [m][n+1] as fheaes_keyswitch_batch
+ * writes it.  FHEAES_STAGE_PFPKS: `block` = -1: out [m][k+1][(k+1)N] as fheaes_pfpks_batch writes it; `block` = 0..k: that key block alone,
+ * out [m][(k+1)N], as the launch of fheaes_pack_bits (block k).  Another stage or block: FHEAES_ERR_INVALID. */
+int fheaes_audit_plain_batch(fheaes_ctx *ctx, int stage, const uint64_t *lwe_in, uint64_t m, int block, uint64_t *out);
 
 /* ---- measurement --------------------------------------------------------------- */
 #define FHEAES_STAGE_KEYSWITCH 0

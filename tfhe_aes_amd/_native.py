@@ -26,6 +26,7 @@ WS_BUFFERS = 17                 # FHEAES_WS_BUFFERS: the scratch buffers fheaes_
 WS_CLASSES = ("f64", "words", "tables")                  # FHEAES_WS_F64 / _WORDS / _TABLES
 WS_POISON_FILL, WS_POISON_RELEASE = 0, 1                 # FHEAES_WS_POISON_*: the modes of fheaes_workspace_poison
 STAGES = ("keyswitch", "blind_rotate", "pfpks", "ggsw_fft", "vertical_packing", "linear")
+AUDIT_STAGES = ("keyswitch", "blind_rotate", "pfpks")    # the stages that have an audit (fheaes_audit_stage_set), in the order they run
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -163,6 +164,10 @@ SIGNATURES = {
     "fheaes_audit_rows": (_c.c_int, [_c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_uint32, _u64p]),
     "fheaes_audit_read": (_c.c_int, [_ctx, _u64p, _u64p, _u64p, _u64p, _c.c_uint64, _u64p]),
     "fheaes_audit_debug": (_c.c_int, [_ctx, _c.c_uint64, _c.c_uint32, _c.c_uint64]),
+    "fheaes_audit_stage_set": (_c.c_int, [_ctx, _c.c_int, _c.c_uint32, _c.c_uint64, _c.c_uint64]),
+    "fheaes_audit_stage_read": (_c.c_int, [_ctx, _c.c_int, _u64p, _u64p, _u64p, _u64p, _c.c_uint64, _u64p]),
+    "fheaes_audit_stage_debug": (_c.c_int, [_ctx, _c.c_int, _c.c_uint64, _c.c_uint32, _c.c_uint64]),
+    "fheaes_audit_plain_batch": (_c.c_int, [_ctx, _c.c_int, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_void_p]),
     "fheaes_workspace_info": (_c.c_int, [_ctx, _c.c_uint32, _c.c_char_p, _c.c_size_t, _u64p, _c.POINTER(_c.c_int), _u64p, _u64p]),
     "fheaes_workspace_poison": (_c.c_int, [_ctx, _c.c_int, _u64p]),
     "fheaes_alloc_debug": (_c.c_int, [_ctx, _c.c_uint64, _u64p]),
@@ -741,6 +746,35 @@ class Engine:
     def audit_debug(self, row: int, word: int, xor_mask: int):
         """test hook (fheaes_audit_debug), one shot: the next audited launch XORs xor_mask into word `word` of row `row` of its output"""
         self._check(self._lib.fheaes_audit_debug(self._h, int(row), int(word), int(xor_mask)))
+
+    @staticmethod
+    def _audit_stage(stage) -> int:
+        """a name of AUDIT_STAGES (or a stage number of STAGES) -> FHEAES_STAGE_*"""
+        return STAGES.index(stage) if isinstance(stage, str) else int(stage)
+
+    def audit_stage_set(self, stage, rows: int, min_rows: int = 0, seed: int = 0):
+        """fheaes_audit_stage_set: the audit of one stage of AUDIT_STAGES ("blind_rotate": audit_set); for a key switch every launch of at
+        least min_rows rows is computed again on min(rows, m) sampled rows by the plain form; zeroes that stage's counters and launch number"""
+        self._check(self._lib.fheaes_audit_stage_set(self._h, self._audit_stage(stage), int(rows), int(min_rows), int(seed) & (2 ** 64 - 1)))
+
+    def audit_stage_read(self, stage) -> dict:
+        """audit_read for one stage of AUDIT_STAGES; a record's word is the offset among the words the launch wrote for the row"""
+        la, ch, wr, n = _c.c_uint64(), _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
+        rec = np.zeros((AUDIT_RECORDS, 5), dtype=np.uint64)
+        self._check(self._lib.fheaes_audit_stage_read(self._h, self._audit_stage(stage), _c.byref(la), _c.byref(ch), _c.byref(wr), rec.ctypes.data_as(_u64p),
+                                                      AUDIT_RECORDS, _c.byref(n)))
+        return {"launches": la.value, "rows_checked": ch.value, "rows_wrong": wr.value, "records": rec[:n.value]}
+
+    def audit_stage_debug(self, stage, row: int, word: int, xor_mask: int):
+        """test hook (fheaes_audit_stage_debug), one shot: that stage's next audited launch XORs xor_mask into word `word` of row `row`"""
+        self._check(self._lib.fheaes_audit_stage_debug(self._h, self._audit_stage(stage), int(row), int(word), int(xor_mask)))
+
+    def audit_plain_batch(self, stage, lwe_in, out, m: int, block: int = -1):
+        """test and tool hook (fheaes_audit_plain_batch): the plain form of a key switch alone over m rows; "keyswitch": out [m][n+1];
+        "pfpks": out [m][k+1][(k+1)N], or [m][(k+1)N] for one key block 0..k.  Device tensors only: the hook stages nothing"""
+        if self._space(lwe_in, out) != DEVICE:
+            raise ValueError("audit_plain_batch takes device tensors only")
+        self._check(self._lib.fheaes_audit_plain_batch(self._h, self._audit_stage(stage), _ptr(lwe_in)[0], int(m), int(block), _ptr(out)[0]))
 
     def workspace_info(self) -> list[dict]:
         """test hook (fheaes_workspace_info): the context's scratch buffers, each {"name", "bytes", "class": one of WS_CLASSES, "first",

@@ -237,6 +237,112 @@ int fheaes_audit_debug(fheaes_ctx *ctx, uint64_t row, uint32_t word, uint64_t xo
     ctx->audit_hook_row = row; ctx->audit_hook_word = word; ctx->audit_hook_mask = xor_mask;
     return FHEAES_OK;
 }
+// ---- the audit of the key switches (kern_audit.h, launch_stage_audit); FHEAES_STAGE_BLIND_ROTATE: the calls above ---------------------
+namespace {
+StageAudit *stage_audit(fheaes_ctx *c, int stage)
+{
+    return stage == FHEAES_STAGE_KEYSWITCH ? &c->ks_audit : stage == FHEAES_STAGE_PFPKS ? &c->pf_audit : nullptr;
+}
+// the written words of one row of the stage's widest launch: K1 n + 1, K3 the k + 1 key blocks
+uint32_t stage_row_words(const fheaes_ctx *c, int stage) { return stage == FHEAES_STAGE_KEYSWITCH ? c->n + 1 : c->k1 * c->k1 * FHE_N; }
+}  // namespace
+int fheaes_audit_stage_set(fheaes_ctx *ctx, int stage, uint32_t rows, uint64_t min_rows, uint64_t seed)
+{
+    if (!ctx) return FHEAES_ERR_INVALID;
+    if (stage == FHEAES_STAGE_BLIND_ROTATE) return fheaes_audit_set(ctx, rows, min_rows, seed);
+    CtxLock lock__(ctx);
+    StageAudit *au = stage_audit(ctx, stage);
+    if (!au) return ctx->fail(FHEAES_ERR_INVALID, "audit_stage_set: stage %d has no audit (the key switch, the blind rotation, the packing key switch)", stage);
+    if (rows > AUDIT_MAX_ROWS) return ctx->fail(FHEAES_ERR_INVALID, "audit_stage_set: at most %d rows per launch (got %u)", AUDIT_MAX_ROWS, rows);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    au->rows = 0;                        // off until everything below has succeeded
+    au->hook = false;
+    au->launch = 0;
+    if (rows == 0) {
+        for (DevBuf *b : {&au->out, &au->state})
+            if (b->p) { HIP_TRY(ctx, hipFree(b->p)); b->p = nullptr; b->bytes = 0; }
+        return FHEAES_OK;
+    }
+    // for FHEAES_AUDIT_MAX_ROWS rows whatever `rows` is, as fheaes_audit_set does
+    TRY(ensure(ctx, au->out, (size_t)AUDIT_MAX_ROWS * stage_row_words(ctx, stage) * 8));
+    TRY(ensure(ctx, au->state, AUDIT_STATE_WORDS * 8));
+    HIP_TRY(ctx, hipMemset(au->state.p, 0, AUDIT_STATE_WORDS * 8));
+    au->min_rows = min_rows;
+    au->seed = seed;
+    au->rows = rows;
+    return FHEAES_OK;
+}
+int fheaes_audit_stage_read(fheaes_ctx *ctx, int stage, uint64_t *launches, uint64_t *rows_checked, uint64_t *rows_wrong, uint64_t *records_out,
+                            uint64_t record_cap, uint64_t *record_n)
+{
+    if (!ctx) return FHEAES_ERR_INVALID;
+    if (stage == FHEAES_STAGE_BLIND_ROTATE) return fheaes_audit_read(ctx, launches, rows_checked, rows_wrong, records_out, record_cap, record_n);
+    CtxLock lock__(ctx);
+    StageAudit *au = stage_audit(ctx, stage);
+    if (!au) return ctx->fail(FHEAES_ERR_INVALID, "audit_stage_read: stage %d has no audit", stage);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t st[AUDIT_STATE_WORDS] = {};            // audit off: all zero
+    if (au->state.p) HIP_TRY(ctx, hipMemcpy(st, au->state.p, sizeof st, hipMemcpyDeviceToHost));
+    const uint64_t n = std::min<uint64_t>(st[AUDIT_ST_WRONG], AUDIT_RECORDS);
+    if (records_out && record_cap < n)
+        return ctx->fail(FHEAES_ERR_INVALID, "audit_stage_read: %llu records do not fit record_cap = %llu", (unsigned long long)n, (unsigned long long)record_cap);
+    if (launches) *launches = st[AUDIT_ST_LAUNCHES];
+    if (rows_checked) *rows_checked = st[AUDIT_ST_CHECKED];
+    if (rows_wrong) *rows_wrong = st[AUDIT_ST_WRONG];
+    if (records_out && n) std::memcpy(records_out, st + AUDIT_ST_RECORDS, n * AUDIT_RECORD_WORDS * 8);
+    if (record_n) *record_n = n;
+    return FHEAES_OK;
+}
+int fheaes_audit_stage_debug(fheaes_ctx *ctx, int stage, uint64_t row, uint32_t word, uint64_t xor_mask)
+{
+    if (!ctx) return FHEAES_ERR_INVALID;
+    if (stage == FHEAES_STAGE_BLIND_ROTATE) return fheaes_audit_debug(ctx, row, word, xor_mask);
+    CtxLock lock__(ctx);
+    StageAudit *au = stage_audit(ctx, stage);
+    if (!au) return ctx->fail(FHEAES_ERR_INVALID, "audit_stage_debug: stage %d has no audit", stage);
+    if (xor_mask == 0 || word >= stage_row_words(ctx, stage))
+        return ctx->fail(FHEAES_ERR_INVALID, "audit_stage_debug: a non-zero mask and a word below %u (got mask %#llx, word %u)", stage_row_words(ctx, stage),
+                         (unsigned long long)xor_mask, word);
+    au->hook = true;
+    au->hook_row = row; au->hook_word = word; au->hook_mask = xor_mask;
+    return FHEAES_OK;
+}
+int fheaes_audit_plain_batch(fheaes_ctx *ctx, int stage, const uint64_t *lwe_in, uint64_t m, int block, uint64_t *out)
+{
+    if (!ctx) return FHEAES_ERR_INVALID;
+    CtxLock lock__(ctx);
+    const bool k1 = stage == FHEAES_STAGE_KEYSWITCH;
+    if (!k1 && stage != FHEAES_STAGE_PFPKS) return ctx->fail(FHEAES_ERR_INVALID, "audit_plain_batch: stage %d has no plain form (the two key switches have)", stage);
+    if (block < -1 || block > (k1 ? -1 : (int)ctx->k))
+        return ctx->fail(FHEAES_ERR_INVALID, "audit_plain_batch: block %d (the key switch takes -1, the packing key switch -1 .. %u)", block, ctx->k);
+    TRY(check_keys(ctx));
+    if (!lwe_in || !out) return ctx->fail(FHEAES_ERR_INVALID, "null pointer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t gsz = ctx->k1 * FHE_N;
+    const unsigned nz = k1 || block >= 0 ? 1 : ctx->k1;
+    const uint64_t row_words = k1 ? ctx->n + 1 : (uint64_t)nz * gsz;
+    // device pointers only: a hook of tests and tools, which hold their arrays on the device; it stages nothing and only enqueues
+    KeyswitchPlainArgs a{};
+    a.in_stride = ctx->big1; a.out_stride = row_words; a.body_index = -1;
+    if (k1) {
+        a.n_in = ctx->big; a.bfrag = ctx->ksk_frag; a.ksteps = ctx->ks_ksteps; a.coltiles = ctx->ks_coltiles; a.ncols = ctx->n + 1;
+        a.body_index = (int32_t)ctx->big; a.body_col = ctx->n;
+    } else {
+        a.n_in = ctx->big1; a.bfrag = ctx->pfpksk_frag; a.ksteps = ctx->pf_ksteps; a.coltiles = ctx->pf_coltiles; a.ncols = gsz;
+        if (block >= 0) a.bfrag += (size_t)block * ctx->pf_ksteps * ctx->pf_coltiles * 8 * 1024;
+        a.out_z_stride = nz > 1 ? gsz : 0;
+    }
+    // in groups of FHEAES_AUDIT_MAX_ROWS rows: the launches the audit makes
+    for (uint64_t r0 = 0; r0 < m; r0 += AUDIT_MAX_ROWS) {
+        a.in = lwe_in + r0 * ctx->big1; a.out = out + r0 * row_words;
+        a.S = (uint32_t)std::min<uint64_t>(AUDIT_MAX_ROWS, m - r0); a.m = a.S;
+        launch_keyswitch_plain(ctx, stage, a, nz);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return FHEAES_OK;
+}
 const char *fheaes_version(void) { return FHEAES_VERSION_STR; }
 
 const char *fheaes_last_error(const fheaes_ctx *ctx)

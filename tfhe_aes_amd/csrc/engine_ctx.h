@@ -28,6 +28,20 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
+// The audit of one key-switching stage (fheaes_audit_stage_set, kern_audit.h): rows > 0 = every launch of the stage of at least min_rows rows
+// is computed again on min(rows, m) sampled rows by the plain form; launch = audited launches of THIS stage since its stage_set (the rows
+// the blind rotation's audit samples do not depend on whether the key switches are audited).  out: the gathered rows of the plain form,
+// state: the counters and records (AUDIT_STATE_WORDS); allocated by stage_set and never by a launch, state and not scratch like the
+// blind rotation's.  hook*: fheaes_audit_stage_debug, one shot.
+struct StageAudit {
+    uint32_t rows = 0;
+    uint64_t min_rows = 0, seed = 0, launch = 0;
+    DevBuf out, state;
+    bool hook = false;
+    uint64_t hook_row = 0, hook_mask = 0;
+    uint32_t hook_word = 0;
+};
+
 struct fheaes_ctx {
     fheaes_params p{};
     const uint64_t id = g_next_ctx_id.fetch_add(1);
@@ -67,6 +81,7 @@ struct fheaes_ctx {
     bool audit_hook = false;
     uint64_t audit_hook_row = 0, audit_hook_mask = 0;
     uint32_t audit_hook_word = 0;
+    StageAudit ks_audit, pf_audit;       // the key switches' (launch_keyswitch, launch_pfpks)
     // test hook (fheaes_alloc_debug), one shot: alloc_seen counts the device allocations ctx_malloc has been asked for since the hook was
     // last set; the alloc_fail_nth-th of them (0: none) goes to the runtime with a size it must refuse
     uint64_t alloc_seen = 0, alloc_fail_nth = 0;

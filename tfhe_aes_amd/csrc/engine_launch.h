@@ -105,6 +105,54 @@ AesWindowPlan aes_window_plan(uint64_t n, uint64_t steps, uint32_t cu_count, uin
     return pl;
 }
 
+// ---- the plain form of the key switches and the audit behind their launches (kern_audit.h) ---------------------------------------
+static_assert(KSP_KSTEP == KS_KSTEP, "kern_audit.h reads the B fragments of kern_keyswitch.h");
+#define KSP_ROWS_K1 4          /* rows per workgroup: K1 has few column tiles (42 at PARAM_OPT), so more row groups */
+#define KSP_ROWS_K3 8
+
+// rows 0 .. a.S - 1 (or the a.S sampled rows) of key switch `stage` through the plain form, nz key blocks
+void launch_keyswitch_plain(fheaes_ctx *c, int stage, const KeyswitchPlainArgs &a, unsigned nz)
+{
+    const unsigned gy = (a.coltiles + KSP_COL_TILES - 1) / KSP_COL_TILES;
+    if (stage == FHEAES_STAGE_KEYSWITCH)
+        hipLaunchKernelGGL((keyswitch_plain_kernel<2, 6, KSP_ROWS_K1>), dim3((a.S + KSP_ROWS_K1 - 1) / KSP_ROWS_K1, gy, nz), dim3(KSP_THREADS), 0, c->stream, a);
+    else
+        hipLaunchKernelGGL((keyswitch_plain_kernel<12, 3, KSP_ROWS_K3>), dim3((a.S + KSP_ROWS_K3 - 1) / KSP_ROWS_K3, gy, nz), dim3(KSP_THREADS), 0, c->stream, a);
+}
+
+// what the plain form takes over from a product launch: its input, its key bytes, its real dimensions; n_in: the words of a row it decomposes
+KeyswitchPlainArgs keyswitch_plain_args(const KeyswitchArgs &prod, uint32_t n_in)
+{
+    KeyswitchPlainArgs a{};
+    a.in = prod.in; a.in_stride = prod.in_stride; a.n_in = n_in;
+    a.bfrag = prod.bfrag; a.ksteps = prod.ksteps; a.coltiles = prod.coltiles; a.ncols = prod.ncols;
+    a.body_index = prod.body_index; a.body_col = prod.body_col;
+    return a;
+}
+
+// The audit of one key-switch launch, behind it on the same stream and inside its StageScope, under launch_audit's rules: the time counts
+// into the stage, `launches` and `units` count the product launch alone, nothing is allocated (fheaes_audit_stage_set did), the host waits
+// for nothing.  `prod`: the product launch's arguments, nz its key blocks: a row's written words are the nz ncols words at
+// out + row out_stride (K3 over all blocks: out_z_stride = ncols), and a record's `word` is the offset among them.
+int launch_stage_audit(fheaes_ctx *c, int stage, StageAudit &au, const KeyswitchArgs &prod, uint32_t n_in, unsigned nz)
+{
+    const uint64_t m = prod.m, launch = au.launch++;
+    const uint32_t S = (uint32_t)std::min<uint64_t>(au.rows, m), row_words = nz * prod.ncols;
+    if (au.hook) {
+        au.hook = false;                             // one shot; a row or a word beyond this launch's is dropped without a write
+        if (au.hook_row < m && au.hook_word < row_words)
+            hipLaunchKernelGGL(audit_tamper_kernel, dim3(1), dim3(1), 0, c->stream, prod.out, (uint32_t)prod.out_stride, au.hook_row, au.hook_word, au.hook_mask);
+    }
+    KeyswitchPlainArgs a = keyswitch_plain_args(prod, n_in);
+    a.out = (uint64_t *)au.out.p; a.out_stride = row_words; a.out_z_stride = nz > 1 ? prod.ncols : 0;
+    a.seed = au.seed; a.launch = launch; a.m = m; a.S = S; a.sampled = 1;
+    launch_keyswitch_plain(c, stage, a, nz);
+    hipLaunchKernelGGL(audit_compare_rows_kernel, dim3(S), dim3(AUDIT_THREADS), 0, c->stream, prod.out, prod.out_stride, a.out, row_words, au.seed, launch, m, S,
+                       (uint64_t *)au.state.p);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
+
 // ---- kernel launchers ------------------------------------------------------------------------
 int launch_keyswitch(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out)
 {
@@ -123,6 +171,7 @@ int launch_keyswitch(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *ou
     dim3 grid((c->ks_coltiles + KSL_COL_TILES - 1) / KSL_COL_TILES, (unsigned)((m + 16 * KSL_CT_TILES - 1) / (16 * KSL_CT_TILES)), 1);
     ks_launch_mfma_lds(1, grid, c->stream, a);
     HIP_TRY(c, hipGetLastError());
+    if (c->ks_audit.rows && m >= c->ks_audit.min_rows) TRY(launch_stage_audit(c, FHEAES_STAGE_KEYSWITCH, c->ks_audit, a, c->big, 1));
     return FHEAES_OK;
 }
 
@@ -146,6 +195,7 @@ int launch_pfpks(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out, u
     dim3 grid((c->pf_coltiles + KSL_COL_TILES - 1) / KSL_COL_TILES, (unsigned)((m + 16 * KSL_CT_TILES - 1) / (16 * KSL_CT_TILES)), block >= 0 ? 1 : c->k1);
     ks_launch_mfma_lds(2, grid, c->stream, a);
     HIP_TRY(c, hipGetLastError());
+    if (c->pf_audit.rows && m >= c->pf_audit.min_rows) TRY(launch_stage_audit(c, FHEAES_STAGE_PFPKS, c->pf_audit, a, c->big1, grid.z));
     return FHEAES_OK;
 }
 

@@ -317,16 +317,38 @@ class AuditReport:
 
 
 class AuditMismatch(_native.FheAesError):
-    """the audit found rows of a blind-rotation launch that the latency form computes differently: a defect of the engine or of the
-    machine, and some result since Server.audit() is wrong.  `report`: the AuditReport, `records`: its records"""
+    """the audit found rows of a launch that the stage's second form computes differently (the latency form of the blind rotation, the plain
+    form of a key switch): a defect of the engine or of the machine, and some result since Server.audit() is wrong.  `stage`: the first
+    stage of _native.AUDIT_STAGES with a wrong row, `report`: that stage's AuditReport, `records`: its records, `reports`: every enabled
+    stage's report by name"""
 
-    def __init__(self, report: AuditReport):
+    def __init__(self, report: AuditReport, stage: str = "blind_rotate", reports: dict | None = None):
         first = report.records[0] if report.records else None
-        super().__init__(-3, "the audit found %d wrong rows in %d checked over %d launches%s" % (
-            report.rows_wrong, report.rows_checked, report.launches,
+        super().__init__(-3, "the audit%s found %d wrong rows in %d checked over %d launches%s" % (
+            "" if stage == "blind_rotate" else " of stage %s" % stage, report.rows_wrong, report.rows_checked, report.launches,
             "" if first is None else "; first: launch %d row %d word %d, %#018x for %#018x" % (first.launch, first.row, first.word, first.got, first.want)))
+        self.stage = stage
         self.report = report
         self.records = report.records
+        self.reports = {stage: report} if reports is None else reports
+
+
+def _audit_stages(stages) -> tuple:
+    """`stages` as a tuple in the order of _native.AUDIT_STAGES; a name outside it is a ValueError"""
+    stages = (stages,) if isinstance(stages, str) else tuple(stages)
+    unknown = [s for s in stages if s not in _native.AUDIT_STAGES]
+    if unknown:
+        raise ValueError("audit stages are a subset of %r (got %r)" % (_native.AUDIT_STAGES, unknown))
+    return tuple(s for s in _native.AUDIT_STAGES if s in stages)
+
+
+def _audit_check(reports: dict) -> AuditReport:
+    """reports: the blind rotation's (all zero while its audit is off) and every enabled key switch's.  Raises AuditMismatch for the first
+    stage with a wrong row; else the blind rotation's report"""
+    for stage, report in reports.items():
+        if report.rows_wrong:
+            raise AuditMismatch(report, stage, reports)
+    return reports["blind_rotate"]
 
 
 class Server:
@@ -340,6 +362,7 @@ class Server:
         # device temporaries this wrapper created for calls that are still in flight on the engine's stream; they must
         # outlive the kernels that read them (torch's caching allocator would hand the block out again): freed in synchronize()
         self._inflight = []
+        self._audit_stages = ()          # the stages audit() enabled, in the order of _native.AUDIT_STAGES
         if clone_from is not None:
             self.engine.clone_keys_from(clone_from.engine)
         else:
@@ -946,25 +969,36 @@ class Server:
     aes_decryption = aes_decrypt
 
     # ---- the audit: a check of the blind rotation that needs no secret key (fheaes_audit_set) -------------------------------------------
-    def audit(self, rows: int = 64, min_bits: int = 0, seed: int | None = None):
-        """Re-run `rows` sampled rows (0: off; at most _native.AUDIT_MAX_ROWS) of every blind-rotation launch of at least min_bits bits
-        through the latency form and compare on the GPU, bit for bit; `seed` None draws 64 bits from os.urandom.  Zeroes the counters.
-        Nothing waits for the comparison: ask audit_report() / audit_check() once the results matter."""
+    def audit(self, rows: int = 64, min_bits: int = 0, seed: int | None = None, stages=("blind_rotate",)):
+        """Re-run `rows` sampled rows (0: off; at most _native.AUDIT_MAX_ROWS) of every launch of at least min_bits bits of the `stages` (a
+        subset of _native.AUDIT_STAGES) through the stage's second form -- the latency form of the blind rotation, the plain form of the
+        key switches -- and compare on the GPU, bit for bit; `seed` None draws 64 bits from os.urandom.  Zeroes the counters; a stage
+        that is not named is turned off, and rows = 0 turns every stage off.  Nothing waits for the comparison: ask audit_report() /
+        audit_check() once the results matter."""
+        stages = _audit_stages(stages) if rows else ()
         if seed is None:
             seed = int.from_bytes(os.urandom(8), "little")
-        self.engine.audit_set(rows, min_bits, seed)
+        others = [s for s in _native.AUDIT_STAGES if s != "blind_rotate" and (s in stages or s in self._audit_stages)]
+        if "blind_rotate" in stages or "blind_rotate" in self._audit_stages or not rows:
+            self.engine.audit_set(rows if "blind_rotate" in stages else 0, min_bits, seed)     # the default: exactly this call
+        self._audit_stages = ()
+        for s in others:
+            self.engine.audit_stage_set(s, rows if s in stages else 0, min_bits, seed)
+        self._audit_stages = stages
 
-    def audit_report(self) -> AuditReport:
-        """synchronises, then the counters and records since audit()"""
-        r = self.engine.audit_read()
+    def audit_report(self, stage: str = "blind_rotate") -> AuditReport:
+        """synchronises, then the counters and records of `stage` since audit()"""
+        r = self.engine.audit_read() if stage == "blind_rotate" else self.engine.audit_stage_read(stage)
         return AuditReport(r["launches"], r["rows_checked"], r["rows_wrong"], [AuditRecord(*(int(x) for x in rec)) for rec in r["records"]])
 
+    def audit_reports(self) -> dict:
+        """{stage: audit_report(stage)} over the stages audit() enabled, in the order of _native.AUDIT_STAGES"""
+        return {s: self.audit_report(s) for s in self._audit_stages}
+
     def audit_check(self) -> AuditReport:
-        """audit_report(), raising AuditMismatch (with the records) if any row since audit() differed"""
-        report = self.audit_report()
-        if report.rows_wrong:
-            raise AuditMismatch(report)
-        return report
+        """the report of the blind rotation's audit, raising AuditMismatch (with the stage and its records) if any row of an enabled stage
+        since audit() differed"""
+        return _audit_check({s: self.audit_report(s) for s in _native.AUDIT_STAGES if s == "blind_rotate" or s in self._audit_stages})
 
     def synchronize(self):
         self.engine.synchronize()
@@ -1360,16 +1394,16 @@ class ServerGroup:
         """per cloned context: how its keys got there ({"path": "same_device" | "peer" | "staged", "bytes", "seconds"})"""
         return [s.engine.clone_info() for s in self.servers[1:]]
 
-    def audit(self, rows: int = 64, min_bits: int = 0, seed: int | None = None):
+    def audit(self, rows: int = 64, min_bits: int = 0, seed: int | None = None, stages=("blind_rotate",)):
         """Server.audit on every context, each under a seed of its own: drawn from os.urandom, or -- a given `seed` -- seed + the context's index"""
         for i, s in enumerate(self.servers):
-            s.audit(rows, min_bits, None if seed is None else (int(seed) + i) % (1 << 64))
+            s.audit(rows, min_bits, None if seed is None else (int(seed) + i) % (1 << 64), stages=stages)
 
-    def audit_report(self) -> AuditReport:
-        """the contexts' counters summed, their records tagged with the device"""
+    def audit_report(self, stage: str = "blind_rotate") -> AuditReport:
+        """the contexts' counters of `stage` summed, their records tagged with the device"""
         total = AuditReport()
         for d, s in zip(self.devices, self.servers):
-            r = s.audit_report()
+            r = s.audit_report(stage)
             total.launches += r.launches
             total.rows_checked += r.rows_checked
             total.rows_wrong += r.rows_wrong
@@ -1377,7 +1411,7 @@ class ServerGroup:
         return total
 
     def audit_check(self) -> AuditReport:
-        report = self.audit_report()
-        if report.rows_wrong:
-            raise AuditMismatch(report)
-        return report
+        """the summed report of the blind rotation's audit, raising AuditMismatch (with the stage, its summed report and, in `reports`, every
+        checked stage's) if any row of an enabled stage differed on any context.  A group has no audit_reports(): audit_report(stage) per
+        stage of servers[0]'s enabled stages gives the same"""
+        return _audit_check({s: self.audit_report(s) for s in _native.AUDIT_STAGES if s == "blind_rotate" or s in self.servers[0]._audit_stages})
