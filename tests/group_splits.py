@@ -1,6 +1,7 @@
-"""ServerGroup re-implements, in Python, the argument handling of every Server method it offers: which slice of the blocks, keys, streams,
-messages, gates, GLWEs or seeded ciphertexts a context gets, which public value goes with it (first_block + lo, first_index + lo, the
-chaining block ct[lo - 1]) and where its output lands.  This is the table of calls that test_group_splits_cpu.py runs on an echo model
+"""ServerGroup decides, for every Server method it offers, which slice of the blocks, keys, streams, messages, gates, GLWEs or seeded
+ciphertexts a context gets, which public value goes with it (first_block + lo, first_index + lo, the chaining block ct[lo - 1]) and where
+its output lands.  The checks and result shapes are Server's own, the splits come from two builders (_even, _by_cost) and run through one
+runner (_each); the slices and offsets are the group's alone.  This is the table of calls that test_group_splits_cpu.py runs on an echo model
 of Server (g = 1..6, n = 0..7) and test_gpu_group_splits.py on groups of 1, 3 and 5 contexts at PARAM_TOY.  A helper module like
 chunk_seams.py and workspace_state.py: no test, no fixture.
 

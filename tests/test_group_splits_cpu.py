@@ -10,7 +10,10 @@ import dataclasses
 import hashlib
 import inspect
 import itertools
+import json
+import re
 import threading
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -491,6 +494,26 @@ def test_a_group_of_echo_models_writes_what_one_model_writes(case):
             assert worked == gs.working(split, g, _shards_by_cost, shard_blocks), (case.name, n, g)
             assert all(s.clean and s.syncs for s in grp.servers if s.calls), "a context that worked was not synchronised"
             assert all(s.syncs == 0 for s in grp.servers if not s.calls) or split[0] == "first"
+
+
+# ---- the class itself ------------------------------------------------------------------------------------------------------------------------
+def test_every_public_method_keeps_its_recorded_signature():
+    """golden/server_group_signatures.json: str(inspect.signature) of every public method, recorded before the class was rewritten over
+    shared helpers; a new method is added to the list, none changes its parameters by the way"""
+    recorded = json.loads((Path(__file__).resolve().parent / "golden" / "server_group_signatures.json").read_text())
+    now = {name: str(inspect.signature(f)) for name, f in inspect.getmembers(ServerGroup, callable) if not name.startswith("_")}
+    assert now == recorded
+
+
+def test_every_split_is_made_by_one_of_the_two_shard_builders():
+    """ServerGroup._even and ServerGroup._by_cost each call their shard function once; no other line of the class calls either"""
+    source = inspect.getsource(ServerGroup)
+    a_call = re.compile(r"\b(shard_blocks|_shards_by_cost)\s*\(")
+    for builder, function in ((ServerGroup._even, "shard_blocks"), (ServerGroup._by_cost, "_shards_by_cost")):
+        own = inspect.getsource(builder)
+        assert [m.group(1) for m in a_call.finditer(own)] == [function] and source.count(own) == 1
+        source = source.replace(own, "")
+    assert a_call.search(source) is None, a_call.search(source)
 
 
 # ---- an exception in one shard ---------------------------------------------------------------------------------------------------------------

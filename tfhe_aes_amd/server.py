@@ -35,6 +35,7 @@ import numpy as np
 from . import _native
 from .aes_clear import INV_SBOX, SBOX, mul2, mul3, mul9, mul11, mul13, mul14  # noqa: F401  (re-exported like sbox.rs)
 from .client import PackedRoundKeys, SeededCiphertexts, ServerKeys, packed_key_glwes, packed_mod_words
+from .dist import shard_blocks
 from .params import WopbsParameters
 
 
@@ -77,6 +78,46 @@ def _key_bits(arr, table, what, ndim=4) -> int:
     if arr.ndim != ndim or lead not in table:
         raise ValueError("%s must be [%s]%s[8][kN+1], got shape %s" % (what, " | ".join(map(str, table)), "[16]" * (ndim - 3), tuple(arr.shape)))
     return table[lead]
+
+
+def many_keys_shape(p, keys, least: int = 1):
+    """keys [n_keys][16 | 24 | 32][8][kN+1] of one size -> (the AES key size, the shape of their round keys [n_keys][Nr+1][16][8][kN+1]).
+    least = 1: a Server's batch holds at least one key; least = 0: a ServerGroup's may be empty -- no context works then -- so the key
+    size is read from the shape, there being no keys[0] to ask"""
+    if keys.ndim != 4 or int(keys.shape[0]) < least or (not least and int(keys.shape[1]) not in KEY_BYTES_TO_BITS):
+        raise ValueError("keys must be [n_keys][16 | 24 | 32][8][kN+1]%s, got shape %s" % (" with n_keys >= 1" * least, tuple(keys.shape)))
+    bits = _key_bits(keys[0], KEY_BYTES_TO_BITS, "key", ndim=3) if least else KEY_BYTES_TO_BITS[int(keys.shape[1])]
+    return bits, (int(keys.shape[0]), bits // 32 + 7, 16, 8, p.big1)
+
+
+def _n_rows(shape) -> int:
+    m = 1
+    for d in shape:
+        m *= int(d)
+    return m
+
+
+def pack_shape(p, ct, width: int):
+    """Server.pack's argument [..., kN+1] -> (its number of bits m, the packed shape [ceil(m / N)][words of a GLWE at `width`])"""
+    if int(ct.shape[-1]) != p.big1:
+        raise ValueError("pack takes [..., kN+1] = [..., %d] words, got shape %s" % (p.big1, tuple(ct.shape)))
+    m = _n_rows(ct.shape[:-1])
+    return m, ((m + p.N - 1) // p.N, packed_mod_words(p, width))
+
+
+def unpack_shape(p, packed, shape, width: int):
+    """Server.unpack's arguments -> (`shape` as a tuple, its number of bits m); `packed` must be those bits' packed shape"""
+    shape = (int(shape),) if isinstance(shape, int) else tuple(int(d) for d in shape)
+    m = _n_rows(shape)
+    gw = packed_mod_words(p, width)
+    if tuple(packed.shape) != ((m + p.N - 1) // p.N, gw):
+        raise ValueError("%d bits are packed as [%d][%d] words, got shape %s" % (m, (m + p.N - 1) // p.N, gw, tuple(packed.shape)))
+    return shape, m
+
+
+def _cut(a, lo: int, hi: int):
+    """items lo .. hi of an optional per-item list or array: None stays None"""
+    return None if a is None else a[lo:hi]
 
 
 def _data_blocks(data, n_blocks: int):
@@ -558,12 +599,9 @@ class Server:
     def aes_key_expansion_many(self, keys, out=None):
         """keys [n_keys][16 | 24 | 32][8][kN+1] (one key size) -> round keys [n_keys][Nr+1][16][8][kN+1] (or `out`); slice i is
         aes_key_expansion(keys[i]) word for word, every step one WoPBS over all keys (include/fheaes.h: fheaes_aes_key_expansion_batch)."""
-        if keys.ndim != 4 or int(keys.shape[0]) < 1:
-            raise ValueError("keys must be [n_keys][16 | 24 | 32][8][kN+1] with n_keys >= 1, got shape %s" % (tuple(keys.shape),))
-        bits = _key_bits(keys[0], KEY_BYTES_TO_BITS, "key", ndim=3)
-        n_keys = int(keys.shape[0])
-        rk = self._many_out(keys, (n_keys, bits // 32 + 7, 16, 8, self.params.big1), out)
-        self.engine.aes_key_expansion_batch(keys, bits, n_keys, rk)
+        bits, shape = many_keys_shape(self.params, keys)
+        rk = self._many_out(keys, shape, out)
+        self.engine.aes_key_expansion_batch(keys, bits, shape[0], rk)
         return rk
 
     @staticmethod
@@ -901,17 +939,8 @@ class Server:
         fheaes_pack_bits).  409.8 times smaller at PARAM_OPT; no key beyond the ones the Server holds; Client.decrypt_packed reads it.
         `width` in 8..32: the words modulus-switched to `width` bits each, [G][(k+1) 8 width] (fheaes_pack_bits_mod; 16 is the width the
         header's noise arithmetic clears for PARAM_OPT: another 4 times smaller); Client.decrypt_packed(..., width=) reads that."""
-        p = self.params
-        if int(ct.shape[-1]) != p.big1:
-            raise ValueError("pack takes [..., kN+1] = [..., %d] words, got shape %s" % (p.big1, tuple(ct.shape)))
-        m = 1
-        for d in ct.shape[:-1]:
-            m *= int(d)
-        shape = ((m + p.N - 1) // p.N, packed_mod_words(p, width))
-        if out is None:
-            out = _empty_like(ct, shape)
-        elif tuple(out.shape) != shape:
-            raise ValueError("out must be %s, got %s" % (shape, tuple(out.shape)))
+        m, shape = pack_shape(self.params, ct, width)
+        out = self._many_out(ct, shape, out)
         if m and width == 64:
             self.engine.pack_bits(ct, m, out)
         elif m:
@@ -922,16 +951,9 @@ class Server:
         """the inverse shape: [G][(k+1)N] -> [*shape, kN+1] (sample extraction of coefficient t % N of GLWE t // N for bit t), LWE
         ciphertexts under the big key that every entry point takes; `shape` may be an int (the number of bits).  `width` in 8..32:
         `packed` is the switched form [G][(k+1) 8 width] and the extraction reads its fields (fheaes_unpack_bits_mod)."""
-        p = self.params
-        shape = (int(shape),) if isinstance(shape, int) else tuple(int(d) for d in shape)
-        m = 1
-        for d in shape:
-            m *= d
-        gw = packed_mod_words(p, width)
-        if tuple(packed.shape) != ((m + p.N - 1) // p.N, gw):
-            raise ValueError("%d bits are packed as [%d][%d] words, got shape %s" % (m, (m + p.N - 1) // p.N, gw, tuple(packed.shape)))
+        shape, m = unpack_shape(self.params, packed, shape, width)
         if out is None:
-            out = _empty_like(packed, shape + (p.big1,))
+            out = _empty_like(packed, shape + (self.params.big1,))
         if m and width == 64:
             self.engine.unpack_bits(packed, m, out)
         elif m:
@@ -1045,151 +1067,150 @@ class ServerGroup:
             if e is not None:
                 raise e
 
-    def _fan_out(self, fn, state):
-        from .dist import shard_blocks
+    # ---- the shared parts: two shard builders, one runner in front of _run_shards, the outputs a call allocates ---------------------------
+    def _even(self, n: int):
+        """n blocks, keys, GLWEs or ciphertexts in contiguous shares that differ by at most one: item i -> context i * G / n"""
+        g = len(self.servers)
+        return [shard_blocks(n, g, i) for i in range(g)]
 
+    def _by_cost(self, costs):
+        """whole streams, messages or gates per context, contiguous and balanced by cost; context 0 may idle"""
+        return _shards_by_cost(costs, len(self.servers))
+
+    def _each(self, shards, job, rows=None):
+        """job(server i, lo, hi) for shard i = [lo, hi) of `shards`, all at once; the context of an empty shard receives no call.  rows:
+        the row offset of every item where a shard is empty by its rows (items rows[lo] .. rows[hi]) and not by its items"""
+        if rows is None:
+            rows = range(shards[-1][1] + 1)           # item i is row i
+        self._run_shards([None if rows[hi] <= rows[lo] else (lambda s, lo=lo, hi=hi: job(s, lo, hi)) for lo, hi in shards])
+
+    def _fill(self, out, job):
+        """even over the leading axis of `out`: job(server, lo, hi, out[lo:hi]); returns `out`"""
+        self._each(self._even(int(out.shape[0])), lambda s, lo, hi: job(s, lo, hi, out[lo:hi]))
+        return out
+
+    def _first(self, result):
+        """what context 0 alone computed, finished before it is returned: a resident result is then read from the other contexts' streams,
+        which do not wait for context 0's"""
+        self.servers[0].synchronize()
+        return result
+
+    _round_keys = Server._round_keys
+    _many_out = staticmethod(Server._many_out)
+    _public_out = Server._public_out
+
+    def _new_blocks(self, round_keys, n: int, what="round keys", many=False):
+        """what a call returns as a NEW [n][16][8][kN+1]: allocated next to the round keys, which are read -- and a malformed argument
+        refused -- before that; every context fills its shard"""
+        return self._public_out(self._round_keys(round_keys, what, many).words, n, None)
+
+    # ---- in place, even over the blocks, the per-block lists sliced alongside ---------------------------------------------------------------
+    def _in_place(self, state, call, *per_block):
+        """call(server, its blocks of `state`, the same slice of every per-block list)"""
         if state.ndim != 4:
             # Server.aes_encrypt also takes ONE state [16][8][kN+1]; here the first axis is what gets sharded, so a single state would
             # be cut into 16 "blocks" of one byte each: refuse it instead of computing nonsense
             raise ValueError("ServerGroup works on a batch [n_blocks][16][8][kN+1]; wrap a single state as state[None]")
-        n, g = int(state.shape[0]), len(self.servers)
-        shards = [shard_blocks(n, g, i) for i in range(g)]
-        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: fn(s, state[lo:hi], lo)) for lo, hi in shards])
-        return state
+        return self._fill(state, lambda s, lo, hi, part: call(s, part, *(a[lo:hi] for a in per_block)))
 
     def aes_encrypt(self, round_keys, state):
         """[n_blocks][16][8][kN+1] in place (host arrays: every context stages its own shard)"""
-        return self._fan_out(lambda s, shard, lo: s.aes_encrypt(round_keys, shard), state)
+        return self._in_place(state, lambda s, part: s.aes_encrypt(round_keys, part))
 
     def aes_decrypt(self, round_keys, state):
-        return self._fan_out(lambda s, shard, lo: s.aes_decrypt(round_keys, shard), state)
-
-    def aes_decryption_round_keys(self, round_keys):
-        """converted on context 0; finished before returning, since device round keys are then read from the other contexts' streams"""
-        dw = self.servers[0].aes_decryption_round_keys(round_keys)
-        self.servers[0].synchronize()
-        return dw
+        return self._in_place(state, lambda s, part: s.aes_decrypt(round_keys, part))
 
     def aes_decrypt_equivalent(self, dec_round_keys, state):
-        return self._fan_out(lambda s, shard, lo: s.aes_decrypt_equivalent(dec_round_keys, shard), state)
-
-    def _fan_out_lists(self, call, state, *per_block):
-        """shard these per-block lists with the output: call(server, shard of `state`, the same slice of every list -- None stays None)"""
-        return self._fan_out(lambda s, shard, lo: call(s, shard, *(None if a is None else a[lo:lo + int(shard.shape[0])] for a in per_block)), state)
+        return self._in_place(state, lambda s, part: s.aes_decrypt_equivalent(dec_round_keys, part))
 
     def add_scalar(self, state, counters):
-        return self._fan_out_lists(lambda s, shard, cnt: s.add_scalar(shard, cnt), state, list(counters))
+        return self._in_place(state, lambda s, part, cnt: s.add_scalar(part, cnt), list(counters))
 
-    _round_keys = Server._round_keys
+    def aes_encrypt_keyed(self, round_keys, key_of_block, state):
+        return self._in_place(state, lambda s, part, kob: s.aes_encrypt_keyed(round_keys, kob, part), list(key_of_block))
 
-    def _new_out(self, k: RoundKeys, *shape):
-        """what a call returns as a NEW array: allocated next to the round keys, every context filling its shard"""
-        return _empty_like(k.words, shape + (self.params.big1,))
+    def aes_decrypt_keyed(self, round_keys, key_of_block, state):
+        return self._in_place(state, lambda s, part, kob: s.aes_decrypt_keyed(round_keys, kob, part), list(key_of_block))
 
-    def _fan_out_new(self, k: RoundKeys, n, fn):
-        """the public-input calls produce a new [n][16][8][kN+1]"""
-        return self._fan_out(lambda s, shard, lo: fn(s, shard, lo, int(shard.shape[0])), self._new_out(k, n, 16, 8))
+    def aes_decrypt_equivalent_keyed(self, dec_round_keys, key_of_block, state):
+        return self._in_place(state, lambda s, part, kob: s.aes_decrypt_equivalent_keyed(dec_round_keys, kob, part), list(key_of_block))
 
+    # ---- a new output, even over the items; a shard at item lo > 0 is handed the public value that goes with lo ------------------------------
     def aes_encrypt_public(self, round_keys, blocks):
         """Server.aes_encrypt_public, the blocks sharded contiguously; each context plans the sharing inside its own shard"""
         blocks = list(blocks)
-        return self._fan_out_lists(lambda s, shard, b: s.aes_encrypt_public(round_keys, b, out=shard), self._new_out(self._round_keys(round_keys), len(blocks), 16, 8), blocks)
+        return self._fill(self._new_blocks(round_keys, len(blocks)), lambda s, lo, hi, out: s.aes_encrypt_public(round_keys, blocks[lo:hi], out=out))
 
     def aes_ctr(self, round_keys, iv, first_block: int, n_blocks: int, data=None, counter_bits: int = 128):
         """Server.aes_ctr: context i takes the counter blocks of its shard (first_block + lo ..) and the matching data"""
         _check_counter_bits(counter_bits)
-        n_blocks = int(n_blocks)
-        data = _data_blocks(data, n_blocks)
-        return self._fan_out_new(self._round_keys(round_keys), n_blocks, lambda s, shard, lo, k: s.aes_ctr(
-            round_keys, iv, int(first_block) + lo, k, None if data is None else data[lo:lo + k], out=shard, counter_bits=counter_bits))
+        data = _data_blocks(data, int(n_blocks))
+        return self._fill(self._new_blocks(round_keys, int(n_blocks)), lambda s, lo, hi, out: s.aes_ctr(
+            round_keys, iv, int(first_block) + lo, hi - lo, _cut(data, lo, hi), out=out, counter_bits=counter_bits))
 
     def aes_gcm_ctr(self, round_keys, iv, data=None, n_blocks=None, first_block: int = 0):
         """Server.aes_gcm_ctr: context i takes the data blocks first_block + lo .. of its shard"""
         _, n_blocks, data = gcm_ctr_args(iv, data, n_blocks, first_block)
-        return self._fan_out_new(self._round_keys(round_keys), n_blocks, lambda s, shard, lo, k: s.aes_gcm_ctr(
-            round_keys, iv, None if data is None else data[lo:lo + k], k, int(first_block) + lo, out=shard))
+        return self._fill(self._new_blocks(round_keys, n_blocks), lambda s, lo, hi, out: s.aes_gcm_ctr(
+            round_keys, iv, _cut(data, lo, hi), hi - lo, int(first_block) + lo, out=out))
 
     def aes_decrypt_public(self, dec_round_keys, blocks, data=None):
         """Server.aes_decrypt_public, the blocks sharded contiguously; each context plans the sharing inside its own shard"""
         blocks = list(blocks)
-        out = self._new_out(self._round_keys(dec_round_keys, "decryption round keys"), len(blocks), 16, 8)
-        return self._fan_out_lists(lambda s, shard, b, d: s.aes_decrypt_public(dec_round_keys, b, data=d, out=shard), out, blocks, _data_blocks(data, len(blocks)))
+        out = self._new_blocks(dec_round_keys, len(blocks), "decryption round keys")
+        data = _data_blocks(data, len(blocks))
+        return self._fill(out, lambda s, lo, hi, part: s.aes_decrypt_public(dec_round_keys, blocks[lo:hi], data=_cut(data, lo, hi), out=part))
+
+    def _chained(self, method, round_keys, what, iv, ciphertext):
+        """CBC and CFB: block i needs block i - 1, so a shard that starts at block lo > 0 is handed C_{lo-1} where shard 0 is handed the iv"""
+        ct = _cipher_blocks(ciphertext)
+        return self._fill(self._new_blocks(round_keys, len(ct), what), lambda s, lo, hi, out: getattr(s, method)(
+            round_keys, ct[lo - 1] if lo else iv, ct[lo:hi], out=out))
 
     def aes_cbc_decrypt(self, dec_round_keys, iv, ciphertext):
         """Server.aes_cbc_decrypt: a shard that starts at block lo > 0 chains its first block with C_{lo-1}"""
-        ct = _cipher_blocks(ciphertext)
-        return self._fan_out_new(self._round_keys(dec_round_keys, "decryption round keys"), len(ct), lambda s, shard, lo, k: s.aes_cbc_decrypt(
-            dec_round_keys, ct[lo - 1] if lo else iv, ct[lo:lo + k], out=shard))
+        return self._chained("aes_cbc_decrypt", dec_round_keys, "decryption round keys", iv, ciphertext)
 
     def aes_cfb_decrypt(self, round_keys, iv, ciphertext):
         """Server.aes_cfb_decrypt: a shard that starts at block lo > 0 enciphers C_{lo-1} first"""
-        ct = _cipher_blocks(ciphertext)
-        return self._fan_out_new(self._round_keys(round_keys), len(ct), lambda s, shard, lo, k: s.aes_cfb_decrypt(
-            round_keys, ct[lo - 1] if lo else iv, ct[lo:lo + k], out=shard))
+        return self._chained("aes_cfb_decrypt", round_keys, "round keys", iv, ciphertext)
 
     def aes_xts_decrypt(self, dec_round_keys1, round_keys2, sectors, ciphertext, unit_bytes: int = 512, first_block: int = 0):
         """Server.aes_xts_decrypt: a shard at block lo passes first_block + lo and needs nothing from its neighbour (it derives its own
         tweaks from the units' anchors)"""
         units, _, ct = xts_args(sectors, ciphertext, unit_bytes, first_block)
-        return self._fan_out_new(self._round_keys(dec_round_keys1, "decryption round keys"), len(ct), lambda s, shard, lo, k: s.aes_xts_decrypt(
-            dec_round_keys1, round_keys2, units, ct[lo:lo + k], unit_bytes, int(first_block) + lo, out=shard))
-
-    def aes_key_expansion(self, key):
-        """expanded on context 0; finished before returning, since device round keys are then read from the other contexts' streams"""
-        rk = self.servers[0].aes_key_expansion(key)
-        self.servers[0].synchronize()
-        return rk
+        return self._fill(self._new_blocks(dec_round_keys1, len(ct), "decryption round keys"), lambda s, lo, hi, out: s.aes_xts_decrypt(
+            dec_round_keys1, round_keys2, units, ct[lo:hi], unit_bytes, int(first_block) + lo, out=out))
 
     # many AES keys: the keyed calls shard on blocks, every context reading the whole set of round keys; the per-key calls shard on keys
-    def _fan_out_keys(self, arr, out, fn):
-        """context i takes keys i * G / n .. of `arr` [n_keys][...] into the same slices of `out`; finished before returning, since device
-        round keys are then read from every context's stream"""
-        from .dist import shard_blocks
-
-        g = len(self.servers)
-        shards = [shard_blocks(int(arr.shape[0]), g, i) for i in range(g)]
-        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: fn(s, arr[lo:hi], out[lo:hi])) for lo, hi in shards])
-        return out
-
     def aes_key_expansion_many(self, keys):
-        if keys.ndim != 4 or int(keys.shape[1]) not in KEY_BYTES_TO_BITS:
-            raise ValueError("keys must be [n_keys][16 | 24 | 32][8][kN+1], got shape %s" % (tuple(keys.shape),))
-        out = _empty_like(keys, (int(keys.shape[0]), int(keys.shape[1]) // 4 + 7, 16, 8, self.params.big1))
-        return self._fan_out_keys(keys, out, lambda s, part, o: s.aes_key_expansion_many(part, out=o))
+        out = self._many_out(keys, many_keys_shape(self.params, keys, least=0)[1], None)
+        return self._fill(out, lambda s, lo, hi, part: s.aes_key_expansion_many(keys[lo:hi], out=part))
 
     def aes_decryption_round_keys_many(self, round_keys):
         self._round_keys(round_keys, many=True, lwe_only=True)
-        out = _empty_like(round_keys, tuple(round_keys.shape))
-        return self._fan_out_keys(round_keys, out, lambda s, part, o: s.aes_decryption_round_keys_many(part, out=o))
+        out = self._many_out(round_keys, tuple(round_keys.shape), None)
+        return self._fill(out, lambda s, lo, hi, part: s.aes_decryption_round_keys_many(round_keys[lo:hi], out=part))
 
-    def aes_encrypt_keyed(self, round_keys, key_of_block, state):
-        return self._fan_out_lists(lambda s, shard, kob: s.aes_encrypt_keyed(round_keys, kob, shard), state, list(key_of_block))
-
-    def aes_decrypt_keyed(self, round_keys, key_of_block, state):
-        return self._fan_out_lists(lambda s, shard, kob: s.aes_decrypt_keyed(round_keys, kob, shard), state, list(key_of_block))
-
-    def aes_decrypt_equivalent_keyed(self, dec_round_keys, key_of_block, state):
-        return self._fan_out_lists(lambda s, shard, kob: s.aes_decrypt_equivalent_keyed(dec_round_keys, kob, shard), state, list(key_of_block))
-
-    def _fan_out_public_keyed(self, method, round_keys, what, key_of_block, blocks, data):
+    def _keyed_public(self, method, round_keys, what, key_of_block, blocks, data):
         """Server.aes_encrypt_public_keyed / aes_decrypt_public_keyed, the blocks sharded contiguously; each context plans the sharing
         inside its own shard"""
         kob, blocks = list(key_of_block), list(blocks)
         data = _data_blocks(data, len(blocks))
         if len(kob) != len(blocks):
             raise ValueError("one key index per block expected")
-        out = self._new_out(self._round_keys(round_keys, what, many=True), len(blocks), 16, 8)
-        return self._fan_out_lists(lambda s, shard, k, b, d: method(s, round_keys, k, b, data=d, out=shard), out, kob, blocks, data)
+        return self._fill(self._new_blocks(round_keys, len(blocks), what, many=True), lambda s, lo, hi, out: method(
+            s, round_keys, kob[lo:hi], blocks[lo:hi], data=_cut(data, lo, hi), out=out))
 
     def aes_encrypt_public_keyed(self, round_keys, key_of_block, blocks, data=None):
-        return self._fan_out_public_keyed(Server.aes_encrypt_public_keyed, round_keys, "round keys", key_of_block, blocks, data)
+        return self._keyed_public(Server.aes_encrypt_public_keyed, round_keys, "round keys", key_of_block, blocks, data)
 
     def aes_ctr_streams(self, round_keys, streams, counter_bits: int = 128):
         key_of_block, blocks, data = ctr_stream_blocks(streams, counter_bits)
         return self.aes_encrypt_public_keyed(round_keys, key_of_block, blocks, data=data)
 
     def aes_decrypt_public_keyed(self, dec_round_keys, key_of_block, blocks, data=None):
-        return self._fan_out_public_keyed(Server.aes_decrypt_public_keyed, dec_round_keys, "decryption round keys", key_of_block, blocks, data)
+        return self._keyed_public(Server.aes_decrypt_public_keyed, dec_round_keys, "decryption round keys", key_of_block, blocks, data)
 
     def aes_cbc_streams(self, dec_round_keys, streams):
         """Server.aes_cbc_streams: the chaining blocks are built before the blocks are sharded, so a shard boundary inside a stream
@@ -1197,14 +1218,14 @@ class ServerGroup:
         key_of_block, blocks, chain = cbc_stream_blocks(streams)
         return self.aes_decrypt_public_keyed(dec_round_keys, key_of_block, blocks, data=chain)
 
+    # ---- a new output, whole streams or messages by cost: a shard needs nothing from its neighbours ----------------------------------------
     def aes_cbc_mac_streams(self, round_keys, streams, init=None):
         """Server.aes_cbc_mac_streams: whole streams per context, contiguous and balanced by block count; a shard needs nothing from
         its neighbours"""
         streams = [tuple(st) for st in streams]
-        out = self._new_out(self._round_keys(round_keys, many=None), len(streams), 16, 8)
-        shards = _shards_by_cost([len(_cipher_blocks(st[1])) + 1 for st in streams], len(self.servers))
-        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_cbc_mac_streams(
-            round_keys, streams[lo:hi], init=None if init is None else init[lo:hi], out=out[lo:hi])) for lo, hi in shards])
+        out = self._new_blocks(round_keys, len(streams), many=None)
+        self._each(self._by_cost([len(_cipher_blocks(st[1])) + 1 for st in streams]), lambda s, lo, hi: s.aes_cbc_mac_streams(
+            round_keys, streams[lo:hi], init=_cut(init, lo, hi), out=out[lo:hi]))
         return out
 
     def aes_ccm_decrypt(self, round_keys, messages, gate: bool = False):
@@ -1213,78 +1234,63 @@ class ServerGroup:
         messages = [tuple(m) for m in messages]
         a = ccm_args(messages)
         at, n = a["block_of_message"], len(messages)
-        k = self._round_keys(round_keys, many=None)
-        out, valid = self._new_out(k, at[-1], 16, 8), self._new_out(k, n)
+        words = self._round_keys(round_keys, many=None).words
+        out, valid = self._public_out(words, at[-1], None), self._many_out(words, (n, self.params.big1), None)
         cost = [a["head_blocks"][i] - 1 + 2 * (at[i + 1] - at[i]) + 2 for i in range(n)]
-        shards = _shards_by_cost(cost, len(self.servers))
-        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_ccm_decrypt(
-            round_keys, messages[lo:hi], out=out[at[lo]:at[hi]], valid_out=valid[lo:hi], gate=gate)) for lo, hi in shards])
+        self._each(self._by_cost(cost), lambda s, lo, hi: s.aes_ccm_decrypt(
+            round_keys, messages[lo:hi], out=out[at[lo]:at[hi]], valid_out=valid[lo:hi], gate=gate))
         return out, valid, at
-
-    def aes_cmac_subkeys(self, round_keys):
-        """derived on context 0; finished before returning, since the subkeys are then read from the other contexts' streams"""
-        sub = self.servers[0].aes_cmac_subkeys(round_keys)
-        self.servers[0].synchronize()
-        return sub
-
-    def _cmac_shards(self, entries):
-        """whole streams per context, contiguous and balanced by chain blocks"""
-        return _shards_by_cost(cmac_args(entries)["chain_blocks"], len(self.servers))
 
     def aes_cmac_streams(self, round_keys, streams, subkeys=None):
         """Server.aes_cmac_streams: whole streams per context, contiguous and balanced by chain blocks; a context without `subkeys` derives
         those of its own shard's keys (the same words on every context).  EAX's OMAC^t is this CMAC over [t]_128 || M and needs nothing
         more."""
         streams = [tuple(st) for st in streams]
-        out = self._new_out(self._round_keys(round_keys, many=None), len(streams), 16, 8)
-        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_cmac_streams(round_keys, streams[lo:hi], subkeys=subkeys, out=out[lo:hi]))
-                          for lo, hi in self._cmac_shards(streams)])
+        out = self._new_blocks(round_keys, len(streams), many=None)
+        self._each(self._by_cost(cmac_args(streams)["chain_blocks"]), lambda s, lo, hi: s.aes_cmac_streams(
+            round_keys, streams[lo:hi], subkeys=subkeys, out=out[lo:hi]))
         return out
 
     def aes_cmac_verify(self, round_keys, messages, subkeys=None):
         """Server.aes_cmac_verify, sharded as aes_cmac_streams.  EAX's OMAC^t is this CMAC over [t]_128 || M and needs nothing more."""
         messages = [tuple(m) for m in messages]
-        valid = self._new_out(self._round_keys(round_keys, many=None), len(messages))
-        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_cmac_verify(round_keys, messages[lo:hi], subkeys=subkeys, valid_out=valid[lo:hi]))
-                          for lo, hi in self._cmac_shards(messages)])
+        valid = self._many_out(self._round_keys(round_keys, many=None).words, (len(messages), self.params.big1), None)
+        self._each(self._by_cost(cmac_args(messages)["chain_blocks"]), lambda s, lo, hi: s.aes_cmac_verify(
+            round_keys, messages[lo:hi], subkeys=subkeys, valid_out=valid[lo:hi]))
         return valid
 
-    def _kw_shards(self, n_keys: int):
-        """whole wrapped keys per context, contiguous: every chain has the same length"""
-        from .dist import shard_blocks
-
-        return [shard_blocks(n_keys, len(self.servers), i) for i in range(len(self.servers))]
+    # ---- key unwrap: even over the wrapped keys, the payloads and `valid` side by side ----------------------------------------------------------
+    def _kw_args(self, kek_dec_round_keys, wrapped, kek_of_key):
+        """both key unwraps' arguments -> (the KEKs as RoundKeys, semiblocks per key, the wrapped keys as a list of bytes, the KEK index of
+        every key or None); whole wrapped keys go to a context, evenly: every chain has the same length"""
+        k = self._round_keys(kek_dec_round_keys, "KEK decryption round keys", many=None)
+        a = kw_args(wrapped, kek_of_key, k.n_keys)
+        return k, a["semiblocks"], [bytes(w) for w in a["wrapped"]], a["kek_of_key"]
 
     def aes_key_unwrap(self, kek_dec_round_keys, wrapped, kek_of_key=None, gate: bool = False):
         """Server.aes_key_unwrap: whole keys per context, contiguous; every context reads all KEKs and, with gate=True, gates its own
         keys.  Returns (keys, valid)."""
-        k = self._round_keys(kek_dec_round_keys, "KEK decryption round keys", many=None)
-        a = kw_args(wrapped, kek_of_key, k.n_keys)
-        wrapped, kok = [bytes(w) for w in a["wrapped"]], a["kek_of_key"]
-        keys, valid = self._new_out(k, len(wrapped), 8 * a["semiblocks"], 8), self._new_out(k, len(wrapped))
-        self._run_shards([None if hi <= lo else (lambda s, lo=lo, hi=hi: s.aes_key_unwrap(kek_dec_round_keys, wrapped[lo:hi], None if kok is None else kok[lo:hi],
-                                                                                          out=keys[lo:hi], valid_out=valid[lo:hi], gate=gate))
-                          for lo, hi in self._kw_shards(len(wrapped))])
+        k, semiblocks, wrapped, kok = self._kw_args(kek_dec_round_keys, wrapped, kek_of_key)
+        n, big1 = len(wrapped), self.params.big1
+        keys, valid = self._many_out(k.words, (n, 8 * semiblocks, 8, big1), None), self._many_out(k.words, (n, big1), None)
+        self._each(self._even(n), lambda s, lo, hi: s.aes_key_unwrap(
+            kek_dec_round_keys, wrapped[lo:hi], _cut(kok, lo, hi), out=keys[lo:hi], valid_out=valid[lo:hi], gate=gate))
         return keys, valid
 
     def aes_key_unwrap_packed(self, kek_dec_round_keys, wrapped, kek_of_key=None, chunk: int = 256, gate: bool = False):
         """Server.aes_key_unwrap_packed with whole keys per context: every context unwraps, expands and packs its shard `chunk` keys at a
         time; the store and `valid` are put together in the caller's order.  Returns (PackedRoundKeys, valid)."""
-        k = self._round_keys(kek_dec_round_keys, "KEK decryption round keys", many=None)
-        a = kw_args(wrapped, kek_of_key, k.n_keys)
-        wrapped, kok = [bytes(w) for w in a["wrapped"]], a["kek_of_key"]
-        parts = [None] * len(self.servers)
+        k, _, wrapped, kok = self._kw_args(kek_dec_round_keys, wrapped, kek_of_key)
+        parts = {}                                   # by the shard's first key: (store, valid) of every context that worked
 
-        def job(i, lo, hi):
-            def run(s):
-                parts[i] = s.aes_key_unwrap_packed(kek_dec_round_keys, wrapped[lo:hi], None if kok is None else kok[lo:hi], chunk, gate=gate)
-            return run
+        def job(s, lo, hi):
+            parts[lo] = s.aes_key_unwrap_packed(kek_dec_round_keys, wrapped[lo:hi], _cut(kok, lo, hi), chunk, gate=gate)
 
-        shards = self._kw_shards(len(wrapped))
+        shards = self._even(len(wrapped))
         if not wrapped:
             raise ValueError("at least one wrapped AES key (a payload of 16, 24 or 32 bytes) expected")
-        self._run_shards([None if hi <= lo else job(i, lo, hi) for i, (lo, hi) in enumerate(shards)])
-        parts = [x for x in parts if x is not None]
+        self._each(shards, job)
+        parts = [parts[lo] for lo in sorted(parts)]
         if isinstance(k.words, np.ndarray):
             data, valid = np.concatenate([x[0].data for x in parts]), np.concatenate([x[1] for x in parts])
         else:
@@ -1294,101 +1300,83 @@ class ServerGroup:
             torch.cuda.current_stream(data.device).synchronize()
         return PackedRoundKeys(self.params, parts[0][0].key_bits, data), valid
 
-    # packed round keys: a store is small, so every context reads the whole of it (as the keyed calls read all round keys); the cipher
-    # methods above take a PackedRoundKeys wherever they take round keys, since every context's Server does
+    # ---- context 0 alone, then finished (_first): the calls on one key or one key set, whose result every context reads afterwards.  A packed
+    # store is small, so every context reads the whole of it (as the keyed calls read all round keys); the cipher methods above take a
+    # PackedRoundKeys wherever they take round keys, since every context's Server does
+    def aes_key_expansion(self, key):
+        """expanded on context 0"""
+        return self._first(self.servers[0].aes_key_expansion(key))
+
+    def aes_decryption_round_keys(self, round_keys):
+        """converted on context 0"""
+        return self._first(self.servers[0].aes_decryption_round_keys(round_keys))
+
+    def aes_cmac_subkeys(self, round_keys):
+        """derived on context 0"""
+        return self._first(self.servers[0].aes_cmac_subkeys(round_keys))
+
     def pack_round_keys(self, round_keys) -> PackedRoundKeys:
-        """packed on context 0; finished before returning, since a resident store is then read from the other contexts' streams"""
-        prk = self.servers[0].pack_round_keys(round_keys)
-        self.servers[0].synchronize()
-        return prk
+        """packed on context 0"""
+        return self._first(self.servers[0].pack_round_keys(round_keys))
 
     def unpack_round_keys(self, prk: PackedRoundKeys, first: int = 0, count: int | None = None):
-        rk = self.servers[0].unpack_round_keys(prk, first, count)
-        self.servers[0].synchronize()
-        return rk
+        return self._first(self.servers[0].unpack_round_keys(prk, first, count))
 
     def aes_key_expansion_packed(self, keys, chunk: int = 256) -> PackedRoundKeys:
-        prk = self.servers[0].aes_key_expansion_packed(keys, chunk)
-        self.servers[0].synchronize()
-        return prk
+        return self._first(self.servers[0].aes_key_expansion_packed(keys, chunk))
 
-    def _fan_out_gates(self, method, ct, valid, runs, unit_words: int):
+    # ---- the gates: whole gates by cost, a context working iff its gates have rows -------------------------------------------------------------
+    _gate_runs = Server._gate_runs
+
+    def _gates(self, method, ct, valid, runs, unit_words: int):
         """whole gates per context, contiguous and balanced by run length: context i gates the rows of its gates, out of place"""
         flat = ct.reshape(-1, unit_words)
-        runs = self.servers[0]._gate_runs(valid, int(flat.shape[0]), runs, "rows")
+        runs = self._gate_runs(valid, int(flat.shape[0]), runs, "rows")
         out = _empty_like(ct, tuple(flat.shape))
         at = [0]
         for r in runs:
             at.append(at[-1] + r)
-        shards = _shards_by_cost([r + 1 for r in runs], len(self.servers))
-        self._run_shards([None if at[hi] <= at[lo] else (lambda s, lo=lo, hi=hi: getattr(s, method)(flat[at[lo]:at[hi]], valid[lo:hi], runs[lo:hi], out=out[at[lo]:at[hi]]))
-                          for lo, hi in shards])
+        self._each(self._by_cost([r + 1 for r in runs]), lambda s, lo, hi: getattr(s, method)(
+            flat[at[lo]:at[hi]], valid[lo:hi], runs[lo:hi], out=out[at[lo]:at[hi]]), rows=at)
         return out.reshape(tuple(ct.shape))
 
     def gate(self, ct, valid, bits_of_gate=None):
         """Server.gate, sharded on whole gates; the words are those of one context whatever the number of contexts"""
-        return self._fan_out_gates("gate", ct, valid, bits_of_gate, self.params.big1)
+        return self._gates("gate", ct, valid, bits_of_gate, self.params.big1)
 
     def gate_packed(self, packed, valid, glwes_of_gate=None):
         """Server.gate_packed, sharded on whole gates"""
-        return self._fan_out_gates("gate_packed", packed, valid, glwes_of_gate, (self.params.k + 1) * self.params.N)
+        return self._gates("gate_packed", packed, valid, glwes_of_gate, (self.params.k + 1) * self.params.N)
 
-    def _glwe_shards(self, n_glwes: int):
-        from .dist import shard_blocks
-
-        return [shard_blocks(n_glwes, len(self.servers), i) for i in range(len(self.servers))]
-
+    # ---- packing and seeded ciphertexts: even over GLWEs of N bits, the last one ragged, and over ciphertexts -------------------------------
     def pack(self, ct, width: int = 64):
         """Server.pack, sharded on whole GLWEs (N bits = 4 AES blocks): context i packs GLWEs i * G / n .. of the flattened input, so the
         words are those of one context whatever the number of contexts"""
         p = self.params
-        if int(ct.shape[-1]) != p.big1:
-            raise ValueError("pack takes [..., kN+1] = [..., %d] words, got shape %s" % (p.big1, tuple(ct.shape)))
+        m, shape = pack_shape(p, ct, width)
         flat = ct.reshape(-1, p.big1)
-        m = int(flat.shape[0])
-        out = _empty_like(ct, ((m + p.N - 1) // p.N, packed_mod_words(p, width)))
-        jobs = []
-        for lo, hi in self._glwe_shards(int(out.shape[0])):
-            b0, b1 = lo * p.N, min(hi * p.N, m)
-            jobs.append(None if hi <= lo else (lambda s, lo=lo, hi=hi, b0=b0, b1=b1: s.pack(flat[b0:b1], out=out[lo:hi], width=width)))
-        self._run_shards(jobs)
-        return out
+        return self._fill(_empty_like(ct, shape), lambda s, lo, hi, out: s.pack(flat[lo * p.N:min(hi * p.N, m)], out=out, width=width))
 
     def unpack(self, packed, shape, width: int = 64):
         """Server.unpack with the same split: context i extracts the bits of its GLWEs"""
         p = self.params
-        shape = (int(shape),) if isinstance(shape, int) else tuple(int(d) for d in shape)
-        m = 1
-        for d in shape:
-            m *= d
-        gw = packed_mod_words(p, width)
-        if tuple(packed.shape) != ((m + p.N - 1) // p.N, gw):
-            raise ValueError("%d bits are packed as [%d][%d] words, got shape %s" % (m, (m + p.N - 1) // p.N, gw, tuple(packed.shape)))
+        shape, m = unpack_shape(p, packed, shape, width)
         out = _empty_like(packed, (m, p.big1))
-        jobs = []
-        for lo, hi in self._glwe_shards(int(packed.shape[0])):
+
+        def job(s, lo, hi):
             b0, b1 = lo * p.N, min(hi * p.N, m)
-            jobs.append(None if hi <= lo else (lambda s, lo=lo, hi=hi, b0=b0, b1=b1: s.unpack(packed[lo:hi], b1 - b0, out=out[b0:b1], width=width)))
-        self._run_shards(jobs)
+            s.unpack(packed[lo:hi], b1 - b0, out=out[b0:b1], width=width)
+
+        self._each(self._even(int(packed.shape[0])), job)
         return out.reshape(shape + (p.big1,))
 
     def expand(self, seeded: SeededCiphertexts):
         """Server.expand, sharded on ciphertexts: context i expands ciphertexts i * G / n .. of the flattened list and passes
         first_index + its offset, so the words are those of one context"""
-        import dataclasses
-
-        from .dist import shard_blocks
-
-        p = self.params
         flat = seeded.bodies.reshape(-1)
-        m, g = int(flat.shape[0]), len(self.servers)
-        out = _empty_like(flat, (m, p.big1))
-        jobs = []
-        for lo, hi in (shard_blocks(m, g, i) for i in range(g)):
-            part = dataclasses.replace(seeded, first_index=(int(seeded.first_index) + lo) % (1 << 64), bodies=flat[lo:hi])
-            jobs.append(None if hi <= lo else (lambda s, part=part, lo=lo, hi=hi: s.expand(part, out=out[lo:hi])))
-        self._run_shards(jobs)
-        return out.reshape(tuple(int(d) for d in seeded.bodies.shape) + (p.big1,))
+        out = self._fill(_empty_like(flat, (int(flat.shape[0]), self.params.big1)), lambda s, lo, hi, part: s.expand(
+            dataclasses.replace(seeded, first_index=(int(seeded.first_index) + lo) % (1 << 64), bodies=flat[lo:hi]), out=part))
+        return out.reshape(tuple(int(d) for d in seeded.bodies.shape) + (self.params.big1,))
 
     def clone_info(self):
         """per cloned context: how its keys got there ({"path": "same_device" | "peer" | "staged", "bytes", "seconds"})"""
