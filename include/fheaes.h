@@ -769,14 +769,16 @@ int fheaes_audit_debug(fheaes_ctx *ctx, uint64_t row, uint32_t word, uint64_t xo
  * recombined from the resident byte planes, one 64-bit multiply-add per term -- no matrix cores, no digit planes, no LDS-DMA) and compared
  * on the device, bit for bit.  Each stage has its own rows, seed, counters, records, launch number and hook; the launch number counts that
  * stage's audited launches alone, so the rows the blind rotation's audit samples do not depend on whether the key switches are audited.
- * `stage` = FHEAES_STAGE_BLIND_ROTATE: the first three calls ARE fheaes_audit_set / _read / _debug and share their state.  Any other stage,
- * a NULL context or `rows` > FHEAES_AUDIT_MAX_ROWS: FHEAES_ERR_INVALID.
+ * `stage` = FHEAES_STAGE_BLIND_ROTATE: the first three calls ARE fheaes_audit_set / _read / _debug -- one implementation, one state per
+ * stage, and what is said of a call here holds under either name.  Any other stage, a NULL context or `rows` > FHEAES_AUDIT_MAX_ROWS:
+ * FHEAES_ERR_INVALID.
  *
  * fheaes_audit_stage_set: as fheaes_audit_set -- `rows` = 0 turns the stage's audit off and frees its buffers (fheaes_destroy frees them
  * too); else every launch of the stage of m >= `min_rows` rows is audited on S = min(rows, m) rows, the rows fheaes_audit_rows(seed,
  * launch, m, rows) names: the WoPBS chunks and round windows of every call, the gate's bootstrap, fheaes_keyswitch_batch,
  * fheaes_pfpks_batch, and the single-block launches of fheaes_pack_bits, fheaes_pack_bits_mod and fheaes_pack_round_keys.  The only place
- * that allocates (the gathered rows of the plain form and the state: two allocations; refused: FHEAES_ERR_NOMEM and the stage is off); an
+ * that allocates (the gathered rows of the plain form and the state: two allocations, and the gathered inputs before them for the blind
+ * rotation: three; sized for FHEAES_AUDIT_MAX_ROWS whatever `rows` is; refused: FHEAES_ERR_NOMEM and the stage is off); an
  * audited call allocates nothing and the host waits for nothing.  Zeroes the stage's counters and launch number, drops its pending hook.
  * With profiling on the audit's time counts into the stage's total_ms; `launches` and `units` count the product launch only.
  * fheaes_audit_stage_read: as fheaes_audit_read.  A record is {launch, row, word, that word of the product launch, that word of the plain

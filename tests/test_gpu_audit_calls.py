@@ -1,4 +1,4 @@
-"""The audit (include/fheaes.h, "audit"; launch_audit in csrc/engine_launch.h) under every call and at every launch site.  It can fail in
+"""The audit (include/fheaes.h, "audit"; launch_blind_rotate_audit in csrc/engine_launch.h) under every call and at every launch site.  It can fail in
 two ways: a false alarm (rows_wrong > 0, or other words, on a correct engine in a call or launch shape nobody ran with it on) and a silent
 miss (a launch that is not audited, or a gather and compare that read other rows than the sample names).  test_gpu_audit.py holds the
 mechanism to its contract through fheaes_cbs_pbs_batch; this file holds the engine to "every blind-rotation launch":

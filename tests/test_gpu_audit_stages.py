@@ -1,4 +1,4 @@
-"""The audit of the two key switches (include/fheaes.h, "audit of the key switches"; kern_audit.h, launch_stage_audit): sampled rows of
+"""The audit of the two key switches (include/fheaes.h, "audit of the key switches"; kern_audit.h, launch_keyswitch_audit): sampled rows of
 every K1 and K3 launch computed again by the plain form and compared on the device.
 
   1. the plain form by itself, every row: fheaes_audit_plain_batch against the product launch and against the oracle, word for word and
@@ -540,6 +540,75 @@ def test_bad_arguments_of_the_stage_calls(toy_server):
         assert counters(E, K2) == (1, 8, 0) and E.audit_read()["rows_checked"] == 8
         E.audit_set(0)
         assert counters(E, K2) == (0, 0, 0)
+        # the word bound of stage 1 is the blind rotation's: a ciphertext of kN + 1 words
+        assert lib.fheaes_audit_stage_debug(h, 1, 0, p.big1, 1) == -1 and lib.fheaes_audit_stage_debug(h, 1, 0, p.big1 - 1, 1) == 0
+
+
+def k2_batch(E, small):
+    """one blind-rotation launch of 24 rows into guard rows; its rows, settled"""
+    buf, out = guarded(24, E.params.big1)
+    E.cbs_pbs_batch(small, out, 24)
+    E.synchronize()
+    assert guards_intact(buf)
+    return out
+
+
+@pytest.mark.parametrize("hook,read", [("stage", "first"), ("first", "stage")], ids=["stage_debug-audit_read", "audit_debug-stage_read"])
+def test_k2_hook_set_through_one_spelling_is_seen_through_the_other(hook, read, toy_server):
+    import torch
+
+    p, m, rows = toy_server.params, 24, 8
+    assert _native.Engine._audit_stage(K2) == 1
+    small = dev(np.random.default_rng(2).integers(0, 1 << 64, (m, p.n + 1), dtype=np.uint64))
+    row, word = _native.audit_rows(SEED, 0, m, rows)[5], p.big1 - 2
+    with private(toy_server) as srv:
+        E = srv.engine
+        want = k2_batch(E, small)
+        (E.audit_stage_set(K2, rows, 0, SEED) if hook == "stage" else E.audit_set(rows, 0, SEED))
+        (E.audit_stage_debug(K2, row, word, MASK) if hook == "stage" else E.audit_debug(row, word, MASK))
+        out = k2_batch(E, small)
+        assert torch.nonzero(out != want).tolist() == [[row, word]]
+        r = E.audit_read() if read == "first" else E.audit_stage_read(K2)
+        assert (r["launches"], r["rows_checked"], r["rows_wrong"]) == (1, rows, 1)
+        w = int(host(want)[row, word])
+        assert [[int(v) for v in rec] for rec in r["records"]] == [[0, row, word, w ^ MASK, w]]
+        out = k2_batch(E, small)                                          # one shot: clean again, the wrong-row counter is sticky
+        assert torch.equal(out, want)
+        assert counters(E, K2) == (2, 2 * rows, 1) and E.audit_read()["launches"] == 2
+        assert counters(E, KS) == (0, 0, 0) and counters(E, PF) == (0, 0, 0)
+
+
+def test_k2_allocations_are_the_same_under_both_spellings(toy_server):
+    with private(toy_server) as srv:
+        E = srv.engine
+        E.audit_set(0)
+        E.alloc_debug(0)
+        E.audit_set(8, 0, SEED)
+        first = E.alloc_debug(0)
+        assert first == 3                                                 # the gathered inputs, the latency form's rows and the state
+        E.audit_set(0)
+        E.alloc_debug(0)
+        E.audit_stage_set(K2, 8, 0, SEED)
+        assert E.alloc_debug(0) == first
+        E.audit_stage_set(K2, 256, 0, SEED)                               # sized for 256 rows whatever `rows` was
+        assert E.alloc_debug(0) == 0
+        E.audit_stage_set(K2, 0)                                          # frees all three
+        E.alloc_debug(0)
+        E.audit_stage_set(K2, 8, 0, SEED)
+        assert E.alloc_debug(0) == first
+
+
+def test_audit_set_0_turns_k2_off_and_leaves_the_key_switches_on(toy_server, env):
+    """three entries, not aliases: K2 off through its first spelling, K1 and K3 still count"""
+    case = ws.BY_NAME["wopbs_8_bits_shared_luts"]
+    h = case.build(env, 0)
+    with private(toy_server) as srv:
+        E = srv.engine
+        all_on(E, 256)
+        E.audit_set(0)
+        once(srv, case, h)
+        assert counters(E, K2) == (0, 0, 0) and E.audit_read()["launches"] == 0
+        assert counters(E, KS) == (1, 24, 0) and counters(E, PF) == (1, 24, 0)
 
 
 # ---- memory --------------------------------------------------------------------------------------------------------------------------------

@@ -735,13 +735,17 @@ class Engine:
         """the rows that audited launch number `launch` of m bits checks under `seed` (fheaes_audit_rows: host only, no GPU)"""
         return audit_rows(seed, launch, m, rows)
 
+    def _audit_read(self, read, *stage) -> dict:
+        """the counters and records of one audit through its C entry point, fheaes_audit_read or fheaes_audit_stage_read with its stage"""
+        la, ch, wr, n = _c.c_uint64(), _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
+        rec = np.zeros((AUDIT_RECORDS, 5), dtype=np.uint64)
+        self._check(read(self._h, *stage, _c.byref(la), _c.byref(ch), _c.byref(wr), rec.ctypes.data_as(_u64p), AUDIT_RECORDS, _c.byref(n)))
+        return {"launches": la.value, "rows_checked": ch.value, "rows_wrong": wr.value, "records": rec[:n.value]}
+
     def audit_read(self) -> dict:
         """{"launches", "rows_checked", "rows_wrong": the counters since audit_set, "records": uint64[n][5] = (launch, row, first differing
         word, word of the product launch, word of the audit) of the first AUDIT_RECORDS wrong rows}; synchronises the stream"""
-        la, ch, wr, n = _c.c_uint64(), _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
-        rec = np.zeros((AUDIT_RECORDS, 5), dtype=np.uint64)
-        self._check(self._lib.fheaes_audit_read(self._h, _c.byref(la), _c.byref(ch), _c.byref(wr), rec.ctypes.data_as(_u64p), AUDIT_RECORDS, _c.byref(n)))
-        return {"launches": la.value, "rows_checked": ch.value, "rows_wrong": wr.value, "records": rec[:n.value]}
+        return self._audit_read(self._lib.fheaes_audit_read)
 
     def audit_debug(self, row: int, word: int, xor_mask: int):
         """test hook (fheaes_audit_debug), one shot: the next audited launch XORs xor_mask into word `word` of row `row` of its output"""
@@ -759,11 +763,7 @@ class Engine:
 
     def audit_stage_read(self, stage) -> dict:
         """audit_read for one stage of AUDIT_STAGES; a record's word is the offset among the words the launch wrote for the row"""
-        la, ch, wr, n = _c.c_uint64(), _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
-        rec = np.zeros((AUDIT_RECORDS, 5), dtype=np.uint64)
-        self._check(self._lib.fheaes_audit_stage_read(self._h, self._audit_stage(stage), _c.byref(la), _c.byref(ch), _c.byref(wr), rec.ctypes.data_as(_u64p),
-                                                      AUDIT_RECORDS, _c.byref(n)))
-        return {"launches": la.value, "rows_checked": ch.value, "rows_wrong": wr.value, "records": rec[:n.value]}
+        return self._audit_read(self._lib.fheaes_audit_stage_read, self._audit_stage(stage))
 
     def audit_stage_debug(self, stage, row: int, word: int, xor_mask: int):
         """test hook (fheaes_audit_stage_debug), one shot: that stage's next audited launch XORs xor_mask into word `word` of row `row`"""

@@ -175,83 +175,27 @@ int fheaes_k2_park_read(fheaes_ctx *ctx, uint64_t *fallbacks, uint64_t *violatio
     if (record_n) *record_n = ctx->k2_park_record_n;
     return FHEAES_OK;
 }
-// ---- the audit (kern_audit.h, launch_audit) -----------------------------------------------------------------------------------------
-int fheaes_audit_set(fheaes_ctx *ctx, uint32_t rows, uint64_t min_bits, uint64_t seed)
-{
-    if (!ctx) return FHEAES_ERR_INVALID;
-    CtxLock lock__(ctx);
-    if (rows > AUDIT_MAX_ROWS) return ctx->fail(FHEAES_ERR_INVALID, "audit_set: at most %d rows per launch (got %u)", AUDIT_MAX_ROWS, rows);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->audit_rows = 0;                 // off until everything below has succeeded
-    ctx->audit_hook = false;
-    ctx->audit_launch = 0;
-    if (rows == 0) {
-        for (DevBuf *b : {&ctx->audit_in, &ctx->audit_out, &ctx->audit_state})
-            if (b->p) { HIP_TRY(ctx, hipFree(b->p)); b->p = nullptr; b->bytes = 0; }
-        return FHEAES_OK;
-    }
-    // for FHEAES_AUDIT_MAX_ROWS rows whatever `rows` is: a later fheaes_audit_set with more rows moves nothing
-    TRY(ensure(ctx, ctx->audit_in, (size_t)AUDIT_MAX_ROWS * (ctx->n + 1) * 8));
-    TRY(ensure(ctx, ctx->audit_out, (size_t)AUDIT_MAX_ROWS * ctx->big1 * 8));
-    TRY(ensure(ctx, ctx->audit_state, AUDIT_STATE_WORDS * 8));
-    HIP_TRY(ctx, hipMemset(ctx->audit_state.p, 0, AUDIT_STATE_WORDS * 8));
-    ctx->audit_min_bits = min_bits;
-    ctx->audit_seed = seed;
-    ctx->audit_rows = rows;
-    return FHEAES_OK;
-}
-int fheaes_audit_rows(uint64_t seed, uint64_t launch, uint64_t m, uint32_t rows, uint64_t *rows_out)
-{
-    if (!rows_out || m == 0 || rows == 0 || rows > AUDIT_MAX_ROWS) return FHEAES_ERR_INVALID;
-    const uint32_t S = (uint32_t)std::min<uint64_t>(rows, m);
-    for (uint32_t s = 0; s < S; ++s) rows_out[s] = audit_row(seed, launch, m, S, s);
-    return FHEAES_OK;
-}
-int fheaes_audit_read(fheaes_ctx *ctx, uint64_t *launches, uint64_t *rows_checked, uint64_t *rows_wrong, uint64_t *records_out, uint64_t record_cap,
-                      uint64_t *record_n)
-{
-    if (!ctx) return FHEAES_ERR_INVALID;
-    CtxLock lock__(ctx);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    uint64_t st[AUDIT_STATE_WORDS] = {};            // audit off: all zero
-    if (ctx->audit_state.p) HIP_TRY(ctx, hipMemcpy(st, ctx->audit_state.p, sizeof st, hipMemcpyDeviceToHost));
-    const uint64_t n = std::min<uint64_t>(st[AUDIT_ST_WRONG], AUDIT_RECORDS);
-    if (records_out && record_cap < n)
-        return ctx->fail(FHEAES_ERR_INVALID, "audit_read: %llu records do not fit record_cap = %llu", (unsigned long long)n, (unsigned long long)record_cap);
-    if (launches) *launches = st[AUDIT_ST_LAUNCHES];
-    if (rows_checked) *rows_checked = st[AUDIT_ST_CHECKED];
-    if (rows_wrong) *rows_wrong = st[AUDIT_ST_WRONG];
-    if (records_out && n) std::memcpy(records_out, st + AUDIT_ST_RECORDS, n * AUDIT_RECORD_WORDS * 8);
-    if (record_n) *record_n = n;
-    return FHEAES_OK;
-}
-int fheaes_audit_debug(fheaes_ctx *ctx, uint64_t row, uint32_t word, uint64_t xor_mask)
-{
-    if (!ctx) return FHEAES_ERR_INVALID;
-    CtxLock lock__(ctx);
-    if (xor_mask == 0 || word >= ctx->big1)
-        return ctx->fail(FHEAES_ERR_INVALID, "audit_debug: a non-zero mask and a word in 0..%u (got mask %#llx, word %u)", ctx->big, (unsigned long long)xor_mask, word);
-    ctx->audit_hook = true;
-    ctx->audit_hook_row = row; ctx->audit_hook_word = word; ctx->audit_hook_mask = xor_mask;
-    return FHEAES_OK;
-}
-// ---- the audit of the key switches (kern_audit.h, launch_stage_audit); FHEAES_STAGE_BLIND_ROTATE: the calls above ---------------------
+// ---- the audit (StageAudit in engine_ctx.h; kern_audit.h; audit_begin, audit_compare and the launchers in engine_launch.h) ---------------
 namespace {
-StageAudit *stage_audit(fheaes_ctx *c, int stage)
+// au: the stage's audit, null for a stage that has none.  in_words: the words of a gathered input row, 0 for a second form that reads the
+// sampled rows where they lie (no buffer).  out_words: the written words of one row of the stage's widest launch.
+struct AuditShape { StageAudit *au; uint32_t in_words, out_words; };
+AuditShape audit_shape(fheaes_ctx *c, int stage)
 {
-    return stage == FHEAES_STAGE_KEYSWITCH ? &c->ks_audit : stage == FHEAES_STAGE_PFPKS ? &c->pf_audit : nullptr;
+    switch (stage) {
+    case FHEAES_STAGE_KEYSWITCH: return {&c->audit[stage], 0, c->n + 1};
+    case FHEAES_STAGE_BLIND_ROTATE: return {&c->audit[stage], c->n + 1, c->big1};
+    case FHEAES_STAGE_PFPKS: return {&c->audit[stage], 0, c->k1 * c->k1 * FHE_N};       // the k + 1 key blocks
+    }
+    return {nullptr, 0, 0};
 }
-// the written words of one row of the stage's widest launch: K1 n + 1, K3 the k + 1 key blocks
-uint32_t stage_row_words(const fheaes_ctx *c, int stage) { return stage == FHEAES_STAGE_KEYSWITCH ? c->n + 1 : c->k1 * c->k1 * FHE_N; }
 }  // namespace
 int fheaes_audit_stage_set(fheaes_ctx *ctx, int stage, uint32_t rows, uint64_t min_rows, uint64_t seed)
 {
     if (!ctx) return FHEAES_ERR_INVALID;
-    if (stage == FHEAES_STAGE_BLIND_ROTATE) return fheaes_audit_set(ctx, rows, min_rows, seed);
     CtxLock lock__(ctx);
-    StageAudit *au = stage_audit(ctx, stage);
+    const AuditShape sh = audit_shape(ctx, stage);
+    StageAudit *const au = sh.au;
     if (!au) return ctx->fail(FHEAES_ERR_INVALID, "audit_stage_set: stage %d has no audit (the key switch, the blind rotation, the packing key switch)", stage);
     if (rows > AUDIT_MAX_ROWS) return ctx->fail(FHEAES_ERR_INVALID, "audit_stage_set: at most %d rows per launch (got %u)", AUDIT_MAX_ROWS, rows);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -260,12 +204,13 @@ int fheaes_audit_stage_set(fheaes_ctx *ctx, int stage, uint32_t rows, uint64_t m
     au->hook = false;
     au->launch = 0;
     if (rows == 0) {
-        for (DevBuf *b : {&au->out, &au->state})
+        for (DevBuf *b : {&au->in, &au->out, &au->state})
             if (b->p) { HIP_TRY(ctx, hipFree(b->p)); b->p = nullptr; b->bytes = 0; }
         return FHEAES_OK;
     }
-    // for FHEAES_AUDIT_MAX_ROWS rows whatever `rows` is, as fheaes_audit_set does
-    TRY(ensure(ctx, au->out, (size_t)AUDIT_MAX_ROWS * stage_row_words(ctx, stage) * 8));
+    // for FHEAES_AUDIT_MAX_ROWS rows whatever `rows` is: a later set with more rows moves nothing
+    if (sh.in_words) TRY(ensure(ctx, au->in, (size_t)AUDIT_MAX_ROWS * sh.in_words * 8));
+    TRY(ensure(ctx, au->out, (size_t)AUDIT_MAX_ROWS * sh.out_words * 8));
     TRY(ensure(ctx, au->state, AUDIT_STATE_WORDS * 8));
     HIP_TRY(ctx, hipMemset(au->state.p, 0, AUDIT_STATE_WORDS * 8));
     au->min_rows = min_rows;
@@ -277,9 +222,8 @@ int fheaes_audit_stage_read(fheaes_ctx *ctx, int stage, uint64_t *launches, uint
                             uint64_t record_cap, uint64_t *record_n)
 {
     if (!ctx) return FHEAES_ERR_INVALID;
-    if (stage == FHEAES_STAGE_BLIND_ROTATE) return fheaes_audit_read(ctx, launches, rows_checked, rows_wrong, records_out, record_cap, record_n);
     CtxLock lock__(ctx);
-    StageAudit *au = stage_audit(ctx, stage);
+    const StageAudit *const au = audit_shape(ctx, stage).au;
     if (!au) return ctx->fail(FHEAES_ERR_INVALID, "audit_stage_read: stage %d has no audit", stage);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -298,15 +242,36 @@ int fheaes_audit_stage_read(fheaes_ctx *ctx, int stage, uint64_t *launches, uint
 int fheaes_audit_stage_debug(fheaes_ctx *ctx, int stage, uint64_t row, uint32_t word, uint64_t xor_mask)
 {
     if (!ctx) return FHEAES_ERR_INVALID;
-    if (stage == FHEAES_STAGE_BLIND_ROTATE) return fheaes_audit_debug(ctx, row, word, xor_mask);
     CtxLock lock__(ctx);
-    StageAudit *au = stage_audit(ctx, stage);
+    const AuditShape sh = audit_shape(ctx, stage);
+    StageAudit *const au = sh.au;
     if (!au) return ctx->fail(FHEAES_ERR_INVALID, "audit_stage_debug: stage %d has no audit", stage);
-    if (xor_mask == 0 || word >= stage_row_words(ctx, stage))
-        return ctx->fail(FHEAES_ERR_INVALID, "audit_stage_debug: a non-zero mask and a word below %u (got mask %#llx, word %u)", stage_row_words(ctx, stage),
+    if (xor_mask == 0 || word >= sh.out_words)
+        return ctx->fail(FHEAES_ERR_INVALID, "audit_stage_debug: a non-zero mask and a word below %u (got mask %#llx, word %u)", sh.out_words,
                          (unsigned long long)xor_mask, word);
     au->hook = true;
     au->hook_row = row; au->hook_word = word; au->hook_mask = xor_mask;
+    return FHEAES_OK;
+}
+// the blind rotation's audit under its first names
+int fheaes_audit_set(fheaes_ctx *ctx, uint32_t rows, uint64_t min_bits, uint64_t seed)
+{
+    return fheaes_audit_stage_set(ctx, FHEAES_STAGE_BLIND_ROTATE, rows, min_bits, seed);
+}
+int fheaes_audit_read(fheaes_ctx *ctx, uint64_t *launches, uint64_t *rows_checked, uint64_t *rows_wrong, uint64_t *records_out, uint64_t record_cap,
+                      uint64_t *record_n)
+{
+    return fheaes_audit_stage_read(ctx, FHEAES_STAGE_BLIND_ROTATE, launches, rows_checked, rows_wrong, records_out, record_cap, record_n);
+}
+int fheaes_audit_debug(fheaes_ctx *ctx, uint64_t row, uint32_t word, uint64_t xor_mask)
+{
+    return fheaes_audit_stage_debug(ctx, FHEAES_STAGE_BLIND_ROTATE, row, word, xor_mask);
+}
+int fheaes_audit_rows(uint64_t seed, uint64_t launch, uint64_t m, uint32_t rows, uint64_t *rows_out)
+{
+    if (!rows_out || m == 0 || rows == 0 || rows > AUDIT_MAX_ROWS) return FHEAES_ERR_INVALID;
+    const uint32_t S = (uint32_t)std::min<uint64_t>(rows, m);
+    for (uint32_t s = 0; s < S; ++s) rows_out[s] = audit_row(seed, launch, m, S, s);
     return FHEAES_OK;
 }
 int fheaes_audit_plain_batch(fheaes_ctx *ctx, int stage, const uint64_t *lwe_in, uint64_t m, int block, uint64_t *out)
@@ -320,23 +285,12 @@ int fheaes_audit_plain_batch(fheaes_ctx *ctx, int stage, const uint64_t *lwe_in,
     TRY(check_keys(ctx));
     if (!lwe_in || !out) return ctx->fail(FHEAES_ERR_INVALID, "null pointer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint32_t gsz = ctx->k1 * FHE_N;
-    const unsigned nz = k1 || block >= 0 ? 1 : ctx->k1;
-    const uint64_t row_words = k1 ? ctx->n + 1 : (uint64_t)nz * gsz;
     // device pointers only: a hook of tests and tools, which hold their arrays on the device; it stages nothing and only enqueues
-    KeyswitchPlainArgs a{};
-    a.in_stride = ctx->big1; a.out_stride = row_words; a.body_index = -1;
-    if (k1) {
-        a.n_in = ctx->big; a.bfrag = ctx->ksk_frag; a.ksteps = ctx->ks_ksteps; a.coltiles = ctx->ks_coltiles; a.ncols = ctx->n + 1;
-        a.body_index = (int32_t)ctx->big; a.body_col = ctx->n;
-    } else {
-        a.n_in = ctx->big1; a.bfrag = ctx->pfpksk_frag; a.ksteps = ctx->pf_ksteps; a.coltiles = ctx->pf_coltiles; a.ncols = gsz;
-        if (block >= 0) a.bfrag += (size_t)block * ctx->pf_ksteps * ctx->pf_coltiles * 8 * 1024;
-        a.out_z_stride = nz > 1 ? gsz : 0;
-    }
+    const unsigned nz = k1 ? 1 : keyswitch_k3_blocks(ctx, block);
+    KeyswitchPlainArgs a = k1 ? keyswitch_plain_args(keyswitch_k1_args(ctx), ctx->big, nz) : keyswitch_plain_args(keyswitch_k3_args(ctx, block), ctx->big1, nz);
     // in groups of FHEAES_AUDIT_MAX_ROWS rows: the launches the audit makes
     for (uint64_t r0 = 0; r0 < m; r0 += AUDIT_MAX_ROWS) {
-        a.in = lwe_in + r0 * ctx->big1; a.out = out + r0 * row_words;
+        a.in = lwe_in + r0 * a.in_stride; a.out = out + r0 * a.out_stride;
         a.S = (uint32_t)std::min<uint64_t>(AUDIT_MAX_ROWS, m - r0); a.m = a.S;
         launch_keyswitch_plain(ctx, stage, a, nz);
         HIP_TRY(ctx, hipGetLastError());

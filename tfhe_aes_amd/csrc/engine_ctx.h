@@ -28,19 +28,28 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
-// The audit of one key-switching stage (fheaes_audit_stage_set, kern_audit.h): rows > 0 = every launch of the stage of at least min_rows rows
-// is computed again on min(rows, m) sampled rows by the plain form; launch = audited launches of THIS stage since its stage_set (the rows
-// the blind rotation's audit samples do not depend on whether the key switches are audited).  out: the gathered rows of the plain form,
-// state: the counters and records (AUDIT_STATE_WORDS); allocated by stage_set and never by a launch, state and not scratch like the
-// blind rotation's.  hook*: fheaes_audit_stage_debug, one shot.
+// The audit of one stage (fheaes_audit_stage_set; fheaes_audit_set is the blind rotation's; kern_audit.h): rows > 0 = every launch of the
+// stage of at least min_rows rows is computed again on min(rows, m) sampled rows by the stage's second form; launch = audited launches of
+// THIS stage since its set (the rows one stage's audit samples do not depend on whether another stage is audited).  out: the second form's
+// results, one row per sample; state: the counters and records (AUDIT_STATE_WORDS).  The buffers are allocated by the set call and never
+// by a launch; like the parking owner words they are state, not scratch (not among FHEAES_WS_BUFFERS).  hook*: the test hook
+// (fheaes_audit_stage_debug), one shot: the next audited launch XORs hook_mask into word hook_word of row hook_row of its output.
+// What differs between the stages (audit_shape in engine.hip, the launchers in engine_launch.h):
+//   K2 (blind rotation)      second form: the latency form on the sampled rows' small LWEs, gathered into `in` (n + 1 words a row);
+//                            a row is the kN + 1 words of an output ciphertext
+//   K1 (LWE key switch)      second form: the plain form (keyswitch_plain_kernel), which reads the sampled rows where they lie: no `in`;
+//                            a row is n + 1 words
+//   K3 (packing key switch)  the plain form, no `in`; a row is the (k+1)N words of each key block of the launch: (k+1)^2 N at the widest
 struct StageAudit {
     uint32_t rows = 0;
     uint64_t min_rows = 0, seed = 0, launch = 0;
-    DevBuf out, state;
+    DevBuf in, out, state;
     bool hook = false;
     uint64_t hook_row = 0, hook_mask = 0;
     uint32_t hook_word = 0;
+    bool wants(uint64_t m) const { return rows && m >= min_rows; }      // a launch of m rows is audited
 };
+static_assert(FHEAES_STAGE_KEYSWITCH == 0 && FHEAES_STAGE_BLIND_ROTATE == 1 && FHEAES_STAGE_PFPKS == 2, "fheaes_ctx::audit is indexed by these three stages");
 
 struct fheaes_ctx {
     fheaes_params p{};
@@ -71,17 +80,7 @@ struct fheaes_ctx {
     bool k2_park_pattern = false, k2_park_record = false;
     uint64_t k2_park_record_n = 0;
     uint32_t aes_window = 0;             // fheaes_aes_set_window: 0 = automatic (aes_window_plan), FHEAES_AES_WINDOW_OFF = one WoPBS per step, else forced
-    // the audit (fheaes_audit_set, kern_audit.h): audit_rows > 0 = every blind-rotation launch of at least audit_min_bits is re-run on
-    // min(audit_rows, m) sampled rows through the latency form; audit_launch = audited launches since fheaes_audit_set.  The buffers are
-    // allocated there and never by a launch; like the parking owner words they are state, not scratch (not among FHEAES_WS_BUFFERS)
-    uint32_t audit_rows = 0;
-    uint64_t audit_min_bits = 0, audit_seed = 0, audit_launch = 0;
-    DevBuf audit_in, audit_out, audit_state;
-    // test hook (fheaes_audit_debug), one shot: the next audited launch XORs audit_hook_mask into word audit_hook_word of row audit_hook_row
-    bool audit_hook = false;
-    uint64_t audit_hook_row = 0, audit_hook_mask = 0;
-    uint32_t audit_hook_word = 0;
-    StageAudit ks_audit, pf_audit;       // the key switches' (launch_keyswitch, launch_pfpks)
+    StageAudit audit[3];                 // by FHEAES_STAGE_KEYSWITCH, _BLIND_ROTATE, _PFPKS (launch_keyswitch, launch_cbs_pbs, launch_pfpks)
     // test hook (fheaes_alloc_debug), one shot: alloc_seen counts the device allocations ctx_malloc has been asked for since the hook was
     // last set; the alloc_fail_nth-th of them (0: none) goes to the runtime with a size it must refuse
     uint64_t alloc_seen = 0, alloc_fail_nth = 0;

@@ -105,10 +105,45 @@ AesWindowPlan aes_window_plan(uint64_t n, uint64_t steps, uint32_t cu_count, uin
     return pl;
 }
 
-// ---- the plain form of the key switches and the audit behind their launches (kern_audit.h) ---------------------------------------
+// ---- the audit behind a product launch (kern_audit.h, StageAudit) and the plain form of the key switches ---------------------------
+static_assert(FHEAES_AUDIT_MAX_ROWS == AUDIT_MAX_ROWS && FHEAES_AUDIT_RECORDS == AUDIT_RECORDS, "include/fheaes.h and kern_audit.h disagree");
 static_assert(KSP_KSTEP == KS_KSTEP, "kern_audit.h reads the B fragments of kern_keyswitch.h");
 #define KSP_ROWS_K1 4          /* rows per workgroup: K1 has few column tiles (42 at PARAM_OPT), so more row groups */
 #define KSP_ROWS_K3 8
+
+// The audit of one product launch runs behind it on the same stream and inside its StageScope: the time counts into the stage, `launches`
+// and `units` count the product launch alone.  Nothing is allocated (the set call did) and the host waits for nothing: a mismatch is learnt
+// from the read call.  A launcher that finds StageAudit::wants(m) calls audit_begin, runs the stage's second form on the S sampled rows
+// into au.out (row s of it: row_words words), and calls audit_compare.
+struct AuditLaunch {
+    StageAudit &au;
+    uint64_t m, launch;          // rows of the product launch; its number among the stage's audited launches
+    uint32_t S;                  // sampled rows: row audit_row(au.seed, launch, m, S, s) for s < S
+    uint64_t *out;               // the product launch's output: row r is the row_words words at out + r out_stride
+    uint64_t out_stride;
+    uint32_t row_words;
+};
+
+// takes the launch number and fires the one-shot hook on the product launch's output
+AuditLaunch audit_begin(fheaes_ctx *c, StageAudit &au, uint64_t m, uint64_t *out, uint64_t out_stride, uint32_t row_words)
+{
+    const AuditLaunch L{au, m, au.launch++, (uint32_t)std::min<uint64_t>(au.rows, m), out, out_stride, row_words};
+    if (au.hook) {
+        au.hook = false;                             // one shot; a row or a word beyond this launch's is dropped without a write
+        if (au.hook_row < m && au.hook_word < row_words)
+            hipLaunchKernelGGL(audit_tamper_kernel, dim3(1), dim3(1), 0, c->stream, out, (uint32_t)out_stride, au.hook_row, au.hook_word, au.hook_mask);
+    }
+    return L;
+}
+
+// the sampled rows of the product launch against au.out, counted and recorded in au.state
+int audit_compare(fheaes_ctx *c, const AuditLaunch &L)
+{
+    hipLaunchKernelGGL(audit_compare_kernel, dim3(L.S), dim3(AUDIT_THREADS), 0, c->stream, L.out, L.out_stride, (const uint64_t *)L.au.out.p, L.row_words, L.au.seed,
+                       L.launch, L.m, L.S, (uint64_t *)L.au.state.p);
+    HIP_TRY(c, hipGetLastError());
+    return FHEAES_OK;
+}
 
 // rows 0 .. a.S - 1 (or the a.S sampled rows) of key switch `stage` through the plain form, nz key blocks
 void launch_keyswitch_plain(fheaes_ctx *c, int stage, const KeyswitchPlainArgs &a, unsigned nz)
@@ -120,37 +155,49 @@ void launch_keyswitch_plain(fheaes_ctx *c, int stage, const KeyswitchPlainArgs &
         hipLaunchKernelGGL((keyswitch_plain_kernel<12, 3, KSP_ROWS_K3>), dim3((a.S + KSP_ROWS_K3 - 1) / KSP_ROWS_K3, gy, nz), dim3(KSP_THREADS), 0, c->stream, a);
 }
 
-// what the plain form takes over from a product launch: its input, its key bytes, its real dimensions; n_in: the words of a row it decomposes
-KeyswitchPlainArgs keyswitch_plain_args(const KeyswitchArgs &prod, uint32_t n_in)
+// K1's key, dimensions and body term, and K3's key, dimensions and -- `block` >= 0: key block r = `block` alone -- the offset and z-stride
+// of a single block, as the product kernels and the plain form take them; the caller adds afrag, in, out, out_stride (K3) and m
+KeyswitchArgs keyswitch_k1_args(const fheaes_ctx *c)
+{
+    KeyswitchArgs a{};
+    a.bfrag = c->ksk_frag; a.ksteps = c->ks_ksteps; a.coltiles = c->ks_coltiles;
+    a.in_stride = c->big1; a.body_index = (int32_t)c->big; a.body_col = c->n; a.ncols = c->n + 1;
+    a.out_stride = c->n + 1; a.out_z_stride = 0;
+    return a;
+}
+KeyswitchArgs keyswitch_k3_args(const fheaes_ctx *c, int block)
+{
+    KeyswitchArgs a{};
+    a.bfrag = c->pfpksk_frag; a.ksteps = c->pf_ksteps; a.coltiles = c->pf_coltiles;
+    if (block >= 0) a.bfrag += (size_t)block * c->pf_ksteps * c->pf_coltiles * 8 * 1024;
+    a.in_stride = c->big1; a.body_index = -1; a.body_col = 0; a.ncols = c->k1 * FHE_N;
+    a.out_z_stride = block >= 0 ? 0 : a.ncols;
+    return a;
+}
+unsigned keyswitch_k3_blocks(const fheaes_ctx *c, int block) { return block >= 0 ? 1 : c->k1; }
+
+// what the plain form takes over from a product launch: its input, its key bytes, its real dimensions; n_in: the words of a row it
+// decomposes; nz: the key blocks, whose nz ncols words make up a row of the plain form's output (K3 over all blocks: out_z_stride = ncols)
+KeyswitchPlainArgs keyswitch_plain_args(const KeyswitchArgs &prod, uint32_t n_in, unsigned nz)
 {
     KeyswitchPlainArgs a{};
     a.in = prod.in; a.in_stride = prod.in_stride; a.n_in = n_in;
     a.bfrag = prod.bfrag; a.ksteps = prod.ksteps; a.coltiles = prod.coltiles; a.ncols = prod.ncols;
     a.body_index = prod.body_index; a.body_col = prod.body_col;
+    a.out_stride = (uint64_t)nz * prod.ncols; a.out_z_stride = nz > 1 ? prod.ncols : 0;
     return a;
 }
 
-// The audit of one key-switch launch, behind it on the same stream and inside its StageScope, under launch_audit's rules: the time counts
-// into the stage, `launches` and `units` count the product launch alone, nothing is allocated (fheaes_audit_stage_set did), the host waits
-// for nothing.  `prod`: the product launch's arguments, nz its key blocks: a row's written words are the nz ncols words at
-// out + row out_stride (K3 over all blocks: out_z_stride = ncols), and a record's `word` is the offset among them.
-int launch_stage_audit(fheaes_ctx *c, int stage, StageAudit &au, const KeyswitchArgs &prod, uint32_t n_in, unsigned nz)
+// The audit of one key-switch launch.  `prod`: the product launch's arguments, nz its key blocks: a row's written words are the nz ncols
+// words at out + row out_stride, and a record's `word` is the offset among them.
+int launch_keyswitch_audit(fheaes_ctx *c, int stage, const KeyswitchArgs &prod, uint32_t n_in, unsigned nz)
 {
-    const uint64_t m = prod.m, launch = au.launch++;
-    const uint32_t S = (uint32_t)std::min<uint64_t>(au.rows, m), row_words = nz * prod.ncols;
-    if (au.hook) {
-        au.hook = false;                             // one shot; a row or a word beyond this launch's is dropped without a write
-        if (au.hook_row < m && au.hook_word < row_words)
-            hipLaunchKernelGGL(audit_tamper_kernel, dim3(1), dim3(1), 0, c->stream, prod.out, (uint32_t)prod.out_stride, au.hook_row, au.hook_word, au.hook_mask);
-    }
-    KeyswitchPlainArgs a = keyswitch_plain_args(prod, n_in);
-    a.out = (uint64_t *)au.out.p; a.out_stride = row_words; a.out_z_stride = nz > 1 ? prod.ncols : 0;
-    a.seed = au.seed; a.launch = launch; a.m = m; a.S = S; a.sampled = 1;
+    const AuditLaunch L = audit_begin(c, c->audit[stage], prod.m, prod.out, prod.out_stride, nz * prod.ncols);
+    KeyswitchPlainArgs a = keyswitch_plain_args(prod, n_in, nz);
+    a.out = (uint64_t *)L.au.out.p;
+    a.seed = L.au.seed; a.launch = L.launch; a.m = L.m; a.S = L.S; a.sampled = 1;
     launch_keyswitch_plain(c, stage, a, nz);
-    hipLaunchKernelGGL(audit_compare_rows_kernel, dim3(S), dim3(AUDIT_THREADS), 0, c->stream, prod.out, prod.out_stride, a.out, row_words, au.seed, launch, m, S,
-                       (uint64_t *)au.state.p);
-    HIP_TRY(c, hipGetLastError());
-    return FHEAES_OK;
+    return audit_compare(c, L);
 }
 
 // ---- kernel launchers ------------------------------------------------------------------------
@@ -163,15 +210,13 @@ int launch_keyswitch(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *ou
     int8_t *af = (int8_t *)c->ws_digits.p;
     const uint64_t threads = ct_tiles16 * c->ks_ksteps * 64;
     ks_launch_digits_k1(dim3((unsigned)((threads + 255) / 256)), c->stream, in, (uint64_t)c->big1, c->big, m, c->ks_ksteps, af);
-    KeyswitchArgs a{};
-    a.afrag = af; a.bfrag = c->ksk_frag; a.ksteps = c->ks_ksteps; a.coltiles = c->ks_coltiles;
-    a.in = in; a.in_stride = c->big1; a.body_index = (int32_t)c->big; a.body_col = c->n; a.ncols = c->n + 1;
-    a.out = out; a.out_stride = c->n + 1; a.out_z_stride = 0; a.m = m;
+    KeyswitchArgs a = keyswitch_k1_args(c);
+    a.afrag = af; a.in = in; a.out = out; a.m = m;
     // K1 through the LDS-tiled kernel too (round 6: 1.87 -> 1.48 ms per 16,384-bit launch, same words)
     dim3 grid((c->ks_coltiles + KSL_COL_TILES - 1) / KSL_COL_TILES, (unsigned)((m + 16 * KSL_CT_TILES - 1) / (16 * KSL_CT_TILES)), 1);
     ks_launch_mfma_lds(1, grid, c->stream, a);
     HIP_TRY(c, hipGetLastError());
-    if (c->ks_audit.rows && m >= c->ks_audit.min_rows) TRY(launch_stage_audit(c, FHEAES_STAGE_KEYSWITCH, c->ks_audit, a, c->big, 1));
+    if (c->audit[FHEAES_STAGE_KEYSWITCH].wants(m)) TRY(launch_keyswitch_audit(c, FHEAES_STAGE_KEYSWITCH, a, c->big, 1));
     return FHEAES_OK;
 }
 
@@ -181,21 +226,17 @@ int launch_pfpks(fheaes_ctx *c, const uint64_t *in, uint64_t m, uint64_t *out, u
 {
     if (m == 0) return FHEAES_OK;
     StageScope sc(c, FHEAES_STAGE_PFPKS, m);
-    const uint32_t gsz = c->k1 * FHE_N;
     const uint64_t ct_tiles16 = ((m + KS_CT_TILE - 1) / KS_CT_TILE) * (KS_CT_TILE / 16);
     TRY(ensure(c, c->ws_digits, ct_tiles16 * c->pf_ksteps * 2 * 1024));
     int8_t *af = (int8_t *)c->ws_digits.p;
     const uint64_t threads = ct_tiles16 * c->pf_ksteps * 64;
     ks_launch_digits_k3(dim3((unsigned)((threads + 255) / 256)), c->stream, in, (uint64_t)c->big1, c->big1, m, c->pf_ksteps, af);
-    KeyswitchArgs a{};
-    a.afrag = af; a.bfrag = c->pfpksk_frag; a.ksteps = c->pf_ksteps; a.coltiles = c->pf_coltiles;
-    if (block >= 0) a.bfrag += (size_t)block * c->pf_ksteps * c->pf_coltiles * 8 * 1024;
-    a.in = in; a.in_stride = c->big1; a.body_index = -1; a.body_col = 0; a.ncols = gsz;
-    a.out = out; a.out_stride = out_stride; a.out_z_stride = block >= 0 ? 0 : gsz; a.m = m;
-    dim3 grid((c->pf_coltiles + KSL_COL_TILES - 1) / KSL_COL_TILES, (unsigned)((m + 16 * KSL_CT_TILES - 1) / (16 * KSL_CT_TILES)), block >= 0 ? 1 : c->k1);
+    KeyswitchArgs a = keyswitch_k3_args(c, block);
+    a.afrag = af; a.in = in; a.out = out; a.out_stride = out_stride; a.m = m;
+    dim3 grid((c->pf_coltiles + KSL_COL_TILES - 1) / KSL_COL_TILES, (unsigned)((m + 16 * KSL_CT_TILES - 1) / (16 * KSL_CT_TILES)), keyswitch_k3_blocks(c, block));
     ks_launch_mfma_lds(2, grid, c->stream, a);
     HIP_TRY(c, hipGetLastError());
-    if (c->pf_audit.rows && m >= c->pf_audit.min_rows) TRY(launch_stage_audit(c, FHEAES_STAGE_PFPKS, c->pf_audit, a, c->big1, grid.z));
+    if (c->audit[FHEAES_STAGE_PFPKS].wants(m)) TRY(launch_keyswitch_audit(c, FHEAES_STAGE_PFPKS, a, c->big1, grid.z));
     return FHEAES_OK;
 }
 
@@ -310,33 +351,21 @@ uint64_t aes_context_window(fheaes_ctx *c, uint64_t n, uint64_t steps)
     return aes_window_plan(n, steps, c->cu_count, c->k1, pair).window;
 }
 
-// The audit of one blind-rotation launch (kern_audit.h), behind it on the same stream and inside its StageScope: the time counts into the
-// stage, `launches` and `units` count the product launch alone.  `prod`: the product launch's arguments -- its input, output, row count and
-// the three constants are the audit's; whatever form it took, the sampled rows go through the latency form, which parks nothing.
-// Nothing is allocated here (fheaes_audit_set did) and the host waits for nothing: a mismatch is learnt from fheaes_audit_read.
-static_assert(FHEAES_AUDIT_MAX_ROWS == AUDIT_MAX_ROWS && FHEAES_AUDIT_RECORDS == AUDIT_RECORDS, "include/fheaes.h and kern_audit.h disagree");
+// The audit of one blind-rotation launch.  `prod`: the product launch's arguments -- its input, output, row count and the three constants
+// are the audit's; whatever form it took, the sampled rows are gathered and go through the latency form, which parks nothing.
 static_assert(AUDIT_MAX_ROWS <= LATENCY_BATCH_BITS, "the audit's rows are one latency-form launch");
-int launch_audit(fheaes_ctx *c, const ExtProdArgs &prod)
+int launch_blind_rotate_audit(fheaes_ctx *c, const ExtProdArgs &prod)
 {
-    const uint64_t m = prod.count, launch = c->audit_launch++;
-    const uint32_t S = (uint32_t)std::min<uint64_t>(c->audit_rows, m);
-    if (c->audit_hook) {
-        c->audit_hook = false;                       // one shot; a row beyond this launch's is dropped without a write
-        if (c->audit_hook_row < m)
-            hipLaunchKernelGGL(audit_tamper_kernel, dim3(1), dim3(1), 0, c->stream, prod.out, c->big1, c->audit_hook_row, c->audit_hook_word, c->audit_hook_mask);
-    }
-    uint64_t *const in = (uint64_t *)c->audit_in.p, *const out = (uint64_t *)c->audit_out.p;
-    hipLaunchKernelGGL(audit_gather_kernel, dim3(S), dim3(AUDIT_THREADS), 0, c->stream, prod.lwe_in, c->n + 1, c->audit_seed, launch, m, S, in);
+    const AuditLaunch L = audit_begin(c, c->audit[FHEAES_STAGE_BLIND_ROTATE], prod.count, prod.out, c->big1, c->big1);
+    uint64_t *const in = (uint64_t *)L.au.in.p;
+    hipLaunchKernelGGL(audit_gather_kernel, dim3(L.S), dim3(AUDIT_THREADS), 0, c->stream, prod.lwe_in, c->n + 1, L.au.seed, L.launch, L.m, L.S, in);
     ExtProdArgs a{};
     a.ggsw = prod.ggsw; a.tw = prod.tw; a.iters = prod.iters;
     a.tv_const = prod.tv_const; a.body_shift = prod.body_shift; a.post_add = prod.post_add;
-    a.lwe_in = in; a.out = out; a.count = S;
+    a.lwe_in = in; a.out = (uint64_t *)L.au.out.p; a.count = L.S;
     void (*const latency)(ExtProdArgs) = c->k1 == 5 ? blind_rotate_latency_kernel<5, 5, 8> : blind_rotate_latency_kernel<2, 5, 8>;
-    hipLaunchKernelGGL(latency, dim3(S), dim3(BL_THREADS), 0, c->stream, a);
-    hipLaunchKernelGGL(audit_compare_kernel, dim3(S), dim3(AUDIT_THREADS), 0, c->stream, prod.out, out, c->big1, c->audit_seed, launch, m, S,
-                       (uint64_t *)c->audit_state.p);
-    HIP_TRY(c, hipGetLastError());
-    return FHEAES_OK;
+    hipLaunchKernelGGL(latency, dim3(L.S), dim3(BL_THREADS), 0, c->stream, a);
+    return audit_compare(c, L);
 }
 
 int launch_cbs_pbs(fheaes_ctx *c, const uint64_t *lwe_small, uint64_t m, uint32_t level, uint64_t *out)
@@ -387,7 +416,7 @@ int launch_cbs_pbs(fheaes_ctx *c, const uint64_t *lwe_small, uint64_t m, uint32_
 #endif
     hipLaunchKernelGGL(L.kernel, dim3(L.grid), dim3(L.threads), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
-    if (c->audit_rows && m >= c->audit_min_bits) TRY(launch_audit(c, a));
+    if (c->audit[FHEAES_STAGE_BLIND_ROTATE].wants(m)) TRY(launch_blind_rotate_audit(c, a));
     return FHEAES_OK;
 }
 

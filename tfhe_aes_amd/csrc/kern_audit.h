@@ -2,14 +2,17 @@
 // stage and the two results are compared on the device, bit for bit.  The engine is deterministic and every form of a stage writes the same
 // words, so a difference is a defect of the engine or of the machine and never noise.
 //
+// What every stage's audit runs (audit_begin, audit_compare in engine_launch.h), around the stage's own second form:
+//   audit_tamper_kernel    the test hook (fheaes_audit_stage_debug): one thread XORs a mask into one word of the product launch's output;
+//   (the second form)      the S sampled rows -> audit_out;
+//   audit_compare_kernel   workgroup s compares audit_out[s] with row audit_row(s) of the product launch's output, row_words words at
+//                          out + row out_stride, counts a wrong row and keeps a record of the first AUDIT_RECORDS of them.
+//
 // The blind rotation (K2): the sampled rows go through the latency form (kern_blindrot_latency.h: no parking, no slot pool, no owner words,
-// no generation plan; tests/test_gpu_k2_shapes.py).  Three small kernels around the context's own latency-form launch:
+// no generation plan; tests/test_gpu_k2_shapes.py), which takes its inputs as one array:
 //   audit_gather_kernel    workgroup s copies the small LWE of its sampled row (n + 1 words) into audit_in[s];
-//   (the latency form)     audit_in -> audit_out, count = S;
-//   audit_compare_kernel   workgroup s compares audit_out[s] with row audit_row(s) of the product launch's output (kN + 1 words), counts a
-//                          wrong row and keeps a record of the first AUDIT_RECORDS of them;
-//   audit_tamper_kernel    the test hook (fheaes_audit_debug): one thread XORs a mask into one word of the product launch's output.
-// 2 x 16 KB per row: nothing here is near any roof.
+//   (the latency form)     audit_in -> audit_out, count = S.
+// A row is the kN + 1 words of a ciphertext, out_stride = row_words; 2 x 16 KB per row: nothing here is near any roof.
 //
 // The key switches (K1, K3): both are an exact integer matrix product mod 2^64, so any order of evaluation gives the same words.  The
 // product kernels (kern_keyswitch.h) slice it onto the int8 matrix cores: digit planes in A-fragment order, 15 byte products recombined with
@@ -18,9 +21,8 @@
 //                           digits recomputed from the input words (decompose_all), the key words recombined from the only copy on the
 //                           device, the balanced byte planes in B-fragment order (KEY = sum_j kb_j 2^(8j)), one 64-bit multiply-add per
 //                           term.  No matrix cores, no digit planes, no LDS-DMA.  row(s) = audit_row(s) behind a launch, s itself under
-//                           fheaes_audit_plain_batch;
-//   audit_compare_rows_kernel  audit_compare_kernel for a row of row_words words at out + row out_stride.
-// What both forms share, and the audit therefore cannot see: the resident key bytes, decompose_all, keybytes_kernel (the oracle tests cover
+//                           fheaes_audit_plain_batch.
+// A row is n + 1 words for K1 and the (k+1)N words of each key block of the launch for K3.  What both forms share, and the audit therefore cannot see: the resident key bytes, decompose_all, keybytes_kernel (the oracle tests cover
 // the last two).
 #pragma once
 #include <stdint.h>
@@ -66,20 +68,21 @@ __global__ __launch_bounds__(AUDIT_THREADS) void audit_gather_kernel(const uint6
     for (uint32_t j = threadIdx.x; j < n1; j += AUDIT_THREADS) dst[j] = src[j];
 }
 
-// grid S, AUDIT_THREADS threads: out[row(s)] against audit_out[s] over big1 = kN + 1 words.  Rows are 8-byte aligned only (big1 is odd):
-// 8-byte loads, consecutive lanes on consecutive words.  The first differing word is a minimum in LDS; a wrong row takes a ticket from
-// the wrong-row counter and, while the ticket is below AUDIT_RECORDS, writes its record.
-__global__ __launch_bounds__(AUDIT_THREADS) void audit_compare_kernel(const uint64_t *out, const uint64_t *audit_out, uint32_t big1, uint64_t seed, uint64_t launch,
-                                                                      uint64_t m, uint32_t S, uint64_t *state)
+// grid S, AUDIT_THREADS threads: the row_words words at out + row(s) out_stride against those at audit_out + s row_words (K2: the kN + 1 words
+// of a ciphertext, out_stride = row_words; K1: n + 1 words; K3: the k + 1 key blocks, or the one of a single-block launch).  Rows are
+// 8-byte aligned only (kN + 1 is odd): 8-byte loads, consecutive lanes on consecutive words.  The first differing word is a minimum in
+// LDS; a wrong row takes a ticket from the wrong-row counter and, while the ticket is below AUDIT_RECORDS, writes its record.
+__global__ __launch_bounds__(AUDIT_THREADS) void audit_compare_kernel(const uint64_t *out, uint64_t out_stride, const uint64_t *audit_out, uint32_t row_words,
+                                                                      uint64_t seed, uint64_t launch, uint64_t m, uint32_t S, uint64_t *state)
 {
     __shared__ unsigned first;
     const uint32_t s = blockIdx.x;
     const uint64_t row = audit_row(seed, launch, m, S, s);
-    const uint64_t *got = out + row * big1, *want = audit_out + (uint64_t)s * big1;
+    const uint64_t *got = out + row * out_stride, *want = audit_out + (uint64_t)s * row_words;
     if (threadIdx.x == 0) first = 0xFFFFFFFFu;
     __syncthreads();
     unsigned mine = 0xFFFFFFFFu;
-    for (uint32_t j = threadIdx.x; j < big1; j += AUDIT_THREADS)
+    for (uint32_t j = threadIdx.x; j < row_words; j += AUDIT_THREADS)
         if (got[j] != want[j] && j < mine) mine = j;
     if (mine != 0xFFFFFFFFu) atomicMin(&first, mine);
     __syncthreads();
@@ -207,33 +210,4 @@ __global__ __launch_bounds__(KSP_THREADS) void keyswitch_plain_kernel(const Keys
         if (A.body_index >= 0 && col == A.body_col) o += A.in[row * A.in_stride + (uint32_t)A.body_index];
         A.out[(s0 + r) * A.out_stride + (uint64_t)z * A.out_z_stride + col] = o;
     }
-}
-
-// audit_compare_kernel for the key switches: row(s) of the product launch is row_words words at out + row out_stride (K1: n + 1 words; K3:
-// the k + 1 key blocks, or the one of a single-block launch), the audit's row s the same words at audit_out + s row_words
-__global__ __launch_bounds__(AUDIT_THREADS) void audit_compare_rows_kernel(const uint64_t *out, uint64_t out_stride, const uint64_t *audit_out, uint32_t row_words,
-                                                                           uint64_t seed, uint64_t launch, uint64_t m, uint32_t S, uint64_t *state)
-{
-    __shared__ unsigned first;
-    const uint32_t s = blockIdx.x;
-    const uint64_t row = audit_row(seed, launch, m, S, s);
-    const uint64_t *got = out + row * out_stride, *want = audit_out + (uint64_t)s * row_words;
-    if (threadIdx.x == 0) first = 0xFFFFFFFFu;
-    __syncthreads();
-    unsigned mine = 0xFFFFFFFFu;
-    for (uint32_t j = threadIdx.x; j < row_words; j += AUDIT_THREADS)
-        if (got[j] != want[j] && j < mine) mine = j;
-    if (mine != 0xFFFFFFFFu) atomicMin(&first, mine);
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    if (s == 0) {
-        atomicAdd((unsigned long long *)&state[AUDIT_ST_LAUNCHES], 1ull);
-        atomicAdd((unsigned long long *)&state[AUDIT_ST_CHECKED], (unsigned long long)S);
-    }
-    const unsigned w = first;
-    if (w == 0xFFFFFFFFu) return;
-    const unsigned long long ticket = atomicAdd((unsigned long long *)&state[AUDIT_ST_WRONG], 1ull);
-    if (ticket >= AUDIT_RECORDS) return;
-    uint64_t *rec = state + AUDIT_ST_RECORDS + ticket * AUDIT_RECORD_WORDS;
-    rec[0] = launch; rec[1] = row; rec[2] = w; rec[3] = got[w]; rec[4] = want[w];
 }
